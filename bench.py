@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Mray/s and ms/frame of the path-trace hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path at the reference's launch granularity (LaunchCurrentFrame,
 PathTracerMain.cpp:184-210): 128 samples per pixel over the whole 1920x1080 image, frame index
@@ -19,7 +19,13 @@ tiles (sutil/WorkDistribution.h) of the same steps, then ONE RCCL reduce of the 
 accumulation buffer to rank 0 + make_color there, all inside the timed region.  Per-GPU work
 shrinks with N -> "scaling": "strong".
 
-One JSON line on rank 0.
+One JSON line on rank 0; `ms_per_step` is the wall time of the timed region over --steps.
+
+--dump-outputs DIR writes what the timed path leaves its caller after the last timed step: the float4
+accumulation buffer and the RGBA8 framebuffer, as DIR/accumulation.npy and DIR/framebuffer.npy in
+float32 (a seeded pixel sample of both where they exceed 64 MB; see dump_outputs).  The inputs depend on
+the arguments alone (committed or seeded scenes, frame-indexed sample seeds), so two builds run with the
+same arguments can be compared output for output.
 
 `roofline` prices the megakernel against the resource that can bind it.  The kernel is BVH pointer
 chasing + fp32 shading: no matrix work, so MFMA never applies.  HBM applies only when the scene
@@ -89,12 +95,16 @@ def parse():
     ap.add_argument("--chunks", type=int, default=0, help="sample runs per pixel (pt_set_sample_chunks); 0 = automatic")
     ap.add_argument("--save", default="", help="write the final framebuffer as PPM (rank 0)")
     ap.add_argument("--save-accum", default="", help="write the final float4 accumulation buffer as .npy (rank 0)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy, float32, at most 64 MB in all (rank 0)")
     a = ap.parse_args()
     preset = PRESETS[a.config]
     if a.scene is None:
         a.scene = preset[0]
     if a.steps is None:
         a.steps = preset[1]
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.max_depth is None:
         a.max_depth = preset[2]
     if a.width is None:
@@ -164,6 +174,28 @@ def cpu_baseline(pt, obj, params, cpu_spp):
     return {"value": rays / secs / 1e6, "unit": "Mray/s", "cores": cores, "kind": "port",
             "sample": "%s %dx%d maxDepth %d DL %d IS %d, %d spp x 1 frame (%.1f s, %d rays)" %
                       (os.path.basename(obj.path), q.width, q.height, q.maxDepth, int(q.useDirectLighting), int(q.useImportanceSampling), cpu_spp, secs, rays)}, rays / max(1, q.width * q.height * cpu_spp)
+
+
+DUMP_BYTES = 64 * 1000 * 1000       # --dump-outputs: all .npy files together, headers included
+DUMP_SEED = 20260101
+
+
+def dump_outputs(d, outputs):
+    """--dump-outputs: outputs maps a name to an (H, W, C) array of the same H x W.  Each is written as d/<name>.npy in float32
+    (exact for the uint8 framebuffer).  When the whole arrays would exceed DUMP_BYTES, every array keeps the same fixed, seeded
+    sample of pixels instead, as (n, C) in row-major pixel order, and d/pixel_index.npy (float64, exact) names them (y * W + x)."""
+    os.makedirs(d, exist_ok=True)
+    arrs = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in outputs.items()}
+    h, w = next(iter(arrs.values())).shape[:2]
+    n = h * w
+    per_pixel = sum(4 * (a.size // n) for a in arrs.values())
+    room = DUMP_BYTES - 1024 * (len(arrs) + 1)          # .npy headers
+    if n * per_pixel > room:
+        keep = np.sort(np.random.default_rng(DUMP_SEED).choice(n, room // (per_pixel + 8), replace=False))
+        arrs = {k: a.reshape(n, -1)[keep] for k, a in arrs.items()}
+        arrs["pixel_index"] = keep.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def primary_miss_fraction(p, info):
@@ -387,6 +419,8 @@ def main():
     elapsed = time.perf_counter() - t0
     cdev = dev if (world > 1 and not rehearse) else None
     elapsed = D.max_over_ranks(elapsed, cdev)
+    # what a caller of the timed path holds after its last step, taken before the untimed leg below borrows the buffers
+    outputs = {"accumulation": accum.cpu().numpy(), "framebuffer": fb.cpu().numpy()} if a.dump_outputs and rank == 0 else None
     tot_rays, tot_shadow, tot_paths, tot_culled = D.sum_over_ranks([rays, shadow, paths, culled], cdev)
     if a.variant >= 0:
         assert int(last_stats.variant) == a.variant, "the kernel variant that ran is not the one requested"
@@ -451,6 +485,8 @@ def main():
         if world == 1 and not a.no_cpu_baseline:
             base, _ = cpu_baseline(pt, obj, p, a.cpu_spp)
             out["cpu_baseline"] = base
+        if outputs:
+            dump_outputs(a.dump_outputs, outputs)
         if a.save_accum:
             np.save(a.save_accum, accum.cpu().numpy())
         if a.save:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/reference_vectors.npz from the REFERENCE'S OWN code.
+"""Generate tests/golden/reference_vectors.npz (and, with --fresh, fresh_reference_digests.json) from the REFERENCE'S OWN code.
 
 Runs only where /root/reference exists: it loads oracle/_ref/libref.so, which oracle/Makefile
 builds from the reference's host-compilable sources where they lie (cuda/random.h, cuda/helpers.h,
@@ -8,7 +8,7 @@ PathTracer_Optix/TinyObjWrapper.cpp + util/tiny_obj_loader.h, and the OptiX-free
 PathTracer_Optix/pathTracerPrograms.cu that oracle/extract_ptprog_math.py lifts verbatim into oracle/_ref at build time).  The outputs are DATA (inputs and
 expected outputs); no reference source text is stored.  Deterministic: fixed numpy seeds.
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [--fresh]
 """
 import os
 import sys
@@ -175,5 +175,21 @@ def main():
     print("wrote", os.path.join(HERE, "reference_vectors.npz"), "with", len(out), "arrays")
 
 
+def fresh():
+    """tests/golden/fresh_reference_digests.json: the digests of the reference's answers on the second, larger input set of
+    tests/test_oracle_golden.py::test_against_live_reference_build (its fresh_inputs, numpy seed 7), and of those inputs."""
+    if not ref_lib.available():
+        raise SystemExit("oracle/_ref/libref.so missing: run `make -C oracle` where /root/reference exists")
+    import json
+    import test_oracle_golden as T
+    X = T.fresh_inputs()
+    answers = T.fresh_answers(ref_lib.Ref(), X)
+    doc = {"seed": T.FRESH_SEED, "inputs": T.inputs_digest(X), "answers": {k: T.digest(a, nan_equal) for k, (a, nan_equal) in answers.items()}}
+    path = os.path.join(HERE, "fresh_reference_digests.json")
+    with open(path, "w") as fh:
+        json.dump(doc, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("wrote", path, "with", len(doc["answers"]), "answers")
+
 if __name__ == "__main__":
-    main()
+    fresh() if sys.argv[1:] == ["--fresh"] else main()

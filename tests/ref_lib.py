@@ -1,8 +1,8 @@
 """ctypes loader of oracle/_ref/libref.so: the REFERENCE'S OWN host-compilable sources
 (cuda/random.h, cuda/helpers.h, sutil/vec_math.h, sutil/Camera.cpp, sutil/Trackball.cpp,
 sutil/WorkDistribution.h, PathTracer_Optix/TinyObjWrapper.cpp) built by oracle/Makefile.
-Exists only where /root/reference exists; tests that need it skip otherwise and rely on the
-committed fixtures in tests/golden/ instead."""
+Exists only where /root/reference exists; tests use it where it exists and rely on the
+committed fixtures in tests/golden/ everywhere."""
 import ctypes as C
 import os
 
