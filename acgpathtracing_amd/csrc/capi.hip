@@ -26,6 +26,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 
 #include "../../include/acgpt.h"
 #include "../../include/acgpt_test.h"
+#include "denoise.h"
 #include "lbvh_build.h"
 #include "pt_device.h"
 #include "render_megakernel.h"
@@ -75,6 +76,7 @@ struct pt_ctx {
     int pixel_classes = 1;                                           // 0: off (pt_debug_pixel_classes)
     int queue_order = 1;                      // tile-strip rows dealt round robin over the queue shards (render_common.h queue_slot; pt_debug_queue_order)
     pt_multi* multi = nullptr;                // pt_create_multi: this context is rank 0 of a group (below)
+    float4* d_denoise[2] = {nullptr, nullptr}; size_t denoise_pixels = 0;   // pt_denoise's ping-pong {colour, variance} buffers
     pt_stats stats;
     uint64_t scene_serial = 0;
     std::string err;
@@ -299,6 +301,7 @@ static void destroy_one(pt_ctx* c)
     if (c->d_wave_scratch) (void)hipFree(c->d_wave_scratch);
     if (c->d_stack_ovf) (void)hipFree(c->d_stack_ovf);
     if (c->d_row_spans) (void)hipFree(c->d_row_spans);
+    for (float4* b : c->d_denoise) if (b) (void)hipFree(b);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1158,6 +1161,65 @@ PT_API int pt_trace_any(pt_ctx* c, const float* rays, size_t n, uint8_t* hit_out
     return trace_common(c, rays, n, n, hit_out, 0, nullptr, [&](float* d_rays, void* a, void*) {
         return ptd::launch_trace_any(sc, se, d_rays, (uint32_t)n, (uint8_t*)a, s);
     });
+}
+
+// ---- denoised preview (pt_render_features, pt_denoise; kernels in denoise.hip) -------------------------------------------------
+static bool overlaps(const void* a, const void* b, size_t bytes)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bytes && y < x + bytes;
+}
+
+static int check_image(pt_ctx* c, const pt_params* p, const char* what)
+{
+    if (p->width == 0 || p->height == 0) return fail(c, std::string(what) + ": width and height must be >= 1");
+    if (p->width > 65535u || p->height > 65535u || (uint64_t)p->width * p->height > (1ull << 28))
+        return fail(c, std::string(what) + ": image too large (65535 per side, 2^28 pixels)");
+    return 0;
+}
+
+PT_API int pt_render_features(pt_ctx* c, const pt_params* p, float* albedo_prim, float* normal_depth)
+{
+    if (!c) return fail(nullptr, "pt_render_features: null context");
+    if (!p || !albedo_prim || !normal_depth) return fail(c, "pt_render_features: null argument");
+    if (int rc = check_image(c, p, "pt_render_features")) return rc;
+    if (overlaps(albedo_prim, normal_depth, (size_t)p->width * p->height * sizeof(float4))) return fail(c, "pt_render_features: the two output buffers overlap");
+    if (c->scene_serial == 0) return fail(c, "pt_render_features: no scene (pt_set_scene first)");
+    CK(c, hipSetDevice(c->device));
+    // the node array the scene holds: fp16 centre / half-extent nodes for the default variants, fp32 nodes for the fp32 ones; only a
+    // variant forced onto another format (pt_set_tuning) leaves neither, and gets the fp32 nodes back as a ray query would
+    int fmt = 0;
+    if (c->bvh.hcnodes) fmt = 11;
+    else if (int rc = ensure_node_format(c, 0)) return rc;
+    Range range("pt_render_features");
+    CK(c, ptd::launch_features(fmt, device_scene(c), c->stack_entries, p->width, p->height, p->cameraEye, p->cameraU, p->cameraV, p->cameraW,
+                               (float4*)albedo_prim, (float4*)normal_depth, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_denoise(pt_ctx* c, const pt_params* p, const float* albedo_prim, const float* normal_depth, float* out_rgba, uint32_t iterations)
+{
+    if (!c) return fail(nullptr, "pt_denoise: null context");
+    if (!p || !p->accumulationBuffer || !albedo_prim || !normal_depth || !out_rgba) return fail(c, "pt_denoise: null argument");
+    if (iterations < 1u || iterations > ptd::kDnMaxIterations) return fail(c, "pt_denoise: iterations must be in [1, 8]");
+    if (int rc = check_image(c, p, "pt_denoise")) return rc;
+    const size_t n = (size_t)p->width * p->height, bytes = n * sizeof(float4);
+    if (overlaps(out_rgba, p->accumulationBuffer, bytes) || overlaps(out_rgba, albedo_prim, bytes) || overlaps(out_rgba, normal_depth, bytes))
+        return fail(c, "pt_denoise: out_rgba overlaps an input (writing into the accumulation buffer would corrupt the progressive state)");
+    CK(c, hipSetDevice(c->device));
+    if (n > c->denoise_pixels) {
+        CK(c, hipStreamSynchronize(c->stream));
+        for (float4*& b : c->d_denoise) if (b) { (void)hipFree(b); b = nullptr; }
+        c->denoise_pixels = 0;
+        for (float4*& b : c->d_denoise) CK(c, hipMalloc((void**)&b, bytes));
+        c->denoise_pixels = n;
+    }
+    Range range("pt_denoise");
+    CK(c, ptd::launch_denoise((const float4*)p->accumulationBuffer, (const float4*)albedo_prim, (const float4*)normal_depth, p->width, p->height, iterations,
+                              c->d_denoise[0], c->d_denoise[1], (float4*)out_rgba, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 PT_API int pt_bench_traversal(pt_ctx* c, const float* rays, size_t n, int repeats, int node_format, float* t_out, uint32_t* prim_out, float* ms_out,

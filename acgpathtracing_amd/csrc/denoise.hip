@@ -1,0 +1,244 @@
+// denoise.hip — the kernels behind pt_render_features and pt_denoise (include/acgpt.h).
+//
+//   k_dn_features   one camera ray per pixel through the pixel centre: first-hit albedo + triangle index, unit normal + distance
+//   k_dn_variance   demodulation and the 5x5 luminance variance (geometry weights only) -> scratch {c, var}
+//   k_dn_atrous     one a-trous iteration (step 1, 2, 4, ...), ping-pong over the scratch; the last one remodulates into the output
+//
+// The filter reads 25 taps of {c, var} and {normal, depth} per pixel and iteration, 32 bytes each, plus the .w of 9 neighbours for
+// the variance blur: bound by the L1 / L2, not by arithmetic.  No atomics anywhere: two calls give the same bits.
+#include "denoise.h"
+
+namespace ptd {
+
+extern __shared__ uint32_t dn_lds[];
+
+// ---- features ---------------------------------------------------------------------------------------------------------------
+// Closest hit on the fp16 centre / half-extent nodes (NODE_FMT 11): the box test of the default render kernels, one ray per lane, the
+// LDS lane stack of traverse().  Boxes only prune; the triangle test, the interval (tmin, tmax) and the tie rule (equal t -> lowest
+// triangle index) are those of traverse<false>, so the hit triangle and t equal pt_trace_closest's bit for bit.
+__device__ __forceinline__ void traverse_hc(const DeviceScene& sc, const LaneStack& st, bool active, const f3& o, const f3& d, float tmin, float tmax,
+                                            HitRec& hit)
+{
+    hit.t = tmax; hit.slot = -1; hit.prim = 0xFFFFFFFFu;
+    f3 mul, add;
+    setup_ray_hc(o, d, sc.hspace, mul, add);
+    int sp = 0;
+    int node = (active && sc.n_tris != 0u) ? 0 : kSentinel;
+    while (node != kSentinel) {
+        if (node >= 0) {
+            // child references of inner nodes are byte offsets into hcnodes; a leaf is ~slot
+            const uint4* np = (const uint4*)((const char*)sc.hcnodes + (size_t)(uint32_t)node);
+            const uint4 qa = np[0], qb = np[1];
+            float n0, f0, n1, f1;
+            slab_hc(qa.x, qa.y, qa.z, mul, add, tmin, n0, f0);
+            slab_hc(qb.x, qb.y, qb.z, mul, add, tmin, n1, f1);
+            f0 = fminf(f0, hit.t * kTieWiden);
+            f1 = fminf(f1, hit.t * kTieWiden);
+            const bool h0 = n0 <= f0, h1 = n1 <= f1;
+            if (h0 && h1) {
+                const bool first0 = n0 <= n1;
+                st.push(sp, first0 ? (int)qb.w : (int)qa.w);
+                sp++;
+                node = first0 ? (int)qa.w : (int)qb.w;
+            } else if (h0) {
+                node = (int)qa.w;
+            } else if (h1) {
+                node = (int)qb.w;
+            } else {
+                if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
+            }
+        } else {
+            const int slot = ~node;
+            const TriRecord* tp = sc.tris + slot;
+            const float4 r0 = tp->r0, r1 = tp->r1, r2 = tp->r2;
+            float t;
+            const bool ok = tri_test(o, d, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x), tmin, tmax, t);
+            const uint32_t prim = __float_as_uint(r2.y);
+            if (ok && (t < hit.t || (t == hit.t && prim < hit.prim))) { hit.t = t; hit.slot = slot; hit.prim = prim; }
+            if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
+        }
+    }
+}
+
+template <int FMT>
+__global__ void __launch_bounds__(256)
+k_dn_features(const DeviceScene sc, uint32_t stack_entries, uint32_t w, uint32_t h, pt_float3 eye, pt_float3 U, pt_float3 V, pt_float3 W,
+              float4* __restrict__ albedo_prim, float4* __restrict__ normal_depth)
+{
+    const uint32_t n = w * h;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    LaneStack st;
+    st.base = dn_lds + (threadIdx.x >> 6) * (stack_entries * 64u) + (threadIdx.x & 63u);
+    const bool active = i < n;
+    const uint32_t x = active ? i % w : 0u, y = active ? i / w : 0u;
+    // pathTracerPrograms.cu:730-740 with the jitter at 0.5; this file is built with -ffp-contract=off: no contraction
+    const float dx = 2.0f * (((float)x + 0.5f) / (float)w) - 1.0f;
+    const float dy = 2.0f * (((float)y + 0.5f) / (float)h) - 1.0f;
+    const f3 dir = normalize(dx * mk(U) + dy * mk(V) + mk(W));
+    const f3 org = mk(eye);
+    HitRec hit;
+    if (FMT == 11) traverse_hc(sc, st, active, org, dir, 0.01f, 1e16f, hit);
+    else traverse<false>(sc, st, active, org, dir, 0.01f, 1e16f, hit);
+    if (!active) return;
+    if (hit.slot >= 0) {
+        const float4 sr = sc.shade[hit.slot];          // normalize(cross(e1, e2)) and the material id (pt_device.h)
+        f3 nrm = mk(sr.x, sr.y, sr.z);
+        if (dot(nrm, dir) > 0.0f) nrm = -nrm;          // towards the camera
+        const float4 kd = sc.mats[__float_as_uint(sr.w) & kShadeMatMask].kd_ior;
+        albedo_prim[i] = make_float4(kd.x, kd.y, kd.z, __uint_as_float(hit.prim));
+        normal_depth[i] = make_float4(nrm.x, nrm.y, nrm.z, hit.t);
+    } else {
+        albedo_prim[i] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
+        normal_depth[i] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    }
+}
+
+// ---- filter -----------------------------------------------------------------------------------------------------------------
+// Every expression below is mirrored operation for operation by tests/denoise_ref.py (fp32, same order, taps dy-major).
+__device__ __forceinline__ bool dn_hit(const float4& nd) { return nd.w >= 0.0f; }
+__device__ __forceinline__ float dn_lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
+__device__ __forceinline__ float4 dn_albedo(const float4& alb, bool hit)
+{
+    return hit ? make_float4(fmaxf(alb.x, kDnAlbedoFloor), fmaxf(alb.y, kDnAlbedoFloor), fmaxf(alb.z, kDnAlbedoFloor), 0.0f) : make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+}
+// w_n and the depth term of the exponent for a tap q of p (zden = sigma_z * step * t_p); false when exactly one of them misses
+__device__ __forceinline__ bool dn_geometry(const float4& ndp, const float4& ndq, bool hp, float zden, float& wn, float& ez)
+{
+    const bool hq = dn_hit(ndq);
+    if (hp != hq) return false;
+    wn = 1.0f; ez = 0.0f;
+    if (hp) {
+        ez = fabsf(ndp.w - ndq.w) / zden;
+        float c = fmaxf(ndp.x * ndq.x + ndp.y * ndq.y + ndp.z * ndq.z, 0.0f);
+#pragma unroll
+        for (int k = 0; k < kDnNormalSquarings; k++) c = c * c;
+        wn = c;
+    }
+    return true;
+}
+
+__constant__ float kDnH[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+__constant__ float kDnG[3] = {0.25f, 0.5f, 0.25f};
+
+// demodulation + variance (step 1, 5x5, geometry weights), about l_p: M1, M2 = weighted means of (l_q - l_p) and its square
+__global__ void __launch_bounds__(256)
+k_dn_variance(const float4* __restrict__ accum, const float4* __restrict__ albedo, const float4* __restrict__ nd, uint32_t w, uint32_t h,
+              float4* __restrict__ cv)
+{
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= w || y >= h) return;
+    const uint32_t p = y * w + x;
+    const float4 ndp = nd[p];
+    const bool hp = dn_hit(ndp);
+    const float4 ap = dn_albedo(albedo[p], hp), cp4 = accum[p];
+    const float cr = cp4.x / ap.x, cg = cp4.y / ap.y, cb = cp4.z / ap.z;
+    const float lp = dn_lum(cr, cg, cb);
+    const float zden = kDnSigmaZ * 1.0f * ndp.w;
+    float sw = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    for (int dy = -2; dy <= 2; dy++) {
+        const int yq = (int)y + dy;
+        if (yq < 0 || yq >= (int)h) continue;
+        for (int dx = -2; dx <= 2; dx++) {
+            const int xq = (int)x + dx;
+            if (xq < 0 || xq >= (int)w) continue;
+            const uint32_t q = (uint32_t)yq * w + (uint32_t)xq;
+            const float4 ndq = nd[q];
+            float wn, ez;
+            if (!dn_geometry(ndp, ndq, hp, zden, wn, ez)) continue;
+            const float4 aq = dn_albedo(albedo[q], hp), c4 = accum[q];
+            const float dl = dn_lum(c4.x / aq.x, c4.y / aq.y, c4.z / aq.z) - lp;
+            const float wq = wn * expf(-ez);
+            sw += wq; s1 += wq * dl; s2 += wq * (dl * dl);
+        }
+    }
+    const float m1 = s1 / sw, m2 = s2 / sw;        // sw > 0: the centre tap has weight ~1
+    cv[p] = make_float4(cr, cg, cb, fmaxf(m2 - m1 * m1, 0.0f));
+}
+
+// one iteration at `step`; LAST: remodulate with max(albedo_p, 0.01) and write {rgb, 1}, else {c', var'}
+template <bool LAST>
+__global__ void __launch_bounds__(256)
+k_dn_atrous(const float4* __restrict__ cv, const float4* __restrict__ nd, const float4* __restrict__ albedo, uint32_t w, uint32_t h, int step,
+            float4* __restrict__ out)
+{
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= w || y >= h) return;
+    const uint32_t p = y * w + x;
+    const float4 ndp = nd[p], cvp = cv[p];
+    const bool hp = dn_hit(ndp);
+    // g(var)_p: 3x3 {1/4, 1/2, 1/4}^2 at distance 1, renormalised at the borders
+    float gs = 0.0f, gw = 0.0f;
+    for (int dy = -1; dy <= 1; dy++) {
+        const int yq = (int)y + dy;
+        if (yq < 0 || yq >= (int)h) continue;
+        for (int dx = -1; dx <= 1; dx++) {
+            const int xq = (int)x + dx;
+            if (xq < 0 || xq >= (int)w) continue;
+            const float k = kDnG[dx + 1] * kDnG[dy + 1];
+            gs += k * cv[(uint32_t)yq * w + (uint32_t)xq].w;
+            gw += k;
+        }
+    }
+    const float lden = kDnSigmaL * sqrtf(gs / gw) + 1e-6f;
+    const float lp = dn_lum(cvp.x, cvp.y, cvp.z);
+    const float zden = kDnSigmaZ * (float)step * ndp.w;
+    float sk = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
+    for (int dy = -2; dy <= 2; dy++) {
+        const int yq = (int)y + dy * step;
+        if (yq < 0 || yq >= (int)h) continue;
+        for (int dx = -2; dx <= 2; dx++) {
+            const int xq = (int)x + dx * step;
+            if (xq < 0 || xq >= (int)w) continue;
+            const uint32_t q = (uint32_t)yq * w + (uint32_t)xq;
+            const float4 ndq = nd[q];
+            float wn, ez;
+            if (!dn_geometry(ndp, ndq, hp, zden, wn, ez)) continue;
+            const float4 c = cv[q];
+            const float el = fabsf(lp - dn_lum(c.x, c.y, c.z)) / lden;
+            const float k = kDnH[dx + 2] * kDnH[dy + 2] * wn * expf(-(ez + el));
+            sk += k;
+            sr += k * c.x; sg += k * c.y; sb += k * c.z;
+            sv += (k * k) * c.w;
+        }
+    }
+    const float r = sr / sk, g = sg / sk, b = sb / sk;      // sk > 0: the centre tap's k is 9/64 * n_p.n_p^128
+    if (LAST) {
+        const float4 ap = dn_albedo(albedo[p], hp);
+        out[p] = make_float4(r * ap.x, g * ap.y, b * ap.z, 1.0f);
+    } else {
+        out[p] = make_float4(r, g, b, sv / (sk * sk));
+    }
+}
+
+hipError_t launch_features(int fmt, const DeviceScene& sc, uint32_t stack_entries, uint32_t w, uint32_t h, pt_float3 eye, pt_float3 U, pt_float3 V,
+                           pt_float3 W, float4* albedo_prim, float4* normal_depth, hipStream_t stream)
+{
+    const uint32_t n = w * h;
+    const size_t lds = (size_t)(256 / 64) * stack_entries * 64u * sizeof(uint32_t);
+    const void* fn = fmt == 11 ? (const void*)k_dn_features<11> : (const void*)k_dn_features<0>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    if (fmt == 11) k_dn_features<11><<<(n + 255) / 256, 256, lds, stream>>>(sc, stack_entries, w, h, eye, U, V, W, albedo_prim, normal_depth);
+    else k_dn_features<0><<<(n + 255) / 256, 256, lds, stream>>>(sc, stack_entries, w, h, eye, U, V, W, albedo_prim, normal_depth);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise(const float4* accum, const float4* albedo_prim, const float4* normal_depth, uint32_t w, uint32_t h, uint32_t iterations,
+                          float4* scratch0, float4* scratch1, float4* out, hipStream_t stream)
+{
+    const dim3 block(32, 8), grid((w + 31u) / 32u, (h + 7u) / 8u);
+    k_dn_variance<<<grid, block, 0, stream>>>(accum, albedo_prim, normal_depth, w, h, scratch0);
+    hipError_t e = hipGetLastError();
+    float4* src = scratch0;
+    float4* dst = scratch1;
+    for (uint32_t i = 0; i < iterations && e == hipSuccess; i++) {
+        const int step = 1 << i;
+        if (i + 1 == iterations) k_dn_atrous<true><<<grid, block, 0, stream>>>(src, normal_depth, albedo_prim, w, h, step, out);
+        else k_dn_atrous<false><<<grid, block, 0, stream>>>(src, normal_depth, albedo_prim, w, h, step, dst);
+        e = hipGetLastError();
+        float4* t = src; src = dst; dst = t;
+    }
+    return e;
+}
+
+}  // namespace ptd

@@ -10,6 +10,11 @@
 //              [--keys "0,1,UP,UP,R"] [--out frame.png] [--dump-every k] [--zero-copy]
 //              [--orbit dx,dy] [--zoom n] [--sample-chunks c] [--build-mode 0|1]
 //              [--gpus N] [--multi] [--save-accum file] [--restore-accum file] [--light-mode 0|1] [--math fast|ieee]
+//              [--denoise N]
+//
+// --denoise N (1..8; default 0 = off): after the last frame, also write <out-stem>_denoised<ext>, the accumulation through N
+// iterations of the edge-avoiding a-trous filter guided by first-hit features (pt_render_features + pt_denoise), coloured by
+// pt_resolve_framebuffer.  The frames and --out are the same with or without it.
 //
 // --math: arithmetic of the shading code (pt_set_math_mode).  fast (default) is what the reference's own build computes with —
 // nvcc --use_fast_math, /root/reference/CMakeLists.txt:267 —, ieee the correctly rounded level of the CPU oracle.
@@ -200,6 +205,32 @@ static void createProgramGroups(PathTracerState&) {}
 static void createPipeline(PathTracerState&) {}
 static void createShaderBindingTable(PathTracerState&, const TinyObjWrapper&) {}
 
+// the denoised preview of the current accumulation, written as an image next to the frame (--denoise)
+static void saveDenoised(PathTracerState& state, const std::string& path, uint32_t iterations)
+{
+    const size_t n = (size_t)state.params.width * state.params.height;
+    void* bufs[4] = {nullptr, nullptr, nullptr, nullptr};      // albedo_prim, normal_depth, denoised float4, colours uchar4
+    std::string err;
+    for (int i = 0; i < 4 && err.empty(); i++)
+        if (pt_device_malloc(state.context, &bufs[i], n * (i < 3 ? 16 : 4)) != 0) err = pt_last_error(state.context);
+    std::vector<uint8_t> host(n * 4);
+    if (err.empty() && (pt_render_features(state.context, &state.params, (float*)bufs[0], (float*)bufs[1]) != 0 ||
+                        pt_denoise(state.context, &state.params, (const float*)bufs[0], (const float*)bufs[1], (float*)bufs[2], iterations) != 0 ||
+                        pt_resolve_framebuffer(state.context, (const float*)bufs[2], (uint8_t*)bufs[3], n) != 0 ||
+                        pt_copy_to_host(state.context, host.data(), bufs[3], n * 4) != 0))
+        err = pt_last_error(state.context);
+    for (void* b : bufs) if (b) pt_device_free(state.context, b);
+    if (!err.empty()) throw Exception("denoise: " + err);
+    if (!saveImage(path, host.data(), (int)state.params.width, (int)state.params.height)) std::cerr << "could not write " << path << std::endl;
+}
+
+static std::string denoisedName(const std::string& out)
+{
+    const size_t slash = out.find_last_of('/'), dot = out.find_last_of('.');
+    if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return out + "_denoised";
+    return out.substr(0, dot) + "_denoised" + out.substr(dot);
+}
+
 static void CleanAllTheThings(PathTracerState& state)                    // :629-646
 {
     if (state.params.accumulationBuffer) pt_device_free(state.context, state.params.accumulationBuffer);
@@ -210,7 +241,7 @@ static void CleanAllTheThings(PathTracerState& state)                    // :629
 int main(int argc, char** argv)
 {
     std::string objfilepath, out = "frame.png", keys, save_accum, restore_accum;
-    int32_t width = 512, height = 512, frames = 8, dump_every = 0;
+    int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false;
     int orbit_dx = 0, orbit_dy = 0, zoom_steps = 0, sample_chunks = 0, build_mode = 1, fuse = 1, light_mode = 0, math_mode = PT_MATH_FAST;
     PathTracerState state;
@@ -243,10 +274,12 @@ int main(int argc, char** argv)
         else if (a == "--build-mode") build_mode = atoi(next());
         else if (a == "--fuse-frames") fuse = std::min(64, std::max(1, atoi(next())));
         else if (a == "--math") { const std::string m = next(); math_mode = (m == "ieee" || m == "0") ? PT_MATH_IEEE : PT_MATH_FAST; }   // fast: the arithmetic of the reference's own build (nvcc --use_fast_math); ieee: the CPU oracle's
+        else if (a == "--denoise") denoise_iters = atoi(next());
         else if (a == "--light-mode") light_mode = atoi(next());      // 0 = the reference's hard-coded rectangle (:154-158), 1 = the OBJ's emissive triangles + MIS
         else { std::cerr << "unknown option " << a << std::endl; return 2; }
     }
     if (objfilepath.empty()) { std::cerr << "usage: acgpt_main --obj scene.obj [options]" << std::endl; return 2; }
+    if (denoise_iters < 0 || denoise_iters > 8) { std::cerr << "--denoise takes 0 (off) to 8 iterations" << std::endl; return 2; }
     std::vector<std::string> key_list;
     { std::stringstream ss(keys); std::string k; while (std::getline(ss, k, ',')) if (!k.empty()) key_list.push_back(k); }
 
@@ -329,6 +362,7 @@ int main(int argc, char** argv)
             if (!saveImage(out, reinterpret_cast<const uint8_t*>(output_buffer.getHostPointer()), width, height))
                 std::cerr << "could not write " << out << std::endl;
             if (!save_accum.empty()) saveAccumulation(state, save_accum);
+            if (denoise_iters > 0) saveDenoised(state, denoisedName(out), (uint32_t)denoise_iters);
         }
         CleanAllTheThings(state);
         if (frame_counter > 0) avg_ms /= frame_counter;

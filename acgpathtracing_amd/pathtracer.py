@@ -371,6 +371,59 @@ def readAccumulation(state):
     return out
 
 
+def _device_buffers(state, count, nbytes):
+    L = _native.hip()
+    out = []
+    try:
+        for _ in range(count):
+            p = C.c_void_p()
+            _check(state.context, L.pt_device_malloc(state.context, C.byref(p), nbytes), "device alloc")
+            out.append(p.value)
+    except Exception:
+        _free_device_buffers(state, out)
+        raise
+    return out
+
+
+def _free_device_buffers(state, ptrs):
+    for p in ptrs:
+        _native.hip().pt_device_free(state.context, p)
+
+
+def _read_image(state, ptr):
+    h, w = int(state.params.height), int(state.params.width)
+    out = np.zeros((h, w, 4), np.float32)
+    _check(state.context, _native.hip().pt_copy_to_host(state.context, out.ctypes.data, ptr, out.nbytes), "copy to host")
+    return out
+
+
+def renderFeatures(state):
+    """First-hit feature buffers of the current camera (include/acgpt.h pt_render_features), float32 [height, width, 4] each (row 0 =
+    bottom): albedo_prim = diffuse colour + triangle index as uint32 bits (0xFFFFFFFF on a miss), normal_depth = camera-facing unit
+    normal + hit distance (-1 on a miss)."""
+    nbytes = int(state.params.width) * int(state.params.height) * 16
+    bufs = _device_buffers(state, 2, nbytes)
+    try:
+        _check(state.context, _native.hip().pt_render_features(state.context, C.byref(state.params), bufs[0], bufs[1]), "pt_render_features")
+        return _read_image(state, bufs[0]), _read_image(state, bufs[1])
+    finally:
+        _free_device_buffers(state, bufs)
+
+
+def denoise(state, iterations=5):
+    """The accumulation buffer through the edge-avoiding a-trous filter (include/acgpt.h pt_denoise), guided by the features of the
+    current camera: float32 [height, width, 4] linear radiance, alpha 1.  The accumulation itself is left as it is."""
+    nbytes = int(state.params.width) * int(state.params.height) * 16
+    bufs = _device_buffers(state, 3, nbytes)
+    try:
+        L = _native.hip()
+        _check(state.context, L.pt_render_features(state.context, C.byref(state.params), bufs[0], bufs[1]), "pt_render_features")
+        _check(state.context, L.pt_denoise(state.context, C.byref(state.params), bufs[0], bufs[1], bufs[2], int(iterations)), "pt_denoise")
+        return _read_image(state, bufs[2])
+    finally:
+        _free_device_buffers(state, bufs)
+
+
 def saveAccumulation(state, filename):
     """The progressive state of the reference — params.accumulationBuffer and currentFrameIdx
     (pathTracerPrograms.cu:803-811) — as a file; same format as acgpt_main --save-accum."""

@@ -278,6 +278,46 @@ int pt_get_stats(pt_ctx* ctx, pt_stats* out);
  * 651-684).                                                                    */
 int pt_trace_closest(pt_ctx* ctx, const float* rays, size_t n, float* t_out, uint32_t* prim_out);
 int pt_trace_any(pt_ctx* ctx, const float* rays, size_t n, uint8_t* hit_out);
+
+/* ---- denoised preview (opt-in; nothing above changes) -------------------------------------------------------------------------
+ * Both calls enqueue on the context's stream and return synchronised, cover the whole image (pt_set_partition does not apply), act
+ * on rank 0 of a pt_create_multi context, and never write the accumulation buffer, the frame buffer or pt_stats.  A caller of the
+ * reference's loop calls them after LaunchCurrentFrame and before display.
+ *
+ * pt_render_features: one camera ray per pixel through the pixel centre, the camera of pathTracerPrograms.cu:730-740 with the jitter at
+ * 0.5 and IEEE fp32 whatever pt_set_math_mode says: d = 2 * ((x + 0.5) / w, (y + 0.5) / h) - 1, dir = normalize(d.x U + d.y V + W) as
+ * 1 / sqrtf(dot) left to right, origin cameraEye, interval (0.01, 1e16), row 0 at the bottom.  Reads width, height and the camera of
+ * params, nothing else.  DEVICE outputs, float4[w*h] each:
+ *   albedo_prim   .xyz the first hit's pt_material.diffuse (any bsdfType), .w the hit triangle's index in the caller's index-buffer order
+ *                 as uint32 bits; a miss: (0, 0, 0, 0xFFFFFFFF bits)
+ *   normal_depth  .xyz the unit geometric normal normalize(cross(e1, e2)), negated if it faces away from the ray; .w the hit distance t;
+ *                 a miss: (0, 0, 0, -1)
+ * Hit triangle and t equal pt_trace_closest's on the same rays bit for bit.  The rays walk the node array the scene holds
+ * (pt_bvh_info.device_bytes does not change), except under a variant forced onto another format by pt_set_tuning, which brings the
+ * fp32 nodes back as a ray query does.  Fails without a scene.
+ *
+ * pt_denoise: edge-avoiding a-trous filter (Dammertz et al. 2010) with the variance-driven luminance edge-stop of SVGF (Schied et al.
+ * 2017), no temporal part.  Reads params->accumulationBuffer (linear radiance, float4[w*h]), width, height and the two feature buffers;
+ * writes linear float4 {r, g, b, 1} to out_rgba (device; pt_resolve_framebuffer makes colours of it).  iterations in [1, 8]; 5 reaches
+ * 2 * (1 + 2 + 4 + 8 + 16) = 62 pixels.  out_rgba must not overlap an input.  All arithmetic fp32 in the order written here
+ * (tests/denoise_ref.py is the NumPy statement of the same thing):
+ *   hit_p    normal_depth_p.w >= 0
+ *   a_p      max(albedo_p, 0.01) per channel on a hit, 1 on a miss;  c_p = rgb_p / a_p;  l(c) = 0.2126 c.r + 0.7152 c.g + 0.0722 c.b
+ *   geometry between p and a tap q at step s: no weight (the tap is skipped) if exactly one of them misses; if both miss w_n = 1 and
+ *            z = 0; if both hit z = |t_p - t_q| / (sigma_z * s * t_p) and w_n = max(0, n_p . n_q)^sigma_n (seven squarings)
+ *   variance pre-pass (s = 1, 5x5 taps inside the image): w = w_n * exp(-z); M1, M2 = sum w (l_q - l_p), sum w (l_q - l_p)^2 over sum w;
+ *            var_p = max(0, M2 - M1^2) — the variance of l about l_p, i.e. the M2 - M1^2 of l without its cancellation
+ *   iteration i = 0 .. iterations-1, s = 2^i, taps q = p + s (dx, dy), dx, dy in -2..2 (dy outer), taps outside the image skipped:
+ *            g_p = 3x3 {1/4, 1/2, 1/4}^2 blur of var at distance 1, renormalised at the borders
+ *            k = h[dx] h[dy] * w_n * exp(-(z + |l_p - l_q| / (sigma_l * sqrt(g_p) + 1e-6))),  h = {1/16, 1/4, 3/8, 1/4, 1/16}
+ *            (w_z * w_l in one exponential); c' = sum k c_q / sum k;  var' = sum k^2 var_q / (sum k)^2
+ *   output   c' * a_p after the last iteration, alpha 1
+ *   sigma_z = 0.01, sigma_n = 128, sigma_l = 5: the best of a sweep (sigma_z 0.002 ... 1, sigma_l 1 ... 16) on the CPU oracle's Cornell
+ *   box at 128 x 128, 8 samples per pixel against 8192 (tests/test_denoise_host.py): the MSE falls 7.0-fold.
+ * The context keeps two float4[w*h] scratch buffers ({c, var}, ping-pong), grown on demand and freed by pt_destroy.  No atomics: two
+ * calls give the same bits, and so do the two math modes.                                                                        */
+int pt_render_features(pt_ctx* ctx, const pt_params* params, float* albedo_prim, float* normal_depth);
+int pt_denoise(pt_ctx* ctx, const pt_params* params, const float* albedo_prim, const float* normal_depth, float* out_rgba, uint32_t iterations);
 /* ---- device memory helpers for bindings that have no HIP runtime of their own
  * (the reference app calls cudaMalloc/cudaMemcpy directly, :145-148).         */
 int pt_device_malloc(pt_ctx* ctx, void** out, size_t bytes);
