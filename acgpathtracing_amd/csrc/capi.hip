@@ -31,6 +31,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "pt_device.h"
 #include "render_megakernel.h"
 #include "selftest.h"
+#include "temporal.h"
 
 #define PT_API extern "C" __attribute__((visibility("default")))
 
@@ -77,6 +78,7 @@ struct pt_ctx {
     int queue_order = 1;                      // tile-strip rows dealt round robin over the queue shards (render_common.h queue_slot; pt_debug_queue_order)
     pt_multi* multi = nullptr;                // pt_create_multi: this context is rank 0 of a group (below)
     float4* d_denoise[2] = {nullptr, nullptr}; size_t denoise_pixels = 0;   // pt_denoise's ping-pong {colour, variance} buffers
+    uint8_t* d_tri_bsdf = nullptr;            // bsdfType per triangle (caller's order): pt_temporal_blend's, built on its first call per scene
     pt_stats stats;
     uint64_t scene_serial = 0;
     std::string err;
@@ -273,6 +275,7 @@ static void free_scene(pt_ctx* c)
     c->n_mats = 0;
     if (c->d_lights) { (void)hipFree(c->d_lights); c->d_lights = nullptr; }
     c->n_lights = 0; c->light_area = 0.0f;
+    if (c->d_tri_bsdf) { (void)hipFree(c->d_tri_bsdf); c->d_tri_bsdf = nullptr; }
 }
 
 PT_API void pt_destroy(pt_ctx* c)
@@ -487,7 +490,7 @@ PT_API int pt_get_bvh_info(pt_ctx* c, pt_bvh_info* out)
     out->half_node_bytes = c->bvh.n_nodes * (uint32_t)sizeof(ptd::HNode);
     out->half_area_ratio = c->bvh.half_area_ratio;
     out->half_box_inflation = c->bvh.half_box_inflation;
-    out->device_bytes = (uint64_t)ptd::scene_device_bytes(c->bvh);
+    out->device_bytes = (uint64_t)ptd::scene_device_bytes(c->bvh) + (c->d_tri_bsdf ? (uint64_t)c->bvh.n_tris : 0u);
     return 0;
 }
 
@@ -1218,6 +1221,61 @@ PT_API int pt_denoise(pt_ctx* c, const pt_params* p, const float* albedo_prim, c
     Range range("pt_denoise");
     CK(c, ptd::launch_denoise((const float4*)p->accumulationBuffer, (const float4*)albedo_prim, (const float4*)normal_depth, p->width, p->height, iterations,
                               c->d_denoise[0], c->d_denoise[1], (float4*)out_rgba, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- temporal reprojection (pt_temporal_blend; kernels in temporal.hip) --------------------------------------------------------
+static bool spans_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
+// the per-triangle bsdfType array: on the first call after pt_set_scene, counted in device_bytes from then on, freed with the scene
+static int ensure_tri_bsdf(pt_ctx* c)
+{
+    if (c->d_tri_bsdf || c->bvh.n_tris == 0) return 0;
+    uint8_t* b = nullptr;
+    CK(c, hipMalloc((void**)&b, c->bvh.n_tris));
+    hipError_t e = ptd::launch_tri_bsdf(device_scene(c), b, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { (void)hipFree(b); return fail(c, std::string("pt_temporal_blend: per-triangle materials: ") + hipGetErrorString(e)); }
+    c->d_tri_bsdf = b;
+    return 0;
+}
+
+PT_API int pt_temporal_blend(pt_ctx* c, const pt_params* p, uint32_t accum_samples, const float* albedo_prim, const float* normal_depth,
+                             const pt_params* prev, const float* prev_history, const float* prev_albedo_prim, const float* prev_normal_depth,
+                             float history_cap, float* out_history)
+{
+    if (!c) return fail(nullptr, "pt_temporal_blend: null context");
+    if (!p || !p->accumulationBuffer || !albedo_prim || !normal_depth || !out_history) return fail(c, "pt_temporal_blend: null argument");
+    const int n_prev = (prev != nullptr) + (prev_history != nullptr) + (prev_albedo_prim != nullptr) + (prev_normal_depth != nullptr);
+    if (n_prev != 0 && n_prev != 4) return fail(c, "pt_temporal_blend: prev, prev_history, prev_albedo_prim and prev_normal_depth are all given or all NULL");
+    if (accum_samples == 0u) return fail(c, "pt_temporal_blend: accum_samples must be >= 1");
+    if (!(history_cap >= 0.0f) || !std::isfinite(history_cap)) return fail(c, "pt_temporal_blend: history_cap must be finite and >= 0");
+    if (int rc = check_image(c, p, "pt_temporal_blend")) return rc;
+    if (prev) if (int rc = check_image(c, prev, "pt_temporal_blend (previous view)")) return rc;
+    const size_t bytes = (size_t)p->width * p->height * sizeof(float4);
+    const size_t prev_bytes = prev ? (size_t)prev->width * prev->height * sizeof(float4) : 0;
+    const void* inputs[6] = {p->accumulationBuffer, albedo_prim, normal_depth, prev_history, prev_albedo_prim, prev_normal_depth};
+    for (int i = 0; i < 6; i++)
+        if (inputs[i] && spans_overlap(out_history, bytes, inputs[i], i < 3 ? bytes : prev_bytes))
+            return fail(c, "pt_temporal_blend: out_history overlaps an input (chained calls ping-pong two history buffers)");
+    if (c->scene_serial == 0) return fail(c, "pt_temporal_blend: no scene (pt_set_scene first)");
+    CK(c, hipSetDevice(c->device));
+    if (int rc = ensure_tri_bsdf(c)) return rc;
+    ptd::TpPrev tp = {};
+    if (prev) {
+        tp.eye = prev->cameraEye; tp.U = prev->cameraU; tp.V = prev->cameraV; tp.W = prev->cameraW;
+        tp.w = prev->width; tp.h = prev->height;
+        tp.hist = (const float4*)prev_history; tp.albedo_prim = (const float4*)prev_albedo_prim; tp.normal_depth = (const float4*)prev_normal_depth;
+    }
+    Range range("pt_temporal_blend");
+    CK(c, ptd::launch_temporal((const float4*)p->accumulationBuffer, (const float4*)albedo_prim, (const float4*)normal_depth, p->width, p->height,
+                               p->cameraEye, p->cameraU, p->cameraV, p->cameraW, (float)accum_samples, tp, c->d_tri_bsdf, c->bvh.n_tris,
+                               history_cap, (float4*)out_history, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -1,0 +1,103 @@
+// temporal.hip — the kernels behind pt_temporal_blend (include/acgpt.h).
+//
+//   k_tp_tri_bsdf   once per scene, on first use: bsdfType per triangle in the caller's index order (a scatter over the leaf slots)
+//   k_tp_blend      one thread per pixel of the current view: reproject its first hit into the previous camera, take the bilinear
+//                   footprint's consistent taps of the previous history, blend them with the accumulation by sample count
+//
+// k_tp_blend reads 48 B of the current view and up to four taps x 48 B of the previous one per pixel and writes 16 B: a gather
+// bound by the caches and HBM, not by arithmetic.  No atomics, no transcendental: two calls give the same bits.
+#include "temporal.h"
+
+namespace ptd {
+
+__global__ void __launch_bounds__(256)
+k_tp_tri_bsdf(const TriRecord* __restrict__ tris, const float4* __restrict__ shade, uint32_t n, uint8_t* __restrict__ bsdf)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t prim = __float_as_uint(tris[i].r2.y);
+    if (prim < n) bsdf[prim] = (uint8_t)((__float_as_uint(shade[i].w) >> kShadeBsdfShift) & 3u);
+}
+
+// Every expression below is mirrored operation for operation by tests/temporal_ref.py (fp32, same order, taps ty-major).  This file
+// is built with -ffp-contract=off: no contraction.
+__global__ void __launch_bounds__(256)
+k_tp_blend(const float4* __restrict__ accum, const float4* __restrict__ albedo_prim, const float4* __restrict__ normal_depth, uint32_t w,
+           uint32_t h, pt_float3 eye, pt_float3 U, pt_float3 V, pt_float3 W, float N, const TpPrev prev, const uint8_t* __restrict__ bsdf,
+           uint32_t n_tris, float cap, float4* __restrict__ out)
+{
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= w || y >= h) return;
+    const uint32_t p = y * w + x;
+    const float4 c = accum[p], ndp = normal_depth[p];
+    const uint32_t prim = __float_as_uint(albedo_prim[p].w);
+    float4 o = make_float4(c.x, c.y, c.z, N);                          // the pass-through
+    if (prev.hist && ndp.w >= 0.0f && prim < n_tris && bsdf[prim] == (uint8_t)PT_BSDF_DIFFUSE) {
+        // the ray of k_dn_features (denoise.hip): same expression, same order, so the same bits
+        const float dx = 2.0f * (((float)x + 0.5f) / (float)w) - 1.0f;
+        const float dy = 2.0f * (((float)y + 0.5f) / (float)h) - 1.0f;
+        const f3 dir = normalize(dx * mk(U) + dy * mk(V) + mk(W));
+        const f3 v = (mk(eye) + ndp.w * dir) - mk(prev.eye);
+        const f3 Up = mk(prev.U), Vp = mk(prev.V), Wp = mk(prev.W);
+        const float s = dot(v, Wp) / dot(Wp, Wp);
+        if (s > 0.0f) {
+            const float du = dot(v, Up) / (s * dot(Up, Up));
+            const float dv = dot(v, Vp) / (s * dot(Vp, Vp));
+            const float fx = (du + 1.0f) * 0.5f * (float)prev.w - 0.5f;
+            const float fy = (dv + 1.0f) * 0.5f * (float)prev.h - 0.5f;
+            // a footprint with a tap inside the previous image has fx in [-1, w'), fy in [-1, h'); NaN fails here too
+            if (fx >= -1.0f && fx < (float)prev.w && fy >= -1.0f && fy < (float)prev.h) {
+                const float x0f = floorf(fx), y0f = floorf(fy);
+                const float ax = fx - x0f, ay = fy - y0f;
+                const int x0 = (int)x0f, y0 = (int)y0f;
+                float a = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hn = 0.0f;
+#pragma unroll
+                for (int ty = 0; ty < 2; ty++) {
+                    const int yq = y0 + ty;
+                    if (yq < 0 || yq >= (int)prev.h) continue;
+                    const float wy = ty ? ay : 1.0f - ay;
+#pragma unroll
+                    for (int tx = 0; tx < 2; tx++) {
+                        const int xq = x0 + tx;
+                        if (xq < 0 || xq >= (int)prev.w) continue;
+                        const uint32_t q = (uint32_t)yq * prev.w + (uint32_t)xq;
+                        if (__float_as_uint(prev.albedo_prim[q].w) != prim) continue;          // another triangle (or a miss)
+                        const float4 nq = prev.normal_depth[q];
+                        if (!(nq.x * ndp.x + nq.y * ndp.y + nq.z * ndp.z > 0.0f)) continue;    // the other side of the plane
+                        const float wq = (tx ? ax : 1.0f - ax) * wy;
+                        const float4 hq = prev.hist[q];
+                        a += wq;
+                        hr += wq * hq.x; hg += wq * hq.y; hb += wq * hq.z;
+                        hn += wq * hq.w;
+                    }
+                }
+                const float n = hn < cap ? hn : cap;
+                if (a > 0.0f && n > 0.0f) {
+                    const float den = n + N;
+                    o = make_float4((n * (hr / a) + N * c.x) / den, (n * (hg / a) + N * c.y) / den, (n * (hb / a) + N * c.z) / den, den);
+                }
+            }
+        }
+    }
+    out[p] = o;
+}
+
+hipError_t launch_tri_bsdf(const DeviceScene& sc, uint8_t* bsdf, hipStream_t stream)
+{
+    if (sc.n_tris == 0u) return hipSuccess;
+    hipError_t e = hipMemsetAsync(bsdf, 0xFF, sc.n_tris, stream);      // a triangle no slot names stays "not diffuse"
+    if (e != hipSuccess) return e;
+    k_tp_tri_bsdf<<<(sc.n_tris + 255u) / 256u, 256, 0, stream>>>(sc.tris, sc.shade, sc.n_tris, bsdf);
+    return hipGetLastError();
+}
+
+hipError_t launch_temporal(const float4* accum, const float4* albedo_prim, const float4* normal_depth, uint32_t w, uint32_t h, pt_float3 eye,
+                           pt_float3 U, pt_float3 V, pt_float3 W, float n_samples, const TpPrev& prev, const uint8_t* bsdf, uint32_t n_tris,
+                           float cap, float4* out, hipStream_t stream)
+{
+    const dim3 block(32, 8), grid((w + 31u) / 32u, (h + 7u) / 8u);
+    k_tp_blend<<<grid, block, 0, stream>>>(accum, albedo_prim, normal_depth, w, h, eye, U, V, W, n_samples, prev, bsdf, n_tris, cap, out);
+    return hipGetLastError();
+}
+
+}  // namespace ptd

@@ -10,11 +10,19 @@
 //              [--keys "0,1,UP,UP,R"] [--out frame.png] [--dump-every k] [--zero-copy]
 //              [--orbit dx,dy] [--zoom n] [--sample-chunks c] [--build-mode 0|1]
 //              [--gpus N] [--multi] [--save-accum file] [--restore-accum file] [--light-mode 0|1] [--math fast|ieee]
-//              [--denoise N]
+//              [--denoise N] [--history-out file] [--history-in file]
 //
 // --denoise N (1..8; default 0 = off): after the last frame, also write <out-stem>_denoised<ext>, the accumulation through N
 // iterations of the edge-avoiding a-trous filter guided by first-hit features (pt_render_features + pt_denoise), coloured by
 // pt_resolve_framebuffer.  The frames and --out are the same with or without it.
+//
+// --history-out / --history-in carry the accumulated image across a camera move (pt_temporal_blend).  --history-out writes, after the
+// last frame, the history of this run's view: the blended one with --history-in, else the accumulation as {rgb, currentFrameIdx * spp}.
+// --history-in reads one written by an earlier run of the same scene and settings (size and camera may differ: --orbit, --zoom) and
+// refuses any other with a message and exit status 1.  After the last frame it traces the stored view's features, blends its history
+// into this view and writes <out-stem>_temporal<ext>; with --denoise N also <out-stem>_temporal_denoised<ext>, the blend through the
+// filter.  File: "ACGPTHST" | width | height | maxDepth | direct lighting | importance sampling | light mode | math mode | triangles
+// (uint32 each) | eye, U, V, W (12 floats) | float4[width * height] {linear rgb, samples}.
 //
 // --math: arithmetic of the shading code (pt_set_math_mode).  fast (default) is what the reference's own build computes with —
 // nvcc --use_fast_math, /root/reference/CMakeLists.txt:267 —, ieee the correctly rounded level of the CPU oracle.
@@ -224,11 +232,117 @@ static void saveDenoised(PathTracerState& state, const std::string& path, uint32
     if (!saveImage(path, host.data(), (int)state.params.width, (int)state.params.height)) std::cerr << "could not write " << path << std::endl;
 }
 
-static std::string denoisedName(const std::string& out)
+static std::string suffixedName(const std::string& out, const std::string& suffix)
 {
     const size_t slash = out.find_last_of('/'), dot = out.find_last_of('.');
-    if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return out + "_denoised";
-    return out.substr(0, dot) + "_denoised" + out.substr(dot);
+    if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return out + suffix;
+    return out.substr(0, dot) + suffix + out.substr(dot);
+}
+static std::string denoisedName(const std::string& out) { return suffixedName(out, "_denoised"); }
+
+// ---- temporal history (--history-out, --history-in) -----------------------------------------------------------------------
+struct HistoryFile {
+    uint32_t hdr[8] = {};            // width, height, maxDepth, direct lighting, importance sampling, light mode, math mode, triangles
+    float camera[12] = {};           // eye, U, V, W
+    std::vector<float> data;         // float4[width * height] {linear rgb, samples}
+};
+static const char kHistoryMagic[8] = {'A', 'C', 'G', 'P', 'T', 'H', 'S', 'T'};
+
+// what a history of this run's view records about it
+static HistoryFile historyOfRun(PathTracerState& state, int light_mode, int math_mode)
+{
+    pt_bvh_info bi;
+    PT_CHECK(state.context, pt_get_bvh_info(state.context, &bi));
+    const pt_params& p = state.params;
+    HistoryFile h;
+    const uint32_t hdr[8] = {p.width, p.height, p.maxDepth, (uint32_t)p.useDirectLighting, (uint32_t)p.useImportanceSampling, (uint32_t)light_mode,
+                             (uint32_t)math_mode, bi.n_tris};
+    memcpy(h.hdr, hdr, sizeof(hdr));
+    const pt_float3 cam[4] = {p.cameraEye, p.cameraU, p.cameraV, p.cameraW};
+    for (int i = 0; i < 4; i++) { h.camera[3 * i] = cam[i].x; h.camera[3 * i + 1] = cam[i].y; h.camera[3 * i + 2] = cam[i].z; }
+    return h;
+}
+
+static void writeHistory(const std::string& path, const HistoryFile& h)
+{
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) throw Exception("cannot write " + path);
+    const bool ok = fwrite(kHistoryMagic, 1, 8, f) == 8 && fwrite(h.hdr, 4, 8, f) == 8 && fwrite(h.camera, 4, 12, f) == 12 &&
+                    fwrite(h.data.data(), sizeof(float), h.data.size(), f) == h.data.size();
+    fclose(f);
+    if (!ok) throw Exception("short write to " + path);
+}
+
+static HistoryFile readHistory(const std::string& path)
+{
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) throw Exception("cannot read " + path);
+    HistoryFile h;
+    char magic[8];
+    bool ok = fread(magic, 1, 8, f) == 8 && memcmp(magic, kHistoryMagic, 8) == 0 && fread(h.hdr, 4, 8, f) == 8 && fread(h.camera, 4, 12, f) == 12 &&
+              h.hdr[0] >= 1 && h.hdr[0] <= 65535 && h.hdr[1] >= 1 && h.hdr[1] <= 65535;
+    if (ok) {
+        h.data.resize((size_t)h.hdr[0] * h.hdr[1] * 4);
+        ok = fread(h.data.data(), sizeof(float), h.data.size(), f) == h.data.size() && fgetc(f) == EOF;
+    }
+    fclose(f);
+    if (!ok) throw Exception(path + ": not a history file (acgpt_main --history-out)");
+    return h;
+}
+
+// "" if the history file was made under this run's scene and settings, else what differs
+static std::string historyMismatch(const HistoryFile& file, const HistoryFile& run)
+{
+    static const char* names[8] = {"width", "height", "maxDepth", "direct lighting", "importance sampling", "light mode", "math mode", "triangles"};
+    for (int i = 2; i < 8; i++)        // the size may differ: it is the previous view's
+        if (file.hdr[i] != run.hdr[i])
+            return std::string(names[i]) + " is " + std::to_string(file.hdr[i]) + " in the history, " + std::to_string(run.hdr[i]) + " in this run";
+    return "";
+}
+
+// blends the history of the view in `file` into this run's view (pt_temporal_blend), writes <out>_temporal (and _temporal_denoised);
+// the blended history comes back in `blended`
+static void blendHistory(PathTracerState& state, const HistoryFile& file, const std::string& out, uint32_t denoise_iters, std::vector<float>& blended)
+{
+    const pt_params& p = state.params;
+    const size_t n = (size_t)p.width * p.height, n_prev = (size_t)file.hdr[0] * file.hdr[1];
+    pt_params prev = p;
+    prev.width = file.hdr[0]; prev.height = file.hdr[1];
+    pt_float3* cam[4] = {&prev.cameraEye, &prev.cameraU, &prev.cameraV, &prev.cameraW};
+    for (int i = 0; i < 4; i++) *cam[i] = {file.camera[3 * i], file.camera[3 * i + 1], file.camera[3 * i + 2]};
+    // prev history, prev albedo_prim, prev normal_depth, albedo_prim, normal_depth, blended history, denoised (float4), colours (uchar4)
+    const size_t sizes[8] = {n_prev * 16, n_prev * 16, n_prev * 16, n * 16, n * 16, n * 16, n * 16, n * 4};
+    void* b[8] = {};
+    std::string err;
+    for (int i = 0; i < 8 && err.empty(); i++)
+        if (pt_device_malloc(state.context, &b[i], sizes[i]) != 0) err = pt_last_error(state.context);
+    std::vector<uint8_t> host(n * 4), host_dn(n * 4);
+    blended.assign(n * 4, 0.0f);
+    pt_params dn = p;
+    dn.accumulationBuffer = (float*)b[5];                         // pt_denoise reads the blend's .xyz
+    const uint32_t samples = p.currentFrameIdx * p.samplesPerPixel;
+    if (err.empty() && (pt_copy_to_device(state.context, b[0], file.data.data(), sizes[0]) != 0 ||
+                        pt_render_features(state.context, &prev, (float*)b[1], (float*)b[2]) != 0 ||
+                        pt_render_features(state.context, &p, (float*)b[3], (float*)b[4]) != 0 ||
+                        pt_temporal_blend(state.context, &p, samples, (const float*)b[3], (const float*)b[4], &prev, (const float*)b[0],
+                                          (const float*)b[1], (const float*)b[2], PT_TEMPORAL_HISTORY_CAP, (float*)b[5]) != 0 ||
+                        pt_copy_to_host(state.context, blended.data(), b[5], n * 16) != 0 ||
+                        pt_resolve_framebuffer(state.context, (const float*)b[5], (uint8_t*)b[7], n) != 0 ||
+                        pt_copy_to_host(state.context, host.data(), b[7], n * 4) != 0))
+        err = pt_last_error(state.context);
+    if (err.empty() && denoise_iters > 0 &&
+        (pt_denoise(state.context, &dn, (const float*)b[3], (const float*)b[4], (float*)b[6], denoise_iters) != 0 ||
+         pt_resolve_framebuffer(state.context, (const float*)b[6], (uint8_t*)b[7], n) != 0 ||
+         pt_copy_to_host(state.context, host_dn.data(), b[7], n * 4) != 0))
+        err = pt_last_error(state.context);
+    for (void* x : b) if (x) pt_device_free(state.context, x);
+    if (!err.empty()) throw Exception("temporal blend: " + err);
+    const std::string name = suffixedName(out, "_temporal");
+    if (!saveImage(name, host.data(), (int)p.width, (int)p.height)) std::cerr << "could not write " << name << std::endl;
+    if (denoise_iters > 0) {
+        const std::string dname = suffixedName(out, "_temporal_denoised");
+        if (!saveImage(dname, host_dn.data(), (int)p.width, (int)p.height)) std::cerr << "could not write " << dname << std::endl;
+    }
 }
 
 static void CleanAllTheThings(PathTracerState& state)                    // :629-646
@@ -240,7 +354,7 @@ static void CleanAllTheThings(PathTracerState& state)                    // :629
 
 int main(int argc, char** argv)
 {
-    std::string objfilepath, out = "frame.png", keys, save_accum, restore_accum;
+    std::string objfilepath, out = "frame.png", keys, save_accum, restore_accum, history_out, history_in;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false;
     int orbit_dx = 0, orbit_dy = 0, zoom_steps = 0, sample_chunks = 0, build_mode = 1, fuse = 1, light_mode = 0, math_mode = PT_MATH_FAST;
@@ -275,6 +389,8 @@ int main(int argc, char** argv)
         else if (a == "--fuse-frames") fuse = std::min(64, std::max(1, atoi(next())));
         else if (a == "--math") { const std::string m = next(); math_mode = (m == "ieee" || m == "0") ? PT_MATH_IEEE : PT_MATH_FAST; }   // fast: the arithmetic of the reference's own build (nvcc --use_fast_math); ieee: the CPU oracle's
         else if (a == "--denoise") denoise_iters = atoi(next());
+        else if (a == "--history-out") history_out = next();
+        else if (a == "--history-in") history_in = next();
         else if (a == "--light-mode") light_mode = atoi(next());      // 0 = the reference's hard-coded rectangle (:154-158), 1 = the OBJ's emissive triangles + MIS
         else { std::cerr << "unknown option " << a << std::endl; return 2; }
     }
@@ -324,6 +440,12 @@ int main(int argc, char** argv)
         std::cout << "Shader Binding Table Created" << std::endl;
         initializeTheLaunch(state);
         std::cout << "Launch Initialized" << std::endl;
+        HistoryFile history;
+        if (!history_in.empty()) {              // refused before any frame is rendered
+            history = readHistory(history_in);
+            const std::string why = historyMismatch(history, historyOfRun(state, light_mode, math_mode));
+            if (!why.empty()) throw Exception(history_in + " was made under other settings: " + why);
+        }
         if (!restore_accum.empty()) {
             restoreAccumulation(state, restore_accum);
             std::cout << "Accumulation restored: " << state.params.currentFrameIdx << " frames" << std::endl;
@@ -363,6 +485,21 @@ int main(int argc, char** argv)
                 std::cerr << "could not write " << out << std::endl;
             if (!save_accum.empty()) saveAccumulation(state, save_accum);
             if (denoise_iters > 0) saveDenoised(state, denoisedName(out), (uint32_t)denoise_iters);
+            if (!history_in.empty() || !history_out.empty()) {
+                HistoryFile mine = historyOfRun(state, light_mode, math_mode);      // the settings at the end: --keys may have changed them
+                if (!history_in.empty()) {
+                    const std::string why = historyMismatch(history, mine);
+                    if (!why.empty()) throw Exception(history_in + " was made under other settings: " + why);
+                    blendHistory(state, history, out, (uint32_t)denoise_iters, mine.data);
+                } else {
+                    const size_t n = (size_t)width * height * 4;
+                    mine.data.resize(n);
+                    PT_CHECK(state.context, pt_copy_to_host(state.context, mine.data.data(), state.params.accumulationBuffer, n * sizeof(float)));
+                    const float samples = (float)(state.params.currentFrameIdx * state.params.samplesPerPixel);
+                    for (size_t i = 3; i < n; i += 4) mine.data[i] = samples;
+                }
+                if (!history_out.empty()) writeHistory(history_out, mine);
+            }
         }
         CleanAllTheThings(state);
         if (frame_counter > 0) avg_ms /= frame_counter;

@@ -236,6 +236,7 @@ class PathTracerState:
         self.sample_summ = 0
         self.total_ms = 0.0
         self._accum_bytes = 0
+        self._temporal = []           # TemporalHistory objects holding device buffers of this context (freed by CleanAllTheThings)
 
 
 def createDeviceContext(state, device_id=0, device_ids=None):
@@ -338,6 +339,7 @@ def setLightMode(state, mode):
     """0: the reference's estimator (hard-coded rectangle, PathTracerMain.cpp:154-158; the default).  1: the scene's own
     emissive triangles as the area light, light and BSDF sampling combined by the power heuristic (opt-in)."""
     _check(state.context, _native.hip().pt_set_light_mode(state.context, int(mode)), "pt_set_light_mode")
+    state._light_mode = int(mode)
     state.refreshAccumulationBuffer = True
 
 
@@ -347,6 +349,7 @@ def setMathMode(state, mode):
     correctly rounded division and square root and the C library's sincosf / acosf, the level the CPU oracle is written at."""
     m = {"ieee": _native.MATH_IEEE, "fast": _native.MATH_FAST}.get(mode, mode)
     _check(state.context, _native.hip().pt_set_math_mode(state.context, int(m)), "pt_set_math_mode")
+    state._math_mode = int(m)
     state.refreshAccumulationBuffer = True
 
 
@@ -424,6 +427,124 @@ def denoise(state, iterations=5):
         _free_device_buffers(state, bufs)
 
 
+TEMPORAL_HISTORY_CAP = 256.0      # include/acgpt.h pt_temporal_blend: the default cap, calibrated in tests/test_temporal_host.py
+
+
+class _TemporalView:
+    """One view's device buffers: history {rgb, samples} and the two feature buffers, plus what they were made under."""
+
+    def __init__(self):
+        self.bufs = []              # history, albedo_prim, normal_depth
+        self.pixels = 0
+        self.params = PathTraceParams()
+        self.key = None             # (width, height, camera) of the view
+        self.samples = 0            # N of the accumulation the history was last blended from
+        self.valid = False
+
+
+class TemporalHistory:
+    """The accumulated image carried across camera moves (include/acgpt.h pt_temporal_blend).
+
+    update(state) traces the current view's features and blends the history of the last view the camera left with the accumulation;
+    the result is this view's history, and becomes the source when the camera moves on.  Called again at the same camera, it blends
+    the same source with the newer accumulation (the accumulation already holds the samples the last call blended in).  The history
+    is dropped, silently, when the scene, maxDepth, a toggle, the light mode or the math mode differ from what it was made under, and
+    when the accumulation at an unmoved camera stands for fewer samples than last time (a reset).  Owns its device buffers: close()
+    frees them, and so does CleanAllTheThings for the context."""
+
+    def __init__(self, cap=TEMPORAL_HISTORY_CAP):
+        self.cap = float(cap)
+        self._state = None
+        self._views = [_TemporalView(), _TemporalView()]
+        self._cur = 0               # index of the view last blended into
+        self._settings = None
+
+    def _bind(self, state):
+        if self._state is None:
+            self._state = state
+            state._temporal.append(self)
+        elif self._state is not state:
+            raise PathTracerError("TemporalHistory: bound to another PathTracerState")
+
+    @staticmethod
+    def _settings_of(state):
+        p = state.params
+        return (_native.hip().pt_scene_handle(state.context), int(p.maxDepth), int(p.useDirectLighting), int(p.useImportanceSampling),
+                getattr(state, "_light_mode", 0), getattr(state, "_math_mode", _native.MATH_FAST))
+
+    @staticmethod
+    def _key_of(p):
+        return (int(p.width), int(p.height)) + tuple(v.tuple() for v in (p.cameraEye, p.cameraU, p.cameraV, p.cameraW))
+
+    def _drop(self):
+        for v in self._views:
+            v.valid = False
+
+    def update(self, state, accum_samples=None):
+        """Blend and keep: float32 [height, width, 4] {linear rgb, samples it stands for}.  accum_samples: the samples the
+        accumulation stands for, by default currentFrameIdx * samplesPerPixel."""
+        self._bind(state)
+        L = _native.hip()
+        p = state.params
+        n = int(p.currentFrameIdx) * int(p.samplesPerPixel) if accum_samples is None else int(accum_samples)
+        key, settings = self._key_of(p), self._settings_of(state)
+        cur = self._views[self._cur]
+        if settings != self._settings or (cur.valid and cur.key == key and n < cur.samples):
+            self._drop()
+        self._settings = settings
+        if cur.valid and cur.key != key:                 # the camera moved: the last result is the history from now on
+            self._cur ^= 1
+        cur, prev = self._views[self._cur], self._views[self._cur ^ 1]
+        pixels = int(p.width) * int(p.height)
+        if cur.pixels != pixels:
+            _free_device_buffers(state, cur.bufs)
+            cur.bufs, cur.pixels = [], 0
+            cur.bufs, cur.pixels = _device_buffers(state, 3, pixels * 16), pixels
+        cur.valid = False
+        C.memmove(C.byref(cur.params), C.byref(p), C.sizeof(p))
+        hist, alb, nd = cur.bufs
+        _check(state.context, L.pt_render_features(state.context, C.byref(p), alb, nd), "pt_render_features")
+        if prev.valid:
+            rc = L.pt_temporal_blend(state.context, C.byref(p), n, alb, nd, C.byref(prev.params), prev.bufs[0], prev.bufs[1], prev.bufs[2],
+                                     self.cap, hist)
+        else:
+            rc = L.pt_temporal_blend(state.context, C.byref(p), n, alb, nd, None, None, None, None, self.cap, hist)
+        _check(state.context, rc, "pt_temporal_blend")
+        cur.key, cur.samples, cur.valid = key, n, True
+        return _read_image(state, hist)
+
+    def denoise(self, state, iterations=5):
+        """The last update's history through pt_denoise (guided by the same features): float32 [height, width, 4], alpha 1."""
+        cur = self._views[self._cur]
+        if self._state is not state or not cur.valid:
+            raise PathTracerError("TemporalHistory.denoise: update(state) first")
+        q = PathTraceParams()
+        C.memmove(C.byref(q), C.byref(cur.params), C.sizeof(q))
+        q.accumulationBuffer = cur.bufs[0]              # pt_denoise reads .xyz only
+        out = _device_buffers(state, 1, cur.pixels * 16)
+        try:
+            _check(state.context, _native.hip().pt_denoise(state.context, C.byref(q), cur.bufs[1], cur.bufs[2], out[0], int(iterations)), "pt_denoise")
+            h, w = int(q.height), int(q.width)
+            img = np.zeros((h, w, 4), np.float32)
+            _check(state.context, _native.hip().pt_copy_to_host(state.context, img.ctypes.data, out[0], img.nbytes), "copy to host")
+            return img
+        finally:
+            _free_device_buffers(state, out)
+
+    def close(self):
+        state = self._state
+        if state is None:
+            return
+        if state.context:
+            for v in self._views:
+                _free_device_buffers(state, v.bufs)
+        for v in self._views:
+            v.bufs, v.pixels, v.valid = [], 0, False
+        if self in state._temporal:
+            state._temporal.remove(self)
+        self._state = None
+
+
 def saveAccumulation(state, filename):
     """The progressive state of the reference — params.accumulationBuffer and currentFrameIdx
     (pathTracerPrograms.cu:803-811) — as a file; same format as acgpt_main --save-accum."""
@@ -483,6 +604,8 @@ def CleanAllTheThings(state):
     """PathTracerMain.cpp:629-646."""
     L = _native.hip()
     if state.context:
+        for hist in list(getattr(state, "_temporal", ())):
+            hist.close()
         if state.params.accumulationBuffer:
             L.pt_device_free(state.context, state.params.accumulationBuffer)
             state.params.accumulationBuffer = None

@@ -129,7 +129,8 @@ typedef struct pt_bvh_info {
     uint64_t device_bytes;    /* bytes of device memory the scene's arrays hold right now (ABI version 4).  A scene keeps ONE node array — the one
                                * its kernel reads: fp16 nodes (32 B per node) or fp32 nodes (64 B) — plus triangle records (48 B) and shading
                                * records (16 B); node_bytes / half_node_bytes above are the SIZES of the two formats, whichever is resident.
-                               * The other array, and the experiment formats, are rebuilt on first use (a ray query, pt_set_tuning) and count from then on. */
+                               * The other array, the experiment formats and pt_temporal_blend's bsdfType per triangle (1 B) are built on first use (a ray
+                               * query, pt_set_tuning, the first blend) and count from then on. */
 } pt_bvh_info;
 
 /* ---- lifetime -------------------------------------------------------------
@@ -297,7 +298,7 @@ int pt_trace_any(pt_ctx* ctx, const float* rays, size_t n, uint8_t* hit_out);
  * fp32 nodes back as a ray query does.  Fails without a scene.
  *
  * pt_denoise: edge-avoiding a-trous filter (Dammertz et al. 2010) with the variance-driven luminance edge-stop of SVGF (Schied et al.
- * 2017), no temporal part.  Reads params->accumulationBuffer (linear radiance, float4[w*h]), width, height and the two feature buffers;
+ * 2017), no temporal part of its own (pt_temporal_blend below is that).  Reads params->accumulationBuffer (linear radiance, float4[w*h]), width, height and the two feature buffers;
  * writes linear float4 {r, g, b, 1} to out_rgba (device; pt_resolve_framebuffer makes colours of it).  iterations in [1, 8]; 5 reaches
  * 2 * (1 + 2 + 4 + 8 + 16) = 62 pixels.  out_rgba must not overlap an input.  All arithmetic fp32 in the order written here
  * (tests/denoise_ref.py is the NumPy statement of the same thing):
@@ -318,6 +319,54 @@ int pt_trace_any(pt_ctx* ctx, const float* rays, size_t n, uint8_t* hit_out);
  * calls give the same bits, and so do the two math modes.                                                                        */
 int pt_render_features(pt_ctx* ctx, const pt_params* params, float* albedo_prim, float* normal_depth);
 int pt_denoise(pt_ctx* ctx, const pt_params* params, const float* albedo_prim, const float* normal_depth, float* out_rgba, uint32_t iterations);
+
+/* ---- temporal reprojection (opt-in; nothing above changes) --------------------------------------------------------------------
+ * pt_temporal_blend carries an accumulated image across a camera move: the history of the previous view is reprojected into the
+ * current one, each reprojected sample is checked for consistency, and what passes is blended with the fresh accumulation by sample
+ * count — the temporal half of SVGF (Schied et al. 2017) that pt_denoise lacks.  Enqueues on the context's stream and returns
+ * synchronised, covers the whole image, acts on rank 0 of a pt_create_multi context, never writes the accumulation buffer, the frame
+ * buffer or pt_stats.  All buffers DEVICE, float4 per pixel, row 0 at the bottom:
+ *   params          the current view: camera, width, height and accumulationBuffer (linear rgb; .w is not read); nothing else is read
+ *   accum_samples   N >= 1, the samples the accumulation stands for (currentFrameIdx * samplesPerPixel for the reference's loop)
+ *   albedo_prim, normal_depth   pt_render_features of the current view
+ *   prev            the previous view: camera, width w' and height h' (any size); nothing else is read
+ *   prev_history    float4[w'*h'] {linear rgb, the samples it stands for}: a former out_history, or an accumulation as {rgb, N}
+ *   prev_albedo_prim, prev_normal_depth   pt_render_features of the previous view
+ *   history_cap     the most samples the history may count for (finite, >= 0; 0: the output is exactly {accum.rgb, N})
+ *   out_history     float4[w*h] {rgb, samples}: the input of the next call; must not overlap an input (chained calls ping-pong two)
+ * prev, prev_history, prev_albedo_prim and prev_normal_depth may be NULL together: no history.  All arithmetic fp32 in the order
+ * written here (tests/temporal_ref.py is the NumPy statement of the same thing):
+ *   c = accum_p.rgb;  the pass-through is out = {c, N}, taken on a miss (normal_depth_p.w < 0, or not >= 0), without a history, where
+ *            the hit triangle's bsdfType is not PT_BSDF_DIFFUSE (metal and glass are view-dependent; a Lambertian hit is not, in light
+ *            mode 0 or 1), and wherever a step below says so
+ *   ray      dir_p exactly as pt_render_features traces it (same expression, same order: the same bits), t_p = normal_depth_p.w;
+ *            v = (eye + t_p * dir_p) - eye'
+ *   project  s = dot(v, W') / dot(W', W'), dot = x*x' + y*y' + z*z' left to right; s > 0 or the pass-through;
+ *            du = dot(v, U') / (s * dot(U', U')), dv = dot(v, V') / (s * dot(V', V'))  (the UVW frame taken as orthogonal);
+ *            fx = (du + 1) * 0.5 * w' - 0.5, fy = (dv + 1) * 0.5 * h' - 0.5  (the inverse of the pixel-centre mapping);
+ *            fx in [-1, w') and fy in [-1, h') or the pass-through
+ *   taps     x0 = floor(fx), y0 = floor(fy), ax = fx - x0, ay = fy - y0; taps (x0 + tx, y0 + ty), ty outer, tx inner, in {0, 1},
+ *            w_q = (tx ? ax : 1 - ax) * (ty ? ay : 1 - ay).  A tap is accepted if it lies inside the previous image, its
+ *            prev_albedo_prim.w bits equal the pixel's triangle, and dot(prev_normal_q, normal_p) > 0 (the same side of the same plane:
+ *            both normals face their camera, so a camera that crossed the plane is rejected)
+ *   sums     over the accepted taps, in tap order: a = sum w_q, (r, g, b) = sum w_q * hist_q.rgb, m = sum w_q * hist_q.w
+ *   count    n = (m < cap) ? m : cap — a times the accepted taps' mean count, so a partly accepted footprint counts for less;
+ *            a > 0 and n > 0, or the pass-through
+ *   blend    h = (r, g, b) / a;  out.rgb = (n * h + N * c) / (n + N) per channel;  out.w = n + N
+ * PT_TEMPORAL_HISTORY_CAP = 256 is the default cap (pathtracer.TemporalHistory, acgpt_main --history-in), from a sweep on the CPU
+ * oracle's Cornell box at 128 x 128 (tests/test_temporal_host.py): a 256-spp history and an 8-spp accumulation 10 degrees of orbit
+ * away, against 8192 spp, lose 5.1x of the MSE at any cap >= 256; with a converged history, caps 128 ... 256 are best (the bilinear
+ * resampling's blur weighs more as the history does).
+ * The first call after pt_set_scene builds an n_tris-byte array of the triangles' bsdfTypes on the device (a scatter over the leaf
+ * slots); it counts in pt_bvh_info.device_bytes from then on and is freed with the scene.  No atomics: two calls, and the two math
+ * modes, give the same bits.
+ * A history stays valid for the caller only while the scene, maxDepth, useDirectLighting, useImportanceSampling, the light mode and the
+ * math mode stay as they were: a key toggle or a reset that restarts the accumulation (PathTracerMain.cpp updateState) also discards
+ * the history.  A camera move does not; it is what the call is for (the scene is static).                                     */
+#define PT_TEMPORAL_HISTORY_CAP 256.0f
+int pt_temporal_blend(pt_ctx* ctx, const pt_params* params, uint32_t accum_samples, const float* albedo_prim, const float* normal_depth,
+                      const pt_params* prev, const float* prev_history, const float* prev_albedo_prim, const float* prev_normal_depth,
+                      float history_cap, float* out_history);
 /* ---- device memory helpers for bindings that have no HIP runtime of their own
  * (the reference app calls cudaMalloc/cudaMemcpy directly, :145-148).         */
 int pt_device_malloc(pt_ctx* ctx, void** out, size_t bytes);
