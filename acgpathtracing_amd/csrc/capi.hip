@@ -29,6 +29,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "denoise.h"
 #include "lbvh_build.h"
 #include "pt_device.h"
+#include "refit.h"
 #include "render_megakernel.h"
 #include "selftest.h"
 #include "temporal.h"
@@ -39,6 +40,7 @@ static_assert(sizeof(pt_params) == 168, "pt_params must mirror PathTraceParams (
 static_assert(sizeof(pt_material) == 40, "pt_material must mirror Material (40 bytes)");
 static_assert(sizeof(pt_area_light) == 60, "pt_area_light must mirror AreaLight (60 bytes)");
 static_assert(sizeof(pt_stats) == 96 && sizeof(pt_bvh_info) == 88, "ABI version 4: a change of these layouts bumps pt_abi_version");
+static_assert(sizeof(pt_update_info) == 16, "pt_update_info: 16 bytes, a change of its layout bumps pt_abi_version");
 
 struct pt_multi;
 
@@ -79,6 +81,14 @@ struct pt_ctx {
     pt_multi* multi = nullptr;                // pt_create_multi: this context is rank 0 of a group (below)
     float4* d_denoise[2] = {nullptr, nullptr}; size_t denoise_pixels = 0;   // pt_denoise's ping-pong {colour, variance} buffers
     uint8_t* d_tri_bsdf = nullptr;            // bsdfType per triangle (caller's order): pt_temporal_blend's, built on its first call per scene
+    // what pt_update_vertices keeps of the last pt_set_scene: host copies of everything but the vertices, and after the first update
+    // the index buffer on the device (freed with the scene)
+    bool scene_kept = false;
+    size_t kept_n_verts = 0;
+    std::vector<uint32_t> kept_idx, kept_mat_ids;
+    std::vector<pt_material> kept_mats;
+    uint32_t* d_idx = nullptr;
+    double build_area = -1.0;                 // inner-node area sum over the root's at the last build (refit_tree_area; < 0: not taken yet)
     pt_stats stats;
     uint64_t scene_serial = 0;
     std::string err;
@@ -276,6 +286,10 @@ static void free_scene(pt_ctx* c)
     if (c->d_lights) { (void)hipFree(c->d_lights); c->d_lights = nullptr; }
     c->n_lights = 0; c->light_area = 0.0f;
     if (c->d_tri_bsdf) { (void)hipFree(c->d_tri_bsdf); c->d_tri_bsdf = nullptr; }
+    if (c->d_idx) { (void)hipFree(c->d_idx); c->d_idx = nullptr; }
+    c->scene_kept = false; c->kept_n_verts = 0;
+    c->kept_idx.clear(); c->kept_mat_ids.clear(); c->kept_mats.clear();
+    c->build_area = -1.0;
 }
 
 PT_API void pt_destroy(pt_ctx* c)
@@ -387,6 +401,54 @@ static int ensure_variant_arrays(pt_ctx* c)
     return ensure_top(c);
 }
 
+// light mode 1: every triangle with an emissive material, in triangle order; same fp32 operations as the oracle's orc_scene_create (edges
+// by one subtraction, cross / length / normalize of sutil/vec_math.h:533-549, running area sum).  Replaces the scene's list.
+static int upload_lights(pt_ctx* c, const float* verts_xyzw, const uint32_t* idx, size_t n_tris, const uint32_t* mat_ids, const pt_material* mats)
+{
+    if (c->d_lights) { (void)hipFree(c->d_lights); c->d_lights = nullptr; }
+    c->n_lights = 0; c->light_area = 0.0f;
+    std::vector<float4> lights;
+    float run = 0.0f;
+    for (size_t i = 0; i < n_tris; i++) {
+        const pt_float3 ke = mats[mat_ids[i]].emission;
+        if (!(sqrtf(ke.x * ke.x + ke.y * ke.y + ke.z * ke.z) > 0.0f)) continue;
+        const float* a = verts_xyzw + 4 * (size_t)idx[3 * i], *b = verts_xyzw + 4 * (size_t)idx[3 * i + 1], *cc = verts_xyzw + 4 * (size_t)idx[3 * i + 2];
+        const float e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {cc[0] - a[0], cc[1] - a[1], cc[2] - a[2]};
+        const float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+        const float len = sqrtf(cx * cx + cy * cy + cz * cz);
+        const float area = 0.5f * len;
+        if (!(area > 0.0f)) continue;
+        const float inv = 1.0f / len;
+        run += area;
+        lights.push_back(make_float4(a[0], a[1], a[2], area));
+        lights.push_back(make_float4(e1[0], e1[1], e1[2], run));
+        lights.push_back(make_float4(e2[0], e2[1], e2[2], 0.0f));
+        lights.push_back(make_float4(cx * inv, cy * inv, cz * inv, 0.0f));
+        lights.push_back(make_float4(ke.x, ke.y, ke.z, 0.0f));
+    }
+    if (!lights.empty()) {
+        CK(c, hipMalloc((void**)&c->d_lights, lights.size() * sizeof(float4)));
+        CK(c, hipMemcpy(c->d_lights, lights.data(), lights.size() * sizeof(float4), hipMemcpyHostToDevice));
+    }
+    c->n_lights = (uint32_t)(lights.size() / 5);
+    c->light_area = run;
+    return 0;
+}
+
+// After a build or a refit: stack depth, the variant chosen per scene, and the one node array its kernel reads (fp16: 32 B per node,
+// fp32: 64 B) — present first, then the others released; they come back on first use.
+static int settle_scene(pt_ctx* c)
+{
+    if (int rc = size_stack(c)) return rc;              // stack depth first: the choice below depends on it
+    if (c->variant_auto) { c->variant = pick_variant(c); if (int rc = size_stack(c)) return rc; }
+    const int fmt = ptd::render_variant_node_format(c->variant);
+    if (int rc = ensure_node_format(c, fmt)) return rc;
+    if (fmt == 11) ptd::keep_one_node_array(c->bvh, 2);
+    else if (fmt == 7 || fmt == 8 || fmt == 9) ptd::keep_one_node_array(c->bvh, 1);
+    else if (fmt == 0 || fmt == 5) ptd::keep_one_node_array(c->bvh, 0);
+    return ensure_variant_arrays(c);
+}
+
 static int set_scene_one(pt_ctx* c, const float* verts_xyzw, size_t n_verts, const uint32_t* idx, size_t n_tris,
                         const uint32_t* mat_ids, const pt_material* mats, size_t n_mats)
 {
@@ -428,43 +490,13 @@ static int set_scene_one(pt_ctx* c, const float* verts_xyzw, size_t n_verts, con
         if (!ptd::tag_shade_records(c->bvh, c->d_mats, c->stream, err)) return fail(c, "pt_set_scene: " + err);
     }
     c->n_mats = (uint32_t)n_mats;
-    {   // light mode 1: every triangle with an emissive material, in triangle order; same fp32 operations as the oracle's
-        // orc_scene_create (edges by one subtraction, cross / length / normalize of sutil/vec_math.h:533-549, running area sum)
-        std::vector<float4> lights;
-        float run = 0.0f;
-        for (size_t i = 0; i < n_tris; i++) {
-            const pt_float3 ke = mats[mat_ids[i]].emission;
-            if (!(sqrtf(ke.x * ke.x + ke.y * ke.y + ke.z * ke.z) > 0.0f)) continue;
-            const float* a = verts_xyzw + 4 * (size_t)idx[3 * i], *b = verts_xyzw + 4 * (size_t)idx[3 * i + 1], *cc = verts_xyzw + 4 * (size_t)idx[3 * i + 2];
-            const float e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {cc[0] - a[0], cc[1] - a[1], cc[2] - a[2]};
-            const float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-            const float len = sqrtf(cx * cx + cy * cy + cz * cz);
-            const float area = 0.5f * len;
-            if (!(area > 0.0f)) continue;
-            const float inv = 1.0f / len;
-            run += area;
-            lights.push_back(make_float4(a[0], a[1], a[2], area));
-            lights.push_back(make_float4(e1[0], e1[1], e1[2], run));
-            lights.push_back(make_float4(e2[0], e2[1], e2[2], 0.0f));
-            lights.push_back(make_float4(cx * inv, cy * inv, cz * inv, 0.0f));
-            lights.push_back(make_float4(ke.x, ke.y, ke.z, 0.0f));
-        }
-        if (!lights.empty()) {
-            CK(c, hipMalloc((void**)&c->d_lights, lights.size() * sizeof(float4)));
-            CK(c, hipMemcpy(c->d_lights, lights.data(), lights.size() * sizeof(float4), hipMemcpyHostToDevice));
-        }
-        c->n_lights = (uint32_t)(lights.size() / 5);
-        c->light_area = run;
-    }
-    if (int rc = size_stack(c)) return rc;              // stack depth first: the choice below depends on it
-    if (c->variant_auto) { c->variant = pick_variant(c); if (int rc = size_stack(c)) return rc; }
-    {   // one node array per scene: the one the chosen kernel reads (fp16: 32 B per node, fp32: 64 B); the other comes back on first use
-        const int fmt = ptd::render_variant_node_format(c->variant);
-        if (fmt == 11) ptd::keep_one_node_array(c->bvh, 2);
-        else if (fmt == 7 || fmt == 8 || fmt == 9) ptd::keep_one_node_array(c->bvh, 1);
-        else if (fmt == 0 || fmt == 5) ptd::keep_one_node_array(c->bvh, 0);
-    }
-    if (int rc = ensure_variant_arrays(c)) return rc;
+    if (int rc = upload_lights(c, verts_xyzw, idx, n_tris, mat_ids, mats)) return rc;
+    if (int rc = settle_scene(c)) return rc;
+    c->kept_n_verts = n_verts;
+    c->kept_idx.assign(idx, idx + 3 * n_tris);
+    c->kept_mat_ids.assign(mat_ids, mat_ids + n_tris);
+    c->kept_mats.assign(mats, mats + n_mats);
+    c->scene_kept = true;
     c->scene_serial++;
     return 0;
 }
@@ -490,7 +522,82 @@ PT_API int pt_get_bvh_info(pt_ctx* c, pt_bvh_info* out)
     out->half_node_bytes = c->bvh.n_nodes * (uint32_t)sizeof(ptd::HNode);
     out->half_area_ratio = c->bvh.half_area_ratio;
     out->half_box_inflation = c->bvh.half_box_inflation;
-    out->device_bytes = (uint64_t)ptd::scene_device_bytes(c->bvh) + (c->d_tri_bsdf ? (uint64_t)c->bvh.n_tris : 0u);
+    out->device_bytes = (uint64_t)ptd::scene_device_bytes(c->bvh) + (c->d_tri_bsdf ? (uint64_t)c->bvh.n_tris : 0u) +
+                        (c->d_idx ? (uint64_t)c->bvh.n_tris * 12u : 0u);
+    return 0;
+}
+
+// ---- in-place vertex updates (pt_update_vertices; kernels in refit.hip) -----------------------------------------------------------
+// Refusals before any device work: the scene stays as it was.
+static int check_update(pt_ctx* c, const float* verts_xyzw, size_t n_verts, int mode)
+{
+    if (!c) return fail(nullptr, "pt_update_vertices: null context");
+    if (mode != PT_UPDATE_REFIT && mode != PT_UPDATE_REBUILD && mode != PT_UPDATE_AUTO) return fail(c, "pt_update_vertices: unknown mode");
+    if (!c->scene_kept) return fail(c, "pt_update_vertices: no scene (pt_set_scene first)");
+    if (c->kept_idx.empty()) return fail(c, "pt_update_vertices: the scene has no triangles");
+    if (!verts_xyzw) return fail(c, "pt_update_vertices: null array");
+    if (n_verts != c->kept_n_verts)
+        return fail(c, "pt_update_vertices: " + std::to_string(n_verts) + " vertices, the scene has " + std::to_string(c->kept_n_verts));
+    return 0;
+}
+
+// pt_set_scene with the kept index buffer, material ids and materials (moved out first: set_scene_one replaces them)
+static int rebuild_one(pt_ctx* c, const float* verts_xyzw, size_t n_verts)
+{
+    std::vector<uint32_t> idx = std::move(c->kept_idx), ids = std::move(c->kept_mat_ids);
+    std::vector<pt_material> mats = std::move(c->kept_mats);
+    return set_scene_one(c, verts_xyzw, n_verts, idx.data(), ids.size(), ids.data(), mats.data(), mats.size());
+}
+
+static int update_one(pt_ctx* c, const float* verts_xyzw, size_t n_verts, int mode, pt_update_info* info)
+{
+    if (int rc = check_update(c, verts_xyzw, n_verts, mode)) return rc;
+    CK(c, hipSetDevice(c->device));
+    CK(c, hipStreamSynchronize(c->stream));
+    if (mode == PT_UPDATE_REBUILD) {
+        if (int rc = rebuild_one(c, verts_xyzw, n_verts)) return rc;
+        info->area_ratio = 1.0f; info->rebuilt = 1u;
+        return 0;
+    }
+    Range range("acgpt: vertex update (refit)");
+    const size_t n_tris = c->kept_mat_ids.size();
+    if (!c->d_idx) {      // the first update of a scene: the index buffer on the device, kept with the scene from here on
+        CK(c, hipMalloc((void**)&c->d_idx, n_tris * 12));
+        CK(c, hipMemcpy(c->d_idx, c->kept_idx.data(), n_tris * 12, hipMemcpyHostToDevice));
+    }
+    std::string err;
+    if (c->build_area < 0.0 && !ptd::refit_tree_area(c->bvh, c->stream, c->build_area, err)) return fail(c, "pt_update_vertices: " + err);
+    double area = 1.0;
+    if (!ptd::refit_lbvh(c->bvh, verts_xyzw, n_verts, c->d_idx, c->stream, area, err)) return fail(c, "pt_update_vertices: " + err);
+    const float ratio = c->build_area > 0.0 ? (float)(area / c->build_area) : 1.0f;
+    if (mode == PT_UPDATE_AUTO && ratio > PT_UPDATE_AUTO_AREA_RATIO) {
+        if (int rc = rebuild_one(c, verts_xyzw, n_verts)) return rc;
+        info->area_ratio = 1.0f; info->rebuilt = 1u;
+        return 0;
+    }
+    if (int rc = upload_lights(c, verts_xyzw, c->kept_idx.data(), n_tris, c->kept_mat_ids.data(), c->kept_mats.data())) return rc;
+    if (int rc = settle_scene(c)) return rc;
+    c->scene_serial++;
+    info->area_ratio = ratio; info->rebuilt = 0u;
+    return 0;
+}
+
+PT_API int pt_update_vertices(pt_ctx* c, const float* verts_xyzw, size_t n_verts, int mode, pt_update_info* info)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int rc = check_update(c, verts_xyzw, n_verts, mode)) return rc;      // every rank holds the same scene: refused on all or none
+    pt_update_info local = {0.0f, 1.0f, 0u, 0u};
+    int rc;
+    if (c->multi) {
+        std::vector<pt_update_info> per(c->multi->ranks.size(), local);
+        rc = on_every_rank(c, [&](pt_ctx* r, int i) { return update_one(r, verts_xyzw, n_verts, mode, &per[i]); });
+        local = per[0];
+    } else {
+        rc = update_one(c, verts_xyzw, n_verts, mode, &local);
+    }
+    if (rc) return rc;
+    local.ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) *info = local;
     return 0;
 }
 

@@ -10,7 +10,12 @@
 //              [--keys "0,1,UP,UP,R"] [--out frame.png] [--dump-every k] [--zero-copy]
 //              [--orbit dx,dy] [--zoom n] [--sample-chunks c] [--build-mode 0|1]
 //              [--gpus N] [--multi] [--save-accum file] [--restore-accum file] [--light-mode 0|1] [--math fast|ieee]
-//              [--denoise N] [--history-out file] [--history-in file]
+//              [--denoise N] [--history-out file] [--history-in file] [--move material:dx,dy,dz]
+//
+// --move material:dx,dy,dz: after the last frame, translate every vertex that a face of that material (its newmtl name) references by
+// (dx, dy, dz), give the scene the new vertices with pt_update_vertices(PT_UPDATE_REFIT) — no rebuild —, render the same --frames again
+// from a zeroed accumulation and write <out-stem>_moved<ext>: the image acgpt_main renders of an OBJ whose vertices were moved so, bit
+// for bit.  The run summary gives the update's time and tree-quality ratio.  An unknown material is refused with exit status 2.
 //
 // --denoise N (1..8; default 0 = off): after the last frame, also write <out-stem>_denoised<ext>, the accumulation through N
 // iterations of the edge-avoiding a-trous filter guided by first-hit features (pt_render_features + pt_denoise), coloured by
@@ -354,7 +359,7 @@ static void CleanAllTheThings(PathTracerState& state)                    // :629
 
 int main(int argc, char** argv)
 {
-    std::string objfilepath, out = "frame.png", keys, save_accum, restore_accum, history_out, history_in;
+    std::string objfilepath, out = "frame.png", keys, save_accum, restore_accum, history_out, history_in, move;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false;
     int orbit_dx = 0, orbit_dy = 0, zoom_steps = 0, sample_chunks = 0, build_mode = 1, fuse = 1, light_mode = 0, math_mode = PT_MATH_FAST;
@@ -391,6 +396,7 @@ int main(int argc, char** argv)
         else if (a == "--denoise") denoise_iters = atoi(next());
         else if (a == "--history-out") history_out = next();
         else if (a == "--history-in") history_in = next();
+        else if (a == "--move") move = next();
         else if (a == "--light-mode") light_mode = atoi(next());      // 0 = the reference's hard-coded rectangle (:154-158), 1 = the OBJ's emissive triangles + MIS
         else { std::cerr << "unknown option " << a << std::endl; return 2; }
     }
@@ -401,6 +407,26 @@ int main(int argc, char** argv)
 
     TinyObjWrapper obj(objfilepath);
     if (!obj.loaded()) return 1;
+    std::vector<float> moved_vertices;          // --move: the scene's vertices after the move
+    if (!move.empty()) {
+        const size_t colon = move.rfind(':');
+        float d[3];
+        if (colon == std::string::npos || sscanf(move.c_str() + colon + 1, "%f,%f,%f", &d[0], &d[1], &d[2]) != 3) {
+            std::cerr << "--move material:dx,dy,dz" << std::endl;
+            return 2;
+        }
+        const std::string name = move.substr(0, colon);
+        const std::vector<std::string>& names = obj.getMaterialNames();
+        const size_t id = (size_t)(std::find(names.begin(), names.end(), name) - names.begin());
+        if (id == names.size()) { std::cerr << "--move: no material named '" << name << "' in " << objfilepath << std::endl; return 2; }
+        moved_vertices = obj.getVerticesFloat();
+        const std::vector<uint32_t> idx = obj.getIndexBuffer(), mat = obj.getMaterialIndices();
+        std::vector<uint8_t> moves(moved_vertices.size() / 4, 0);
+        for (size_t t = 0; t < mat.size(); t++)
+            if (mat[t] == (uint32_t)id) moves[idx[3 * t]] = moves[idx[3 * t + 1]] = moves[idx[3 * t + 2]] = 1;
+        for (size_t v = 0; v < moves.size(); v++)
+            if (moves[v]) for (int k = 0; k < 3; k++) moved_vertices[4 * v + k] += d[k];
+    }
     state.params.width = width;
     state.params.height = height;
     try {
@@ -452,6 +478,7 @@ int main(int argc, char** argv)
         }
         if (state.gpus > 1 || state.multi) std::cout << "Devices: " << pt_device_count(state.context) << std::endl;
         uint64_t rays = 0;
+        pt_update_info moved = {0.0f, 0.0f, 0u, 0u};
         {
             OutputBuffer<uchar4> output_buffer(zero_copy ? OutputBufferType::ZERO_COPY : OutputBufferType::DEVICE,
                                                state.params.width, state.params.height);
@@ -500,6 +527,22 @@ int main(int argc, char** argv)
                 }
                 if (!history_out.empty()) writeHistory(history_out, mine);
             }
+            if (!moved_vertices.empty()) {          // --move: refit, then the same frames again from zero
+                PT_CHECK(state.context, pt_update_vertices(state.context, moved_vertices.data(), moved_vertices.size() / 4, PT_UPDATE_REFIT, &moved));
+                state.params.handle = pt_scene_handle(state.context);
+                state.params.currentFrameIdx = 0u;
+                PT_CHECK(state.context, pt_device_memset(state.context, state.params.accumulationBuffer, 0,
+                                                         (size_t)state.params.width * state.params.height * 4 * sizeof(float)));
+                for (int f = 0; f < frames;) {
+                    const int batch = std::min(fuse, frames - f);
+                    LaunchCurrentFrame(output_buffer, state, (uint32_t)batch);
+                    state.params.currentFrameIdx += (uint32_t)batch;
+                    f += batch;
+                }
+                const std::string name = suffixedName(out, "_moved");
+                if (!saveImage(name, reinterpret_cast<const uint8_t*>(output_buffer.getHostPointer()), width, height))
+                    std::cerr << "could not write " << name << std::endl;
+            }
         }
         CleanAllTheThings(state);
         if (frame_counter > 0) avg_ms /= frame_counter;
@@ -507,6 +550,7 @@ int main(int argc, char** argv)
         std::cout << "Average ms per frame: " << (long)avg_ms << std::endl;
         std::cout << "Total ms: " << (long)total_ms << std::endl;
         std::cout << "Rays: " << rays << "  Mray/s: " << (total_ms > 0 ? rays / total_ms / 1e3 : 0.0) << std::endl;
+        if (!moved_vertices.empty()) std::cout << "Refit: " << moved.ms << " ms  area ratio: " << moved.area_ratio << std::endl;
     } catch (const std::exception& e) {
         std::cerr << "Caught exception: " << e.what() << std::endl;
         return 1;

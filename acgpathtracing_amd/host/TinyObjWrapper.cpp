@@ -488,7 +488,7 @@ TinyObjWrapper::TinyObjWrapper(const std::string& filename) { loadFile(filename)
 bool TinyObjWrapper::loadFile(const std::string& filename)
 {
     _warn.clear(); _err.clear();
-    _vertices.clear(); _materials.clear(); _materialIndices.clear(); _indexBuffer.clear();
+    _vertices.clear(); _materials.clear(); _materialNames.clear(); _materialIndices.clear(); _indexBuffer.clear();
     dataLoaded = false;
     const bool timing = getenv("ACGPT_OBJ_TIMING") != nullptr;
     const auto t_start = std::chrono::steady_clock::now();
@@ -693,6 +693,7 @@ bool TinyObjWrapper::loadFile(const std::string& filename)
         else if (m.name.find("Metallic") != std::string::npos) mat.bsdfType = BSDF_METALLIC;
         else mat.bsdfType = BSDF_DIFFUSE;
         _materials.push_back(mat);
+        _materialNames.push_back(m.name);
     }
     _materialIndices.swap(mesh.mat);
     _indexBuffer.swap(mesh.idx);
@@ -709,5 +710,6 @@ std::vector<Material> TinyObjWrapper::getMaterials() const { return _materials; 
 std::vector<uint32_t> TinyObjWrapper::getMaterialIndices() const { return _materialIndices; }
 std::vector<uint32_t> TinyObjWrapper::getIndexBuffer() const { return _indexBuffer; }
 size_t TinyObjWrapper::getNumMaterials() const { return _materials.size(); }
+const std::vector<std::string>& TinyObjWrapper::getMaterialNames() const { return _materialNames; }
 
 }  // namespace acgpt

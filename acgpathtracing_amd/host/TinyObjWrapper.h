@@ -50,11 +50,13 @@ public:
     const std::string& warning() const { return _warn; }
     const std::string& error() const { return _err; }
     bool loaded() const { return dataLoaded; }
+    const std::vector<std::string>& getMaterialNames() const;   // newmtl names, in getMaterials() order
 
 private:
     bool dataLoaded = false;
     std::vector<float> _vertices;
     std::vector<Material> _materials;
+    std::vector<std::string> _materialNames;
     std::vector<uint32_t> _materialIndices;
     std::vector<uint32_t> _indexBuffer;
     std::string _warn, _err;

@@ -365,6 +365,32 @@ def getBvhInfo(state):
     return b
 
 
+UPDATE_MODES = {"refit": _native.UPDATE_REFIT, "rebuild": _native.UPDATE_REBUILD, "auto": _native.UPDATE_AUTO}
+
+
+def updateVertices(state, verts, mode="refit"):
+    """New vertex positions for the scene of the last buildTheAccelarationStructure (pt_update_vertices): index buffer and materials
+    stay.  verts: float32 (n, 4) or flat n * 4 array (w ignored), or a CPU tensor of either, n the scene's vertex count.  mode "refit"
+    keeps the tree's topology and refits its boxes, "rebuild" builds anew, "auto" refits and rebuilds if the tree got too much worse.
+    Every image and query bit equals a fresh build's.  Refreshes state.params.handle; returns pt_update_info as a dict."""
+    if mode not in UPDATE_MODES:
+        raise ValueError("updateVertices: mode must be one of %s" % sorted(UPDATE_MODES))
+    if hasattr(verts, "detach"):            # a torch tensor: host memory only (device-pointer input is not part of the ABI)
+        if verts.device.type != "cpu":
+            raise ValueError("updateVertices: vertices must be in host memory")
+        verts = verts.detach().numpy()
+    v = np.asarray(verts)
+    if not ((v.ndim == 2 and v.shape[1] == 4) or (v.ndim == 1 and v.size % 4 == 0)) or v.size == 0:
+        raise ValueError("updateVertices: expected an (n, 4) or flat n * 4 array, got shape %s" % (v.shape,))
+    v = np.ascontiguousarray(v, np.float32)
+    L = _native.hip()
+    info = _native.UpdateInfo()
+    _check(state.context, L.pt_update_vertices(state.context, v.ctypes.data, v.size // 4, UPDATE_MODES[mode], C.byref(info)),
+           "updateVertices")
+    state.params.handle = L.pt_scene_handle(state.context)
+    return {"ms": info.ms, "area_ratio": info.area_ratio, "rebuilt": bool(info.rebuilt)}
+
+
 def readAccumulation(state):
     """float32 [height, width, 4] copy of params.accumulationBuffer (row 0 = bottom)."""
     h, w = int(state.params.height), int(state.params.width)

@@ -178,6 +178,46 @@ int      pt_set_build_mode(pt_ctx* ctx, int mode);
 uint64_t pt_scene_handle(pt_ctx* ctx);
 int      pt_get_bvh_info(pt_ctx* ctx, pt_bvh_info* out);
 
+/* ---- in-place vertex updates (OPTIX_BUILD_OPERATION_UPDATE; nothing above changes) ------------------------------------------------
+ * pt_update_vertices gives the scene new vertex positions and keeps everything else of the last pt_set_scene: the index buffer, the
+ * material ids and the materials.  verts_xyzw: a HOST array in pt_set_scene's layout, n_verts * 4 floats; n_verts must equal the
+ * scene's vertex count.
+ *   PT_UPDATE_REFIT    keeps the tree's topology and node order (the depth-first numbering of large scenes included) and recomputes
+ *                      from the new vertices: the triangle records, the shading records' geometric normals, the scene box and the
+ *                      triangle boxes' absolute pad, every node's box in the node array the scene keeps, the fp16 space and
+ *                      pt_bvh_info.half_area_ratio / half_box_inflation.  A variant chosen per scene is chosen again as pt_set_scene
+ *                      chooses it; arrays derived from the old boxes (the other node formats, the four-wide records, ...) are released
+ *                      and come back on first use.  Light mode 1's list of emissive triangles is rebuilt.  Upload plus two passes over
+ *                      the leaves and one over the nodes: milliseconds where a build takes a hundred.
+ *   PT_UPDATE_REBUILD  pt_set_scene with the kept index buffer, ids and materials: every bit, pt_get_bvh_info included, as a fresh one.
+ *   PT_UPDATE_AUTO     refits, then rebuilds if the refitted tree's area_ratio exceeds PT_UPDATE_AUTO_AREA_RATIO.
+ * THE CONTRACT: after a refit every query result, every pt_render_features output and every accumulation and frame-buffer bit equals
+ * what a context gets from pt_set_scene with the same arguments and the new vertices, in both math modes and both light modes (boxes only
+ * prune; hits are bit-exact whatever the tree).  Only speed differs: a refitted tree over vertices that moved far from where it was
+ * built has larger, more overlapping boxes.  half_area_ratio and half_box_inflation are summed in a fixed order here and with float
+ * atomics by the build: they agree to about 1e-6 relative, not bit for bit.
+ * area_ratio (the tree's quality): the sum of the inner nodes' surface areas divided by the root's, over the same quantity at the last
+ * build — scale-invariant; 1 for unchanged vertices (exactly: summed from per-block partials in a fixed order, no float atomics), 1 after
+ * a rebuild.
+ * pt_scene_handle changes on every successful update, whatever the mode: a params.handle taken before is refused by pt_launch as any
+ * stale handle is.  A caller refreshes it after the call, as an OptiX caller stores the handle optixAccelBuild returns from an update.
+ * A pt_create_multi context updates every rank.  Refused before any device work, leaving the scene as it was: no scene, a scene without
+ * triangles, a null array, a wrong n_verts, an unknown mode.
+ * Memory: the context keeps host copies of the index buffer, the ids and the materials from pt_set_scene on.  The first update puts the
+ * index buffer on the device (12 B per triangle); it counts in pt_bvh_info.device_bytes from then on and is freed with the scene.  Later
+ * updates allocate nothing that stays.  info may be NULL.                                                                             */
+typedef struct pt_update_info {
+    float    ms;            /* host wall time of the call, upload included                                     */
+    float    area_ratio;    /* tree quality after the update vs at the last build (>= 0; 1 = unchanged)        */
+    uint32_t rebuilt;       /* 1 if the call ran a full build                                                  */
+    uint32_t reserved;
+} pt_update_info;
+#define PT_UPDATE_REFIT   0
+#define PT_UPDATE_REBUILD 1
+#define PT_UPDATE_AUTO    2
+#define PT_UPDATE_AUTO_AREA_RATIO 1.25f
+int pt_update_vertices(pt_ctx* ctx, const float* verts_xyzw, size_t n_verts, int mode, pt_update_info* info);
+
 /* ---- the hot call -------------------------------------------------------------
  * pt_launch <- LaunchCurrentFrame(), PathTracerMain.cpp:184-210: consumes a
  * PathTraceParams by value, runs the megakernel over width x height pixels and
