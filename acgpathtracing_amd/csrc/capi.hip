@@ -528,6 +528,20 @@ PT_API int pt_get_bvh_info(pt_ctx* c, pt_bvh_info* out)
 }
 
 // ---- in-place vertex updates (pt_update_vertices; kernels in refit.hip) -----------------------------------------------------------
+// the scene's index buffer on the device, for pt_update_vertices and pt_temporal_blend_motion: uploaded on the first call of either,
+// counted in device_bytes from then on, freed with the scene
+static int ensure_dev_idx(pt_ctx* c)
+{
+    if (c->d_idx || c->kept_idx.empty()) return 0;
+    const size_t bytes = c->kept_idx.size() * sizeof(uint32_t);
+    uint32_t* d = nullptr;
+    CK(c, hipMalloc((void**)&d, bytes));
+    const hipError_t e = hipMemcpy(d, c->kept_idx.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); return fail(c, std::string("index buffer upload: ") + hipGetErrorString(e)); }
+    c->d_idx = d;
+    return 0;
+}
+
 // Refusals before any device work: the scene stays as it was.
 static int check_update(pt_ctx* c, const float* verts_xyzw, size_t n_verts, int mode)
 {
@@ -561,10 +575,7 @@ static int update_one(pt_ctx* c, const float* verts_xyzw, size_t n_verts, int mo
     }
     Range range("acgpt: vertex update (refit)");
     const size_t n_tris = c->kept_mat_ids.size();
-    if (!c->d_idx) {      // the first update of a scene: the index buffer on the device, kept with the scene from here on
-        CK(c, hipMalloc((void**)&c->d_idx, n_tris * 12));
-        CK(c, hipMemcpy(c->d_idx, c->kept_idx.data(), n_tris * 12, hipMemcpyHostToDevice));
-    }
+    if (int rc = ensure_dev_idx(c)) return rc;
     std::string err;
     if (c->build_area < 0.0 && !ptd::refit_tree_area(c->bvh, c->stream, c->build_area, err)) return fail(c, "pt_update_vertices: " + err);
     double area = 1.0;
@@ -1352,39 +1363,79 @@ static int ensure_tri_bsdf(pt_ctx* c)
     return 0;
 }
 
-PT_API int pt_temporal_blend(pt_ctx* c, const pt_params* p, uint32_t accum_samples, const float* albedo_prim, const float* normal_depth,
-                             const pt_params* prev, const float* prev_history, const float* prev_albedo_prim, const float* prev_normal_depth,
-                             float history_cap, float* out_history)
+// pt_temporal_blend and pt_temporal_blend_motion: every refusal before any device work, in this order, named after the caller
+static int temporal_blend(pt_ctx* c, const char* fn, const pt_params* p, uint32_t accum_samples, const float* albedo_prim,
+                          const float* normal_depth, const pt_params* prev, const float* prev_history, const float* prev_albedo_prim,
+                          const float* prev_normal_depth, float history_cap, bool motion, const float* verts_xyzw, const float* prev_verts_xyzw,
+                          size_t n_verts, float clip_gamma, float* out_history)
 {
-    if (!c) return fail(nullptr, "pt_temporal_blend: null context");
-    if (!p || !p->accumulationBuffer || !albedo_prim || !normal_depth || !out_history) return fail(c, "pt_temporal_blend: null argument");
+    const std::string f(fn);
+    if (!c) return fail(nullptr, f + ": null context");
+    if (!p || !p->accumulationBuffer || !albedo_prim || !normal_depth || !out_history) return fail(c, f + ": null argument");
     const int n_prev = (prev != nullptr) + (prev_history != nullptr) + (prev_albedo_prim != nullptr) + (prev_normal_depth != nullptr);
-    if (n_prev != 0 && n_prev != 4) return fail(c, "pt_temporal_blend: prev, prev_history, prev_albedo_prim and prev_normal_depth are all given or all NULL");
-    if (accum_samples == 0u) return fail(c, "pt_temporal_blend: accum_samples must be >= 1");
-    if (!(history_cap >= 0.0f) || !std::isfinite(history_cap)) return fail(c, "pt_temporal_blend: history_cap must be finite and >= 0");
-    if (int rc = check_image(c, p, "pt_temporal_blend")) return rc;
-    if (prev) if (int rc = check_image(c, prev, "pt_temporal_blend (previous view)")) return rc;
+    if (n_prev != 0 && n_prev != 4) return fail(c, f + ": prev, prev_history, prev_albedo_prim and prev_normal_depth are all given or all NULL");
+    if (accum_samples == 0u) return fail(c, f + ": accum_samples must be >= 1");
+    if (!(history_cap >= 0.0f) || !std::isfinite(history_cap)) return fail(c, f + ": history_cap must be finite and >= 0");
+    if (int rc = check_image(c, p, fn)) return rc;
+    if (prev) if (int rc = check_image(c, prev, (f + " (previous view)").c_str())) return rc;
     const size_t bytes = (size_t)p->width * p->height * sizeof(float4);
     const size_t prev_bytes = prev ? (size_t)prev->width * prev->height * sizeof(float4) : 0;
     const void* inputs[6] = {p->accumulationBuffer, albedo_prim, normal_depth, prev_history, prev_albedo_prim, prev_normal_depth};
     for (int i = 0; i < 6; i++)
         if (inputs[i] && spans_overlap(out_history, bytes, inputs[i], i < 3 ? bytes : prev_bytes))
-            return fail(c, "pt_temporal_blend: out_history overlaps an input (chained calls ping-pong two history buffers)");
-    if (c->scene_serial == 0) return fail(c, "pt_temporal_blend: no scene (pt_set_scene first)");
+            return fail(c, f + ": out_history overlaps an input (chained calls ping-pong two history buffers)");
+    if (c->scene_serial == 0) return fail(c, f + ": no scene (pt_set_scene first)");
+    if (motion) {
+        if ((verts_xyzw != nullptr) != (prev_verts_xyzw != nullptr)) return fail(c, f + ": verts_xyzw and prev_verts_xyzw are both given or both NULL");
+        if (!(clip_gamma >= 0.0f) || !std::isfinite(clip_gamma)) return fail(c, f + ": clip_gamma must be finite and >= 0");
+        if (n_verts != c->kept_n_verts)
+            return fail(c, f + ": " + std::to_string(n_verts) + " vertices, the scene has " + std::to_string(c->kept_n_verts));
+        const size_t vbytes = n_verts * sizeof(float4);
+        if (verts_xyzw && (spans_overlap(out_history, bytes, verts_xyzw, vbytes) || spans_overlap(out_history, bytes, prev_verts_xyzw, vbytes)))
+            return fail(c, f + ": out_history overlaps an input (a vertex array)");
+    }
     CK(c, hipSetDevice(c->device));
     if (int rc = ensure_tri_bsdf(c)) return rc;
+    ptd::TpMotion mo = {};
+    if (motion && verts_xyzw && c->bvh.n_tris > 0) {
+        if (int rc = ensure_dev_idx(c)) return rc;
+        mo.idx = c->d_idx; mo.verts = (const float4*)verts_xyzw; mo.prev_verts = (const float4*)prev_verts_xyzw;
+    }
+    mo.gamma = motion ? clip_gamma : 0.0f;
     ptd::TpPrev tp = {};
     if (prev) {
         tp.eye = prev->cameraEye; tp.U = prev->cameraU; tp.V = prev->cameraV; tp.W = prev->cameraW;
         tp.w = prev->width; tp.h = prev->height;
         tp.hist = (const float4*)prev_history; tp.albedo_prim = (const float4*)prev_albedo_prim; tp.normal_depth = (const float4*)prev_normal_depth;
     }
-    Range range("pt_temporal_blend");
-    CK(c, ptd::launch_temporal((const float4*)p->accumulationBuffer, (const float4*)albedo_prim, (const float4*)normal_depth, p->width, p->height,
-                               p->cameraEye, p->cameraU, p->cameraV, p->cameraW, (float)accum_samples, tp, c->d_tri_bsdf, c->bvh.n_tris,
-                               history_cap, (float4*)out_history, c->stream));
+    Range range(fn);
+    if (motion)
+        CK(c, ptd::launch_temporal_motion((const float4*)p->accumulationBuffer, (const float4*)albedo_prim, (const float4*)normal_depth, p->width,
+                                          p->height, p->cameraEye, p->cameraU, p->cameraV, p->cameraW, (float)accum_samples, tp, c->d_tri_bsdf,
+                                          c->bvh.n_tris, history_cap, mo, (float4*)out_history, c->stream));
+    else
+        CK(c, ptd::launch_temporal((const float4*)p->accumulationBuffer, (const float4*)albedo_prim, (const float4*)normal_depth, p->width, p->height,
+                                   p->cameraEye, p->cameraU, p->cameraV, p->cameraW, (float)accum_samples, tp, c->d_tri_bsdf, c->bvh.n_tris,
+                                   history_cap, (float4*)out_history, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
+}
+
+PT_API int pt_temporal_blend(pt_ctx* c, const pt_params* p, uint32_t accum_samples, const float* albedo_prim, const float* normal_depth,
+                             const pt_params* prev, const float* prev_history, const float* prev_albedo_prim, const float* prev_normal_depth,
+                             float history_cap, float* out_history)
+{
+    return temporal_blend(c, "pt_temporal_blend", p, accum_samples, albedo_prim, normal_depth, prev, prev_history, prev_albedo_prim,
+                          prev_normal_depth, history_cap, false, nullptr, nullptr, 0, 0.0f, out_history);
+}
+
+PT_API int pt_temporal_blend_motion(pt_ctx* c, const pt_params* p, uint32_t accum_samples, const float* albedo_prim, const float* normal_depth,
+                                    const pt_params* prev, const float* prev_history, const float* prev_albedo_prim,
+                                    const float* prev_normal_depth, const float* verts_xyzw, const float* prev_verts_xyzw, size_t n_verts,
+                                    float history_cap, float clip_gamma, float* out_history)
+{
+    return temporal_blend(c, "pt_temporal_blend_motion", p, accum_samples, albedo_prim, normal_depth, prev, prev_history, prev_albedo_prim,
+                          prev_normal_depth, history_cap, true, verts_xyzw, prev_verts_xyzw, n_verts, clip_gamma, out_history);
 }
 
 PT_API int pt_bench_traversal(pt_ctx* c, const float* rays, size_t n, int repeats, int node_format, float* t_out, uint32_t* prim_out, float* ms_out,

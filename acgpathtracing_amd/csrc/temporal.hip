@@ -2,10 +2,14 @@
 //
 //   k_tp_tri_bsdf   once per scene, on first use: bsdfType per triangle in the caller's index order (a scatter over the leaf slots)
 //   k_tp_blend      one thread per pixel of the current view: reproject its first hit into the previous camera, take the bilinear
-//                   footprint's consistent taps of the previous history, blend them with the accumulation by sample count
+//                   footprint's consistent taps of the previous history, blend them with the accumulation by sample count.
+//                   k_tp_blend<true> (pt_temporal_blend_motion) adds the hit point's motion between the two views' vertex positions
+//                   and the variance clip of the history mean
 //
 // k_tp_blend reads 48 B of the current view and up to four taps x 48 B of the previous one per pixel and writes 16 B: a gather
-// bound by the caches and HBM, not by arithmetic.  No atomics, no transcendental: two calls give the same bits.
+// bound by the caches and HBM, not by arithmetic.  The motion adds 12 B of indices and six scattered 16-B vertex loads per diffuse hit,
+// the clip nine 16-B accumulation taps shared with the neighbours.  No atomics, no transcendental: two calls
+// give the same bits.
 #include "temporal.h"
 
 namespace ptd {
@@ -19,12 +23,14 @@ k_tp_tri_bsdf(const TriRecord* __restrict__ tris, const float4* __restrict__ sha
     if (prim < n) bsdf[prim] = (uint8_t)((__float_as_uint(shade[i].w) >> kShadeBsdfShift) & 3u);
 }
 
-// Every expression below is mirrored operation for operation by tests/temporal_ref.py (fp32, same order, taps ty-major).  This file
-// is built with -ffp-contract=off: no contraction.
+// Every expression below is mirrored operation for operation by tests/temporal_ref.py (fp32, same order, taps ty-major), and with
+// kMotion by tests/motion_ref.py.  This file is built with -ffp-contract=off: no contraction.  kMotion = false is pt_temporal_blend:
+// the motion and clip steps are compiled out, and what remains is the expressions it always had.
+template <bool kMotion>
 __global__ void __launch_bounds__(256)
 k_tp_blend(const float4* __restrict__ accum, const float4* __restrict__ albedo_prim, const float4* __restrict__ normal_depth, uint32_t w,
            uint32_t h, pt_float3 eye, pt_float3 U, pt_float3 V, pt_float3 W, float N, const TpPrev prev, const uint8_t* __restrict__ bsdf,
-           uint32_t n_tris, float cap, float4* __restrict__ out)
+           uint32_t n_tris, float cap, const TpMotion mo, float4* __restrict__ out)
 {
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
     if (x >= w || y >= h) return;
@@ -37,10 +43,34 @@ k_tp_blend(const float4* __restrict__ accum, const float4* __restrict__ albedo_p
         const float dx = 2.0f * (((float)x + 0.5f) / (float)w) - 1.0f;
         const float dy = 2.0f * (((float)y + 0.5f) / (float)h) - 1.0f;
         const f3 dir = normalize(dx * mk(U) + dy * mk(V) + mk(W));
-        const f3 v = (mk(eye) + ndp.w * dir) - mk(prev.eye);
+        f3 hit = mk(eye) + ndp.w * dir;
+        bool moved_ok = true;
+        if (kMotion && mo.verts) {
+            // motion: the hit point's displacement from this view's positions to the previous view's, by its barycentrics on the
+            // current triangle (Moller-Trumbore on the feature ray); a triangle that did not move adds nothing, not even a zero
+            const uint32_t i0 = mo.idx[3u * prim], i1 = mo.idx[3u * prim + 1u], i2 = mo.idx[3u * prim + 2u];
+            const float4 a0 = mo.verts[i0], a1 = mo.verts[i1], a2 = mo.verts[i2];
+            const float4 q0 = mo.prev_verts[i0], q1 = mo.prev_verts[i1], q2 = mo.prev_verts[i2];
+            const f3 v0 = mk(a0.x, a0.y, a0.z), v1 = mk(a1.x, a1.y, a1.z), v2 = mk(a2.x, a2.y, a2.z);
+            const f3 D0 = mk(q0.x, q0.y, q0.z) - v0, D1 = mk(q1.x, q1.y, q1.z) - v1, D2 = mk(q2.x, q2.y, q2.z) - v2;
+            if (D0.x != 0.0f || D0.y != 0.0f || D0.z != 0.0f || D1.x != 0.0f || D1.y != 0.0f || D1.z != 0.0f ||
+                D2.x != 0.0f || D2.y != 0.0f || D2.z != 0.0f) {
+                const f3 e1 = v1 - v0, e2 = v2 - v0;
+                const f3 pv = cross(dir, e2);
+                const float det = dot(e1, pv);
+                const f3 tv = mk(eye) - v0;
+                const float b1 = dot(tv, pv) / det;
+                const f3 qv = cross(tv, e1);
+                const float b2 = dot(dir, qv) / det;
+                const f3 m = (D0 + b1 * (D1 - D0)) + b2 * (D2 - D0);
+                moved_ok = isfinite(m.x) && isfinite(m.y) && isfinite(m.z);
+                hit = hit + m;
+            }
+        }
+        const f3 v = hit - mk(prev.eye);
         const f3 Up = mk(prev.U), Vp = mk(prev.V), Wp = mk(prev.W);
         const float s = dot(v, Wp) / dot(Wp, Wp);
-        if (s > 0.0f) {
+        if (moved_ok && s > 0.0f) {
             const float du = dot(v, Up) / (s * dot(Up, Up));
             const float dv = dot(v, Vp) / (s * dot(Vp, Vp));
             const float fx = (du + 1.0f) * 0.5f * (float)prev.w - 0.5f;
@@ -73,8 +103,35 @@ k_tp_blend(const float4* __restrict__ accum, const float4* __restrict__ albedo_p
                 }
                 const float n = hn < cap ? hn : cap;
                 if (a > 0.0f && n > 0.0f) {
+                    float h0 = hr / a, h1 = hg / a, h2 = hb / a;
+                    if (kMotion && mo.gamma > 0.0f) {
+                        // clip: the history mean into mu +- gamma sigma of the accumulation's 3 x 3 neighbourhood (taps inside the
+                        // image, dy outer); neighbouring pixels read the same taps, so they come from L1/L2
+                        float s1r = 0.0f, s1g = 0.0f, s1b = 0.0f, s2r = 0.0f, s2g = 0.0f, s2b = 0.0f, k = 0.0f;
+#pragma unroll
+                        for (int ny = -1; ny <= 1; ny++) {
+                            const int yq = (int)y + ny;
+                            if (yq < 0 || yq >= (int)h) continue;
+#pragma unroll
+                            for (int nx = -1; nx <= 1; nx++) {
+                                const int xq = (int)x + nx;
+                                if (xq < 0 || xq >= (int)w) continue;
+                                const float4 cq = accum[(uint32_t)yq * w + (uint32_t)xq];
+                                s1r += cq.x; s1g += cq.y; s1b += cq.z;
+                                s2r += cq.x * cq.x; s2g += cq.y * cq.y; s2b += cq.z * cq.z;
+                                k += 1.0f;
+                            }
+                        }
+                        const float g = mo.gamma;
+                        const float mr = s1r / k, mg = s1g / k, mb = s1b / k;
+                        const float sr = sqrtf(fmaxf(0.0f, s2r / k - mr * mr)), sg = sqrtf(fmaxf(0.0f, s2g / k - mg * mg)),
+                                    sb = sqrtf(fmaxf(0.0f, s2b / k - mb * mb));
+                        h0 = fminf(fmaxf(h0, mr - g * sr), mr + g * sr);
+                        h1 = fminf(fmaxf(h1, mg - g * sg), mg + g * sg);
+                        h2 = fminf(fmaxf(h2, mb - g * sb), mb + g * sb);
+                    }
                     const float den = n + N;
-                    o = make_float4((n * (hr / a) + N * c.x) / den, (n * (hg / a) + N * c.y) / den, (n * (hb / a) + N * c.z) / den, den);
+                    o = make_float4((n * h0 + N * c.x) / den, (n * h1 + N * c.y) / den, (n * h2 + N * c.z) / den, den);
                 }
             }
         }
@@ -96,7 +153,18 @@ hipError_t launch_temporal(const float4* accum, const float4* albedo_prim, const
                            float cap, float4* out, hipStream_t stream)
 {
     const dim3 block(32, 8), grid((w + 31u) / 32u, (h + 7u) / 8u);
-    k_tp_blend<<<grid, block, 0, stream>>>(accum, albedo_prim, normal_depth, w, h, eye, U, V, W, n_samples, prev, bsdf, n_tris, cap, out);
+    k_tp_blend<false><<<grid, block, 0, stream>>>(accum, albedo_prim, normal_depth, w, h, eye, U, V, W, n_samples, prev, bsdf, n_tris, cap,
+                                                  TpMotion{}, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_temporal_motion(const float4* accum, const float4* albedo_prim, const float4* normal_depth, uint32_t w, uint32_t h,
+                                  pt_float3 eye, pt_float3 U, pt_float3 V, pt_float3 W, float n_samples, const TpPrev& prev, const uint8_t* bsdf,
+                                  uint32_t n_tris, float cap, const TpMotion& motion, float4* out, hipStream_t stream)
+{
+    const dim3 block(32, 8), grid((w + 31u) / 32u, (h + 7u) / 8u);
+    k_tp_blend<true><<<grid, block, 0, stream>>>(accum, albedo_prim, normal_depth, w, h, eye, U, V, W, n_samples, prev, bsdf, n_tris, cap,
+                                                 motion, out);
     return hipGetLastError();
 }
 

@@ -10,12 +10,15 @@
 //              [--keys "0,1,UP,UP,R"] [--out frame.png] [--dump-every k] [--zero-copy]
 //              [--orbit dx,dy] [--zoom n] [--sample-chunks c] [--build-mode 0|1]
 //              [--gpus N] [--multi] [--save-accum file] [--restore-accum file] [--light-mode 0|1] [--math fast|ieee]
-//              [--denoise N] [--history-out file] [--history-in file] [--move material:dx,dy,dz]
+//              [--denoise N] [--history-out file] [--history-in file] [--move material:dx,dy,dz [--move-history]]
 //
 // --move material:dx,dy,dz: after the last frame, translate every vertex that a face of that material (its newmtl name) references by
 // (dx, dy, dz), give the scene the new vertices with pt_update_vertices(PT_UPDATE_REFIT) — no rebuild —, render the same --frames again
 // from a zeroed accumulation and write <out-stem>_moved<ext>: the image acgpt_main renders of an OBJ whose vertices were moved so, bit
 // for bit.  The run summary gives the update's time and tree-quality ratio.  An unknown material is refused with exit status 2.
+// --move-history (with --move only): keep the accumulation before the refit as a history {rgb, frames * spp} with its features, and
+// after the moved frames also write <out-stem>_moved_temporal<ext>: that history carried into the moved scene at the same camera by
+// pt_temporal_blend_motion (default cap and clip); with --denoise N also <out-stem>_moved_temporal_denoised<ext>.
 //
 // --denoise N (1..8; default 0 = off): after the last frame, also write <out-stem>_denoised<ext>, the accumulation through N
 // iterations of the edge-avoiding a-trous filter guided by first-hit features (pt_render_features + pt_denoise), coloured by
@@ -350,6 +353,72 @@ static void blendHistory(PathTracerState& state, const HistoryFile& file, const 
     }
 }
 
+// --move-history: the view before the refit (accumulation as {rgb, frames * spp}, features), carried into the moved scene after it
+struct MovedHistory {
+    PathTracerState* state = nullptr;
+    pt_params prev = {};
+    void* b[3] = {nullptr, nullptr, nullptr};       // history, albedo_prim, normal_depth of the view before the move
+
+    void keep(PathTracerState& s)
+    {
+        state = &s;
+        prev = s.params;
+        const size_t n = (size_t)prev.width * prev.height;
+        for (int i = 0; i < 3; i++) PT_CHECK(s.context, pt_device_malloc(s.context, &b[i], n * 16));
+        std::vector<float> host(n * 4);
+        PT_CHECK(s.context, pt_copy_to_host(s.context, host.data(), prev.accumulationBuffer, n * 16));
+        const float samples = (float)(prev.currentFrameIdx * prev.samplesPerPixel);
+        for (size_t i = 3; i < host.size(); i += 4) host[i] = samples;
+        PT_CHECK(s.context, pt_copy_to_device(s.context, b[0], host.data(), n * 16));
+        PT_CHECK(s.context, pt_render_features(s.context, &prev, (float*)b[1], (float*)b[2]));
+    }
+
+    // writes <out>_moved_temporal (and _moved_temporal_denoised); `before` / `after`: the vertices of the two views
+    void blend(PathTracerState& s, const std::vector<float>& before, const std::vector<float>& after, const std::string& out, uint32_t denoise_iters)
+    {
+        const pt_params& p = s.params;
+        const size_t n = (size_t)p.width * p.height, vbytes = before.size() * sizeof(float);
+        // albedo_prim, normal_depth, blended history, denoised (float4), colours (uchar4), vertices now, vertices before
+        const size_t sizes[7] = {n * 16, n * 16, n * 16, n * 16, n * 4, vbytes, vbytes};
+        void* d[7] = {};
+        std::string err;
+        for (int i = 0; i < 7 && err.empty(); i++)
+            if (pt_device_malloc(s.context, &d[i], sizes[i]) != 0) err = pt_last_error(s.context);
+        std::vector<uint8_t> host(n * 4), host_dn(n * 4);
+        pt_params dn = p;
+        dn.accumulationBuffer = (float*)d[2];                         // pt_denoise reads the blend's .xyz
+        if (err.empty() && (pt_copy_to_device(s.context, d[5], after.data(), vbytes) != 0 ||
+                            pt_copy_to_device(s.context, d[6], before.data(), vbytes) != 0 ||
+                            pt_render_features(s.context, &p, (float*)d[0], (float*)d[1]) != 0 ||
+                            pt_temporal_blend_motion(s.context, &p, p.currentFrameIdx * p.samplesPerPixel, (const float*)d[0], (const float*)d[1],
+                                                     &prev, (const float*)b[0], (const float*)b[1], (const float*)b[2], (const float*)d[5],
+                                                     (const float*)d[6], before.size() / 4, PT_TEMPORAL_HISTORY_CAP, PT_TEMPORAL_CLIP_GAMMA,
+                                                     (float*)d[2]) != 0 ||
+                            pt_resolve_framebuffer(s.context, (const float*)d[2], (uint8_t*)d[4], n) != 0 ||
+                            pt_copy_to_host(s.context, host.data(), d[4], n * 4) != 0))
+            err = pt_last_error(s.context);
+        if (err.empty() && denoise_iters > 0 &&
+            (pt_denoise(s.context, &dn, (const float*)d[0], (const float*)d[1], (float*)d[3], denoise_iters) != 0 ||
+             pt_resolve_framebuffer(s.context, (const float*)d[3], (uint8_t*)d[4], n) != 0 ||
+             pt_copy_to_host(s.context, host_dn.data(), d[4], n * 4) != 0))
+            err = pt_last_error(s.context);
+        for (void* x : d) if (x) pt_device_free(s.context, x);
+        if (!err.empty()) throw Exception("moved temporal blend: " + err);
+        const std::string name = suffixedName(out, "_moved_temporal");
+        if (!saveImage(name, host.data(), (int)p.width, (int)p.height)) std::cerr << "could not write " << name << std::endl;
+        if (denoise_iters > 0) {
+            const std::string dname = suffixedName(out, "_moved_temporal_denoised");
+            if (!saveImage(dname, host_dn.data(), (int)p.width, (int)p.height)) std::cerr << "could not write " << dname << std::endl;
+        }
+    }
+
+    ~MovedHistory()
+    {
+        if (state && state->context)
+            for (void* x : b) if (x) pt_device_free(state->context, x);
+    }
+};
+
 static void CleanAllTheThings(PathTracerState& state)                    // :629-646
 {
     if (state.params.accumulationBuffer) pt_device_free(state.context, state.params.accumulationBuffer);
@@ -361,7 +430,7 @@ int main(int argc, char** argv)
 {
     std::string objfilepath, out = "frame.png", keys, save_accum, restore_accum, history_out, history_in, move;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
-    bool zero_copy = false;
+    bool zero_copy = false, move_history = false;
     int orbit_dx = 0, orbit_dy = 0, zoom_steps = 0, sample_chunks = 0, build_mode = 1, fuse = 1, light_mode = 0, math_mode = PT_MATH_FAST;
     PathTracerState state;
     state.params.useDirectLighting = false;
@@ -397,11 +466,13 @@ int main(int argc, char** argv)
         else if (a == "--history-out") history_out = next();
         else if (a == "--history-in") history_in = next();
         else if (a == "--move") move = next();
+        else if (a == "--move-history") move_history = true;
         else if (a == "--light-mode") light_mode = atoi(next());      // 0 = the reference's hard-coded rectangle (:154-158), 1 = the OBJ's emissive triangles + MIS
         else { std::cerr << "unknown option " << a << std::endl; return 2; }
     }
     if (objfilepath.empty()) { std::cerr << "usage: acgpt_main --obj scene.obj [options]" << std::endl; return 2; }
     if (denoise_iters < 0 || denoise_iters > 8) { std::cerr << "--denoise takes 0 (off) to 8 iterations" << std::endl; return 2; }
+    if (move_history && move.empty()) { std::cerr << "--move-history needs --move" << std::endl; return 2; }
     std::vector<std::string> key_list;
     { std::stringstream ss(keys); std::string k; while (std::getline(ss, k, ',')) if (!k.empty()) key_list.push_back(k); }
 
@@ -528,6 +599,8 @@ int main(int argc, char** argv)
                 if (!history_out.empty()) writeHistory(history_out, mine);
             }
             if (!moved_vertices.empty()) {          // --move: refit, then the same frames again from zero
+                MovedHistory kept;
+                if (move_history) kept.keep(state);
                 PT_CHECK(state.context, pt_update_vertices(state.context, moved_vertices.data(), moved_vertices.size() / 4, PT_UPDATE_REFIT, &moved));
                 state.params.handle = pt_scene_handle(state.context);
                 state.params.currentFrameIdx = 0u;
@@ -542,6 +615,7 @@ int main(int argc, char** argv)
                 const std::string name = suffixedName(out, "_moved");
                 if (!saveImage(name, reinterpret_cast<const uint8_t*>(output_buffer.getHostPointer()), width, height))
                     std::cerr << "could not write " << name << std::endl;
+                if (move_history) kept.blend(state, obj.getVerticesFloat(), moved_vertices, out, (uint32_t)denoise_iters);
             }
         }
         CleanAllTheThings(state);

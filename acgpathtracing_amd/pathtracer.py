@@ -237,6 +237,9 @@ class PathTracerState:
         self.total_ms = 0.0
         self._accum_bytes = 0
         self._temporal = []           # TemporalHistory objects holding device buffers of this context (freed by CleanAllTheThings)
+        self._scene_verts = None      # host copy of the scene's current vertex positions, (n, 4) float32
+        self._scene_serial = 0        # advanced by buildTheAccelarationStructure only (pt_set_scene): TemporalHistory(motion=True)'s key
+        self._verts_serial = 0        # advanced by every change of the positions (a build or updateVertices)
 
 
 def createDeviceContext(state, device_id=0, device_ids=None):
@@ -267,6 +270,9 @@ def buildTheAccelarationStructure(state, objs):
                         mid.ctypes.data, C.addressof(mats) if len(mats) else None, len(mats))
     _check(state.context, rc, "buildTheAccelarationStructure")
     state.params.handle = L.pt_scene_handle(state.context)
+    state._scene_verts = v.reshape(-1, 4).copy()
+    state._scene_serial += 1
+    state._verts_serial += 1
 
 
 def createModule(state): pass
@@ -388,6 +394,8 @@ def updateVertices(state, verts, mode="refit"):
     _check(state.context, L.pt_update_vertices(state.context, v.ctypes.data, v.size // 4, UPDATE_MODES[mode], C.byref(info)),
            "updateVertices")
     state.params.handle = L.pt_scene_handle(state.context)
+    state._scene_verts = v.reshape(-1, 4).copy()
+    state._verts_serial += 1
     return {"ms": info.ms, "area_ratio": info.area_ratio, "rebuilt": bool(info.rebuilt)}
 
 
@@ -454,6 +462,7 @@ def denoise(state, iterations=5):
 
 
 TEMPORAL_HISTORY_CAP = 256.0      # include/acgpt.h pt_temporal_blend: the default cap, calibrated in tests/test_temporal_host.py
+TEMPORAL_CLIP_GAMMA = 4.0         # include/acgpt.h PT_TEMPORAL_CLIP_GAMMA: the default clip, calibrated in tests/test_motion_host.py
 
 
 class _TemporalView:
@@ -466,6 +475,9 @@ class _TemporalView:
         self.key = None             # (width, height, camera) of the view
         self.samples = 0            # N of the accumulation the history was last blended from
         self.valid = False
+        self.verts_buf = []         # motion=True: the positions the view was traced with, on the device ...
+        self.verts = None           # ... and on the host
+        self.verts_serial = 0
 
 
 class TemporalHistory:
@@ -476,10 +488,16 @@ class TemporalHistory:
     the same source with the newer accumulation (the accumulation already holds the samples the last call blended in).  The history
     is dropped, silently, when the scene, maxDepth, a toggle, the light mode or the math mode differ from what it was made under, and
     when the accumulation at an unmoved camera stands for fewer samples than last time (a reset).  Owns its device buffers: close()
-    frees them, and so does CleanAllTheThings for the context."""
+    frees them, and so does CleanAllTheThings for the context.
 
-    def __init__(self, cap=TEMPORAL_HISTORY_CAP):
+    motion=True (pt_temporal_blend_motion): a vertex update (updateVertices) between two update() calls keeps the history.  Each view
+    keeps the positions it was traced with; the blend moves every hit point by its triangle's motion between the two views, and clips
+    the history mean to the current neighbourhood (TEMPORAL_CLIP_GAMMA) when the positions differ.  A new scene
+    (buildTheAccelarationStructure), the toggles, the modes and a reset still drop it."""
+
+    def __init__(self, cap=TEMPORAL_HISTORY_CAP, motion=False):
         self.cap = float(cap)
+        self.motion = bool(motion)
         self._state = None
         self._views = [_TemporalView(), _TemporalView()]
         self._cur = 0               # index of the view last blended into
@@ -492,15 +510,16 @@ class TemporalHistory:
         elif self._state is not state:
             raise PathTracerError("TemporalHistory: bound to another PathTracerState")
 
-    @staticmethod
-    def _settings_of(state):
+    def _settings_of(self, state):
         p = state.params
-        return (_native.hip().pt_scene_handle(state.context), int(p.maxDepth), int(p.useDirectLighting), int(p.useImportanceSampling),
+        scene = ("scene", state._scene_serial) if self.motion else _native.hip().pt_scene_handle(state.context)
+        return (scene, int(p.maxDepth), int(p.useDirectLighting), int(p.useImportanceSampling),
                 getattr(state, "_light_mode", 0), getattr(state, "_math_mode", _native.MATH_FAST))
 
-    @staticmethod
-    def _key_of(p):
-        return (int(p.width), int(p.height)) + tuple(v.tuple() for v in (p.cameraEye, p.cameraU, p.cameraV, p.cameraW))
+    def _key_of(self, state):
+        p = state.params
+        key = (int(p.width), int(p.height)) + tuple(v.tuple() for v in (p.cameraEye, p.cameraU, p.cameraV, p.cameraW))
+        return key + (state._verts_serial,) if self.motion else key      # with motion, moved vertices make a new view
 
     def _drop(self):
         for v in self._views:
@@ -513,7 +532,7 @@ class TemporalHistory:
         L = _native.hip()
         p = state.params
         n = int(p.currentFrameIdx) * int(p.samplesPerPixel) if accum_samples is None else int(accum_samples)
-        key, settings = self._key_of(p), self._settings_of(state)
+        key, settings = self._key_of(state), self._settings_of(state)
         cur = self._views[self._cur]
         if settings != self._settings or (cur.valid and cur.key == key and n < cur.samples):
             self._drop()
@@ -530,7 +549,9 @@ class TemporalHistory:
         C.memmove(C.byref(cur.params), C.byref(p), C.sizeof(p))
         hist, alb, nd = cur.bufs
         _check(state.context, L.pt_render_features(state.context, C.byref(p), alb, nd), "pt_render_features")
-        if prev.valid:
+        if self.motion:
+            rc = self._blend_motion(state, p, n, cur, prev)
+        elif prev.valid:
             rc = L.pt_temporal_blend(state.context, C.byref(p), n, alb, nd, C.byref(prev.params), prev.bufs[0], prev.bufs[1], prev.bufs[2],
                                      self.cap, hist)
         else:
@@ -538,6 +559,26 @@ class TemporalHistory:
         _check(state.context, rc, "pt_temporal_blend")
         cur.key, cur.samples, cur.valid = key, n, True
         return _read_image(state, hist)
+
+    def _blend_motion(self, state, p, n, cur, prev):
+        """pt_temporal_blend_motion into cur, with the positions each view was traced with (uploaded into the views' own buffers)."""
+        L = _native.hip()
+        verts = state._scene_verts
+        n_verts = verts.shape[0]
+        if cur.verts_serial != state._verts_serial:
+            if cur.verts is None or cur.verts.shape != verts.shape:
+                _free_device_buffers(state, cur.verts_buf)
+                cur.verts_buf, cur.verts = [], None
+                cur.verts_buf = _device_buffers(state, 1, verts.nbytes)
+            _check(state.context, L.pt_copy_to_device(state.context, cur.verts_buf[0], verts.ctypes.data, verts.nbytes), "vertex upload")
+            cur.verts, cur.verts_serial = verts, state._verts_serial
+        hist, alb, nd = cur.bufs
+        if not prev.valid:
+            return L.pt_temporal_blend_motion(state.context, C.byref(p), n, alb, nd, None, None, None, None, None, None, n_verts, self.cap, 0.0,
+                                              hist)
+        gamma = TEMPORAL_CLIP_GAMMA if not np.array_equal(prev.verts, cur.verts) else 0.0
+        return L.pt_temporal_blend_motion(state.context, C.byref(p), n, alb, nd, C.byref(prev.params), prev.bufs[0], prev.bufs[1], prev.bufs[2],
+                                          cur.verts_buf[0], prev.verts_buf[0], n_verts, self.cap, gamma, hist)
 
     def denoise(self, state, iterations=5):
         """The last update's history through pt_denoise (guided by the same features): float32 [height, width, 4], alpha 1."""
@@ -564,8 +605,10 @@ class TemporalHistory:
         if state.context:
             for v in self._views:
                 _free_device_buffers(state, v.bufs)
+                _free_device_buffers(state, v.verts_buf)
         for v in self._views:
             v.bufs, v.pixels, v.valid = [], 0, False
+            v.verts_buf, v.verts, v.verts_serial = [], None, 0
         if self in state._temporal:
             state._temporal.remove(self)
         self._state = None

@@ -203,8 +203,8 @@ int      pt_get_bvh_info(pt_ctx* ctx, pt_bvh_info* out);
  * stale handle is.  A caller refreshes it after the call, as an OptiX caller stores the handle optixAccelBuild returns from an update.
  * A pt_create_multi context updates every rank.  Refused before any device work, leaving the scene as it was: no scene, a scene without
  * triangles, a null array, a wrong n_verts, an unknown mode.
- * Memory: the context keeps host copies of the index buffer, the ids and the materials from pt_set_scene on.  The first update puts the
- * index buffer on the device (12 B per triangle); it counts in pt_bvh_info.device_bytes from then on and is freed with the scene.  Later
+ * Memory: the context keeps host copies of the index buffer, the ids and the materials from pt_set_scene on.  The first update (or the
+ * first pt_temporal_blend_motion with vertex arrays) puts the index buffer on the device (12 B per triangle); it counts in pt_bvh_info.device_bytes from then on and is freed with the scene.  Later
  * updates allocate nothing that stays.  info may be NULL.                                                                             */
 typedef struct pt_update_info {
     float    ms;            /* host wall time of the call, upload included                                     */
@@ -407,6 +407,40 @@ int pt_denoise(pt_ctx* ctx, const pt_params* params, const float* albedo_prim, c
 int pt_temporal_blend(pt_ctx* ctx, const pt_params* params, uint32_t accum_samples, const float* albedo_prim, const float* normal_depth,
                       const pt_params* prev, const float* prev_history, const float* prev_albedo_prim, const float* prev_normal_depth,
                       float history_cap, float* out_history);
+
+/* pt_temporal_blend_motion is pt_temporal_blend for a scene whose vertices moved between the two views (pt_update_vertices): the
+ * motion of each hit point enters the reprojection, and the history mean is clipped to the current neighbourhood's spread, which limits
+ * moved shadows and changed indirect light on surfaces that did not move themselves (SVGF's motion vectors and a variance clip).
+ * Every argument pt_temporal_blend takes means the same here, every step above stays as it is, and so does everything it promises
+ * (rank 0 of a group, never writes the accumulation, the frame buffer or pt_stats, no atomics, same bits twice and in both math modes).
+ *   verts_xyzw, prev_verts_xyzw   DEVICE float[n_verts * 4] in pt_set_scene's layout (w ignored): the positions the current view was
+ *                 traced with (the scene's current ones) and those the previous view was traced with; both or neither (no motion)
+ *   n_verts       the scene's vertex count
+ *   clip_gamma    finite, >= 0; 0 turns the clip off
+ * Two additions, fp32 in the order written (tests/motion_ref.py is the NumPy statement of the same thing):
+ *   motion   after "ray", for a diffuse hit p on triangle prim: i0, i1, i2 = the scene's index buffer at prim, D_k = prev_v[i_k] - v[i_k]
+ *            per component.  If all nine components are zero, nothing is added (m = 0) and no barycentrics are computed.  Else
+ *            Moller-Trumbore on the current triangle with the feature ray (o = eye, d = dir_p), no fma, dots left to right:
+ *            e1 = v1 - v0, e2 = v2 - v0, pv = cross(d, e2), det = dot(e1, pv), b1 = dot(o - v0, pv) / det,
+ *            b2 = dot(d, cross(o - v0, e1)) / det, m = (D0 + b1 (D1 - D0)) + b2 (D2 - D0); a non-finite m is the pass-through.
+ *            Then v = ((eye + t_p * dir_p) + m) - eye', and project, taps, sums and count go on exactly as above.  A triangle that did
+ *            not move therefore gives pt_temporal_blend's bits exactly.
+ *   clip     (clip_gamma > 0) before the blend, per channel: over the 3 x 3 neighbourhood of p in the accumulation, taps inside the
+ *            image, dy outer, dx inner, k taps: mu = sum c / k, sigma = sqrtf(max(0, sum c^2 / k - mu^2));
+ *            h = min(max(h, mu - gamma sigma), mu + gamma sigma)
+ * PT_TEMPORAL_CLIP_GAMMA is the default clip (pathtracer.TemporalHistory(motion=True) when the positions differ between the views,
+ * acgpt_main --move-history), the best gamma at cap 256 of a sweep on the CPU oracle (tests/test_motion_host.py).
+ * The index buffer is read on the device: the first call with vertex arrays uploads it, as the first pt_update_vertices does (the same
+ * array, 12 B per triangle, counted in pt_bvh_info.device_bytes from then on, freed with the scene).  Refused before any device work,
+ * with a message, leaving the context usable: whatever pt_temporal_blend refuses, one vertex array without the other, a wrong n_verts,
+ * a negative or non-finite clip_gamma, out_history overlapping any input (the vertex arrays included).
+ * A history stays valid across pt_update_vertices when the caller keeps the positions each view was traced with and passes them here;
+ * everything else that discards it above still does.                                                                            */
+#define PT_TEMPORAL_CLIP_GAMMA 4.0f
+int pt_temporal_blend_motion(pt_ctx* ctx, const pt_params* params, uint32_t accum_samples, const float* albedo_prim, const float* normal_depth,
+                             const pt_params* prev, const float* prev_history, const float* prev_albedo_prim, const float* prev_normal_depth,
+                             const float* verts_xyzw, const float* prev_verts_xyzw, size_t n_verts, float history_cap, float clip_gamma,
+                             float* out_history);
 /* ---- device memory helpers for bindings that have no HIP runtime of their own
  * (the reference app calls cudaMalloc/cudaMemcpy directly, :145-148).         */
 int pt_device_malloc(pt_ctx* ctx, void** out, size_t bytes);
