@@ -28,6 +28,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "../../include/acgpt_test.h"
 #include "denoise.h"
 #include "lbvh_build.h"
+#include "materials.h"
 #include "pt_device.h"
 #include "refit.h"
 #include "render_megakernel.h"
@@ -402,36 +403,69 @@ static int ensure_variant_arrays(pt_ctx* c)
 }
 
 // light mode 1: every triangle with an emissive material, in triangle order; same fp32 operations as the oracle's orc_scene_create (edges
-// by one subtraction, cross / length / normalize of sutil/vec_math.h:533-549, running area sum).  Replaces the scene's list.
-static int upload_lights(pt_ctx* c, const float* verts_xyzw, const uint32_t* idx, size_t n_tris, const uint32_t* mat_ids, const pt_material* mats)
+// by one subtraction, cross / length / normalize of sutil/vec_math.h:533-549, running area sum).
+static bool emits_light(const pt_float3& ke) { return sqrtf(ke.x * ke.x + ke.y * ke.y + ke.z * ke.z) > 0.0f; }
+
+// one emissive triangle from its first vertex and two edges (skipped when its area is not positive)
+static void add_light(std::vector<float4>& lights, float& run, const float a[3], const float e1[3], const float e2[3], const pt_float3& ke)
+{
+    const float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+    const float len = sqrtf(cx * cx + cy * cy + cz * cz);
+    const float area = 0.5f * len;
+    if (!(area > 0.0f)) return;
+    const float inv = 1.0f / len;
+    run += area;
+    lights.push_back(make_float4(a[0], a[1], a[2], area));
+    lights.push_back(make_float4(e1[0], e1[1], e1[2], run));
+    lights.push_back(make_float4(e2[0], e2[1], e2[2], 0.0f));
+    lights.push_back(make_float4(cx * inv, cy * inv, cz * inv, 0.0f));
+    lights.push_back(make_float4(ke.x, ke.y, ke.z, 0.0f));
+}
+
+// replaces the scene's list
+static int put_lights(pt_ctx* c, const std::vector<float4>& lights, float run)
 {
     if (c->d_lights) { (void)hipFree(c->d_lights); c->d_lights = nullptr; }
     c->n_lights = 0; c->light_area = 0.0f;
-    std::vector<float4> lights;
-    float run = 0.0f;
-    for (size_t i = 0; i < n_tris; i++) {
-        const pt_float3 ke = mats[mat_ids[i]].emission;
-        if (!(sqrtf(ke.x * ke.x + ke.y * ke.y + ke.z * ke.z) > 0.0f)) continue;
-        const float* a = verts_xyzw + 4 * (size_t)idx[3 * i], *b = verts_xyzw + 4 * (size_t)idx[3 * i + 1], *cc = verts_xyzw + 4 * (size_t)idx[3 * i + 2];
-        const float e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {cc[0] - a[0], cc[1] - a[1], cc[2] - a[2]};
-        const float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-        const float len = sqrtf(cx * cx + cy * cy + cz * cz);
-        const float area = 0.5f * len;
-        if (!(area > 0.0f)) continue;
-        const float inv = 1.0f / len;
-        run += area;
-        lights.push_back(make_float4(a[0], a[1], a[2], area));
-        lights.push_back(make_float4(e1[0], e1[1], e1[2], run));
-        lights.push_back(make_float4(e2[0], e2[1], e2[2], 0.0f));
-        lights.push_back(make_float4(cx * inv, cy * inv, cz * inv, 0.0f));
-        lights.push_back(make_float4(ke.x, ke.y, ke.z, 0.0f));
-    }
     if (!lights.empty()) {
         CK(c, hipMalloc((void**)&c->d_lights, lights.size() * sizeof(float4)));
         CK(c, hipMemcpy(c->d_lights, lights.data(), lights.size() * sizeof(float4), hipMemcpyHostToDevice));
     }
     c->n_lights = (uint32_t)(lights.size() / 5);
     c->light_area = run;
+    return 0;
+}
+
+static int upload_lights(pt_ctx* c, const float* verts_xyzw, const uint32_t* idx, size_t n_tris, const uint32_t* mat_ids, const pt_material* mats)
+{
+    std::vector<float4> lights;
+    float run = 0.0f;
+    for (size_t i = 0; i < n_tris; i++) {
+        const pt_float3 ke = mats[mat_ids[i]].emission;
+        if (!emits_light(ke)) continue;
+        const float* a = verts_xyzw + 4 * (size_t)idx[3 * i], *b = verts_xyzw + 4 * (size_t)idx[3 * i + 1], *cc = verts_xyzw + 4 * (size_t)idx[3 * i + 2];
+        const float e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {cc[0] - a[0], cc[1] - a[1], cc[2] - a[2]};
+        add_light(lights, run, a, e1, e2, ke);
+    }
+    return put_lights(c, lights, run);
+}
+
+// the material table on the device, repacked (pt_device.h DevMaterial); reallocated only when the count changes
+static int upload_materials(pt_ctx* c, const pt_material* mats, size_t n_mats)
+{
+    if (c->d_mats && c->n_mats != n_mats) { (void)hipFree(c->d_mats); c->d_mats = nullptr; }
+    c->n_mats = 0;
+    if (n_mats == 0) return 0;
+    std::vector<ptd::DevMaterial> dm(n_mats);
+    for (size_t i = 0; i < n_mats; i++) {
+        const pt_material& m = mats[i];
+        uint32_t b = (uint32_t)m.bsdfType; float bf; memcpy(&bf, &b, 4);
+        dm[i].kd_ior = make_float4(m.diffuse.x, m.diffuse.y, m.diffuse.z, m.ior);
+        dm[i].ke_bsdf = make_float4(m.emission.x, m.emission.y, m.emission.z, bf);
+    }
+    if (!c->d_mats) CK(c, hipMalloc((void**)&c->d_mats, n_mats * sizeof(ptd::DevMaterial)));
+    CK(c, hipMemcpy(c->d_mats, dm.data(), n_mats * sizeof(ptd::DevMaterial), hipMemcpyHostToDevice));
+    c->n_mats = (uint32_t)n_mats;
     return 0;
 }
 
@@ -477,19 +511,8 @@ static int set_scene_one(pt_ctx* c, const float* verts_xyzw, size_t n_verts, con
         free_scene(c);
         if (!ptd::build_lbvh(verts_xyzw, n_verts, idx, n_tris, mat_ids, 0, c->stream, c->bvh, err)) return fail(c, "pt_set_scene: " + err);
     }
-    if (n_mats) {
-        std::vector<ptd::DevMaterial> dm(n_mats);
-        for (size_t i = 0; i < n_mats; i++) {
-            const pt_material& m = mats[i];
-            uint32_t b = (uint32_t)m.bsdfType; float bf; memcpy(&bf, &b, 4);
-            dm[i].kd_ior = make_float4(m.diffuse.x, m.diffuse.y, m.diffuse.z, m.ior);
-            dm[i].ke_bsdf = make_float4(m.emission.x, m.emission.y, m.emission.z, bf);
-        }
-        CK(c, hipMalloc((void**)&c->d_mats, n_mats * sizeof(ptd::DevMaterial)));
-        CK(c, hipMemcpy(c->d_mats, dm.data(), n_mats * sizeof(ptd::DevMaterial), hipMemcpyHostToDevice));
-        if (!ptd::tag_shade_records(c->bvh, c->d_mats, c->stream, err)) return fail(c, "pt_set_scene: " + err);
-    }
-    c->n_mats = (uint32_t)n_mats;
+    if (int rc = upload_materials(c, mats, n_mats)) return rc;
+    if (n_mats && !ptd::tag_shade_records(c->bvh, c->d_mats, c->stream, err)) return fail(c, "pt_set_scene: " + err);
     if (int rc = upload_lights(c, verts_xyzw, idx, n_tris, mat_ids, mats)) return rc;
     if (int rc = settle_scene(c)) return rc;
     c->kept_n_verts = n_verts;
@@ -609,6 +632,73 @@ PT_API int pt_update_vertices(pt_ctx* c, const float* verts_xyzw, size_t n_verts
     if (rc) return rc;
     local.ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (info) *info = local;
+    return 0;
+}
+
+// ---- material edits (pt_update_materials; kernels in materials.hip) ---------------------------------------------------------------
+// Refusals before any device work, the same as set_scene_one's: the scene stays as it was.
+static int check_materials(pt_ctx* c, const pt_material* mats, size_t n_mats, const uint32_t* mat_ids, size_t n_tris)
+{
+    if (!c) return fail(nullptr, "pt_update_materials: null context");
+    if (!c->scene_kept) return fail(c, "pt_update_materials: no scene (pt_set_scene first)");
+    const size_t scene_tris = c->kept_mat_ids.size();
+    if (!mats && (scene_tris > 0 || n_mats > 0)) return fail(c, "pt_update_materials: null array");
+    if (mat_ids && n_tris != scene_tris)
+        return fail(c, "pt_update_materials: " + std::to_string(n_tris) + " material ids, the scene has " + std::to_string(scene_tris) + " triangles");
+    if (n_mats > (size_t)ptd::kShadeMatMask + 1u) return fail(c, "pt_update_materials: more than 2^24 materials");
+    const uint32_t* ids = mat_ids ? mat_ids : c->kept_mat_ids.data();
+    for (size_t i = 0; i < scene_tris; i++)
+        if (ids[i] >= n_mats)
+            return fail(c, std::string("pt_update_materials: material index out of range") + (mat_ids ? "" : " (a kept id: pass mat_ids)"));
+    for (size_t i = 0; i < n_mats; i++)
+        if (mats[i].bsdfType < 0 || mats[i].bsdfType > 2) return fail(c, "pt_update_materials: unknown bsdfType");
+    return 0;
+}
+
+// light_prims: the triangles light mode 1 lists (emits_light of their new material), in triangle order
+static int update_materials_one(pt_ctx* c, const pt_material* mats, size_t n_mats, const uint32_t* mat_ids, const std::vector<uint32_t>& light_prims)
+{
+    CK(c, hipSetDevice(c->device));
+    CK(c, hipStreamSynchronize(c->stream));
+    Range range("acgpt: material update");
+    if (c->bvh.n_tris != c->kept_mat_ids.size()) return fail(c, "pt_update_materials: the scene's tree does not hold its triangles");
+    if (int rc = upload_materials(c, mats, n_mats)) return rc;
+    std::vector<float> edges;
+    std::string err;
+    if (!ptd::update_materials(c->bvh, c->d_mats, mat_ids, light_prims, edges, c->stream, err)) return fail(c, "pt_update_materials: " + err);
+    if (mat_ids) c->kept_mat_ids.assign(mat_ids, mat_ids + c->kept_mat_ids.size());
+    c->kept_mats.assign(mats, mats + n_mats);
+    {   // upload_lights' list: the records hold the very v0, e1, e2 it computes from the vertices
+        std::vector<float4> lights;
+        float run = 0.0f;
+        for (size_t j = 0; j < light_prims.size(); j++)
+            add_light(lights, run, &edges[9 * j], &edges[9 * j + 3], &edges[9 * j + 6], mats[c->kept_mat_ids[light_prims[j]]].emission);
+        if (int rc = put_lights(c, lights, run)) return rc;
+    }
+    if (c->d_tri_bsdf) { (void)hipFree(c->d_tri_bsdf); c->d_tri_bsdf = nullptr; }      // back on pt_temporal_blend's first call
+    if (int rc = settle_scene(c)) return rc;        // the four-wide records, if the variant walks them
+    c->scene_serial++;
+    return 0;
+}
+
+PT_API int pt_update_materials(pt_ctx* c, const pt_material* mats, size_t n_mats, const uint32_t* mat_ids, size_t n_tris, pt_update_info* info)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int rc = check_materials(c, mats, n_mats, mat_ids, n_tris)) return rc;      // every rank holds the same scene: refused on all or none
+    const uint32_t* ids = mat_ids ? mat_ids : c->kept_mat_ids.data();
+    std::vector<uint8_t> lit(n_mats);              // emits_light per material, then per triangle by lookup
+    for (size_t m = 0; m < n_mats; m++) lit[m] = emits_light(mats[m].emission);
+    std::vector<uint32_t> light_prims;
+    for (size_t i = 0; i < c->kept_mat_ids.size(); i++)
+        if (lit[ids[i]]) light_prims.push_back((uint32_t)i);
+    int rc;
+    if (c->multi) rc = on_every_rank(c, [&](pt_ctx* r, int) { return update_materials_one(r, mats, n_mats, mat_ids, light_prims); });
+    else rc = update_materials_one(c, mats, n_mats, mat_ids, light_prims);
+    if (rc) return rc;
+    if (info) {
+        info->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        info->area_ratio = 1.0f; info->rebuilt = 0u; info->reserved = 0u;
+    }
     return 0;
 }
 

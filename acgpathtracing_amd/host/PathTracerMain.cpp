@@ -11,7 +11,13 @@
 //              [--orbit dx,dy] [--zoom n] [--sample-chunks c] [--build-mode 0|1]
 //              [--gpus N] [--multi] [--save-accum file] [--restore-accum file] [--light-mode 0|1] [--math fast|ieee]
 //              [--denoise N] [--history-out file] [--history-in file] [--move material:dx,dy,dz [--move-history]]
+//              [--set-material name:kd=r,g,b[,ke=r,g,b][,bsdf=diffuse|metal|glass][,ior=x] ...]
 //
+// --set-material (repeatable): after the last frame (and after --move's, if given), give the named material (its newmtl name) the
+// fields listed — any of kd, ke, bsdf, ior, in any order, each at most once —, apply every edit at once with pt_update_materials —
+// no rebuild —, render the same --frames again from a zeroed accumulation and write <out-stem>_material<ext>: the image acgpt_main
+// renders of the OBJ with a .mtl edited so, bit for bit.  The run summary gives the update's time.  An unknown material or a
+// malformed field is refused, before any device work, with a message and exit status 1.
 // --move material:dx,dy,dz: after the last frame, translate every vertex that a face of that material (its newmtl name) references by
 // (dx, dy, dz), give the scene the new vertices with pt_update_vertices(PT_UPDATE_REFIT) — no rebuild —, render the same --frames again
 // from a zeroed accumulation and write <out-stem>_moved<ext>: the image acgpt_main renders of an OBJ whose vertices were moved so, bit
@@ -419,6 +425,65 @@ struct MovedHistory {
     }
 };
 
+// --set-material name:field,field,...: applies one spec to `mats` (indexed as `names`); false + why on an unknown name or a bad field
+static bool applyMaterialEdit(const std::string& spec, const std::vector<std::string>& names, std::vector<Material>& mats, std::string& why)
+{
+    const size_t colon = spec.rfind(':');
+    if (colon == std::string::npos || colon == 0 || colon + 1 == spec.size()) {
+        why = "expected name:kd=r,g,b[,ke=r,g,b][,bsdf=diffuse|metal|glass][,ior=x], got '" + spec + "'";
+        return false;
+    }
+    const std::string name = spec.substr(0, colon);
+    const size_t id = (size_t)(std::find(names.begin(), names.end(), name) - names.begin());
+    if (id == names.size()) { why = "no material named '" + name + "'"; return false; }
+    Material m = mats[id];
+    const char* p = spec.c_str() + colon + 1;
+    std::vector<std::string> seen;
+    // n finite floats separated by commas, from p on
+    auto floats = [&](float* out, int n) -> bool {
+        for (int k = 0; k < n; k++) {
+            if (k > 0) { if (*p != ',') return false; ++p; }
+            char* end = nullptr;
+            out[k] = strtof(p, &end);
+            if (end == p || !std::isfinite(out[k])) return false;
+            p = end;
+        }
+        return true;
+    };
+    while (true) {
+        const char* eq = strchr(p, '=');
+        if (!eq) { why = "field without '=' in '" + spec + "'"; return false; }
+        const std::string key(p, eq);
+        if (std::find(seen.begin(), seen.end(), key) != seen.end()) { why = "field '" + key + "' given twice in '" + spec + "'"; return false; }
+        seen.push_back(key);
+        p = eq + 1;
+        float v[3];
+        if (key == "kd" || key == "ke") {
+            if (!floats(v, 3)) { why = "'" + key + "' takes three finite numbers r,g,b in '" + spec + "'"; return false; }
+            (key == "kd" ? m.diffuse : m.emission) = make_float3(v[0], v[1], v[2]);
+        } else if (key == "ior") {
+            if (!floats(v, 1)) { why = "'ior' takes one finite number in '" + spec + "'"; return false; }
+            m.ior = v[0];
+        } else if (key == "bsdf") {
+            const char* end = strchr(p, ',');
+            const std::string b = end ? std::string(p, end) : std::string(p);
+            if (b == "diffuse") m.bsdfType = BSDF_DIFFUSE;
+            else if (b == "metal") m.bsdfType = BSDF_METALLIC;
+            else if (b == "glass") m.bsdfType = BSDF_REFRACTION;
+            else { why = "'bsdf' is diffuse, metal or glass, not '" + b + "'"; return false; }
+            p += b.size();
+        } else {
+            why = "unknown field '" + key + "' (kd, ke, bsdf, ior)";
+            return false;
+        }
+        if (*p == '\0') break;
+        if (*p != ',') { why = "unexpected '" + std::string(p) + "' in '" + spec + "'"; return false; }
+        ++p;
+    }
+    mats[id] = m;
+    return true;
+}
+
 static void CleanAllTheThings(PathTracerState& state)                    // :629-646
 {
     if (state.params.accumulationBuffer) pt_device_free(state.context, state.params.accumulationBuffer);
@@ -429,6 +494,7 @@ static void CleanAllTheThings(PathTracerState& state)                    // :629
 int main(int argc, char** argv)
 {
     std::string objfilepath, out = "frame.png", keys, save_accum, restore_accum, history_out, history_in, move;
+    std::vector<std::string> material_edits;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false, move_history = false;
     int orbit_dx = 0, orbit_dy = 0, zoom_steps = 0, sample_chunks = 0, build_mode = 1, fuse = 1, light_mode = 0, math_mode = PT_MATH_FAST;
@@ -467,6 +533,7 @@ int main(int argc, char** argv)
         else if (a == "--history-in") history_in = next();
         else if (a == "--move") move = next();
         else if (a == "--move-history") move_history = true;
+        else if (a == "--set-material") material_edits.push_back(next());
         else if (a == "--light-mode") light_mode = atoi(next());      // 0 = the reference's hard-coded rectangle (:154-158), 1 = the OBJ's emissive triangles + MIS
         else { std::cerr << "unknown option " << a << std::endl; return 2; }
     }
@@ -497,6 +564,17 @@ int main(int argc, char** argv)
             if (mat[t] == (uint32_t)id) moves[idx[3 * t]] = moves[idx[3 * t + 1]] = moves[idx[3 * t + 2]] = 1;
         for (size_t v = 0; v < moves.size(); v++)
             if (moves[v]) for (int k = 0; k < 3; k++) moved_vertices[4 * v + k] += d[k];
+    }
+    std::vector<Material> edited_materials;     // --set-material: the table after every edit
+    if (!material_edits.empty()) {
+        edited_materials = obj.getMaterials();
+        for (const std::string& spec : material_edits) {
+            std::string why;
+            if (!applyMaterialEdit(spec, obj.getMaterialNames(), edited_materials, why)) {
+                std::cerr << "--set-material: " << why << " (" << objfilepath << ")" << std::endl;
+                return 1;
+            }
+        }
     }
     state.params.width = width;
     state.params.height = height;
@@ -549,7 +627,7 @@ int main(int argc, char** argv)
         }
         if (state.gpus > 1 || state.multi) std::cout << "Devices: " << pt_device_count(state.context) << std::endl;
         uint64_t rays = 0;
-        pt_update_info moved = {0.0f, 0.0f, 0u, 0u};
+        pt_update_info moved = {0.0f, 0.0f, 0u, 0u}, material_update = {0.0f, 0.0f, 0u, 0u};
         {
             OutputBuffer<uchar4> output_buffer(zero_copy ? OutputBufferType::ZERO_COPY : OutputBufferType::DEVICE,
                                                state.params.width, state.params.height);
@@ -617,6 +695,23 @@ int main(int argc, char** argv)
                     std::cerr << "could not write " << name << std::endl;
                 if (move_history) kept.blend(state, obj.getVerticesFloat(), moved_vertices, out, (uint32_t)denoise_iters);
             }
+            if (!edited_materials.empty()) {        // --set-material: the new table, then the same frames again from zero
+                PT_CHECK(state.context, pt_update_materials(state.context, reinterpret_cast<const pt_material*>(edited_materials.data()),
+                                                            edited_materials.size(), nullptr, 0, &material_update));
+                state.params.handle = pt_scene_handle(state.context);
+                state.params.currentFrameIdx = 0u;
+                PT_CHECK(state.context, pt_device_memset(state.context, state.params.accumulationBuffer, 0,
+                                                         (size_t)state.params.width * state.params.height * 4 * sizeof(float)));
+                for (int f = 0; f < frames;) {
+                    const int batch = std::min(fuse, frames - f);
+                    LaunchCurrentFrame(output_buffer, state, (uint32_t)batch);
+                    state.params.currentFrameIdx += (uint32_t)batch;
+                    f += batch;
+                }
+                const std::string name = suffixedName(out, "_material");
+                if (!saveImage(name, reinterpret_cast<const uint8_t*>(output_buffer.getHostPointer()), width, height))
+                    std::cerr << "could not write " << name << std::endl;
+            }
         }
         CleanAllTheThings(state);
         if (frame_counter > 0) avg_ms /= frame_counter;
@@ -625,6 +720,7 @@ int main(int argc, char** argv)
         std::cout << "Total ms: " << (long)total_ms << std::endl;
         std::cout << "Rays: " << rays << "  Mray/s: " << (total_ms > 0 ? rays / total_ms / 1e3 : 0.0) << std::endl;
         if (!moved_vertices.empty()) std::cout << "Refit: " << moved.ms << " ms  area ratio: " << moved.area_ratio << std::endl;
+        if (!edited_materials.empty()) std::cout << "Material update: " << material_update.ms << " ms" << std::endl;
     } catch (const std::exception& e) {
         std::cerr << "Caught exception: " << e.what() << std::endl;
         return 1;

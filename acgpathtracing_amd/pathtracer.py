@@ -240,6 +240,7 @@ class PathTracerState:
         self._scene_verts = None      # host copy of the scene's current vertex positions, (n, 4) float32
         self._scene_serial = 0        # advanced by buildTheAccelarationStructure only (pt_set_scene): TemporalHistory(motion=True)'s key
         self._verts_serial = 0        # advanced by every change of the positions (a build or updateVertices)
+        self._mats_serial = 0         # advanced by every change of the materials (a build or updateMaterials)
 
 
 def createDeviceContext(state, device_id=0, device_ids=None):
@@ -273,6 +274,7 @@ def buildTheAccelarationStructure(state, objs):
     state._scene_verts = v.reshape(-1, 4).copy()
     state._scene_serial += 1
     state._verts_serial += 1
+    state._mats_serial += 1
 
 
 def createModule(state): pass
@@ -399,6 +401,51 @@ def updateVertices(state, verts, mode="refit"):
     return {"ms": info.ms, "area_ratio": info.area_ratio, "rebuilt": bool(info.rebuilt)}
 
 
+def updateMaterials(state, materials=None, material_ids=None):
+    """A new material table and/or assignment for the scene of the last buildTheAccelarationStructure (pt_update_materials): the
+    vertices, the index buffer and the tree stay.  materials: the whole new table — TinyObjWrapper.getMaterials()' array or a list of
+    Material —, None for the current one.  material_ids: one id per triangle in the scene's order, a uint32-valued integer array
+    (NumPy or a CPU tensor), None to keep every triangle's.  Every image and query bit equals a fresh build's with the new materials.
+    Refreshes state.params.handle; returns pt_update_info as a dict.  The accumulation is left as it is: restart it
+    (state.params.currentFrameIdx = 0), as after updateVertices.  A TemporalHistory starts anew after the call."""
+    if materials is None and material_ids is None:
+        raise ValueError("updateMaterials: give materials, material_ids or both")
+    if materials is None:
+        mats = getattr(state, "_materials", None)
+        if mats is None:
+            raise ValueError("updateMaterials: no scene (buildTheAccelarationStructure first)")
+    elif isinstance(materials, C.Array) and materials._type_ is Material:
+        mats = materials
+    else:
+        items = list(materials)
+        if not all(isinstance(m, Material) for m in items):
+            raise ValueError("updateMaterials: materials must be Material structures (pt_material)")
+        mats = (Material * len(items))(*items)
+    ids = None
+    if material_ids is not None:
+        if hasattr(material_ids, "detach"):     # a torch tensor: host memory only
+            if material_ids.device.type != "cpu":
+                raise ValueError("updateMaterials: material ids must be in host memory")
+            material_ids = material_ids.detach().numpy()
+        a = np.asarray(material_ids)
+        if a.ndim != 1:
+            raise ValueError("updateMaterials: expected a flat array of one id per triangle, got shape %s" % (a.shape,))
+        if a.dtype.kind not in "iu":
+            raise ValueError("updateMaterials: material ids must be integers, got %s" % a.dtype)
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise ValueError("updateMaterials: material ids must fit uint32")
+        ids = np.ascontiguousarray(a, np.uint32)
+    L = _native.hip()
+    info = _native.UpdateInfo()
+    rc = L.pt_update_materials(state.context, C.addressof(mats) if len(mats) else None, len(mats),
+                               ids.ctypes.data if ids is not None else None, ids.size if ids is not None else 0, C.byref(info))
+    _check(state.context, rc, "updateMaterials")
+    state.params.handle = L.pt_scene_handle(state.context)
+    state._materials = mats
+    state._mats_serial += 1
+    return {"ms": info.ms, "area_ratio": info.area_ratio, "rebuilt": bool(info.rebuilt)}
+
+
 def readAccumulation(state):
     """float32 [height, width, 4] copy of params.accumulationBuffer (row 0 = bottom)."""
     h, w = int(state.params.height), int(state.params.width)
@@ -493,7 +540,10 @@ class TemporalHistory:
     motion=True (pt_temporal_blend_motion): a vertex update (updateVertices) between two update() calls keeps the history.  Each view
     keeps the positions it was traced with; the blend moves every hit point by its triangle's motion between the two views, and clips
     the history mean to the current neighbourhood (TEMPORAL_CLIP_GAMMA) when the positions differ.  A new scene
-    (buildTheAccelarationStructure), the toggles, the modes and a reset still drop it."""
+    (buildTheAccelarationStructure), the toggles, the modes and a reset still drop it.
+
+    A material edit (updateMaterials) drops the history in both modes: a changed material changes the lighting wherever its light
+    reaches, not only on its own pixels, and the motion path's clip bounds only part of that."""
 
     def __init__(self, cap=TEMPORAL_HISTORY_CAP, motion=False):
         self.cap = float(cap)
@@ -513,7 +563,7 @@ class TemporalHistory:
     def _settings_of(self, state):
         p = state.params
         scene = ("scene", state._scene_serial) if self.motion else _native.hip().pt_scene_handle(state.context)
-        return (scene, int(p.maxDepth), int(p.useDirectLighting), int(p.useImportanceSampling),
+        return (scene, getattr(state, "_mats_serial", 0), int(p.maxDepth), int(p.useDirectLighting), int(p.useImportanceSampling),
                 getattr(state, "_light_mode", 0), getattr(state, "_math_mode", _native.MATH_FAST))
 
     def _key_of(self, state):

@@ -218,6 +218,28 @@ typedef struct pt_update_info {
 #define PT_UPDATE_AUTO_AREA_RATIO 1.25f
 int pt_update_vertices(pt_ctx* ctx, const float* verts_xyzw, size_t n_verts, int mode, pt_update_info* info);
 
+/* ---- material edits (an SBT update without an accel rebuild; nothing above changes) -------------------------------------------------
+ * pt_update_materials replaces the scene's material table and, optionally, which material each triangle has; the vertices, the index
+ * buffer and the tree stay.  mats: a HOST array of n_mats pt_material, the whole new table (n_mats may differ from the old count).
+ * mat_ids: a HOST array of n_tris ids in the caller's triangle order (pt_set_scene's), or NULL to keep every triangle's id (n_tris is
+ * then ignored).  The call uploads the table, rewrites each leaf slot's material id and its shading record's bsdfType / emission tag
+ * (one pass over the leaves), rebuilds light mode 1's list of emissive triangles, and releases pt_temporal_blend's bsdfType array and
+ * the arrays that copy triangle records (four-wide and experiment records): they come back on first use.  The light list takes each
+ * emissive triangle's v0, e1 and e2 from its triangle record — the same single subtractions pt_set_scene makes from the vertices —, so
+ * no host copy of the vertices is kept; the running area sum is the host's fp32 sum in triangle order, as pt_set_scene's.
+ * THE CONTRACT: afterwards every query result, every pt_render_features output, every pt_temporal_blend output and every accumulation
+ * and frame-buffer bit equals what a context gets from pt_set_scene with the same vertices, index buffer, ids and table, in both math
+ * modes and both light modes; so does pt_get_bvh_info except build_ms (device_bytes does not count the material table).  The kernel
+ * variant chosen per scene does not depend on materials and stays.  A later pt_update_vertices(PT_UPDATE_REBUILD) builds with the new
+ * table and ids.  A pt_create_multi context updates every rank.
+ * pt_scene_handle changes on every successful call: a params.handle taken before is refused by pt_launch, as after pt_update_vertices.
+ * Refused before any device work, leaving the scene and context as they were: a null context, no scene, a null mats while the scene
+ * has triangles (or n_mats > 0), n_tris not the scene's triangle count (mat_ids given), an id not below n_mats (a kept one included
+ * when mat_ids is NULL), a bsdfType outside 0..2, more than 2^24 materials — pt_set_scene's checks.
+ * Memory: the table is reallocated only when n_mats changes; the call's scratch (the ids, 4 B per triangle and per light) is freed
+ * before it returns.  info may be NULL; else ms is the host wall time, area_ratio 1 and rebuilt 0.                                     */
+int pt_update_materials(pt_ctx* ctx, const pt_material* mats, size_t n_mats, const uint32_t* mat_ids, size_t n_tris, pt_update_info* info);
+
 /* ---- the hot call -------------------------------------------------------------
  * pt_launch <- LaunchCurrentFrame(), PathTracerMain.cpp:184-210: consumes a
  * PathTraceParams by value, runs the megakernel over width x height pixels and
