@@ -80,12 +80,12 @@ ABI_SYMBOLS = [
     "pt_create", "pt_create_multi", "pt_device_count", "pt_destroy", "pt_last_error", "pt_set_scene", "pt_set_build_mode", "pt_scene_handle", "pt_get_bvh_info",
     "pt_launch", "pt_launch_frames", "pt_resolve_framebuffer", "pt_set_partition", "pt_set_sample_chunks", "pt_set_light_mode", "pt_set_math_mode", "pt_set_scratch_limit", "pt_set_tuning",
     "pt_variant_name", "pt_variant_kernel", "pt_kernel_source_hash", "pt_set_stream", "pt_get_stats",
-    "pt_trace_closest", "pt_trace_any", "pt_render_features", "pt_denoise", "pt_temporal_blend", "pt_temporal_blend_motion", "pt_update_vertices", "pt_update_materials",
+    "pt_trace_closest", "pt_trace_any", "pt_render_features", "pt_denoise", "pt_temporal_blend", "pt_temporal_blend_motion", "pt_update_vertices", "pt_update_materials", "pt_set_environment",
     "pt_device_malloc", "pt_device_free", "pt_device_memset", "pt_copy_to_host", "pt_copy_to_device",
     "pt_host_malloc_mapped", "pt_host_free_mapped", "pt_abi_version",
 ]
 # ... and include/acgpt_test.h (test hooks and diagnostics; same library)
-TEST_SYMBOLS = ["pt_bench_traversal", "pt_selftest", "pt_debug_wave_times", "pt_debug_queue_progress", "pt_debug_window_moves", "pt_debug_queue_order", "pt_debug_pixel_classes", "pt_debug_row_spans", "pt_read_morton"]
+TEST_SYMBOLS = ["pt_bench_traversal", "pt_selftest", "pt_debug_wave_times", "pt_debug_queue_progress", "pt_debug_window_moves", "pt_debug_queue_order", "pt_debug_pixel_classes", "pt_debug_row_spans", "pt_read_morton", "pt_debug_environment"]
 
 _hip = None
 _host = None
@@ -171,6 +171,8 @@ def hip():
     L.pt_temporal_blend_motion.restype = C.c_int
     L.pt_update_vertices.argtypes = [vp, vp, sz, C.c_int, C.POINTER(UpdateInfo)]; L.pt_update_vertices.restype = C.c_int
     L.pt_update_materials.argtypes = [vp, vp, sz, vp, sz, C.POINTER(UpdateInfo)]; L.pt_update_materials.restype = C.c_int
+    L.pt_set_environment.argtypes = [vp, vp, C.c_uint32, C.c_uint32, Float3]; L.pt_set_environment.restype = C.c_int
+    L.pt_debug_environment.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_debug_environment.restype = C.c_int
     L.pt_bench_traversal.argtypes = [vp, vp, sz, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_float), vp]; L.pt_bench_traversal.restype = C.c_int
     L.pt_selftest.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_selftest.restype = C.c_int
     L.pt_debug_wave_times.argtypes = [vp, vp, sz]; L.pt_debug_wave_times.restype = C.c_int
@@ -219,5 +221,6 @@ def host():
     L.pth_trackball_script.argtypes = [vp, vp, vp, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, vp, sz, vp]
     L.pth_trackball_script.restype = None
     L.pth_save_image.argtypes = [C.c_char_p, vp, C.c_int, C.c_int]; L.pth_save_image.restype = C.c_int
+    L.pth_load_environment.argtypes = [C.c_char_p, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, sz]; L.pth_load_environment.restype = C.c_int
     _host = L
     return L

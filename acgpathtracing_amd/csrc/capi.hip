@@ -27,6 +27,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "../../include/acgpt.h"
 #include "../../include/acgpt_test.h"
 #include "denoise.h"
+#include "environment.h"
 #include "lbvh_build.h"
 #include "materials.h"
 #include "pt_device.h"
@@ -81,6 +82,7 @@ struct pt_ctx {
     int queue_order = 1;                      // tile-strip rows dealt round robin over the queue shards (render_common.h queue_slot; pt_debug_queue_order)
     pt_multi* multi = nullptr;                // pt_create_multi: this context is rank 0 of a group (below)
     float4* d_denoise[2] = {nullptr, nullptr}; size_t denoise_pixels = 0;   // pt_denoise's ping-pong {colour, variance} buffers
+    ptd::EnvDevice env;                       // pt_set_environment's map and CDFs (w == 0: none); the context's, kept across scene changes
     uint8_t* d_tri_bsdf = nullptr;            // bsdfType per triangle (caller's order): pt_temporal_blend's, built on its first call per scene
     // what pt_update_vertices keeps of the last pt_set_scene: host copies of everything but the vertices, and after the first update
     // the index buffer on the device (freed with the scene)
@@ -319,6 +321,7 @@ static void destroy_one(pt_ctx* c)
     if (c->d_wave_scratch) (void)hipFree(c->d_wave_scratch);
     if (c->d_stack_ovf) (void)hipFree(c->d_stack_ovf);
     if (c->d_row_spans) (void)hipFree(c->d_row_spans);
+    ptd::env_free(c->env);
     for (float4* b : c->d_denoise) if (b) (void)hipFree(b);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -788,6 +791,40 @@ PT_API int pt_set_light_mode(pt_ctx* c, int mode)
     return set_light_mode_one(c, mode);
 }
 
+// texels {r, g, b, 0} with the scale applied (empty: clear the map)
+static int set_environment_one(pt_ctx* c, const std::vector<float4>& rgba, uint32_t w, uint32_t h)
+{
+    CK(c, hipSetDevice(c->device));
+    CK(c, hipStreamSynchronize(c->stream));      // a launch in flight may still read the old map
+    if (rgba.empty()) { ptd::env_free(c->env); return 0; }
+    std::string err;
+    if (!ptd::env_upload(c->env, rgba.data(), w, h, c->stream, err)) return fail(c, err);
+    return 0;
+}
+
+PT_API int pt_set_environment(pt_ctx* c, const float* rgb, uint32_t width, uint32_t height, pt_float3 scale)
+{
+    if (!c) return fail(nullptr, "pt_set_environment: null context");
+    std::vector<float4> rgba;
+    if (rgb != nullptr && width != 0u) {
+        if (height < 1u || width > ptd::kEnvMaxDim || height > ptd::kEnvMaxDim)
+            return fail(c, "pt_set_environment: width and height must lie in [1, " + std::to_string(ptd::kEnvMaxDim) + "]");
+        if ((uint64_t)width * height > ptd::kEnvMaxTexels)
+            return fail(c, "pt_set_environment: more than 2^25 texels");
+        const size_t n = (size_t)width * height;
+        rgba.resize(n);
+        for (size_t i = 0; i < n; i++) {
+            const float r = rgb[3 * i] * scale.x, g = rgb[3 * i + 1] * scale.y, b = rgb[3 * i + 2] * scale.z;
+            if (!(r >= 0.0f && g >= 0.0f && b >= 0.0f) || std::isinf(r) || std::isinf(g) || std::isinf(b))
+                return fail(c, "pt_set_environment: texel " + std::to_string(i) + " (row " + std::to_string(i / width) + ", column " + std::to_string(i % width) +
+                               ") is NaN, infinite or negative after the scale");
+            rgba[i] = make_float4(r, g, b, 0.0f);
+        }
+    }
+    if (c->multi) return on_every_rank(c, [&](pt_ctx* r, int) { return set_environment_one(r, rgba, width, height); });
+    return set_environment_one(c, rgba, width, height);
+}
+
 PT_API int pt_set_math_mode(pt_ctx* c, int mode)
 {
     if (c && c->multi) return on_every_rank(c, [&](pt_ctx* r, int) { return set_math_mode_one(r, mode); });
@@ -1106,7 +1143,17 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
     CK(c, hipSetDevice(c->device));
     // light mode 1 has its own kernel (the estimator differs); every other choice is c->variant.  The node array that kernel
     // walks is on the device before the launch (a scene keeps one array; the lights kernel reads the fp16 nodes whatever the scene chose)
-    const int variant = c->light_mode == 1 ? ptd::kVariantLights : c->variant;
+    // with an environment map: the ENV twin of that choice (light mode 0: by the criterion that picks the windowed-stack kernel; a
+    // variant pt_set_tuning named among the ENV rows stays).  Without one, pt_set_tuning may still name an ENV row: it sees a black map.
+    const bool env = c->env.w != 0u;
+    const bool env_row = c->variant == ptd::kVariantEnv || c->variant == ptd::kVariantEnvDeep;
+    int variant = c->light_mode == 1 ? (env ? ptd::kVariantLightsEnv : ptd::kVariantLights) : c->variant;
+    if (c->light_mode != 1 && env && !env_row) {
+        int w5_blocks = 0;
+        const bool deep = c->bvh.n_tris > ptd::kWindowSceneTris ||
+                          ptd::render_occupancy(ptd::kVariantEnv, c->math_mode, c->stack_entries, c->bvh.n_nodes, &w5_blocks) != hipSuccess || w5_blocks < 5;
+        variant = deep ? ptd::kVariantEnvDeep : ptd::kVariantEnv;
+    }
     if (int rc = ensure_node_format(c, ptd::render_variant_node_format(variant))) return rc;
 
     ptd::RenderArgs a;
@@ -1219,6 +1266,9 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
         }
         if (c->spans_key.back() == 1.0f) a.row_spans = c->d_row_spans;
     }
+    ptd::EnvArgs ea;
+    ea.map = ptd::env_view(c->env);
+    ea.p = c->env.pdf_scale > 0.0f ? (c->n_lights != 0u ? 0.5f : 1.0f) : 0.0f;
     a.queue_heads = c->d_queue;
     a.counters = c->d_counters;
     a.stack_entries = c->stack_entries;
@@ -1277,7 +1327,7 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
     CK(c, hipMemsetAsync(c->d_queue, 0, 8 * sizeof(uint32_t), c->stream));
     CK(c, hipMemsetAsync(c->d_counters, 0, (size_t)ptd::kCounterWords * sizeof(unsigned long long), c->stream));
     CK(c, hipEventRecord(c->ev0, c->stream));
-    { Range range("acgpt: render megakernel (launch_batch)"); CK(c, ptd::launch_render(variant, c->math_mode, a, grid, c->stream)); }
+    { Range range("acgpt: render megakernel (launch_batch)"); CK(c, ptd::launch_render(variant, c->math_mode, a, grid, c->stream, &ea)); }
     CK(c, hipEventRecord(c->ev1, c->stream));
     { Range range("acgpt: k_finalize"); CK(c, ptd::launch_finalize(a, c->stream)); }
     unsigned long long h[8], h_tail[2] = {0, 0};      // h_tail: culled camera rays; experiments build: workgroups of a wavefront kernel that gave up
@@ -1595,6 +1645,26 @@ PT_API int pt_selftest(pt_ctx* c, int op, const void* in, size_t n, void* out)
     if (d_in) (void)hipFree(d_in);
     if (d_out) (void)hipFree(d_out);
     if (e != hipSuccess) return fail(c, std::string("pt_selftest: ") + hipGetErrorString(e));
+    return 0;
+}
+
+PT_API int pt_debug_environment(pt_ctx* c, int op, const float* in, size_t n, float* out)
+{
+    static const int in_dw[3] = {3, 3, 2}, out_dw[3] = {4, 1, 4};
+    if (!c || op < 0 || op > 2 || (n != 0 && (!in || !out)) || n > (1u << 24)) return fail(c, "pt_debug_environment: bad argument");
+    if (n == 0) return 0;
+    CK(c, hipSetDevice(c->device));
+    const size_t in_bytes = n * (size_t)in_dw[op] * 4, out_bytes = n * (size_t)out_dw[op] * 4;
+    float* d_in = nullptr; float* d_out = nullptr;
+    hipError_t e = hipMalloc((void**)&d_in, in_bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_out, out_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = ptd::env_debug(ptd::env_view(c->env), op, c->math_mode != 0 ? 1 : 0, d_in, (uint32_t)n, d_out, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(c, std::string("pt_debug_environment: ") + hipGetErrorString(e));
     return 0;
 }
 

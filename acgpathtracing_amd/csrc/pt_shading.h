@@ -3,6 +3,7 @@
 // pt_device.h: 0 = IEEE operations without contraction, the oracle's level; 2 = the reference build's fast-math kind.
 #pragma once
 #include "pt_device.h"
+#include "pt_environment.h"
 
 namespace ptd {
 
@@ -294,10 +295,14 @@ __device__ __forceinline__ bool shade_hit(const DeviceScene& sc, Late late, cons
 // (pd.done), or, when the function returns true, only if the shadow ray (P, L, 0.01, Ldist - 0.01) is unoccluded.
 // att becomes the throughput of the continuation; prev_pdf the solid-angle pdf of the sampled direction where a
 // light sample was taken (0 elsewhere: a later emitter hit then counts in full).
-template <int FM = 0, typename Late>
+// ENV: the environment map is a light too (pt_set_environment).  A light sample goes to the map with probability p_env
+// (EnvArgs::p: 0.5 beside emissive triangles, 1 without, 0 for a black map), chosen by z1 and z1 rescaled for the strategy it
+// chose, so the draws stay the same; the triangles' pdfs carry the factor 1 - p_env.  With p_env = 0 every value is the one of ENV = false.
+// env(): the EnvArgs (render_megakernel.h) of the launch, read where used (ENV only).
+template <int FM = 0, bool ENV = false, typename Late, typename EnvLate = int>
 __device__ __forceinline__ bool shade_hit_lights(const DeviceScene& sc, Late late, const f3& org, const f3& dir,
                                                  float t_hit, int slot, int depth, uint32_t& pseed, f3& att, float& prev_pdf,
-                                                 Pending& pd, f3& P, f3& L, float& Ldist)
+                                                 Pending& pd, f3& P, f3& L, float& Ldist, EnvLate env = 0)
 {
     const float4 sr = sc.shade[slot];
     const uint32_t mw = __float_as_uint(sr.w);
@@ -312,7 +317,9 @@ __device__ __forceinline__ bool shade_hit_lights(const DeviceScene& sc, Late lat
     const f3 N = faceforward(N0, -dir, N0);
     P = org + t_hit * dir;
     const auto& La = late();
-    const bool useDL = La.useDL != 0u && sc.n_lights != 0u;
+    float p_env = 0.0f;
+    if constexpr (ENV) p_env = env().p;
+    const bool useDL = La.useDL != 0u && (sc.n_lights != 0u || (ENV && p_env > 0.0f));
     const bool useIS = La.useIS != 0u;
     const float area_total = sc.light_area;
     uint32_t s = pseed;
@@ -322,7 +329,8 @@ __device__ __forceinline__ bool shade_hit_lights(const DeviceScene& sc, Late lat
         float w = 1.0f;
         if (depth > 0 && prev_pdf > 0.0f) {
             const float cos_l = fabsf(dot(N0, dir));
-            const float p_l = m_div<FM>(t_hit * t_hit, area_total * cos_l);
+            float p_l = m_div<FM>(t_hit * t_hit, area_total * cos_l);
+            if (ENV) p_l = p_l * (1.0f - p_env);
             w = cos_l > 0.0f ? m_div<FM>(prev_pdf * prev_pdf, prev_pdf * prev_pdf + p_l * p_l) : 1.0f;
         }
         pd.radiance = att * Ke * w;
@@ -373,8 +381,28 @@ __device__ __forceinline__ bool shade_hit_lights(const DeviceScene& sc, Late lat
     pseed = s;
     prev_pdf = 0.0f;
     bool want_shadow = false;
-    if (useDL && bsdf == PT_BSDF_DIFFUSE) {
-        const float target = z1 * area_total;
+    bool to_env = false;
+    float zl = z1;
+    if (ENV && useDL && bsdf == PT_BSDF_DIFFUSE) {
+        to_env = z1 < p_env;
+        zl = to_env ? m_div<FM>(z1, p_env) : m_div<FM>(z1 - p_env, 1.0f - p_env);
+    }
+    bool to_tris = useDL && bsdf == PT_BSDF_DIFFUSE;
+    if constexpr (ENV) if (to_env) {                  // a direction from the map; its shadow ray reaches as far as a radiance ray
+        to_tris = false;
+        float pdf_e; f3 Le;
+        const bool ok = env_sample<FM>(env().map, zl, z2, L, pdf_e, Le);
+        Ldist = 1e16f;
+        const float nDl = dot(N, L);
+        prev_pdf = bsdf_pdf;
+        want_shadow = ok && nDl > 0.0f;
+        const float p_l = p_env * pdf_e;
+        const float p_b = useIS ? (FM >= 2 ? nDl * (1.0f / kPIf) : nDl / kPIf) : 1.0f / (2.0f * kPIf);
+        const float w = m_div<FM>(p_l * p_l, p_l * p_l + p_b * p_b);
+        if (want_shadow) pd.radiance = att_in * Kd * Le * (m_div<FM>(nDl, kPIf * p_l) * w);
+    }
+    if (to_tris) {
+        const float target = zl * area_total;
         uint32_t k = 0;
         while (k + 1u < sc.n_lights && !(target < sc.lights[5u * k + 1u].w)) k++;
         const float4 l0 = sc.lights[5u * k], l1 = sc.lights[5u * k + 1u], l2 = sc.lights[5u * k + 2u], l3 = sc.lights[5u * k + 3u], l4 = sc.lights[5u * k + 4u];
@@ -390,10 +418,12 @@ __device__ __forceinline__ bool shade_hit_lights(const DeviceScene& sc, Late lat
         const float LnDl = fabsf(dot(mk(l3.x, l3.y, l3.z), L));
         prev_pdf = bsdf_pdf;
         want_shadow = nDl > 0.0f && LnDl > 0.0f;
-        const float p_l = m_div<FM>(dist2, area_total * LnDl);
+        float p_l = m_div<FM>(dist2, area_total * LnDl);
+        if (ENV) p_l = p_l * (1.0f - p_env);
         const float p_b = useIS ? (FM >= 2 ? nDl * (1.0f / kPIf) : nDl / kPIf) : 1.0f / (2.0f * kPIf);
         const float w = m_div<FM>(p_l * p_l, p_l * p_l + p_b * p_b);
-        const float geom = m_div<FM>(nDl * LnDl * area_total, kPIf * dist2);
+        float geom = m_div<FM>(nDl * LnDl * area_total, kPIf * dist2);
+        if (ENV) geom = m_div<FM>(geom, 1.0f - p_env);
         if (want_shadow) pd.radiance = att_in * Kd * mk(l4.x, l4.y, l4.z) * (geom * w);      // counted only if the shadow ray finds nothing
     }
     return want_shadow;

@@ -132,7 +132,8 @@ __device__ __forceinline__ uint32_t queue_slot(const RenderArgs& A, uint32_t pos
 // in the kernel-argument segment would be a global load on the deal's critical path)
 // late(): the launch constants again, for the grant decode — once per 256 items, so they are read there (kernel-argument segment,
 // scalar cache) instead of being held in scalar registers across the whole persistent kernel (see RenderArgsBox below)
-template <bool STATS = false, typename Late>
+// OUTSIDE: settle the pixels of the class "outside" here (false: kernels with an environment map, whose pixels see it instead)
+template <bool STATS = false, bool OUTSIDE = true, typename Late>
 __device__ __forceinline__ void refill_lanes(const RenderArgs& A, Late late, QueueState& q, uint32_t lane, unsigned long long below, LanePixel& lp,
                                              const uint32_t* lcg_skip, const WaveBook& book)
 {
@@ -181,7 +182,7 @@ __device__ __forceinline__ void refill_lanes(const RenderArgs& A, Late late, Que
                     // group never becomes work items.  Inside the inner span every ray reaches the box (bit 31): path starts skip the cull test.
                     const uint2 sp = G.row_spans[ok ? (pxy >> 16) : 0u];
                     const uint32_t px = pxy & 0xFFFFu;
-                    const bool outside = ok && (px < (sp.x & 0xFFFFu) || px >= (sp.x >> 16));
+                    const bool outside = OUTSIDE && ok && (px < (sp.x & 0xFFFFu) || px >= (sp.x >> 16));
                     if (outside) write_frame_sum(G, pxy, f, mk(0.0f));
                     q.skipped += (uint32_t)popc(vote(outside));
                     if (ok && px >= (sp.y & 0xFFFFu) && px < (sp.y >> 16)) pxy |= 0x80000000u;
@@ -341,11 +342,12 @@ __device__ __forceinline__ bool reaches_scene(const f3& D, const f3& elo, const 
 // kernel therefore re-reads what only the shade phase needs at the start of every shade round, through an index the
 // compiler cannot see through (a zero made by an opaque instruction), so those values never live across the BVH loop.
 struct RenderArgsBox { RenderArgs a[1]; };
+struct RenderArgsEnvBox { RenderArgs a[1]; EnvArgs e[1]; };      // the ENV kernels' argument: RenderArgs at the same offsets, the map behind it
 __device__ __forceinline__ uint32_t opaque_zero() { uint32_t z; asm volatile("s_mov_b32 %0, 0" : "=s"(z)); return z; }
 
 
 // ---- host-side interface of the kernel translation units --------------------------------------------------------------------
-typedef void (*RenderKernel)(const RenderArgsBox);
+typedef void (*RenderKernel)(const RenderArgsBox);      // (ENV rows: void (*)(const RenderArgsEnvBox), stored as this type and launched by address)
 #ifdef ACGPT_EXPERIMENTS
 // workgroup-level wavefront kernels (render_wavefront.hip; measured, lost, experiments build only)
 struct WfDesc { RenderKernel k; int nt, ns, pool, stack_cap; const char* name; const char* kernel; RenderKernel k_fast; const char* kernel_fast; };

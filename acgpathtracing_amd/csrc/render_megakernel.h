@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "pt_device.h"
+#include "pt_environment.h"
 
 namespace ptd {
 
@@ -30,8 +31,12 @@ constexpr uint32_t kCounterWords = kCulledCounter + kTailCounters;
 // 1.31 M triangles, 5 % slower at 20 k).  fp32 nodes otherwise, with triangle rounds at 8 lanes above kLargeSceneTris.
 constexpr int kVariantSync = 0, kVariantF32 = 1, kVariantF32Stats = 2, kVariantF32Large = 3, kVariantTrig = 4;      // 4: the cosine sampler's trigonometry in hardware, rest as the math mode says
 constexpr int kVariantF16 = 5, kVariantF16Stats = 6, kVariantF16W5 = 7, kVariantLights = 8, kVariantF16W5Deep = 9;
+// the twins of 7, 9 and 8 with an environment map on miss (pt_set_environment; k_render_env, render_pw.inc): what pt_launch runs
+// while a map is set — light mode 0: kVariantEnv, or kVariantEnvDeep by the criterion that sends a scene to kVariantF16W5Deep;
+// light mode 1: kVariantLightsEnv, which also samples the map
+constexpr int kVariantEnv = 10, kVariantEnvDeep = 11, kVariantLightsEnv = 12;
 #ifdef ACGPT_EXPERIMENTS
-constexpr int kVariantWf = 10, kVariantWfStats = 11;      // experiments build: the workgroup-level wavefront kernel (render_wavefront.hip) and its twin with time stamps
+constexpr int kVariantWf = 13, kVariantWfStats = 14;      // experiments build: the workgroup-level wavefront kernel (render_wavefront.hip) and its twin with time stamps
 #endif
 constexpr int kDefaultVariant = kVariantF16W5;
 constexpr uint32_t kLargeSceneTris = 100000;
@@ -85,6 +90,12 @@ struct RenderArgs {
     // plane: kOriginEps * (largest scene coordinate + length of the segment that produced the hit point).  skip_base = the first term.
     float     skip_base;
 };
+// What the ENV kernels (k_render_env) take beside RenderArgs, in a kernel-argument box of their own (render_common.h RenderArgsEnvBox):
+// RenderArgs itself keeps its layout, so the kernels without a map are the same code as before there was one
+struct EnvArgs {
+    EnvMap map;       // pt_environment.h; map.w == 0: no map (a black one)
+    float  p;         // light mode 1: probability of a light sample going to the map (0 for a black map, 0.5 beside emissive triangles, 1 without)
+};
 constexpr float kOriginEps = 16.0f * 1.1920929e-7f;      // 16 * 2^-23
 
 int render_variant_count();
@@ -96,7 +107,8 @@ int render_variant_top_nodes(int variant);      // > 0: the variant stages that 
 int render_variant_stack_cap(int variant);      // 0 = the whole stack in LDS
 int render_variant_node_format(int variant);   // 0 fp32 two-child; 11 fp16 two-child as centre / half extent (the default); 7 / 8 / 9 fp16 two-child {lo, hi} (min-max / rotated / rotated, flags in the multipliers); experiments: 1/2/4 16-bit grid, 3 four-wide 8-bit, 10 / 12 shared-plane records
 hipError_t render_occupancy(int variant, int math, uint32_t stack_entries, uint32_t n_nodes, int* blocks_per_cu);
-hipError_t launch_render(int variant, int math, const RenderArgs& args, uint32_t grid_blocks, hipStream_t stream);
+hipError_t launch_render(int variant, int math, const RenderArgs& args, uint32_t grid_blocks, hipStream_t stream, const EnvArgs* env = nullptr);   // env: the map of an ENV variant (null: a black one)
+int render_variant_has_env(int variant);        // 1: an ENV row (k_render_env)
 hipError_t launch_finalize(const RenderArgs& args, hipStream_t stream);
 hipError_t launch_resolve(const float4* accum, uint32_t* fb, uint32_t n, hipStream_t stream);
 hipError_t launch_keep_owned(float4* accum, uint32_t width, uint32_t height, int rank, int world, hipStream_t stream);

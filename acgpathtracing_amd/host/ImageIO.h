@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdint>
 #include <string>
+#include <vector>
 
 namespace acgpt {
 
@@ -11,5 +12,12 @@ namespace acgpt {
 bool saveImage(const std::string& filename, const uint8_t* rgba, int width, int height);
 bool savePPM(const std::string& filename, const uint8_t* rgba, int width, int height);
 bool savePNG(const std::string& filename, const uint8_t* rgba, int width, int height);
+
+// HDR readers for environment maps (pt_set_environment): Radiance .hdr (RGBE, flat or run-length encoded scanlines, "-Y H +X W"
+// only) and .pfm (PF colour / Pf grey, either byte order).  rgb: height*width*3 linear floats, row 0 = the TOP row of the picture.
+// false + why on a malformed or unsupported file.
+bool loadHDR(const std::string& filename, std::vector<float>& rgb, int& width, int& height, std::string& err);
+bool loadPFM(const std::string& filename, std::vector<float>& rgb, int& width, int& height, std::string& err);
+bool loadEnvironment(const std::string& filename, std::vector<float>& rgb, int& width, int& height, std::string& err);   // by suffix
 
 }  // namespace acgpt

@@ -12,6 +12,10 @@
 //              [--gpus N] [--multi] [--save-accum file] [--restore-accum file] [--light-mode 0|1] [--math fast|ieee]
 //              [--denoise N] [--history-out file] [--history-in file] [--move material:dx,dy,dz [--move-history]]
 //              [--set-material name:kd=r,g,b[,ke=r,g,b][,bsdf=diffuse|metal|glass][,ior=x] ...]
+//              [--env map.hdr|map.pfm [--env-scale s]] [--no-area-light]
+// --env: an environment map (Radiance .hdr or .pfm, latitude-longitude, top row = +Y) that rays leaving the scene see, scaled by
+// --env-scale (default 1); in light mode 1 it is importance-sampled as a light (pt_set_environment).  --no-area-light zeroes
+// params.areaLight.emission, so that a model can be lit by the map alone in light mode 0.
 //
 // --set-material (repeatable): after the last frame (and after --move's, if given), give the named material (its newmtl name) the
 // fields listed — any of kd, ke, bsdf, ior, in any order, each at most once —, apply every edit at once with pt_update_materials —
@@ -496,7 +500,9 @@ int main(int argc, char** argv)
     std::string objfilepath, out = "frame.png", keys, save_accum, restore_accum, history_out, history_in, move;
     std::vector<std::string> material_edits;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
-    bool zero_copy = false, move_history = false;
+    bool zero_copy = false, move_history = false, no_area_light = false;
+    std::string env_path;
+    float env_scale = 1.0f;
     int orbit_dx = 0, orbit_dy = 0, zoom_steps = 0, sample_chunks = 0, build_mode = 1, fuse = 1, light_mode = 0, math_mode = PT_MATH_FAST;
     PathTracerState state;
     state.params.useDirectLighting = false;
@@ -534,6 +540,9 @@ int main(int argc, char** argv)
         else if (a == "--move") move = next();
         else if (a == "--move-history") move_history = true;
         else if (a == "--set-material") material_edits.push_back(next());
+        else if (a == "--env") env_path = next();
+        else if (a == "--env-scale") env_scale = (float)atof(next());
+        else if (a == "--no-area-light") no_area_light = true;
         else if (a == "--light-mode") light_mode = atoi(next());      // 0 = the reference's hard-coded rectangle (:154-158), 1 = the OBJ's emissive triangles + MIS
         else { std::cerr << "unknown option " << a << std::endl; return 2; }
     }
@@ -603,6 +612,14 @@ int main(int argc, char** argv)
         PT_CHECK(state.context, pt_set_sample_chunks(state.context, sample_chunks));
         PT_CHECK(state.context, pt_set_light_mode(state.context, light_mode));
         PT_CHECK(state.context, pt_set_math_mode(state.context, math_mode));
+        if (!env_path.empty()) {
+            std::vector<float> env_rgb;
+            int ew = 0, eh = 0;
+            std::string why;
+            if (!acgpt::loadEnvironment(env_path, env_rgb, ew, eh, why)) throw Exception(why);
+            PT_CHECK(state.context, pt_set_environment(state.context, env_rgb.data(), (uint32_t)ew, (uint32_t)eh, pt_float3{env_scale, env_scale, env_scale}));
+            std::cout << "Environment map: " << env_path << " (" << ew << " x " << eh << ", scale " << env_scale << ")" << std::endl;
+        }
         buildTheAccelarationStructure(state, obj);
         std::cout << "Acceleration Structure Built" << std::endl;
         createModule(state);
@@ -614,6 +631,7 @@ int main(int argc, char** argv)
         createShaderBindingTable(state, obj);
         std::cout << "Shader Binding Table Created" << std::endl;
         initializeTheLaunch(state);
+        if (no_area_light) state.params.areaLight.emission = {0.0f, 0.0f, 0.0f};
         std::cout << "Launch Initialized" << std::endl;
         HistoryFile history;
         if (!history_in.empty()) {              // refused before any frame is rendered

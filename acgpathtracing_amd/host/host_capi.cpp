@@ -74,6 +74,22 @@ HOST_API void pth_trackball_script(const float* eye, const float* lookat, const 
 }
 
 // rgba: width*height*4 bytes, row 0 = bottom; suffix selects PPM or PNG (sutil::saveImage conventions)
+// environment map file (.hdr / .pfm): rgb == NULL returns the size in *width / *height; else fills rgb (height*width*3 floats, row 0 =
+// the top row).  0 = ok; 1 = error (message in err, up to err_len bytes)
+HOST_API int pth_load_environment(const char* path, float* rgb, int* width, int* height, char* err, size_t err_len)
+{
+    std::vector<float> v;
+    std::string e;
+    int w = 0, h = 0;
+    if (!loadEnvironment(path, v, w, h, e)) {
+        if (err && err_len) { strncpy(err, e.c_str(), err_len - 1); err[err_len - 1] = 0; }
+        return 1;
+    }
+    *width = w; *height = h;
+    if (rgb) memcpy(rgb, v.data(), v.size() * sizeof(float));
+    return 0;
+}
+
 HOST_API int pth_save_image(const char* path, const unsigned char* rgba, int width, int height)
 {
     return saveImage(path, rgba, width, height) ? 0 : 1;

@@ -351,6 +351,101 @@ def setLightMode(state, mode):
     state.refreshAccumulationBuffer = True
 
 
+def readHDR(path):
+    """Radiance .hdr (RGBE, flat or run-length encoded scanlines, "-Y H +X W"): float32 [H, W, 3], row 0 = the top row.
+    The same reader as host/ImageIO.cpp loadHDR."""
+    d = open(path, "rb").read()
+    pos = d.index(b"\n") + 1
+    if not d.startswith(b"#?"):
+        raise ValueError("%s: not a Radiance HDR file" % path)
+    while True:
+        end = d.index(b"\n", pos)
+        line = d[pos:end]
+        pos = end + 1
+        if not line:
+            break
+        if line.startswith(b"FORMAT=") and line != b"FORMAT=32-bit_rle_rgbe":
+            raise ValueError("%s: unsupported %s" % (path, line.decode()))
+    end = d.index(b"\n", pos)
+    f = d[pos:end].split()
+    pos = end + 1
+    if len(f) != 4 or f[0] != b"-Y" or f[2] != b"+X":
+        raise ValueError("%s: unsupported resolution line" % path)
+    h, w = int(f[1]), int(f[3])
+    px = np.zeros((h, w, 4), np.uint8)
+    for y in range(h):
+        if 8 <= w < 32768 and d[pos:pos + 2] == b"\x02\x02" and ((d[pos + 2] << 8) | d[pos + 3]) == w and not d[pos + 2] & 0x80:
+            pos += 4
+            for c in range(4):
+                x = 0
+                while x < w:
+                    n = d[pos]
+                    pos += 1
+                    if n > 128:
+                        n -= 128
+                        px[y, x:x + n, c] = d[pos]
+                        pos += 1
+                    else:
+                        if n == 0:
+                            raise ValueError("%s: bad run-length data" % path)
+                        px[y, x:x + n, c] = np.frombuffer(d, np.uint8, n, pos)
+                        pos += n
+                    x += n
+        else:
+            px[y] = np.frombuffer(d, np.uint8, 4 * w, pos).reshape(w, 4)
+            pos += 4 * w
+    e = px[..., 3:4].astype(np.int32)
+    return np.where(e > 0, np.ldexp(px[..., :3].astype(np.float32), e - 136), 0).astype(np.float32)
+
+
+def readPFM(path):
+    """.pfm (PF colour / Pf grey, either byte order): float32 [H, W, 3], row 0 = the top row (the file stores the bottom row first)."""
+    d = open(path, "rb").read()
+    toks, pos = [], 0
+    for _ in range(4):
+        while d[pos:pos + 1].isspace():
+            pos += 1
+        b = pos
+        while pos < len(d) and not d[pos:pos + 1].isspace():
+            pos += 1
+        toks.append(d[b:pos])
+    pos += 1
+    nc = {b"PF": 3, b"Pf": 1}.get(toks[0])
+    w, h, scale = int(toks[1]), int(toks[2]), float(toks[3])
+    if nc is None or scale == 0.0:
+        raise ValueError("%s: not a PFM file" % path)
+    a = np.frombuffer(d, "<f4" if scale < 0 else ">f4", w * h * nc, pos).astype(np.float32).reshape(h, w, nc)[::-1]
+    return np.ascontiguousarray(np.repeat(a, 3, axis=2) if nc == 1 else a)
+
+
+def loadEnvironment(path):
+    """An environment map file by its suffix (.hdr / .pfm): float32 [H, W, 3], row 0 = the +Y pole."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".hdr":
+        return readHDR(path)
+    if ext == ".pfm":
+        return readPFM(path)
+    raise ValueError("%s: unknown environment map format (.hdr or .pfm)" % path)
+
+
+def setEnvironment(state, image_or_path=None, scale=1.0):
+    """Environment lighting (include/acgpt.h pt_set_environment): a latitude-longitude map of linear radiance, [H, W, 3] with row 0 =
+    the +Y pole, or a .hdr / .pfm path, seen by rays that leave the scene and, in light mode 1, importance-sampled as a light.
+    scale: a number or an (r, g, b) triple.  None clears the map."""
+    L = _native.hip()
+    s = (float(scale),) * 3 if np.isscalar(scale) else tuple(float(v) for v in scale)
+    if image_or_path is None:
+        rc = L.pt_set_environment(state.context, None, 0, 0, _f3(s))
+    else:
+        img = loadEnvironment(image_or_path) if isinstance(image_or_path, (str, os.PathLike)) else image_or_path
+        img = np.ascontiguousarray(np.asarray(img, dtype=np.float32))
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("setEnvironment: an image of shape [H, W, 3], got %s" % (img.shape,))
+        rc = L.pt_set_environment(state.context, img.ctypes.data, img.shape[1], img.shape[0], _f3(s))
+    _check(state.context, rc, "pt_set_environment")
+    state.refreshAccumulationBuffer = True
+
+
 def setMathMode(state, mode):
     """Arithmetic of the shading code (include/acgpt.h pt_set_math_mode).  "fast" / 1 (the default): what the reference's own build
     computes with (nvcc --use_fast_math, CMakeLists.txt:267): approximate reciprocal, square root, sine and cosine.  "ieee" / 0:

@@ -283,6 +283,22 @@ int pt_resolve_framebuffer(pt_ctx* ctx, const float* accumulation_rgba, uint8_t*
  *      the same image.  Same random draws per segment as mode 0.  One kernel variant serves it (pt_variant_name "LIGHTS").  */
 int pt_set_light_mode(pt_ctx* ctx, int mode);
 
+/* Environment lighting: an HDR latitude-longitude map that a ray leaving the scene sees (the reference's
+ * MissData::backgroundColor, 0 there, PathTracerMain.cpp:568, replaced by the map).
+ *   rgb: linear radiance, HOST float[height][width][3]; row 0 is the +Y pole.  Each texel is multiplied by `scale`.
+ *   rgb == NULL or width == 0 clears the map.  Refused, with the previous map left in place: width or height outside
+ *   [1, 16384], more than 2^25 texels, a texel that is NaN, infinite or negative after the scale.
+ * Mapping, for the unit direction d:  u = 0.5 + atan2(d.x, -d.z) / (2 pi),  v = acos(clamp(d.y, -1, 1)) / pi;
+ *   texel column min(int(u W), W - 1), row min(int(v H), H - 1); nearest texel (no filtering), so that what a ray sees is what the
+ *   sampling pdf assumes.  A caller rotates the map by shifting its columns.
+ * Light mode 0: a radiance ray that misses returns the map's radiance (the reference's estimator otherwise; the map is not
+ *   light-sampled, params->areaLight still is).  Light mode 1: the map is also a light — importance-sampled by luminance
+ *   times sin(theta), chosen for a light sample with probability 0.5 beside emissive triangles (1 without; 0 for a black map),
+ *   MIS with BSDF sampling by the power heuristic.
+ * The map belongs to the context: it survives pt_set_scene, pt_update_vertices and pt_update_materials; under
+ * pt_create_multi every rank gets it.  While a map is set pt_launch runs the "ENV" kernel variants (pt_variant_name). */
+int pt_set_environment(pt_ctx* ctx, const float* rgb, uint32_t width, uint32_t height, pt_float3 scale);
+
 /* Arithmetic of the shading code (closest-hit, samplers, light sample, roulette, camera-ray set-up).
  *   PT_MATH_FAST (default): the arithmetic of the reference's own build.  /root/reference/CMakeLists.txt:267 compiles
  *      pathTracerPrograms.cu with nvcc --use_fast_math (-prec-div=false -prec-sqrt=false, sinf -> __sinf, cosf -> __cosf):

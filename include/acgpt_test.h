@@ -91,6 +91,10 @@ int pt_debug_node_order(pt_ctx* ctx, int mode);
  * records}, trace waves {exchange time / exchanges / records taken in, loop trips}. */
 int pt_debug_wf(pt_ctx* ctx, uint64_t* out);
 #endif
+/* The environment map's device functions (csrc/pt_environment.h, what the render kernels call) in the context's math mode, for n
+ * queries, HOST arrays.  op 0: unit direction {x, y, z} -> {r, g, b, texel index (-1 without a map)}; op 1: direction -> solid-angle
+ * pdf of the map's sampling; op 2: {u1, u2} in [0, 1)^2 -> {x, y, z, pdf} of the sampled direction (pdf 0: nothing to sample). */
+int pt_debug_environment(pt_ctx* ctx, int op, const float* in, size_t n, float* out);
 /* Sorted (morton, triangle) pairs of the last build, HOST outputs of n_tris. */
 int pt_read_morton(pt_ctx* ctx, uint32_t* codes_sorted, uint32_t* prims_sorted);
 
