@@ -74,6 +74,7 @@ assert C.sizeof(UpdateInfo) == 16
 UPDATE_REFIT, UPDATE_REBUILD, UPDATE_AUTO = 0, 1, 2                # pt_update_vertices
 UPDATE_AUTO_AREA_RATIO = 1.25                                      # PT_UPDATE_AUTO_AREA_RATIO
 MATH_IEEE, MATH_FAST = 0, 1                                        # pt_set_math_mode
+MATERIALS_REFERENCE, MATERIALS_MICROFACET = 0, 1                   # pt_set_material_model
 
 # every symbol include/acgpt.h declares (the drop-in boundary) ...
 ABI_SYMBOLS = [
@@ -81,11 +82,12 @@ ABI_SYMBOLS = [
     "pt_launch", "pt_launch_frames", "pt_resolve_framebuffer", "pt_set_partition", "pt_set_sample_chunks", "pt_set_light_mode", "pt_set_math_mode", "pt_set_scratch_limit", "pt_set_tuning",
     "pt_variant_name", "pt_variant_kernel", "pt_kernel_source_hash", "pt_set_stream", "pt_get_stats",
     "pt_trace_closest", "pt_trace_any", "pt_render_features", "pt_denoise", "pt_temporal_blend", "pt_temporal_blend_motion", "pt_update_vertices", "pt_update_materials", "pt_set_environment",
+    "pt_set_material_model",
     "pt_device_malloc", "pt_device_free", "pt_device_memset", "pt_copy_to_host", "pt_copy_to_device",
     "pt_host_malloc_mapped", "pt_host_free_mapped", "pt_abi_version",
 ]
 # ... and include/acgpt_test.h (test hooks and diagnostics; same library)
-TEST_SYMBOLS = ["pt_bench_traversal", "pt_selftest", "pt_debug_wave_times", "pt_debug_queue_progress", "pt_debug_window_moves", "pt_debug_queue_order", "pt_debug_pixel_classes", "pt_debug_row_spans", "pt_read_morton", "pt_debug_environment"]
+TEST_SYMBOLS = ["pt_bench_traversal", "pt_selftest", "pt_debug_wave_times", "pt_debug_queue_progress", "pt_debug_window_moves", "pt_debug_queue_order", "pt_debug_pixel_classes", "pt_debug_row_spans", "pt_read_morton", "pt_debug_environment", "pt_debug_microfacet"]
 
 _hip = None
 _host = None
@@ -173,6 +175,8 @@ def hip():
     L.pt_update_materials.argtypes = [vp, vp, sz, vp, sz, C.POINTER(UpdateInfo)]; L.pt_update_materials.restype = C.c_int
     L.pt_set_environment.argtypes = [vp, vp, C.c_uint32, C.c_uint32, Float3]; L.pt_set_environment.restype = C.c_int
     L.pt_debug_environment.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_debug_environment.restype = C.c_int
+    L.pt_set_material_model.argtypes = [vp, C.c_int]; L.pt_set_material_model.restype = C.c_int
+    L.pt_debug_microfacet.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_debug_microfacet.restype = C.c_int
     L.pt_bench_traversal.argtypes = [vp, vp, sz, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_float), vp]; L.pt_bench_traversal.restype = C.c_int
     L.pt_selftest.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_selftest.restype = C.c_int
     L.pt_debug_wave_times.argtypes = [vp, vp, sz]; L.pt_debug_wave_times.restype = C.c_int

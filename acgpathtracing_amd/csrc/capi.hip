@@ -59,6 +59,8 @@ struct pt_ctx {
     uint32_t n_lights = 0;
     float light_area = 0.0f;
     int light_mode = 0;                       // 0 the reference's estimator, 1 scene lights + MIS (pt_set_light_mode)
+    int material_model = PT_MATERIALS_REFERENCE;   // pt_set_material_model: the context's, kept across scene changes
+    float* d_alpha = nullptr;                 // GGX alpha per material (the GGX kernels' table, pt_microfacet.h), beside d_mats
     int math_mode = PT_MATH_FAST;             // arithmetic of the shading code (pt_set_math_mode): the reference's own build uses nvcc --use_fast_math
     uint32_t stack_entries = 8;
     int blocks_per_cu = 0;        // from the occupancy query for the current stack size
@@ -285,6 +287,7 @@ static void free_scene(pt_ctx* c)
 {
     ptd::free_lbvh(c->bvh);
     if (c->d_mats) { (void)hipFree(c->d_mats); c->d_mats = nullptr; }
+    if (c->d_alpha) { (void)hipFree(c->d_alpha); c->d_alpha = nullptr; }
     c->n_mats = 0;
     if (c->d_lights) { (void)hipFree(c->d_lights); c->d_lights = nullptr; }
     c->n_lights = 0; c->light_area = 0.0f;
@@ -453,21 +456,27 @@ static int upload_lights(pt_ctx* c, const float* verts_xyzw, const uint32_t* idx
     return put_lights(c, lights, run);
 }
 
-// the material table on the device, repacked (pt_device.h DevMaterial); reallocated only when the count changes
+// the material table on the device, repacked (pt_device.h DevMaterial), and the GGX alpha per material beside it (the microfacet
+// model, pt_set_material_model: roughness clamped to [0, 1], NaN as 0); reallocated only when the count changes
 static int upload_materials(pt_ctx* c, const pt_material* mats, size_t n_mats)
 {
     if (c->d_mats && c->n_mats != n_mats) { (void)hipFree(c->d_mats); c->d_mats = nullptr; }
+    if (c->d_alpha && c->n_mats != n_mats) { (void)hipFree(c->d_alpha); c->d_alpha = nullptr; }
     c->n_mats = 0;
     if (n_mats == 0) return 0;
     std::vector<ptd::DevMaterial> dm(n_mats);
+    std::vector<float> alpha(n_mats);
     for (size_t i = 0; i < n_mats; i++) {
         const pt_material& m = mats[i];
         uint32_t b = (uint32_t)m.bsdfType; float bf; memcpy(&bf, &b, 4);
         dm[i].kd_ior = make_float4(m.diffuse.x, m.diffuse.y, m.diffuse.z, m.ior);
         dm[i].ke_bsdf = make_float4(m.emission.x, m.emission.y, m.emission.z, bf);
+        alpha[i] = m.roughness > 0.0f ? fminf(m.roughness, 1.0f) : 0.0f;         // NaN and negative values: 0
     }
     if (!c->d_mats) CK(c, hipMalloc((void**)&c->d_mats, n_mats * sizeof(ptd::DevMaterial)));
     CK(c, hipMemcpy(c->d_mats, dm.data(), n_mats * sizeof(ptd::DevMaterial), hipMemcpyHostToDevice));
+    if (!c->d_alpha) CK(c, hipMalloc((void**)&c->d_alpha, n_mats * sizeof(float)));
+    CK(c, hipMemcpy(c->d_alpha, alpha.data(), n_mats * sizeof(float), hipMemcpyHostToDevice));
     c->n_mats = (uint32_t)n_mats;
     return 0;
 }
@@ -730,6 +739,15 @@ static int set_light_mode_one(pt_ctx* c, int mode)
     return 0;
 }
 
+static int set_material_model_one(pt_ctx* c, int model)
+{
+    if (!c) return fail(nullptr, "pt_set_material_model: null context");
+    if (model != PT_MATERIALS_REFERENCE && model != PT_MATERIALS_MICROFACET)
+        return fail(c, "pt_set_material_model: PT_MATERIALS_REFERENCE (0) or PT_MATERIALS_MICROFACET (1)");
+    c->material_model = model;
+    return 0;
+}
+
 static int set_math_mode_one(pt_ctx* c, int mode)
 {
     if (!c) return fail(nullptr, "pt_set_math_mode: null context");
@@ -789,6 +807,12 @@ PT_API int pt_set_light_mode(pt_ctx* c, int mode)
 {
     if (c && c->multi) return on_every_rank(c, [&](pt_ctx* r, int) { return set_light_mode_one(r, mode); });
     return set_light_mode_one(c, mode);
+}
+
+PT_API int pt_set_material_model(pt_ctx* c, int model)
+{
+    if (c && c->multi) return on_every_rank(c, [&](pt_ctx* r, int) { return set_material_model_one(r, model); });
+    return set_material_model_one(c, model);
 }
 
 // texels {r, g, b, 0} with the scale applied (empty: clear the map)
@@ -1012,6 +1036,8 @@ PT_API int pt_launch_frames(pt_ctx* c, const pt_params* p, uint32_t n_frames)
 {
     if (!c || !p) return fail(c, "pt_launch: null argument");
     if (n_frames < 1u || n_frames > 64u) return fail(c, "pt_launch_frames: n_frames must be in [1, 64]");
+    if (c->material_model == PT_MATERIALS_MICROFACET && c->light_mode != 1)     // every rank holds the same settings: refused on all or none
+        return fail(c, "pt_launch: the microfacet material model (pt_set_material_model 1) is part of light mode 1's estimator: call pt_set_light_mode(ctx, 1) or pt_set_material_model(ctx, 0)");
     Range range("acgpt: pt_launch_frames");
     return c->multi ? launch_frames_multi(c, p, n_frames) : launch_frames_single(c, p, n_frames);
 }
@@ -1147,7 +1173,10 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
     // variant pt_set_tuning named among the ENV rows stays).  Without one, pt_set_tuning may still name an ENV row: it sees a black map.
     const bool env = c->env.w != 0u;
     const bool env_row = c->variant == ptd::kVariantEnv || c->variant == ptd::kVariantEnvDeep;
-    int variant = c->light_mode == 1 ? (env ? ptd::kVariantLightsEnv : ptd::kVariantLights) : c->variant;
+    // light mode 1 under the microfacet model: the GGX twins of the LIGHTS rows
+    const bool ggx = c->light_mode == 1 && c->material_model == PT_MATERIALS_MICROFACET;
+    int variant = c->light_mode == 1 ? (ggx ? (env ? ptd::kVariantLightsGgxEnv : ptd::kVariantLightsGgx) : (env ? ptd::kVariantLightsEnv : ptd::kVariantLights))
+                                     : c->variant;
     if (c->light_mode != 1 && env && !env_row) {
         int w5_blocks = 0;
         const bool deep = c->bvh.n_tris > ptd::kWindowSceneTris ||
@@ -1269,6 +1298,8 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
     ptd::EnvArgs ea;
     ea.map = ptd::env_view(c->env);
     ea.p = c->env.pdf_scale > 0.0f ? (c->n_lights != 0u ? 0.5f : 1.0f) : 0.0f;
+    ptd::GgxArgs ga;
+    ga.alpha = c->d_alpha;
     a.queue_heads = c->d_queue;
     a.counters = c->d_counters;
     a.stack_entries = c->stack_entries;
@@ -1327,7 +1358,7 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
     CK(c, hipMemsetAsync(c->d_queue, 0, 8 * sizeof(uint32_t), c->stream));
     CK(c, hipMemsetAsync(c->d_counters, 0, (size_t)ptd::kCounterWords * sizeof(unsigned long long), c->stream));
     CK(c, hipEventRecord(c->ev0, c->stream));
-    { Range range("acgpt: render megakernel (launch_batch)"); CK(c, ptd::launch_render(variant, c->math_mode, a, grid, c->stream, &ea)); }
+    { Range range("acgpt: render megakernel (launch_batch)"); CK(c, ptd::launch_render(variant, c->math_mode, a, grid, c->stream, &ea, &ga)); }
     CK(c, hipEventRecord(c->ev1, c->stream));
     { Range range("acgpt: k_finalize"); CK(c, ptd::launch_finalize(a, c->stream)); }
     unsigned long long h[8], h_tail[2] = {0, 0};      // h_tail: culled camera rays; experiments build: workgroups of a wavefront kernel that gave up
@@ -1665,6 +1696,26 @@ PT_API int pt_debug_environment(pt_ctx* c, int op, const float* in, size_t n, fl
     if (d_in) (void)hipFree(d_in);
     if (d_out) (void)hipFree(d_out);
     if (e != hipSuccess) return fail(c, std::string("pt_debug_environment: ") + hipGetErrorString(e));
+    return 0;
+}
+
+PT_API int pt_debug_microfacet(pt_ctx* c, int op, const float* in, size_t n, float* out)
+{
+    static const int out_dw[2] = {8, 4};
+    if (!c || op < 0 || op > 1 || (n != 0 && (!in || !out)) || n > (1u << 24)) return fail(c, "pt_debug_microfacet: bad argument");
+    if (n == 0) return 0;
+    CK(c, hipSetDevice(c->device));
+    const size_t in_bytes = n * 9u * 4u, out_bytes = n * (size_t)out_dw[op] * 4u;
+    float* d_in = nullptr; float* d_out = nullptr;
+    hipError_t e = hipMalloc((void**)&d_in, in_bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_out, out_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = ptd::microfacet_debug(op, c->math_mode != 0 ? 1 : 0, d_in, (uint32_t)n, d_out, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(c, std::string("pt_debug_microfacet: ") + hipGetErrorString(e));
     return 0;
 }
 

@@ -343,11 +343,13 @@ __device__ __forceinline__ bool reaches_scene(const f3& D, const f3& elo, const 
 // compiler cannot see through (a zero made by an opaque instruction), so those values never live across the BVH loop.
 struct RenderArgsBox { RenderArgs a[1]; };
 struct RenderArgsEnvBox { RenderArgs a[1]; EnvArgs e[1]; };      // the ENV kernels' argument: RenderArgs at the same offsets, the map behind it
+struct RenderArgsGgxBox { RenderArgs a[1]; GgxArgs g[1]; };                   // k_render_ggx: the alpha table behind RenderArgs
+struct RenderArgsGgxEnvBox { RenderArgs a[1]; EnvArgs e[1]; GgxArgs g[1]; };  // k_render_ggx_env: the map, then the alpha table
 __device__ __forceinline__ uint32_t opaque_zero() { uint32_t z; asm volatile("s_mov_b32 %0, 0" : "=s"(z)); return z; }
 
 
 // ---- host-side interface of the kernel translation units --------------------------------------------------------------------
-typedef void (*RenderKernel)(const RenderArgsBox);      // (ENV rows: void (*)(const RenderArgsEnvBox), stored as this type and launched by address)
+typedef void (*RenderKernel)(const RenderArgsBox);      // (ENV and GGX rows: their own box types, stored as this type and launched by address)
 #ifdef ACGPT_EXPERIMENTS
 // workgroup-level wavefront kernels (render_wavefront.hip; measured, lost, experiments build only)
 struct WfDesc { RenderKernel k; int nt, ns, pool, stack_cap; const char* name; const char* kernel; RenderKernel k_fast; const char* kernel_fast; };

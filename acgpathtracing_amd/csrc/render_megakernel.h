@@ -35,8 +35,11 @@ constexpr int kVariantF16 = 5, kVariantF16Stats = 6, kVariantF16W5 = 7, kVariant
 // while a map is set — light mode 0: kVariantEnv, or kVariantEnvDeep by the criterion that sends a scene to kVariantF16W5Deep;
 // light mode 1: kVariantLightsEnv, which also samples the map
 constexpr int kVariantEnv = 10, kVariantEnvDeep = 11, kVariantLightsEnv = 12;
+// the twins of 8 and 12 with the microfacet material model (pt_set_material_model; k_render_ggx / k_render_ggx_env, render_pw.inc):
+// what pt_launch runs in light mode 1 under PT_MATERIALS_MICROFACET, without and with a map
+constexpr int kVariantLightsGgx = 13, kVariantLightsGgxEnv = 14;
 #ifdef ACGPT_EXPERIMENTS
-constexpr int kVariantWf = 13, kVariantWfStats = 14;      // experiments build: the workgroup-level wavefront kernel (render_wavefront.hip) and its twin with time stamps
+constexpr int kVariantWf = 15, kVariantWfStats = 16;      // experiments build: the workgroup-level wavefront kernel (render_wavefront.hip) and its twin with time stamps
 #endif
 constexpr int kDefaultVariant = kVariantF16W5;
 constexpr uint32_t kLargeSceneTris = 100000;
@@ -96,6 +99,10 @@ struct EnvArgs {
     EnvMap map;       // pt_environment.h; map.w == 0: no map (a black one)
     float  p;         // light mode 1: probability of a light sample going to the map (0 for a black map, 0.5 beside emissive triangles, 1 without)
 };
+// What the GGX kernels (k_render_ggx, k_render_ggx_env) take beside RenderArgs (and EnvArgs), in a box of their own (render_common.h)
+struct GgxArgs {
+    const float* alpha;   // [material] GGX alpha (the material's roughness clamped to [0, 1], NaN as 0; pt_set_scene / pt_update_materials)
+};
 constexpr float kOriginEps = 16.0f * 1.1920929e-7f;      // 16 * 2^-23
 
 int render_variant_count();
@@ -107,8 +114,13 @@ int render_variant_top_nodes(int variant);      // > 0: the variant stages that 
 int render_variant_stack_cap(int variant);      // 0 = the whole stack in LDS
 int render_variant_node_format(int variant);   // 0 fp32 two-child; 11 fp16 two-child as centre / half extent (the default); 7 / 8 / 9 fp16 two-child {lo, hi} (min-max / rotated / rotated, flags in the multipliers); experiments: 1/2/4 16-bit grid, 3 four-wide 8-bit, 10 / 12 shared-plane records
 hipError_t render_occupancy(int variant, int math, uint32_t stack_entries, uint32_t n_nodes, int* blocks_per_cu);
-hipError_t launch_render(int variant, int math, const RenderArgs& args, uint32_t grid_blocks, hipStream_t stream, const EnvArgs* env = nullptr);   // env: the map of an ENV variant (null: a black one)
-int render_variant_has_env(int variant);        // 1: an ENV row (k_render_env)
+hipError_t launch_render(int variant, int math, const RenderArgs& args, uint32_t grid_blocks, hipStream_t stream, const EnvArgs* env = nullptr,
+                         const GgxArgs* ggx = nullptr);   // env: the map of an ENV variant (null: a black one); ggx: the alpha table of a GGX variant (required there)
+int render_variant_has_env(int variant);        // 1: an ENV row (k_render_env, k_render_ggx_env)
+int render_variant_has_ggx(int variant);        // 1: a GGX row (k_render_ggx, k_render_ggx_env)
+// pt_debug_microfacet: op 0 {wo[3], alpha, ior, bsdf, u1, u2, u3} -> {wi[3], weight[3], pdf, lobe}, op 1 {wo[3], wi[3], alpha, ior, bsdf}
+// -> {f[3], pdf}; normal (0, 0, 1) face-forwarded to wo; math 0 IEEE, 1 fast (pt_microfacet.h)
+hipError_t microfacet_debug(int op, int math, const float* d_in, uint32_t n, float* d_out, hipStream_t stream);
 hipError_t launch_finalize(const RenderArgs& args, hipStream_t stream);
 hipError_t launch_resolve(const float4* accum, uint32_t* fb, uint32_t n, hipStream_t stream);
 hipError_t launch_keep_owned(float4* accum, uint32_t width, uint32_t height, int rank, int world, hipStream_t stream);

@@ -25,6 +25,7 @@
 // Item order inside the queue is the 8x4-tile order of sutil/WorkDistribution.h:60-81 for
 // (rank, world), which is also the multi-GPU partition.
 #include "render_common.h"
+#include "pt_microfacet.h"
 
 namespace ptd {
 
@@ -226,12 +227,22 @@ __device__ __forceinline__ void setup_ray(const f3& ro, const f3& rd, const QGri
 // INNER: 0 = stack entirely in LDS, nested branches; 1 = stack top cached in a register (the LDS read of
 // a pop is consumed one push/pop later, off the critical path) and child selection by selects; 2, 3 = the same with
 // that many node visits per trip through the loop control.
+#define RENDER_PW_GGX 0
 #define RENDER_PW_ENV 0
 #include "render_pw.inc"        // k_render_pw
 #undef RENDER_PW_ENV
 #define RENDER_PW_ENV 1
 #include "render_pw.inc"        // k_render_env: the same kernel with the environment map
 #undef RENDER_PW_ENV
+#undef RENDER_PW_GGX
+#define RENDER_PW_GGX 1
+#define RENDER_PW_ENV 0
+#include "render_pw.inc"        // k_render_ggx: the LIGHTS kernel with the microfacet material model
+#undef RENDER_PW_ENV
+#define RENDER_PW_ENV 1
+#include "render_pw.inc"        // k_render_ggx_env: ... and the environment map
+#undef RENDER_PW_ENV
+#undef RENDER_PW_GGX
 
 __global__ void k_resolve(const float4* __restrict__ accum, uint32_t* __restrict__ fb, uint32_t n)
 {
@@ -626,7 +637,7 @@ hipError_t trace_stream_occupancy(int fmt, uint32_t stack_entries, int* blocks_p
 // ---- host-side launchers ------------------------------------------------------------------
 // k / kernel: the instantiation with IEEE arithmetic in the shading code; k_fast / kernel_fast: its twin with the arithmetic of the
 // reference's own build (pt_set_math_mode; nullptr: the variant exists at the IEEE level only — experiment rows)
-struct VariantDesc { RenderKernel k; int threads; int node_fmt; const char* name; int stack_cap = 0; const char* kernel = ""; int wf = -1; int top_n = 0; RenderKernel k_fast = nullptr; const char* kernel_fast = ""; bool env = false; };   // env: k_render_env (argument RenderArgsEnvBox); wf >= 0 (experiments build only): index into render_wavefront.hip's table
+struct VariantDesc { RenderKernel k; int threads; int node_fmt; const char* name; int stack_cap = 0; const char* kernel = ""; int wf = -1; int top_n = 0; RenderKernel k_fast = nullptr; const char* kernel_fast = ""; bool env = false; bool ggx = false; };   // env: k_render_env (argument RenderArgsEnvBox); ggx: k_render_ggx (RenderArgsGgxBox), with env k_render_ggx_env (RenderArgsGgxEnvBox); wf >= 0 (experiments build only): index into render_wavefront.hip's table
 
 // Render kernel variants.  0: segment-synchronous (fp32 nodes).  Others: persistent traversal
 // <SHADE_K, LEAF_K, NODE_FMT, THREADS, MINW, STATS, DIAG, INNER, LEAVES, LIGHTS, STACK_CAP, TOPN>.  The product library carries the
@@ -643,6 +654,15 @@ struct VariantDesc { RenderKernel k; int threads; int node_fmt; const char* name
 #define PEN(...) "k_render_env<" #__VA_ARGS__ ">"
 #define ROW_ENV(threads, fmt, name, cap, ...) {reinterpret_cast<RenderKernel>(&PE(__VA_ARGS__, 0)), threads, fmt, name, cap, PEN(__VA_ARGS__, 0), -1, 0, \
                                                reinterpret_cast<RenderKernel>(&PE(__VA_ARGS__, 1)), PEN(__VA_ARGS__, 1), true}
+// ... and the twins of row 8 with the microfacet material model (k_render_ggx, k_render_ggx_env: the same twelve arguments)
+#define PG(...) k_render_ggx<__VA_ARGS__>
+#define PGN(...) "k_render_ggx<" #__VA_ARGS__ ">"
+#define ROW_GGX(threads, fmt, name, cap, ...) {reinterpret_cast<RenderKernel>(&PG(__VA_ARGS__, 0)), threads, fmt, name, cap, PGN(__VA_ARGS__, 0), -1, 0, \
+                                               reinterpret_cast<RenderKernel>(&PG(__VA_ARGS__, 1)), PGN(__VA_ARGS__, 1), false, true}
+#define PGE(...) k_render_ggx_env<__VA_ARGS__>
+#define PGEN(...) "k_render_ggx_env<" #__VA_ARGS__ ">"
+#define ROW_GGX_ENV(threads, fmt, name, cap, ...) {reinterpret_cast<RenderKernel>(&PGE(__VA_ARGS__, 0)), threads, fmt, name, cap, PGEN(__VA_ARGS__, 0), -1, 0, \
+                                                   reinterpret_cast<RenderKernel>(&PGE(__VA_ARGS__, 1)), PGEN(__VA_ARGS__, 1), true, true}
 static const VariantDesc kVariants[] = {
     {k_render<0>, 256, 0, "sync fp32-nodes", 0, "k_render<0>", -1, 0, k_render<1>, "k_render<1>"},
     ROW(256, 0, "pw K44 L16 fp32 nodes w4, register stack top, two visits and two triangle tests per loop trip", 0, 44, 16, 0, 256, 4, false, 0, 2, 2, false, 0, 0),
@@ -658,6 +678,9 @@ static const VariantDesc kVariants[] = {
     ROW_ENV(256, 11, "ENV the five-wave fp16 kernel (row 7) with an environment map on miss", 0, 40, 16, 11, 256, 5, false, 0, 6, 2, false, 0, 0),
     ROW_ENV(256, 11, "ENV deep: the large-scene / deep-tree kernel (row 9) with an environment map on miss", -16, 24, 16, 11, 256, 5, false, 0, 5, 2, false, -16, 0),
     ROW_ENV(256, 11, "LIGHTS ENV scene-driven area lights + an importance-sampled environment map, MIS (light mode 1; row 8's twin)", 0, 44, 16, 11, 256, 4, false, 0, 5, 2, true, 0, 0),
+    // 13, 14: rows 8 and 12 with the microfacet material model (pt_set_material_model)
+    ROW_GGX(256, 11, "LIGHTS GGX scene-driven area lights + MIS with rough GGX metal and glass (light mode 1, PT_MATERIALS_MICROFACET; row 8's twin)", 0, 44, 16, 11, 256, 4, false, 0, 5, 2, true, 0, 0),
+    ROW_GGX_ENV(256, 11, "LIGHTS GGX ENV area lights + the environment map, MIS, rough GGX metal and glass (light mode 1, PT_MATERIALS_MICROFACET; row 12's twin)", 0, 44, 16, 11, 256, 4, false, 0, 5, 2, true, 0, 0),
 #ifdef ACGPT_EXPERIMENTS
 #include "render_experiments.inc"
 #endif
@@ -690,6 +713,7 @@ const char* render_variant_kernel(int v, int math)
     return (math != 0 && d.k_fast != nullptr) ? d.kernel_fast : d.kernel;
 }
 int render_variant_has_env(int v) { return (v >= 0 && v < render_variant_count()) ? (int)kVariants[v].env : 0; }
+int render_variant_has_ggx(int v) { return (v >= 0 && v < render_variant_count()) ? (int)kVariants[v].ggx : 0; }
 int render_variant_has_fast_math(int v) { return (v >= 0 && v < render_variant_count()) ? variant_desc(v).k_fast != nullptr : 0; }
 
 static size_t variant_lds(const VariantDesc& d, uint32_t stack_entries, uint32_t n_nodes)
@@ -720,12 +744,28 @@ hipError_t render_occupancy(int variant, int math, uint32_t stack_entries, uint3
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (const void*)d.k, d.threads, lds);
 }
 
-hipError_t launch_render(int variant, int math, const RenderArgs& args, uint32_t grid_blocks, hipStream_t stream, const EnvArgs* env)
+hipError_t launch_render(int variant, int math, const RenderArgs& args, uint32_t grid_blocks, hipStream_t stream, const EnvArgs* env, const GgxArgs* ggx)
 {
     if (variant < 0 || variant >= render_variant_count()) return hipErrorInvalidValue;
     VariantDesc d = variant_desc(variant);
     d.k = variant_kernel(d, math);
     const size_t lds = variant_lds(d, args.stack_entries, args.n_lds_nodes);
+    if (d.ggx) {        // k_render_ggx / k_render_ggx_env: the alpha table behind RenderArgs (and the map)
+        if (!ggx || (!ggx->alpha && args.scene.n_mats != 0u)) return hipErrorInvalidValue;
+        if (d.env) {
+            RenderArgsGgxEnvBox gbox;
+            gbox.a[0] = args;
+            gbox.e[0] = env ? *env : EnvArgs{};
+            gbox.g[0] = *ggx;
+            void* kargs[] = {&gbox};
+            return hipLaunchKernel((const void*)d.k, dim3(grid_blocks), dim3(d.threads), kargs, lds, stream);
+        }
+        RenderArgsGgxBox gbox;
+        gbox.a[0] = args;
+        gbox.g[0] = *ggx;
+        void* kargs[] = {&gbox};
+        return hipLaunchKernel((const void*)d.k, dim3(grid_blocks), dim3(d.threads), kargs, lds, stream);
+    }
     if (d.env) {        // k_render_env: the same RenderArgs with the map behind them (launched by address: the table holds it as a RenderKernel)
         RenderArgsEnvBox ebox;
         ebox.a[0] = args;

@@ -1,11 +1,20 @@
-// render_pw.inc — the body of the persistent path-trace kernel (render_megakernel.hip), included there twice:
+// render_pw.inc — the body of the persistent path-trace kernel (render_megakernel.hip), included there four times:
 //   RENDER_PW_ENV 0: k_render_pw(const RenderArgsBox), the kernels without an environment map;
 //   RENDER_PW_ENV 1: k_render_env(const RenderArgsEnvBox), the same kernel with the map of pt_set_environment (pt_environment.h) on
 //                    miss: a radiance ray that leaves the scene and a camera ray the cull settles see the map, the pixel class
 //                    "outside" is not applied (its pixels see the map too); with LIGHTS the map is also a light (shade_hit_lights).
-// Two kernels from one text rather than one kernel template with a flag, so that k_render_pw is compiled exactly as it was before
+//   RENDER_PW_GGX 1: k_render_ggx(const RenderArgsGgxBox) and, with RENDER_PW_ENV 1, k_render_ggx_env(const RenderArgsGgxEnvBox):
+//                    the LIGHTS kernels with the microfacet material model (pt_set_material_model; shade_hit_micro, pt_microfacet.h),
+//                    the per-material alpha behind RenderArgs (and the map).
+// Several kernels from one text rather than one kernel template with a flag, so that k_render_pw is compiled exactly as it was before
 // the map existed (an inlined body behind a wrapper, or a larger RenderArgs, changes its schedule).
-#if RENDER_PW_ENV
+#if RENDER_PW_GGX && RENDER_PW_ENV
+#define RENDER_PW_KERNEL k_render_ggx_env
+#define RENDER_PW_BOX RenderArgsGgxEnvBox
+#elif RENDER_PW_GGX
+#define RENDER_PW_KERNEL k_render_ggx
+#define RENDER_PW_BOX RenderArgsGgxBox
+#elif RENDER_PW_ENV
 #define RENDER_PW_KERNEL k_render_env
 #define RENDER_PW_BOX RenderArgsEnvBox
 #else
@@ -168,7 +177,14 @@ RENDER_PW_KERNEL(const RENDER_PW_BOX B)
                 bool want_shadow = false;
                 f3 P, L; float Ldist;
                 if (best_slot >= 0) {
-#if RENDER_PW_ENV
+#if RENDER_PW_GGX && RENDER_PW_ENV
+                    if (LIGHTS) want_shadow = shade_hit_micro<FM, true>(sc, late, ro, rd, best_t, best_slot, depth, pseed, att, prev_pdf, pd, P, L, Ldist,
+                                                                        [&]() -> const GgxArgs& { return B.g[opaque_zero()]; },
+                                                                        [&]() -> const EnvArgs& { return B.e[opaque_zero()]; });
+#elif RENDER_PW_GGX
+                    if (LIGHTS) want_shadow = shade_hit_micro<FM>(sc, late, ro, rd, best_t, best_slot, depth, pseed, att, prev_pdf, pd, P, L, Ldist,
+                                                                  [&]() -> const GgxArgs& { return B.g[opaque_zero()]; });
+#elif RENDER_PW_ENV
                     if (LIGHTS) want_shadow = shade_hit_lights<FM, true>(sc, late, ro, rd, best_t, best_slot, depth, pseed, att, prev_pdf, pd, P, L, Ldist,
                                                                          [&]() -> const EnvArgs& { return B.e[opaque_zero()]; });
 #else

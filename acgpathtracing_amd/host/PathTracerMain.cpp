@@ -12,7 +12,9 @@
 //              [--gpus N] [--multi] [--save-accum file] [--restore-accum file] [--light-mode 0|1] [--math fast|ieee]
 //              [--denoise N] [--history-out file] [--history-in file] [--move material:dx,dy,dz [--move-history]]
 //              [--set-material name:kd=r,g,b[,ke=r,g,b][,bsdf=diffuse|metal|glass][,ior=x] ...]
-//              [--env map.hdr|map.pfm [--env-scale s]] [--no-area-light]
+//              [--env map.hdr|map.pfm [--env-scale s]] [--no-area-light] [--materials reference|microfacet]
+// --materials microfacet (with --light-mode 1): metal and glass honour the MTL's Pr as rough GGX BSDFs (pt_set_material_model); the
+// default, reference, is the reference's materials.
 // --env: an environment map (Radiance .hdr or .pfm, latitude-longitude, top row = +Y) that rays leaving the scene see, scaled by
 // --env-scale (default 1); in light mode 1 it is importance-sampled as a light (pt_set_environment).  --no-area-light zeroes
 // params.areaLight.emission, so that a model can be lit by the map alone in light mode 0.
@@ -260,20 +262,21 @@ static std::string denoisedName(const std::string& out) { return suffixedName(ou
 
 // ---- temporal history (--history-out, --history-in) -----------------------------------------------------------------------
 struct HistoryFile {
-    uint32_t hdr[8] = {};            // width, height, maxDepth, direct lighting, importance sampling, light mode, math mode, triangles
+    uint32_t hdr[8] = {};            // width, height, maxDepth, direct lighting, importance sampling, light mode (| material model << 8), math mode, triangles
     float camera[12] = {};           // eye, U, V, W
     std::vector<float> data;         // float4[width * height] {linear rgb, samples}
 };
 static const char kHistoryMagic[8] = {'A', 'C', 'G', 'P', 'T', 'H', 'S', 'T'};
 
 // what a history of this run's view records about it
-static HistoryFile historyOfRun(PathTracerState& state, int light_mode, int math_mode)
+// (the material model is folded into bit 8 of the light-mode word: 0 for the reference's materials, so such files are as before)
+static HistoryFile historyOfRun(PathTracerState& state, int light_mode, int math_mode, int material_model)
 {
     pt_bvh_info bi;
     PT_CHECK(state.context, pt_get_bvh_info(state.context, &bi));
     const pt_params& p = state.params;
     HistoryFile h;
-    const uint32_t hdr[8] = {p.width, p.height, p.maxDepth, (uint32_t)p.useDirectLighting, (uint32_t)p.useImportanceSampling, (uint32_t)light_mode,
+    const uint32_t hdr[8] = {p.width, p.height, p.maxDepth, (uint32_t)p.useDirectLighting, (uint32_t)p.useImportanceSampling, (uint32_t)light_mode | ((uint32_t)material_model << 8),
                              (uint32_t)math_mode, bi.n_tris};
     memcpy(h.hdr, hdr, sizeof(hdr));
     const pt_float3 cam[4] = {p.cameraEye, p.cameraU, p.cameraV, p.cameraW};
@@ -503,7 +506,7 @@ int main(int argc, char** argv)
     bool zero_copy = false, move_history = false, no_area_light = false;
     std::string env_path;
     float env_scale = 1.0f;
-    int orbit_dx = 0, orbit_dy = 0, zoom_steps = 0, sample_chunks = 0, build_mode = 1, fuse = 1, light_mode = 0, math_mode = PT_MATH_FAST;
+    int orbit_dx = 0, orbit_dy = 0, zoom_steps = 0, sample_chunks = 0, build_mode = 1, fuse = 1, light_mode = 0, math_mode = PT_MATH_FAST, material_model = PT_MATERIALS_REFERENCE;
     PathTracerState state;
     state.params.useDirectLighting = false;
     state.params.useImportanceSampling = false;
@@ -543,6 +546,12 @@ int main(int argc, char** argv)
         else if (a == "--env") env_path = next();
         else if (a == "--env-scale") env_scale = (float)atof(next());
         else if (a == "--no-area-light") no_area_light = true;
+        else if (a == "--materials") {
+            const std::string m = next();
+            if (m == "reference") material_model = PT_MATERIALS_REFERENCE;
+            else if (m == "microfacet") material_model = PT_MATERIALS_MICROFACET;
+            else { std::cerr << "--materials reference|microfacet" << std::endl; return 2; }
+        }
         else if (a == "--light-mode") light_mode = atoi(next());      // 0 = the reference's hard-coded rectangle (:154-158), 1 = the OBJ's emissive triangles + MIS
         else { std::cerr << "unknown option " << a << std::endl; return 2; }
     }
@@ -611,6 +620,7 @@ int main(int argc, char** argv)
         PT_CHECK(state.context, pt_set_build_mode(state.context, build_mode));
         PT_CHECK(state.context, pt_set_sample_chunks(state.context, sample_chunks));
         PT_CHECK(state.context, pt_set_light_mode(state.context, light_mode));
+        PT_CHECK(state.context, pt_set_material_model(state.context, material_model));
         PT_CHECK(state.context, pt_set_math_mode(state.context, math_mode));
         if (!env_path.empty()) {
             std::vector<float> env_rgb;
@@ -636,7 +646,7 @@ int main(int argc, char** argv)
         HistoryFile history;
         if (!history_in.empty()) {              // refused before any frame is rendered
             history = readHistory(history_in);
-            const std::string why = historyMismatch(history, historyOfRun(state, light_mode, math_mode));
+            const std::string why = historyMismatch(history, historyOfRun(state, light_mode, math_mode, material_model));
             if (!why.empty()) throw Exception(history_in + " was made under other settings: " + why);
         }
         if (!restore_accum.empty()) {
@@ -680,7 +690,7 @@ int main(int argc, char** argv)
             if (!save_accum.empty()) saveAccumulation(state, save_accum);
             if (denoise_iters > 0) saveDenoised(state, denoisedName(out), (uint32_t)denoise_iters);
             if (!history_in.empty() || !history_out.empty()) {
-                HistoryFile mine = historyOfRun(state, light_mode, math_mode);      // the settings at the end: --keys may have changed them
+                HistoryFile mine = historyOfRun(state, light_mode, math_mode, material_model);      // the settings at the end: --keys may have changed them
                 if (!history_in.empty()) {
                     const std::string why = historyMismatch(history, mine);
                     if (!why.empty()) throw Exception(history_in + " was made under other settings: " + why);

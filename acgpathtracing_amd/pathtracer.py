@@ -351,6 +351,16 @@ def setLightMode(state, mode):
     state.refreshAccumulationBuffer = True
 
 
+def setMaterialModel(state, model):
+    """0 / "reference": the reference's materials (the default).  1 / "microfacet": metal and glass honour pt_material.roughness as
+    rough GGX BSDFs, light-sampled with MIS (include/acgpt.h pt_set_material_model); part of light mode 1: a launch in light mode 0
+    under model 1 is refused."""
+    m = {"reference": _native.MATERIALS_REFERENCE, "microfacet": _native.MATERIALS_MICROFACET}.get(model, model)
+    _check(state.context, _native.hip().pt_set_material_model(state.context, int(m)), "pt_set_material_model")
+    state._material_model = int(m)
+    state.refreshAccumulationBuffer = True
+
+
 def readHDR(path):
     """Radiance .hdr (RGBE, flat or run-length encoded scanlines, "-Y H +X W"): float32 [H, W, 3], row 0 = the top row.
     The same reader as host/ImageIO.cpp loadHDR."""
@@ -659,7 +669,7 @@ class TemporalHistory:
         p = state.params
         scene = ("scene", state._scene_serial) if self.motion else _native.hip().pt_scene_handle(state.context)
         return (scene, getattr(state, "_mats_serial", 0), int(p.maxDepth), int(p.useDirectLighting), int(p.useImportanceSampling),
-                getattr(state, "_light_mode", 0), getattr(state, "_math_mode", _native.MATH_FAST))
+                getattr(state, "_light_mode", 0) | (getattr(state, "_material_model", 0) << 8), getattr(state, "_math_mode", _native.MATH_FAST))
 
     def _key_of(self, state):
         p = state.params

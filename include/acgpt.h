@@ -299,6 +299,38 @@ int pt_set_light_mode(pt_ctx* ctx, int mode);
  * pt_create_multi every rank gets it.  While a map is set pt_launch runs the "ENV" kernel variants (pt_variant_name). */
 int pt_set_environment(pt_ctx* ctx, const float* rgb, uint32_t width, uint32_t height, pt_float3 scale);
 
+/* Material model of light mode 1 (opt-in; the default, PT_MATERIALS_REFERENCE, changes nothing).
+ *   PT_MATERIALS_REFERENCE (0): the reference's materials — the conductor samples its literal GGX lobe of width 0.2 with weight
+ *      F Kd, glass is perfectly smooth; pt_material.roughness is not read.
+ *   PT_MATERIALS_MICROFACET (1): metal and glass honour pt_material.roughness as isotropic GGX microfacet BSDFs, light-sampled and
+ *      combined with BSDF sampling by the power heuristic, against emissive triangles and the environment map.  The model
+ *      (tests/microfacet_ref.py states it in NumPy):
+ *      - N is light mode 1's face-forwarded geometric normal, the tangent frame onb_transform's.  alpha = roughness clamped to
+ *        [0, 1] (NaN: 0), the meaning of the reference's sampleGGX parameter; alpha < 1e-3 is smooth.  D is GGX, G1 Smith,
+ *        G2 the height-correlated 1 / (1 + Lambda(wo) + Lambda(wi)); half vectors from Heitz 2018's visible-normal sampling.
+ *      - DIFFUSE: light mode 1's code, the same draws and bits.
+ *      - METALLIC, rough: wi reflected about the sampled h; weight F Kd G2 / G1(wo) with the reference's conductor Fresnel
+ *        F(wo.h) (eta (1.45, 0.7, 1.55), k (3, 2.2, 3.5)); pdf G1(wo) D(h) / (4 cos_o); a wi below the plane ends the path.
+ *        A light sample (triangles or map, chosen as at a diffuse vertex) is weighed against the BRDF's pdf.  Draws 2 + 2.
+ *        Smooth: a mirror about N with weight F(cos_o) Kd, the same draws, no light sample (an emitter seen next counts in full).
+ *      - REFRACTION, rough: Walter et al. 2007 with the material's ior (eta swapped on exit as fr_dielectric swaps it); reflection
+ *        with probability F = fr_dielectric(wo.h) (1 under total internal reflection), else refraction about h; weight Kd G2 / G1(wo)
+ *        for both lobes.  There is no 1 / eta^2 radiance factor, as smooth glass carries none: the BTDF is normalised as
+ *        f = Kd (1 - F) D G2 eta^2 |wo.h| |wi.h| / (cos_o |cos_i| (wo.h + eta wi.h)^2), so that f |cos_i| / pdf is the sampled
+ *        weight and rough glass tends to smooth glass as alpha goes to 0.  Light samples on either side use the matching lobe.
+ *        Draws 3 + 2.  Smooth: light mode 1's glass, the same single draw and bits.
+ *      - After a rough vertex that took a light sample, an emitter or the map hit by the sampled direction is weighed by the
+ *        power heuristic against its pdf (lobe choice included), as after a diffuse vertex.  Emitters, the roulette,
+ *        pt_render_features and the temporal blends are unchanged.  pt_material.metallic is not used.
+ *   Model 1 is part of light mode 1's estimator: pt_launch / pt_launch_frames with model 1 in light mode 0 are refused before any
+ *   device work (the buffers are left as they were).  Unknown models are refused.  The model belongs to the context: it survives
+ *   pt_set_scene, pt_update_vertices and pt_update_materials; under pt_create_multi every rank gets it.  Memory: one float of alpha
+ *   per material on the device, uploaded with the material table and, like it, not counted in pt_bvh_info.device_bytes.  Under
+ *   model 1 pt_launch runs the "LIGHTS GGX" kernel variants (pt_variant_name). */
+#define PT_MATERIALS_REFERENCE 0
+#define PT_MATERIALS_MICROFACET 1
+int pt_set_material_model(pt_ctx* ctx, int model);
+
 /* Arithmetic of the shading code (closest-hit, samplers, light sample, roulette, camera-ray set-up).
  *   PT_MATH_FAST (default): the arithmetic of the reference's own build.  /root/reference/CMakeLists.txt:267 compiles
  *      pathTracerPrograms.cu with nvcc --use_fast_math (-prec-div=false -prec-sqrt=false, sinf -> __sinf, cosf -> __cosf):

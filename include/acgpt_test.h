@@ -95,6 +95,11 @@ int pt_debug_wf(pt_ctx* ctx, uint64_t* out);
  * queries, HOST arrays.  op 0: unit direction {x, y, z} -> {r, g, b, texel index (-1 without a map)}; op 1: direction -> solid-angle
  * pdf of the map's sampling; op 2: {u1, u2} in [0, 1)^2 -> {x, y, z, pdf} of the sampled direction (pdf 0: nothing to sample). */
 int pt_debug_environment(pt_ctx* ctx, int op, const float* in, size_t n, float* out);
+/* The microfacet BSDF of pt_set_material_model(1) (csrc/pt_microfacet.h) in the context's math mode, for n items of 9 floats,
+ * normal (0, 0, 1) face-forwarded to wo (wo.z < 0: leaving a dielectric's inside):
+ *   op 0: {wo[3], alpha, ior, bsdf, u1, u2, u3} -> {wi[3], weight[3], pdf, lobe (0 ended, 1 reflection, 2 transmission)}
+ *   op 1: {wo[3], wi[3], alpha, ior, bsdf} -> {f[3], pdf}.  HOST arrays. */
+int pt_debug_microfacet(pt_ctx* ctx, int op, const float* in, size_t n, float* out);
 /* Sorted (morton, triangle) pairs of the last build, HOST outputs of n_tris. */
 int pt_read_morton(pt_ctx* ctx, uint32_t* codes_sorted, uint32_t* prims_sorted);
 
