@@ -37,12 +37,18 @@
  *   occlusion          any triangle hit inside (tmin,tmax) occludes.
  * The GPU kernels must reproduce exactly these three definitions bit for bit.
  *
+ * Beyond the reference, opt-in and off by default (a scene without them computes what it did before they existed): light mode 1
+ * (closesthit_scene_lights), an environment map (orc_scene_set_environment) and the microfacet material model
+ * (orc_scene_set_material_model).  Their maths are tests/env_ref.py and tests/microfacet_ref.py, to which
+ * tests/test_oracle_env_ggx.py pins these functions.
+ *
  * Build: see oracle/Makefile.  -ffp-contract=off is REQUIRED (the only fused operations
  * are the explicit __builtin_fmaf calls).
  */
 #include <stdint.h>
 #include <stddef.h>
 #include <math.h>
+#include <cmath>
 #include <string.h>
 #include <stdlib.h>
 #include <atomic>
@@ -277,6 +283,14 @@ struct BNode { float lo[3], hi[3]; uint32_t left, right, first, count; };  /* co
  * the running sum of the areas up to and including this one (the selection CDF). */
 struct LightTri { f3 v0, e1, e2, n, Ke; float area, cdf; };
 
+/* An environment map (NOT the reference: pt_set_environment, include/acgpt.h).  texels: {r, g, b, weight} with the scale applied, row 0
+ * the +Y pole; marg[h] / cond[h][w]: the normalised inclusive scans of the row totals and of each row's weights; w == 0: no map. */
+struct EnvMapH {
+    std::vector<float> texels, marg, cond;
+    uint32_t w = 0, h = 0;
+    float total = 0.0f, pdf_scale = 0.0f;
+};
+
 struct Scene {
     std::vector<Tri> tris;
     std::vector<uint32_t> mat_ids;
@@ -285,6 +299,10 @@ struct Scene {
     std::vector<uint32_t> order;   /* leaf triangle order */
     std::vector<LightTri> lights;  /* emissive triangles in triangle order */
     int light_mode;                /* 0 = the reference's estimator (hard-coded rectangle, double counting); 1 = scene lights + MIS */
+    EnvMapH env;                   /* orc_scene_set_environment */
+    float p_env;                   /* light mode 1: probability that a light sample goes to the map (0: no map or a black one) */
+    int material_model;            /* light mode 1: 0 = the reference's materials, 1 = GGX metal and glass (orc_scene_set_material_model) */
+    std::vector<float> alpha;      /* GGX alpha per material: roughness clamped to [0, 1], NaN and negative values as 0 */
 };
 
 static void tri_bounds(const Tri& t, float lo[3], float hi[3])
@@ -537,6 +555,247 @@ static inline void closesthit(const Scene& sc, const pt_params& params, int use_
     }
 }
 
+/* ------------------------------------------------------- environment map (NOT the reference) ----
+ * The maths of tests/env_ref.py (which tests/test_oracle_env_ggx.py pins these functions to); float32 operations in the order the
+ * device kernels use at the IEEE level, so that a render can match theirs bit for bit. */
+static const float kInv2PIf = 0.159154943091895336f, kInvPIf = 0.318309886183790672f;
+
+/* env_ref.block_scan: 256 runs of ceil(n / 256) values summed in order, Hillis-Steele over the run sums, then each run's values added
+ * in order to the sum of the runs before it; normalised by the total (a zero total: the uniform CDF (i + 1) / n).  Returns the total. */
+static float env_block_scan(const float* vals, uint32_t n, float* out)
+{
+    const uint32_t T = 256, run = (n + T - 1) / T;
+    float sums[256];
+    for (uint32_t t = 0; t < T; t++) {
+        const uint32_t b = std::min(t * run, n), e = std::min(b + run, n);
+        float s = 0.0f;
+        for (uint32_t i = b; i < e; i++) s += vals[i];
+        sums[t] = s;
+    }
+    for (uint32_t off = 1; off < T; off <<= 1) {
+        float old[256];
+        memcpy(old, sums, sizeof(old));
+        for (uint32_t t = off; t < T; t++) sums[t] = old[t] + old[t - off];
+    }
+    const float total = sums[T - 1];
+    for (uint32_t t = 0; t < T; t++) {
+        const uint32_t b = std::min(t * run, n), e = std::min(b + run, n);
+        float acc = t ? sums[t - 1] : 0.0f;
+        for (uint32_t i = b; i < e; i++) {
+            acc += vals[i];
+            out[i] = total > 0.0f ? acc / total : (float)(i + 1) / (float)n;
+        }
+    }
+    return total;
+}
+
+/* texels times scale; weight = lum(rgb) * sin(pi (row + 0.5) / h), the sine in double rounded to float; the CDFs; pdf_scale =
+ * w h / (2 pi^2 total) in double (0 for a black map) */
+static void env_build(EnvMapH& E, const float* rgb, uint32_t w, uint32_t h, const float* scale3)
+{
+    const float sx = scale3 ? scale3[0] : 1.0f, sy = scale3 ? scale3[1] : 1.0f, sz = scale3 ? scale3[2] : 1.0f;
+    E.w = w; E.h = h;
+    E.texels.assign((size_t)w * h * 4, 0.0f);
+    E.cond.assign((size_t)w * h, 0.0f);
+    E.marg.assign(h, 0.0f);
+    std::vector<float> weight(w), row_total(h);
+    for (uint32_t r = 0; r < h; r++) {
+        const float s = (float)sin(M_PI * ((double)r + 0.5) / (double)h);
+        for (uint32_t c = 0; c < w; c++) {
+            const size_t i = (size_t)r * w + c;
+            float* t = &E.texels[4 * i];
+            t[0] = rgb[3 * i] * sx; t[1] = rgb[3 * i + 1] * sy; t[2] = rgb[3 * i + 2] * sz;
+            t[3] = (0.2126f * t[0] + 0.7152f * t[1] + 0.0722f * t[2]) * s;
+            weight[c] = t[3];
+        }
+        row_total[r] = env_block_scan(weight.data(), w, &E.cond[(size_t)r * w]);
+    }
+    E.total = env_block_scan(row_total.data(), h, E.marg.data());
+    E.pdf_scale = E.total > 0.0f ? (float)((double)w * (double)h / (2.0 * M_PI * M_PI * (double)E.total)) : 0.0f;
+    if (!std::isfinite(E.pdf_scale)) E.pdf_scale = 0.0f;
+}
+
+/* u = 0.5 + atan2(d.x, -d.z) / (2 pi), v = acos(d.y) / pi; the texel that holds (u, v) */
+static inline uint32_t env_texel(const EnvMapH& E, const f3& d)
+{
+    const float u = 0.5f + atan2f(d.x, -d.z) * kInv2PIf;
+    const float v = acosf(clampf(d.y, -1.0f, 1.0f)) * kInvPIf;
+    const int col = std::min(std::max((int)(u * (float)E.w), 0), (int)E.w - 1);
+    const int row = std::min(std::max((int)(v * (float)E.h), 0), (int)E.h - 1);
+    return (uint32_t)row * E.w + (uint32_t)col;
+}
+static inline f3 env_eval(const EnvMapH& E, const f3& d)
+{
+    if (E.w == 0) return mk(0.0f);
+    const float* t = &E.texels[4 * (size_t)env_texel(E, d)];
+    return mk(t[0], t[1], t[2]);
+}
+static inline float env_pdf_weight(float w, float sin_theta, float pdf_scale) { return sin_theta > 0.0f ? (w * pdf_scale) / sin_theta : 0.0f; }
+/* solid-angle pdf of env_sample for d: weight * pdf_scale / sin(theta), sin(theta) = sqrt((1 - y)(1 + y)) */
+static inline float env_pdf(const EnvMapH& E, const f3& d)
+{
+    if (E.w == 0 || !(E.pdf_scale > 0.0f)) return 0.0f;
+    const float w = E.texels[4 * (size_t)env_texel(E, d) + 3];
+    return env_pdf_weight(w, sqrtf(fmaxf(0.0f, (1.0f - d.y) * (1.0f + d.y))), E.pdf_scale);
+}
+/* the bin of x: the first k with cdf[k] > x (n - 1 if none), and where x lies inside it */
+static inline uint32_t env_search(const float* cdf, uint32_t n, float x)
+{
+    uint32_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (cdf[mid] > x) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+static inline float env_offset(const float* cdf, uint32_t k, float x)
+{
+    const float c0 = k ? cdf[k - 1] : 0.0f, c1 = cdf[k];
+    const float f = c1 > c0 ? (x - c0) / (c1 - c0) : 0.5f;
+    return fminf(fmaxf(f, 0.0f), 0.99999994f);
+}
+/* (u1, u2) -> a direction from the map's distribution: the row by u1, the column by u2, a linear offset inside each bin */
+static inline bool env_sample(const EnvMapH& E, float u1, float u2, f3& dir, float& pdf, f3& Le)
+{
+    pdf = 0.0f; Le = mk(0.0f); dir = mk(0.0f, 1.0f, 0.0f);
+    if (E.w == 0 || !(E.pdf_scale > 0.0f)) return false;
+    const uint32_t row = env_search(E.marg.data(), E.h, u1);
+    const float fv = env_offset(E.marg.data(), row, u1);
+    const float* cdf = &E.cond[(size_t)row * E.w];
+    const uint32_t col = env_search(cdf, E.w, u2);
+    const float fu = env_offset(cdf, col, u2);
+    const float u = ((float)col + fu) / (float)E.w, v = ((float)row + fv) / (float)E.h;
+    float st = sinf(kPIf * v);
+    const float ct = cosf(kPIf * v);
+    const float ph = 2.0f * kPIf * (u - 0.5f);
+    const float sp = sinf(ph), cp = cosf(ph);
+    st = fmaxf(st, 0.0f);
+    dir = mk(st * sp, ct, -(st * cp));
+    const float* t = &E.texels[4 * ((size_t)row * E.w + col)];
+    Le = mk(t[0], t[1], t[2]);
+    pdf = env_pdf_weight(t[3], st, E.pdf_scale);
+    return pdf > 0.0f;
+}
+
+/* ------------------------------------------------------ microfacet model (NOT the reference) ----
+ * The maths of tests/microfacet_ref.py: isotropic GGX, Smith Lambda, height-correlated G2, Heitz 2018 visible-normal sampling, the
+ * reference's conductor Fresnel and FrDielectric.  float32 in the device's operation order at the IEEE level. */
+static const float kSmoothAlpha = 1e-3f;      /* alpha below this: the smooth BSDF (mirror / light mode 1's glass) */
+
+static inline void onb_axes(const f3& n, f3& tg, f3& bn)
+{
+    const OrthonormalBasis onb(n);
+    tg = onb.m_tangent; bn = onb.m_binormal;
+}
+static inline float ggx_lambda(float c, float a2)
+{
+    const float c2 = c * c;
+    return 0.5f * (sqrtf(1.0f + a2 * ((1.0f - c2) / c2)) - 1.0f);
+}
+static inline float ggx_d(float ch, float a2)
+{
+    const float t = ch * ch * (a2 - 1.0f) + 1.0f;
+    return a2 / (kPIf * t * t);
+}
+static inline f3 ggx_sample_vndf(const f3& ve, float alpha, float u1, float u2)
+{
+    const f3 vh = normalize(mk(alpha * ve.x, alpha * ve.y, ve.z));
+    const float lensq = vh.x * vh.x + vh.y * vh.y;
+    const f3 t1v = lensq > 0.0f ? mk(-vh.y, vh.x, 0.0f) * (1.0f / sqrtf(lensq)) : mk(1.0f, 0.0f, 0.0f);
+    const f3 t2v = cross(vh, t1v);
+    const float r = sqrtf(u1);
+    const float phi = 2.0f * kPIf * u2;
+    const float sp = sinf(phi), cp = cosf(phi);
+    const float t1 = r * cp;
+    const float s = 0.5f * (1.0f + vh.z);
+    const float t2 = (1.0f - s) * sqrtf(fmaxf(0.0f, 1.0f - t1 * t1)) + s * (r * sp);
+    const f3 nh = t1 * t1v + t2 * t2v + sqrtf(fmaxf(0.0f, 1.0f - t1 * t1 - t2 * t2)) * vh;
+    return normalize(mk(alpha * nh.x, alpha * nh.y, fmaxf(0.0f, nh.z)));
+}
+static inline f3 mf_conductor_f(float c) { return fresnelSchlickConductor(c, mk(1.45f, 0.7f, 1.55f), mk(3.0f, 2.2f, 3.5f)); }
+static inline float mf_dielectric_f(float c, bool entering, float ior) { return FrDielectric(entering ? c : -c, 1.0f, ior); }
+
+/* microfacet_ref.sample for one wo (unit, away from the surface) at the face-forwarded normal N: u1, u2 the visible normal, u3 the
+ * dielectric's lobe.  Out: wi, weight = f |cos_i| / pdf without Kd, pdf, lobe (1 reflection, 2 transmission).  false (lobe 0, weight
+ * 0, pdf 0): wi lies on the wrong side, the path ends. */
+static inline bool mf_sample(int bsdf, const f3& wo, const f3& N, bool entering, float alpha, float ior, float u1, float u2, float u3,
+                             f3& wi, f3& weight, float& pdf, int& lobe)
+{
+    f3 tg, bn;
+    onb_axes(N, tg, bn);
+    const float co = dot(wo, N);
+    f3 h = ggx_sample_vndf(mk(dot(wo, tg), dot(wo, bn), co), alpha, u1, u2);
+    h = h.x * tg + h.y * bn + h.z * N;
+    const float a2 = alpha * alpha;
+    const float oh = dot(wo, h);
+    const float lo = ggx_lambda(co, a2);
+    const float d = ggx_d(dot(N, h), a2);
+    const float pdf_h = d / (4.0f * co * (1.0f + lo));
+    weight = mk(0.0f); pdf = 0.0f; lobe = 0;
+    float F = 1.0f;
+    bool transmit = false;
+    if (bsdf == PT_BSDF_REFRACTION) {
+        F = mf_dielectric_f(oh, entering, ior);
+        transmit = !(u3 < F);
+    }
+    if (!transmit) {
+        wi = (2.0f * oh) * h - wo;
+        const float ci = dot(wi, N);
+        if (!(ci > 0.0f)) return false;
+        const float g = (1.0f + lo) / (1.0f + lo + ggx_lambda(ci, a2));
+        weight = bsdf == PT_BSDF_METALLIC ? mf_conductor_f(oh) * g : mk(g);
+        pdf = bsdf == PT_BSDF_METALLIC ? pdf_h : F * pdf_h;
+        lobe = 1;
+        return true;
+    }
+    const float eta = entering ? ior : 1.0f / ior;
+    const float e = 1.0f / eta;
+    const float k = 1.0f - e * e * (1.0f - oh * oh);
+    if (!(k >= 0.0f)) { wi = mk(0.0f); return false; }
+    wi = (e * oh - sqrtf(k)) * h - e * wo;
+    const float ci = dot(wi, N);
+    if (!(ci < 0.0f)) return false;
+    const float ih = dot(wi, h);
+    const float den = oh + eta * ih;
+    weight = mk((1.0f + lo) / (1.0f + lo + ggx_lambda(ci, a2)));
+    pdf = (1.0f - F) * ((d * oh * eta * eta * fabsf(ih)) / (co * (1.0f + lo) * den * den));
+    lobe = 2;
+    return true;
+}
+
+/* microfacet_ref.evaluate: f (without Kd) and the solid-angle pdf of mf_sample for (wo, wi); zero where mf_sample cannot draw wi */
+static inline void mf_eval(int bsdf, const f3& wo, const f3& N, bool entering, float alpha, float ior, const f3& wi, f3& f, float& pdf)
+{
+    f = mk(0.0f); pdf = 0.0f;
+    const float a2 = alpha * alpha;
+    const float co = dot(wo, N), ci = dot(wi, N);
+    const float lo = ggx_lambda(co, a2);
+    if (ci > 0.0f) {
+        const f3 h = normalize(wo + wi);
+        const float oh = dot(wo, h);
+        if (!(oh > 0.0f)) return;
+        const float d = ggx_d(dot(N, h), a2);
+        const float g2 = 1.0f / (1.0f + lo + ggx_lambda(ci, a2));
+        const float dg = (d * g2) / (4.0f * co * ci);
+        const float pdf_h = d / (4.0f * co * (1.0f + lo));
+        if (bsdf == PT_BSDF_METALLIC) { f = mf_conductor_f(oh) * dg; pdf = pdf_h; }
+        else { const float F = mf_dielectric_f(oh, entering, ior); f = mk(F * dg); pdf = F * pdf_h; }
+    } else if (ci < 0.0f && bsdf == PT_BSDF_REFRACTION) {
+        const float eta = entering ? ior : 1.0f / ior;
+        f3 h = normalize(wo + eta * wi);
+        if (dot(h, N) < 0.0f) h = -h;
+        const float oh = dot(wo, h), ih = dot(wi, h);
+        if (!(oh > 0.0f && ih < 0.0f)) return;
+        const float F = mf_dielectric_f(oh, entering, ior);
+        const float d = ggx_d(dot(N, h), a2);
+        const float g2 = 1.0f / (1.0f + lo + ggx_lambda(ci, a2));
+        const float den = oh + eta * ih;
+        const float j = (d * oh * eta * eta * fabsf(ih)) / (co * den * den);
+        f = mk((1.0f - F) * ((j * g2) / fabsf(ci)));
+        pdf = (1.0f - F) * (j / (1.0f + lo));
+    }
+}
+
 /* ---------------------------------------------------------- light mode 1 (NOT the reference) ----
  * SURVEY.md section 8 f4, opt-in: the area light is what the OBJ says is emissive (every triangle whose material has
  * Ke != 0) instead of the rectangle hard-coded at PathTracerMain.cpp:154-158, and the estimator is a consistent one:
@@ -549,8 +808,14 @@ static inline void closesthit(const Scene& sc, const pt_params& params, int use_
  *     throughput * Ke (mode 0: throughput * Kd_emitter * Ke);
  *   - uniform hemisphere sampling carries its 2 cos(theta) weight (mode 0 omits it), so importance sampling
  *     on / off and direct lighting on / off all converge to the same image;
- *   - conductor and dielectric keep the reference's directions and throughput; they take no light sample (their
- *     emitter hits count in full).
+ *   - under the reference's material model (orc_scene_set_material_model 0) conductor and dielectric keep the reference's
+ *     directions and throughput; they take no light sample (their emitter hits count in full).
+ * With an environment map (orc_scene_set_environment) the map is a light too: a light sample goes to it when z1 < p_env (0.5 beside
+ * emissive triangles, 1 without, 0 for a black map), z1 rescaled for the strategy chosen; the triangles' pdfs carry 1 - p_env; the
+ * map's shadow ray runs to 1e16; a miss after a light-sampled vertex is weighted against p_env * env_pdf (raygen_pixel).
+ * Under the microfacet model (1) metal and glass of alpha >= kSmoothAlpha are GGX BSDFs (mf_sample: metal 2 draws, glass 3; a failed
+ * sample ends the path, its light sample still counts) that take light samples weighted against mf_eval's pdf; a smooth conductor
+ * draws 2, discards them and is a mirror about N; smooth glass is the code above.
  * `contrib` is everything this segment adds to the pixel, already multiplied by the path throughput. */
 static inline float light_pdf_area_to_solid(float dist2, float cos_l, float area_total) { return dist2 / (area_total * cos_l); }
 
@@ -558,9 +823,12 @@ static inline void closesthit_scene_lights(const Scene& sc, const pt_params& par
                                            const f3& ray_org, const f3& ray_dir, float t_hit, uint32_t prim_idx,
                                            PRD& prd, float& prev_pdf, f3& contrib, Counters& cnt)
 {
-    const pt_material& rt = sc.mats[sc.mat_ids[prim_idx]];
+    const uint32_t mat_id = sc.mat_ids[prim_idx];
+    const pt_material& rt = sc.mats[mat_id];
     const Tri& tri = sc.tris[prim_idx];
-    const bool useDirectLighting = params.useDirectLighting != 0 && !sc.lights.empty();
+    const bool env = sc.env.w != 0;
+    const float p_env = sc.p_env;
+    const bool useDirectLighting = params.useDirectLighting != 0 && (!sc.lights.empty() || (env && p_env > 0.0f));
     const bool useImportanceSampling = params.useImportanceSampling != 0;
     const int bsdfType = rt.bsdfType;
     const f3 N_0 = normalize(cross(tri.e1, tri.e2));
@@ -579,7 +847,8 @@ static inline void closesthit_scene_lights(const Scene& sc, const pt_params& par
         float w = 1.0f;
         if (prd.depth > 0 && prev_pdf > 0.0f) {
             const float cos_l = fabsf(dot(N_0, ray_dir));
-            const float p_l = light_pdf_area_to_solid(t_hit * t_hit, cos_l, area_total);
+            float p_l = light_pdf_area_to_solid(t_hit * t_hit, cos_l, area_total);
+            if (env) p_l = p_l * (1.0f - p_env);
             w = cos_l > 0.0f ? (prev_pdf * prev_pdf) / (prev_pdf * prev_pdf + p_l * p_l) : 1.0f;
         }
         contrib = prd.attenuation * Ke * w;
@@ -593,8 +862,12 @@ static inline void closesthit_scene_lights(const Scene& sc, const pt_params& par
     prd.done = 0;
     const f3 att_in = prd.attenuation;
     float bsdf_pdf = 0.0f;                 /* solid-angle pdf of the sampled continuation; 0 = no light sample taken here */
-    switch (bsdfType) {
-    case PT_BSDF_DIFFUSE: {
+    const bool micro = sc.material_model == 1 && bsdfType != PT_BSDF_DIFFUSE;
+    const float alpha = micro ? sc.alpha[mat_id] : 0.0f;
+    const bool rough = micro && !(alpha < kSmoothAlpha);
+    const f3 wo = -ray_dir;
+    const bool entering = dot(wo, N_0) > 0.0f;
+    if (bsdfType == PT_BSDF_DIFFUSE) {
         const float z1 = rnd(seed);
         const float z2 = rnd(seed);
         OrthonormalBasis onb(N);
@@ -607,9 +880,24 @@ static inline void closesthit_scene_lights(const Scene& sc, const pt_params& par
         prd.origin = P;
         if (useImportanceSampling) { prd.attenuation = att_in * Kd; bsdf_pdf = cos_out / kPIf; }
         else                       { prd.attenuation = att_in * Kd * (2.0f * cos_out); bsdf_pdf = 1.0f / (2.0f * kPIf); }
-        break;
-    }
-    case PT_BSDF_METALLIC: {
+    } else if (rough) {                    /* metal: 2 draws, glass: 3 */
+        const float z1 = rnd(seed);
+        const float z2 = rnd(seed);
+        const float z3 = bsdfType == PT_BSDF_REFRACTION ? rnd(seed) : 0.0f;
+        f3 wi = mk(0.0f), wt; float pdf; int lobe;
+        const bool ok = mf_sample(bsdfType, wo, N, entering, alpha, rt.ior, z1, z2, z3, wi, wt, pdf, lobe);
+        prd.direction = wi;
+        prd.origin = P + wi * (bsdfType == PT_BSDF_METALLIC ? 1e-4f : 1e-3f);
+        prd.attenuation = att_in * (wt * Kd);
+        bsdf_pdf = pdf;
+        prd.done = !ok;                    /* below the plane: the path ends here (its light sample still counts) */
+    } else if (bsdfType == PT_BSDF_METALLIC && micro) {     /* smooth conductor: a mirror about N, the same two draws */
+        (void)rnd(seed); (void)rnd(seed);
+        const f3 R = reflect(ray_dir, N);
+        prd.direction = R;
+        prd.origin = P + R * 1e-4f;
+        prd.attenuation = att_in * (mf_conductor_f(fmaxf(dot(N, wo), 0.0f)) * Kd);
+    } else if (bsdfType == PT_BSDF_METALLIC) {
         const float z1 = rnd(seed);
         const float z2 = rnd(seed);
         f3 microfacetNormal = sampleGGX(z1, z2, 0.2f, N);
@@ -620,9 +908,7 @@ static inline void closesthit_scene_lights(const Scene& sc, const pt_params& par
         f3 k = mk((float)3.0, (float)2.2, (float)3.5);
         float cosTheta = fmaxf(dot(microfacetNormal, -ray_dir), 0.0f);
         prd.attenuation = att_in * (fresnelSchlickConductor(cosTheta, eta, k) * Kd);
-        break;
-    }
-    case PT_BSDF_REFRACTION: {
+    } else if (bsdfType == PT_BSDF_REFRACTION) {
         f3 incidentRayDir = normalize(ray_dir);
         float cos_theta = dot(normalize(-ray_dir), N_0);
         float F = FrDielectric(cos_theta, 1.0f, rt.ior);
@@ -635,17 +921,32 @@ static inline void closesthit_scene_lights(const Scene& sc, const pt_params& par
         }
         prd.origin = P + prd.direction * 1e-3f;
         prd.attenuation = att_in * Kd;
-        break;
-    }
-    default: break;
     }
     const float z1 = rnd(seed);
     const float z2 = rnd(seed);
     prd.randomSeed = seed;
     prev_pdf = 0.0f;
-    if (useDirectLighting && bsdfType == PT_BSDF_DIFFUSE) {
-        /* pick the triangle whose CDF interval holds z1 * A, reuse the position inside the interval as first variate */
-        const float target = z1 * area_total;
+    const bool lit = useDirectLighting && (bsdfType == PT_BSDF_DIFFUSE || rough);     /* this vertex takes a light sample */
+    if (!lit) return;
+    bool to_env = false;
+    float zl = z1;
+    if (env) {
+        to_env = z1 < p_env;
+        zl = to_env ? z1 / p_env : (z1 - p_env) / (1.0f - p_env);
+    }
+    prev_pdf = bsdf_pdf;                   /* a later emitter hit or miss is MIS-weighted */
+    f3 L, Le = mk(0.0f);
+    float Ldist, p_l, nDl, geom = 0.0f;
+    bool want_shadow;
+    if (to_env) {                          /* a direction from the map; its shadow ray reaches as far as a radiance ray */
+        float pdf_e;
+        const bool ok = env_sample(sc.env, zl, z2, L, pdf_e, Le);
+        Ldist = 1e16f;
+        nDl = dot(N, L);
+        p_l = p_env * pdf_e;
+        want_shadow = ok && (rough || nDl > 0.0f);
+    } else {                               /* pick the triangle whose CDF interval holds zl * A, reuse the position inside the interval */
+        const float target = zl * area_total;
         size_t k = 0;
         while (k + 1 < sc.lights.size() && !(target < sc.lights[k].cdf)) k++;
         const LightTri& lt = sc.lights[k];
@@ -655,23 +956,34 @@ static inline void closesthit_scene_lights(const Scene& sc, const pt_params& par
         const f3 light_pos = lt.v0 + lt.e1 * (su * (1.0f - z2)) + lt.e2 * (su * z2);
         const f3 Lv = light_pos - P;
         const float dist2 = dot(Lv, Lv);
-        const float Ldist = sqrtf(dist2);
-        const f3 L = Lv / Ldist;
-        const float nDl = dot(N, L);
+        Ldist = sqrtf(dist2);
+        L = Lv / Ldist;
+        nDl = dot(N, L);
         const float LnDl = fabsf(dot(lt.n, L));
-        prev_pdf = bsdf_pdf;               /* this vertex takes a light sample: a later emitter hit is MIS-weighted */
-        if (nDl > 0.0f && LnDl > 0.0f) {
-            cnt.shadow_rays++;
-            const bool occluded = use_bvh ? any_bvh(sc, P, L, 0.01f, Ldist - 0.01f) : any_brute(sc, P, L, 0.01f, Ldist - 0.01f);
-            if (!occluded) {
-                const float p_l = light_pdf_area_to_solid(dist2, LnDl, area_total);
-                const float p_b = useImportanceSampling ? nDl / kPIf : 1.0f / (2.0f * kPIf);
-                const float w = (p_l * p_l) / (p_l * p_l + p_b * p_b);
-                const float geom = nDl * LnDl * area_total / (kPIf * dist2);      /* (Kd / pi) cos / p_area-as-solid-angle, Kd below */
-                contrib = att_in * Kd * lt.Ke * (geom * w);
-            }
-        }
+        p_l = light_pdf_area_to_solid(dist2, LnDl, area_total);
+        if (env) p_l = p_l * (1.0f - p_env);
+        geom = nDl * LnDl * area_total / (kPIf * dist2);      /* (Kd / pi) cos / p_area-as-solid-angle, Kd below */
+        if (env) geom = geom / (1.0f - p_env);
+        Le = lt.Ke;
+        want_shadow = nDl > 0.0f && LnDl > 0.0f;
+        if (rough) want_shadow = LnDl > 0.0f;
     }
+    f3 f = mk(0.0f);
+    float p_b;
+    if (bsdfType == PT_BSDF_DIFFUSE) {
+        p_b = useImportanceSampling ? nDl / kPIf : 1.0f / (2.0f * kPIf);
+    } else {
+        mf_eval(bsdfType, wo, N, entering, alpha, rt.ior, L, f, p_b);
+        want_shadow = want_shadow && p_b > 0.0f;
+    }
+    if (!want_shadow) return;
+    cnt.shadow_rays++;
+    const bool occluded = use_bvh ? any_bvh(sc, P, L, 0.01f, Ldist - 0.01f) : any_brute(sc, P, L, 0.01f, Ldist - 0.01f);
+    if (occluded) return;
+    const float w = (p_l * p_l) / (p_l * p_l + p_b * p_b);
+    if (bsdfType != PT_BSDF_DIFFUSE) contrib = att_in * Kd * f * Le * ((fabsf(nDl) / p_l) * w);
+    else if (to_env)                 contrib = att_in * Kd * Le * ((nDl / (kPIf * p_l)) * w);
+    else                             contrib = att_in * Kd * Le * (geom * w);
 }
 
 /* __raygen__rg, pathTracerPrograms.cu:707-816, for launch index (x, y) */
@@ -721,6 +1033,19 @@ static void raygen_pixel(const Scene& sc, const pt_params& params, int use_bvh, 
                 prd.radiance = mk(0.0f);
                 prd.emissionColor = mk(0.f);
                 prd.done = 1;
+                if (sc.env.w != 0) {                   /* NOT the reference: the environment map replaces the background */
+                    const f3 Le = env_eval(sc.env, ray_direction);
+                    if (sc.light_mode == 1) {          /* a BSDF-sampled direction after a light sample: power heuristic against the map */
+                        float wm = 1.0f;
+                        if (prd.depth > 0 && prev_pdf > 0.0f) {
+                            const float pe = sc.p_env * env_pdf(sc.env, ray_direction);
+                            wm = (prev_pdf * prev_pdf) / (prev_pdf * prev_pdf + pe * pe);
+                        }
+                        result += prd.attenuation * Le * wm;
+                    } else {
+                        prd.radiance = Le;
+                    }
+                }
             }
             result += prd.emissionColor;               /* :760-761 */
             result += prd.radiance * prd.attenuation;
@@ -902,6 +1227,11 @@ ORC_API void* orc_scene_create(const float* verts_xyzw, size_t n_verts, const ui
     if (mat_ids) sc->mat_ids.assign(mat_ids, mat_ids + n_tris);
     if (mats) sc->mats.assign(mats, mats + n_mats);
     sc->light_mode = 0;
+    sc->p_env = 0.0f;
+    sc->material_model = 0;
+    sc->alpha.assign(n_mats, 0.0f);
+    for (size_t i = 0; mats && i < n_mats; i++)
+        sc->alpha[i] = mats[i].roughness > 0.0f ? fminf(mats[i].roughness, 1.0f) : 0.0f;     /* NaN and negative values: 0 */
     if (mat_ids && mats) {
         float run = 0.0f;
         for (size_t i = 0; i < n_tris; i++) {
@@ -921,6 +1251,86 @@ ORC_API void* orc_scene_create(const float* verts_xyzw, size_t n_verts, const ui
 /* 0: the reference's estimator; 1: scene lights + MIS (closesthit_scene_lights).  Returns the number of light triangles. */
 ORC_API int orc_scene_set_light_mode(void* s, int mode) { Scene* sc = (Scene*)s; sc->light_mode = mode == 1 ? 1 : 0; return (int)sc->lights.size(); }
 ORC_API void orc_scene_destroy(void* s) { delete (Scene*)s; }
+
+/* The environment map (pt_set_environment): rgb float[h][w][3], row 0 the +Y pole, times scale3 (NULL: 1); rgb NULL or w 0 clears
+ * it.  p_env follows: 0.5 with emissive triangles, 1 without, 0 for a black map.  Returns 0, or -1 for a bad size. */
+ORC_API int orc_scene_set_environment(void* s, const float* rgb, uint32_t w, uint32_t h, const float* scale3)
+{
+    Scene* sc = (Scene*)s;
+    sc->env = EnvMapH();
+    sc->p_env = 0.0f;
+    if (!rgb || w == 0) return 0;
+    if (h == 0) return -1;
+    env_build(sc->env, rgb, w, h, scale3);
+    sc->p_env = sc->env.pdf_scale > 0.0f ? (sc->lights.empty() ? 1.0f : 0.5f) : 0.0f;
+    return 0;
+}
+/* the map's tables: texels float[h][w][4] ({r, g, b, weight}), marginal float[h], conditional float[h][w], info {total, pdf_scale,
+ * p_env} (any may be NULL).  Returns w * h (0: no map). */
+ORC_API size_t orc_scene_environment_tables(void* s, float* texels, float* marginal, float* conditional, float* info3)
+{
+    const Scene* sc = (const Scene*)s;
+    const EnvMapH& E = sc->env;
+    if (texels && E.w) memcpy(texels, E.texels.data(), E.texels.size() * sizeof(float));
+    if (marginal && E.w) memcpy(marginal, E.marg.data(), E.marg.size() * sizeof(float));
+    if (conditional && E.w) memcpy(conditional, E.cond.data(), E.cond.size() * sizeof(float));
+    if (info3) { info3[0] = E.total; info3[1] = E.pdf_scale; info3[2] = sc->p_env; }
+    return (size_t)E.w * E.h;
+}
+/* light mode 1's material model (pt_set_material_model): 0 the reference's, 1 GGX metal and glass.  Returns the model set, -1 if unknown. */
+ORC_API int orc_scene_set_material_model(void* s, int model)
+{
+    if (model != 0 && model != 1) return -1;
+    ((Scene*)s)->material_model = model;
+    return model;
+}
+
+/* pt_debug_environment's layouts on the scene's map: op 0 lookup, in float[n][3] -> out float[n][4] (rgb, texel index or -1 without
+ * a map); op 1 pdf, in float[n][3] -> out float[n]; op 2 sample, in float[n][2] (u1, u2) -> out float[n][4] (direction, pdf). */
+ORC_API int orc_debug_environment(void* s, int op, const float* in, size_t n, float* out)
+{
+    const EnvMapH& E = ((const Scene*)s)->env;
+    if (op < 0 || op > 2) return -1;
+    for (size_t i = 0; i < n; i++) {
+        if (op == 2) {
+            f3 d, Le; float pdf;
+            env_sample(E, in[2 * i], in[2 * i + 1], d, pdf, Le);
+            out[4 * i] = d.x; out[4 * i + 1] = d.y; out[4 * i + 2] = d.z; out[4 * i + 3] = pdf;
+            continue;
+        }
+        const f3 d = mk(in[3 * i], in[3 * i + 1], in[3 * i + 2]);
+        if (op == 1) { out[i] = env_pdf(E, d); continue; }
+        const f3 c = env_eval(E, d);
+        out[4 * i] = c.x; out[4 * i + 1] = c.y; out[4 * i + 2] = c.z;
+        out[4 * i + 3] = E.w ? (float)env_texel(E, d) : -1.0f;
+    }
+    return 0;
+}
+/* pt_debug_microfacet's layouts: normal (0, 0, 1) face-forwarded to wo.  op 0 mf_sample, in float[n][9] = wo, alpha, ior, bsdf, u1, u2,
+ * u3 -> out float[n][8] = wi, weight, pdf, lobe; op 1 mf_eval, in float[n][9] = wo, wi, alpha, ior, bsdf -> out float[n][4] = f, pdf. */
+ORC_API int orc_debug_microfacet(int op, const float* in, size_t n, float* out)
+{
+    if (op < 0 || op > 1) return -1;
+    for (size_t i = 0; i < n; i++) {
+        const float* a = in + 9 * i;
+        const f3 wo = mk(a[0], a[1], a[2]);
+        const f3 N0 = mk(0.0f, 0.0f, 1.0f);
+        const f3 N = faceforward(N0, wo, N0);
+        const bool entering = wo.z > 0.0f;
+        if (op == 0) {
+            f3 wi = mk(0.0f), wt; float pdf; int lobe;
+            (void)mf_sample((int)a[5], wo, N, entering, a[3], a[4], a[6], a[7], a[8], wi, wt, pdf, lobe);
+            float* o = out + 8 * i;
+            o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = wt.x; o[4] = wt.y; o[5] = wt.z; o[6] = pdf; o[7] = (float)lobe;
+        } else {
+            f3 f; float pdf;
+            mf_eval((int)a[8], wo, N, entering, a[6], a[7], mk(a[3], a[4], a[5]), f, pdf);
+            float* o = out + 4 * i;
+            o[0] = f.x; o[1] = f.y; o[2] = f.z; o[3] = pdf;
+        }
+    }
+    return 0;
+}
 
 ORC_API void orc_trace_closest(void* s, const float* rays, size_t n, int use_bvh, float* t_out, uint32_t* prim_out)
 {

@@ -47,6 +47,11 @@ class Oracle(MathMixin):
         L.orc_render_window.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]; L.orc_render_window.restype = C.c_double
         L.orc_scene_set_light_mode.argtypes = [vp, C.c_int]; L.orc_scene_set_light_mode.restype = C.c_int
         L.orc_uses_hw_fma.argtypes = []; L.orc_uses_hw_fma.restype = C.c_int
+        L.orc_scene_set_environment.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp]; L.orc_scene_set_environment.restype = C.c_int
+        L.orc_scene_environment_tables.argtypes = [vp, vp, vp, vp, vp]; L.orc_scene_environment_tables.restype = sz
+        L.orc_scene_set_material_model.argtypes = [vp, C.c_int]; L.orc_scene_set_material_model.restype = C.c_int
+        L.orc_debug_environment.argtypes = [vp, C.c_int, vp, sz, vp]; L.orc_debug_environment.restype = C.c_int
+        L.orc_debug_microfacet.argtypes = [C.c_int, vp, sz, vp]; L.orc_debug_microfacet.restype = C.c_int
 
     # -- small functions -------------------------------------------------------------
     def tea4(self, v0, v1):
@@ -93,6 +98,13 @@ class Oracle(MathMixin):
         self.lib.orc_sample_pixel(world, w, rank, si, C.byref(x), C.byref(y))
         return x.value, y.value
 
+    def microfacet_hook(self, op, x):
+        """pt_debug_microfacet's layouts (include/acgpt_test.h): op 0 mf_sample, float[n][9] -> float[n][8]; op 1 mf_eval -> float[n][4]."""
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, 9)
+        out = np.zeros((x.shape[0], 8 if op == 0 else 4), np.float32)
+        assert self.lib.orc_debug_microfacet(int(op), x.ctypes.data, x.shape[0], out.ctypes.data) == 0
+        return out
+
     # -- scene / tracing / rendering ----------------------------------------------------
     def scene(self, verts, idx, mat_ids, mats):
         return OracleScene(self, verts, idx, mat_ids, mats)
@@ -111,6 +123,38 @@ class OracleScene:
     def set_light_mode(self, mode):
         """0: the reference's estimator; 1: scene lights + MIS.  Returns the number of emissive triangles."""
         return int(self.orc.lib.orc_scene_set_light_mode(self.h, int(mode)))
+
+    def set_environment(self, rgb, scale=(1.0, 1.0, 1.0)):
+        """pt_set_environment's map: rgb float[h, w, 3] (row 0 the +Y pole) times scale; None clears it."""
+        if rgb is None:
+            assert self.orc.lib.orc_scene_set_environment(self.h, None, 0, 0, None) == 0
+            return
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        sc = np.ascontiguousarray(scale, np.float32)
+        self._env_shape = rgb.shape[:2]
+        assert self.orc.lib.orc_scene_set_environment(self.h, rgb.ctypes.data, rgb.shape[1], rgb.shape[0], sc.ctypes.data) == 0
+
+    def environment_tables(self):
+        """{texels [h, w, 4] (rgb times scale, the sampling weight in [..., 3]), marginal [h], conditional [h, w], total, pdf_scale,
+        p_env} of the map set last; None without one"""
+        info = np.zeros(3, np.float32)
+        if self.orc.lib.orc_scene_environment_tables(self.h, None, None, None, info.ctypes.data) == 0:
+            return None
+        h, w = self._env_shape
+        tex = np.zeros((h, w, 4), np.float32); marg = np.zeros(h, np.float32); cond = np.zeros((h, w), np.float32)
+        self.orc.lib.orc_scene_environment_tables(self.h, tex.ctypes.data, marg.ctypes.data, cond.ctypes.data, None)
+        return {"texels": tex, "marginal": marg, "conditional": cond, "total": info[0], "pdf_scale": info[1], "p_env": float(info[2])}
+
+    def set_material_model(self, model):
+        """light mode 1's material model: 0 the reference's, 1 GGX metal and glass (pt_set_material_model)"""
+        assert self.orc.lib.orc_scene_set_material_model(self.h, int(model)) == int(model)
+
+    def env_hook(self, op, x):
+        """pt_debug_environment's layouts (include/acgpt_test.h) on this scene's map: op 0 lookup -> [n, 4], 1 pdf -> [n, 1], 2 sample -> [n, 4]"""
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.zeros((x.shape[0], 1 if op == 1 else 4), np.float32)
+        assert self.orc.lib.orc_debug_environment(self.h, int(op), x.ctypes.data, x.shape[0], out.ctypes.data) == 0
+        return out
 
     def close(self):
         if self.h:
