@@ -905,12 +905,12 @@ static ptd::DeviceScene device_scene(pt_ctx* c)
 }
 
 // StaticWorkDistribution::numSamples, sutil/WorkDistribution.h:50-57
-static uint32_t num_samples(int world, uint32_t w, uint32_t h)
+static uint64_t num_samples(int world, uint32_t w, uint32_t h)
 {
     const uint32_t strip_w = 8u * (uint32_t)world, strip_h = 4u;
     const uint32_t cols = w / strip_w + (w % strip_w == 0 ? 0 : 1);
     const uint32_t rows = h / strip_h + (h % strip_h == 0 ? 0 : 1);
-    return rows * cols * 32u;
+    return (uint64_t)rows * cols * 32u;      // 64-bit: 65535 x 65535 on one rank is 2^32 slots, which wrapped to 0 and was admitted
 }
 
 // Granlund & Montgomery division by an invariant (N = 32): exact for every 32-bit numerator
@@ -1232,9 +1232,9 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
             for (uint32_t i = 0; i < 2u * a.chunk_spp; i++) { add = 1664525u * add + 1013904223u; mul = 1664525u * mul; }
         }
     }
-    if (((uint64_t)num_samples(c->world, p->width, p->height) << a.sub_shift) >= 0x7FFFFFFFull)
+    if ((num_samples(c->world, p->width, p->height) << a.sub_shift) >= 0x7FFFFFFFull)
         return fail(c, "pt_launch: image too large for this sample-chunk count and frame batch (2^31 work items)");
-    a.total_samples = num_samples(c->world, p->width, p->height) << a.sub_shift;
+    a.total_samples = (uint32_t)(num_samples(c->world, p->width, p->height) << a.sub_shift);
     a.strip_cols = p->width / (8u * (uint32_t)c->world) + (p->width % (8u * (uint32_t)c->world) == 0 ? 0u : 1u);
     if (c->div_width != p->width || c->div_world_n != c->world) {      // the constants depend on (width, world) only: built and verified when those change
         const ptd::FastDiv dc = make_fast_div(a.strip_cols), dw = make_fast_div((uint32_t)c->world);

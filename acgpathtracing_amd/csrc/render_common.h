@@ -54,6 +54,7 @@ struct QueueState {
     uint32_t grant_g0;                    // first group of the current grant
     uint32_t free_top;                    // entries on the wave's stack of free fold slots (WaveBook::free)
     uint32_t grp_pxy, grp_seed;           // PER LANE: lane j holds pixel (x | y << 16, bit 31: every ray of the pixel reaches the scene box; 0xFFFFFFFF = padding) and tea<4> seed of group grant_g0 + j
+    uint32_t reach_bit;                   // 0x80000000 when the grant's bit 31 is that flag (pixel classes on: height <= 32767), else 0: bit 15 of y
     uint32_t skipped;                     // groups of pixels that cannot reach the scene box, settled when their grant was decoded (the kernel books their samples)
 };
 
@@ -207,7 +208,7 @@ __device__ __forceinline__ void refill_lanes(const RenderArgs& A, Late late, Que
             const uint32_t pxy_f = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)q.grp_pxy);
             const uint32_t seed0 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)q.grp_seed);
             const bool mine = !lp.alive && rank < take && pxy_f != 0xFFFFFFFFu;
-            const uint32_t pxy = pxy_f & 0x7FFFFFFFu;
+            const uint32_t pxy = pxy_f & ~q.reach_bit;        // masking bit 31 always turned rows >= 32768 into row y - 32768
             uint32_t sl = kNoSlot;
             if (cs != 0u) {
                 // fold slot of the group: the lane that gets run 0 pops one (the n-th such lane of this deal the n-th entry from
@@ -222,7 +223,7 @@ __device__ __forceinline__ void refill_lanes(const RenderArgs& A, Late late, Que
             }
             if (mine) {
                 lp.pxy = pxy;
-                lp.tag = (((item >> cs) & fmask) << cs) | run | (sl << 16) | ((pxy_f >> 31) << 24);      // bit 24: no cull test needed
+                lp.tag = (((item >> cs) & fmask) << cs) | run | (sl << 16) | (((pxy_f & q.reach_bit) >> 31) << 24);      // bit 24: no cull test needed
                 lp.seed = lcg_skip[2u * run] * seed0 + lcg_skip[2u * run + 1u];     // skip the jitter draws of the samples before this run (2 per sample)
                 lp.result = mk(0.0f);
                 lp.samples_left = A.chunk_spp;

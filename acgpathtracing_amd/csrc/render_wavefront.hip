@@ -459,6 +459,7 @@ k_render_wf(const RenderArgsBox B)
                 QueueState q;
                 q.shard = ctl->shard; q.shards_left = ctl->shards_left; q.res_first = ctl->res_first; q.res_count = ctl->res_count;
                 q.grant_g0 = ctl->grant_g0; q.free_top = ctl->free_top; q.grp_pxy = ctl->grp_pxy[lane]; q.grp_seed = ctl->grp_seed[lane];
+                q.reach_bit = Ad.row_spans != nullptr ? 0x80000000u : 0u;
                 int live_delta = 0;
                 uint32_t slot = ring_pop<POOL>(&ctl->q[QR], cells + QR * POOL, true, lane, below, trouble);
                 const bool from_run = slot != kWfNone;
