@@ -65,6 +65,22 @@ class UpdateInfo(C.Structure):
     _fields_ = [("ms", C.c_float), ("area_ratio", C.c_float), ("rebuilt", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class DisplayParams(C.Structure):
+    """pt_display_params (include/acgpt.h)."""
+    _fields_ = [("tone_curve", C.c_uint32), ("exposure", C.c_float), ("key", C.c_float), ("white", C.c_float),
+                ("lo_permille", C.c_uint32), ("hi_permille", C.c_uint32), ("min_exposure", C.c_float), ("max_exposure", C.c_float),
+                ("prev_exposure", C.c_float), ("adapt", C.c_float)]
+
+
+DISPLAY_BINS = 320                                                 # PT_DISPLAY_BINS
+
+
+class DisplayInfo(C.Structure):
+    """pt_display_info (include/acgpt.h)."""
+    _fields_ = [("exposure", C.c_float), ("metered_luminance", C.c_float), ("metered_pixels", C.c_uint32), ("unmetered_pixels", C.c_uint32),
+                ("histogram", C.c_uint32 * DISPLAY_BINS)]
+
+
 assert C.sizeof(PathTraceParams) == 168
 assert C.sizeof(Material) == 40
 assert C.sizeof(AreaLight) == 60
@@ -75,6 +91,8 @@ UPDATE_REFIT, UPDATE_REBUILD, UPDATE_AUTO = 0, 1, 2                # pt_update_v
 UPDATE_AUTO_AREA_RATIO = 1.25                                      # PT_UPDATE_AUTO_AREA_RATIO
 MATH_IEEE, MATH_FAST = 0, 1                                        # pt_set_math_mode
 MATERIALS_REFERENCE, MATERIALS_MICROFACET = 0, 1                   # pt_set_material_model
+TONE_LINEAR, TONE_REINHARD, TONE_ACES = 0, 1, 2                    # pt_display_params.tone_curve
+assert C.sizeof(DisplayParams) == 40 and C.sizeof(DisplayInfo) == 16 + 4 * DISPLAY_BINS
 
 # every symbol include/acgpt.h declares (the drop-in boundary) ...
 ABI_SYMBOLS = [
@@ -82,7 +100,7 @@ ABI_SYMBOLS = [
     "pt_launch", "pt_launch_frames", "pt_resolve_framebuffer", "pt_set_partition", "pt_set_sample_chunks", "pt_set_light_mode", "pt_set_math_mode", "pt_set_scratch_limit", "pt_set_tuning",
     "pt_variant_name", "pt_variant_kernel", "pt_kernel_source_hash", "pt_set_stream", "pt_get_stats",
     "pt_trace_closest", "pt_trace_any", "pt_render_features", "pt_denoise", "pt_temporal_blend", "pt_temporal_blend_motion", "pt_update_vertices", "pt_update_materials", "pt_set_environment",
-    "pt_set_material_model",
+    "pt_set_material_model", "pt_display_transform",
     "pt_device_malloc", "pt_device_free", "pt_device_memset", "pt_copy_to_host", "pt_copy_to_device",
     "pt_host_malloc_mapped", "pt_host_free_mapped", "pt_abi_version",
 ]
@@ -176,6 +194,7 @@ def hip():
     L.pt_set_environment.argtypes = [vp, vp, C.c_uint32, C.c_uint32, Float3]; L.pt_set_environment.restype = C.c_int
     L.pt_debug_environment.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_debug_environment.restype = C.c_int
     L.pt_set_material_model.argtypes = [vp, C.c_int]; L.pt_set_material_model.restype = C.c_int
+    L.pt_display_transform.argtypes = [vp, vp, sz, C.POINTER(DisplayParams), vp, vp, C.POINTER(DisplayInfo)]; L.pt_display_transform.restype = C.c_int
     L.pt_debug_microfacet.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_debug_microfacet.restype = C.c_int
     L.pt_bench_traversal.argtypes = [vp, vp, sz, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_float), vp]; L.pt_bench_traversal.restype = C.c_int
     L.pt_selftest.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_selftest.restype = C.c_int
@@ -225,6 +244,7 @@ def host():
     L.pth_trackball_script.argtypes = [vp, vp, vp, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, vp, sz, vp]
     L.pth_trackball_script.restype = None
     L.pth_save_image.argtypes = [C.c_char_p, vp, C.c_int, C.c_int]; L.pth_save_image.restype = C.c_int
+    L.pth_save_pfm.argtypes = [C.c_char_p, vp, C.c_int, C.c_int, C.c_int]; L.pth_save_pfm.restype = C.c_int
     L.pth_load_environment.argtypes = [C.c_char_p, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, sz]; L.pth_load_environment.restype = C.c_int
     _host = L
     return L

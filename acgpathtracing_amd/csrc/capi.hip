@@ -27,6 +27,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "../../include/acgpt.h"
 #include "../../include/acgpt_test.h"
 #include "denoise.h"
+#include "display.h"
 #include "environment.h"
 #include "lbvh_build.h"
 #include "materials.h"
@@ -85,6 +86,7 @@ struct pt_ctx {
     pt_multi* multi = nullptr;                // pt_create_multi: this context is rank 0 of a group (below)
     float4* d_denoise[2] = {nullptr, nullptr}; size_t denoise_pixels = 0;   // pt_denoise's ping-pong {colour, variance} buffers
     ptd::EnvDevice env;                       // pt_set_environment's map and CDFs (w == 0: none); the context's, kept across scene changes
+    ptd::DisplayState* d_display = nullptr; bool display_dirty = false;     // pt_display_transform's counts and meter record (dirty: a call failed half way)
     uint8_t* d_tri_bsdf = nullptr;            // bsdfType per triangle (caller's order): pt_temporal_blend's, built on its first call per scene
     // what pt_update_vertices keeps of the last pt_set_scene: host copies of everything but the vertices, and after the first update
     // the index buffer on the device (freed with the scene)
@@ -326,6 +328,7 @@ static void destroy_one(pt_ctx* c)
     if (c->d_row_spans) (void)hipFree(c->d_row_spans);
     ptd::env_free(c->env);
     for (float4* b : c->d_denoise) if (b) (void)hipFree(b);
+    if (c->d_display) (void)hipFree(c->d_display);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1511,6 +1514,48 @@ PT_API int pt_denoise(pt_ctx* c, const pt_params* p, const float* albedo_prim, c
     CK(c, ptd::launch_denoise((const float4*)p->accumulationBuffer, (const float4*)albedo_prim, (const float4*)normal_depth, p->width, p->height, iterations,
                               c->d_denoise[0], c->d_denoise[1], (float4*)out_rgba, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- display transform (pt_display_transform; kernels in display.hip) ----------------------------------------------------------
+static_assert(sizeof(pt_display_params) == 40 && sizeof(pt_display_info) == 16 + 4 * PT_DISPLAY_BINS, "pt_display_params / pt_display_info: a change of these layouts bumps pt_abi_version");
+
+PT_API int pt_display_transform(pt_ctx* c, const float* src_rgba, size_t n_pixels, const pt_display_params* dp, float* out_rgba, uint8_t* framebuffer_rgba,
+                                pt_display_info* info)
+{
+    const char* f = "pt_display_transform: ";
+    if (!c) return fail(nullptr, std::string(f) + "null context");
+    if (!src_rgba || !dp) return fail(c, std::string(f) + "null argument");
+    if (!out_rgba && !framebuffer_rgba) return fail(c, std::string(f) + "out_rgba and framebuffer_rgba are both null");
+    if (n_pixels < 1u || n_pixels > ((size_t)1 << 31)) return fail(c, std::string(f) + "n_pixels must be in [1, 2^31]");
+    if (dp->tone_curve != PT_TONE_LINEAR && dp->tone_curve != PT_TONE_REINHARD && dp->tone_curve != PT_TONE_ACES) return fail(c, std::string(f) + "unknown tone curve");
+    if (!std::isfinite(dp->exposure) || dp->exposure < 0.0f) return fail(c, std::string(f) + "exposure must be finite and >= 0 (0: automatic)");
+    const bool automatic = !(dp->exposure > 0.0f);
+    if (automatic) {
+        if (!std::isfinite(dp->key) || !(dp->key > 0.0f)) return fail(c, std::string(f) + "key must be finite and > 0");
+        if (dp->lo_permille >= dp->hi_permille || dp->hi_permille > 1000u) return fail(c, std::string(f) + "the metering window needs lo_permille < hi_permille <= 1000");
+        if (!std::isfinite(dp->min_exposure) || !std::isfinite(dp->max_exposure) || !(dp->min_exposure > 0.0f) || !(dp->min_exposure <= dp->max_exposure))
+            return fail(c, std::string(f) + "the exposure limits need 0 < min_exposure <= max_exposure, both finite");
+        if (!std::isfinite(dp->prev_exposure) || dp->prev_exposure < 0.0f) return fail(c, std::string(f) + "prev_exposure must be finite and >= 0 (0: none)");
+        if (!(dp->adapt >= 0.0f && dp->adapt <= 1.0f)) return fail(c, std::string(f) + "adapt must be in [0, 1]");
+    }
+    if (dp->tone_curve == PT_TONE_REINHARD && (!std::isfinite(dp->white) || !(dp->white > 0.0f))) return fail(c, std::string(f) + "white must be finite and > 0");
+    if (out_rgba && overlaps(out_rgba, src_rgba, n_pixels * sizeof(float4))) return fail(c, std::string(f) + "out_rgba overlaps src_rgba");
+    CK(c, hipSetDevice(c->device));
+    if (automatic && (!c->d_display || c->display_dirty)) {
+        if (!c->d_display) CK(c, hipMalloc((void**)&c->d_display, sizeof(ptd::DisplayState)));
+        c->display_dirty = true;
+        CK(c, hipMemsetAsync(c->d_display, 0, sizeof(ptd::DisplayState), c->stream));
+    }
+    Range range("pt_display_transform");
+    c->display_dirty = automatic;            // until the meter kernel has run to its end and cleared the counts
+    CK(c, ptd::launch_display((const float4*)src_rgba, (uint64_t)n_pixels, *dp, c->d_display, (float4*)out_rgba, (uint32_t*)framebuffer_rgba, c->stream));
+    if (info) {
+        if (automatic) CK(c, hipMemcpyAsync(info, &c->d_display->record, sizeof(pt_display_info), hipMemcpyDeviceToHost, c->stream));
+        else { memset(info, 0, sizeof(*info)); info->exposure = dp->exposure; }
+    }
+    CK(c, hipStreamSynchronize(c->stream));
+    c->display_dirty = false;
     return 0;
 }
 

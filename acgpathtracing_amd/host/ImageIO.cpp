@@ -212,6 +212,27 @@ bool loadPFM(const std::string& filename, std::vector<float>& rgb, int& width, i
     return true;
 }
 
+bool savePFM(const std::string& filename, const float* pixels, int width, int height, int channels)
+{
+    if (!pixels || !valid_dims(width, height) || (channels != 3 && channels != 4)) return false;
+    FILE* f = fopen(filename.c_str(), "wb");
+    if (!f) return false;
+    fprintf(f, "PF\n%d %d\n-1.0\n", width, height);
+    uint32_t one = 1; uint8_t host_le = 0; memcpy(&host_le, &one, 1);
+    std::vector<uint8_t> row((size_t)width * 12);
+    bool ok = true;
+    for (int y = 0; y < height && ok; y++) {
+        for (int x = 0; x < width; x++)
+            for (int c = 0; c < 3; c++) {
+                uint8_t* b = row.data() + ((size_t)x * 3 + c) * 4;
+                memcpy(b, pixels + ((size_t)y * width + x) * channels + c, 4);
+                if (!host_le) { std::swap(b[0], b[3]); std::swap(b[1], b[2]); }
+            }
+        ok = fwrite(row.data(), 1, row.size(), f) == row.size();
+    }
+    return fclose(f) == 0 && ok;
+}
+
 bool loadEnvironment(const std::string& filename, std::vector<float>& rgb, int& width, int& height, std::string& err)
 {
     const size_t n = filename.size();

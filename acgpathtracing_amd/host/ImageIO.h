@@ -20,4 +20,9 @@ bool loadHDR(const std::string& filename, std::vector<float>& rgb, int& width, i
 bool loadPFM(const std::string& filename, std::vector<float>& rgb, int& width, int& height, std::string& err);
 bool loadEnvironment(const std::string& filename, std::vector<float>& rgb, int& width, int& height, std::string& err);   // by suffix
 
+// .pfm writer (colour "PF", little-endian, scale -1.0).  pixels: height*width*channels linear floats, channels 3 or 4 (the fourth is
+// dropped); row 0 of the buffer is the BOTTOM row, which is PFM's own order: no flip.  loadPFM(savePFM(x)) returns x's bits, rows
+// reversed.  false on I/O failure.
+bool savePFM(const std::string& filename, const float* pixels, int width, int height, int channels);
+
 }  // namespace acgpt

@@ -13,6 +13,11 @@
 //              [--denoise N] [--history-out file] [--history-in file] [--move material:dx,dy,dz [--move-history]]
 //              [--set-material name:kd=r,g,b[,ke=r,g,b][,bsdf=diffuse|metal|glass][,ior=x] ...]
 //              [--env map.hdr|map.pfm [--env-scale s]] [--no-area-light] [--materials reference|microfacet]
+//              [--tonemap linear|reinhard|aces] [--exposure auto|<EV>] [--out-hdr file.pfm]
+// --tonemap / --exposure: after the last frame, also write <out-stem>_display<ext>: the accumulation (with --denoise N the denoised
+// image) through pt_display_transform — the histogram auto-exposure (auto, the default) or the manual factor 2^EV, computed here, then
+// the tone curve (default aces).  The frames and --out are the same with or without them.  --out-hdr writes the linear accumulation
+// as a .pfm (bottom row first, as the buffer holds it).
 // --materials microfacet (with --light-mode 1): metal and glass honour the MTL's Pr as rough GGX BSDFs (pt_set_material_model); the
 // default, reference, is the reference's materials.
 // --env: an environment map (Radiance .hdr or .pfm, latitude-longitude, top row = +Y) that rays leaving the scene see, scaled by
@@ -233,8 +238,28 @@ static void createProgramGroups(PathTracerState&) {}
 static void createPipeline(PathTracerState&) {}
 static void createShaderBindingTable(PathTracerState&, const TinyObjWrapper&) {}
 
-// the denoised preview of the current accumulation, written as an image next to the frame (--denoise)
-static void saveDenoised(PathTracerState& state, const std::string& path, uint32_t iterations)
+// src (DEVICE float4[width * height], linear) through pt_display_transform, written as an image (--tonemap, --exposure)
+static void saveDisplay(PathTracerState& state, const std::string& path, const float* src, const pt_display_params& dp)
+{
+    const size_t n = (size_t)state.params.width * state.params.height;
+    void* fb = nullptr;
+    std::string err;
+    pt_display_info info;
+    std::vector<uint8_t> host(n * 4);
+    if (pt_device_malloc(state.context, &fb, n * 4) != 0 ||
+        pt_display_transform(state.context, src, n, &dp, nullptr, (uint8_t*)fb, &info) != 0 ||
+        pt_copy_to_host(state.context, host.data(), fb, n * 4) != 0)
+        err = pt_last_error(state.context);
+    if (fb) pt_device_free(state.context, fb);
+    if (!err.empty()) throw Exception("display transform: " + err);
+    std::cout << "Display exposure: " << info.exposure << (dp.exposure > 0.0f ? " (manual)" : " (metered)") << std::endl;
+    if (!saveImage(path, host.data(), (int)state.params.width, (int)state.params.height)) std::cerr << "could not write " << path << std::endl;
+}
+
+// the denoised preview of the current accumulation, written as an image next to the frame (--denoise); with a display transform
+// (dp), that of the denoised image goes to display_path
+static void saveDenoised(PathTracerState& state, const std::string& path, uint32_t iterations, const pt_display_params* dp = nullptr,
+                         const std::string& display_path = std::string())
 {
     const size_t n = (size_t)state.params.width * state.params.height;
     void* bufs[4] = {nullptr, nullptr, nullptr, nullptr};      // albedo_prim, normal_depth, denoised float4, colours uchar4
@@ -247,6 +272,9 @@ static void saveDenoised(PathTracerState& state, const std::string& path, uint32
                         pt_resolve_framebuffer(state.context, (const float*)bufs[2], (uint8_t*)bufs[3], n) != 0 ||
                         pt_copy_to_host(state.context, host.data(), bufs[3], n * 4) != 0))
         err = pt_last_error(state.context);
+    if (err.empty() && dp) {
+        try { saveDisplay(state, display_path, (const float*)bufs[2], *dp); } catch (const std::exception& e) { err = e.what(); }
+    }
     for (void* b : bufs) if (b) pt_device_free(state.context, b);
     if (!err.empty()) throw Exception("denoise: " + err);
     if (!saveImage(path, host.data(), (int)state.params.width, (int)state.params.height)) std::cerr << "could not write " << path << std::endl;
@@ -504,7 +532,7 @@ int main(int argc, char** argv)
     std::vector<std::string> material_edits;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false, move_history = false, no_area_light = false;
-    std::string env_path;
+    std::string env_path, tonemap, exposure_arg, out_hdr;
     float env_scale = 1.0f;
     int orbit_dx = 0, orbit_dy = 0, zoom_steps = 0, sample_chunks = 0, build_mode = 1, fuse = 1, light_mode = 0, math_mode = PT_MATH_FAST, material_model = PT_MATERIALS_REFERENCE;
     PathTracerState state;
@@ -546,6 +574,9 @@ int main(int argc, char** argv)
         else if (a == "--env") env_path = next();
         else if (a == "--env-scale") env_scale = (float)atof(next());
         else if (a == "--no-area-light") no_area_light = true;
+        else if (a == "--tonemap") tonemap = next();
+        else if (a == "--exposure") exposure_arg = next();
+        else if (a == "--out-hdr") out_hdr = next();
         else if (a == "--materials") {
             const std::string m = next();
             if (m == "reference") material_model = PT_MATERIALS_REFERENCE;
@@ -557,6 +588,21 @@ int main(int argc, char** argv)
     }
     if (objfilepath.empty()) { std::cerr << "usage: acgpt_main --obj scene.obj [options]" << std::endl; return 2; }
     if (denoise_iters < 0 || denoise_iters > 8) { std::cerr << "--denoise takes 0 (off) to 8 iterations" << std::endl; return 2; }
+    const bool display = !tonemap.empty() || !exposure_arg.empty();
+    // pt_display_params' defaults (include/acgpt.h): key 0.18, white 4, the window 100 .. 900 permille, exposure within 2^-16 .. 2^16
+    pt_display_params display_params = {PT_TONE_ACES, 0.0f, 0.18f, 4.0f, 100u, 900u, 1.0f / 65536.0f, 65536.0f, 0.0f, 1.0f};
+    if (display) {
+        if (tonemap == "linear") display_params.tone_curve = PT_TONE_LINEAR;
+        else if (tonemap == "reinhard") display_params.tone_curve = PT_TONE_REINHARD;
+        else if (!tonemap.empty() && tonemap != "aces") { std::cerr << "--tonemap linear|reinhard|aces" << std::endl; return 2; }
+        if (!exposure_arg.empty() && exposure_arg != "auto") {
+            char* end = nullptr;
+            const double ev = strtod(exposure_arg.c_str(), &end);
+            const float factor = (float)std::exp2(ev);
+            if (end == exposure_arg.c_str() || *end != '\0' || !std::isfinite(factor) || !(factor > 0.0f)) { std::cerr << "--exposure auto|<EV>" << std::endl; return 2; }
+            display_params.exposure = factor;
+        }
+    }
     if (move_history && move.empty()) { std::cerr << "--move-history needs --move" << std::endl; return 2; }
     std::vector<std::string> key_list;
     { std::stringstream ss(keys); std::string k; while (std::getline(ss, k, ',')) if (!k.empty()) key_list.push_back(k); }
@@ -688,7 +734,13 @@ int main(int argc, char** argv)
             if (!saveImage(out, reinterpret_cast<const uint8_t*>(output_buffer.getHostPointer()), width, height))
                 std::cerr << "could not write " << out << std::endl;
             if (!save_accum.empty()) saveAccumulation(state, save_accum);
-            if (denoise_iters > 0) saveDenoised(state, denoisedName(out), (uint32_t)denoise_iters);
+            if (!out_hdr.empty()) {
+                std::vector<float> host((size_t)width * height * 4);
+                PT_CHECK(state.context, pt_copy_to_host(state.context, host.data(), state.params.accumulationBuffer, host.size() * sizeof(float)));
+                if (!savePFM(out_hdr, host.data(), width, height, 4)) std::cerr << "could not write " << out_hdr << std::endl;
+            }
+            if (denoise_iters > 0) saveDenoised(state, denoisedName(out), (uint32_t)denoise_iters, display ? &display_params : nullptr, suffixedName(out, "_display"));
+            else if (display) saveDisplay(state, suffixedName(out, "_display"), state.params.accumulationBuffer, display_params);
             if (!history_in.empty() || !history_out.empty()) {
                 HistoryFile mine = historyOfRun(state, light_mode, math_mode, material_model);      // the settings at the end: --keys may have changed them
                 if (!history_in.empty()) {

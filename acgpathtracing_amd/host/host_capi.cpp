@@ -90,6 +90,12 @@ HOST_API int pth_load_environment(const char* path, float* rgb, int* width, int*
     return 0;
 }
 
+// pixels: height*width*channels floats (channels 3 or 4), row 0 = bottom (ImageIO.h savePFM)
+HOST_API int pth_save_pfm(const char* path, const float* pixels, int width, int height, int channels)
+{
+    return savePFM(path, pixels, width, height, channels) ? 0 : 1;
+}
+
 HOST_API int pth_save_image(const char* path, const unsigned char* rgba, int width, int height)
 {
     return saveImage(path, rgba, width, height) ? 0 : 1;

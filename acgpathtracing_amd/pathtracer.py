@@ -428,6 +428,17 @@ def readPFM(path):
     return np.ascontiguousarray(np.repeat(a, 3, axis=2) if nc == 1 else a)
 
 
+def writePFM(path, rgb):
+    """The counterpart of readPFM: float32 [H, W, 3] with row 0 = the top row, as a little-endian colour .pfm (the file stores the
+    bottom row first).  readPFM(writePFM(x)) returns x bit for bit."""
+    a = np.asarray(rgb, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("writePFM: an image of shape [H, W, 3], got %s" % (a.shape,))
+    with open(path, "wb") as fh:
+        fh.write(b"PF\n%d %d\n-1.0\n" % (a.shape[1], a.shape[0]))
+        fh.write(np.ascontiguousarray(a[::-1]).astype("<f4").tobytes())
+
+
 def loadEnvironment(path):
     """An environment map file by its suffix (.hdr / .pfm): float32 [H, W, 3], row 0 = the +Y pole."""
     ext = os.path.splitext(path)[1].lower()
@@ -611,6 +622,70 @@ def denoise(state, iterations=5):
         return _read_image(state, bufs[2])
     finally:
         _free_device_buffers(state, bufs)
+
+
+TONE_CURVES = {"linear": _native.TONE_LINEAR, "reinhard": _native.TONE_REINHARD, "aces": _native.TONE_ACES}
+
+
+def displayTransform(state, image=None, curve="aces", exposure=None, key=0.18, white=4.0, window=(100, 900), limits=(2.0 ** -16, 2.0 ** 16),
+                     prev_exposure=None, adapt=1.0):
+    """Exposure and tone mapping of a linear HDR image (include/acgpt.h pt_display_transform): (rgba8 [height, width, 4] with row 0 =
+    bottom, info).  image: None for the state's accumulation buffer, a device pointer to float4[height * width], or a float32
+    [height, width, 4] array (uploaded).  exposure: None for the histogram auto-exposure (key, window = (lo, hi) in permille of the
+    metered pixels, limits = (min, max) exposure, prev_exposure / adapt for eye adaptation), else the manual factor.  curve: "linear",
+    "reinhard" (white point `white`) or "aces".  info: exposure, metered_luminance, metered_pixels, unmetered_pixels, histogram.  The
+    source image is left as it is."""
+    if curve not in TONE_CURVES:
+        raise ValueError("displayTransform: curve must be one of %s" % sorted(TONE_CURVES))
+    if exposure is not None and not float(exposure) > 0.0:
+        raise ValueError("displayTransform: a manual exposure must be > 0 (None: automatic)")
+    L = _native.hip()
+    h, w = int(state.params.height), int(state.params.width)
+    dp = _native.DisplayParams(TONE_CURVES[curve], 0.0 if exposure is None else float(exposure), float(key), float(white), int(window[0]), int(window[1]),
+                               float(limits[0]), float(limits[1]), 0.0 if prev_exposure is None else float(prev_exposure), float(adapt))
+    bufs = _device_buffers(state, 1, w * h * 4)
+    try:
+        if image is None:
+            src = state.params.accumulationBuffer
+        elif isinstance(image, np.ndarray):
+            if image.shape != (h, w, 4):
+                raise ValueError("displayTransform: an image of shape %s, got %s" % ((h, w, 4), image.shape))
+            a = np.ascontiguousarray(image, np.float32)
+            bufs += _device_buffers(state, 1, a.nbytes)
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[1], a.ctypes.data, a.nbytes), "copy to device")
+            src = bufs[1]
+        else:
+            src = int(image)
+        info = _native.DisplayInfo()
+        _check(state.context, L.pt_display_transform(state.context, src, w * h, C.byref(dp), None, bufs[0], C.byref(info)), "pt_display_transform")
+        rgba = np.zeros((h, w, 4), np.uint8)
+        _check(state.context, L.pt_copy_to_host(state.context, rgba.ctypes.data, bufs[0], rgba.nbytes), "copy to host")
+    finally:
+        _free_device_buffers(state, bufs)
+    return rgba, {"exposure": float(info.exposure), "metered_luminance": float(info.metered_luminance), "metered_pixels": int(info.metered_pixels),
+                  "unmetered_pixels": int(info.unmetered_pixels), "histogram": np.array(info.histogram, np.uint32)}
+
+
+class AutoExposure:
+    """Eye adaptation over displayTransform: carries the exposure from call to call.  frame(state, dt) meters the image and moves the
+    exposure towards its target by adapt = 1 - exp(-dt * speed), computed here on the host (dt in seconds since the last call; the
+    first call jumps).  The other arguments are displayTransform's."""
+
+    def __init__(self, speed=3.0, **settings):
+        self.speed = float(speed)
+        self.settings = settings
+        self.exposure = None
+
+    def adapt(self, dt):
+        return float(min(1.0, max(0.0, 1.0 - np.exp(-float(dt) * self.speed))))
+
+    def reset(self):
+        self.exposure = None
+
+    def frame(self, state, dt, image=None):
+        rgba, info = displayTransform(state, image=image, prev_exposure=self.exposure, adapt=self.adapt(dt), **self.settings)
+        self.exposure = info["exposure"]
+        return rgba, info
 
 
 TEMPORAL_HISTORY_CAP = 256.0      # include/acgpt.h pt_temporal_blend: the default cap, calibrated in tests/test_temporal_host.py

@@ -511,6 +511,82 @@ int pt_temporal_blend_motion(pt_ctx* ctx, const pt_params* params, uint32_t accu
                              const pt_params* prev, const float* prev_history, const float* prev_albedo_prim, const float* prev_normal_depth,
                              const float* verts_xyzw, const float* prev_verts_xyzw, size_t n_verts, float history_cap, float clip_gamma,
                              float* out_history);
+
+/* ---- display transform (opt-in; nothing above changes) ------------------------------------------------------------------------
+ * pt_display_transform is the last stage of the preview chain: it meters a linear HDR image (histogram auto-exposure), applies the
+ * exposure and a tone curve, and writes display-linear floats and / or the 8-bit sRGB colours of make_color.  Enqueues on the
+ * context's stream and returns synchronised, acts on rank 0 of a pt_create_multi context, never writes the accumulation buffer, the
+ * context's frame buffer or pt_stats.  A caller of the reference's loop calls it after LaunchCurrentFrame, or after the denoise or
+ * the blend, and before display.
+ *   src_rgba          DEVICE float4[n_pixels] of linear radiance: the accumulation buffer, a pt_denoise output, a temporal history;
+ *                     .w is not read
+ *   out_rgba          DEVICE float4[n_pixels], display-linear {r, g, b, 1} in [0, 1]; must not overlap src_rgba
+ *   framebuffer_rgba  uchar4[n_pixels], device or mapped host, as for pt_resolve_framebuffer: make_color of the same {r, g, b}
+ *   info              HOST, what was metered and applied
+ * Each of out_rgba, framebuffer_rgba and info may be NULL, but not both outputs.  n_pixels in [1, 2^31].
+ * The arithmetic.  All floating point is fp32, one rounding per written operation, no contraction, IEEE division; no transcendental
+ * function anywhere in the metering or the curves (the sRGB powf of make_color is the only one, after them); the metering runs on
+ * integers, so the order of the atomic adds cannot change a bit.  tests/display_ref.py is the NumPy statement of the same thing.
+ *   lum(c) = 0.2126 c.r + 0.7152 c.g + 0.0722 c.b, left to right (pt_denoise's l)
+ *   Metering (exposure == 0):
+ *     a pixel is metered if l = lum(src.rgb) is finite and l >= 2^-20, else it counts in unmetered_pixels
+ *     its bin is k = min((bits(l) >> 20) - 856, 319): eight bins per octave from 2^-20 upward, read off the float's own exponent and
+ *     top three mantissa bits (856 = bits(2^-20) >> 20); counts h_k are uint32; c_k = h_0 + ... + h_(k-1)
+ *     1  n = sum h_k;  r_lo = n * lo_permille / 1000, r_hi = n * hi_permille / 1000  (uint64, integer division)
+ *     2  if r_hi <= r_lo: r_lo = 0, r_hi = n
+ *     3  t_k = max(0, min(c_k + h_k, r_hi) - max(c_k, r_lo)): the pixels of bin k whose rank lies in the window
+ *     4  T = sum t_k,  S = sum t_k * (2k + 1)  (uint64)
+ *     5  L_avg = as_float((856 << 20) + (S << 19) / T)  (integer division): the windowed mean of the bin centres in the piecewise-
+ *        linear log domain, turned back into a float
+ *     6  target = key / L_avg, then max(target, min_exposure), then min(that, max_exposure)
+ *     7  exposure = prev_exposure > 0 ? prev_exposure + (target - prev_exposure) * adapt : target
+ *     n == 0: exposure = prev_exposure > 0 ? prev_exposure : 1, metered_luminance = 0 (no clamp, no adaptation)
+ *     A flat image of luminance L gets key / (the centre of L's bin): within half a bin of key / L, about 4.4 % (2^(1/16); the bins
+ *     are linear inside an octave, so it is 5.9 % in an octave's first bin and 3.2 % in its last).
+ *   Manual (exposure > 0): that factor; nothing is metered, and info holds it, zero counts and a zero histogram.
+ *   Apply, per channel:  v = src * exposure;  x = v > 0 ? (v < 65504 ? v : 65504) : 0  (NaN and negatives 0, infinity 65504)
+ *     PT_TONE_LINEAR    y = min(x, 1)
+ *     PT_TONE_ACES      y = min((x * (2.51 x + 0.03)) / (x * (2.43 x + 0.59) + 0.14), 1)  (Narkowicz 2015)
+ *     PT_TONE_REINHARD  l = lum(x);  s = l > 0 ? (1 + l / (white * white)) / (1 + l) : 0;  y = min(x * s, 1)
+ *     out_rgba = {y.r, y.g, y.b, 1};  framebuffer_rgba = make_color(y), the function behind pt_resolve_framebuffer
+ * Refused before any device work, with a message, leaving the context usable: a NULL src_rgba or params; both outputs NULL; n_pixels
+ * outside [1, 2^31]; an unknown tone curve; a negative or non-finite exposure; in automatic mode a key that is not finite or not
+ * > 0, lo_permille >= hi_permille, hi_permille > 1000, min_exposure or max_exposure not finite, min_exposure <= 0 or > max_exposure,
+ * a negative or non-finite prev_exposure, adapt outside [0, 1]; under PT_TONE_REINHARD a white that is not finite or not > 0;
+ * out_rgba overlapping src_rgba.
+ * Three kernels (csrc/display.hip): a grid-stride histogram (per-wave LDS histograms, one vector atomicAdd per non-empty bin and
+ * workgroup), one wave that turns the counts into the exposure, and the apply pass, which reads the exposure from the device
+ * record: no host round trip in between.  The context keeps the histogram and that record (about 2.6 KB), freed by pt_destroy.  Two
+ * calls give the same bits, and so do the two math modes (pt_set_math_mode does not reach this code).                            */
+#define PT_TONE_LINEAR   0   /* exposure only, clamp */
+#define PT_TONE_REINHARD 1   /* extended Reinhard on luminance, white point `white` */
+#define PT_TONE_ACES     2   /* Narkowicz' fitted ACES curve, per channel */
+
+typedef struct {
+    uint32_t tone_curve;     /* PT_TONE_* */
+    float    exposure;       /* > 0: manual, metering is skipped; 0: automatic */
+    float    key;            /* automatic: target for the metered luminance; default 0.18 */
+    float    white;          /* REINHARD: luminance that maps to 1; finite, > 0; default 4 */
+    uint32_t lo_permille;    /* automatic: share of metered pixels ignored at the dark end; default 100 */
+    uint32_t hi_permille;    /* ... the metering window ends here; default 900; lo < hi <= 1000 */
+    float    min_exposure;   /* clamp of the automatic exposure; 0 < min <= max, finite */
+    float    max_exposure;
+    float    prev_exposure;  /* > 0: the last frame's exposure (eye adaptation); 0: none */
+    float    adapt;          /* in [0, 1]: exposure = prev + (target - prev) * adapt; 1 = jump */
+} pt_display_params;
+
+#define PT_DISPLAY_BINS 320
+typedef struct {
+    float    exposure;            /* the factor that was applied */
+    float    metered_luminance;   /* automatic: L_avg above; manual: 0 */
+    uint32_t metered_pixels;      /* pixels that entered the histogram */
+    uint32_t unmetered_pixels;    /* the rest: luminance below 2^-20, zero, negative or not finite */
+    uint32_t histogram[PT_DISPLAY_BINS];   /* automatic: the counts; manual: zeros */
+} pt_display_info;
+
+int pt_display_transform(pt_ctx* ctx, const float* src_rgba, size_t n_pixels, const pt_display_params* dp,
+                         float* out_rgba, uint8_t* framebuffer_rgba, pt_display_info* info);
+
 /* ---- device memory helpers for bindings that have no HIP runtime of their own
  * (the reference app calls cudaMalloc/cudaMemcpy directly, :145-148).         */
 int pt_device_malloc(pt_ctx* ctx, void** out, size_t bytes);
