@@ -81,6 +81,21 @@ class DisplayInfo(C.Structure):
                 ("histogram", C.c_uint32 * DISPLAY_BINS)]
 
 
+class ConvergenceParams(C.Structure):
+    """pt_convergence_params (include/acgpt.h)."""
+    _fields_ = [("lum_floor", C.c_float), ("threshold", C.c_float), ("quantile_permille", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+CONVERGENCE_BINS, CONVERGENCE_TILE = 256, 16                       # PT_CONVERGENCE_BINS, PT_CONVERGENCE_TILE
+
+
+class ConvergenceInfo(C.Structure):
+    """pt_convergence_info (include/acgpt.h)."""
+    _fields_ = [("frames", C.c_uint32), ("measured_pixels", C.c_uint32), ("unmeasured_pixels", C.c_uint32), ("invalid_pixels", C.c_uint32),
+                ("converged_pixels", C.c_uint32), ("max_error", C.c_float), ("quantile_error", C.c_float), ("reserved", C.c_uint32),
+                ("histogram", C.c_uint32 * CONVERGENCE_BINS)]
+
+
 assert C.sizeof(PathTraceParams) == 168
 assert C.sizeof(Material) == 40
 assert C.sizeof(AreaLight) == 60
@@ -93,6 +108,7 @@ MATH_IEEE, MATH_FAST = 0, 1                                        # pt_set_math
 MATERIALS_REFERENCE, MATERIALS_MICROFACET = 0, 1                   # pt_set_material_model
 TONE_LINEAR, TONE_REINHARD, TONE_ACES = 0, 1, 2                    # pt_display_params.tone_curve
 assert C.sizeof(DisplayParams) == 40 and C.sizeof(DisplayInfo) == 16 + 4 * DISPLAY_BINS
+assert C.sizeof(ConvergenceParams) == 16 and C.sizeof(ConvergenceInfo) == 32 + 4 * CONVERGENCE_BINS
 
 # every symbol include/acgpt.h declares (the drop-in boundary) ...
 ABI_SYMBOLS = [
@@ -100,7 +116,7 @@ ABI_SYMBOLS = [
     "pt_launch", "pt_launch_frames", "pt_resolve_framebuffer", "pt_set_partition", "pt_set_sample_chunks", "pt_set_light_mode", "pt_set_math_mode", "pt_set_scratch_limit", "pt_set_tuning",
     "pt_variant_name", "pt_variant_kernel", "pt_kernel_source_hash", "pt_set_stream", "pt_get_stats",
     "pt_trace_closest", "pt_trace_any", "pt_render_features", "pt_denoise", "pt_temporal_blend", "pt_temporal_blend_motion", "pt_update_vertices", "pt_update_materials", "pt_set_environment",
-    "pt_set_material_model", "pt_display_transform",
+    "pt_set_material_model", "pt_display_transform", "pt_convergence_update",
     "pt_device_malloc", "pt_device_free", "pt_device_memset", "pt_copy_to_host", "pt_copy_to_device",
     "pt_host_malloc_mapped", "pt_host_free_mapped", "pt_abi_version",
 ]
@@ -195,6 +211,8 @@ def hip():
     L.pt_debug_environment.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_debug_environment.restype = C.c_int
     L.pt_set_material_model.argtypes = [vp, C.c_int]; L.pt_set_material_model.restype = C.c_int
     L.pt_display_transform.argtypes = [vp, vp, sz, C.POINTER(DisplayParams), vp, vp, C.POINTER(DisplayInfo)]; L.pt_display_transform.restype = C.c_int
+    L.pt_convergence_update.argtypes = [vp, C.POINTER(PathTraceParams), C.c_uint32, C.POINTER(ConvergenceParams), vp, vp, vp, C.POINTER(ConvergenceInfo)]
+    L.pt_convergence_update.restype = C.c_int
     L.pt_debug_microfacet.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_debug_microfacet.restype = C.c_int
     L.pt_bench_traversal.argtypes = [vp, vp, sz, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_float), vp]; L.pt_bench_traversal.restype = C.c_int
     L.pt_selftest.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_selftest.restype = C.c_int

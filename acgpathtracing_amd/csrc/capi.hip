@@ -26,6 +26,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 
 #include "../../include/acgpt.h"
 #include "../../include/acgpt_test.h"
+#include "convergence.h"
 #include "denoise.h"
 #include "display.h"
 #include "environment.h"
@@ -87,6 +88,7 @@ struct pt_ctx {
     float4* d_denoise[2] = {nullptr, nullptr}; size_t denoise_pixels = 0;   // pt_denoise's ping-pong {colour, variance} buffers
     ptd::EnvDevice env;                       // pt_set_environment's map and CDFs (w == 0: none); the context's, kept across scene changes
     ptd::DisplayState* d_display = nullptr; bool display_dirty = false;     // pt_display_transform's counts and meter record (dirty: a call failed half way)
+    ptd::ConvergenceState* d_convergence = nullptr; bool convergence_dirty = false;   // pt_convergence_update's counts and record (dirty: a call failed half way)
     uint8_t* d_tri_bsdf = nullptr;            // bsdfType per triangle (caller's order): pt_temporal_blend's, built on its first call per scene
     // what pt_update_vertices keeps of the last pt_set_scene: host copies of everything but the vertices, and after the first update
     // the index buffer on the device (freed with the scene)
@@ -329,6 +331,7 @@ static void destroy_one(pt_ctx* c)
     ptd::env_free(c->env);
     for (float4* b : c->d_denoise) if (b) (void)hipFree(b);
     if (c->d_display) (void)hipFree(c->d_display);
+    if (c->d_convergence) (void)hipFree(c->d_convergence);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1559,13 +1562,54 @@ PT_API int pt_display_transform(pt_ctx* c, const float* src_rgba, size_t n_pixel
     return 0;
 }
 
-// ---- temporal reprojection (pt_temporal_blend; kernels in temporal.hip) --------------------------------------------------------
 static bool spans_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
 {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + b_bytes && y < x + a_bytes;
 }
 
+// ---- convergence estimate (pt_convergence_update; kernels in convergence.hip) --------------------------------------------------
+static_assert(sizeof(pt_convergence_params) == 16 && sizeof(pt_convergence_info) == 32 + 4 * PT_CONVERGENCE_BINS,
+              "pt_convergence_params / pt_convergence_info: a change of these layouts bumps pt_abi_version");
+
+PT_API int pt_convergence_update(pt_ctx* c, const pt_params* p, uint32_t accum_frames, const pt_convergence_params* cp, float* state, float* out_error,
+                                 float* out_tiles, pt_convergence_info* info)
+{
+    const std::string f("pt_convergence_update: ");
+    if (!c) return fail(nullptr, f + "null context");
+    if (!p || !cp || !state || !p->accumulationBuffer) return fail(c, f + "null argument");
+    if (p->width == 0 || p->height == 0) return fail(c, f + "width and height must be >= 1");
+    const uint64_t n = (uint64_t)p->width * p->height;
+    if (n > (1ull << 31)) return fail(c, f + "image too large (2^31 pixels)");
+    if (accum_frames < 1u || accum_frames > (1u << 24)) return fail(c, f + "accum_frames must be in [1, 2^24]");
+    if (!std::isfinite(cp->lum_floor) || !(cp->lum_floor > 0.0f)) return fail(c, f + "lum_floor must be finite and > 0");
+    if (!std::isfinite(cp->threshold) || !(cp->threshold > 0.0f)) return fail(c, f + "threshold must be finite and > 0");
+    if (cp->quantile_permille < 1u || cp->quantile_permille > 1000u) return fail(c, f + "quantile_permille must be in [1, 1000]");
+    if (cp->reserved != 0u) return fail(c, f + "reserved must be 0");
+    const uint64_t tiles = (uint64_t)((p->width + PT_CONVERGENCE_TILE - 1u) / PT_CONVERGENCE_TILE) * ((p->height + PT_CONVERGENCE_TILE - 1u) / PT_CONVERGENCE_TILE);
+    const void* bufs[4] = {p->accumulationBuffer, state, out_error, out_tiles};
+    const size_t sizes[4] = {(size_t)n * sizeof(float4), (size_t)n * sizeof(float4), (size_t)n * sizeof(float), (size_t)tiles * sizeof(float)};
+    const char* names[4] = {"the accumulation buffer", "state", "out_error", "out_tiles"};
+    for (int i = 0; i < 4; i++)
+        for (int j = i + 1; j < 4; j++)
+            if (bufs[i] && bufs[j] && spans_overlap(bufs[i], sizes[i], bufs[j], sizes[j])) return fail(c, f + names[j] + " overlaps " + names[i]);
+    CK(c, hipSetDevice(c->device));
+    if (!c->d_convergence || c->convergence_dirty) {
+        if (!c->d_convergence) CK(c, hipMalloc((void**)&c->d_convergence, sizeof(ptd::ConvergenceState)));
+        c->convergence_dirty = true;
+        CK(c, hipMemsetAsync(c->d_convergence, 0, sizeof(ptd::ConvergenceState), c->stream));
+    }
+    Range range("pt_convergence_update");
+    c->convergence_dirty = true;             // until the meter kernel has run to its end and cleared the counts
+    CK(c, ptd::launch_convergence((const float4*)p->accumulationBuffer, p->width, p->height, accum_frames, *cp, (float4*)state, out_error, out_tiles,
+                                  c->d_convergence, c->stream));
+    if (info) CK(c, hipMemcpyAsync(info, &c->d_convergence->record, sizeof(pt_convergence_info), hipMemcpyDeviceToHost, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    c->convergence_dirty = false;
+    return 0;
+}
+
+// ---- temporal reprojection (pt_temporal_blend; kernels in temporal.hip) --------------------------------------------------------
 // the per-triangle bsdfType array: on the first call after pt_set_scene, counted in device_bytes from then on, freed with the scene
 static int ensure_tri_bsdf(pt_ctx* c)
 {

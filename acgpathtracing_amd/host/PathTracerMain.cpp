@@ -14,6 +14,13 @@
 //              [--set-material name:kd=r,g,b[,ke=r,g,b][,bsdf=diffuse|metal|glass][,ior=x] ...]
 //              [--env map.hdr|map.pfm [--env-scale s]] [--no-area-light] [--materials reference|microfacet]
 //              [--tonemap linear|reinhard|aces] [--exposure auto|<EV>] [--out-hdr file.pfm]
+//              [--until-error E [--until-permille P] [--error-floor F] [--error-out file.pfm]]
+// --until-error E: stop when the image is finished instead of after a fixed count.  After every launch (with --fuse-frames, every
+// batch) pt_convergence_update estimates each pixel's relative standard error; the run ends as soon as every pixel has an estimate
+// and --until-permille (default 950) of them are at or below E.  --frames becomes the cap.  --error-floor (default 0.01) is the
+// luminance below which the error is taken against the floor instead of the pixel.  The last line printed names the frames used,
+// the quantile error and the converged share.  --error-out writes the error map as a .pfm (grey in three channels, bottom row
+// first, -1 where a pixel has no estimate).  The frames rendered are the same with or without these options.
 // --tonemap / --exposure: after the last frame, also write <out-stem>_display<ext>: the accumulation (with --denoise N the denoised
 // image) through pt_display_transform — the histogram auto-exposure (auto, the default) or the manual factor 2^EV, computed here, then
 // the tone curve (default aces).  The frames and --out are the same with or without them.  --out-hdr writes the linear accumulation
@@ -532,7 +539,9 @@ int main(int argc, char** argv)
     std::vector<std::string> material_edits;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false, move_history = false, no_area_light = false;
-    std::string env_path, tonemap, exposure_arg, out_hdr;
+    std::string env_path, tonemap, exposure_arg, out_hdr, error_out;
+    // pt_convergence_params' defaults (include/acgpt.h); threshold 0: no --until-error
+    pt_convergence_params until = {0.01f, 0.0f, 950u, 0u};
     float env_scale = 1.0f;
     int orbit_dx = 0, orbit_dy = 0, zoom_steps = 0, sample_chunks = 0, build_mode = 1, fuse = 1, light_mode = 0, math_mode = PT_MATH_FAST, material_model = PT_MATERIALS_REFERENCE;
     PathTracerState state;
@@ -577,6 +586,10 @@ int main(int argc, char** argv)
         else if (a == "--tonemap") tonemap = next();
         else if (a == "--exposure") exposure_arg = next();
         else if (a == "--out-hdr") out_hdr = next();
+        else if (a == "--until-error") { until.threshold = (float)atof(next()); if (!std::isfinite(until.threshold) || !(until.threshold > 0.0f)) { std::cerr << "--until-error takes an error > 0" << std::endl; return 2; } }
+        else if (a == "--until-permille") { const int v = atoi(next()); if (v < 1 || v > 1000) { std::cerr << "--until-permille takes 1 to 1000" << std::endl; return 2; } until.quantile_permille = (uint32_t)v; }
+        else if (a == "--error-floor") { until.lum_floor = (float)atof(next()); if (!std::isfinite(until.lum_floor) || !(until.lum_floor > 0.0f)) { std::cerr << "--error-floor takes a luminance > 0" << std::endl; return 2; } }
+        else if (a == "--error-out") error_out = next();
         else if (a == "--materials") {
             const std::string m = next();
             if (m == "reference") material_model = PT_MATERIALS_REFERENCE;
@@ -604,6 +617,8 @@ int main(int argc, char** argv)
         }
     }
     if (move_history && move.empty()) { std::cerr << "--move-history needs --move" << std::endl; return 2; }
+    const bool until_error = until.threshold > 0.0f;
+    if (!error_out.empty() && !until_error) { std::cerr << "--error-out needs --until-error" << std::endl; return 2; }
     std::vector<std::string> key_list;
     { std::stringstream ss(keys); std::string k; while (std::getline(ss, k, ',')) if (!k.empty()) key_list.push_back(k); }
 
@@ -701,11 +716,22 @@ int main(int argc, char** argv)
         }
         if (state.gpus > 1 || state.multi) std::cout << "Devices: " << pt_device_count(state.context) << std::endl;
         uint64_t rays = 0;
+        std::string stop_line;                  // --until-error: printed last
         pt_update_info moved = {0.0f, 0.0f, 0u, 0u}, material_update = {0.0f, 0.0f, 0u, 0u};
         {
             OutputBuffer<uchar4> output_buffer(zero_copy ? OutputBufferType::ZERO_COPY : OutputBufferType::DEVICE,
                                                state.params.width, state.params.height);
             size_t next_key = 0;
+            const size_t n_pixels = (size_t)width * height;
+            void* conv_state = nullptr; void* conv_error = nullptr;          // --until-error: the estimate's state and its error map
+            pt_convergence_info conv_info;
+            bool conv_done = false;
+            memset(&conv_info, 0, sizeof(conv_info));
+            if (until_error) {
+                PT_CHECK(state.context, pt_device_malloc(state.context, &conv_state, n_pixels * 16));
+                PT_CHECK(state.context, pt_device_memset(state.context, conv_state, 0, n_pixels * 16));
+                if (!error_out.empty()) PT_CHECK(state.context, pt_device_malloc(state.context, &conv_error, n_pixels * 4));
+            }
             for (int f = 0; f < frames;) {
                 auto start = std::chrono::high_resolution_clock::now();
                 if (next_key < key_list.size() && f > 0) { if (!keyCallback(state, key_list[next_key++])) break; }
@@ -729,8 +755,29 @@ int main(int argc, char** argv)
                     saveImage(nm.str(), reinterpret_cast<const uint8_t*>(output_buffer.getHostPointer()), width, height);
                 }
                 f++;
+                if (until_error) {              // one update per launch; a key press that reset the accumulation restarts the estimate by itself
+                    PT_CHECK(state.context, pt_convergence_update(state.context, &state.params, state.params.currentFrameIdx, &until, (float*)conv_state,
+                                                                  (float*)conv_error, nullptr, &conv_info));
+                    if (conv_info.unmeasured_pixels == 0u && conv_info.invalid_pixels == 0u &&
+                        (uint64_t)conv_info.converged_pixels * 1000u >= (uint64_t)conv_info.measured_pixels * until.quantile_permille) { conv_done = true; break; }
+                }
             }
             std::cout << std::endl;
+            if (until_error) {
+                if (!error_out.empty()) {
+                    std::vector<float> err(n_pixels), grey(n_pixels * 3);
+                    PT_CHECK(state.context, pt_copy_to_host(state.context, err.data(), conv_error, n_pixels * sizeof(float)));
+                    for (size_t i = 0; i < n_pixels; i++) grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = err[i];
+                    if (!savePFM(error_out, grey.data(), width, height, 3)) std::cerr << "could not write " << error_out << std::endl;
+                }
+                pt_device_free(state.context, conv_state);
+                if (conv_error) pt_device_free(state.context, conv_error);
+                std::stringstream line;
+                line << "Stopped after " << state.params.currentFrameIdx << " of " << frames << " frames: " << until.quantile_permille << " permille error "
+                     << conv_info.quantile_error << ", " << conv_info.converged_pixels << " of " << conv_info.measured_pixels << " pixels at or below "
+                     << until.threshold << (conv_done ? " (converged)" : " (frame cap)");
+                stop_line = line.str();
+            }
             if (!saveImage(out, reinterpret_cast<const uint8_t*>(output_buffer.getHostPointer()), width, height))
                 std::cerr << "could not write " << out << std::endl;
             if (!save_accum.empty()) saveAccumulation(state, save_accum);
@@ -801,6 +848,7 @@ int main(int argc, char** argv)
         std::cout << "Rays: " << rays << "  Mray/s: " << (total_ms > 0 ? rays / total_ms / 1e3 : 0.0) << std::endl;
         if (!moved_vertices.empty()) std::cout << "Refit: " << moved.ms << " ms  area ratio: " << moved.area_ratio << std::endl;
         if (!edited_materials.empty()) std::cout << "Material update: " << material_update.ms << " ms" << std::endl;
+        if (!stop_line.empty()) std::cout << stop_line << std::endl;
     } catch (const std::exception& e) {
         std::cerr << "Caught exception: " << e.what() << std::endl;
         return 1;

@@ -844,6 +844,131 @@ class TemporalHistory:
         self._state = None
 
 
+class Convergence:
+    """The noise of the accumulated image, and a stopping rule (include/acgpt.h pt_convergence_update).
+
+    update(state) after every launch (or batch of frames) feeds the accumulation to the per-pixel estimate and returns the info
+    record as a dict; `converged` is then true when every pixel has an error, none is invalid and at least `permille` of them have
+    a relative standard error <= threshold.  errorImage() is the per-pixel error, float32 [height, width] with row 0 = bottom and
+    -1 where a pixel has none yet; tiles() the max per 16 x 16 tile, float32 [ceil(height / 16), ceil(width / 16)].  The state is
+    zero-filled, silently, when the image size, the camera or the samples per frame differ from the last update; an accumulation
+    that was restarted (fewer frames than last time) restarts its pixels by itself.  Owns its device buffers: close() frees
+    them, and so does CleanAllTheThings for the context.  maps=False leaves the error image and the tiles out."""
+
+    def __init__(self, threshold=0.02, permille=950, floor=0.01, maps=True):
+        self.threshold, self.permille, self.floor = float(threshold), int(permille), float(floor)
+        self.maps = bool(maps)
+        self.info = None
+        self._state = None
+        self._bufs = []             # state, then out_error and out_tiles
+        self._key = None
+        self._shape = None
+
+    def _bind(self, state):
+        if self._state is None:
+            self._state = state
+            state._temporal.append(self)
+        elif self._state is not state:
+            raise PathTracerError("Convergence: bound to another PathTracerState")
+
+    @staticmethod
+    def _key_of(state):
+        p = state.params
+        return (int(p.width), int(p.height)) + tuple(v.tuple() for v in (p.cameraEye, p.cameraU, p.cameraV, p.cameraW)) + (int(p.samplesPerPixel),)
+
+    @property
+    def converged(self):
+        i = self.info
+        return bool(i) and i["unmeasured_pixels"] == 0 and i["invalid_pixels"] == 0 and i["converged_pixels"] * 1000 >= i["measured_pixels"] * self.permille
+
+    def reset(self):
+        """Zero-fill the state: the next update is a first observation."""
+        if self._bufs:
+            w, h = self._shape
+            _check(self._state.context, _native.hip().pt_device_memset(self._state.context, self._bufs[0], 0, w * h * 16), "state clear")
+        self.info = None
+
+    def update(self, state, accum_frames=None):
+        """accum_frames: the frames the accumulation stands for, by default currentFrameIdx (which the caller advances after a
+        launch)."""
+        self._bind(state)
+        L = _native.hip()
+        p = state.params
+        w, h = int(p.width), int(p.height)
+        key = self._key_of(state)
+        if self._shape != (w, h):
+            _free_device_buffers(state, self._bufs)
+            self._bufs, self._shape = [], None
+            tiles = ((w + _native.CONVERGENCE_TILE - 1) // _native.CONVERGENCE_TILE) * ((h + _native.CONVERGENCE_TILE - 1) // _native.CONVERGENCE_TILE)
+            self._bufs = _device_buffers(state, 1, w * h * 16)
+            if self.maps:
+                self._bufs += _device_buffers(state, 1, w * h * 4) + _device_buffers(state, 1, tiles * 4)
+            self._shape, self._key = (w, h), None
+        if key != self._key:
+            self.reset()
+            self._key = key
+        n = int(p.currentFrameIdx) if accum_frames is None else int(accum_frames)
+        cp = _native.ConvergenceParams(self.floor, self.threshold, self.permille, 0)
+        info = _native.ConvergenceInfo()
+        err, til = (self._bufs[1], self._bufs[2]) if self.maps else (None, None)
+        _check(state.context, L.pt_convergence_update(state.context, C.byref(p), n, C.byref(cp), self._bufs[0], err, til, C.byref(info)), "pt_convergence_update")
+        self.info = {"frames": int(info.frames), "measured_pixels": int(info.measured_pixels), "unmeasured_pixels": int(info.unmeasured_pixels),
+                     "invalid_pixels": int(info.invalid_pixels), "converged_pixels": int(info.converged_pixels), "max_error": float(info.max_error),
+                     "quantile_error": float(info.quantile_error), "histogram": np.array(info.histogram, np.uint32)}
+        return self.info
+
+    def _read(self, index, shape, what):
+        if self._state is None or self.info is None or not self.maps:
+            raise PathTracerError("Convergence.%s: update(state) first (with maps=True)" % what)
+        out = np.zeros(shape, np.float32)
+        _check(self._state.context, _native.hip().pt_copy_to_host(self._state.context, out.ctypes.data, self._bufs[index], out.nbytes), "copy to host")
+        return out
+
+    def stateImage(self):
+        """float32 [height, width, 4] {l0, M2, k0, B} (row 0 = bottom)."""
+        if self._state is None or not self._bufs:
+            raise PathTracerError("Convergence.stateImage: update(state) first")
+        w, h = self._shape
+        out = np.zeros((h, w, 4), np.float32)
+        _check(self._state.context, _native.hip().pt_copy_to_host(self._state.context, out.ctypes.data, self._bufs[0], out.nbytes), "copy to host")
+        return out
+
+    def errorImage(self):
+        w, h = self._shape or (0, 0)
+        return self._read(1, (h, w), "errorImage")
+
+    def tiles(self):
+        w, h = self._shape or (0, 0)
+        t = _native.CONVERGENCE_TILE
+        return self._read(2, ((h + t - 1) // t, (w + t - 1) // t), "tiles")
+
+    def close(self):
+        state = self._state
+        if state is None:
+            return
+        if state.context:
+            _free_device_buffers(state, self._bufs)
+        self._bufs, self._shape, self._key, self.info = [], None, None, None
+        if self in state._temporal:
+            state._temporal.remove(self)
+        self._state = None
+
+
+def renderUntil(output_buffer, state, conv, max_frames, sub_frames=1):
+    """Launch and update until conv.converged or the accumulation stands for max_frames frames: sub_frames frames per launch
+    (LaunchCurrentFrame; the last batch is cut to the cap), currentFrameIdx advanced here, one conv.update per launch.  Returns the
+    frames the accumulation stands for."""
+    sub_frames = max(1, int(sub_frames))
+    while int(state.params.currentFrameIdx) < int(max_frames):
+        n = min(sub_frames, int(max_frames) - int(state.params.currentFrameIdx))
+        LaunchCurrentFrame(output_buffer, state, n)
+        state.params.currentFrameIdx += n
+        conv.update(state)
+        if conv.converged:
+            break
+    return int(state.params.currentFrameIdx)
+
+
 def saveAccumulation(state, filename):
     """The progressive state of the reference — params.accumulationBuffer and currentFrameIdx
     (pathTracerPrograms.cu:803-811) — as a file; same format as acgpt_main --save-accum."""

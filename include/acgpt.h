@@ -587,6 +587,71 @@ typedef struct {
 int pt_display_transform(pt_ctx* ctx, const float* src_rgba, size_t n_pixels, const pt_display_params* dp,
                          float* out_rgba, uint8_t* framebuffer_rgba, pt_display_info* info);
 
+/* ---- convergence estimate (opt-in; nothing above changes) ---------------------------------------------------------------------
+ * pt_convergence_update says when an image is finished and where its noise is: a per-pixel estimate of the relative standard error
+ * of the accumulated mean, a per-tile max of it, and a histogram with a quantile for a stopping rule.  It needs nothing from the
+ * render kernel: after k frames the accumulation holds the running mean A_k, the difference between two successive accumulations
+ * fixes the mean of the frames rendered in between, and a weighted Welford update (West 1979) over those batch means gives an
+ * unbiased variance of the accumulated mean.  Enqueues on the context's stream and returns synchronised, covers the whole image, acts
+ * on rank 0 of a pt_create_multi context, never writes the accumulation buffer, the frame buffer or pt_stats.  A caller of the
+ * reference's loop calls it after LaunchCurrentFrame, once per launch or per batch of frames.
+ *   params        only width, height and accumulationBuffer are read (DEVICE float4[w*h], row 0 at the bottom; .w is not read)
+ *   accum_frames  in [1, 2^24]: the equal-spp frames the accumulation stands for (currentFrameIdx plus the frames just launched)
+ *   state         DEVICE float4[w*h] {l0, M2, k0, B}: the luminance and frame count at the last call, the weighted sum of squares
+ *                 and the number of observations.  The caller owns it, as it owns a temporal history, zero-fills it to start, and
+ *                 passes it to every call; it is updated in place
+ *   out_error     DEVICE float[w*h] or NULL: err below, -1 where the pixel has none yet
+ *   out_tiles     DEVICE float[ceil(w/16) * ceil(h/16)] or NULL, row-major with tile row 0 at the bottom: the max err over the
+ *                 measured pixels of each 16 x 16 tile, -1 for a tile without one
+ *   info          HOST or NULL
+ * The arithmetic.  All floating point is fp32, one rounding per written operation, no contraction, IEEE division and sqrtf; every
+ * reduction runs on integers or is a max, so the order of the atomics cannot change a bit.  tests/convergence_ref.py is the NumPy
+ * statement of the same thing.
+ *   lum as for pt_denoise, left to right;  k1 = (float)accum_frames;  l1 = lum(accum.rgb);  {l0, M2, k0, B} = state
+ *   1  l1 not finite: state = {0, 0, 0, 0}, the pixel counts as invalid (and not as unmeasured), out_error = -1
+ *   2  else if !(k0 > 0) || !(k1 > k0): state = {l1, 0, k1, 1}: a first observation or a restarted accumulation; unmeasured, -1
+ *   3  else n = k1 - k0;  d = l1 - l0;  w = (k0 * k1) / n;  M2' = M2 + w * (d * d);  B' = B + 1;  state = {l1, M2', k1, B'}
+ *      (West's update with the batch mean eliminated: no k A_k - (k - 1) A_(k-1) cancellation); the pixel is measured:
+ *      v = M2' / ((B' - 1) * k1);  sem = sqrtf(v);  err = sem / max(l1, lum_floor)
+ *   over the measured pixels: converged_pixels counts err <= threshold; max_error is the max of bits(err) as uint32 (non-negative
+ *   floats: unsigned order is float order); the histogram bin is clamp((bits(err) >> 20) - 824, 0, 255): eight bins per octave from
+ *   2^-24, both end bins open (a NaN err lands in bin 255); with n = measured_pixels, r = max(1, (n * quantile_permille + 999) /
+ *   1000) in uint64, j the first bin whose inclusive prefix count is >= r, quantile_error = as_float((824 + j + 1) << 20).
+ * Refused before any device work, with a message, leaving the context usable: a NULL ctx, params, cp, state or accumulationBuffer; a
+ * zero width or height, or w * h > 2^31; accum_frames outside [1, 2^24]; a lum_floor or threshold that is not finite or not > 0; a
+ * quantile_permille outside [1, 1000]; a non-zero reserved; state, out_error or out_tiles overlapping the accumulation buffer or
+ * each other.
+ * Two kernels (csrc/convergence.hip): the update, one workgroup per 16 x 16 tile with per-wave LDS counters and one vector atomic
+ * per non-empty slot and workgroup, and one wave that scans the bins for the quantile, writes the record and clears the counts.
+ * The context keeps the counts and that record (about 2 KB), freed by pt_destroy.  Two calls with the same inputs give the same
+ * bits, and so do the two math modes (pt_set_math_mode does not reach this code).
+ * The estimate assumes frames of equal spp and independent seeds (distinct currentFrameIdx); it measures the noise of the luminance,
+ * not bias, and a pixel whose every batch mean is equal (a black pixel, a directly seen light) reads err = 0.                   */
+typedef struct {
+    float    lum_floor;         /* finite, > 0: error = sem / max(l, lum_floor); default 0.01 */
+    float    threshold;         /* finite, > 0: a pixel is converged when its error <= threshold; default 0.02 */
+    uint32_t quantile_permille; /* in [1, 1000]: which quantile of the error info reports; default 950 */
+    uint32_t reserved;          /* 0 */
+} pt_convergence_params;
+
+#define PT_CONVERGENCE_BINS 256
+#define PT_CONVERGENCE_TILE 16
+typedef struct {
+    uint32_t frames;              /* accum_frames of this call */
+    uint32_t measured_pixels;     /* pixels with an error (at least two observations) */
+    uint32_t unmeasured_pixels;   /* one observation so far, or restarted in this call */
+    uint32_t invalid_pixels;      /* luminance not finite: the pixel's state was cleared */
+    uint32_t converged_pixels;    /* measured pixels with error <= threshold */
+    float    max_error;           /* over the measured pixels; 0 if none */
+    float    quantile_error;      /* upper edge of the histogram bin holding the quantile; 0 if none */
+    uint32_t reserved;
+    uint32_t histogram[PT_CONVERGENCE_BINS];
+} pt_convergence_info;
+
+int pt_convergence_update(pt_ctx* ctx, const pt_params* params, uint32_t accum_frames,
+                          const pt_convergence_params* cp, float* state,
+                          float* out_error, float* out_tiles, pt_convergence_info* info);
+
 /* ---- device memory helpers for bindings that have no HIP runtime of their own
  * (the reference app calls cudaMalloc/cudaMemcpy directly, :145-148).         */
 int pt_device_malloc(pt_ctx* ctx, void** out, size_t bytes);
