@@ -96,6 +96,17 @@ class ConvergenceInfo(C.Structure):
                 ("histogram", C.c_uint32 * CONVERGENCE_BINS)]
 
 
+class FireflyParams(C.Structure):
+    """pt_firefly_params (include/acgpt.h)."""
+    _fields_ = [("ratio", C.c_float), ("floor", C.c_float), ("rank", C.c_uint32), ("radius", C.c_uint32)]
+
+
+class FireflyInfo(C.Structure):
+    """pt_firefly_info (include/acgpt.h)."""
+    _fields_ = [("clamped_pixels", C.c_uint32), ("replaced_pixels", C.c_uint32), ("passed_pixels", C.c_uint32), ("reserved", C.c_uint32),
+                ("total_luma_q16", C.c_uint64), ("removed_luma_q16", C.c_uint64), ("max_ratio", C.c_float), ("reserved2", C.c_uint32)]
+
+
 assert C.sizeof(PathTraceParams) == 168
 assert C.sizeof(Material) == 40
 assert C.sizeof(AreaLight) == 60
@@ -109,6 +120,7 @@ MATERIALS_REFERENCE, MATERIALS_MICROFACET = 0, 1                   # pt_set_mate
 TONE_LINEAR, TONE_REINHARD, TONE_ACES = 0, 1, 2                    # pt_display_params.tone_curve
 assert C.sizeof(DisplayParams) == 40 and C.sizeof(DisplayInfo) == 16 + 4 * DISPLAY_BINS
 assert C.sizeof(ConvergenceParams) == 16 and C.sizeof(ConvergenceInfo) == 32 + 4 * CONVERGENCE_BINS
+assert C.sizeof(FireflyParams) == 16 and C.sizeof(FireflyInfo) == 40
 
 # every symbol include/acgpt.h declares (the drop-in boundary) ...
 ABI_SYMBOLS = [
@@ -116,7 +128,7 @@ ABI_SYMBOLS = [
     "pt_launch", "pt_launch_frames", "pt_resolve_framebuffer", "pt_set_partition", "pt_set_sample_chunks", "pt_set_light_mode", "pt_set_math_mode", "pt_set_scratch_limit", "pt_set_tuning",
     "pt_variant_name", "pt_variant_kernel", "pt_kernel_source_hash", "pt_set_stream", "pt_get_stats",
     "pt_trace_closest", "pt_trace_any", "pt_render_features", "pt_denoise", "pt_temporal_blend", "pt_temporal_blend_motion", "pt_update_vertices", "pt_update_materials", "pt_set_environment",
-    "pt_set_material_model", "pt_display_transform", "pt_convergence_update",
+    "pt_set_material_model", "pt_display_transform", "pt_convergence_update", "pt_firefly_filter",
     "pt_device_malloc", "pt_device_free", "pt_device_memset", "pt_copy_to_host", "pt_copy_to_device",
     "pt_host_malloc_mapped", "pt_host_free_mapped", "pt_abi_version",
 ]
@@ -213,6 +225,7 @@ def hip():
     L.pt_display_transform.argtypes = [vp, vp, sz, C.POINTER(DisplayParams), vp, vp, C.POINTER(DisplayInfo)]; L.pt_display_transform.restype = C.c_int
     L.pt_convergence_update.argtypes = [vp, C.POINTER(PathTraceParams), C.c_uint32, C.POINTER(ConvergenceParams), vp, vp, vp, C.POINTER(ConvergenceInfo)]
     L.pt_convergence_update.restype = C.c_int
+    L.pt_firefly_filter.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(FireflyParams), vp, C.POINTER(FireflyInfo)]; L.pt_firefly_filter.restype = C.c_int
     L.pt_debug_microfacet.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_debug_microfacet.restype = C.c_int
     L.pt_bench_traversal.argtypes = [vp, vp, sz, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_float), vp]; L.pt_bench_traversal.restype = C.c_int
     L.pt_selftest.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_selftest.restype = C.c_int

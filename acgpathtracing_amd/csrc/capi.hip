@@ -30,6 +30,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "denoise.h"
 #include "display.h"
 #include "environment.h"
+#include "firefly.h"
 #include "lbvh_build.h"
 #include "materials.h"
 #include "pt_device.h"
@@ -88,6 +89,7 @@ struct pt_ctx {
     float4* d_denoise[2] = {nullptr, nullptr}; size_t denoise_pixels = 0;   // pt_denoise's ping-pong {colour, variance} buffers
     ptd::EnvDevice env;                       // pt_set_environment's map and CDFs (w == 0: none); the context's, kept across scene changes
     ptd::DisplayState* d_display = nullptr; bool display_dirty = false;     // pt_display_transform's counts and meter record (dirty: a call failed half way)
+    ptd::FireflyState* d_firefly = nullptr; bool firefly_dirty = false;     // pt_firefly_filter's counts and record (dirty: a call failed half way)
     ptd::ConvergenceState* d_convergence = nullptr; bool convergence_dirty = false;   // pt_convergence_update's counts and record (dirty: a call failed half way)
     uint8_t* d_tri_bsdf = nullptr;            // bsdfType per triangle (caller's order): pt_temporal_blend's, built on its first call per scene
     // what pt_update_vertices keeps of the last pt_set_scene: host copies of everything but the vertices, and after the first update
@@ -332,6 +334,7 @@ static void destroy_one(pt_ctx* c)
     for (float4* b : c->d_denoise) if (b) (void)hipFree(b);
     if (c->d_display) (void)hipFree(c->d_display);
     if (c->d_convergence) (void)hipFree(c->d_convergence);
+    if (c->d_firefly) (void)hipFree(c->d_firefly);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1606,6 +1609,37 @@ PT_API int pt_convergence_update(pt_ctx* c, const pt_params* p, uint32_t accum_f
     if (info) CK(c, hipMemcpyAsync(info, &c->d_convergence->record, sizeof(pt_convergence_info), hipMemcpyDeviceToHost, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     c->convergence_dirty = false;
+    return 0;
+}
+
+// ---- firefly filter (pt_firefly_filter; kernels in firefly.hip) -----------------------------------------------------------------
+static_assert(sizeof(pt_firefly_params) == 16 && sizeof(pt_firefly_info) == 40, "pt_firefly_params / pt_firefly_info: a change of these layouts bumps pt_abi_version");
+
+PT_API int pt_firefly_filter(pt_ctx* c, const float* src_rgba, uint32_t width, uint32_t height, const pt_firefly_params* fp, float* out_rgba, pt_firefly_info* info)
+{
+    const std::string f("pt_firefly_filter: ");
+    if (!c) return fail(nullptr, f + "null context");
+    if (!src_rgba || !fp || !out_rgba) return fail(c, f + "null argument");
+    if (width == 0 || height == 0) return fail(c, f + "width and height must be >= 1");
+    const uint64_t n = (uint64_t)width * height;
+    if (n > (1ull << 31)) return fail(c, f + "image too large (2^31 pixels)");
+    if (!std::isfinite(fp->ratio) || !(fp->ratio >= 1.0f)) return fail(c, f + "ratio must be finite and >= 1");
+    if (!std::isfinite(fp->floor) || !(fp->floor > 0.0f)) return fail(c, f + "floor must be finite and > 0");
+    if (fp->rank < 1u || fp->rank > 4u) return fail(c, f + "rank must be in [1, 4]");
+    if (fp->radius < 1u || fp->radius > 2u) return fail(c, f + "radius must be 1 or 2");
+    if (spans_overlap(src_rgba, (size_t)n * sizeof(float4), out_rgba, (size_t)n * sizeof(float4))) return fail(c, f + "out_rgba overlaps src_rgba");
+    CK(c, hipSetDevice(c->device));
+    if (!c->d_firefly || c->firefly_dirty) {
+        if (!c->d_firefly) CK(c, hipMalloc((void**)&c->d_firefly, sizeof(ptd::FireflyState)));
+        c->firefly_dirty = true;
+        CK(c, hipMemsetAsync(c->d_firefly, 0, sizeof(ptd::FireflyState), c->stream));
+    }
+    Range range("pt_firefly_filter");
+    c->firefly_dirty = true;                 // until the finish kernel has run to its end and cleared the counts
+    CK(c, ptd::launch_firefly((const float4*)src_rgba, width, height, *fp, (float4*)out_rgba, c->d_firefly, c->stream));
+    if (info) CK(c, hipMemcpyAsync(info, &c->d_firefly->record, sizeof(pt_firefly_info), hipMemcpyDeviceToHost, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    c->firefly_dirty = false;
     return 0;
 }
 

@@ -15,6 +15,11 @@
 //              [--env map.hdr|map.pfm [--env-scale s]] [--no-area-light] [--materials reference|microfacet]
 //              [--tonemap linear|reinhard|aces] [--exposure auto|<EV>] [--out-hdr file.pfm]
 //              [--until-error E [--until-permille P] [--error-floor F] [--error-out file.pfm]]
+//              [--firefly ratio[,rank[,radius]]]
+// --firefly: after the last frame the accumulation goes through pt_firefly_filter into a buffer of its own, and that image is what
+// --out, --out-hdr, --denoise and --tonemap see; --save-accum, --history-out and --until-error keep the raw accumulation (the
+// convergence estimate measures the renderer's noise, not a clamped image).  One line names the pixels clamped and replaced, the
+// share of the luminance removed and the largest excess.  rank defaults to 1, radius to 1.
 // --until-error E: stop when the image is finished instead of after a fixed count.  After every launch (with --fuse-frames, every
 // batch) pt_convergence_update estimates each pixel's relative standard error; the run ends as soon as every pixel has an estimate
 // and --until-permille (default 950) of them are at or below E.  --frames becomes the cap.  --error-floor (default 0.01) is the
@@ -266,8 +271,10 @@ static void saveDisplay(PathTracerState& state, const std::string& path, const f
 // the denoised preview of the current accumulation, written as an image next to the frame (--denoise); with a display transform
 // (dp), that of the denoised image goes to display_path
 static void saveDenoised(PathTracerState& state, const std::string& path, uint32_t iterations, const pt_display_params* dp = nullptr,
-                         const std::string& display_path = std::string())
+                         const std::string& display_path = std::string(), const float* image = nullptr)
 {
+    auto params = state.params;                 // image (--firefly): denoise that instead of the accumulation
+    if (image) params.accumulationBuffer = const_cast<float*>(image);
     const size_t n = (size_t)state.params.width * state.params.height;
     void* bufs[4] = {nullptr, nullptr, nullptr, nullptr};      // albedo_prim, normal_depth, denoised float4, colours uchar4
     std::string err;
@@ -275,7 +282,7 @@ static void saveDenoised(PathTracerState& state, const std::string& path, uint32
         if (pt_device_malloc(state.context, &bufs[i], n * (i < 3 ? 16 : 4)) != 0) err = pt_last_error(state.context);
     std::vector<uint8_t> host(n * 4);
     if (err.empty() && (pt_render_features(state.context, &state.params, (float*)bufs[0], (float*)bufs[1]) != 0 ||
-                        pt_denoise(state.context, &state.params, (const float*)bufs[0], (const float*)bufs[1], (float*)bufs[2], iterations) != 0 ||
+                        pt_denoise(state.context, &params, (const float*)bufs[0], (const float*)bufs[1], (float*)bufs[2], iterations) != 0 ||
                         pt_resolve_framebuffer(state.context, (const float*)bufs[2], (uint8_t*)bufs[3], n) != 0 ||
                         pt_copy_to_host(state.context, host.data(), bufs[3], n * 4) != 0))
         err = pt_last_error(state.context);
@@ -540,6 +547,7 @@ int main(int argc, char** argv)
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false, move_history = false, no_area_light = false;
     std::string env_path, tonemap, exposure_arg, out_hdr, error_out;
+    pt_firefly_params firefly = {0.0f, 0.01f, 1u, 1u};       // ratio 0: no --firefly; the other defaults of include/acgpt.h
     // pt_convergence_params' defaults (include/acgpt.h); threshold 0: no --until-error
     pt_convergence_params until = {0.01f, 0.0f, 950u, 0u};
     float env_scale = 1.0f;
@@ -590,6 +598,14 @@ int main(int argc, char** argv)
         else if (a == "--until-permille") { const int v = atoi(next()); if (v < 1 || v > 1000) { std::cerr << "--until-permille takes 1 to 1000" << std::endl; return 2; } until.quantile_permille = (uint32_t)v; }
         else if (a == "--error-floor") { until.lum_floor = (float)atof(next()); if (!std::isfinite(until.lum_floor) || !(until.lum_floor > 0.0f)) { std::cerr << "--error-floor takes a luminance > 0" << std::endl; return 2; } }
         else if (a == "--error-out") error_out = next();
+        else if (a == "--firefly") {
+            int rank = 1, radius = 1;
+            const int got = sscanf(next(), "%f,%d,%d", &firefly.ratio, &rank, &radius);
+            if (got < 1 || !std::isfinite(firefly.ratio) || !(firefly.ratio >= 1.0f) || rank < 1 || rank > 4 || radius < 1 || radius > 2) {
+                std::cerr << "--firefly takes ratio[,rank[,radius]]: ratio >= 1, rank 1 to 4, radius 1 or 2" << std::endl; return 2;
+            }
+            firefly.rank = (uint32_t)rank; firefly.radius = (uint32_t)radius;
+        }
         else if (a == "--materials") {
             const std::string m = next();
             if (m == "reference") material_model = PT_MATERIALS_REFERENCE;
@@ -778,16 +794,35 @@ int main(int argc, char** argv)
                      << until.threshold << (conv_done ? " (converged)" : " (frame cap)");
                 stop_line = line.str();
             }
-            if (!saveImage(out, reinterpret_cast<const uint8_t*>(output_buffer.getHostPointer()), width, height))
+            void* filtered = nullptr;               // --firefly: the image the outputs below see instead of the accumulation
+            if (firefly.ratio > 0.0f) {
+                pt_firefly_info fi;
+                void* fb = nullptr;
+                std::vector<uint8_t> host(n_pixels * 4);
+                PT_CHECK(state.context, pt_device_malloc(state.context, &filtered, n_pixels * 16));
+                PT_CHECK(state.context, pt_device_malloc(state.context, &fb, n_pixels * 4));
+                PT_CHECK(state.context, pt_firefly_filter(state.context, state.params.accumulationBuffer, (uint32_t)width, (uint32_t)height, &firefly,
+                                                          (float*)filtered, &fi));
+                PT_CHECK(state.context, pt_resolve_framebuffer(state.context, (const float*)filtered, (uint8_t*)fb, n_pixels));
+                PT_CHECK(state.context, pt_copy_to_host(state.context, host.data(), fb, n_pixels * 4));
+                pt_device_free(state.context, fb);
+                std::cout << "Firefly filter: " << fi.clamped_pixels << " clamped, " << fi.replaced_pixels << " replaced, " << fi.passed_pixels
+                          << " passed; removed share " << (fi.total_luma_q16 ? (double)fi.removed_luma_q16 / (double)fi.total_luma_q16 : 0.0)
+                          << ", max ratio " << fi.max_ratio << std::endl;
+                if (!saveImage(out, host.data(), width, height)) std::cerr << "could not write " << out << std::endl;
+            } else if (!saveImage(out, reinterpret_cast<const uint8_t*>(output_buffer.getHostPointer()), width, height))
                 std::cerr << "could not write " << out << std::endl;
+            const float* shown = filtered ? (const float*)filtered : state.params.accumulationBuffer;
             if (!save_accum.empty()) saveAccumulation(state, save_accum);
             if (!out_hdr.empty()) {
                 std::vector<float> host((size_t)width * height * 4);
-                PT_CHECK(state.context, pt_copy_to_host(state.context, host.data(), state.params.accumulationBuffer, host.size() * sizeof(float)));
+                PT_CHECK(state.context, pt_copy_to_host(state.context, host.data(), shown, host.size() * sizeof(float)));
                 if (!savePFM(out_hdr, host.data(), width, height, 4)) std::cerr << "could not write " << out_hdr << std::endl;
             }
-            if (denoise_iters > 0) saveDenoised(state, denoisedName(out), (uint32_t)denoise_iters, display ? &display_params : nullptr, suffixedName(out, "_display"));
-            else if (display) saveDisplay(state, suffixedName(out, "_display"), state.params.accumulationBuffer, display_params);
+            if (denoise_iters > 0) saveDenoised(state, denoisedName(out), (uint32_t)denoise_iters, display ? &display_params : nullptr, suffixedName(out, "_display"),
+                                                (const float*)filtered);
+            else if (display) saveDisplay(state, suffixedName(out, "_display"), shown, display_params);
+            if (filtered) pt_device_free(state.context, filtered);
             if (!history_in.empty() || !history_out.empty()) {
                 HistoryFile mine = historyOfRun(state, light_mode, math_mode, material_model);      // the settings at the end: --keys may have changed them
                 if (!history_in.empty()) {

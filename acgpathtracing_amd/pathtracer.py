@@ -610,15 +610,85 @@ def renderFeatures(state):
         _free_device_buffers(state, bufs)
 
 
-def denoise(state, iterations=5):
+# pt_firefly_params' defaults (include/acgpt.h; DESIGN.md section 20 has the calibration)
+FIREFLY_DEFAULTS = {"ratio": 16.0, "rank": 1, "radius": 1, "floor": 0.01}
+
+
+def _firefly_params(settings, what):
+    unknown = set(settings) - set(FIREFLY_DEFAULTS)
+    if unknown:
+        raise ValueError("%s: unknown firefly settings %s (known: %s)" % (what, sorted(unknown), sorted(FIREFLY_DEFAULTS)))
+    d = dict(FIREFLY_DEFAULTS)
+    d.update(settings)
+    return _native.FireflyParams(float(d["ratio"]), float(d["floor"]), int(d["rank"]), int(d["radius"]))
+
+
+def _firefly_info(info):
+    total, removed = int(info.total_luma_q16), int(info.removed_luma_q16)
+    return {"clamped_pixels": int(info.clamped_pixels), "replaced_pixels": int(info.replaced_pixels), "passed_pixels": int(info.passed_pixels),
+            "total_luma_q16": total, "removed_luma_q16": removed, "max_ratio": float(info.max_ratio), "removed_share": removed / total if total else 0.0}
+
+
+def fireflyFilter(state, image=None, ratio=FIREFLY_DEFAULTS["ratio"], rank=FIREFLY_DEFAULTS["rank"], radius=FIREFLY_DEFAULTS["radius"],
+                  floor=FIREFLY_DEFAULTS["floor"]):
+    """Outlier pixels clamped and invalid ones replaced (include/acgpt.h pt_firefly_filter): (float32 [height, width, 4], info).  image:
+    None for the state's accumulation buffer, a device pointer to float4[height * width], or a float32 [height, width, 4] array
+    (uploaded).  A pixel may be `ratio` times brighter than the rank-th brightest valid pixel of its (2 radius + 1)^2 window, taken no
+    darker than `floor`.  info: clamped_pixels, replaced_pixels, passed_pixels, total_luma_q16, removed_luma_q16, max_ratio and
+    removed_share, the part of the image's luminance the clamp took.  The source image is left as it is."""
+    L = _native.hip()
+    h, w = int(state.params.height), int(state.params.width)
+    fp = _firefly_params({"ratio": ratio, "rank": rank, "radius": radius, "floor": floor}, "fireflyFilter")
+    bufs = _device_buffers(state, 1, w * h * 16)
+    try:
+        if image is None:
+            src = state.params.accumulationBuffer
+        elif isinstance(image, np.ndarray):
+            if image.shape != (h, w, 4):
+                raise ValueError("fireflyFilter: an image of shape %s, got %s" % ((h, w, 4), image.shape))
+            a = np.ascontiguousarray(image, np.float32)
+            bufs += _device_buffers(state, 1, a.nbytes)
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[1], a.ctypes.data, a.nbytes), "copy to device")
+            src = bufs[1]
+        else:
+            src = int(image)
+        info = _native.FireflyInfo()
+        _check(state.context, L.pt_firefly_filter(state.context, src, w, h, C.byref(fp), bufs[0], C.byref(info)), "pt_firefly_filter")
+        out = _read_image(state, bufs[0])
+    finally:
+        _free_device_buffers(state, bufs)
+    return out, _firefly_info(info)
+
+
+def _denoise_filtered(state, params, albedo, normal_depth, out, iterations, firefly, width, height):
+    """pt_denoise of params' accumulation through pt_firefly_filter first: the filter writes a buffer of its own and the denoiser gets
+    a copy of params that names it; params and the accumulation are left as they are."""
+    L = _native.hip()
+    fp = _firefly_params(firefly, "denoise")
+    tmp = _device_buffers(state, 1, width * height * 16)
+    try:
+        _check(state.context, L.pt_firefly_filter(state.context, params.accumulationBuffer, width, height, C.byref(fp), tmp[0], None), "pt_firefly_filter")
+        q = PathTraceParams()
+        C.memmove(C.byref(q), C.byref(params), C.sizeof(q))
+        q.accumulationBuffer = tmp[0]
+        _check(state.context, L.pt_denoise(state.context, C.byref(q), albedo, normal_depth, out, int(iterations)), "pt_denoise")
+    finally:
+        _free_device_buffers(state, tmp)
+
+
+def denoise(state, iterations=5, firefly=None):
     """The accumulation buffer through the edge-avoiding a-trous filter (include/acgpt.h pt_denoise), guided by the features of the
-    current camera: float32 [height, width, 4] linear radiance, alpha 1.  The accumulation itself is left as it is."""
+    current camera: float32 [height, width, 4] linear radiance, alpha 1.  The accumulation itself is left as it is.  firefly: None, or
+    a dict of fireflyFilter's settings ({} for the defaults): the accumulation goes through pt_firefly_filter first."""
     nbytes = int(state.params.width) * int(state.params.height) * 16
     bufs = _device_buffers(state, 3, nbytes)
     try:
         L = _native.hip()
         _check(state.context, L.pt_render_features(state.context, C.byref(state.params), bufs[0], bufs[1]), "pt_render_features")
-        _check(state.context, L.pt_denoise(state.context, C.byref(state.params), bufs[0], bufs[1], bufs[2], int(iterations)), "pt_denoise")
+        if firefly is None:
+            _check(state.context, L.pt_denoise(state.context, C.byref(state.params), bufs[0], bufs[1], bufs[2], int(iterations)), "pt_denoise")
+        else:
+            _denoise_filtered(state, state.params, bufs[0], bufs[1], bufs[2], iterations, firefly, int(state.params.width), int(state.params.height))
         return _read_image(state, bufs[2])
     finally:
         _free_device_buffers(state, bufs)
@@ -810,8 +880,9 @@ class TemporalHistory:
         return L.pt_temporal_blend_motion(state.context, C.byref(p), n, alb, nd, C.byref(prev.params), prev.bufs[0], prev.bufs[1], prev.bufs[2],
                                           cur.verts_buf[0], prev.verts_buf[0], n_verts, self.cap, gamma, hist)
 
-    def denoise(self, state, iterations=5):
-        """The last update's history through pt_denoise (guided by the same features): float32 [height, width, 4], alpha 1."""
+    def denoise(self, state, iterations=5, firefly=None):
+        """The last update's history through pt_denoise (guided by the same features): float32 [height, width, 4], alpha 1.  firefly:
+        None, or a dict of fireflyFilter's settings: the history goes through pt_firefly_filter first (and is left as it is)."""
         cur = self._views[self._cur]
         if self._state is not state or not cur.valid:
             raise PathTracerError("TemporalHistory.denoise: update(state) first")
@@ -820,7 +891,10 @@ class TemporalHistory:
         q.accumulationBuffer = cur.bufs[0]              # pt_denoise reads .xyz only
         out = _device_buffers(state, 1, cur.pixels * 16)
         try:
-            _check(state.context, _native.hip().pt_denoise(state.context, C.byref(q), cur.bufs[1], cur.bufs[2], out[0], int(iterations)), "pt_denoise")
+            if firefly is None:
+                _check(state.context, _native.hip().pt_denoise(state.context, C.byref(q), cur.bufs[1], cur.bufs[2], out[0], int(iterations)), "pt_denoise")
+            else:
+                _denoise_filtered(state, q, cur.bufs[1], cur.bufs[2], out[0], iterations, firefly, int(q.width), int(q.height))
             h, w = int(q.height), int(q.width)
             img = np.zeros((h, w, 4), np.float32)
             _check(state.context, _native.hip().pt_copy_to_host(state.context, img.ctypes.data, out[0], img.nbytes), "copy to host")

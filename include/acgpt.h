@@ -652,6 +652,64 @@ int pt_convergence_update(pt_ctx* ctx, const pt_params* params, uint32_t accum_f
                           const pt_convergence_params* cp, float* state,
                           float* out_error, float* out_tiles, pt_convergence_info* info);
 
+/* ---- firefly filter (opt-in; nothing above changes) ---------------------------------------------------------------------------
+ * pt_firefly_filter clamps isolated outlier pixels ahead of the denoiser and replaces pixels that hold no usable value: a pixel may
+ * be `ratio` times brighter than the rank-th brightest of its 3 x 3 or 5 x 5 neighbours and no more.  pt_denoise widens its
+ * luminance stop with the local variance, so one spike opens the stop of its whole neighbourhood and is spread into a blob; a NaN
+ * or an infinity in the accumulation passes every other stage untouched.  The clamp removes energy, which is a bias: info reports
+ * how much.  Enqueues on the context's stream and returns synchronised, acts on rank 0 of a pt_create_multi context, needs no scene,
+ * never touches the accumulation buffer (unless it is passed as src, which is only read), the frame buffer or pt_stats.  A caller of
+ * the reference's loop calls it between LaunchCurrentFrame and the denoiser.
+ *   src_rgba   DEVICE float4[width * height], row-major; only read
+ *   out_rgba   DEVICE float4[width * height]; must not overlap src_rgba (refused, not undefined)
+ *   info       HOST or NULL (NULL skips only the copy to the host)
+ * The arithmetic.  All floating point is fp32, one rounding per written operation, no contraction, IEEE division; the reductions are
+ * integer sums and a max of bit patterns, so the order of the atomics cannot change a bit.  tests/firefly_ref.py is the NumPy
+ * statement of the same thing.
+ *   l(p) = (0.2126f * r + 0.7152f * g) + 0.0722f * b;   valid(p): l(p) is finite and l(p) >= 0
+ *   N(p): the taps q = p + (dx, dy), dx and dy in [-radius, radius] without (0, 0), dy outer, dx inner, both ascending, that lie
+ *         inside the image and are valid
+ *   R(p): the rank-th largest l(q) over N(p), counted with multiplicity; undefined when |N(p)| < rank
+ *   1  valid p, R undefined: out = src, all four floats as bits; the pixel passes
+ *   2  valid p, R defined: t = ratio * max(R(p), floor); if l(p) > t: s = t / l(p), out.rgb = rgb * s, the pixel is clamped;
+ *      otherwise out = src as bits and the pixel passes
+ *   3  invalid p: out.rgb = (the sum of src.rgb over N(p), per channel, added in tap order from 0.0f) / (float)|N(p)|, or (0, 0, 0)
+ *      when N(p) is empty; the pixel is replaced
+ *   out.w is src.w as bits in every case (pt_temporal_blend keeps a sample count there).  Neighbours are read from src, never from
+ *   out: the result does not depend on the execution order and two calls give the same bits.
+ *   info: clamped_pixels + replaced_pixels + passed_pixels = width * height; max_ratio is the max of bits(l(p) / t) as uint32 over
+ *   the clamped pixels (positive floats: unsigned order is float order), 0 if none; removed_luma_q16 is the sum over the clamped
+ *   pixels of (uint64) trunc(min(l(p) - t, 2^24) * 65536) and total_luma_q16 the sum over the valid pixels of (uint64) trunc(min(l(p),
+ *   2^24) * 65536), both modulo 2^64: removed / total is the share of the image's energy the filter took.
+ * Refused before any device work, with a message, leaving the context usable: a NULL ctx, src_rgba, fp or out_rgba; a zero width or
+ * height, or width * height > 2^31; a ratio that is not finite or < 1; a floor that is not finite or not > 0; a rank outside [1, 4];
+ * a radius other than 1 or 2; out_rgba overlapping src_rgba.
+ * Two kernels (csrc/firefly.hip): the filter, one workgroup per 16 x 16 tile with the tile's luminances and their halo in LDS and
+ * one vector atomic per workgroup and field, and one lane that writes the record and clears the counts.  The context keeps the
+ * counts and that record (72 bytes), freed by pt_destroy.  pt_set_math_mode does not reach this code.
+ * An edge between two materials or at an emitter survives: an edge pixel has neighbours on its own side.  A bright feature thinner
+ * than `rank` pixels of a window does not; raise rank to keep it.                                                                */
+typedef struct pt_firefly_params {
+    float    ratio;    /* finite, >= 1: a pixel may be this many times brighter than its reference neighbour; default 16 */
+    float    floor;    /* finite, > 0: the reference luminance is never taken below this; default 0.01 */
+    uint32_t rank;     /* 1..4: the reference neighbour is the rank-th brightest; default 1 */
+    uint32_t radius;   /* 1 or 2: a 3 x 3 or a 5 x 5 window; default 1 */
+} pt_firefly_params;
+
+typedef struct pt_firefly_info {
+    uint32_t clamped_pixels;    /* valid pixels scaled down to their limit */
+    uint32_t replaced_pixels;   /* invalid pixels (NaN, infinite or negative luminance) replaced by their neighbours' mean */
+    uint32_t passed_pixels;     /* valid pixels left as they were */
+    uint32_t reserved;
+    uint64_t total_luma_q16;    /* the luminance of the valid pixels, in 2^-16 */
+    uint64_t removed_luma_q16;  /* the luminance the clamp took, in 2^-16 */
+    float    max_ratio;         /* the largest l / t among the clamped pixels; 0 if none */
+    uint32_t reserved2;
+} pt_firefly_info;
+
+int pt_firefly_filter(pt_ctx* ctx, const float* src_rgba, uint32_t width, uint32_t height,
+                      const pt_firefly_params* fp, float* out_rgba, pt_firefly_info* info);
+
 /* ---- device memory helpers for bindings that have no HIP runtime of their own
  * (the reference app calls cudaMalloc/cudaMemcpy directly, :145-148).         */
 int pt_device_malloc(pt_ctx* ctx, void** out, size_t bytes);
