@@ -31,6 +31,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "display.h"
 #include "environment.h"
 #include "firefly.h"
+#include "image_common.h"
 #include "lbvh_build.h"
 #include "materials.h"
 #include "pt_device.h"
@@ -1415,27 +1416,34 @@ PT_API int pt_get_stats(pt_ctx* c, pt_stats* out)
     return 0;
 }
 
+// The round trip of the ray queries and the debug entry points: upload in_bytes, launch(d_in, d_a, d_b) on the context's stream,
+// download the one or two outputs (bytes_b == 0: no second one, d_b is null).  fn: the entry point's name.
+template <typename F>
+static int device_round_trip(pt_ctx* c, const char* fn, const void* in, size_t in_bytes, void* out_a, size_t bytes_a, void* out_b, size_t bytes_b, F launch)
+{
+    void* d_in = nullptr; void* d_a = nullptr; void* d_b = nullptr;
+    hipError_t e = hipMalloc(&d_in, in_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_a, bytes_a);
+    if (e == hipSuccess && bytes_b) e = hipMalloc(&d_b, bytes_b);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch(d_in, d_a, d_b);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_a, d_a, bytes_a, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && bytes_b) e = hipMemcpyAsync(out_b, d_b, bytes_b, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (d_in) (void)hipFree(d_in);
+    if (d_a) (void)hipFree(d_a);
+    if (d_b) (void)hipFree(d_b);
+    if (e != hipSuccess) return fail(c, std::string(fn) + ": " + hipGetErrorString(e));
+    return 0;
+}
+
 template <typename F>
 static int trace_common(pt_ctx* c, const float* rays, size_t n, size_t out_bytes_a, void* out_a, size_t out_bytes_b, void* out_b, F launch)
 {
     if (n == 0) return 0;
     if (n > 0x7FFFFFFFull) return fail(c, "pt_trace: too many rays");
     CK(c, hipSetDevice(c->device));
-    float* d_rays = nullptr; void* d_a = nullptr; void* d_b = nullptr;
-    int rc = 0;
-    hipError_t e = hipMalloc((void**)&d_rays, n * 32);
-    if (e == hipSuccess) e = hipMalloc(&d_a, out_bytes_a);
-    if (e == hipSuccess && out_bytes_b) e = hipMalloc(&d_b, out_bytes_b);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rays, rays, n * 32, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch(d_rays, d_a, d_b);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_a, d_a, out_bytes_a, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && out_bytes_b) e = hipMemcpyAsync(out_b, d_b, out_bytes_b, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) rc = fail(c, std::string("pt_trace: ") + hipGetErrorString(e));
-    if (d_rays) (void)hipFree(d_rays);
-    if (d_a) (void)hipFree(d_a);
-    if (d_b) (void)hipFree(d_b);
-    return rc;
+    return device_round_trip(c, "pt_trace", rays, n * 32, out_a, out_bytes_a, out_b, out_bytes_b, launch);
 }
 
 PT_API int pt_trace_closest(pt_ctx* c, const float* rays, size_t n, float* t_out, uint32_t* prim_out)
@@ -1446,8 +1454,8 @@ PT_API int pt_trace_closest(pt_ctx* c, const float* rays, size_t n, float* t_out
     const ptd::DeviceScene sc = device_scene(c);
     const uint32_t se = c->stack_entries;
     hipStream_t s = c->stream;
-    return trace_common(c, rays, n, n * 4, t_out, n * 4, prim_out, [&](float* d_rays, void* a, void* b) {
-        return ptd::launch_trace_closest(sc, se, d_rays, (uint32_t)n, (float*)a, (uint32_t*)b, s);
+    return trace_common(c, rays, n, n * 4, t_out, n * 4, prim_out, [&](void* d_rays, void* a, void* b) {
+        return ptd::launch_trace_closest(sc, se, (const float*)d_rays, (uint32_t)n, (float*)a, (uint32_t*)b, s);
     });
 }
 
@@ -1459,16 +1467,16 @@ PT_API int pt_trace_any(pt_ctx* c, const float* rays, size_t n, uint8_t* hit_out
     const ptd::DeviceScene sc = device_scene(c);
     const uint32_t se = c->stack_entries;
     hipStream_t s = c->stream;
-    return trace_common(c, rays, n, n, hit_out, 0, nullptr, [&](float* d_rays, void* a, void*) {
-        return ptd::launch_trace_any(sc, se, d_rays, (uint32_t)n, (uint8_t*)a, s);
+    return trace_common(c, rays, n, n, hit_out, 0, nullptr, [&](void* d_rays, void* a, void*) {
+        return ptd::launch_trace_any(sc, se, (const float*)d_rays, (uint32_t)n, (uint8_t*)a, s);
     });
 }
 
 // ---- denoised preview (pt_render_features, pt_denoise; kernels in denoise.hip) -------------------------------------------------
-static bool overlaps(const void* a, const void* b, size_t bytes)
+static bool spans_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
 {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bytes && y < x + bytes;
+    return x < y + b_bytes && y < x + a_bytes;
 }
 
 static int check_image(pt_ctx* c, const pt_params* p, const char* what)
@@ -1484,7 +1492,8 @@ PT_API int pt_render_features(pt_ctx* c, const pt_params* p, float* albedo_prim,
     if (!c) return fail(nullptr, "pt_render_features: null context");
     if (!p || !albedo_prim || !normal_depth) return fail(c, "pt_render_features: null argument");
     if (int rc = check_image(c, p, "pt_render_features")) return rc;
-    if (overlaps(albedo_prim, normal_depth, (size_t)p->width * p->height * sizeof(float4))) return fail(c, "pt_render_features: the two output buffers overlap");
+    const size_t bytes = (size_t)p->width * p->height * sizeof(float4);
+    if (spans_overlap(albedo_prim, bytes, normal_depth, bytes)) return fail(c, "pt_render_features: the two output buffers overlap");
     if (c->scene_serial == 0) return fail(c, "pt_render_features: no scene (pt_set_scene first)");
     CK(c, hipSetDevice(c->device));
     // the node array the scene holds: fp16 centre / half-extent nodes for the default variants, fp32 nodes for the fp32 ones; only a
@@ -1506,7 +1515,8 @@ PT_API int pt_denoise(pt_ctx* c, const pt_params* p, const float* albedo_prim, c
     if (iterations < 1u || iterations > ptd::kDnMaxIterations) return fail(c, "pt_denoise: iterations must be in [1, 8]");
     if (int rc = check_image(c, p, "pt_denoise")) return rc;
     const size_t n = (size_t)p->width * p->height, bytes = n * sizeof(float4);
-    if (overlaps(out_rgba, p->accumulationBuffer, bytes) || overlaps(out_rgba, albedo_prim, bytes) || overlaps(out_rgba, normal_depth, bytes))
+    if (spans_overlap(out_rgba, bytes, p->accumulationBuffer, bytes) || spans_overlap(out_rgba, bytes, albedo_prim, bytes) ||
+        spans_overlap(out_rgba, bytes, normal_depth, bytes))
         return fail(c, "pt_denoise: out_rgba overlaps an input (writing into the accumulation buffer would corrupt the progressive state)");
     CK(c, hipSetDevice(c->device));
     if (n > c->denoise_pixels) {
@@ -1520,6 +1530,26 @@ PT_API int pt_denoise(pt_ctx* c, const pt_params* p, const float* albedo_prim, c
     CK(c, ptd::launch_denoise((const float4*)p->accumulationBuffer, (const float4*)albedo_prim, (const float4*)normal_depth, p->width, p->height, iterations,
                               c->d_denoise[0], c->d_denoise[1], (float4*)out_rgba, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- the metered stages (display, convergence, firefly) -----------------------------------------------------------------------
+// Each keeps a small state on the device: live counts, which the stage's last kernel clears after it has read them, and the record
+// that kernel writes.  run_metered allocates the state on first use, zeroes it when it is new or dirty (an earlier call failed half
+// way), runs launch(state), copies the record to `info` if there is one, and synchronises.  fn: the entry point's name.
+template <typename State, typename Info, typename F>
+static int run_metered(pt_ctx* c, const char* fn, State*& d_state, bool& dirty, Info* info, F launch)
+{
+    hipError_t e = hipSuccess;
+    if (!d_state) { e = hipMalloc((void**)&d_state, sizeof(State)); dirty = true; }
+    if (e == hipSuccess && dirty) e = hipMemsetAsync(d_state, 0, sizeof(State), c->stream);
+    Range range(fn);
+    dirty = true;                            // until the stage's last kernel has run to its end and cleared the counts
+    if (e == hipSuccess) e = launch(d_state);
+    if (e == hipSuccess && info) e = hipMemcpyAsync(info, &d_state->record, sizeof(Info), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, std::string(fn) + ": " + hipGetErrorString(e));
+    dirty = false;
     return 0;
 }
 
@@ -1546,29 +1576,18 @@ PT_API int pt_display_transform(pt_ctx* c, const float* src_rgba, size_t n_pixel
         if (!(dp->adapt >= 0.0f && dp->adapt <= 1.0f)) return fail(c, std::string(f) + "adapt must be in [0, 1]");
     }
     if (dp->tone_curve == PT_TONE_REINHARD && (!std::isfinite(dp->white) || !(dp->white > 0.0f))) return fail(c, std::string(f) + "white must be finite and > 0");
-    if (out_rgba && overlaps(out_rgba, src_rgba, n_pixels * sizeof(float4))) return fail(c, std::string(f) + "out_rgba overlaps src_rgba");
+    if (out_rgba && spans_overlap(out_rgba, n_pixels * sizeof(float4), src_rgba, n_pixels * sizeof(float4))) return fail(c, std::string(f) + "out_rgba overlaps src_rgba");
     CK(c, hipSetDevice(c->device));
-    if (automatic && (!c->d_display || c->display_dirty)) {
-        if (!c->d_display) CK(c, hipMalloc((void**)&c->d_display, sizeof(ptd::DisplayState)));
-        c->display_dirty = true;
-        CK(c, hipMemsetAsync(c->d_display, 0, sizeof(ptd::DisplayState), c->stream));
-    }
+    const auto launch = [&](ptd::DisplayState* st) {
+        return ptd::launch_display((const float4*)src_rgba, (uint64_t)n_pixels, *dp, st, (float4*)out_rgba, (uint32_t*)framebuffer_rgba, c->stream);
+    };
+    if (automatic) return run_metered(c, "pt_display_transform", c->d_display, c->display_dirty, info, launch);
+    // a manual exposure: the apply kernel alone, the state neither read nor written
     Range range("pt_display_transform");
-    c->display_dirty = automatic;            // until the meter kernel has run to its end and cleared the counts
-    CK(c, ptd::launch_display((const float4*)src_rgba, (uint64_t)n_pixels, *dp, c->d_display, (float4*)out_rgba, (uint32_t*)framebuffer_rgba, c->stream));
-    if (info) {
-        if (automatic) CK(c, hipMemcpyAsync(info, &c->d_display->record, sizeof(pt_display_info), hipMemcpyDeviceToHost, c->stream));
-        else { memset(info, 0, sizeof(*info)); info->exposure = dp->exposure; }
-    }
+    CK(c, launch(c->d_display));
+    if (info) { memset(info, 0, sizeof(*info)); info->exposure = dp->exposure; }
     CK(c, hipStreamSynchronize(c->stream));
-    c->display_dirty = false;
     return 0;
-}
-
-static bool spans_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + b_bytes && y < x + a_bytes;
 }
 
 // ---- convergence estimate (pt_convergence_update; kernels in convergence.hip) --------------------------------------------------
@@ -1589,7 +1608,7 @@ PT_API int pt_convergence_update(pt_ctx* c, const pt_params* p, uint32_t accum_f
     if (!std::isfinite(cp->threshold) || !(cp->threshold > 0.0f)) return fail(c, f + "threshold must be finite and > 0");
     if (cp->quantile_permille < 1u || cp->quantile_permille > 1000u) return fail(c, f + "quantile_permille must be in [1, 1000]");
     if (cp->reserved != 0u) return fail(c, f + "reserved must be 0");
-    const uint64_t tiles = (uint64_t)((p->width + PT_CONVERGENCE_TILE - 1u) / PT_CONVERGENCE_TILE) * ((p->height + PT_CONVERGENCE_TILE - 1u) / PT_CONVERGENCE_TILE);
+    const uint64_t tiles = ptd::tile_walk(p->width, p->height, ptd::kConvTile, ptd::kConvBlocks).tiles;
     const void* bufs[4] = {p->accumulationBuffer, state, out_error, out_tiles};
     const size_t sizes[4] = {(size_t)n * sizeof(float4), (size_t)n * sizeof(float4), (size_t)n * sizeof(float), (size_t)tiles * sizeof(float)};
     const char* names[4] = {"the accumulation buffer", "state", "out_error", "out_tiles"};
@@ -1597,19 +1616,10 @@ PT_API int pt_convergence_update(pt_ctx* c, const pt_params* p, uint32_t accum_f
         for (int j = i + 1; j < 4; j++)
             if (bufs[i] && bufs[j] && spans_overlap(bufs[i], sizes[i], bufs[j], sizes[j])) return fail(c, f + names[j] + " overlaps " + names[i]);
     CK(c, hipSetDevice(c->device));
-    if (!c->d_convergence || c->convergence_dirty) {
-        if (!c->d_convergence) CK(c, hipMalloc((void**)&c->d_convergence, sizeof(ptd::ConvergenceState)));
-        c->convergence_dirty = true;
-        CK(c, hipMemsetAsync(c->d_convergence, 0, sizeof(ptd::ConvergenceState), c->stream));
-    }
-    Range range("pt_convergence_update");
-    c->convergence_dirty = true;             // until the meter kernel has run to its end and cleared the counts
-    CK(c, ptd::launch_convergence((const float4*)p->accumulationBuffer, p->width, p->height, accum_frames, *cp, (float4*)state, out_error, out_tiles,
-                                  c->d_convergence, c->stream));
-    if (info) CK(c, hipMemcpyAsync(info, &c->d_convergence->record, sizeof(pt_convergence_info), hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    c->convergence_dirty = false;
-    return 0;
+    return run_metered(c, "pt_convergence_update", c->d_convergence, c->convergence_dirty, info, [&](ptd::ConvergenceState* st) {
+        return ptd::launch_convergence((const float4*)p->accumulationBuffer, p->width, p->height, accum_frames, *cp, (float4*)state, out_error, out_tiles,
+                                       st, c->stream);
+    });
 }
 
 // ---- firefly filter (pt_firefly_filter; kernels in firefly.hip) -----------------------------------------------------------------
@@ -1629,18 +1639,9 @@ PT_API int pt_firefly_filter(pt_ctx* c, const float* src_rgba, uint32_t width, u
     if (fp->radius < 1u || fp->radius > 2u) return fail(c, f + "radius must be 1 or 2");
     if (spans_overlap(src_rgba, (size_t)n * sizeof(float4), out_rgba, (size_t)n * sizeof(float4))) return fail(c, f + "out_rgba overlaps src_rgba");
     CK(c, hipSetDevice(c->device));
-    if (!c->d_firefly || c->firefly_dirty) {
-        if (!c->d_firefly) CK(c, hipMalloc((void**)&c->d_firefly, sizeof(ptd::FireflyState)));
-        c->firefly_dirty = true;
-        CK(c, hipMemsetAsync(c->d_firefly, 0, sizeof(ptd::FireflyState), c->stream));
-    }
-    Range range("pt_firefly_filter");
-    c->firefly_dirty = true;                 // until the finish kernel has run to its end and cleared the counts
-    CK(c, ptd::launch_firefly((const float4*)src_rgba, width, height, *fp, (float4*)out_rgba, c->d_firefly, c->stream));
-    if (info) CK(c, hipMemcpyAsync(info, &c->d_firefly->record, sizeof(pt_firefly_info), hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    c->firefly_dirty = false;
-    return 0;
+    return run_metered(c, "pt_firefly_filter", c->d_firefly, c->firefly_dirty, info, [&](ptd::FireflyState* st) {
+        return ptd::launch_firefly((const float4*)src_rgba, width, height, *fp, (float4*)out_rgba, st, c->stream);
+    });
 }
 
 // ---- temporal reprojection (pt_temporal_blend; kernels in temporal.hip) --------------------------------------------------------
@@ -1703,14 +1704,9 @@ static int temporal_blend(pt_ctx* c, const char* fn, const pt_params* p, uint32_
         tp.hist = (const float4*)prev_history; tp.albedo_prim = (const float4*)prev_albedo_prim; tp.normal_depth = (const float4*)prev_normal_depth;
     }
     Range range(fn);
-    if (motion)
-        CK(c, ptd::launch_temporal_motion((const float4*)p->accumulationBuffer, (const float4*)albedo_prim, (const float4*)normal_depth, p->width,
-                                          p->height, p->cameraEye, p->cameraU, p->cameraV, p->cameraW, (float)accum_samples, tp, c->d_tri_bsdf,
-                                          c->bvh.n_tris, history_cap, mo, (float4*)out_history, c->stream));
-    else
-        CK(c, ptd::launch_temporal((const float4*)p->accumulationBuffer, (const float4*)albedo_prim, (const float4*)normal_depth, p->width, p->height,
-                                   p->cameraEye, p->cameraU, p->cameraV, p->cameraW, (float)accum_samples, tp, c->d_tri_bsdf, c->bvh.n_tris,
-                                   history_cap, (float4*)out_history, c->stream));
+    CK(c, ptd::launch_temporal((const float4*)p->accumulationBuffer, (const float4*)albedo_prim, (const float4*)normal_depth, p->width, p->height,
+                               p->cameraEye, p->cameraU, p->cameraV, p->cameraW, (float)accum_samples, tp, c->d_tri_bsdf, c->bvh.n_tris,
+                               history_cap, motion ? &mo : nullptr, (float4*)out_history, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1789,17 +1785,9 @@ PT_API int pt_selftest(pt_ctx* c, int op, const void* in, size_t n, void* out)
         if (n != 1 || count == 0 || count > (1u << 22)) return fail(c, "pt_selftest: op 1 takes one {seed, count} record");
         in_bytes = 8; out_bytes = (size_t)count * 8; launch_n = 1;
     }
-    uint32_t* d_in = nullptr; uint32_t* d_out = nullptr;
-    hipError_t e = hipMalloc((void**)&d_in, in_bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_out, out_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = ptd::launch_selftest(op, d_in, launch_n, d_out, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(c, std::string("pt_selftest: ") + hipGetErrorString(e));
-    return 0;
+    return device_round_trip(c, "pt_selftest", in, in_bytes, out, out_bytes, nullptr, 0, [&](void* d_in, void* d_out, void*) {
+        return ptd::launch_selftest(op, (const uint32_t*)d_in, launch_n, (uint32_t*)d_out, c->stream);
+    });
 }
 
 PT_API int pt_debug_environment(pt_ctx* c, int op, const float* in, size_t n, float* out)
@@ -1809,17 +1797,9 @@ PT_API int pt_debug_environment(pt_ctx* c, int op, const float* in, size_t n, fl
     if (n == 0) return 0;
     CK(c, hipSetDevice(c->device));
     const size_t in_bytes = n * (size_t)in_dw[op] * 4, out_bytes = n * (size_t)out_dw[op] * 4;
-    float* d_in = nullptr; float* d_out = nullptr;
-    hipError_t e = hipMalloc((void**)&d_in, in_bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_out, out_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = ptd::env_debug(ptd::env_view(c->env), op, c->math_mode != 0 ? 1 : 0, d_in, (uint32_t)n, d_out, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(c, std::string("pt_debug_environment: ") + hipGetErrorString(e));
-    return 0;
+    return device_round_trip(c, "pt_debug_environment", in, in_bytes, out, out_bytes, nullptr, 0, [&](void* d_in, void* d_out, void*) {
+        return ptd::env_debug(ptd::env_view(c->env), op, c->math_mode != 0 ? 1 : 0, (const float*)d_in, (uint32_t)n, (float*)d_out, c->stream);
+    });
 }
 
 PT_API int pt_debug_microfacet(pt_ctx* c, int op, const float* in, size_t n, float* out)
@@ -1829,17 +1809,9 @@ PT_API int pt_debug_microfacet(pt_ctx* c, int op, const float* in, size_t n, flo
     if (n == 0) return 0;
     CK(c, hipSetDevice(c->device));
     const size_t in_bytes = n * 9u * 4u, out_bytes = n * (size_t)out_dw[op] * 4u;
-    float* d_in = nullptr; float* d_out = nullptr;
-    hipError_t e = hipMalloc((void**)&d_in, in_bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_out, out_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = ptd::microfacet_debug(op, c->math_mode != 0 ? 1 : 0, d_in, (uint32_t)n, d_out, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(c, std::string("pt_debug_microfacet: ") + hipGetErrorString(e));
-    return 0;
+    return device_round_trip(c, "pt_debug_microfacet", in, in_bytes, out, out_bytes, nullptr, 0, [&](void* d_in, void* d_out, void*) {
+        return ptd::microfacet_debug(op, c->math_mode != 0 ? 1 : 0, (const float*)d_in, (uint32_t)n, (float*)d_out, c->stream);
+    });
 }
 
 PT_API int pt_debug_wave_times(pt_ctx* c, uint64_t* out, size_t max_waves)

@@ -10,16 +10,9 @@
 // Every expression is mirrored operation for operation by tests/convergence_ref.py (fp32, same order; this file is built with
 // -ffp-contract=off).  The counts are integers and the max is a max of bit patterns: the order of the atomics cannot change a bit.
 #include "convergence.h"
+#include "image_common.h"
 
 namespace ptd {
-
-__device__ __forceinline__ float cv_lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
-
-__device__ __forceinline__ uint32_t cv_wave_max(uint32_t v)
-{
-    for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)v, d); v = o > v ? o : v; }
-    return v;
-}
 
 __global__ void __launch_bounds__(kConvThreads)
 k_convergence_update(const float4* __restrict__ accum, float4* __restrict__ state, uint32_t w, uint32_t h, uint32_t tiles_x, uint64_t tiles, float k1,
@@ -37,8 +30,8 @@ k_convergence_update(const float4* __restrict__ accum, float4* __restrict__ stat
     const uint32_t lx = threadIdx.x & (kConvTile - 1u), ly = threadIdx.x / kConvTile;      // a wave covers four rows of the tile
     uint32_t run_max = 0u, par = 0u;
     for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x, par ^= 1u) {
-        const uint64_t ty = t / tiles_x, tx = t - ty * tiles_x;
-        const uint64_t x = tx * kConvTile + lx, y = ty * kConvTile + ly;
+        const ulonglong2 tile = tile_xy(t, tiles_x);
+        const uint64_t x = tile.x * kConvTile + lx, y = tile.y * kConvTile + ly;
         int k = -1;                      // the slot this pixel counts in; -1 outside the image
         uint32_t err_bits = 0u;
         bool measured = false, converged = false;
@@ -46,7 +39,7 @@ k_convergence_update(const float4* __restrict__ accum, float4* __restrict__ stat
             const uint64_t i = y * w + x;
             const float4 a = accum[i];
             float4 s = state[i];
-            const float l1 = cv_lum(a.x, a.y, a.z);
+            const float l1 = image_lum(a.x, a.y, a.z);
             float err = -1.0f;
             if (!(fabsf(l1) <= 3.402823466e+38f)) {
                 s = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -74,7 +67,7 @@ k_convergence_update(const float4* __restrict__ accum, float4* __restrict__ stat
             if (out_error) out_error[i] = err;
         }
         // the tile's max: the error's bits as uint32 (non-negative floats: unsigned order is float order)
-        const uint32_t wmax = cv_wave_max(err_bits);
+        const uint32_t wmax = wave_max(err_bits);
         const uint64_t any = __ballot(measured), conv = __ballot(converged);
         run_max = wmax > run_max ? wmax : run_max;
         if (out_tiles) {
@@ -88,29 +81,11 @@ k_convergence_update(const float4* __restrict__ accum, float4* __restrict__ stat
             }
         }
         if (lane == 0 && conv != 0ull) atomicAdd(&mine[kConvConverged], (uint32_t)__popcll(conv));
-        // A flat region puts all 64 lanes into one slot, an edge into two: 64 adds to one LDS word would run one after the other.  Up to
-        // two rounds take the first pending lane's slot and add the number of lanes that share it at once; what is left adds singly.
-        uint64_t todo = __ballot(k >= 0);
-#pragma unroll
-        for (int r = 0; r < 2; r++) {
-            if (todo == 0ull) break;
-            const int lead = __ffsll((unsigned long long)todo) - 1;
-            const int kb = __shfl(k, lead);
-            const uint64_t same = __ballot(k == kb);
-            if (lane == lead) atomicAdd(&mine[kb], (uint32_t)__popcll(same));
-            if (k == kb) k = -1;
-            todo &= ~same;
-        }
-        if (k >= 0) atomicAdd(&mine[k], 1u);
+        wave_count(mine, k, lane);
     }
     if (lane == 0 && run_max != 0u) atomicMax(&block_max, run_max);
     __syncthreads();
-    for (uint32_t b = threadIdx.x; b < kCounts; b += kConvThreads) {
-        uint32_t s = 0u;
-#pragma unroll
-        for (uint32_t v = 0; v < kWaves; v++) s += counts[v * kCounts + b];
-        if (s != 0u) atomicAdd(&live[b], s);
-    }
+    flush_wave_counts<kCounts, kWaves, kConvThreads>(counts, live);
     if (threadIdx.x == kConvThreads - 1u && block_max != 0u) atomicMax(&live[kConvMax], block_max);
 }
 
@@ -125,8 +100,7 @@ k_convergence_meter(ConvergenceState* __restrict__ st, uint32_t frames, uint32_t
 #pragma unroll
     for (uint32_t j = 0; j < kPer; j++) { hgm[j] = st->live[lane * kPer + j]; sum += hgm[j]; }
     const uint32_t unmeasured = st->live[kConvUnmeasured], invalid = st->live[kConvInvalid], converged = st->live[kConvConverged], max_bits = st->live[kConvMax];
-    uint32_t incl = sum;                                    // counts are at most 2^31 in all: uint32 holds every partial sum
-    for (uint32_t d = 1u; d < 64u; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+    const uint32_t incl = wave_scan_inclusive(sum, lane);      // counts are at most 2^31 in all: uint32 holds every partial sum
     const uint32_t n = __shfl(incl, 63);
     uint64_t r = ((uint64_t)n * quantile_permille + 999u) / 1000u;
     if (r < 1u) r = 1u;
@@ -156,10 +130,8 @@ k_convergence_meter(ConvergenceState* __restrict__ st, uint32_t frames, uint32_t
 hipError_t launch_convergence(const float4* accum, uint32_t w, uint32_t h, uint32_t accum_frames, const pt_convergence_params& cp, float4* state,
                               float* out_error, float* out_tiles, ConvergenceState* st, hipStream_t stream)
 {
-    const uint32_t tiles_x = (w + kConvTile - 1u) / kConvTile, tiles_y = (h + kConvTile - 1u) / kConvTile;
-    const uint64_t tiles = (uint64_t)tiles_x * tiles_y;     // one grid dimension, strided: no 65 535 limit on the tile rows
-    const uint32_t grid = (uint32_t)(tiles < kConvBlocks ? tiles : kConvBlocks);
-    k_convergence_update<<<grid, kConvThreads, 0, stream>>>(accum, state, w, h, tiles_x, tiles, (float)accum_frames, cp.lum_floor, cp.threshold, out_error,
+    const TileWalk tw = tile_walk(w, h, kConvTile, kConvBlocks);
+    k_convergence_update<<<tw.grid, kConvThreads, 0, stream>>>(accum, state, w, h, tw.tiles_x, tw.tiles, (float)accum_frames, cp.lum_floor, cp.threshold, out_error,
                                                            out_tiles, st->live);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

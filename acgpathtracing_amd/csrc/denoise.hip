@@ -7,6 +7,7 @@
 // The filter reads 25 taps of {c, var} and {normal, depth} per pixel and iteration, 32 bytes each, plus the .w of 9 neighbours for
 // the variance blur: bound by the L1 / L2, not by arithmetic.  No atomics anywhere: two calls give the same bits.
 #include "denoise.h"
+#include "image_common.h"
 
 namespace ptd {
 
@@ -71,10 +72,7 @@ k_dn_features(const DeviceScene sc, uint32_t stack_entries, uint32_t w, uint32_t
     st.base = dn_lds + (threadIdx.x >> 6) * (stack_entries * 64u) + (threadIdx.x & 63u);
     const bool active = i < n;
     const uint32_t x = active ? i % w : 0u, y = active ? i / w : 0u;
-    // pathTracerPrograms.cu:730-740 with the jitter at 0.5; this file is built with -ffp-contract=off: no contraction
-    const float dx = 2.0f * (((float)x + 0.5f) / (float)w) - 1.0f;
-    const float dy = 2.0f * (((float)y + 0.5f) / (float)h) - 1.0f;
-    const f3 dir = normalize(dx * mk(U) + dy * mk(V) + mk(W));
+    const f3 dir = pixel_centre_dir(x, y, w, h, U, V, W);
     const f3 org = mk(eye);
     HitRec hit;
     if (FMT == 11) traverse_hc(sc, st, active, org, dir, 0.01f, 1e16f, hit);
@@ -96,7 +94,6 @@ k_dn_features(const DeviceScene sc, uint32_t stack_entries, uint32_t w, uint32_t
 // ---- filter -----------------------------------------------------------------------------------------------------------------
 // Every expression below is mirrored operation for operation by tests/denoise_ref.py (fp32, same order, taps dy-major).
 __device__ __forceinline__ bool dn_hit(const float4& nd) { return nd.w >= 0.0f; }
-__device__ __forceinline__ float dn_lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
 __device__ __forceinline__ float4 dn_albedo(const float4& alb, bool hit)
 {
     return hit ? make_float4(fmaxf(alb.x, kDnAlbedoFloor), fmaxf(alb.y, kDnAlbedoFloor), fmaxf(alb.z, kDnAlbedoFloor), 0.0f) : make_float4(1.0f, 1.0f, 1.0f, 0.0f);
@@ -132,7 +129,7 @@ k_dn_variance(const float4* __restrict__ accum, const float4* __restrict__ albed
     const bool hp = dn_hit(ndp);
     const float4 ap = dn_albedo(albedo[p], hp), cp4 = accum[p];
     const float cr = cp4.x / ap.x, cg = cp4.y / ap.y, cb = cp4.z / ap.z;
-    const float lp = dn_lum(cr, cg, cb);
+    const float lp = image_lum(cr, cg, cb);
     const float zden = kDnSigmaZ * 1.0f * ndp.w;
     float sw = 0.0f, s1 = 0.0f, s2 = 0.0f;
     for (int dy = -2; dy <= 2; dy++) {
@@ -146,7 +143,7 @@ k_dn_variance(const float4* __restrict__ accum, const float4* __restrict__ albed
             float wn, ez;
             if (!dn_geometry(ndp, ndq, hp, zden, wn, ez)) continue;
             const float4 aq = dn_albedo(albedo[q], hp), c4 = accum[q];
-            const float dl = dn_lum(c4.x / aq.x, c4.y / aq.y, c4.z / aq.z) - lp;
+            const float dl = image_lum(c4.x / aq.x, c4.y / aq.y, c4.z / aq.z) - lp;
             const float wq = wn * expf(-ez);
             sw += wq; s1 += wq * dl; s2 += wq * (dl * dl);
         }
@@ -180,7 +177,7 @@ k_dn_atrous(const float4* __restrict__ cv, const float4* __restrict__ nd, const 
         }
     }
     const float lden = kDnSigmaL * sqrtf(gs / gw) + 1e-6f;
-    const float lp = dn_lum(cvp.x, cvp.y, cvp.z);
+    const float lp = image_lum(cvp.x, cvp.y, cvp.z);
     const float zden = kDnSigmaZ * (float)step * ndp.w;
     float sk = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
     for (int dy = -2; dy <= 2; dy++) {
@@ -194,7 +191,7 @@ k_dn_atrous(const float4* __restrict__ cv, const float4* __restrict__ nd, const 
             float wn, ez;
             if (!dn_geometry(ndp, ndq, hp, zden, wn, ez)) continue;
             const float4 c = cv[q];
-            const float el = fabsf(lp - dn_lum(c.x, c.y, c.z)) / lden;
+            const float el = fabsf(lp - image_lum(c.x, c.y, c.z)) / lden;
             const float k = kDnH[dx + 2] * kDnH[dy + 2] * wn * expf(-(ez + el));
             sk += k;
             sr += k * c.x; sg += k * c.y; sb += k * c.z;
@@ -226,15 +223,15 @@ hipError_t launch_features(int fmt, const DeviceScene& sc, uint32_t stack_entrie
 hipError_t launch_denoise(const float4* accum, const float4* albedo_prim, const float4* normal_depth, uint32_t w, uint32_t h, uint32_t iterations,
                           float4* scratch0, float4* scratch1, float4* out, hipStream_t stream)
 {
-    const dim3 block(32, 8), grid((w + 31u) / 32u, (h + 7u) / 8u);
-    k_dn_variance<<<grid, block, 0, stream>>>(accum, albedo_prim, normal_depth, w, h, scratch0);
+    const PixelLaunch pl = pixel_launch(w, h);
+    k_dn_variance<<<pl.grid, pl.block, 0, stream>>>(accum, albedo_prim, normal_depth, w, h, scratch0);
     hipError_t e = hipGetLastError();
     float4* src = scratch0;
     float4* dst = scratch1;
     for (uint32_t i = 0; i < iterations && e == hipSuccess; i++) {
         const int step = 1 << i;
-        if (i + 1 == iterations) k_dn_atrous<true><<<grid, block, 0, stream>>>(src, normal_depth, albedo_prim, w, h, step, out);
-        else k_dn_atrous<false><<<grid, block, 0, stream>>>(src, normal_depth, albedo_prim, w, h, step, dst);
+        if (i + 1 == iterations) k_dn_atrous<true><<<pl.grid, pl.block, 0, stream>>>(src, normal_depth, albedo_prim, w, h, step, out);
+        else k_dn_atrous<false><<<pl.grid, pl.block, 0, stream>>>(src, normal_depth, albedo_prim, w, h, step, dst);
         e = hipGetLastError();
         float4* t = src; src = dst; dst = t;
     }

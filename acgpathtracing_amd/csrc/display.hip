@@ -9,11 +9,10 @@
 // Every expression is mirrored operation for operation by tests/display_ref.py (fp32, same order; this file is built with
 // -ffp-contract=off).  The counts are integers: the order of the atomic adds cannot change a bit, two calls give the same bits.
 #include "display.h"
+#include "image_common.h"
 #include "pt_shading.h"
 
 namespace ptd {
-
-__device__ __forceinline__ float dp_lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
 
 // bin of a luminance, kDisplayBins for a pixel that is not metered (below 2^-20, zero, negative, NaN or infinite)
 __device__ __forceinline__ uint32_t dp_bin(float l)
@@ -35,29 +34,10 @@ k_display_histogram(const float4* __restrict__ src, uint64_t n, uint32_t* __rest
     const uint64_t stride = (uint64_t)gridDim.x * kDisplayThreads;
     for (uint64_t i = (uint64_t)blockIdx.x * kDisplayThreads + threadIdx.x; i < n; i += stride) {
         const float4 c = src[i];
-        int k = (int)dp_bin(dp_lum(c.x, c.y, c.z));
-        // A flat region puts all 64 lanes into one bin, an edge into two: 64 adds to one LDS word would run one after the other.  Up to
-        // two rounds take the first pending lane's bin and add the number of lanes that share it at once; what is left adds singly.
-        uint64_t todo = __ballot(1);
-#pragma unroll
-        for (int r = 0; r < 2; r++) {
-            if (todo == 0ull) break;
-            const int lead = __ffsll((unsigned long long)todo) - 1;
-            const int kb = __shfl(k, lead);
-            const uint64_t same = __ballot(k == kb);
-            if (lane == lead) atomicAdd(&mine[kb], (uint32_t)__popcll(same));
-            if (k == kb) k = -1;
-            todo &= ~same;
-        }
-        if (k >= 0) atomicAdd(&mine[k], 1u);
+        wave_count(mine, (int)dp_bin(image_lum(c.x, c.y, c.z)), lane);      // every active lane counts: no k < 0 here
     }
     __syncthreads();
-    for (uint32_t b = threadIdx.x; b < kSlots; b += kDisplayThreads) {
-        uint32_t s = 0u;
-#pragma unroll
-        for (uint32_t w = 0; w < kWaves; w++) s += hist[w * kSlots + b];
-        if (s != 0u) atomicAdd(&live[b], s);
-    }
+    flush_wave_counts<kSlots, kWaves, kDisplayThreads>(hist, live);
 }
 
 // <<<1, 64>>>: lane j owns bins 5j .. 5j+4
@@ -72,8 +52,7 @@ k_display_meter(DisplayState* __restrict__ st, float key, uint32_t lo_permille, 
 #pragma unroll
     for (uint32_t j = 0; j < kPer; j++) { h[j] = st->live[lane * kPer + j]; sum += h[j]; }
     const uint32_t unmetered = st->live[kDisplayBins];
-    uint32_t incl = sum;                                    // counts are at most 2^31 in all: uint32 holds every partial sum
-    for (uint32_t d = 1u; d < 64u; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+    const uint32_t incl = wave_scan_inclusive(sum, lane);      // counts are at most 2^31 in all: uint32 holds every partial sum
     const uint32_t n = __shfl(incl, 63);
     uint64_t r_lo = (uint64_t)n * lo_permille / 1000u, r_hi = (uint64_t)n * hi_permille / 1000u;
     if (r_hi <= r_lo) { r_lo = 0u; r_hi = n; }
@@ -125,7 +104,7 @@ k_display_apply(const float4* __restrict__ src, uint64_t n, const DisplayState* 
     if (CURVE == PT_TONE_ACES) {
         yr = dp_aces(xr); yg = dp_aces(xg); yb = dp_aces(xb);
     } else if (CURVE == PT_TONE_REINHARD) {
-        const float l = dp_lum(xr, xg, xb);
+        const float l = image_lum(xr, xg, xb);
         const float s = l > 0.0f ? (1.0f + l / white2) / (1.0f + l) : 0.0f;
         yr = fminf(xr * s, 1.0f); yg = fminf(xg * s, 1.0f); yb = fminf(xb * s, 1.0f);
     } else {

@@ -12,10 +12,10 @@
 // -ffp-contract=off).  The reductions are integer sums and a max of bit patterns: the order of the atomics cannot change a bit, and
 // neighbours are read from src only, so two calls give the same bits.
 #include "firefly.h"
+#include "image_common.h"
 
 namespace ptd {
 
-__device__ __forceinline__ float ff_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 __device__ __forceinline__ bool ff_valid(float l) { return l >= 0.0f && l <= 3.402823466e+38f; }
 __device__ __forceinline__ unsigned long long ff_q16(float x) { return (unsigned long long)(fminf(x, 16777216.0f) * 65536.0f); }
 
@@ -54,8 +54,8 @@ k_firefly_filter(const float4* __restrict__ src, float4* __restrict__ out, uint3
     uint32_t n_clamped = 0u, n_replaced = 0u, n_passed = 0u, max_bits = 0u;
     unsigned long long total = 0ull, removed = 0ull;
     for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
-        const uint64_t ty = t / tiles_x, tx = t - ty * tiles_x;
-        const int64_t x0 = (int64_t)(tx * kFireflyTile), y0 = (int64_t)(ty * kFireflyTile);
+        const ulonglong2 tile = tile_xy(t, tiles_x);
+        const int64_t x0 = (int64_t)(tile.x * kFireflyTile), y0 = (int64_t)(tile.y * kFireflyTile);
         const int64_t x = x0 + lx, y = y0 + ly;
         const bool inside = x < (int64_t)w && y < (int64_t)h;
         const uint64_t i = (uint64_t)y * w + (uint64_t)x;
@@ -64,7 +64,7 @@ k_firefly_filter(const float4* __restrict__ src, float4* __restrict__ out, uint3
         bool ok = false;
         if (inside) {
             c = src[i];
-            l = ff_lum(c.x, c.y, c.z);
+            l = image_lum(c.x, c.y, c.z);
             ok = ff_valid(l);
         }
         lds[(ly + RADIUS) * kStride + lx + RADIUS] = ok ? l : -1.0f;
@@ -73,7 +73,7 @@ k_firefly_filter(const float4* __restrict__ src, float4* __restrict__ out, uint3
             float v = -1.0f;
             if (qx >= 0 && qx < (int64_t)w && qy >= 0 && qy < (int64_t)h) {
                 const float4 q = src[(uint64_t)qy * w + (uint64_t)qx];
-                const float lq = ff_lum(q.x, q.y, q.z);
+                const float lq = image_lum(q.x, q.y, q.z);
                 if (ff_valid(lq)) v = lq;
             }
             lds[hrow * kStride + hcol] = v;
@@ -131,9 +131,8 @@ k_firefly_filter(const float4* __restrict__ src, float4* __restrict__ out, uint3
         passed += __shfl_xor(passed, d);
         total += __shfl_xor(total, d);
         removed += __shfl_xor(removed, d);
-        const uint32_t o = (uint32_t)__shfl_xor((int)max_bits, d);
-        max_bits = o > max_bits ? o : max_bits;
     }
+    max_bits = wave_max(max_bits);
     const uint32_t wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63u) == 0u) {
         part[wave][0] = counts & 0xFFFFFFFFull; part[wave][1] = counts >> 32; part[wave][2] = passed;
@@ -172,11 +171,9 @@ k_firefly_finish(FireflyState* __restrict__ st)
 
 hipError_t launch_firefly(const float4* src, uint32_t w, uint32_t h, const pt_firefly_params& fp, float4* out, FireflyState* st, hipStream_t stream)
 {
-    const uint32_t tiles_x = (w + kFireflyTile - 1u) / kFireflyTile, tiles_y = (h + kFireflyTile - 1u) / kFireflyTile;
-    const uint64_t tiles = (uint64_t)tiles_x * tiles_y;     // one grid dimension, strided: no 65 535 limit on the tile rows
-    const uint32_t grid = (uint32_t)(tiles < kFireflyBlocks ? tiles : kFireflyBlocks);
-    if (fp.radius == 1u) k_firefly_filter<1><<<grid, kFireflyThreads, 0, stream>>>(src, out, w, h, tiles_x, tiles, fp.ratio, fp.floor, fp.rank, st);
-    else k_firefly_filter<2><<<grid, kFireflyThreads, 0, stream>>>(src, out, w, h, tiles_x, tiles, fp.ratio, fp.floor, fp.rank, st);
+    const TileWalk tw = tile_walk(w, h, kFireflyTile, kFireflyBlocks);
+    if (fp.radius == 1u) k_firefly_filter<1><<<tw.grid, kFireflyThreads, 0, stream>>>(src, out, w, h, tw.tiles_x, tw.tiles, fp.ratio, fp.floor, fp.rank, st);
+    else k_firefly_filter<2><<<tw.grid, kFireflyThreads, 0, stream>>>(src, out, w, h, tw.tiles_x, tw.tiles, fp.ratio, fp.floor, fp.rank, st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     k_firefly_finish<<<1, 64, 0, stream>>>(st);

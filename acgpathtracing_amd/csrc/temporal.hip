@@ -11,6 +11,7 @@
 // the clip nine 16-B accumulation taps shared with the neighbours.  No atomics, no transcendental: two calls
 // give the same bits.
 #include "temporal.h"
+#include "image_common.h"
 
 namespace ptd {
 
@@ -39,10 +40,7 @@ k_tp_blend(const float4* __restrict__ accum, const float4* __restrict__ albedo_p
     const uint32_t prim = __float_as_uint(albedo_prim[p].w);
     float4 o = make_float4(c.x, c.y, c.z, N);                          // the pass-through
     if (prev.hist && ndp.w >= 0.0f && prim < n_tris && bsdf[prim] == (uint8_t)PT_BSDF_DIFFUSE) {
-        // the ray of k_dn_features (denoise.hip): same expression, same order, so the same bits
-        const float dx = 2.0f * (((float)x + 0.5f) / (float)w) - 1.0f;
-        const float dy = 2.0f * (((float)y + 0.5f) / (float)h) - 1.0f;
-        const f3 dir = normalize(dx * mk(U) + dy * mk(V) + mk(W));
+        const f3 dir = pixel_centre_dir(x, y, w, h, U, V, W);      // the ray k_dn_features traced (denoise.hip)
         f3 hit = mk(eye) + ndp.w * dir;
         bool moved_ok = true;
         if (kMotion && mo.verts) {
@@ -150,21 +148,13 @@ hipError_t launch_tri_bsdf(const DeviceScene& sc, uint8_t* bsdf, hipStream_t str
 
 hipError_t launch_temporal(const float4* accum, const float4* albedo_prim, const float4* normal_depth, uint32_t w, uint32_t h, pt_float3 eye,
                            pt_float3 U, pt_float3 V, pt_float3 W, float n_samples, const TpPrev& prev, const uint8_t* bsdf, uint32_t n_tris,
-                           float cap, float4* out, hipStream_t stream)
+                           float cap, const TpMotion* motion, float4* out, hipStream_t stream)
 {
-    const dim3 block(32, 8), grid((w + 31u) / 32u, (h + 7u) / 8u);
-    k_tp_blend<false><<<grid, block, 0, stream>>>(accum, albedo_prim, normal_depth, w, h, eye, U, V, W, n_samples, prev, bsdf, n_tris, cap,
-                                                  TpMotion{}, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_temporal_motion(const float4* accum, const float4* albedo_prim, const float4* normal_depth, uint32_t w, uint32_t h,
-                                  pt_float3 eye, pt_float3 U, pt_float3 V, pt_float3 W, float n_samples, const TpPrev& prev, const uint8_t* bsdf,
-                                  uint32_t n_tris, float cap, const TpMotion& motion, float4* out, hipStream_t stream)
-{
-    const dim3 block(32, 8), grid((w + 31u) / 32u, (h + 7u) / 8u);
-    k_tp_blend<true><<<grid, block, 0, stream>>>(accum, albedo_prim, normal_depth, w, h, eye, U, V, W, n_samples, prev, bsdf, n_tris, cap,
-                                                 motion, out);
+    const PixelLaunch pl = pixel_launch(w, h);
+    if (!motion) k_tp_blend<false><<<pl.grid, pl.block, 0, stream>>>(accum, albedo_prim, normal_depth, w, h, eye, U, V, W, n_samples, prev, bsdf, n_tris,
+                                                                     cap, TpMotion{}, out);
+    else k_tp_blend<true><<<pl.grid, pl.block, 0, stream>>>(accum, albedo_prim, normal_depth, w, h, eye, U, V, W, n_samples, prev, bsdf, n_tris, cap,
+                                                            *motion, out);
     return hipGetLastError();
 }
 

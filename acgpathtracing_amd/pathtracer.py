@@ -597,6 +597,22 @@ def _read_image(state, ptr):
     return out
 
 
+def _source_image(state, image, bufs, what):
+    """The device pointer behind the `image` argument of `what`: None is the state's accumulation buffer, a float32 [height, width, 4]
+    array is uploaded into a new buffer appended to bufs (the caller frees those), anything else is a device pointer."""
+    if image is None:
+        return state.params.accumulationBuffer
+    if not isinstance(image, np.ndarray):
+        return int(image)
+    h, w = int(state.params.height), int(state.params.width)
+    if image.shape != (h, w, 4):
+        raise ValueError("%s: an image of shape %s, got %s" % (what, (h, w, 4), image.shape))
+    a = np.ascontiguousarray(image, np.float32)
+    bufs += _device_buffers(state, 1, a.nbytes)
+    _check(state.context, _native.hip().pt_copy_to_device(state.context, bufs[-1], a.ctypes.data, a.nbytes), "copy to device")
+    return bufs[-1]
+
+
 def renderFeatures(state):
     """First-hit feature buffers of the current camera (include/acgpt.h pt_render_features), float32 [height, width, 4] each (row 0 =
     bottom): albedo_prim = diffuse colour + triangle index as uint32 bits (0xFFFFFFFF on a miss), normal_depth = camera-facing unit
@@ -641,17 +657,7 @@ def fireflyFilter(state, image=None, ratio=FIREFLY_DEFAULTS["ratio"], rank=FIREF
     fp = _firefly_params({"ratio": ratio, "rank": rank, "radius": radius, "floor": floor}, "fireflyFilter")
     bufs = _device_buffers(state, 1, w * h * 16)
     try:
-        if image is None:
-            src = state.params.accumulationBuffer
-        elif isinstance(image, np.ndarray):
-            if image.shape != (h, w, 4):
-                raise ValueError("fireflyFilter: an image of shape %s, got %s" % ((h, w, 4), image.shape))
-            a = np.ascontiguousarray(image, np.float32)
-            bufs += _device_buffers(state, 1, a.nbytes)
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[1], a.ctypes.data, a.nbytes), "copy to device")
-            src = bufs[1]
-        else:
-            src = int(image)
+        src = _source_image(state, image, bufs, "fireflyFilter")
         info = _native.FireflyInfo()
         _check(state.context, L.pt_firefly_filter(state.context, src, w, h, C.byref(fp), bufs[0], C.byref(info)), "pt_firefly_filter")
         out = _read_image(state, bufs[0])
@@ -715,17 +721,7 @@ def displayTransform(state, image=None, curve="aces", exposure=None, key=0.18, w
                                float(limits[0]), float(limits[1]), 0.0 if prev_exposure is None else float(prev_exposure), float(adapt))
     bufs = _device_buffers(state, 1, w * h * 4)
     try:
-        if image is None:
-            src = state.params.accumulationBuffer
-        elif isinstance(image, np.ndarray):
-            if image.shape != (h, w, 4):
-                raise ValueError("displayTransform: an image of shape %s, got %s" % ((h, w, 4), image.shape))
-            a = np.ascontiguousarray(image, np.float32)
-            bufs += _device_buffers(state, 1, a.nbytes)
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[1], a.ctypes.data, a.nbytes), "copy to device")
-            src = bufs[1]
-        else:
-            src = int(image)
+        src = _source_image(state, image, bufs, "displayTransform")
         info = _native.DisplayInfo()
         _check(state.context, L.pt_display_transform(state.context, src, w * h, C.byref(dp), None, bufs[0], C.byref(info)), "pt_display_transform")
         rgba = np.zeros((h, w, 4), np.uint8)
