@@ -107,6 +107,18 @@ class FireflyInfo(C.Structure):
                 ("total_luma_q16", C.c_uint64), ("removed_luma_q16", C.c_uint64), ("max_ratio", C.c_float), ("reserved2", C.c_uint32)]
 
 
+class BloomParams(C.Structure):
+    """pt_bloom_params (include/acgpt.h)."""
+    _fields_ = [("threshold", C.c_float), ("knee", C.c_float), ("clamp", C.c_float), ("intensity", C.c_float), ("spread", C.c_float),
+                ("levels", C.c_uint32)]
+
+
+class BloomInfo(C.Structure):
+    """pt_bloom_info (include/acgpt.h)."""
+    _fields_ = [("levels", C.c_uint32), ("bright_pixels", C.c_uint32), ("invalid_pixels", C.c_uint32), ("reserved", C.c_uint32),
+                ("total_luma_q16", C.c_uint64), ("bright_luma_q16", C.c_uint64), ("max_luma", C.c_float), ("reserved2", C.c_uint32)]
+
+
 assert C.sizeof(PathTraceParams) == 168
 assert C.sizeof(Material) == 40
 assert C.sizeof(AreaLight) == 60
@@ -121,6 +133,8 @@ TONE_LINEAR, TONE_REINHARD, TONE_ACES = 0, 1, 2                    # pt_display_
 assert C.sizeof(DisplayParams) == 40 and C.sizeof(DisplayInfo) == 16 + 4 * DISPLAY_BINS
 assert C.sizeof(ConvergenceParams) == 16 and C.sizeof(ConvergenceInfo) == 32 + 4 * CONVERGENCE_BINS
 assert C.sizeof(FireflyParams) == 16 and C.sizeof(FireflyInfo) == 40
+assert C.sizeof(BloomParams) == 24 and C.sizeof(BloomInfo) == 40
+BLOOM_MAX_LEVELS = 8                                               # pt_bloom_params.levels
 
 # every symbol include/acgpt.h declares (the drop-in boundary) ...
 ABI_SYMBOLS = [
@@ -128,7 +142,7 @@ ABI_SYMBOLS = [
     "pt_launch", "pt_launch_frames", "pt_resolve_framebuffer", "pt_set_partition", "pt_set_sample_chunks", "pt_set_light_mode", "pt_set_math_mode", "pt_set_scratch_limit", "pt_set_tuning",
     "pt_variant_name", "pt_variant_kernel", "pt_kernel_source_hash", "pt_set_stream", "pt_get_stats",
     "pt_trace_closest", "pt_trace_any", "pt_render_features", "pt_denoise", "pt_temporal_blend", "pt_temporal_blend_motion", "pt_update_vertices", "pt_update_materials", "pt_set_environment",
-    "pt_set_material_model", "pt_display_transform", "pt_convergence_update", "pt_firefly_filter",
+    "pt_set_material_model", "pt_display_transform", "pt_convergence_update", "pt_firefly_filter", "pt_bloom",
     "pt_device_malloc", "pt_device_free", "pt_device_memset", "pt_copy_to_host", "pt_copy_to_device",
     "pt_host_malloc_mapped", "pt_host_free_mapped", "pt_abi_version",
 ]
@@ -226,6 +240,7 @@ def hip():
     L.pt_convergence_update.argtypes = [vp, C.POINTER(PathTraceParams), C.c_uint32, C.POINTER(ConvergenceParams), vp, vp, vp, C.POINTER(ConvergenceInfo)]
     L.pt_convergence_update.restype = C.c_int
     L.pt_firefly_filter.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(FireflyParams), vp, C.POINTER(FireflyInfo)]; L.pt_firefly_filter.restype = C.c_int
+    L.pt_bloom.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(BloomParams), vp, C.POINTER(BloomInfo)]; L.pt_bloom.restype = C.c_int
     L.pt_debug_microfacet.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_debug_microfacet.restype = C.c_int
     L.pt_bench_traversal.argtypes = [vp, vp, sz, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_float), vp]; L.pt_bench_traversal.restype = C.c_int
     L.pt_selftest.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_selftest.restype = C.c_int

@@ -31,6 +31,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "display.h"
 #include "environment.h"
 #include "firefly.h"
+#include "bloom.h"
 #include "image_common.h"
 #include "lbvh_build.h"
 #include "materials.h"
@@ -91,6 +92,8 @@ struct pt_ctx {
     ptd::EnvDevice env;                       // pt_set_environment's map and CDFs (w == 0: none); the context's, kept across scene changes
     ptd::DisplayState* d_display = nullptr; bool display_dirty = false;     // pt_display_transform's counts and meter record (dirty: a call failed half way)
     ptd::FireflyState* d_firefly = nullptr; bool firefly_dirty = false;     // pt_firefly_filter's counts and record (dirty: a call failed half way)
+    ptd::BloomState* d_bloom = nullptr; bool bloom_dirty = false;           // pt_bloom's counts and record (dirty: a call failed half way) ...
+    float4* d_bloom_pyramid = nullptr; uint64_t bloom_texels = 0;           // ... and its pyramid, all levels in one allocation: grows on demand
     ptd::ConvergenceState* d_convergence = nullptr; bool convergence_dirty = false;   // pt_convergence_update's counts and record (dirty: a call failed half way)
     uint8_t* d_tri_bsdf = nullptr;            // bsdfType per triangle (caller's order): pt_temporal_blend's, built on its first call per scene
     // what pt_update_vertices keeps of the last pt_set_scene: host copies of everything but the vertices, and after the first update
@@ -336,6 +339,8 @@ static void destroy_one(pt_ctx* c)
     if (c->d_display) (void)hipFree(c->d_display);
     if (c->d_convergence) (void)hipFree(c->d_convergence);
     if (c->d_firefly) (void)hipFree(c->d_firefly);
+    if (c->d_bloom) (void)hipFree(c->d_bloom);
+    if (c->d_bloom_pyramid) (void)hipFree(c->d_bloom_pyramid);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1533,7 +1538,7 @@ PT_API int pt_denoise(pt_ctx* c, const pt_params* p, const float* albedo_prim, c
     return 0;
 }
 
-// ---- the metered stages (display, convergence, firefly) -----------------------------------------------------------------------
+// ---- the metered stages (display, convergence, firefly, bloom) -----------------------------------------------------------------------
 // Each keeps a small state on the device: live counts, which the stage's last kernel clears after it has read them, and the record
 // that kernel writes.  run_metered allocates the state on first use, zeroes it when it is new or dirty (an earlier call failed half
 // way), runs launch(state), copies the record to `info` if there is one, and synchronises.  fn: the entry point's name.
@@ -1641,6 +1646,39 @@ PT_API int pt_firefly_filter(pt_ctx* c, const float* src_rgba, uint32_t width, u
     CK(c, hipSetDevice(c->device));
     return run_metered(c, "pt_firefly_filter", c->d_firefly, c->firefly_dirty, info, [&](ptd::FireflyState* st) {
         return ptd::launch_firefly((const float4*)src_rgba, width, height, *fp, (float4*)out_rgba, st, c->stream);
+    });
+}
+
+// ---- bloom (pt_bloom; kernels in bloom.hip) -------------------------------------------------------------------------------------
+static_assert(sizeof(pt_bloom_params) == 24 && sizeof(pt_bloom_info) == 40, "pt_bloom_params / pt_bloom_info: a change of these layouts bumps pt_abi_version");
+
+PT_API int pt_bloom(pt_ctx* c, const float* src_rgba, uint32_t width, uint32_t height, const pt_bloom_params* bp, float* out_rgba, pt_bloom_info* info)
+{
+    const std::string f("pt_bloom: ");
+    if (!c) return fail(nullptr, f + "null context");
+    if (!src_rgba || !bp || !out_rgba) return fail(c, f + "null argument");
+    if (width == 0 || height == 0) return fail(c, f + "width and height must be >= 1");
+    const uint64_t n = (uint64_t)width * height;
+    if (n > (1ull << 31)) return fail(c, f + "image too large (2^31 pixels)");
+    if (!std::isfinite(bp->threshold) || bp->threshold < 0.0f) return fail(c, f + "threshold must be finite and >= 0");
+    if (!std::isfinite(bp->knee) || bp->knee < 0.0f || bp->knee > bp->threshold) return fail(c, f + "knee must be finite and in [0, threshold]");
+    if (!std::isfinite(bp->clamp) || bp->clamp < 0.0f) return fail(c, f + "clamp must be finite and >= 0 (0: no limit)");
+    if (!std::isfinite(bp->intensity) || bp->intensity < 0.0f) return fail(c, f + "intensity must be finite and >= 0");
+    if (!std::isfinite(bp->spread) || bp->spread < 0.0f || bp->spread > 4.0f) return fail(c, f + "spread must be finite and in [0, 4]");
+    if (bp->levels < 1u || bp->levels > ptd::kBloomMaxLevels) return fail(c, f + "levels must be in [1, 8]");
+    if (spans_overlap(src_rgba, (size_t)n * sizeof(float4), out_rgba, (size_t)n * sizeof(float4))) return fail(c, f + "out_rgba overlaps src_rgba");
+    CK(c, hipSetDevice(c->device));
+    const ptd::BloomLevels lv = ptd::bloom_levels(width, height, bp->levels);
+    const uint64_t texels = lv.off[lv.n + 1u];
+    if (texels > c->bloom_texels) {
+        CK(c, hipStreamSynchronize(c->stream));
+        if (c->d_bloom_pyramid) { (void)hipFree(c->d_bloom_pyramid); c->d_bloom_pyramid = nullptr; }
+        c->bloom_texels = 0;
+        CK(c, hipMalloc((void**)&c->d_bloom_pyramid, (size_t)texels * sizeof(float4)));
+        c->bloom_texels = texels;
+    }
+    return run_metered(c, "pt_bloom", c->d_bloom, c->bloom_dirty, info, [&](ptd::BloomState* st) {
+        return ptd::launch_bloom((const float4*)src_rgba, width, height, *bp, (float4*)out_rgba, c->d_bloom_pyramid, st, c->stream);
     });
 }
 

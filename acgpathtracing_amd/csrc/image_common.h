@@ -1,4 +1,4 @@
-// image_common.h — what the image stages share (denoise.hip, temporal.hip, display.hip, convergence.hip, firefly.hip): the luminance,
+// image_common.h — what the image stages share (denoise.hip, temporal.hip, display.hip, convergence.hip, firefly.hip, bloom.hip): the luminance,
 // the wave helpers of the metered stages, the tile walk, the per-pixel launch shape and the pixel-centre camera ray.  A new stage
 // starts from here.
 //

@@ -15,7 +15,12 @@
 //              [--env map.hdr|map.pfm [--env-scale s]] [--no-area-light] [--materials reference|microfacet]
 //              [--tonemap linear|reinhard|aces] [--exposure auto|<EV>] [--out-hdr file.pfm]
 //              [--until-error E [--until-permille P] [--error-floor F] [--error-out file.pfm]]
-//              [--firefly ratio[,rank[,radius]]]
+//              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]]
+// --bloom (with --tonemap or --exposure): the image the display transform shows goes through pt_bloom first.  threshold is in display
+// units, multiples of exposed white, and is divided by the exposure (and so are the default knee, half the threshold, and the
+// clamp, none); an automatic exposure is metered on the image without its glare and then applied as a manual one.  --out-hdr gets
+// the glare too.  One line names the levels built, the bright and invalid pixels and the bright share of the luminance.  Without a
+// value: threshold 1, intensity 0.02, levels 6, spread 1.
 // --firefly: after the last frame the accumulation goes through pt_firefly_filter into a buffer of its own, and that image is what
 // --out, --out-hdr, --denoise and --tonemap see; --save-accum, --history-out and --until-error keep the raw accumulation (the
 // convergence estimate measures the renderer's noise, not a clamped image).  One line names the pixels clamped and replaced, the
@@ -250,20 +255,49 @@ static void createProgramGroups(PathTracerState&) {}
 static void createPipeline(PathTracerState&) {}
 static void createShaderBindingTable(PathTracerState&, const TinyObjWrapper&) {}
 
-// src (DEVICE float4[width * height], linear) through pt_display_transform, written as an image (--tonemap, --exposure)
-static void saveDisplay(PathTracerState& state, const std::string& path, const float* src, const pt_display_params& dp)
+// --bloom: src (DEVICE float4[width * height], linear) through pt_bloom into dst.  bloom holds threshold, knee and clamp in display
+// units: they are divided by the exposure, which is dp's manual one or is metered on src here (a pt_display_transform call whose
+// frame buffer, fb, is discarded).  Returns the exposure; "" in err if all went well.
+static float bloomForDisplay(PathTracerState& state, const float* src, const pt_display_params& dp, const pt_bloom_params& bloom, float* dst, void* fb,
+                             pt_display_info& info, pt_bloom_info& bi, std::string& err)
+{
+    const size_t n = (size_t)state.params.width * state.params.height;
+    memset(&info, 0, sizeof(info));
+    info.exposure = dp.exposure;
+    if (!(dp.exposure > 0.0f) && pt_display_transform(state.context, src, n, &dp, nullptr, (uint8_t*)fb, &info) != 0) { err = pt_last_error(state.context); return 0.0f; }
+    pt_bloom_params bp = bloom;
+    bp.threshold = bloom.threshold / info.exposure; bp.knee = bloom.knee / info.exposure; bp.clamp = bloom.clamp / info.exposure;
+    if (pt_bloom(state.context, src, state.params.width, state.params.height, &bp, dst, &bi) != 0) err = pt_last_error(state.context);
+    return info.exposure;
+}
+
+// src (DEVICE float4[width * height], linear) through pt_display_transform, written as an image (--tonemap, --exposure); with bloom,
+// through pt_bloom first
+static void saveDisplay(PathTracerState& state, const std::string& path, const float* src, const pt_display_params& dp, const pt_bloom_params* bloom = nullptr)
 {
     const size_t n = (size_t)state.params.width * state.params.height;
     void* fb = nullptr;
+    void* glared = nullptr;
     std::string err;
     pt_display_info info;
+    pt_bloom_info bi;
     std::vector<uint8_t> host(n * 4);
-    if (pt_device_malloc(state.context, &fb, n * 4) != 0 ||
-        pt_display_transform(state.context, src, n, &dp, nullptr, (uint8_t*)fb, &info) != 0 ||
-        pt_copy_to_host(state.context, host.data(), fb, n * 4) != 0)
+    if (pt_device_malloc(state.context, &fb, n * 4) != 0) err = pt_last_error(state.context);
+    if (err.empty() && bloom) {
+        if (pt_device_malloc(state.context, &glared, n * 16) != 0) err = pt_last_error(state.context);
+        pt_display_params manual = dp;
+        if (err.empty()) manual.exposure = bloomForDisplay(state, src, dp, *bloom, (float*)glared, fb, info, bi, err);
+        if (err.empty() && pt_display_transform(state.context, (const float*)glared, n, &manual, nullptr, (uint8_t*)fb, nullptr) != 0) err = pt_last_error(state.context);
+    } else if (err.empty() && pt_display_transform(state.context, src, n, &dp, nullptr, (uint8_t*)fb, &info) != 0) {
         err = pt_last_error(state.context);
+    }
+    if (err.empty() && pt_copy_to_host(state.context, host.data(), fb, n * 4) != 0) err = pt_last_error(state.context);
     if (fb) pt_device_free(state.context, fb);
+    if (glared) pt_device_free(state.context, glared);
     if (!err.empty()) throw Exception("display transform: " + err);
+    if (bloom)
+        std::cout << "Bloom: " << bi.levels << " levels, " << bi.bright_pixels << " bright, " << bi.invalid_pixels << " invalid; bright share "
+                  << (bi.total_luma_q16 ? (double)bi.bright_luma_q16 / (double)bi.total_luma_q16 : 0.0) << ", max luminance " << bi.max_luma << std::endl;
     std::cout << "Display exposure: " << info.exposure << (dp.exposure > 0.0f ? " (manual)" : " (metered)") << std::endl;
     if (!saveImage(path, host.data(), (int)state.params.width, (int)state.params.height)) std::cerr << "could not write " << path << std::endl;
 }
@@ -271,7 +305,7 @@ static void saveDisplay(PathTracerState& state, const std::string& path, const f
 // the denoised preview of the current accumulation, written as an image next to the frame (--denoise); with a display transform
 // (dp), that of the denoised image goes to display_path
 static void saveDenoised(PathTracerState& state, const std::string& path, uint32_t iterations, const pt_display_params* dp = nullptr,
-                         const std::string& display_path = std::string(), const float* image = nullptr)
+                         const std::string& display_path = std::string(), const float* image = nullptr, const pt_bloom_params* bloom = nullptr)
 {
     auto params = state.params;                 // image (--firefly): denoise that instead of the accumulation
     if (image) params.accumulationBuffer = const_cast<float*>(image);
@@ -287,7 +321,7 @@ static void saveDenoised(PathTracerState& state, const std::string& path, uint32
                         pt_copy_to_host(state.context, host.data(), bufs[3], n * 4) != 0))
         err = pt_last_error(state.context);
     if (err.empty() && dp) {
-        try { saveDisplay(state, display_path, (const float*)bufs[2], *dp); } catch (const std::exception& e) { err = e.what(); }
+        try { saveDisplay(state, display_path, (const float*)bufs[2], *dp, bloom); } catch (const std::exception& e) { err = e.what(); }
     }
     for (void* b : bufs) if (b) pt_device_free(state.context, b);
     if (!err.empty()) throw Exception("denoise: " + err);
@@ -548,6 +582,8 @@ int main(int argc, char** argv)
     bool zero_copy = false, move_history = false, no_area_light = false;
     std::string env_path, tonemap, exposure_arg, out_hdr, error_out;
     pt_firefly_params firefly = {0.0f, 0.01f, 1u, 1u};       // ratio 0: no --firefly; the other defaults of include/acgpt.h
+    pt_bloom_params bloom = {1.0f, 0.5f, 0.0f, 0.02f, 1.0f, 6u};   // pt_bloom_params' defaults (include/acgpt.h), in display units
+    bool use_bloom = false;
     // pt_convergence_params' defaults (include/acgpt.h); threshold 0: no --until-error
     pt_convergence_params until = {0.01f, 0.0f, 950u, 0u};
     float env_scale = 1.0f;
@@ -606,6 +642,18 @@ int main(int argc, char** argv)
             }
             firefly.rank = (uint32_t)rank; firefly.radius = (uint32_t)radius;
         }
+        else if (a == "--bloom") {
+            use_bloom = true;
+            if (i + 1 < argc && argv[i + 1][0] != '-') {              // a value: threshold,intensity[,levels[,spread]]; the knee is half the threshold
+                int levels = 6;
+                const int got = sscanf(next(), "%f,%f,%d,%f", &bloom.threshold, &bloom.intensity, &levels, &bloom.spread);
+                if (got < 2 || !std::isfinite(bloom.threshold) || bloom.threshold < 0.0f || !std::isfinite(bloom.intensity) || bloom.intensity < 0.0f || levels < 1 ||
+                    levels > 8 || !std::isfinite(bloom.spread) || bloom.spread < 0.0f || bloom.spread > 4.0f) {
+                    std::cerr << "--bloom takes threshold,intensity[,levels[,spread]]: threshold and intensity >= 0, levels 1 to 8, spread 0 to 4" << std::endl; return 2;
+                }
+                bloom.levels = (uint32_t)levels; bloom.knee = 0.5f * bloom.threshold;
+            }
+        }
         else if (a == "--materials") {
             const std::string m = next();
             if (m == "reference") material_model = PT_MATERIALS_REFERENCE;
@@ -632,6 +680,7 @@ int main(int argc, char** argv)
             display_params.exposure = factor;
         }
     }
+    if (use_bloom && !display) { std::cerr << "--bloom needs --tonemap or --exposure" << std::endl; return 2; }
     if (move_history && move.empty()) { std::cerr << "--move-history needs --move" << std::endl; return 2; }
     const bool until_error = until.threshold > 0.0f;
     if (!error_out.empty() && !until_error) { std::cerr << "--error-out needs --until-error" << std::endl; return 2; }
@@ -816,12 +865,23 @@ int main(int argc, char** argv)
             if (!save_accum.empty()) saveAccumulation(state, save_accum);
             if (!out_hdr.empty()) {
                 std::vector<float> host((size_t)width * height * 4);
-                PT_CHECK(state.context, pt_copy_to_host(state.context, host.data(), shown, host.size() * sizeof(float)));
+                if (use_bloom) {                    // the glare at the exposure the display image of `shown` gets
+                    void* glared = nullptr; void* fb = nullptr;
+                    pt_display_info di; pt_bloom_info bi; std::string err;
+                    PT_CHECK(state.context, pt_device_malloc(state.context, &glared, n_pixels * 16));
+                    PT_CHECK(state.context, pt_device_malloc(state.context, &fb, n_pixels * 4));
+                    bloomForDisplay(state, shown, display_params, bloom, (float*)glared, fb, di, bi, err);
+                    if (err.empty() && pt_copy_to_host(state.context, host.data(), glared, host.size() * sizeof(float)) != 0) err = pt_last_error(state.context);
+                    pt_device_free(state.context, fb); pt_device_free(state.context, glared);
+                    if (!err.empty()) throw Exception("bloom: " + err);
+                } else {
+                    PT_CHECK(state.context, pt_copy_to_host(state.context, host.data(), shown, host.size() * sizeof(float)));
+                }
                 if (!savePFM(out_hdr, host.data(), width, height, 4)) std::cerr << "could not write " << out_hdr << std::endl;
             }
             if (denoise_iters > 0) saveDenoised(state, denoisedName(out), (uint32_t)denoise_iters, display ? &display_params : nullptr, suffixedName(out, "_display"),
-                                                (const float*)filtered);
-            else if (display) saveDisplay(state, suffixedName(out, "_display"), shown, display_params);
+                                                (const float*)filtered, use_bloom ? &bloom : nullptr);
+            else if (display) saveDisplay(state, suffixedName(out, "_display"), shown, display_params, use_bloom ? &bloom : nullptr);
             if (filtered) pt_device_free(state.context, filtered);
             if (!history_in.empty() || !history_out.empty()) {
                 HistoryFile mine = historyOfRun(state, light_mode, math_mode, material_model);      // the settings at the end: --keys may have changed them

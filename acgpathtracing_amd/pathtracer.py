@@ -703,22 +703,125 @@ def denoise(state, iterations=5, firefly=None):
 TONE_CURVES = {"linear": _native.TONE_LINEAR, "reinhard": _native.TONE_REINHARD, "aces": _native.TONE_ACES}
 
 
+# pt_bloom_params' defaults (include/acgpt.h; DESIGN.md section 21 has the table the intensity was picked from)
+BLOOM_DEFAULTS = {"threshold": 1.0, "knee": 0.5, "clamp": 0.0, "intensity": 0.02, "spread": 1.0, "levels": 6}
+
+
+def _bloom_settings(settings, what):
+    """BLOOM_DEFAULTS overlaid with `settings`, checked against pt_bloom_params' ranges here on the host"""
+    unknown = set(settings) - set(BLOOM_DEFAULTS)
+    if unknown:
+        raise ValueError("%s: unknown bloom settings %s (known: %s)" % (what, sorted(unknown), sorted(BLOOM_DEFAULTS)))
+    d = dict(BLOOM_DEFAULTS)
+    d.update(settings)
+    v = {k: float(d[k]) for k in ("threshold", "knee", "clamp", "intensity", "spread")}
+    for k in ("threshold", "clamp", "intensity"):
+        if not (np.isfinite(v[k]) and v[k] >= 0.0):
+            raise ValueError("%s: %s must be finite and >= 0" % (what, k))
+    if not (np.isfinite(v["knee"]) and 0.0 <= v["knee"] <= v["threshold"]):
+        raise ValueError("%s: knee must be finite and in [0, threshold]" % what)
+    if not (np.isfinite(v["spread"]) and 0.0 <= v["spread"] <= 4.0):
+        raise ValueError("%s: spread must be finite and in [0, 4]" % what)
+    if int(d["levels"]) != d["levels"] or not 1 <= int(d["levels"]) <= _native.BLOOM_MAX_LEVELS:
+        raise ValueError("%s: levels must be an integer in [1, %d]" % (what, _native.BLOOM_MAX_LEVELS))
+    v["levels"] = int(d["levels"])
+    return v
+
+
+def _bloom_params(v, exposure=None):
+    """pt_bloom_params of checked settings; with an exposure, threshold, knee and clamp are in display units (multiples of exposed
+    white) and are divided by it, in fp32"""
+    t, k, c = (np.float32(v[name]) for name in ("threshold", "knee", "clamp"))
+    if exposure is not None:
+        e = np.float32(exposure)
+        t, k, c = t / e, k / e, c / e
+    return _native.BloomParams(float(t), float(k), float(c), v["intensity"], v["spread"], v["levels"])
+
+
+def _bloom_info(info):
+    total, bright = int(info.total_luma_q16), int(info.bright_luma_q16)
+    return {"levels": int(info.levels), "bright_pixels": int(info.bright_pixels), "invalid_pixels": int(info.invalid_pixels), "total_luma_q16": total,
+            "bright_luma_q16": bright, "max_luma": float(info.max_luma), "bright_share": bright / total if total else 0.0}
+
+
+def bloom(state, image=None, threshold=BLOOM_DEFAULTS["threshold"], knee=BLOOM_DEFAULTS["knee"], clamp=BLOOM_DEFAULTS["clamp"],
+          intensity=BLOOM_DEFAULTS["intensity"], spread=BLOOM_DEFAULTS["spread"], levels=BLOOM_DEFAULTS["levels"]):
+    """The glare of the pixels brighter than `threshold` added to a linear HDR image (include/acgpt.h pt_bloom): (float32 [height,
+    width, 4], info).  image: None for the state's accumulation buffer, a device pointer to float4[height * width], or a float32
+    [height, width, 4] array (uploaded).  threshold, knee and clamp are in the image's radiance units here (displayTransform(bloom=)
+    takes them in display units).  info: levels, bright_pixels, invalid_pixels, total_luma_q16, bright_luma_q16, max_luma and
+    bright_share, the part of the image's luminance that went into the pyramid.  The source image is left as it is."""
+    v = _bloom_settings({"threshold": threshold, "knee": knee, "clamp": clamp, "intensity": intensity, "spread": spread, "levels": levels}, "bloom")
+    L = _native.hip()
+    h, w = int(state.params.height), int(state.params.width)
+    bp = _bloom_params(v)
+    bufs = _device_buffers(state, 1, w * h * 16)
+    try:
+        src = _source_image(state, image, bufs, "bloom")
+        info = _native.BloomInfo()
+        _check(state.context, L.pt_bloom(state.context, src, w, h, C.byref(bp), bufs[0], C.byref(info)), "pt_bloom")
+        out = _read_image(state, bufs[0])
+    finally:
+        _free_device_buffers(state, bufs)
+    return out, _bloom_info(info)
+
+
+def _display_info(info):
+    return {"exposure": float(info.exposure), "metered_luminance": float(info.metered_luminance), "metered_pixels": int(info.metered_pixels),
+            "unmetered_pixels": int(info.unmetered_pixels), "histogram": np.array(info.histogram, np.uint32)}
+
+
+def _display_bloomed(state, image, dp, settings):
+    """displayTransform(bloom=settings): the exposure first (metered on the image without its glare, or the manual one), pt_bloom with
+    threshold, knee and clamp divided by it, then the curve at that exposure as a manual one"""
+    L = _native.hip()
+    h, w = int(state.params.height), int(state.params.width)
+    bufs = _device_buffers(state, 1, w * h * 4) + _device_buffers(state, 1, w * h * 16)
+    try:
+        src = _source_image(state, image, bufs, "displayTransform")
+        info = _native.DisplayInfo()
+        if dp.exposure > 0.0:
+            info.exposure = dp.exposure             # as the manual call reports it: nothing metered
+        else:
+            _check(state.context, L.pt_display_transform(state.context, src, w * h, C.byref(dp), None, bufs[0], C.byref(info)), "pt_display_transform")
+        bp = _bloom_params(settings, info.exposure)
+        binfo = _native.BloomInfo()
+        _check(state.context, L.pt_bloom(state.context, src, w, h, C.byref(bp), bufs[1], C.byref(binfo)), "pt_bloom")
+        manual = _native.DisplayParams()
+        C.memmove(C.byref(manual), C.byref(dp), C.sizeof(manual))
+        manual.exposure = info.exposure
+        _check(state.context, L.pt_display_transform(state.context, bufs[1], w * h, C.byref(manual), None, bufs[0], None), "pt_display_transform")
+        rgba = np.zeros((h, w, 4), np.uint8)
+        _check(state.context, L.pt_copy_to_host(state.context, rgba.ctypes.data, bufs[0], rgba.nbytes), "copy to host")
+    finally:
+        _free_device_buffers(state, bufs)
+    out = _display_info(info)
+    out["bloom"] = _bloom_info(binfo)
+    return rgba, out
+
+
 def displayTransform(state, image=None, curve="aces", exposure=None, key=0.18, white=4.0, window=(100, 900), limits=(2.0 ** -16, 2.0 ** 16),
-                     prev_exposure=None, adapt=1.0):
+                     prev_exposure=None, adapt=1.0, bloom=None):
     """Exposure and tone mapping of a linear HDR image (include/acgpt.h pt_display_transform): (rgba8 [height, width, 4] with row 0 =
     bottom, info).  image: None for the state's accumulation buffer, a device pointer to float4[height * width], or a float32
     [height, width, 4] array (uploaded).  exposure: None for the histogram auto-exposure (key, window = (lo, hi) in permille of the
     metered pixels, limits = (min, max) exposure, prev_exposure / adapt for eye adaptation), else the manual factor.  curve: "linear",
     "reinhard" (white point `white`) or "aces".  info: exposure, metered_luminance, metered_pixels, unmetered_pixels, histogram.  The
-    source image is left as it is."""
+    source image is left as it is.  bloom: None, or a dict of bloom()'s settings ({} for the defaults): the image goes through pt_bloom
+    before the curve.  threshold, knee and clamp are then in display units, multiples of exposed white, and are divided by the
+    exposure; an automatic exposure is metered on the image without its glare (one more pt_display_transform call, which honours
+    prev_exposure and adapt) and applied as a manual one.  info is the metering call's, plus "bloom": bloom()'s info."""
     if curve not in TONE_CURVES:
         raise ValueError("displayTransform: curve must be one of %s" % sorted(TONE_CURVES))
     if exposure is not None and not float(exposure) > 0.0:
         raise ValueError("displayTransform: a manual exposure must be > 0 (None: automatic)")
+    settings = None if bloom is None else _bloom_settings(bloom, "displayTransform")
     L = _native.hip()
     h, w = int(state.params.height), int(state.params.width)
     dp = _native.DisplayParams(TONE_CURVES[curve], 0.0 if exposure is None else float(exposure), float(key), float(white), int(window[0]), int(window[1]),
                                float(limits[0]), float(limits[1]), 0.0 if prev_exposure is None else float(prev_exposure), float(adapt))
+    if settings is not None:
+        return _display_bloomed(state, image, dp, settings)
     bufs = _device_buffers(state, 1, w * h * 4)
     try:
         src = _source_image(state, image, bufs, "displayTransform")
@@ -728,14 +831,14 @@ def displayTransform(state, image=None, curve="aces", exposure=None, key=0.18, w
         _check(state.context, L.pt_copy_to_host(state.context, rgba.ctypes.data, bufs[0], rgba.nbytes), "copy to host")
     finally:
         _free_device_buffers(state, bufs)
-    return rgba, {"exposure": float(info.exposure), "metered_luminance": float(info.metered_luminance), "metered_pixels": int(info.metered_pixels),
-                  "unmetered_pixels": int(info.unmetered_pixels), "histogram": np.array(info.histogram, np.uint32)}
+    return rgba, _display_info(info)
 
 
 class AutoExposure:
     """Eye adaptation over displayTransform: carries the exposure from call to call.  frame(state, dt) meters the image and moves the
     exposure towards its target by adapt = 1 - exp(-dt * speed), computed here on the host (dt in seconds since the last call; the
-    first call jumps).  The other arguments are displayTransform's."""
+    first call jumps).  The other arguments are displayTransform's, bloom= among them: every frame then gets the glare, at the adapted
+    exposure."""
 
     def __init__(self, speed=3.0, **settings):
         self.speed = float(speed)

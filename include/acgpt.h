@@ -710,6 +710,76 @@ typedef struct pt_firefly_info {
 int pt_firefly_filter(pt_ctx* ctx, const float* src_rgba, uint32_t width, uint32_t height,
                       const pt_firefly_params* fp, float* out_rgba, pt_firefly_info* info);
 
+/* ---- bloom (opt-in; nothing above changes) -------------------------------------------------------------------------------------
+ * pt_bloom adds the glare of the pixels brighter than display white to a linear HDR image, ahead of pt_display_transform: the tone
+ * curves clamp at 1, so without it an emitter of radiance 15 and one of 1500 are the same flat disc.  The part of every pixel above
+ * a threshold goes down an image pyramid (a 4 x 4 binomial per level) and comes up again (bilinear), every level added to the next
+ * finer one; the sum, scaled so that the filters together have the gain `intensity`, is added to the source.  Enqueues on the
+ * context's stream and returns synchronised, acts on rank 0 of a pt_create_multi context, needs no scene, never writes the
+ * accumulation buffer (unless it is passed as src, which is only read), the frame buffer or pt_stats.  A caller of the reference's
+ * loop calls it after the denoiser and before the display transform.
+ *   src_rgba   DEVICE float4[width * height], row-major, linear radiance; only read
+ *   out_rgba   DEVICE float4[width * height]; must not overlap src_rgba (refused, not undefined)
+ *   info       HOST or NULL (NULL skips only the copy to the host)
+ * The arithmetic.  All floating point is fp32, one rounding per written operation, evaluated left to right as bracketed, no
+ * contraction, IEEE division, no transcendental function; the reductions are integer sums and a max of bit patterns, so the order of
+ * the atomics cannot change a bit.  tests/bloom_ref.py is the NumPy statement of the same thing.
+ *   Levels.  (w_0, h_0) = (width, height); w_k = (w_(k-1) + 1) / 2 in integers, h_k likewise; n = min(levels, the first k with
+ *     w_k = h_k = 1): a 1 x 1 source builds one 1 x 1 level.  cx_k(i) = min(max(i, 0), w_k - 1), cy_k likewise: clamp to the edge.
+ *   Prefilter P(p).  l = (0.2126f * r + 0.7152f * g) + 0.0722f * b;  valid(p): l is finite and l >= 0.  An invalid pixel gives
+ *     P = (0, 0, 0).  A valid one:  d = l - threshold;
+ *       knee > 0:  s = min(max(l - (threshold - knee), 0), knee + knee);  q = (s * s) / ((knee + knee) + (knee + knee));  e = max(q, d)
+ *       knee = 0:  e = max(d, 0)
+ *       clamp > 0: e = min(e, clamp)
+ *     e > 0: c = e / l, P = rgb * c per channel, the pixel is bright; otherwise P = 0.  With threshold = knee = clamp = 0, c is
+ *     exactly 1 and P is the pixel's own bits.
+ *   Down D, level a to level a + 1 at (X, Y), per channel: the separable binomial {1, 3, 3, 1} / 8 over the 4 x 4 footprint
+ *     row(y) = ((0.125f * A(cx_a(2X-1), y) + 0.375f * A(cx_a(2X), y)) + 0.375f * A(cx_a(2X+1), y)) + 0.125f * A(cx_a(2X+2), y)
+ *     D = ((0.125f * row(cy_a(2Y-1)) + 0.375f * row(cy_a(2Y))) + 0.375f * row(cy_a(2Y+1))) + 0.125f * row(cy_a(2Y+2))
+ *     level 1 = D of the prefiltered source (P in A's place), level k + 1 = D of level k.
+ *   Up U, level b to the size of level b - 1 at (x, y), per channel: bilinear at the texel centres.  i = x >> 1;
+ *       x even: j0 = cx_b(i - 1), j1 = i, (a0, a1) = (0.25f, 0.75f);   x odd: j0 = i, j1 = cx_b(i + 1), (a0, a1) = (0.75f, 0.25f)
+ *     row(yy) = a0 * E(j0, yy) + a1 * E(j1, yy); the same rule in y gives k0, k1, b0, b1;  U = b0 * row(k0) + b1 * row(k1)
+ *   Combine.  E_n = level n; for k = n - 1 .. 1: E_k = D_k + spread * U(E_(k+1)), in place (a texel reads only itself on its own
+ *     level).  On the host, in fp32: norm = 1, t = 1, then n - 1 times t = t * spread, norm = norm + t;  gain = intensity / norm.
+ *   Output.  out.rgb = src.rgb + gain * U(E_1);  out.w = src.w as bits.  The add is a plain IEEE add: a NaN or infinite source pixel
+ *     stays what it was (a signalling NaN quieted) and, feeding nothing, reaches no other pixel; -0 becomes +0.
+ *   info: total_luma_q16 is the sum over the valid pixels of (uint64) trunc(min(l, 2^24) * 65536) and bright_luma_q16 the same
+ *     conversion of e over the bright pixels, both modulo 2^64: bright / total is the share of the image's luminance that glares;
+ *     max_luma is the max of bits(l) as uint32 over the valid pixels (unsigned order is float order for l >= +0; a luminance of -0,
+ *     which only a pixel of zeros with a sign gives, counts with its own bits), 0 if none.
+ * Refused before any device work, with a message, leaving the context usable: a NULL ctx, src_rgba, bp or out_rgba; a zero width or
+ * height, or width * height > 2^31; a threshold, clamp or intensity that is not finite or < 0; a knee that is not finite or outside
+ * [0, threshold]; a spread that is not finite or outside [0, 4]; levels outside [1, 8]; out_rgba overlapping src_rgba.
+ * Kernels (csrc/bloom.hip): prefilter and first down step in one, a workgroup per 16 x 16 tile of level 1 with the prefiltered 34 x
+ * 34 source footprint in LDS and one vector atomic per workgroup and field; the same kernel without the prefilter for the further
+ * levels; one kernel for every up step, the last of which is the composite; one lane that writes the record and clears the counts:
+ * 2 n + 1 launches.  The context keeps the pyramid (float4 per texel, all levels in one allocation, at most a third of the source
+ * plus a few texels; it grows on demand), the counts and the record (72 bytes), all freed by pt_destroy.  Two calls give the same
+ * bits; pt_set_math_mode does not reach this code.                                                                              */
+typedef struct pt_bloom_params {
+    float    threshold;  /* finite, >= 0, in src's radiance units: luminance below it does not glare; 0: everything does; default 1 */
+    float    knee;       /* finite, 0 <= knee <= threshold: half width of the soft transition around threshold; 0: hard; default 0.5 */
+    float    clamp;      /* finite, >= 0: most luminance one pixel may feed into the pyramid; 0: no limit (the default) */
+    float    intensity;  /* finite, >= 0: the glare added is intensity x the spread-out bright part; default 0.02 */
+    float    spread;     /* finite, in [0, 4]: weight of each coarser level against the next finer one; 1: all equal (the default) */
+    uint32_t levels;     /* 1..8 requested; fewer are built when the image runs out (info.levels); default 6 */
+} pt_bloom_params;
+
+typedef struct pt_bloom_info {
+    uint32_t levels;           /* n, the levels built */
+    uint32_t bright_pixels;    /* valid pixels with e > 0 */
+    uint32_t invalid_pixels;   /* NaN, infinite or negative luminance: they feed nothing */
+    uint32_t reserved;
+    uint64_t total_luma_q16;   /* the luminance of the valid pixels, in 2^-16 */
+    uint64_t bright_luma_q16;  /* the luminance e the bright pixels fed into the pyramid, in 2^-16 */
+    float    max_luma;         /* the largest luminance among the valid pixels; 0 if none */
+    uint32_t reserved2;
+} pt_bloom_info;
+
+int pt_bloom(pt_ctx* ctx, const float* src_rgba, uint32_t width, uint32_t height,
+             const pt_bloom_params* bp, float* out_rgba, pt_bloom_info* info);
+
 /* ---- device memory helpers for bindings that have no HIP runtime of their own
  * (the reference app calls cudaMalloc/cudaMemcpy directly, :145-148).         */
 int pt_device_malloc(pt_ctx* ctx, void** out, size_t bytes);
