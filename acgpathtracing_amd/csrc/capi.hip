@@ -1,47 +1,19 @@
-// capi.hip — implementation of include/acgpt.h on the HIP runtime.
+// capi.hip — the render core of include/acgpt.h on the HIP runtime: errors, context lifetime, the multi-GPU group, scene set-up
+// and updates, the setters, the launch path.  The stages that work on a finished image are in capi_image.hip, the entry points
+// of include/acgpt_test.h in capi_test.hip; context.h holds what the three share.
 // Each export names the reference function it stands in for (see acgpt.h).  There is no
 // CPU path in this library: every entry point fails if no HIP device is usable.
-#include <hip/hip_runtime.h>
-// RCCL: types only — librccl is loaded with dlopen by pt_create_multi, a single-GPU caller never touches it, and a box without
-// the RCCL headers still builds the library (the handful of types and enumerators used below, with rccl.h's values)
-#if __has_include(<rccl/rccl.h>)
-#include <rccl/rccl.h>
-#else
-typedef struct ncclComm* ncclComm_t;
-typedef enum { ncclSuccess = 0 } ncclResult_t;
-typedef enum { ncclFloat = 7 } ncclDataType_t;
-typedef enum { ncclSum = 0 } ncclRedOp_t;
-#endif
 #include <dlfcn.h>
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
 
-#include "../../include/acgpt.h"
-#include "../../include/acgpt_test.h"
-#include "convergence.h"
-#include "denoise.h"
-#include "display.h"
-#include "environment.h"
-#include "firefly.h"
-#include "bloom.h"
-#include "image_common.h"
-#include "lbvh_build.h"
+#include "context.h"
 #include "materials.h"
-#include "pt_device.h"
 #include "refit.h"
-#include "render_megakernel.h"
-#include "selftest.h"
-#include "temporal.h"
-
-#define PT_API extern "C" __attribute__((visibility("default")))
 
 static_assert(sizeof(pt_params) == 168, "pt_params must mirror PathTraceParams (168 bytes)");
 static_assert(sizeof(pt_material) == 40, "pt_material must mirror Material (40 bytes)");
@@ -49,77 +21,16 @@ static_assert(sizeof(pt_area_light) == 60, "pt_area_light must mirror AreaLight 
 static_assert(sizeof(pt_stats) == 96 && sizeof(pt_bvh_info) == 88, "ABI version 4: a change of these layouts bumps pt_abi_version");
 static_assert(sizeof(pt_update_info) == 16, "pt_update_info: 16 bytes, a change of its layout bumps pt_abi_version");
 
-struct pt_multi;
-
-struct pt_ctx {
-    int device = 0;
-    int n_cus = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // bracket the render kernel alone (k_finalize sits outside)
-    ptd::LbvhResult bvh;
-    ptd::DevMaterial* d_mats = nullptr;       // pt_material repacked into two aligned 16-byte halves (pt_device.h)
-    uint32_t n_mats = 0;
-    float4* d_lights = nullptr;               // emissive triangles of the scene (light mode 1), 5 float4 each
-    uint32_t n_lights = 0;
-    float light_area = 0.0f;
-    int light_mode = 0;                       // 0 the reference's estimator, 1 scene lights + MIS (pt_set_light_mode)
-    int material_model = PT_MATERIALS_REFERENCE;   // pt_set_material_model: the context's, kept across scene changes
-    float* d_alpha = nullptr;                 // GGX alpha per material (the GGX kernels' table, pt_microfacet.h), beside d_mats
-    int math_mode = PT_MATH_FAST;             // arithmetic of the shading code (pt_set_math_mode): the reference's own build uses nvcc --use_fast_math
-    uint32_t stack_entries = 8;
-    int blocks_per_cu = 0;        // from the occupancy query for the current stack size
-    int tune_blocks_per_cu = 0;   // user override
-    int build_mode = 2;           // 0 Karras LBVH, 1 PLOC over the Morton order, 2 PLOC + insertion-based optimisation of small trees (the default)
-    int variant = ptd::kDefaultVariant;   // render kernel variant (render_megakernel.hip)
-    bool variant_auto = true;             // until pt_set_tuning picks one: chosen per scene size in pt_set_scene
-    uint32_t* d_queue = nullptr;              // 8 shard heads
-    unsigned long long* d_counters = nullptr; // 8 counters
-    int rank = 0, world = 1;
-    int chunks = 0;                           // sample chunks per pixel: 0 = automatic, else 1/2/4/8/16
-    float4* d_frame_sums = nullptr; size_t frame_sums_bytes = 0;   // [pixel][sub-frame] of a frame batch
-    float* d_wave_scratch = nullptr; size_t wave_scratch_bytes = 0;    // fold slots of every wave of the grid
-    uint32_t* d_stack_ovf = nullptr; size_t stack_ovf_bytes = 0;       // stack entries beyond a kernel's LDS cap
-    size_t scratch_limit = (size_t)1 << 30;                          // a frame batch is cut into launches whose frame sums fit
-    // division constants of the tile order, valid for (div_width, div_world_n): built and verified once per image width
-    uint32_t div_width = 0; int div_world_n = 0; ptd::FastDiv div_cols = {0, 0, 0}, div_world = {0, 0, 0};
-    uint2* d_row_spans = nullptr; size_t row_spans_rows = 0;         // pixel classes per image row (row_spans below)
-    std::vector<float> spans_key;                                    // what the spans on the device were computed from
-    int pixel_classes = 1;                                           // 0: off (pt_debug_pixel_classes)
-    int queue_order = 1;                      // tile-strip rows dealt round robin over the queue shards (render_common.h queue_slot; pt_debug_queue_order)
-    pt_multi* multi = nullptr;                // pt_create_multi: this context is rank 0 of a group (below)
-    float4* d_denoise[2] = {nullptr, nullptr}; size_t denoise_pixels = 0;   // pt_denoise's ping-pong {colour, variance} buffers
-    ptd::EnvDevice env;                       // pt_set_environment's map and CDFs (w == 0: none); the context's, kept across scene changes
-    ptd::DisplayState* d_display = nullptr; bool display_dirty = false;     // pt_display_transform's counts and meter record (dirty: a call failed half way)
-    ptd::FireflyState* d_firefly = nullptr; bool firefly_dirty = false;     // pt_firefly_filter's counts and record (dirty: a call failed half way)
-    ptd::BloomState* d_bloom = nullptr; bool bloom_dirty = false;           // pt_bloom's counts and record (dirty: a call failed half way) ...
-    float4* d_bloom_pyramid = nullptr; uint64_t bloom_texels = 0;           // ... and its pyramid, all levels in one allocation: grows on demand
-    ptd::ConvergenceState* d_convergence = nullptr; bool convergence_dirty = false;   // pt_convergence_update's counts and record (dirty: a call failed half way)
-    uint8_t* d_tri_bsdf = nullptr;            // bsdfType per triangle (caller's order): pt_temporal_blend's, built on its first call per scene
-    // what pt_update_vertices keeps of the last pt_set_scene: host copies of everything but the vertices, and after the first update
-    // the index buffer on the device (freed with the scene)
-    bool scene_kept = false;
-    size_t kept_n_verts = 0;
-    std::vector<uint32_t> kept_idx, kept_mat_ids;
-    std::vector<pt_material> kept_mats;
-    uint32_t* d_idx = nullptr;
-    double build_area = -1.0;                 // inner-node area sum over the root's at the last build (refit_tree_area; < 0: not taken yet)
-    pt_stats stats;
-    uint64_t scene_serial = 0;
-    std::string err;
-};
-
 static std::mutex g_err_mu;
 static std::string g_err;
 
-static int fail(pt_ctx* c, const std::string& m)
+int fail(pt_ctx* c, const std::string& m)
 {
     if (c) c->err = m;
     std::lock_guard<std::mutex> lk(g_err_mu);
     g_err = m;
     return 1;
 }
-#define CK(c, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail((c), std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 // ---- ROCTx ranges (tracing): scene build, launch, finalize, reduce show up labelled in a
 // `rocprofv3 --marker-trace` of any caller.  The marker library is looked up once at run time; without it the ranges are no-ops.
@@ -139,40 +50,9 @@ struct Roctx {
     }
 };
 static Roctx& roctx() { static Roctx r; return r; }
-struct Range {
-    bool on;
-    explicit Range(const char* name) : on(roctx().push != nullptr) { if (on) roctx().push(name); }
-    ~Range() { if (on) roctx().pop(); }
-};
 }  // namespace
-
-// ---- multi-GPU group (pt_create_multi): rank 0 is the context the caller holds; it owns the others -----------------
-// One context, stream and host thread per device; the tile partition of sutil/WorkDistribution.h:50-81 per rank; each rank
-// accumulates its own pixels in a private full-size float4 buffer that is zero elsewhere; ONE ncclReduce(SUM) per launch
-// brings them into the caller's accumulation buffer on rank 0 (every pixel has exactly one non-zero term, so the sum is
-// that term bit for bit) and rank 0 applies make_color.  Replaces the dormant multi-GPU branch of the reference
-// (sutil/WorkDistribution.h, sutil/CUDAOutputBuffer.h CUDA_P2P).
-struct RcclApi {
-    void* lib = nullptr;
-    ncclResult_t (*CommInitAll)(ncclComm_t*, int, const int*) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*Reduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*GroupStart)() = nullptr;
-    ncclResult_t (*GroupEnd)() = nullptr;
-    const char* (*GetErrorString)(ncclResult_t) = nullptr;
-};
-struct pt_multi {
-    std::vector<pt_ctx*> ranks;          // ranks[0] = the context the caller holds
-    std::vector<float4*> accum;          // private accumulation buffer of each rank (its own pixels, zero elsewhere)
-    uint32_t accum_w = 0, accum_h = 0;   // image shape the private buffers were allocated for
-    bool rehearsal = false;              // all ranks on ONE device (one-GPU box): a sum kernel stands in for RCCL
-    RcclApi rccl;
-    std::vector<ncclComm_t> comms;
-    const void* cont_accum = nullptr;    // the caller's buffer and the frame index a straight continuation would pass next
-    uint32_t cont_frame = 0, cont_w = 0, cont_h = 0;
-    float reduce_ms = 0.0f;
-    pt_stats group_stats;
-};
+Range::Range(const char* name) : on(roctx().push != nullptr) { if (on) roctx().push(name); }
+Range::~Range() { if (on) roctx().pop(); }
 
 PT_API uint32_t pt_abi_version(void) { return 4u; }
 
@@ -198,8 +78,7 @@ static int create_one(pt_ctx** out, int device_id)
     c->n_cus = prop.multiProcessorCount;
     memset(&c->stats, 0, sizeof(c->stats));
     if (hipStreamCreate(&c->own_stream) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
-        hipMalloc((void**)&c->d_queue, 8 * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void**)&c->d_counters, (size_t)ptd::kCounterWords * sizeof(unsigned long long)) != hipSuccess) {
+        c->d_queue.reserve(8, c->own_stream) != hipSuccess || c->d_counters.reserve((size_t)ptd::kCounterWords, c->own_stream) != hipSuccess) {
         delete c;
         return fail(nullptr, "pt_create: device resource allocation failed");
     }
@@ -253,7 +132,6 @@ PT_API int pt_create_multi(pt_ctx** out, const int* device_ids, int n_devices)
         c->rank = i; c->world = n_devices;
         m->ranks.push_back(c);
     }
-    m->accum.assign((size_t)n_devices, nullptr);
     if (!m->rehearsal) {
         std::string err;
         bool ok = load_rccl(m->rccl, err);
@@ -276,33 +154,11 @@ PT_API int pt_create_multi(pt_ctx** out, const int* device_ids, int n_devices)
 
 PT_API int pt_device_count(pt_ctx* c) { return !c ? 0 : (c->multi ? (int)c->multi->ranks.size() : 1); }
 
-// f(rank context, rank index) on every rank of a group, each on its own host thread (rank 0 on the caller's); the first
-// failure's message becomes the group's
-template <typename F>
-static int on_every_rank(pt_ctx* c, F f)
-{
-    pt_multi* m = c->multi;
-    const size_t n = m->ranks.size();
-    std::vector<int> rc(n, 0);
-    std::vector<std::thread> th;
-    for (size_t i = 1; i < n; i++) th.emplace_back([&, i]() { rc[i] = f(m->ranks[i], (int)i); });
-    rc[0] = f(m->ranks[0], 0);
-    for (auto& t : th) t.join();
-    for (size_t i = 0; i < n; i++)
-        if (rc[i] != 0) return fail(c, "rank " + std::to_string(i) + " (device " + std::to_string(m->ranks[i]->device) + "): " + m->ranks[i]->err);
-    return 0;
-}
-
 static void free_scene(pt_ctx* c)
 {
     ptd::free_lbvh(c->bvh);
-    if (c->d_mats) { (void)hipFree(c->d_mats); c->d_mats = nullptr; }
-    if (c->d_alpha) { (void)hipFree(c->d_alpha); c->d_alpha = nullptr; }
-    c->n_mats = 0;
-    if (c->d_lights) { (void)hipFree(c->d_lights); c->d_lights = nullptr; }
-    c->n_lights = 0; c->light_area = 0.0f;
-    if (c->d_tri_bsdf) { (void)hipFree(c->d_tri_bsdf); c->d_tri_bsdf = nullptr; }
-    if (c->d_idx) { (void)hipFree(c->d_idx); c->d_idx = nullptr; }
+    c->d_mats.release(); c->d_alpha.release(); c->d_lights.release(); c->d_tri_bsdf.release(); c->d_idx.release();
+    c->n_mats = 0; c->n_lights = 0; c->light_area = 0.0f;
     c->scene_kept = false; c->kept_n_verts = 0;
     c->kept_idx.clear(); c->kept_mat_ids.clear(); c->kept_mats.clear();
     c->build_area = -1.0;
@@ -315,7 +171,6 @@ PT_API void pt_destroy(pt_ctx* c)
         c->multi = nullptr;
         for (size_t i = 0; i < m->ranks.size(); i++) { (void)hipSetDevice(m->ranks[i]->device); (void)hipStreamSynchronize(m->ranks[i]->stream); }
         for (ncclComm_t k : m->comms) if (k) (void)m->rccl.CommDestroy(k);
-        for (size_t i = 0; i < m->ranks.size(); i++) if (m->accum[i]) { (void)hipSetDevice(m->ranks[i]->device); (void)hipFree(m->accum[i]); }
         for (size_t i = 1; i < m->ranks.size(); i++) destroy_one(m->ranks[i]);
         // librccl stays loaded: unloading a library that owns threads and device state at this point buys nothing
         delete m;
@@ -323,28 +178,20 @@ PT_API void pt_destroy(pt_ctx* c)
     destroy_one(c);
 }
 
+// Order: device selected, stream synchronised, buffers freed (the tree, the map, and with the context every DevBuf it holds: nothing
+// to list, a buffer added to pt_ctx is freed here), then the events, then the stream.
 static void destroy_one(pt_ctx* c)
 {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    free_scene(c);
-    if (c->d_queue) (void)hipFree(c->d_queue);
-    if (c->d_counters) (void)hipFree(c->d_counters);
-    if (c->d_frame_sums) (void)hipFree(c->d_frame_sums);
-    if (c->d_wave_scratch) (void)hipFree(c->d_wave_scratch);
-    if (c->d_stack_ovf) (void)hipFree(c->d_stack_ovf);
-    if (c->d_row_spans) (void)hipFree(c->d_row_spans);
+    ptd::free_lbvh(c->bvh);
     ptd::env_free(c->env);
-    for (float4* b : c->d_denoise) if (b) (void)hipFree(b);
-    if (c->d_display) (void)hipFree(c->d_display);
-    if (c->d_convergence) (void)hipFree(c->d_convergence);
-    if (c->d_firefly) (void)hipFree(c->d_firefly);
-    if (c->d_bloom) (void)hipFree(c->d_bloom);
-    if (c->d_bloom_pyramid) (void)hipFree(c->d_bloom_pyramid);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+    const hipEvent_t ev0 = c->ev0, ev1 = c->ev1;
+    const hipStream_t own_stream = c->own_stream;
     delete c;
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
 }
 
 static int pick_variant(const pt_ctx* c)
@@ -396,7 +243,7 @@ static int ensure_wide(pt_ctx* c)
 
 // The node array a kernel variant traverses, present on the device before anything is launched on it.  A scene keeps one of
 // the two — set_scene_one releases the other — and any of them comes back on first use (lbvh_build.h).
-static int ensure_node_format(pt_ctx* c, int fmt)
+int ensure_node_format(pt_ctx* c, int fmt)
 {
     if (c->bvh.n_tris == 0) return 0;
     std::string err;
@@ -446,11 +293,11 @@ static void add_light(std::vector<float4>& lights, float& run, const float a[3],
 // replaces the scene's list
 static int put_lights(pt_ctx* c, const std::vector<float4>& lights, float run)
 {
-    if (c->d_lights) { (void)hipFree(c->d_lights); c->d_lights = nullptr; }
+    c->d_lights.release();
     c->n_lights = 0; c->light_area = 0.0f;
     if (!lights.empty()) {
-        CK(c, hipMalloc((void**)&c->d_lights, lights.size() * sizeof(float4)));
-        CK(c, hipMemcpy(c->d_lights, lights.data(), lights.size() * sizeof(float4), hipMemcpyHostToDevice));
+        CK(c, c->d_lights.reserve(lights.size(), c->stream));
+        CK(c, hipMemcpy(c->d_lights.p, lights.data(), lights.size() * sizeof(float4), hipMemcpyHostToDevice));
     }
     c->n_lights = (uint32_t)(lights.size() / 5);
     c->light_area = run;
@@ -475,8 +322,7 @@ static int upload_lights(pt_ctx* c, const float* verts_xyzw, const uint32_t* idx
 // model, pt_set_material_model: roughness clamped to [0, 1], NaN as 0); reallocated only when the count changes
 static int upload_materials(pt_ctx* c, const pt_material* mats, size_t n_mats)
 {
-    if (c->d_mats && c->n_mats != n_mats) { (void)hipFree(c->d_mats); c->d_mats = nullptr; }
-    if (c->d_alpha && c->n_mats != n_mats) { (void)hipFree(c->d_alpha); c->d_alpha = nullptr; }
+    if (c->n_mats != n_mats) { c->d_mats.release(); c->d_alpha.release(); }
     c->n_mats = 0;
     if (n_mats == 0) return 0;
     std::vector<ptd::DevMaterial> dm(n_mats);
@@ -488,10 +334,10 @@ static int upload_materials(pt_ctx* c, const pt_material* mats, size_t n_mats)
         dm[i].ke_bsdf = make_float4(m.emission.x, m.emission.y, m.emission.z, bf);
         alpha[i] = m.roughness > 0.0f ? fminf(m.roughness, 1.0f) : 0.0f;         // NaN and negative values: 0
     }
-    if (!c->d_mats) CK(c, hipMalloc((void**)&c->d_mats, n_mats * sizeof(ptd::DevMaterial)));
-    CK(c, hipMemcpy(c->d_mats, dm.data(), n_mats * sizeof(ptd::DevMaterial), hipMemcpyHostToDevice));
-    if (!c->d_alpha) CK(c, hipMalloc((void**)&c->d_alpha, n_mats * sizeof(float)));
-    CK(c, hipMemcpy(c->d_alpha, alpha.data(), n_mats * sizeof(float), hipMemcpyHostToDevice));
+    CK(c, c->d_mats.reserve(n_mats, c->stream));
+    CK(c, hipMemcpy(c->d_mats.p, dm.data(), n_mats * sizeof(ptd::DevMaterial), hipMemcpyHostToDevice));
+    CK(c, c->d_alpha.reserve(n_mats, c->stream));
+    CK(c, hipMemcpy(c->d_alpha.p, alpha.data(), n_mats * sizeof(float), hipMemcpyHostToDevice));
     c->n_mats = (uint32_t)n_mats;
     return 0;
 }
@@ -513,7 +359,6 @@ static int settle_scene(pt_ctx* c)
 static int set_scene_one(pt_ctx* c, const float* verts_xyzw, size_t n_verts, const uint32_t* idx, size_t n_tris,
                         const uint32_t* mat_ids, const pt_material* mats, size_t n_mats)
 {
-    if (!c) return fail(nullptr, "pt_set_scene: null context");
     if (n_tris > 0 && (!verts_xyzw || !idx || !mat_ids || !mats)) return fail(c, "pt_set_scene: null array");
     // the render kernel addresses nodes (64 B) and triangle records (48 B) with 32-bit byte offsets
     if (n_tris >= (1ull << 26) || n_verts >= 0xFFFFFFFFull) return fail(c, "pt_set_scene: too many triangles (limit 2^26) or vertices");
@@ -539,7 +384,7 @@ static int set_scene_one(pt_ctx* c, const float* verts_xyzw, size_t n_verts, con
         if (!ptd::build_lbvh(verts_xyzw, n_verts, idx, n_tris, mat_ids, 0, c->stream, c->bvh, err)) return fail(c, "pt_set_scene: " + err);
     }
     if (int rc = upload_materials(c, mats, n_mats)) return rc;
-    if (n_mats && !ptd::tag_shade_records(c->bvh, c->d_mats, c->stream, err)) return fail(c, "pt_set_scene: " + err);
+    if (n_mats && !ptd::tag_shade_records(c->bvh, c->d_mats.p, c->stream, err)) return fail(c, "pt_set_scene: " + err);
     if (int rc = upload_lights(c, verts_xyzw, idx, n_tris, mat_ids, mats)) return rc;
     if (int rc = settle_scene(c)) return rc;
     c->kept_n_verts = n_verts;
@@ -572,23 +417,20 @@ PT_API int pt_get_bvh_info(pt_ctx* c, pt_bvh_info* out)
     out->half_node_bytes = c->bvh.n_nodes * (uint32_t)sizeof(ptd::HNode);
     out->half_area_ratio = c->bvh.half_area_ratio;
     out->half_box_inflation = c->bvh.half_box_inflation;
-    out->device_bytes = (uint64_t)ptd::scene_device_bytes(c->bvh) + (c->d_tri_bsdf ? (uint64_t)c->bvh.n_tris : 0u) +
-                        (c->d_idx ? (uint64_t)c->bvh.n_tris * 12u : 0u);
+    out->device_bytes = (uint64_t)ptd::scene_device_bytes(c->bvh) + (c->d_tri_bsdf.p ? (uint64_t)c->bvh.n_tris : 0u) +
+                        (c->d_idx.p ? (uint64_t)c->bvh.n_tris * 12u : 0u);
     return 0;
 }
 
 // ---- in-place vertex updates (pt_update_vertices; kernels in refit.hip) -----------------------------------------------------------
 // the scene's index buffer on the device, for pt_update_vertices and pt_temporal_blend_motion: uploaded on the first call of either,
 // counted in device_bytes from then on, freed with the scene
-static int ensure_dev_idx(pt_ctx* c)
+int ensure_dev_idx(pt_ctx* c)
 {
-    if (c->d_idx || c->kept_idx.empty()) return 0;
-    const size_t bytes = c->kept_idx.size() * sizeof(uint32_t);
-    uint32_t* d = nullptr;
-    CK(c, hipMalloc((void**)&d, bytes));
-    const hipError_t e = hipMemcpy(d, c->kept_idx.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); return fail(c, std::string("index buffer upload: ") + hipGetErrorString(e)); }
-    c->d_idx = d;
+    if (c->d_idx.p || c->kept_idx.empty()) return 0;
+    CK(c, c->d_idx.reserve(c->kept_idx.size(), c->stream));
+    const hipError_t e = hipMemcpy(c->d_idx.p, c->kept_idx.data(), c->kept_idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { c->d_idx.release(); return fail(c, std::string("index buffer upload: ") + hipGetErrorString(e)); }
     return 0;
 }
 
@@ -629,7 +471,7 @@ static int update_one(pt_ctx* c, const float* verts_xyzw, size_t n_verts, int mo
     std::string err;
     if (c->build_area < 0.0 && !ptd::refit_tree_area(c->bvh, c->stream, c->build_area, err)) return fail(c, "pt_update_vertices: " + err);
     double area = 1.0;
-    if (!ptd::refit_lbvh(c->bvh, verts_xyzw, n_verts, c->d_idx, c->stream, area, err)) return fail(c, "pt_update_vertices: " + err);
+    if (!ptd::refit_lbvh(c->bvh, verts_xyzw, n_verts, c->d_idx.p, c->stream, area, err)) return fail(c, "pt_update_vertices: " + err);
     const float ratio = c->build_area > 0.0 ? (float)(area / c->build_area) : 1.0f;
     if (mode == PT_UPDATE_AUTO && ratio > PT_UPDATE_AUTO_AREA_RATIO) {
         if (int rc = rebuild_one(c, verts_xyzw, n_verts)) return rc;
@@ -692,7 +534,7 @@ static int update_materials_one(pt_ctx* c, const pt_material* mats, size_t n_mat
     if (int rc = upload_materials(c, mats, n_mats)) return rc;
     std::vector<float> edges;
     std::string err;
-    if (!ptd::update_materials(c->bvh, c->d_mats, mat_ids, light_prims, edges, c->stream, err)) return fail(c, "pt_update_materials: " + err);
+    if (!ptd::update_materials(c->bvh, c->d_mats.p, mat_ids, light_prims, edges, c->stream, err)) return fail(c, "pt_update_materials: " + err);
     if (mat_ids) c->kept_mat_ids.assign(mat_ids, mat_ids + c->kept_mat_ids.size());
     c->kept_mats.assign(mats, mats + n_mats);
     {   // upload_lights' list: the records hold the very v0, e1, e2 it computes from the vertices
@@ -702,7 +544,7 @@ static int update_materials_one(pt_ctx* c, const pt_material* mats, size_t n_mat
             add_light(lights, run, &edges[9 * j], &edges[9 * j + 3], &edges[9 * j + 6], mats[c->kept_mat_ids[light_prims[j]]].emission);
         if (int rc = put_lights(c, lights, run)) return rc;
     }
-    if (c->d_tri_bsdf) { (void)hipFree(c->d_tri_bsdf); c->d_tri_bsdf = nullptr; }      // back on pt_temporal_blend's first call
+    c->d_tri_bsdf.release();      // back on pt_temporal_blend's first call
     if (int rc = settle_scene(c)) return rc;        // the four-wide records, if the variant walks them
     c->scene_serial++;
     return 0;
@@ -738,113 +580,49 @@ PT_API int pt_set_partition(pt_ctx* c, int rank, int world)
     return 0;
 }
 
-static int set_scratch_limit_one(pt_ctx* c, size_t bytes)
-{
-    if (!c) return fail(nullptr, "pt_set_scratch_limit: null context");
-    if (bytes < ((size_t)1 << 20)) return fail(c, "pt_set_scratch_limit: at least 1 MiB");
-    c->scratch_limit = bytes;
-    return 0;
-}
-
-static int set_light_mode_one(pt_ctx* c, int mode)
-{
-    if (!c) return fail(nullptr, "pt_set_light_mode: null context");
-    if (mode != 0 && mode != 1) return fail(c, "pt_set_light_mode: 0 = the reference's estimator (hard-coded rectangle, PathTracerMain.cpp:154-158), 1 = scene lights + MIS");
-    c->light_mode = mode;
-    return 0;
-}
-
-static int set_material_model_one(pt_ctx* c, int model)
-{
-    if (!c) return fail(nullptr, "pt_set_material_model: null context");
-    if (model != PT_MATERIALS_REFERENCE && model != PT_MATERIALS_MICROFACET)
-        return fail(c, "pt_set_material_model: PT_MATERIALS_REFERENCE (0) or PT_MATERIALS_MICROFACET (1)");
-    c->material_model = model;
-    return 0;
-}
-
-static int set_math_mode_one(pt_ctx* c, int mode)
-{
-    if (!c) return fail(nullptr, "pt_set_math_mode: null context");
-    if (mode != PT_MATH_IEEE && mode != PT_MATH_FAST) return fail(c, "pt_set_math_mode: PT_MATH_IEEE (0) or PT_MATH_FAST (1)");
-    c->math_mode = mode;
-    CK(c, hipSetDevice(c->device));           // the twin's occupancy (its register count differs)
-    CK(c, ptd::render_occupancy(c->variant, c->math_mode, c->stack_entries, c->bvh.n_nodes, &c->blocks_per_cu));
-    if (c->blocks_per_cu < 1) return fail(c, "pt_set_math_mode: the kernel of this mode does not fit the current scene in LDS");
-    return 0;
-}
-
-static int set_sample_chunks_one(pt_ctx* c, int chunks)
-{
-    if (!c) return fail(nullptr, "pt_set_sample_chunks: null context");
-    if (chunks != 0 && chunks != 1 && chunks != 2 && chunks != 4 && chunks != 8 && chunks != 16 && chunks != 32) return fail(c, "pt_set_sample_chunks: 0 (automatic), 1, 2, 4, 8, 16 or 32");
-    c->chunks = chunks;
-    return 0;
-}
-
-static int set_tuning_one(pt_ctx* c, int blocks_per_cu, int variant)
-{
-    if (!c) return fail(nullptr, "pt_set_tuning: null context");
-    if (blocks_per_cu < 0 || blocks_per_cu > 16) return fail(c, "pt_set_tuning: blocks_per_cu out of range");
-    if (variant < -1 || variant >= ptd::render_variant_count()) return fail(c, "pt_set_tuning: unknown kernel variant");
-    CK(c, hipSetDevice(c->device));
-    c->tune_blocks_per_cu = blocks_per_cu;
-    c->variant_auto = variant < 0;
-    c->variant = variant < 0 ? pick_variant(c) : variant;
-    if (int rc = ensure_variant_arrays(c)) return rc;
-    CK(c, ptd::render_occupancy(c->variant, c->math_mode, c->stack_entries, c->bvh.n_nodes, &c->blocks_per_cu));
-    if (c->blocks_per_cu < 1) return fail(c, "pt_set_tuning: this kernel variant does not fit the current scene in LDS");
-    return 0;
-}
-
-static int set_build_mode_one(pt_ctx* c, int mode)
-{
-    if (!c) return fail(nullptr, "pt_set_build_mode: null context");
-    if (mode != 0 && mode != 1 && mode != 2) return fail(c, "pt_set_build_mode: 0 = Karras LBVH, 1 = PLOC, 2 = PLOC + insertion-based optimisation");
-    c->build_mode = mode;
-    return 0;
-}
-
+// The setters: a null context refused first, then the same on every rank of a group (on_every_rank: a plain context is its own only rank)
 PT_API int pt_set_scene(pt_ctx* c, const float* verts_xyzw, size_t n_verts, const uint32_t* idx, size_t n_tris,
                         const uint32_t* mat_ids, const pt_material* mats, size_t n_mats)
 {
-    if (c && c->multi) return on_every_rank(c, [&](pt_ctx* r, int) { return set_scene_one(r, verts_xyzw, n_verts, idx, n_tris, mat_ids, mats, n_mats); });
-    return set_scene_one(c, verts_xyzw, n_verts, idx, n_tris, mat_ids, mats, n_mats);
+    if (!c) return fail(nullptr, "pt_set_scene: null context");
+    return on_every_rank(c, [&](pt_ctx* r, int) { return set_scene_one(r, verts_xyzw, n_verts, idx, n_tris, mat_ids, mats, n_mats); });
 }
 
 PT_API int pt_set_scratch_limit(pt_ctx* c, size_t bytes)
 {
-    if (c && c->multi) return on_every_rank(c, [&](pt_ctx* r, int) { return set_scratch_limit_one(r, bytes); });
-    return set_scratch_limit_one(c, bytes);
+    if (!c) return fail(nullptr, "pt_set_scratch_limit: null context");
+    return on_every_rank(c, [&](pt_ctx* r, int) {
+        if (bytes < ((size_t)1 << 20)) return fail(r, "pt_set_scratch_limit: at least 1 MiB");
+        r->scratch_limit = bytes;
+        return 0;
+    });
 }
 
 PT_API int pt_set_light_mode(pt_ctx* c, int mode)
 {
-    if (c && c->multi) return on_every_rank(c, [&](pt_ctx* r, int) { return set_light_mode_one(r, mode); });
-    return set_light_mode_one(c, mode);
+    if (!c) return fail(nullptr, "pt_set_light_mode: null context");
+    return on_every_rank(c, [&](pt_ctx* r, int) {
+        if (mode != 0 && mode != 1) return fail(r, "pt_set_light_mode: 0 = the reference's estimator (hard-coded rectangle, PathTracerMain.cpp:154-158), 1 = scene lights + MIS");
+        r->light_mode = mode;
+        return 0;
+    });
 }
 
 PT_API int pt_set_material_model(pt_ctx* c, int model)
 {
-    if (c && c->multi) return on_every_rank(c, [&](pt_ctx* r, int) { return set_material_model_one(r, model); });
-    return set_material_model_one(c, model);
-}
-
-// texels {r, g, b, 0} with the scale applied (empty: clear the map)
-static int set_environment_one(pt_ctx* c, const std::vector<float4>& rgba, uint32_t w, uint32_t h)
-{
-    CK(c, hipSetDevice(c->device));
-    CK(c, hipStreamSynchronize(c->stream));      // a launch in flight may still read the old map
-    if (rgba.empty()) { ptd::env_free(c->env); return 0; }
-    std::string err;
-    if (!ptd::env_upload(c->env, rgba.data(), w, h, c->stream, err)) return fail(c, err);
-    return 0;
+    if (!c) return fail(nullptr, "pt_set_material_model: null context");
+    return on_every_rank(c, [&](pt_ctx* r, int) {
+        if (model != PT_MATERIALS_REFERENCE && model != PT_MATERIALS_MICROFACET)
+            return fail(r, "pt_set_material_model: PT_MATERIALS_REFERENCE (0) or PT_MATERIALS_MICROFACET (1)");
+        r->material_model = model;
+        return 0;
+    });
 }
 
 PT_API int pt_set_environment(pt_ctx* c, const float* rgb, uint32_t width, uint32_t height, pt_float3 scale)
 {
     if (!c) return fail(nullptr, "pt_set_environment: null context");
-    std::vector<float4> rgba;
+    std::vector<float4> rgba;      // texels {r, g, b, 0} with the scale applied (empty: clear the map)
     if (rgb != nullptr && width != 0u) {
         if (height < 1u || width > ptd::kEnvMaxDim || height > ptd::kEnvMaxDim)
             return fail(c, "pt_set_environment: width and height must lie in [1, " + std::to_string(ptd::kEnvMaxDim) + "]");
@@ -860,32 +638,64 @@ PT_API int pt_set_environment(pt_ctx* c, const float* rgb, uint32_t width, uint3
             rgba[i] = make_float4(r, g, b, 0.0f);
         }
     }
-    if (c->multi) return on_every_rank(c, [&](pt_ctx* r, int) { return set_environment_one(r, rgba, width, height); });
-    return set_environment_one(c, rgba, width, height);
+    return on_every_rank(c, [&](pt_ctx* r, int) {
+        CK(r, hipSetDevice(r->device));
+        CK(r, hipStreamSynchronize(r->stream));      // a launch in flight may still read the old map
+        if (rgba.empty()) { ptd::env_free(r->env); return 0; }
+        std::string err;
+        if (!ptd::env_upload(r->env, rgba.data(), width, height, r->stream, err)) return fail(r, err);
+        return 0;
+    });
 }
 
 PT_API int pt_set_math_mode(pt_ctx* c, int mode)
 {
-    if (c && c->multi) return on_every_rank(c, [&](pt_ctx* r, int) { return set_math_mode_one(r, mode); });
-    return set_math_mode_one(c, mode);
+    if (!c) return fail(nullptr, "pt_set_math_mode: null context");
+    return on_every_rank(c, [&](pt_ctx* r, int) {
+        if (mode != PT_MATH_IEEE && mode != PT_MATH_FAST) return fail(r, "pt_set_math_mode: PT_MATH_IEEE (0) or PT_MATH_FAST (1)");
+        r->math_mode = mode;
+        CK(r, hipSetDevice(r->device));           // the twin's occupancy (its register count differs)
+        CK(r, ptd::render_occupancy(r->variant, r->math_mode, r->stack_entries, r->bvh.n_nodes, &r->blocks_per_cu));
+        if (r->blocks_per_cu < 1) return fail(r, "pt_set_math_mode: the kernel of this mode does not fit the current scene in LDS");
+        return 0;
+    });
 }
 
 PT_API int pt_set_sample_chunks(pt_ctx* c, int chunks)
 {
-    if (c && c->multi) return on_every_rank(c, [&](pt_ctx* r, int) { return set_sample_chunks_one(r, chunks); });
-    return set_sample_chunks_one(c, chunks);
+    if (!c) return fail(nullptr, "pt_set_sample_chunks: null context");
+    return on_every_rank(c, [&](pt_ctx* r, int) {
+        if (chunks != 0 && chunks != 1 && chunks != 2 && chunks != 4 && chunks != 8 && chunks != 16 && chunks != 32) return fail(r, "pt_set_sample_chunks: 0 (automatic), 1, 2, 4, 8, 16 or 32");
+        r->chunks = chunks;
+        return 0;
+    });
 }
 
 PT_API int pt_set_tuning(pt_ctx* c, int blocks_per_cu, int variant)
 {
-    if (c && c->multi) return on_every_rank(c, [&](pt_ctx* r, int) { return set_tuning_one(r, blocks_per_cu, variant); });
-    return set_tuning_one(c, blocks_per_cu, variant);
+    if (!c) return fail(nullptr, "pt_set_tuning: null context");
+    return on_every_rank(c, [&](pt_ctx* r, int) {
+        if (blocks_per_cu < 0 || blocks_per_cu > 16) return fail(r, "pt_set_tuning: blocks_per_cu out of range");
+        if (variant < -1 || variant >= ptd::render_variant_count()) return fail(r, "pt_set_tuning: unknown kernel variant");
+        CK(r, hipSetDevice(r->device));
+        r->tune_blocks_per_cu = blocks_per_cu;
+        r->variant_auto = variant < 0;
+        r->variant = variant < 0 ? pick_variant(r) : variant;
+        if (int rc = ensure_variant_arrays(r)) return rc;
+        CK(r, ptd::render_occupancy(r->variant, r->math_mode, r->stack_entries, r->bvh.n_nodes, &r->blocks_per_cu));
+        if (r->blocks_per_cu < 1) return fail(r, "pt_set_tuning: this kernel variant does not fit the current scene in LDS");
+        return 0;
+    });
 }
 
 PT_API int pt_set_build_mode(pt_ctx* c, int mode)
 {
-    if (c && c->multi) return on_every_rank(c, [&](pt_ctx* r, int) { return set_build_mode_one(r, mode); });
-    return set_build_mode_one(c, mode);
+    if (!c) return fail(nullptr, "pt_set_build_mode: null context");
+    return on_every_rank(c, [&](pt_ctx* r, int) {
+        if (mode != 0 && mode != 1 && mode != 2) return fail(r, "pt_set_build_mode: 0 = Karras LBVH, 1 = PLOC, 2 = PLOC + insertion-based optimisation");
+        r->build_mode = mode;
+        return 0;
+    });
 }
 
 PT_API const char* pt_variant_name(int variant)
@@ -910,12 +720,12 @@ PT_API int pt_set_stream(pt_ctx* c, void* s)
     return 0;
 }
 
-static ptd::DeviceScene device_scene(pt_ctx* c)
+ptd::DeviceScene device_scene(pt_ctx* c)
 {
     ptd::DeviceScene sc;
-    sc.nodes = c->bvh.nodes; sc.qnodes = c->bvh.qnodes; sc.cnodes = c->bvh.cnodes; sc.hnodes = c->bvh.hnodes; sc.top = c->bvh.top_nodes; sc.n_top = c->bvh.n_top; sc.hspace = c->bvh.hspace; sc.grid = c->bvh.grid; sc.tris = c->bvh.tris; sc.shade = c->bvh.shade; sc.wrecs = c->bvh.wrecs; sc.hcnodes = c->bvh.hcnodes_alt ? c->bvh.hcnodes_alt : c->bvh.hcnodes; sc.srecs = c->bvh.srecs; sc.sspace = c->bvh.sspace; sc.mats = c->d_mats;
+    sc.nodes = c->bvh.nodes; sc.qnodes = c->bvh.qnodes; sc.cnodes = c->bvh.cnodes; sc.hnodes = c->bvh.hnodes; sc.top = c->bvh.top_nodes; sc.n_top = c->bvh.n_top; sc.hspace = c->bvh.hspace; sc.grid = c->bvh.grid; sc.tris = c->bvh.tris; sc.shade = c->bvh.shade; sc.wrecs = c->bvh.wrecs; sc.hcnodes = c->bvh.hcnodes_alt ? c->bvh.hcnodes_alt : c->bvh.hcnodes; sc.srecs = c->bvh.srecs; sc.sspace = c->bvh.sspace; sc.mats = c->d_mats.p;
     sc.n_tris = c->bvh.n_tris; sc.n_mats = c->n_mats;
-    sc.lights = c->d_lights; sc.n_lights = c->n_lights; sc.light_area = c->light_area;
+    sc.lights = c->d_lights.p; sc.n_lights = c->n_lights; sc.light_area = c->light_area;
     return sc;
 }
 
@@ -958,7 +768,7 @@ static bool check_fast_div(const ptd::FastDiv& f, uint32_t d, uint32_t n_max)
 // books its samples as misses without starting them), and the columns inside which the square lies wholly inside it (path starts
 // there skip the cull test; a hint only: a ray that misses after all is traversed and misses).  false: the box is not entirely
 // in front of the eye, or the camera frame is degenerate — no classes for this launch.
-static bool row_spans(const pt_params* p, const float lo[3], const float hi[3], std::vector<uint32_t>& out)
+bool row_spans(const pt_params* p, const float lo[3], const float hi[3], std::vector<uint32_t>& out)
 {
     const uint32_t W = p->width, H = p->height;
     out.assign((size_t)2 * H, 0u);
@@ -1068,7 +878,7 @@ static int launch_frames_multi(pt_ctx* c, const pt_params* p, uint32_t n_frames)
     if (!p->accumulationBuffer) return fail(c, "pt_launch: accumulationBuffer is null");
     const size_t pixels = (size_t)p->width * p->height;
     if (pixels > 0x7FFFFFFFull / 4u) return fail(c, "pt_launch: image too large for the group reduce");
-    // private buffers: (re)allocated zero-filled; a launch that is not the straight continuation of the previous one with
+    // private buffers (d_group_accum): grown on demand, zero-filled; a launch that is not the straight continuation of the previous one with
     // frame > 0 (a restored accumulation) first takes the caller's values for the rank's own pixels
     // The tile layout depends on the image SHAPE, not on its pixel count (640x360 and 360x640 share one): keyed on (width, height).
     const bool fresh = m->accum_w != p->width || m->accum_h != p->height;
@@ -1079,19 +889,17 @@ static int launch_frames_multi(pt_ctx* c, const pt_params* p, uint32_t n_frames)
     }
     int rc = on_every_rank(c, [&](pt_ctx* r, int i) -> int {
         CK(r, hipSetDevice(r->device));
-        if (fresh) {
-            if (m->accum[(size_t)i]) { CK(r, hipStreamSynchronize(r->stream)); (void)hipFree(m->accum[(size_t)i]); m->accum[(size_t)i] = nullptr; }
-            CK(r, hipMalloc((void**)&m->accum[(size_t)i], pixels * sizeof(float4)));
-        }
+        CK(r, r->d_group_accum.reserve(pixels, r->stream));
+        float4* own = r->d_group_accum.p;
         // every launch that is not a straight continuation starts from "own pixels or zero": the reduce relies on every pixel
         // having exactly one non-zero term, whatever an earlier launch of another shape or frame sequence left behind
-        if (!continues) CK(r, hipMemsetAsync(m->accum[(size_t)i], 0, pixels * sizeof(float4), r->stream));
+        if (!continues) CK(r, hipMemsetAsync(own, 0, pixels * sizeof(float4), r->stream));
         if (p->currentFrameIdx > 0u && !continues) {
-            CK(r, hipMemcpyAsync(m->accum[(size_t)i], p->accumulationBuffer, pixels * sizeof(float4), hipMemcpyDefault, r->stream));
-            CK(r, ptd::launch_keep_owned(m->accum[(size_t)i], p->width, p->height, i, world, r->stream));
+            CK(r, hipMemcpyAsync(own, p->accumulationBuffer, pixels * sizeof(float4), hipMemcpyDefault, r->stream));
+            CK(r, ptd::launch_keep_owned(own, p->width, p->height, i, world, r->stream));
         }
         pt_params q = *p;
-        q.accumulationBuffer = (float*)m->accum[(size_t)i];
+        q.accumulationBuffer = (float*)own;
         q.frameBuffer = nullptr;
         r->rank = i; r->world = world;
         return launch_frames_single(r, &q, n_frames);
@@ -1102,7 +910,8 @@ static int launch_frames_multi(pt_ctx* c, const pt_params* p, uint32_t n_frames)
         Range range("acgpt: reduce of the accumulation buffers to rank 0");
         const auto tr = std::chrono::steady_clock::now();
         if (m->rehearsal) {         // every buffer lives on the one device: add them there
-            std::vector<const float4*> src(m->accum.begin(), m->accum.end());
+            std::vector<const float4*> src;
+            for (const pt_ctx* r : m->ranks) src.push_back(r->d_group_accum.p);
             CK(c, hipSetDevice(c->device));
             CK(c, ptd::launch_sum_ranks((float4*)p->accumulationBuffer, src.data(), world, (uint32_t)pixels, c->stream));
             CK(c, hipStreamSynchronize(c->stream));
@@ -1113,8 +922,8 @@ static int launch_frames_multi(pt_ctx* c, const pt_params* p, uint32_t n_frames)
             for (int i = 0; i < world && r == ncclSuccess && dev_err == hipSuccess; i++) {
                 dev_err = hipSetDevice(m->ranks[(size_t)i]->device);
                 if (dev_err != hipSuccess) break;
-                r = m->rccl.Reduce(m->accum[(size_t)i], i == 0 ? (void*)p->accumulationBuffer : (void*)m->accum[(size_t)i], pixels * 4u, ncclFloat, ncclSum, 0,
-                                   m->comms[(size_t)i], m->ranks[(size_t)i]->stream);
+                float4* own = m->ranks[(size_t)i]->d_group_accum.p;
+                r = m->rccl.Reduce(own, i == 0 ? (void*)p->accumulationBuffer : (void*)own, pixels * 4u, ncclFloat, ncclSum, 0, m->comms[(size_t)i], m->ranks[(size_t)i]->stream);
             }
             const ncclResult_t e = m->rccl.GroupEnd();
             if (r == ncclSuccess) r = e;
@@ -1264,14 +1073,8 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
     a.row_interleave = (uint32_t)c->queue_order;
     a.strip_rows = p->height / 4u + (p->height % 4u == 0 ? 0u : 1u);
     {   // one float4 per (pixel slot of this rank's tile order, sub-frame): what the megakernel hands to k_finalize
-        const size_t need = (size_t)num_samples(c->world, p->width, p->height) * n_frames * sizeof(float4);
-        if (need > c->frame_sums_bytes) {
-            CK(c, hipStreamSynchronize(c->stream));
-            if (c->d_frame_sums) { (void)hipFree(c->d_frame_sums); c->d_frame_sums = nullptr; c->frame_sums_bytes = 0; }
-            CK(c, hipMalloc((void**)&c->d_frame_sums, need));
-            c->frame_sums_bytes = need;
-        }
-        a.frame_sums = c->d_frame_sums;
+        CK(c, c->d_frame_sums.reserve((size_t)num_samples(c->world, p->width, p->height) * n_frames, c->stream));
+        a.frame_sums = c->d_frame_sums.p;
     }
     {   // scene box for the camera-ray cull, enlarged by 2^-10 of its extent (+ a floor) beyond the roundings of reaches_scene()
         float ext = 0.0f;
@@ -1297,26 +1100,21 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
             const bool ok = row_spans(p, c->bvh.scene_lo, c->bvh.scene_hi, spans);
             key.back() = ok ? 1.0f : 0.0f;
             if (ok) {
-                if (c->row_spans_rows < p->height) {
-                    CK(c, hipStreamSynchronize(c->stream));
-                    if (c->d_row_spans) { (void)hipFree(c->d_row_spans); c->d_row_spans = nullptr; c->row_spans_rows = 0; }
-                    CK(c, hipMalloc((void**)&c->d_row_spans, (size_t)p->height * sizeof(uint2)));
-                    c->row_spans_rows = p->height;
-                }
+                CK(c, c->d_row_spans.reserve(p->height, c->stream));
                 CK(c, hipStreamSynchronize(c->stream));       // a launch in flight may still read the old spans (launches return synchronised, so this is a formality)
-                CK(c, hipMemcpy(c->d_row_spans, spans.data(), (size_t)p->height * sizeof(uint2), hipMemcpyHostToDevice));
+                CK(c, hipMemcpy(c->d_row_spans.p, spans.data(), (size_t)p->height * sizeof(uint2), hipMemcpyHostToDevice));
             }
             c->spans_key = key;
         }
-        if (c->spans_key.back() == 1.0f) a.row_spans = c->d_row_spans;
+        if (c->spans_key.back() == 1.0f) a.row_spans = c->d_row_spans.p;
     }
     ptd::EnvArgs ea;
     ea.map = ptd::env_view(c->env);
     ea.p = c->env.pdf_scale > 0.0f ? (c->n_lights != 0u ? 0.5f : 1.0f) : 0.0f;
     ptd::GgxArgs ga;
-    ga.alpha = c->d_alpha;
-    a.queue_heads = c->d_queue;
-    a.counters = c->d_counters;
+    ga.alpha = c->d_alpha.p;
+    a.queue_heads = c->d_queue.p;
+    a.counters = c->d_counters.p;
     a.stack_entries = c->stack_entries;
     a.n_lds_nodes = c->bvh.n_nodes;
 
@@ -1346,39 +1144,28 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
     }
 
     if (a.chunk_shift) {   // fold slots for every wave of the grid
-        const size_t need = (size_t)grid * wpb * ((size_t)ptd::kRenderFoldSlots << a.chunk_shift) * 3 * sizeof(float);
-        if (need > c->wave_scratch_bytes) {
-            CK(c, hipStreamSynchronize(c->stream));
-            if (c->d_wave_scratch) { (void)hipFree(c->d_wave_scratch); c->d_wave_scratch = nullptr; c->wave_scratch_bytes = 0; }
-            CK(c, hipMalloc((void**)&c->d_wave_scratch, need));
-            c->wave_scratch_bytes = need;
-        }
-        a.wave_scratch = c->d_wave_scratch;
+        CK(c, c->d_wave_scratch.reserve((size_t)grid * wpb * ((size_t)ptd::kRenderFoldSlots << a.chunk_shift) * 3, c->stream));
+        a.wave_scratch = c->d_wave_scratch.p;
     }
     {   // kernels whose LDS stack is capped keep deeper entries here
         const int cap_signed = ptd::render_variant_stack_cap(variant);      // > 0: entries in LDS, the rest here; < 0: a sliding window of that many, every slot has a home here
         const uint32_t cap = (uint32_t)(cap_signed < 0 ? -cap_signed : cap_signed);
         if (cap > 0u && c->stack_entries > cap) {
-            const size_t need = (size_t)grid * wpb * 64u * (cap_signed < 0 ? c->stack_entries : c->stack_entries - cap) * sizeof(uint32_t)
+            const size_t need = (size_t)grid * wpb * 64u * (cap_signed < 0 ? c->stack_entries : c->stack_entries - cap)
                                 * ((ptd::render_variant_node_format(variant) == 10 || ptd::render_variant_node_format(variant) == 12) ? 2u : 1u);       // the shared-plane kernel's entries are {node, interval}
-            if (need > c->stack_ovf_bytes) {
-                CK(c, hipStreamSynchronize(c->stream));
-                if (c->d_stack_ovf) { (void)hipFree(c->d_stack_ovf); c->d_stack_ovf = nullptr; c->stack_ovf_bytes = 0; }
-                CK(c, hipMalloc((void**)&c->d_stack_ovf, need));
-                c->stack_ovf_bytes = need;
-            }
-            a.stack_overflow = c->d_stack_ovf;
+            CK(c, c->d_stack_ovf.reserve(need, c->stream));
+            a.stack_overflow = c->d_stack_ovf.p;
         }
     }
-    CK(c, hipMemsetAsync(c->d_queue, 0, 8 * sizeof(uint32_t), c->stream));
-    CK(c, hipMemsetAsync(c->d_counters, 0, (size_t)ptd::kCounterWords * sizeof(unsigned long long), c->stream));
+    CK(c, hipMemsetAsync(c->d_queue.p, 0, 8 * sizeof(uint32_t), c->stream));
+    CK(c, hipMemsetAsync(c->d_counters.p, 0, (size_t)ptd::kCounterWords * sizeof(unsigned long long), c->stream));
     CK(c, hipEventRecord(c->ev0, c->stream));
     { Range range("acgpt: render megakernel (launch_batch)"); CK(c, ptd::launch_render(variant, c->math_mode, a, grid, c->stream, &ea, &ga)); }
     CK(c, hipEventRecord(c->ev1, c->stream));
     { Range range("acgpt: k_finalize"); CK(c, ptd::launch_finalize(a, c->stream)); }
     unsigned long long h[8], h_tail[2] = {0, 0};      // h_tail: culled camera rays; experiments build: workgroups of a wavefront kernel that gave up
-    CK(c, hipMemcpyAsync(h, c->d_counters, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    CK(c, hipMemcpyAsync(h_tail, c->d_counters + ptd::kCulledCounter, sizeof(h_tail), hipMemcpyDeviceToHost, c->stream));
+    CK(c, hipMemcpyAsync(h, c->d_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    CK(c, hipMemcpyAsync(h_tail, c->d_counters.p + ptd::kCulledCounter, sizeof(h_tail), hipMemcpyDeviceToHost, c->stream));
     CK(c, hipStreamSynchronize(c->stream));            // CUDA_SYNC_CHECK, PathTracerMain.cpp:209
     const unsigned long long h_culled = h_tail[0];
 #ifdef ACGPT_EXPERIMENTS
@@ -1421,27 +1208,6 @@ PT_API int pt_get_stats(pt_ctx* c, pt_stats* out)
     return 0;
 }
 
-// The round trip of the ray queries and the debug entry points: upload in_bytes, launch(d_in, d_a, d_b) on the context's stream,
-// download the one or two outputs (bytes_b == 0: no second one, d_b is null).  fn: the entry point's name.
-template <typename F>
-static int device_round_trip(pt_ctx* c, const char* fn, const void* in, size_t in_bytes, void* out_a, size_t bytes_a, void* out_b, size_t bytes_b, F launch)
-{
-    void* d_in = nullptr; void* d_a = nullptr; void* d_b = nullptr;
-    hipError_t e = hipMalloc(&d_in, in_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_a, bytes_a);
-    if (e == hipSuccess && bytes_b) e = hipMalloc(&d_b, bytes_b);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch(d_in, d_a, d_b);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_a, d_a, bytes_a, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && bytes_b) e = hipMemcpyAsync(out_b, d_b, bytes_b, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (d_in) (void)hipFree(d_in);
-    if (d_a) (void)hipFree(d_a);
-    if (d_b) (void)hipFree(d_b);
-    if (e != hipSuccess) return fail(c, std::string(fn) + ": " + hipGetErrorString(e));
-    return 0;
-}
-
 template <typename F>
 static int trace_common(pt_ctx* c, const float* rays, size_t n, size_t out_bytes_a, void* out_a, size_t out_bytes_b, void* out_b, F launch)
 {
@@ -1475,470 +1241,6 @@ PT_API int pt_trace_any(pt_ctx* c, const float* rays, size_t n, uint8_t* hit_out
     return trace_common(c, rays, n, n, hit_out, 0, nullptr, [&](void* d_rays, void* a, void*) {
         return ptd::launch_trace_any(sc, se, (const float*)d_rays, (uint32_t)n, (uint8_t*)a, s);
     });
-}
-
-// ---- denoised preview (pt_render_features, pt_denoise; kernels in denoise.hip) -------------------------------------------------
-static bool spans_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + b_bytes && y < x + a_bytes;
-}
-
-static int check_image(pt_ctx* c, const pt_params* p, const char* what)
-{
-    if (p->width == 0 || p->height == 0) return fail(c, std::string(what) + ": width and height must be >= 1");
-    if (p->width > 65535u || p->height > 65535u || (uint64_t)p->width * p->height > (1ull << 28))
-        return fail(c, std::string(what) + ": image too large (65535 per side, 2^28 pixels)");
-    return 0;
-}
-
-PT_API int pt_render_features(pt_ctx* c, const pt_params* p, float* albedo_prim, float* normal_depth)
-{
-    if (!c) return fail(nullptr, "pt_render_features: null context");
-    if (!p || !albedo_prim || !normal_depth) return fail(c, "pt_render_features: null argument");
-    if (int rc = check_image(c, p, "pt_render_features")) return rc;
-    const size_t bytes = (size_t)p->width * p->height * sizeof(float4);
-    if (spans_overlap(albedo_prim, bytes, normal_depth, bytes)) return fail(c, "pt_render_features: the two output buffers overlap");
-    if (c->scene_serial == 0) return fail(c, "pt_render_features: no scene (pt_set_scene first)");
-    CK(c, hipSetDevice(c->device));
-    // the node array the scene holds: fp16 centre / half-extent nodes for the default variants, fp32 nodes for the fp32 ones; only a
-    // variant forced onto another format (pt_set_tuning) leaves neither, and gets the fp32 nodes back as a ray query would
-    int fmt = 0;
-    if (c->bvh.hcnodes) fmt = 11;
-    else if (int rc = ensure_node_format(c, 0)) return rc;
-    Range range("pt_render_features");
-    CK(c, ptd::launch_features(fmt, device_scene(c), c->stack_entries, p->width, p->height, p->cameraEye, p->cameraU, p->cameraV, p->cameraW,
-                               (float4*)albedo_prim, (float4*)normal_depth, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-PT_API int pt_denoise(pt_ctx* c, const pt_params* p, const float* albedo_prim, const float* normal_depth, float* out_rgba, uint32_t iterations)
-{
-    if (!c) return fail(nullptr, "pt_denoise: null context");
-    if (!p || !p->accumulationBuffer || !albedo_prim || !normal_depth || !out_rgba) return fail(c, "pt_denoise: null argument");
-    if (iterations < 1u || iterations > ptd::kDnMaxIterations) return fail(c, "pt_denoise: iterations must be in [1, 8]");
-    if (int rc = check_image(c, p, "pt_denoise")) return rc;
-    const size_t n = (size_t)p->width * p->height, bytes = n * sizeof(float4);
-    if (spans_overlap(out_rgba, bytes, p->accumulationBuffer, bytes) || spans_overlap(out_rgba, bytes, albedo_prim, bytes) ||
-        spans_overlap(out_rgba, bytes, normal_depth, bytes))
-        return fail(c, "pt_denoise: out_rgba overlaps an input (writing into the accumulation buffer would corrupt the progressive state)");
-    CK(c, hipSetDevice(c->device));
-    if (n > c->denoise_pixels) {
-        CK(c, hipStreamSynchronize(c->stream));
-        for (float4*& b : c->d_denoise) if (b) { (void)hipFree(b); b = nullptr; }
-        c->denoise_pixels = 0;
-        for (float4*& b : c->d_denoise) CK(c, hipMalloc((void**)&b, bytes));
-        c->denoise_pixels = n;
-    }
-    Range range("pt_denoise");
-    CK(c, ptd::launch_denoise((const float4*)p->accumulationBuffer, (const float4*)albedo_prim, (const float4*)normal_depth, p->width, p->height, iterations,
-                              c->d_denoise[0], c->d_denoise[1], (float4*)out_rgba, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// ---- the metered stages (display, convergence, firefly, bloom) -----------------------------------------------------------------------
-// Each keeps a small state on the device: live counts, which the stage's last kernel clears after it has read them, and the record
-// that kernel writes.  run_metered allocates the state on first use, zeroes it when it is new or dirty (an earlier call failed half
-// way), runs launch(state), copies the record to `info` if there is one, and synchronises.  fn: the entry point's name.
-template <typename State, typename Info, typename F>
-static int run_metered(pt_ctx* c, const char* fn, State*& d_state, bool& dirty, Info* info, F launch)
-{
-    hipError_t e = hipSuccess;
-    if (!d_state) { e = hipMalloc((void**)&d_state, sizeof(State)); dirty = true; }
-    if (e == hipSuccess && dirty) e = hipMemsetAsync(d_state, 0, sizeof(State), c->stream);
-    Range range(fn);
-    dirty = true;                            // until the stage's last kernel has run to its end and cleared the counts
-    if (e == hipSuccess) e = launch(d_state);
-    if (e == hipSuccess && info) e = hipMemcpyAsync(info, &d_state->record, sizeof(Info), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, std::string(fn) + ": " + hipGetErrorString(e));
-    dirty = false;
-    return 0;
-}
-
-// ---- display transform (pt_display_transform; kernels in display.hip) ----------------------------------------------------------
-static_assert(sizeof(pt_display_params) == 40 && sizeof(pt_display_info) == 16 + 4 * PT_DISPLAY_BINS, "pt_display_params / pt_display_info: a change of these layouts bumps pt_abi_version");
-
-PT_API int pt_display_transform(pt_ctx* c, const float* src_rgba, size_t n_pixels, const pt_display_params* dp, float* out_rgba, uint8_t* framebuffer_rgba,
-                                pt_display_info* info)
-{
-    const char* f = "pt_display_transform: ";
-    if (!c) return fail(nullptr, std::string(f) + "null context");
-    if (!src_rgba || !dp) return fail(c, std::string(f) + "null argument");
-    if (!out_rgba && !framebuffer_rgba) return fail(c, std::string(f) + "out_rgba and framebuffer_rgba are both null");
-    if (n_pixels < 1u || n_pixels > ((size_t)1 << 31)) return fail(c, std::string(f) + "n_pixels must be in [1, 2^31]");
-    if (dp->tone_curve != PT_TONE_LINEAR && dp->tone_curve != PT_TONE_REINHARD && dp->tone_curve != PT_TONE_ACES) return fail(c, std::string(f) + "unknown tone curve");
-    if (!std::isfinite(dp->exposure) || dp->exposure < 0.0f) return fail(c, std::string(f) + "exposure must be finite and >= 0 (0: automatic)");
-    const bool automatic = !(dp->exposure > 0.0f);
-    if (automatic) {
-        if (!std::isfinite(dp->key) || !(dp->key > 0.0f)) return fail(c, std::string(f) + "key must be finite and > 0");
-        if (dp->lo_permille >= dp->hi_permille || dp->hi_permille > 1000u) return fail(c, std::string(f) + "the metering window needs lo_permille < hi_permille <= 1000");
-        if (!std::isfinite(dp->min_exposure) || !std::isfinite(dp->max_exposure) || !(dp->min_exposure > 0.0f) || !(dp->min_exposure <= dp->max_exposure))
-            return fail(c, std::string(f) + "the exposure limits need 0 < min_exposure <= max_exposure, both finite");
-        if (!std::isfinite(dp->prev_exposure) || dp->prev_exposure < 0.0f) return fail(c, std::string(f) + "prev_exposure must be finite and >= 0 (0: none)");
-        if (!(dp->adapt >= 0.0f && dp->adapt <= 1.0f)) return fail(c, std::string(f) + "adapt must be in [0, 1]");
-    }
-    if (dp->tone_curve == PT_TONE_REINHARD && (!std::isfinite(dp->white) || !(dp->white > 0.0f))) return fail(c, std::string(f) + "white must be finite and > 0");
-    if (out_rgba && spans_overlap(out_rgba, n_pixels * sizeof(float4), src_rgba, n_pixels * sizeof(float4))) return fail(c, std::string(f) + "out_rgba overlaps src_rgba");
-    CK(c, hipSetDevice(c->device));
-    const auto launch = [&](ptd::DisplayState* st) {
-        return ptd::launch_display((const float4*)src_rgba, (uint64_t)n_pixels, *dp, st, (float4*)out_rgba, (uint32_t*)framebuffer_rgba, c->stream);
-    };
-    if (automatic) return run_metered(c, "pt_display_transform", c->d_display, c->display_dirty, info, launch);
-    // a manual exposure: the apply kernel alone, the state neither read nor written
-    Range range("pt_display_transform");
-    CK(c, launch(c->d_display));
-    if (info) { memset(info, 0, sizeof(*info)); info->exposure = dp->exposure; }
-    CK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// ---- convergence estimate (pt_convergence_update; kernels in convergence.hip) --------------------------------------------------
-static_assert(sizeof(pt_convergence_params) == 16 && sizeof(pt_convergence_info) == 32 + 4 * PT_CONVERGENCE_BINS,
-              "pt_convergence_params / pt_convergence_info: a change of these layouts bumps pt_abi_version");
-
-PT_API int pt_convergence_update(pt_ctx* c, const pt_params* p, uint32_t accum_frames, const pt_convergence_params* cp, float* state, float* out_error,
-                                 float* out_tiles, pt_convergence_info* info)
-{
-    const std::string f("pt_convergence_update: ");
-    if (!c) return fail(nullptr, f + "null context");
-    if (!p || !cp || !state || !p->accumulationBuffer) return fail(c, f + "null argument");
-    if (p->width == 0 || p->height == 0) return fail(c, f + "width and height must be >= 1");
-    const uint64_t n = (uint64_t)p->width * p->height;
-    if (n > (1ull << 31)) return fail(c, f + "image too large (2^31 pixels)");
-    if (accum_frames < 1u || accum_frames > (1u << 24)) return fail(c, f + "accum_frames must be in [1, 2^24]");
-    if (!std::isfinite(cp->lum_floor) || !(cp->lum_floor > 0.0f)) return fail(c, f + "lum_floor must be finite and > 0");
-    if (!std::isfinite(cp->threshold) || !(cp->threshold > 0.0f)) return fail(c, f + "threshold must be finite and > 0");
-    if (cp->quantile_permille < 1u || cp->quantile_permille > 1000u) return fail(c, f + "quantile_permille must be in [1, 1000]");
-    if (cp->reserved != 0u) return fail(c, f + "reserved must be 0");
-    const uint64_t tiles = ptd::tile_walk(p->width, p->height, ptd::kConvTile, ptd::kConvBlocks).tiles;
-    const void* bufs[4] = {p->accumulationBuffer, state, out_error, out_tiles};
-    const size_t sizes[4] = {(size_t)n * sizeof(float4), (size_t)n * sizeof(float4), (size_t)n * sizeof(float), (size_t)tiles * sizeof(float)};
-    const char* names[4] = {"the accumulation buffer", "state", "out_error", "out_tiles"};
-    for (int i = 0; i < 4; i++)
-        for (int j = i + 1; j < 4; j++)
-            if (bufs[i] && bufs[j] && spans_overlap(bufs[i], sizes[i], bufs[j], sizes[j])) return fail(c, f + names[j] + " overlaps " + names[i]);
-    CK(c, hipSetDevice(c->device));
-    return run_metered(c, "pt_convergence_update", c->d_convergence, c->convergence_dirty, info, [&](ptd::ConvergenceState* st) {
-        return ptd::launch_convergence((const float4*)p->accumulationBuffer, p->width, p->height, accum_frames, *cp, (float4*)state, out_error, out_tiles,
-                                       st, c->stream);
-    });
-}
-
-// ---- firefly filter (pt_firefly_filter; kernels in firefly.hip) -----------------------------------------------------------------
-static_assert(sizeof(pt_firefly_params) == 16 && sizeof(pt_firefly_info) == 40, "pt_firefly_params / pt_firefly_info: a change of these layouts bumps pt_abi_version");
-
-PT_API int pt_firefly_filter(pt_ctx* c, const float* src_rgba, uint32_t width, uint32_t height, const pt_firefly_params* fp, float* out_rgba, pt_firefly_info* info)
-{
-    const std::string f("pt_firefly_filter: ");
-    if (!c) return fail(nullptr, f + "null context");
-    if (!src_rgba || !fp || !out_rgba) return fail(c, f + "null argument");
-    if (width == 0 || height == 0) return fail(c, f + "width and height must be >= 1");
-    const uint64_t n = (uint64_t)width * height;
-    if (n > (1ull << 31)) return fail(c, f + "image too large (2^31 pixels)");
-    if (!std::isfinite(fp->ratio) || !(fp->ratio >= 1.0f)) return fail(c, f + "ratio must be finite and >= 1");
-    if (!std::isfinite(fp->floor) || !(fp->floor > 0.0f)) return fail(c, f + "floor must be finite and > 0");
-    if (fp->rank < 1u || fp->rank > 4u) return fail(c, f + "rank must be in [1, 4]");
-    if (fp->radius < 1u || fp->radius > 2u) return fail(c, f + "radius must be 1 or 2");
-    if (spans_overlap(src_rgba, (size_t)n * sizeof(float4), out_rgba, (size_t)n * sizeof(float4))) return fail(c, f + "out_rgba overlaps src_rgba");
-    CK(c, hipSetDevice(c->device));
-    return run_metered(c, "pt_firefly_filter", c->d_firefly, c->firefly_dirty, info, [&](ptd::FireflyState* st) {
-        return ptd::launch_firefly((const float4*)src_rgba, width, height, *fp, (float4*)out_rgba, st, c->stream);
-    });
-}
-
-// ---- bloom (pt_bloom; kernels in bloom.hip) -------------------------------------------------------------------------------------
-static_assert(sizeof(pt_bloom_params) == 24 && sizeof(pt_bloom_info) == 40, "pt_bloom_params / pt_bloom_info: a change of these layouts bumps pt_abi_version");
-
-PT_API int pt_bloom(pt_ctx* c, const float* src_rgba, uint32_t width, uint32_t height, const pt_bloom_params* bp, float* out_rgba, pt_bloom_info* info)
-{
-    const std::string f("pt_bloom: ");
-    if (!c) return fail(nullptr, f + "null context");
-    if (!src_rgba || !bp || !out_rgba) return fail(c, f + "null argument");
-    if (width == 0 || height == 0) return fail(c, f + "width and height must be >= 1");
-    const uint64_t n = (uint64_t)width * height;
-    if (n > (1ull << 31)) return fail(c, f + "image too large (2^31 pixels)");
-    if (!std::isfinite(bp->threshold) || bp->threshold < 0.0f) return fail(c, f + "threshold must be finite and >= 0");
-    if (!std::isfinite(bp->knee) || bp->knee < 0.0f || bp->knee > bp->threshold) return fail(c, f + "knee must be finite and in [0, threshold]");
-    if (!std::isfinite(bp->clamp) || bp->clamp < 0.0f) return fail(c, f + "clamp must be finite and >= 0 (0: no limit)");
-    if (!std::isfinite(bp->intensity) || bp->intensity < 0.0f) return fail(c, f + "intensity must be finite and >= 0");
-    if (!std::isfinite(bp->spread) || bp->spread < 0.0f || bp->spread > 4.0f) return fail(c, f + "spread must be finite and in [0, 4]");
-    if (bp->levels < 1u || bp->levels > ptd::kBloomMaxLevels) return fail(c, f + "levels must be in [1, 8]");
-    if (spans_overlap(src_rgba, (size_t)n * sizeof(float4), out_rgba, (size_t)n * sizeof(float4))) return fail(c, f + "out_rgba overlaps src_rgba");
-    CK(c, hipSetDevice(c->device));
-    const ptd::BloomLevels lv = ptd::bloom_levels(width, height, bp->levels);
-    const uint64_t texels = lv.off[lv.n + 1u];
-    if (texels > c->bloom_texels) {
-        CK(c, hipStreamSynchronize(c->stream));
-        if (c->d_bloom_pyramid) { (void)hipFree(c->d_bloom_pyramid); c->d_bloom_pyramid = nullptr; }
-        c->bloom_texels = 0;
-        CK(c, hipMalloc((void**)&c->d_bloom_pyramid, (size_t)texels * sizeof(float4)));
-        c->bloom_texels = texels;
-    }
-    return run_metered(c, "pt_bloom", c->d_bloom, c->bloom_dirty, info, [&](ptd::BloomState* st) {
-        return ptd::launch_bloom((const float4*)src_rgba, width, height, *bp, (float4*)out_rgba, c->d_bloom_pyramid, st, c->stream);
-    });
-}
-
-// ---- temporal reprojection (pt_temporal_blend; kernels in temporal.hip) --------------------------------------------------------
-// the per-triangle bsdfType array: on the first call after pt_set_scene, counted in device_bytes from then on, freed with the scene
-static int ensure_tri_bsdf(pt_ctx* c)
-{
-    if (c->d_tri_bsdf || c->bvh.n_tris == 0) return 0;
-    uint8_t* b = nullptr;
-    CK(c, hipMalloc((void**)&b, c->bvh.n_tris));
-    hipError_t e = ptd::launch_tri_bsdf(device_scene(c), b, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { (void)hipFree(b); return fail(c, std::string("pt_temporal_blend: per-triangle materials: ") + hipGetErrorString(e)); }
-    c->d_tri_bsdf = b;
-    return 0;
-}
-
-// pt_temporal_blend and pt_temporal_blend_motion: every refusal before any device work, in this order, named after the caller
-static int temporal_blend(pt_ctx* c, const char* fn, const pt_params* p, uint32_t accum_samples, const float* albedo_prim,
-                          const float* normal_depth, const pt_params* prev, const float* prev_history, const float* prev_albedo_prim,
-                          const float* prev_normal_depth, float history_cap, bool motion, const float* verts_xyzw, const float* prev_verts_xyzw,
-                          size_t n_verts, float clip_gamma, float* out_history)
-{
-    const std::string f(fn);
-    if (!c) return fail(nullptr, f + ": null context");
-    if (!p || !p->accumulationBuffer || !albedo_prim || !normal_depth || !out_history) return fail(c, f + ": null argument");
-    const int n_prev = (prev != nullptr) + (prev_history != nullptr) + (prev_albedo_prim != nullptr) + (prev_normal_depth != nullptr);
-    if (n_prev != 0 && n_prev != 4) return fail(c, f + ": prev, prev_history, prev_albedo_prim and prev_normal_depth are all given or all NULL");
-    if (accum_samples == 0u) return fail(c, f + ": accum_samples must be >= 1");
-    if (!(history_cap >= 0.0f) || !std::isfinite(history_cap)) return fail(c, f + ": history_cap must be finite and >= 0");
-    if (int rc = check_image(c, p, fn)) return rc;
-    if (prev) if (int rc = check_image(c, prev, (f + " (previous view)").c_str())) return rc;
-    const size_t bytes = (size_t)p->width * p->height * sizeof(float4);
-    const size_t prev_bytes = prev ? (size_t)prev->width * prev->height * sizeof(float4) : 0;
-    const void* inputs[6] = {p->accumulationBuffer, albedo_prim, normal_depth, prev_history, prev_albedo_prim, prev_normal_depth};
-    for (int i = 0; i < 6; i++)
-        if (inputs[i] && spans_overlap(out_history, bytes, inputs[i], i < 3 ? bytes : prev_bytes))
-            return fail(c, f + ": out_history overlaps an input (chained calls ping-pong two history buffers)");
-    if (c->scene_serial == 0) return fail(c, f + ": no scene (pt_set_scene first)");
-    if (motion) {
-        if ((verts_xyzw != nullptr) != (prev_verts_xyzw != nullptr)) return fail(c, f + ": verts_xyzw and prev_verts_xyzw are both given or both NULL");
-        if (!(clip_gamma >= 0.0f) || !std::isfinite(clip_gamma)) return fail(c, f + ": clip_gamma must be finite and >= 0");
-        if (n_verts != c->kept_n_verts)
-            return fail(c, f + ": " + std::to_string(n_verts) + " vertices, the scene has " + std::to_string(c->kept_n_verts));
-        const size_t vbytes = n_verts * sizeof(float4);
-        if (verts_xyzw && (spans_overlap(out_history, bytes, verts_xyzw, vbytes) || spans_overlap(out_history, bytes, prev_verts_xyzw, vbytes)))
-            return fail(c, f + ": out_history overlaps an input (a vertex array)");
-    }
-    CK(c, hipSetDevice(c->device));
-    if (int rc = ensure_tri_bsdf(c)) return rc;
-    ptd::TpMotion mo = {};
-    if (motion && verts_xyzw && c->bvh.n_tris > 0) {
-        if (int rc = ensure_dev_idx(c)) return rc;
-        mo.idx = c->d_idx; mo.verts = (const float4*)verts_xyzw; mo.prev_verts = (const float4*)prev_verts_xyzw;
-    }
-    mo.gamma = motion ? clip_gamma : 0.0f;
-    ptd::TpPrev tp = {};
-    if (prev) {
-        tp.eye = prev->cameraEye; tp.U = prev->cameraU; tp.V = prev->cameraV; tp.W = prev->cameraW;
-        tp.w = prev->width; tp.h = prev->height;
-        tp.hist = (const float4*)prev_history; tp.albedo_prim = (const float4*)prev_albedo_prim; tp.normal_depth = (const float4*)prev_normal_depth;
-    }
-    Range range(fn);
-    CK(c, ptd::launch_temporal((const float4*)p->accumulationBuffer, (const float4*)albedo_prim, (const float4*)normal_depth, p->width, p->height,
-                               p->cameraEye, p->cameraU, p->cameraV, p->cameraW, (float)accum_samples, tp, c->d_tri_bsdf, c->bvh.n_tris,
-                               history_cap, motion ? &mo : nullptr, (float4*)out_history, c->stream));
-    CK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-PT_API int pt_temporal_blend(pt_ctx* c, const pt_params* p, uint32_t accum_samples, const float* albedo_prim, const float* normal_depth,
-                             const pt_params* prev, const float* prev_history, const float* prev_albedo_prim, const float* prev_normal_depth,
-                             float history_cap, float* out_history)
-{
-    return temporal_blend(c, "pt_temporal_blend", p, accum_samples, albedo_prim, normal_depth, prev, prev_history, prev_albedo_prim,
-                          prev_normal_depth, history_cap, false, nullptr, nullptr, 0, 0.0f, out_history);
-}
-
-PT_API int pt_temporal_blend_motion(pt_ctx* c, const pt_params* p, uint32_t accum_samples, const float* albedo_prim, const float* normal_depth,
-                                    const pt_params* prev, const float* prev_history, const float* prev_albedo_prim,
-                                    const float* prev_normal_depth, const float* verts_xyzw, const float* prev_verts_xyzw, size_t n_verts,
-                                    float history_cap, float clip_gamma, float* out_history)
-{
-    return temporal_blend(c, "pt_temporal_blend_motion", p, accum_samples, albedo_prim, normal_depth, prev, prev_history, prev_albedo_prim,
-                          prev_normal_depth, history_cap, true, verts_xyzw, prev_verts_xyzw, n_verts, clip_gamma, out_history);
-}
-
-PT_API int pt_bench_traversal(pt_ctx* c, const float* rays, size_t n, int repeats, int node_format, float* t_out, uint32_t* prim_out, float* ms_out,
-                              uint64_t* counters_out)
-{
-    if (!c || !rays || !t_out || !prim_out || !ms_out || n == 0 || n > 0x7FFFFFFFull || repeats < 1 || node_format < 0 || node_format > 4)
-        return fail(c, "pt_bench_traversal: bad argument");
-    CK(c, hipSetDevice(c->device));
-    if (int rc = ensure_node_format(c, node_format == 1 ? 3 : node_format == 3 ? 9 : node_format == 4 ? 11 : 0)) return rc;       // stream formats 0 / 2: fp32 nodes, 3: fp16 {lo, hi}, 4: fp16 {centre, half extent}, 1: four-wide
-    const uint32_t entries = node_format == 1 ? (c->bvh.wide_depth + 1u) : c->stack_entries;
-    float* d_rays = nullptr; float* d_t = nullptr; uint32_t* d_p = nullptr; uint32_t* d_head = nullptr;
-    int bpc = 0;
-    hipError_t e = ptd::trace_stream_occupancy(node_format, entries, &bpc);
-    if (e == hipSuccess && bpc < 1) e = hipErrorInvalidValue;
-    if (e == hipSuccess) e = hipMalloc((void**)&d_rays, n * 32);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_t, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_p, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_head, 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rays, rays, n * 32, hipMemcpyHostToDevice, c->stream);
-    float best = 1e30f;
-    const ptd::DeviceScene sc = device_scene(c);
-    for (int r = 0; r < repeats && e == hipSuccess; r++) {
-        e = hipMemsetAsync(d_head, 0, 4, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(c->d_counters, 0, 8 * sizeof(unsigned long long), c->stream);
-        if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
-        if (e == hipSuccess) e = ptd::launch_trace_stream(node_format, sc, entries, d_rays, (uint32_t)n, d_head, d_t, d_p, c->d_counters, (uint32_t)(c->n_cus * bpc), c->stream);
-        if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        float ms = 0.0f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
-        if (ms < best) best = ms;
-    }
-    if (e == hipSuccess) e = hipMemcpy(t_out, d_t, n * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(prim_out, d_p, n * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && counters_out) e = hipMemcpy(counters_out, c->d_counters, 5 * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    if (d_rays) (void)hipFree(d_rays);
-    if (d_t) (void)hipFree(d_t);
-    if (d_p) (void)hipFree(d_p);
-    if (d_head) (void)hipFree(d_head);
-    if (e != hipSuccess) return fail(c, std::string("pt_bench_traversal: ") + hipGetErrorString(e));
-    *ms_out = best;
-    return 0;
-}
-
-// in / out sizes per element, in dwords (op 1: in = {seed, count}, out = 2 * count)
-PT_API int pt_selftest(pt_ctx* c, int op, const void* in, size_t n, void* out)
-{
-    //                            0  1  2   3   4   5   6   7   8  9 10 11 12 13 14 15 16 17 18  19  20 .. 29 unused           30 31 32 33 34 35 36 37 38  39  40  41
-    static const int in_dw[42] = {2, 2, 3, 10, 10, 10, 10, 10, 10, 7, 4, 1, 6, 4, 2, 2, 6, 7, 3, 17, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 2, 1, 6, 4, 2, 2, 6, 7, 3, 20, 17, 19},
-                     out_dw[42] = {1, 0, 1, 3, 3, 3, 3, 3, 3, 4, 2, 4, 3, 3, 3, 3, 3, 3, 1, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 4, 4, 3, 3, 3, 3, 3, 3, 1, 3, 3, 3};
-    if (!c || !in || !out || op < 0 || op > 41 || in_dw[op] == 0 || n == 0 || n > (1u << 24)) return fail(c, "pt_selftest: bad argument");
-    CK(c, hipSetDevice(c->device));
-    size_t in_bytes = n * (size_t)in_dw[op] * 4, out_bytes = n * (size_t)out_dw[op] * 4;
-    uint32_t launch_n = (uint32_t)n;
-    if (op == 1) {
-        const uint32_t count = ((const uint32_t*)in)[1];
-        if (n != 1 || count == 0 || count > (1u << 22)) return fail(c, "pt_selftest: op 1 takes one {seed, count} record");
-        in_bytes = 8; out_bytes = (size_t)count * 8; launch_n = 1;
-    }
-    return device_round_trip(c, "pt_selftest", in, in_bytes, out, out_bytes, nullptr, 0, [&](void* d_in, void* d_out, void*) {
-        return ptd::launch_selftest(op, (const uint32_t*)d_in, launch_n, (uint32_t*)d_out, c->stream);
-    });
-}
-
-PT_API int pt_debug_environment(pt_ctx* c, int op, const float* in, size_t n, float* out)
-{
-    static const int in_dw[3] = {3, 3, 2}, out_dw[3] = {4, 1, 4};
-    if (!c || op < 0 || op > 2 || (n != 0 && (!in || !out)) || n > (1u << 24)) return fail(c, "pt_debug_environment: bad argument");
-    if (n == 0) return 0;
-    CK(c, hipSetDevice(c->device));
-    const size_t in_bytes = n * (size_t)in_dw[op] * 4, out_bytes = n * (size_t)out_dw[op] * 4;
-    return device_round_trip(c, "pt_debug_environment", in, in_bytes, out, out_bytes, nullptr, 0, [&](void* d_in, void* d_out, void*) {
-        return ptd::env_debug(ptd::env_view(c->env), op, c->math_mode != 0 ? 1 : 0, (const float*)d_in, (uint32_t)n, (float*)d_out, c->stream);
-    });
-}
-
-PT_API int pt_debug_microfacet(pt_ctx* c, int op, const float* in, size_t n, float* out)
-{
-    static const int out_dw[2] = {8, 4};
-    if (!c || op < 0 || op > 1 || (n != 0 && (!in || !out)) || n > (1u << 24)) return fail(c, "pt_debug_microfacet: bad argument");
-    if (n == 0) return 0;
-    CK(c, hipSetDevice(c->device));
-    const size_t in_bytes = n * 9u * 4u, out_bytes = n * (size_t)out_dw[op] * 4u;
-    return device_round_trip(c, "pt_debug_microfacet", in, in_bytes, out, out_bytes, nullptr, 0, [&](void* d_in, void* d_out, void*) {
-        return ptd::microfacet_debug(op, c->math_mode != 0 ? 1 : 0, (const float*)d_in, (uint32_t)n, (float*)d_out, c->stream);
-    });
-}
-
-PT_API int pt_debug_wave_times(pt_ctx* c, uint64_t* out, size_t max_waves)
-{
-    if (!c || !out) return fail(c, "pt_debug_wave_times: null argument");
-    if (max_waves > ptd::kMaxTimedWaves) max_waves = ptd::kMaxTimedWaves;
-    CK(c, hipSetDevice(c->device));
-    CK(c, hipMemcpy(out, c->d_counters + 8, 3 * max_waves * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-PT_API int pt_debug_queue_progress(pt_ctx* c, uint64_t* out)
-{
-    if (!c || !out) return fail(c, "pt_debug_queue_progress: null argument");
-    CK(c, hipSetDevice(c->device));
-    CK(c, hipMemcpy(out, c->d_counters + 8 + 3 * (size_t)ptd::kMaxTimedWaves, 2056 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-PT_API int pt_debug_queue_order(pt_ctx* c, int mode)
-{
-    if (!c || mode < 0 || mode > 3) return fail(c, "pt_debug_queue_order: 0 = contiguous eighths of the tile order per shard; round robin over the shards in units of 1 = a tile-strip row (default), 2 = a tile; 3 = one queue in image order");
-    c->queue_order = mode;
-    if (c->multi) for (size_t i = 1; i < c->multi->ranks.size(); i++) c->multi->ranks[i]->queue_order = mode;
-    return 0;
-}
-
-// The host side of the pixel classes alone (no context, no GPU): out = 2 * params->height words, {outer lo | hi << 16, inner lo | hi << 16}
-// per image row.  Returns 0 when the spans could be computed, 1 when they could not (box not entirely in front of the eye, ...).
-PT_API int pt_debug_row_spans(const pt_params* p, const float* box_lo, const float* box_hi, uint32_t* out)
-{
-    if (!p || !box_lo || !box_hi || !out || p->width == 0 || p->height == 0 || p->width > 65535u || p->height > 32767u) return 2;
-    std::vector<uint32_t> spans;
-    const bool ok = row_spans(p, box_lo, box_hi, spans);
-    memcpy(out, spans.data(), spans.size() * sizeof(uint32_t));
-    return ok ? 0 : 1;
-}
-
-PT_API int pt_debug_pixel_classes(pt_ctx* c, int on)
-{
-    if (!c) return fail(c, "pt_debug_pixel_classes: null context");
-    c->pixel_classes = on ? 1 : 0;
-    if (c->multi) for (size_t i = 1; i < c->multi->ranks.size(); i++) c->multi->ranks[i]->pixel_classes = c->pixel_classes;
-    return 0;
-}
-
-PT_API int pt_debug_window_moves(pt_ctx* c, uint64_t* out)
-{
-    if (!c || !out) return fail(c, "pt_debug_window_moves: null argument");
-    CK(c, hipSetDevice(c->device));
-    CK(c, hipMemcpy(out, c->d_counters + ptd::kWindowMoves, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-#ifdef ACGPT_EXPERIMENTS
-// experiments build only: renumber the resident fp16 nodes (0: the build's order, 1: sibling pairs share a 64-byte line, 2: depth first)
-namespace ptd { bool reorder_records_dfs(LbvhResult& r, hipStream_t stream, std::string& err); }      // lbvh_experiments.inc
-PT_API int pt_debug_node_order(pt_ctx* c, int mode)
-{
-    if (!c || mode < 0 || mode > 3) return fail(c, "pt_debug_node_order: mode 0, 1, 2 or 3");
-    CK(c, hipSetDevice(c->device));
-    CK(c, hipStreamSynchronize(c->stream));
-    std::string err;
-    if (mode == 3) {        // the triangle records in depth-first leaf order (in place; the nodes stay as they are)
-        if (!ptd::reorder_records_dfs(c->bvh, c->stream, err)) return fail(c, "pt_debug_node_order: " + err);
-        return 0;
-    }
-    if (!ptd::reorder_hcnodes(c->bvh, mode, c->stream, err)) return fail(c, "pt_debug_node_order: " + err);
-    return 0;
-}
-
-// experiments build only: per-role times of the last launch of a wavefront kernel (render_wavefront.hip), 17 values (tools/wf_check.py)
-PT_API int pt_debug_wf(pt_ctx* c, uint64_t* out)
-{
-    if (!c || !out) return fail(c, "pt_debug_wf: null argument");
-    CK(c, hipSetDevice(c->device));
-    CK(c, hipMemcpy(out, c->d_counters + ptd::kWfDiag, 17 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return 0;
-}
-#endif
-
-PT_API int pt_read_morton(pt_ctx* c, uint32_t* codes_sorted, uint32_t* prims_sorted)
-{
-    if (!c || !codes_sorted || !prims_sorted) return fail(c, "pt_read_morton: null argument");
-    if (c->bvh.n_tris == 0) return 0;
-    CK(c, hipSetDevice(c->device));
-    std::string err;
-    if (!ptd::read_morton(c->bvh, c->stream, codes_sorted, prims_sorted, err)) return fail(c, "pt_read_morton: " + err);
-    return 0;
 }
 
 PT_API int pt_device_malloc(pt_ctx* c, void** out, size_t bytes)

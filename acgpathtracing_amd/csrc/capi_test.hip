@@ -1,0 +1,178 @@
+// capi_test.hip — the test hooks and diagnostics of include/acgpt_test.h (not part of the drop-in boundary).  Host code only.
+#include <cstring>
+
+#include "../../include/acgpt_test.h"
+#include "context.h"
+#include "selftest.h"
+
+PT_API int pt_bench_traversal(pt_ctx* c, const float* rays, size_t n, int repeats, int node_format, float* t_out, uint32_t* prim_out, float* ms_out,
+                              uint64_t* counters_out)
+{
+    if (!c || !rays || !t_out || !prim_out || !ms_out || n == 0 || n > 0x7FFFFFFFull || repeats < 1 || node_format < 0 || node_format > 4)
+        return fail(c, "pt_bench_traversal: bad argument");
+    CK(c, hipSetDevice(c->device));
+    if (int rc = ensure_node_format(c, node_format == 1 ? 3 : node_format == 3 ? 9 : node_format == 4 ? 11 : 0)) return rc;       // stream formats 0 / 2: fp32 nodes, 3: fp16 {lo, hi}, 4: fp16 {centre, half extent}, 1: four-wide
+    const uint32_t entries = node_format == 1 ? (c->bvh.wide_depth + 1u) : c->stack_entries;
+    DevBuf<float> d_rays, d_t;
+    DevBuf<uint32_t> d_p, d_head;
+    int bpc = 0;
+    hipError_t e = ptd::trace_stream_occupancy(node_format, entries, &bpc);
+    if (e == hipSuccess && bpc < 1) e = hipErrorInvalidValue;
+    if (e == hipSuccess) e = d_rays.reserve(n * 8, c->stream);
+    if (e == hipSuccess) e = d_t.reserve(n, c->stream);
+    if (e == hipSuccess) e = d_p.reserve(n, c->stream);
+    if (e == hipSuccess) e = d_head.reserve(1, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rays.p, rays, n * 32, hipMemcpyHostToDevice, c->stream);
+    float best = 1e30f;
+    const ptd::DeviceScene sc = device_scene(c);
+    for (int r = 0; r < repeats && e == hipSuccess; r++) {
+        e = hipMemsetAsync(d_head.p, 0, 4, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(c->d_counters.p, 0, 8 * sizeof(unsigned long long), c->stream);
+        if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
+        if (e == hipSuccess) e = ptd::launch_trace_stream(node_format, sc, entries, d_rays.p, (uint32_t)n, d_head.p, d_t.p, d_p.p, c->d_counters.p, (uint32_t)(c->n_cus * bpc), c->stream);
+        if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        float ms = 0.0f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        if (ms < best) best = ms;
+    }
+    if (e == hipSuccess) e = hipMemcpy(t_out, d_t.p, n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(prim_out, d_p.p, n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && counters_out) e = hipMemcpy(counters_out, c->d_counters.p, 5 * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(c, std::string("pt_bench_traversal: ") + hipGetErrorString(e));
+    *ms_out = best;
+    return 0;
+}
+
+// in / out sizes per element, in dwords (op 1: in = {seed, count}, out = 2 * count)
+PT_API int pt_selftest(pt_ctx* c, int op, const void* in, size_t n, void* out)
+{
+    //                            0  1  2   3   4   5   6   7   8  9 10 11 12 13 14 15 16 17 18  19  20 .. 29 unused           30 31 32 33 34 35 36 37 38  39  40  41
+    static const int in_dw[42] = {2, 2, 3, 10, 10, 10, 10, 10, 10, 7, 4, 1, 6, 4, 2, 2, 6, 7, 3, 17, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 2, 1, 6, 4, 2, 2, 6, 7, 3, 20, 17, 19},
+                     out_dw[42] = {1, 0, 1, 3, 3, 3, 3, 3, 3, 4, 2, 4, 3, 3, 3, 3, 3, 3, 1, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 4, 4, 3, 3, 3, 3, 3, 3, 1, 3, 3, 3};
+    if (!c || !in || !out || op < 0 || op > 41 || in_dw[op] == 0 || n == 0 || n > (1u << 24)) return fail(c, "pt_selftest: bad argument");
+    CK(c, hipSetDevice(c->device));
+    size_t in_bytes = n * (size_t)in_dw[op] * 4, out_bytes = n * (size_t)out_dw[op] * 4;
+    uint32_t launch_n = (uint32_t)n;
+    if (op == 1) {
+        const uint32_t count = ((const uint32_t*)in)[1];
+        if (n != 1 || count == 0 || count > (1u << 22)) return fail(c, "pt_selftest: op 1 takes one {seed, count} record");
+        in_bytes = 8; out_bytes = (size_t)count * 8; launch_n = 1;
+    }
+    return device_round_trip(c, "pt_selftest", in, in_bytes, out, out_bytes, nullptr, 0, [&](void* d_in, void* d_out, void*) {
+        return ptd::launch_selftest(op, (const uint32_t*)d_in, launch_n, (uint32_t*)d_out, c->stream);
+    });
+}
+
+PT_API int pt_debug_environment(pt_ctx* c, int op, const float* in, size_t n, float* out)
+{
+    static const int in_dw[3] = {3, 3, 2}, out_dw[3] = {4, 1, 4};
+    if (!c || op < 0 || op > 2 || (n != 0 && (!in || !out)) || n > (1u << 24)) return fail(c, "pt_debug_environment: bad argument");
+    if (n == 0) return 0;
+    CK(c, hipSetDevice(c->device));
+    const size_t in_bytes = n * (size_t)in_dw[op] * 4, out_bytes = n * (size_t)out_dw[op] * 4;
+    return device_round_trip(c, "pt_debug_environment", in, in_bytes, out, out_bytes, nullptr, 0, [&](void* d_in, void* d_out, void*) {
+        return ptd::env_debug(ptd::env_view(c->env), op, c->math_mode != 0 ? 1 : 0, (const float*)d_in, (uint32_t)n, (float*)d_out, c->stream);
+    });
+}
+
+PT_API int pt_debug_microfacet(pt_ctx* c, int op, const float* in, size_t n, float* out)
+{
+    static const int out_dw[2] = {8, 4};
+    if (!c || op < 0 || op > 1 || (n != 0 && (!in || !out)) || n > (1u << 24)) return fail(c, "pt_debug_microfacet: bad argument");
+    if (n == 0) return 0;
+    CK(c, hipSetDevice(c->device));
+    const size_t in_bytes = n * 9u * 4u, out_bytes = n * (size_t)out_dw[op] * 4u;
+    return device_round_trip(c, "pt_debug_microfacet", in, in_bytes, out, out_bytes, nullptr, 0, [&](void* d_in, void* d_out, void*) {
+        return ptd::microfacet_debug(op, c->math_mode != 0 ? 1 : 0, (const float*)d_in, (uint32_t)n, (float*)d_out, c->stream);
+    });
+}
+
+PT_API int pt_debug_wave_times(pt_ctx* c, uint64_t* out, size_t max_waves)
+{
+    if (!c || !out) return fail(c, "pt_debug_wave_times: null argument");
+    if (max_waves > ptd::kMaxTimedWaves) max_waves = ptd::kMaxTimedWaves;
+    CK(c, hipSetDevice(c->device));
+    CK(c, hipMemcpy(out, c->d_counters.p + 8, 3 * max_waves * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+PT_API int pt_debug_queue_progress(pt_ctx* c, uint64_t* out)
+{
+    if (!c || !out) return fail(c, "pt_debug_queue_progress: null argument");
+    CK(c, hipSetDevice(c->device));
+    CK(c, hipMemcpy(out, c->d_counters.p + 8 + 3 * (size_t)ptd::kMaxTimedWaves, 2056 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+PT_API int pt_debug_queue_order(pt_ctx* c, int mode)
+{
+    if (!c || mode < 0 || mode > 3) return fail(c, "pt_debug_queue_order: 0 = contiguous eighths of the tile order per shard; round robin over the shards in units of 1 = a tile-strip row (default), 2 = a tile; 3 = one queue in image order");
+    c->queue_order = mode;
+    if (c->multi) for (size_t i = 1; i < c->multi->ranks.size(); i++) c->multi->ranks[i]->queue_order = mode;
+    return 0;
+}
+
+// The host side of the pixel classes alone (no context, no GPU): out = 2 * params->height words, {outer lo | hi << 16, inner lo | hi << 16}
+// per image row.  Returns 0 when the spans could be computed, 1 when they could not (box not entirely in front of the eye, ...).
+PT_API int pt_debug_row_spans(const pt_params* p, const float* box_lo, const float* box_hi, uint32_t* out)
+{
+    if (!p || !box_lo || !box_hi || !out || p->width == 0 || p->height == 0 || p->width > 65535u || p->height > 32767u) return 2;
+    std::vector<uint32_t> spans;
+    const bool ok = row_spans(p, box_lo, box_hi, spans);
+    memcpy(out, spans.data(), spans.size() * sizeof(uint32_t));
+    return ok ? 0 : 1;
+}
+
+PT_API int pt_debug_pixel_classes(pt_ctx* c, int on)
+{
+    if (!c) return fail(c, "pt_debug_pixel_classes: null context");
+    c->pixel_classes = on ? 1 : 0;
+    if (c->multi) for (size_t i = 1; i < c->multi->ranks.size(); i++) c->multi->ranks[i]->pixel_classes = c->pixel_classes;
+    return 0;
+}
+
+PT_API int pt_debug_window_moves(pt_ctx* c, uint64_t* out)
+{
+    if (!c || !out) return fail(c, "pt_debug_window_moves: null argument");
+    CK(c, hipSetDevice(c->device));
+    CK(c, hipMemcpy(out, c->d_counters.p + ptd::kWindowMoves, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+#ifdef ACGPT_EXPERIMENTS
+// experiments build only: renumber the resident fp16 nodes (0: the build's order, 1: sibling pairs share a 64-byte line, 2: depth first)
+namespace ptd { bool reorder_records_dfs(LbvhResult& r, hipStream_t stream, std::string& err); }      // lbvh_experiments.inc
+PT_API int pt_debug_node_order(pt_ctx* c, int mode)
+{
+    if (!c || mode < 0 || mode > 3) return fail(c, "pt_debug_node_order: mode 0, 1, 2 or 3");
+    CK(c, hipSetDevice(c->device));
+    CK(c, hipStreamSynchronize(c->stream));
+    std::string err;
+    if (mode == 3) {        // the triangle records in depth-first leaf order (in place; the nodes stay as they are)
+        if (!ptd::reorder_records_dfs(c->bvh, c->stream, err)) return fail(c, "pt_debug_node_order: " + err);
+        return 0;
+    }
+    if (!ptd::reorder_hcnodes(c->bvh, mode, c->stream, err)) return fail(c, "pt_debug_node_order: " + err);
+    return 0;
+}
+
+// experiments build only: per-role times of the last launch of a wavefront kernel (render_wavefront.hip), 17 values (tools/wf_check.py)
+PT_API int pt_debug_wf(pt_ctx* c, uint64_t* out)
+{
+    if (!c || !out) return fail(c, "pt_debug_wf: null argument");
+    CK(c, hipSetDevice(c->device));
+    CK(c, hipMemcpy(out, c->d_counters.p + ptd::kWfDiag, 17 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+#endif
+
+PT_API int pt_read_morton(pt_ctx* c, uint32_t* codes_sorted, uint32_t* prims_sorted)
+{
+    if (!c || !codes_sorted || !prims_sorted) return fail(c, "pt_read_morton: null argument");
+    if (c->bvh.n_tris == 0) return 0;
+    CK(c, hipSetDevice(c->device));
+    std::string err;
+    if (!ptd::read_morton(c->bvh, c->stream, codes_sorted, prims_sorted, err)) return fail(c, "pt_read_morton: " + err);
+    return 0;
+}

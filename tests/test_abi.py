@@ -44,6 +44,31 @@ def test_exports_every_declared_symbol(lib):
     assert C.sizeof(_native.Stats) == 96 and C.sizeof(_native.BvhInfo) == 88
 
 
+def test_setters_refuse_a_null_context(lib):
+    """The nine setters that run on every rank of a group refuse a null context before the rank dispatch (which reads the context's
+    group) and say which entry point it was.  No GPU: nothing is created."""
+    texel = (C.c_float * 3)(1.0, 1.0, 1.0)
+    one = _native.Float3(1.0, 1.0, 1.0)
+    calls = [
+        ("pt_set_scene", lambda: lib.pt_set_scene(None, None, 0, None, 0, None, None, 0)),
+        ("pt_set_scratch_limit", lambda: lib.pt_set_scratch_limit(None, 1 << 30)),
+        ("pt_set_light_mode", lambda: lib.pt_set_light_mode(None, 1)),
+        ("pt_set_material_model", lambda: lib.pt_set_material_model(None, _native.MATERIALS_MICROFACET)),
+        ("pt_set_math_mode", lambda: lib.pt_set_math_mode(None, _native.MATH_IEEE)),
+        ("pt_set_sample_chunks", lambda: lib.pt_set_sample_chunks(None, 4)),
+        ("pt_set_tuning", lambda: lib.pt_set_tuning(None, 0, -1)),
+        ("pt_set_build_mode", lambda: lib.pt_set_build_mode(None, 1)),
+        ("pt_set_environment", lambda: lib.pt_set_environment(None, None, 0, 0, one)),                            # clearing the map
+        ("pt_set_environment", lambda: lib.pt_set_environment(None, C.cast(texel, C.c_void_p), 1, 1, one)),     # a 1 x 1 map
+    ]
+    assert len(set(name for name, _ in calls)) == 9
+    for name, call in calls:
+        assert lib.pt_set_partition(None, 0, 1) != 0 and lib.pt_last_error(None).startswith(b"pt_set_partition:")     # another text first
+        assert call() != 0, name
+        err = lib.pt_last_error(None).decode()
+        assert err.startswith(name + ":") and "null context" in err, (name, err)
+
+
 def test_pod_layouts_match_the_reference():
     assert C.sizeof(_native.PathTraceParams) == 168          # pathTracer.h:85-108 on LP64
     assert _native.PathTraceParams.accumulationBuffer.offset == 8
