@@ -141,7 +141,7 @@ ABI_SYMBOLS = [
     "pt_create", "pt_create_multi", "pt_device_count", "pt_destroy", "pt_last_error", "pt_set_scene", "pt_set_build_mode", "pt_scene_handle", "pt_get_bvh_info",
     "pt_launch", "pt_launch_frames", "pt_resolve_framebuffer", "pt_set_partition", "pt_set_sample_chunks", "pt_set_light_mode", "pt_set_math_mode", "pt_set_scratch_limit", "pt_set_tuning",
     "pt_variant_name", "pt_variant_kernel", "pt_kernel_source_hash", "pt_set_stream", "pt_get_stats",
-    "pt_trace_closest", "pt_trace_any", "pt_render_features", "pt_denoise", "pt_temporal_blend", "pt_temporal_blend_motion", "pt_update_vertices", "pt_update_materials", "pt_set_environment",
+    "pt_trace_closest", "pt_trace_any", "pt_query_closest", "pt_query_any", "pt_render_features", "pt_denoise", "pt_temporal_blend", "pt_temporal_blend_motion", "pt_update_vertices", "pt_update_materials", "pt_set_environment",
     "pt_set_material_model", "pt_display_transform", "pt_convergence_update", "pt_firefly_filter", "pt_bloom",
     "pt_device_malloc", "pt_device_free", "pt_device_memset", "pt_copy_to_host", "pt_copy_to_device",
     "pt_host_malloc_mapped", "pt_host_free_mapped", "pt_abi_version",
@@ -224,6 +224,8 @@ def hip():
     L.pt_get_stats.argtypes = [vp, C.POINTER(Stats)]; L.pt_get_stats.restype = C.c_int
     L.pt_trace_closest.argtypes = [vp, vp, sz, vp, vp]; L.pt_trace_closest.restype = C.c_int
     L.pt_trace_any.argtypes = [vp, vp, sz, vp]; L.pt_trace_any.restype = C.c_int
+    L.pt_query_closest.argtypes = [vp, vp, sz, vp]; L.pt_query_closest.restype = C.c_int
+    L.pt_query_any.argtypes = [vp, vp, sz, vp]; L.pt_query_any.restype = C.c_int
     L.pt_render_features.argtypes = [vp, C.POINTER(PathTraceParams), vp, vp]; L.pt_render_features.restype = C.c_int
     L.pt_denoise.argtypes = [vp, C.POINTER(PathTraceParams), vp, vp, vp, C.c_uint32]; L.pt_denoise.restype = C.c_int
     L.pt_temporal_blend.argtypes = [vp, C.POINTER(PathTraceParams), C.c_uint32, vp, vp, C.POINTER(PathTraceParams), vp, vp, vp, C.c_float, vp]

@@ -14,12 +14,6 @@
 #include "temporal.h"
 
 // ---- denoised preview (pt_render_features, pt_denoise; kernels in denoise.hip) -------------------------------------------------
-static bool spans_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + b_bytes && y < x + a_bytes;
-}
-
 static int check_image(pt_ctx* c, const pt_params* p, const char* what)
 {
     if (p->width == 0 || p->height == 0) return fail(c, std::string(what) + ": width and height must be >= 1");

@@ -1,6 +1,6 @@
 // context.h — what the host units of the C ABI share: the context, the group, error reporting, the owner of a device allocation.
 // Host only (no kernel, not under pt_kernel_source_hash).  capi.hip: render core; capi_image.hip: the stages on a finished image;
-// capi_test.hip: include/acgpt_test.h.
+// capi_query.hip: the device-resident ray queries; capi_test.hip: include/acgpt_test.h.
 #pragma once
 #include <hip/hip_runtime.h>
 // RCCL: types only — librccl is loaded with dlopen by pt_create_multi, a single-GPU caller never touches it, and a box without
@@ -165,6 +165,13 @@ int on_every_rank(pt_ctx* c, F f)
     for (size_t i = 0; i < n; i++)
         if (rc[i] != 0) return fail(c, "rank " + std::to_string(i) + " (device " + std::to_string(m->ranks[i]->device) + "): " + m->ranks[i]->err);
     return 0;
+}
+
+// do the byte spans [a, a + a_bytes) and [b, b + b_bytes) share a byte?
+inline bool spans_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + b_bytes && y < x + a_bytes;
 }
 
 // helpers of capi.hip that the other units need

@@ -8,59 +8,15 @@
 // the variance blur: bound by the L1 / L2, not by arithmetic.  No atomics anywhere: two calls give the same bits.
 #include "denoise.h"
 #include "image_common.h"
+#include "traverse_hc.h"
 
 namespace ptd {
 
 extern __shared__ uint32_t dn_lds[];
 
 // ---- features ---------------------------------------------------------------------------------------------------------------
-// Closest hit on the fp16 centre / half-extent nodes (NODE_FMT 11): the box test of the default render kernels, one ray per lane, the
-// LDS lane stack of traverse().  Boxes only prune; the triangle test, the interval (tmin, tmax) and the tie rule (equal t -> lowest
-// triangle index) are those of traverse<false>, so the hit triangle and t equal pt_trace_closest's bit for bit.
-__device__ __forceinline__ void traverse_hc(const DeviceScene& sc, const LaneStack& st, bool active, const f3& o, const f3& d, float tmin, float tmax,
-                                            HitRec& hit)
-{
-    hit.t = tmax; hit.slot = -1; hit.prim = 0xFFFFFFFFu;
-    f3 mul, add;
-    setup_ray_hc(o, d, sc.hspace, mul, add);
-    int sp = 0;
-    int node = (active && sc.n_tris != 0u) ? 0 : kSentinel;
-    while (node != kSentinel) {
-        if (node >= 0) {
-            // child references of inner nodes are byte offsets into hcnodes; a leaf is ~slot
-            const uint4* np = (const uint4*)((const char*)sc.hcnodes + (size_t)(uint32_t)node);
-            const uint4 qa = np[0], qb = np[1];
-            float n0, f0, n1, f1;
-            slab_hc(qa.x, qa.y, qa.z, mul, add, tmin, n0, f0);
-            slab_hc(qb.x, qb.y, qb.z, mul, add, tmin, n1, f1);
-            f0 = fminf(f0, hit.t * kTieWiden);
-            f1 = fminf(f1, hit.t * kTieWiden);
-            const bool h0 = n0 <= f0, h1 = n1 <= f1;
-            if (h0 && h1) {
-                const bool first0 = n0 <= n1;
-                st.push(sp, first0 ? (int)qb.w : (int)qa.w);
-                sp++;
-                node = first0 ? (int)qa.w : (int)qb.w;
-            } else if (h0) {
-                node = (int)qa.w;
-            } else if (h1) {
-                node = (int)qb.w;
-            } else {
-                if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
-            }
-        } else {
-            const int slot = ~node;
-            const TriRecord* tp = sc.tris + slot;
-            const float4 r0 = tp->r0, r1 = tp->r1, r2 = tp->r2;
-            float t;
-            const bool ok = tri_test(o, d, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x), tmin, tmax, t);
-            const uint32_t prim = __float_as_uint(r2.y);
-            if (ok && (t < hit.t || (t == hit.t && prim < hit.prim))) { hit.t = t; hit.slot = slot; hit.prim = prim; }
-            if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
-        }
-    }
-}
-
+// The closest-hit walk over the fp16 centre / half-extent nodes (NODE_FMT 11) is traverse_hc (traverse_hc.h): hit triangle and t equal
+// pt_trace_closest's bit for bit.
 template <int FMT>
 __global__ void __launch_bounds__(256)
 k_dn_features(const DeviceScene sc, uint32_t stack_entries, uint32_t w, uint32_t h, pt_float3 eye, pt_float3 U, pt_float3 V, pt_float3 W,

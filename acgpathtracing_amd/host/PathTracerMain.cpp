@@ -15,7 +15,12 @@
 //              [--env map.hdr|map.pfm [--env-scale s]] [--no-area-light] [--materials reference|microfacet]
 //              [--tonemap linear|reinhard|aces] [--exposure auto|<EV>] [--out-hdr file.pfm]
 //              [--until-error E [--until-permille P] [--error-floor F] [--error-out file.pfm]]
-//              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]]
+//              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
+// --pick x,y (repeatable): once the scene is set and before the first frame, what lies under pixel (x, y), row 0 at the bottom: the
+// closest hit of the camera ray through the pixel's centre (pt_query_closest; the ray of pt_render_features), one JSON line each:
+// {"pick": [x, y], "hit": true, "t": .., "prim": .., "material": "<newmtl name>", "position": [eye + t * dir], "normal": [..]}, on a
+// miss {"pick": [x, y], "hit": false}.  Floats are printed with nine digits: they read back as the same fp32 values.  A pixel
+// outside the image is refused with exit status 2.  The frames are the same with or without it.
 // --bloom (with --tonemap or --exposure): the image the display transform shows goes through pt_bloom first.  threshold is in display
 // units, multiples of exposed white, and is divided by the exposure (and so are the default knee, half the threshold, and the
 // clamp, none); an automatic exposure is metered on the image without its glare and then applied as a manual one.  --out-hdr gets
@@ -567,6 +572,47 @@ static bool applyMaterialEdit(const std::string& spec, const std::vector<std::st
     return true;
 }
 
+// --pick: the camera ray through the centre of each pixel (the direction of pixel_centre_dir, csrc/image_common.h, restated: the same
+// fp32 operations), traced by pt_query_closest in one call; one JSON line per pick
+static void pickPixels(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<int2>& picks)
+{
+    const pt_params& p = state.params;
+    const size_t n = picks.size();
+    std::vector<float> rays(n * 8);
+    const float3 eye = make_float3(p.cameraEye.x, p.cameraEye.y, p.cameraEye.z);
+    const float3 U = make_float3(p.cameraU.x, p.cameraU.y, p.cameraU.z), V = make_float3(p.cameraV.x, p.cameraV.y, p.cameraV.z),
+                 W = make_float3(p.cameraW.x, p.cameraW.y, p.cameraW.z);
+    for (size_t i = 0; i < n; i++) {
+        const float dx = 2.0f * (((float)picks[i].x + 0.5f) / (float)p.width) - 1.0f;
+        const float dy = 2.0f * (((float)picks[i].y + 0.5f) / (float)p.height) - 1.0f;
+        const float3 dir = normalize(dx * U + dy * V + W);
+        const float r[8] = {eye.x, eye.y, eye.z, dir.x, dir.y, dir.z, 0.01f, 1e16f};      // pt_render_features' interval
+        memcpy(&rays[8 * i], r, sizeof(r));
+    }
+    void* d_rays = nullptr; void* d_hits = nullptr;
+    std::vector<pt_hit> hits(n);
+    std::string err;
+    if (pt_device_malloc(state.context, &d_rays, n * 32) != 0 || pt_device_malloc(state.context, &d_hits, n * sizeof(pt_hit)) != 0 ||
+        pt_copy_to_device(state.context, d_rays, rays.data(), n * 32) != 0 ||
+        pt_query_closest(state.context, (const float*)d_rays, n, (pt_hit*)d_hits) != 0 ||
+        pt_copy_to_host(state.context, hits.data(), d_hits, n * sizeof(pt_hit)) != 0)
+        err = pt_last_error(state.context);
+    if (d_rays) pt_device_free(state.context, d_rays);
+    if (d_hits) pt_device_free(state.context, d_hits);
+    if (!err.empty()) throw Exception("pick: " + err);
+    const std::vector<std::string>& names = obj.getMaterialNames();
+    for (size_t i = 0; i < n; i++) {
+        const pt_hit& h = hits[i];
+        if (h.prim == 0xFFFFFFFFu) { printf("{\"pick\": [%d, %d], \"hit\": false}\n", picks[i].x, picks[i].y); continue; }
+        const float* r = &rays[8 * i];
+        std::string name = h.material < names.size() ? names[h.material] : std::string();
+        for (size_t k = 0; k < name.size(); k++) if (name[k] == '"' || name[k] == '\\' || (unsigned char)name[k] < 0x20) name[k] = '_';
+        printf("{\"pick\": [%d, %d], \"hit\": true, \"t\": %.9g, \"prim\": %u, \"material\": \"%s\", \"position\": [%.9g, %.9g, %.9g], \"normal\": [%.9g, %.9g, %.9g]}\n",
+               picks[i].x, picks[i].y, h.t, h.prim, name.c_str(), r[0] + h.t * r[3], r[1] + h.t * r[4], r[2] + h.t * r[5], h.nx, h.ny, h.nz);
+    }
+    fflush(stdout);
+}
+
 static void CleanAllTheThings(PathTracerState& state)                    // :629-646
 {
     if (state.params.accumulationBuffer) pt_device_free(state.context, state.params.accumulationBuffer);
@@ -578,6 +624,7 @@ int main(int argc, char** argv)
 {
     std::string objfilepath, out = "frame.png", keys, save_accum, restore_accum, history_out, history_in, move;
     std::vector<std::string> material_edits;
+    std::vector<int2> picks;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false, move_history = false, no_area_light = false;
     std::string env_path, tonemap, exposure_arg, out_hdr, error_out;
@@ -654,6 +701,7 @@ int main(int argc, char** argv)
                 bloom.levels = (uint32_t)levels; bloom.knee = 0.5f * bloom.threshold;
             }
         }
+        else if (a == "--pick") { int2 px; if (sscanf(next(), "%d,%d", &px.x, &px.y) != 2) { std::cerr << "--pick x,y" << std::endl; return 2; } picks.push_back(px); }
         else if (a == "--materials") {
             const std::string m = next();
             if (m == "reference") material_model = PT_MATERIALS_REFERENCE;
@@ -681,6 +729,8 @@ int main(int argc, char** argv)
         }
     }
     if (use_bloom && !display) { std::cerr << "--bloom needs --tonemap or --exposure" << std::endl; return 2; }
+    for (const int2& px : picks)
+        if (px.x < 0 || px.y < 0 || px.x >= width || px.y >= height) { std::cerr << "--pick: pixel " << px.x << "," << px.y << " is outside the " << width << " x " << height << " image" << std::endl; return 2; }
     if (move_history && move.empty()) { std::cerr << "--move-history needs --move" << std::endl; return 2; }
     const bool until_error = until.threshold > 0.0f;
     if (!error_out.empty() && !until_error) { std::cerr << "--error-out needs --until-error" << std::endl; return 2; }
@@ -769,6 +819,7 @@ int main(int argc, char** argv)
         initializeTheLaunch(state);
         if (no_area_light) state.params.areaLight.emission = {0.0f, 0.0f, 0.0f};
         std::cout << "Launch Initialized" << std::endl;
+        if (!picks.empty()) { std::cout.flush(); pickPixels(state, obj, picks); }
         HistoryFile history;
         if (!history_in.empty()) {              // refused before any frame is rendered
             history = readHistory(history_in);

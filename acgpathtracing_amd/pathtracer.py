@@ -241,6 +241,7 @@ class PathTracerState:
         self._scene_serial = 0        # advanced by buildTheAccelarationStructure only (pt_set_scene): TemporalHistory(motion=True)'s key
         self._verts_serial = 0        # advanced by every change of the positions (a build or updateVertices)
         self._mats_serial = 0         # advanced by every change of the materials (a build or updateMaterials)
+        self._device = 0              # the context's device (rank 0's of a group): where queryRays expects a tensor of rays
 
 
 def createDeviceContext(state, device_id=0, device_ids=None):
@@ -257,6 +258,7 @@ def createDeviceContext(state, device_id=0, device_ids=None):
         msg = L.pt_last_error(None)
         raise PathTracerError("createDeviceContext failed: %s" % (msg.decode() if msg else "unknown"))
     state.context = ctx
+    state._device = int(device_ids[0]) if device_ids is not None else int(device_id)
 
 
 def buildTheAccelarationStructure(state, objs):
@@ -624,6 +626,76 @@ def renderFeatures(state):
         return _read_image(state, bufs[0]), _read_image(state, bufs[1])
     finally:
         _free_device_buffers(state, bufs)
+
+
+HIT_DTYPE = np.dtype([("t", np.float32), ("prim", np.uint32), ("uv", np.float32, 2), ("normal", np.float32, 3), ("material", np.uint32)])      # pt_hit
+assert HIT_DTYPE.itemsize == 32
+
+
+def _is_tensor(x):
+    """A torch tensor, told without importing torch: only a caller that has one has paid for the import."""
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
+def _query_rays_tensor(state, rays, any_hit):
+    import torch
+    if rays.device.type != "cuda" or rays.device.index != state._device:
+        raise PathTracerError("queryRays: the rays are on %s, the context is on cuda:%d" % (rays.device, state._device))
+    if rays.dtype != torch.float32:
+        raise PathTracerError("queryRays: the rays must be float32, got %s" % rays.dtype)
+    if rays.dim() != 2 or rays.shape[1] != 8:
+        raise PathTracerError("queryRays: expected an (n, 8) tensor, got shape %s" % (tuple(rays.shape),))
+    if not rays.is_contiguous():
+        raise PathTracerError("queryRays: the rays must be contiguous (nothing is copied)")
+    n = int(rays.shape[0])
+    L = _native.hip()
+    with torch.cuda.device(rays.device):
+        out = torch.empty((n,), dtype=torch.uint8, device=rays.device) if any_hit else torch.empty((n, 8), dtype=torch.float32, device=rays.device)
+        torch.cuda.current_stream().synchronize()      # the rays' producer and the allocation; the call below returns synchronised
+    if any_hit:
+        _check(state.context, L.pt_query_any(state.context, rays.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_any")
+        return out.view(torch.bool)
+    _check(state.context, L.pt_query_closest(state.context, rays.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_closest")
+    return {"t": out[:, 0], "prim": out[:, 1].view(torch.int32), "uv": out[:, 2:4], "normal": out[:, 4:7], "material": out[:, 7].view(torch.int32)}
+
+
+def queryRays(state, rays, any_hit=False):
+    """Rays against the scene on the GPU (include/acgpt.h pt_query_closest / pt_query_any).  rays: (n, 8) float32 records of origin xyz,
+    direction xyz (not normalised; t is in units of its length), tmin, tmax (open interval; +inf allowed).
+
+    A NumPy array (or anything np.asarray takes) goes to the device and the answer comes back: a dict of arrays t (n,) float32 (-1 on a
+    miss), prim (n,) uint32 (the triangle's index in the scene's order, 0xFFFFFFFF on a miss), uv (n, 2) barycentrics of v1 and v2,
+    normal (n, 3) unit geometric normal facing the ray's origin, material (n,) uint32 — or, with any_hit, a bool array: is anything hit
+    inside the interval.
+
+    A torch tensor must be float32, contiguous and on the context's device; nothing is copied, its data_ptr() goes straight in, and
+    the answer is torch tensors on that device: views of one (n, 8) float32 tensor, prim and material as int32 (-1 on a miss), or a
+    bool tensor with any_hit.  torch's current stream is synchronised before the call, and the call returns synchronised."""
+    if _is_tensor(rays):
+        return _query_rays_tensor(state, rays, any_hit)
+    r = np.asarray(rays)
+    if r.ndim != 2 or r.shape[1] != 8:
+        raise PathTracerError("queryRays: expected an (n, 8) array, got shape %s" % (r.shape,))
+    if r.dtype.kind not in "fiu":
+        raise PathTracerError("queryRays: the rays must be numbers, got %s" % r.dtype)
+    r = np.ascontiguousarray(r, np.float32)
+    n = r.shape[0]
+    out = np.zeros(n, np.uint8) if any_hit else np.zeros(n, HIT_DTYPE)
+    if n:
+        L = _native.hip()
+        bufs = _device_buffers(state, 2, max(r.nbytes, out.nbytes))
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], r.ctypes.data, r.nbytes), "copy to device")
+            if any_hit:
+                _check(state.context, L.pt_query_any(state.context, bufs[0], n, bufs[1]), "pt_query_any")
+            else:
+                _check(state.context, L.pt_query_closest(state.context, bufs[0], n, bufs[1]), "pt_query_closest")
+            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    if any_hit:
+        return out.view(np.bool_)
+    return {k: np.ascontiguousarray(out[k]) for k in HIT_DTYPE.names}
 
 
 # pt_firefly_params' defaults (include/acgpt.h; DESIGN.md section 20 has the calibration)

@@ -386,9 +386,43 @@ int pt_get_stats(pt_ctx* ctx, pt_stats* out);
  * caller's index-buffer order) or 0xFFFFFFFF; interval is open (tmin, tmax),
  * two-sided, ties -> lowest triangle index.  any: hit_out[i] = 1 if any
  * triangle is hit inside the interval (traceOcclusion, pathTracerPrograms.cu:
- * 651-684).                                                                    */
+ * 651-684).  Both bring the fp32 node array onto the device first, whatever the
+ * scene holds.  pt_query_closest / pt_query_any below give the same answers for
+ * rays and results in DEVICE memory, add the rest of the hit record, and walk the
+ * node array the scene already holds.                                           */
 int pt_trace_closest(pt_ctx* ctx, const float* rays, size_t n, float* t_out, uint32_t* prim_out);
 int pt_trace_any(pt_ctx* ctx, const float* rays, size_t n, uint8_t* hit_out);
+
+/* ---- device-resident ray queries (opt-in; nothing above changes) ---------------------------------------------------------------
+ * A scene on the GPU to shoot rays at: picking, visibility and ambient-occlusion passes, probe baking, range sensors.  Rays and results
+ * stay in DEVICE memory (a hipMalloc'ed or pt_device_malloc'ed buffer, a torch tensor's data_ptr()), 16-byte aligned.  Both calls
+ * enqueue on the context's stream and return synchronised, act on rank 0 of a pt_create_multi context, and never write the
+ * accumulation buffer, the frame buffer or pt_stats.
+ *
+ *   rays      n records of 8 floats, pt_trace_closest's: origin xyz, direction xyz, tmin, tmax.  The direction is not normalised and t is
+ *             in units of its length; the interval (tmin, tmax) is open and two-sided; ties go to the lowest triangle index;
+ *             tmax = +inf is allowed.
+ *   same hits t and prim equal pt_trace_closest's, occluded equals pt_trace_any's, on every ray, as bits.
+ *   nodes     the rays walk the node array the scene holds — the fp16 centre / half-extent nodes of a default scene, else the fp32
+ *             nodes: pt_render_features' choice —, so pt_bvh_info.device_bytes is the same before and after a call (except under a
+ *             variant forced onto another format by pt_set_tuning, which brings the fp32 nodes back as pt_trace_closest does).
+ *   a miss before any traversal: a non-finite origin or direction component, a NaN tmin or tmax, !(tmax > tmin), a scene without
+ *             triangles.  (A zero direction needs no rule of its own: the triangle test rejects a zero determinant.)
+ *   miss      {t -1, prim 0xFFFFFFFF, u 0, v 0, n (0, 0, 0), material 0xFFFFFFFF}; occluded 0
+ *   hit       t the distance, prim the triangle's index in the caller's index-buffer order, material its material id;
+ *             n the unit geometric normal normalize(cross(e1, e2)), negated if dot(n, dir) > 0: it faces the ray's origin;
+ *             u, v the barycentrics of v1 and v2 (the point is (1 - u - v) v0 + u v1 + v v2), not clamped, recomputed once from the
+ *             hit triangle with e1 = v1 - v0, e2 = v2 - v0, o the origin and d the direction, in plain fp32 multiplies and adds,
+ *             left to right, and one IEEE division each (tests/query_ref.py is the NumPy statement, equal bit for bit):
+ *               p = cross(d, e2);  det = dot(e1, p);  s = o - v0;  u = dot(s, p) / det;  q = cross(s, e1);  v = dot(d, q) / det
+ *               cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x);  dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z
+ *   occluded  one byte per ray, 1 if any triangle is hit inside the interval, else 0
+ * n == 0 is a no-op success.  Refused, with the context left usable: n > 0x7FFFFFFF, a null rays or output pointer with n > 0, an array
+ * that is not 16-byte aligned (occluded may have any alignment), an output that overlaps the rays, a context without a scene.
+ * No atomics: two calls give the same bits.                                                                                        */
+typedef struct { float t; uint32_t prim; float u, v; float nx, ny, nz; uint32_t material; } pt_hit;   /* 32 bytes */
+int pt_query_closest(pt_ctx* ctx, const float* rays, size_t n, pt_hit* hits);
+int pt_query_any(pt_ctx* ctx, const float* rays, size_t n, uint8_t* occluded);
 
 /* ---- denoised preview (opt-in; nothing above changes) -------------------------------------------------------------------------
  * Both calls enqueue on the context's stream and return synchronised, cover the whole image (pt_set_partition does not apply), act
