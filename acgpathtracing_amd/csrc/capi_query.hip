@@ -1,9 +1,27 @@
-// capi_query.hip — the entry points of include/acgpt.h that answer ray queries in device memory: pt_query_closest, pt_query_any.
-// Host code only; the kernels are in query.hip.  The context and what the units share: context.h.
+// capi_query.hip — the entry points of include/acgpt.h that answer ray queries in device memory: pt_query_closest, pt_query_any, and
+// the ambient-occlusion stage on top of them: pt_ao_points, pt_ao_image.
+// Host code only; the kernels are in query.hip and ao.hip.  The context and what the units share: context.h.
+#include <cmath>
+
 #include "context.h"
+#include "ao.h"
 #include "query.h"
 
 static_assert(sizeof(pt_hit) == 32, "pt_hit: a change of this layout bumps pt_abi_version");
+static_assert(sizeof(pt_ao_params) == 32, "pt_ao_params: a change of this layout bumps pt_abi_version");
+
+// The node array the scene holds, as pt_render_features picks it: fp16 centre / half-extent nodes for the default variants, fp32
+// nodes for the fp32 ones; only a variant forced onto another format (pt_set_tuning) leaves neither and gets the fp32 nodes back.
+// The last refusals of a call: no scene, no device.  f: the entry point's name and ": ".
+static int query_node_format(pt_ctx* c, const std::string& f, int* fmt)
+{
+    if (c->scene_serial == 0) return fail(c, f + "no scene (pt_set_scene first)");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, f + "hipSetDevice failed");
+    *fmt = 0;
+    if (c->bvh.hcnodes) *fmt = 11;
+    else if (int rc = ensure_node_format(c, 0)) return rc;
+    return 0;
+}
 
 // every refusal of the two calls before any device work, in this order; out_bytes: bytes of output per ray.  *fmt: the node format
 // the scene holds (pt_render_features' choice).  Returns 0 to go on, 1 refused, -1 nothing to do (n == 0).
@@ -16,14 +34,7 @@ static int query_prepare(pt_ctx* c, const char* fn, const float* rays, size_t n,
     if (n > 0x7FFFFFFFull) return fail(c, f + "too many rays (2^31 - 1 per call)");
     if (((uintptr_t)rays & 15u) || (out_aligned && ((uintptr_t)out & 15u))) return fail(c, f + "the ray and hit arrays must be 16-byte aligned");
     if (spans_overlap(rays, n * 32u, out, n * out_bytes)) return fail(c, f + "the output overlaps the rays");
-    if (c->scene_serial == 0) return fail(c, f + "no scene (pt_set_scene first)");
-    if (hipSetDevice(c->device) != hipSuccess) return fail(c, f + "hipSetDevice failed");
-    // the node array the scene holds, as pt_render_features picks it: fp16 centre / half-extent nodes for the default variants, fp32
-    // nodes for the fp32 ones; only a variant forced onto another format (pt_set_tuning) leaves neither and gets the fp32 nodes back
-    *fmt = 0;
-    if (c->bvh.hcnodes) *fmt = 11;
-    else if (int rc = ensure_node_format(c, 0)) return rc;
-    return 0;
+    return query_node_format(c, f, fmt);
 }
 
 PT_API int pt_query_closest(pt_ctx* c, const float* rays, size_t n, pt_hit* hits)
@@ -42,6 +53,66 @@ PT_API int pt_query_any(pt_ctx* c, const float* rays, size_t n, uint8_t* occlude
     if (int rc = query_prepare(c, "pt_query_any", rays, n, occluded, 1, false, &fmt)) return rc < 0 ? 0 : rc;
     Range range("pt_query_any");
     CK(c, ptd::launch_query_any(fmt, device_scene(c), c->stack_entries, (const float4*)rays, (uint32_t)n, occluded, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- ambient occlusion ----------------------------------------------------------------------------------------------------------
+// every refusal of the two calls before any device work, in this order.  in: the points or the feature buffer, in_bytes per point.
+// On 0 the disk pattern is in c->d_ao_disk (enqueued on the context's stream) and *args is what the kernel gets.
+static int ao_prepare(pt_ctx* c, const std::string& f, const void* in, size_t in_bytes, size_t n, const float* disk, const pt_ao_params* ap,
+                      const uint32_t* visible, const float* ao, int* fmt, ptd::AoArgs* args)
+{
+    if (!in || !disk || !ap || !visible) return fail(c, f + "null argument");
+    if (n > 0x7FFFFFFFull) return fail(c, f + "too many points (2^31 - 1 per call)");
+    if (((uintptr_t)in & 15u) || ((uintptr_t)visible & 3u) || ((uintptr_t)ao & 3u)) return fail(c, f + "the input must be 16-byte aligned, the outputs 4-byte aligned");
+    if (ap->samples < 1u || ap->samples > ptd::kAoMaxSamples) return fail(c, f + "samples must be 1..256");
+    if (!(ap->radius > 0.0f) || !std::isfinite(ap->radius)) return fail(c, f + "radius must be positive and finite");
+    if (!(ap->bias >= 0.0f) || !std::isfinite(ap->bias)) return fail(c, f + "bias must be non-negative and finite");
+    if (ap->total_samples < ap->samples) return fail(c, f + "total_samples must be at least samples");
+    if (ap->reserved[0] || ap->reserved[1]) return fail(c, f + "reserved fields must be 0");
+    for (uint32_t k = 0; k < ap->samples; k++) {
+        const float x = disk[2u * k], y = disk[2u * k + 1u];
+        if (!std::isfinite(x) || !std::isfinite(y) || !(x * x + y * y <= 1.0f))
+            return fail(c, f + "disk point " + std::to_string(k) + " is outside the unit disk");
+    }
+    if (spans_overlap(in, n * in_bytes, visible, n * 4u)) return fail(c, f + "visible overlaps the input");
+    if (ao && spans_overlap(in, n * in_bytes, ao, n * 4u)) return fail(c, f + "ao overlaps the input");
+    if (ao && spans_overlap(visible, n * 4u, ao, n * 4u)) return fail(c, f + "ao overlaps visible");
+    if (int rc = query_node_format(c, f, fmt)) return rc;
+    CK(c, c->d_ao_disk.reserve(ptd::kAoMaxSamples, c->stream));
+    CK(c, hipMemcpyAsync(c->d_ao_disk.p, disk, (size_t)ap->samples * sizeof(float2), hipMemcpyHostToDevice, c->stream));
+    *args = {ap->samples, ap->radius, ap->bias, ap->seed, ap->accumulate, ap->total_samples};
+    return 0;
+}
+
+PT_API int pt_ao_points(pt_ctx* c, const float* points, size_t n, const float* disk, const pt_ao_params* ap, uint32_t* visible, float* ao)
+{
+    const std::string f = "pt_ao_points: ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (n == 0) return 0;
+    int fmt = 0;
+    ptd::AoArgs args;
+    if (int rc = ao_prepare(c, f, points, 32u, n, disk, ap, visible, ao, &fmt, &args)) return rc;
+    Range range("pt_ao_points");
+    CK(c, ptd::launch_ao_points(fmt, device_scene(c), c->stack_entries, (const float4*)points, (uint32_t)n, c->d_ao_disk.p, args, visible, ao, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_ao_image(pt_ctx* c, const pt_params* p, const float* normal_depth, const float* disk, const pt_ao_params* ap, uint32_t* visible, float* ao)
+{
+    const std::string f = "pt_ao_image: ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (!p) return fail(c, f + "null argument");
+    const size_t n = (size_t)p->width * p->height;
+    if (n == 0) return 0;
+    int fmt = 0;
+    ptd::AoArgs args;
+    if (int rc = ao_prepare(c, f, normal_depth, 16u, n, disk, ap, visible, ao, &fmt, &args)) return rc;
+    Range range("pt_ao_image");
+    const ptd::AoView view = {p->cameraEye, p->cameraU, p->cameraV, p->cameraW, p->width, p->height};
+    CK(c, ptd::launch_ao_image(fmt, device_scene(c), c->stack_entries, view, (const float4*)normal_depth, c->d_ao_disk.p, args, visible, ao, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -1,6 +1,6 @@
 // context.h — what the host units of the C ABI share: the context, the group, error reporting, the owner of a device allocation.
 // Host only (no kernel, not under pt_kernel_source_hash).  capi.hip: render core; capi_image.hip: the stages on a finished image;
-// capi_query.hip: the device-resident ray queries; capi_test.hip: include/acgpt_test.h.
+// capi_query.hip: the device-resident ray queries and ambient occlusion; capi_test.hip: include/acgpt_test.h.
 #pragma once
 #include <hip/hip_runtime.h>
 // RCCL: types only — librccl is loaded with dlopen by pt_create_multi, a single-GPU caller never touches it, and a box without
@@ -98,6 +98,7 @@ struct pt_ctx {
     StageBuf<ptd::BloomState> d_bloom;                // pt_bloom's counts and record ...
     DevBuf<float4> d_bloom_pyramid;                   // ... and its pyramid, all levels in one allocation
     StageBuf<ptd::ConvergenceState> d_convergence;    // pt_convergence_update's counts and record
+    DevBuf<float2> d_ao_disk;                 // pt_ao_points / pt_ao_image: the caller's disk pattern of the last call (at most 256 pairs)
     DevBuf<uint8_t> d_tri_bsdf;               // bsdfType per triangle (caller's order): pt_temporal_blend's, built on its first call per scene
     // what pt_update_vertices keeps of the last pt_set_scene: host copies of everything but the vertices, and after the first update
     // the index buffer on the device (freed with the scene)

@@ -16,6 +16,12 @@
 //              [--tonemap linear|reinhard|aces] [--exposure auto|<EV>] [--out-hdr file.pfm]
 //              [--until-error E [--until-permille P] [--error-floor F] [--error-out file.pfm]]
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
+//              [--ao K[,radius[,bias]] --ao-out file.pfm [--ao-frames n]]
+// --ao K[,radius[,bias]] with --ao-out: once the scene is set and before the first frame, the ambient occlusion of the view
+// (pt_render_features + pt_ao_image): K rays per pixel (1..256) and call over --ao-frames calls (default 1; call j has seed j and
+// accumulates), on the default pattern — the Vogel spiral of pathtracer.aoSamples, the same formula in double —, written as a .pfm
+// (grey in three channels, bottom row first).  radius defaults to a quarter of the scene box's diagonal, bias to a thousandth of it,
+// both computed in double and rounded.  The frames are the same with or without it.
 // --pick x,y (repeatable): once the scene is set and before the first frame, what lies under pixel (x, y), row 0 at the bottom: the
 // closest hit of the camera ray through the pixel's centre (pt_query_closest; the ray of pt_render_features), one JSON line each:
 // {"pick": [x, y], "hit": true, "t": .., "prim": .., "material": "<newmtl name>", "position": [eye + t * dir], "normal": [..]}, on a
@@ -613,6 +619,55 @@ static void pickPixels(PathTracerState& state, const TinyObjWrapper& obj, const 
     fflush(stdout);
 }
 
+// --ao: the default sample pattern (pathtracer.aoSamples restated: the same double operations, the same fp32 pull-in)
+static std::vector<float> aoSamples(int K)
+{
+    const double golden = M_PI * (3.0 - std::sqrt(5.0));
+    std::vector<float> disk(2 * (size_t)K);
+    for (int k = 0; k < K; k++) {
+        const double r = std::sqrt((k + 0.5) / K);
+        float x = (float)(r * std::cos(k * golden)), y = (float)(r * std::sin(k * golden));
+        while (x * x + y * y > 1.0f) { x = std::nextafterf(x, 0.0f); y = std::nextafterf(y, 0.0f); }
+        disk[2 * k] = x; disk[2 * k + 1] = y;
+    }
+    return disk;
+}
+
+// --ao: pt_render_features, then `frames` accumulating pt_ao_image calls; the AO image as a grey .pfm
+static void ambientOcclusion(PathTracerState& state, int K, float radius, float bias, int frames, const std::string& path)
+{
+    const pt_params& p = state.params;
+    const size_t n = (size_t)p.width * p.height;
+    pt_bvh_info info;
+    PT_CHECK(state.context, pt_get_bvh_info(state.context, &info));
+    double diag = 0.0;
+    for (int k = 0; k < 3; k++) diag += ((double)info.scene_hi[k] - (double)info.scene_lo[k]) * ((double)info.scene_hi[k] - (double)info.scene_lo[k]);
+    diag = std::sqrt(diag);
+    if (!(radius > 0.0f)) radius = (float)(0.25 * diag);
+    if (bias < 0.0f) bias = (float)(1e-3 * diag);
+    const std::vector<float> disk = aoSamples(K);
+    void* d_alb = nullptr; void* d_nd = nullptr; void* d_vis = nullptr; void* d_ao = nullptr;
+    std::vector<float> ao(n);
+    std::string err;
+    bool ok = pt_device_malloc(state.context, &d_alb, n * 16) == 0 && pt_device_malloc(state.context, &d_nd, n * 16) == 0 &&
+              pt_device_malloc(state.context, &d_vis, n * 4) == 0 && pt_device_malloc(state.context, &d_ao, n * 4) == 0 &&
+              pt_render_features(state.context, &p, (float*)d_alb, (float*)d_nd) == 0;
+    for (int j = 0; ok && j < frames; j++) {
+        const pt_ao_params ap = {(uint32_t)K, radius, bias, (uint32_t)j, j > 0 ? 1u : 0u, (uint32_t)K * (uint32_t)(j + 1), {0u, 0u}};
+        ok = pt_ao_image(state.context, &p, (const float*)d_nd, disk.data(), &ap, (uint32_t*)d_vis, (float*)d_ao) == 0;
+    }
+    ok = ok && pt_copy_to_host(state.context, ao.data(), d_ao, n * 4) == 0;
+    if (!ok) err = pt_last_error(state.context);
+    for (void* b : {d_alb, d_nd, d_vis, d_ao}) if (b) pt_device_free(state.context, b);
+    if (!ok) throw Exception("ao: " + err);
+    std::vector<float> grey(n * 3);
+    double sum = 0.0;
+    for (size_t i = 0; i < n; i++) { grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = ao[i]; sum += ao[i]; }
+    if (!savePFM(path, grey.data(), (int)p.width, (int)p.height, 3)) throw Exception("could not write " + path);
+    std::cout << "Ambient occlusion: " << K << " x " << frames << " rays per pixel, radius " << radius << ", bias " << bias << ", mean " << sum / (double)n
+              << " -> " << path << std::endl;
+}
+
 static void CleanAllTheThings(PathTracerState& state)                    // :629-646
 {
     if (state.params.accumulationBuffer) pt_device_free(state.context, state.params.accumulationBuffer);
@@ -627,7 +682,9 @@ int main(int argc, char** argv)
     std::vector<int2> picks;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false, move_history = false, no_area_light = false;
-    std::string env_path, tonemap, exposure_arg, out_hdr, error_out;
+    std::string env_path, tonemap, exposure_arg, out_hdr, error_out, ao_out;
+    int ao_samples = 0, ao_frames = 1;
+    float ao_radius = 0.0f, ao_bias = -1.0f;      // the defaults: from the scene box (ambientOcclusion)
     pt_firefly_params firefly = {0.0f, 0.01f, 1u, 1u};       // ratio 0: no --firefly; the other defaults of include/acgpt.h
     pt_bloom_params bloom = {1.0f, 0.5f, 0.0f, 0.02f, 1.0f, 6u};   // pt_bloom_params' defaults (include/acgpt.h), in display units
     bool use_bloom = false;
@@ -701,6 +758,14 @@ int main(int argc, char** argv)
                 bloom.levels = (uint32_t)levels; bloom.knee = 0.5f * bloom.threshold;
             }
         }
+        else if (a == "--ao") {
+            const int got = sscanf(next(), "%d,%f,%f", &ao_samples, &ao_radius, &ao_bias);
+            if (got < 1 || ao_samples < 1 || ao_samples > 256 || (got >= 2 && (!std::isfinite(ao_radius) || !(ao_radius > 0.0f))) || (got >= 3 && (!std::isfinite(ao_bias) || !(ao_bias >= 0.0f)))) {
+                std::cerr << "--ao takes K[,radius[,bias]]: K 1 to 256, radius > 0, bias >= 0" << std::endl; return 2;
+            }
+        }
+        else if (a == "--ao-out") ao_out = next();
+        else if (a == "--ao-frames") { ao_frames = atoi(next()); if (ao_frames < 1 || ao_frames > 65536) { std::cerr << "--ao-frames takes 1 to 65536" << std::endl; return 2; } }
         else if (a == "--pick") { int2 px; if (sscanf(next(), "%d,%d", &px.x, &px.y) != 2) { std::cerr << "--pick x,y" << std::endl; return 2; } picks.push_back(px); }
         else if (a == "--materials") {
             const std::string m = next();
@@ -731,6 +796,7 @@ int main(int argc, char** argv)
     if (use_bloom && !display) { std::cerr << "--bloom needs --tonemap or --exposure" << std::endl; return 2; }
     for (const int2& px : picks)
         if (px.x < 0 || px.y < 0 || px.x >= width || px.y >= height) { std::cerr << "--pick: pixel " << px.x << "," << px.y << " is outside the " << width << " x " << height << " image" << std::endl; return 2; }
+    if ((ao_samples > 0) != !ao_out.empty()) { std::cerr << "--ao and --ao-out go together" << std::endl; return 2; }
     if (move_history && move.empty()) { std::cerr << "--move-history needs --move" << std::endl; return 2; }
     const bool until_error = until.threshold > 0.0f;
     if (!error_out.empty() && !until_error) { std::cerr << "--error-out needs --until-error" << std::endl; return 2; }
@@ -820,6 +886,7 @@ int main(int argc, char** argv)
         if (no_area_light) state.params.areaLight.emission = {0.0f, 0.0f, 0.0f};
         std::cout << "Launch Initialized" << std::endl;
         if (!picks.empty()) { std::cout.flush(); pickPixels(state, obj, picks); }
+        if (ao_samples > 0) ambientOcclusion(state, ao_samples, ao_radius, ao_bias, ao_frames, ao_out);
         HistoryFile history;
         if (!history_in.empty()) {              // refused before any frame is rendered
             history = readHistory(history_in);

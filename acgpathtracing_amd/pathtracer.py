@@ -238,6 +238,7 @@ class PathTracerState:
         self._accum_bytes = 0
         self._temporal = []           # TemporalHistory objects holding device buffers of this context (freed by CleanAllTheThings)
         self._scene_verts = None      # host copy of the scene's current vertex positions, (n, 4) float32
+        self._scene_idx = None        # host copy of the scene's index buffer, (n_tris, 3) uint32: bakeVertexAO's triangles
         self._scene_serial = 0        # advanced by buildTheAccelarationStructure only (pt_set_scene): TemporalHistory(motion=True)'s key
         self._verts_serial = 0        # advanced by every change of the positions (a build or updateVertices)
         self._mats_serial = 0         # advanced by every change of the materials (a build or updateMaterials)
@@ -274,6 +275,7 @@ def buildTheAccelarationStructure(state, objs):
     _check(state.context, rc, "buildTheAccelarationStructure")
     state.params.handle = L.pt_scene_handle(state.context)
     state._scene_verts = v.reshape(-1, 4).copy()
+    state._scene_idx = idx.reshape(-1, 3).copy()
     state._scene_serial += 1
     state._verts_serial += 1
     state._mats_serial += 1
@@ -696,6 +698,281 @@ def queryRays(state, rays, any_hit=False):
     if any_hit:
         return out.view(np.bool_)
     return {k: np.ascontiguousarray(out[k]) for k in HIT_DTYPE.names}
+
+
+# ------------------------------------------------------------------ ambient occlusion ----
+def aoSamples(K):
+    """The default sample pattern of the ambient-occlusion calls: K points of a Vogel spiral on the unit disk, float32 (K, 2):
+    r = sqrt((k + 0.5) / K), angle k * pi * (3 - sqrt(5)), computed in float64 and rounded; a point that rounding pushed outside the disk
+    (x * x + y * y > 1 in fp32) is pulled back in, one fp32 step towards zero per component at a time.  Lifted over the hemisphere its
+    points are cosine-distributed."""
+    import math
+    K = int(K)
+    if not 1 <= K <= _native.AO_MAX_SAMPLES:
+        raise PathTracerError("aoSamples: K must be 1..%d, got %d" % (_native.AO_MAX_SAMPLES, K))
+    golden = math.pi * (3.0 - math.sqrt(5.0))
+    out = np.zeros((K, 2), np.float32)
+    zero, one = np.float32(0.0), np.float32(1.0)
+    for k in range(K):
+        r = math.sqrt((k + 0.5) / K)
+        x, y = np.float32(r * math.cos(k * golden)), np.float32(r * math.sin(k * golden))
+        while x * x + y * y > one:
+            x, y = np.nextafter(x, zero), np.nextafter(y, zero)
+        out[k] = (x, y)
+    return out
+
+
+def _ao_disk(disk, samples, what):
+    """The (K, 2) float32 pattern of a call: the caller's, checked as the library checks it, or the default one for `samples`."""
+    if disk is None:
+        return aoSamples(samples)
+    d = np.asarray(disk)
+    if d.ndim != 2 or d.shape[1] != 2 or d.dtype.kind not in "fiu":
+        raise PathTracerError("%s: the disk pattern must be a (K, 2) array of numbers, got %s %s" % (what, d.dtype, d.shape))
+    if not 1 <= d.shape[0] <= _native.AO_MAX_SAMPLES:
+        raise PathTracerError("%s: the disk pattern must have 1..%d points, got %d" % (what, _native.AO_MAX_SAMPLES, d.shape[0]))
+    d = np.ascontiguousarray(d, np.float32)
+    with np.errstate(all="ignore"):
+        inside = np.isfinite(d).all(axis=1) & (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] <= np.float32(1.0))
+    if not inside.all():
+        raise PathTracerError("%s: disk point %d is outside the unit disk" % (what, int(np.flatnonzero(~inside)[0])))
+    return d
+
+
+def _ao_reach(state, radius, bias, what):
+    """(radius, bias): the caller's, or a quarter and a thousandth of the scene box's diagonal."""
+    if radius is None or bias is None:
+        info = getBvhInfo(state)
+        diag = float(np.sqrt(sum((float(info.scene_hi[k]) - float(info.scene_lo[k])) ** 2 for k in range(3))))
+        radius = 0.25 * diag if radius is None else radius
+        bias = 1e-3 * diag if bias is None else bias
+    radius, bias = float(radius), float(bias)
+    if not (radius > 0.0 and np.isfinite(radius)):
+        raise PathTracerError("%s: radius must be positive and finite, got %r" % (what, radius))
+    if not (bias >= 0.0 and np.isfinite(bias)):
+        raise PathTracerError("%s: bias must be non-negative and finite, got %r" % (what, bias))
+    return radius, bias
+
+
+def _ao_params(disk, radius, bias, seed=0, accumulate=False, total=None):
+    K = disk.shape[0]
+    return _native.AoParams(K, radius, bias, int(seed) & 0xFFFFFFFF, 1 if accumulate else 0, K if total is None else int(total), (C.c_uint32 * 2)(0, 0))
+
+
+def _ao_image_call(state, nd_ptr, disk, ap, visible_ptr):
+    """pt_ao_image on a feature buffer on the device: the AO image, float32 [height, width]"""
+    h, w = int(state.params.height), int(state.params.width)
+    out = np.zeros((h, w), np.float32)
+    bufs = _device_buffers(state, 1, max(w * h * 4, 4))
+    try:
+        _check(state.context, _native.hip().pt_ao_image(state.context, C.byref(state.params), nd_ptr, disk.ctypes.data, C.byref(ap), visible_ptr, bufs[0]), "pt_ao_image")
+        if out.size:
+            _check(state.context, _native.hip().pt_copy_to_host(state.context, out.ctypes.data, bufs[0], out.nbytes), "copy to host")
+    finally:
+        _free_device_buffers(state, bufs)
+    return out
+
+
+def _ao_features(state, normal_depth, bufs, what):
+    """The device pointer of the normal_depth buffer of the current view: rendered now (None), uploaded (an array) or the caller's
+    (a device pointer).  New buffers are appended to bufs; the caller frees those."""
+    h, w = int(state.params.height), int(state.params.width)
+    if normal_depth is not None and not isinstance(normal_depth, np.ndarray):
+        return int(normal_depth)
+    bufs += _device_buffers(state, 2 if normal_depth is None else 1, max(w * h * 16, 16))
+    if normal_depth is None:
+        _check(state.context, _native.hip().pt_render_features(state.context, C.byref(state.params), bufs[-2], bufs[-1]), "pt_render_features")
+    else:
+        if normal_depth.shape != (h, w, 4):
+            raise PathTracerError("%s: normal_depth of shape %s, got %s" % (what, (h, w, 4), normal_depth.shape))
+        a = np.ascontiguousarray(normal_depth, np.float32)
+        _check(state.context, _native.hip().pt_copy_to_device(state.context, bufs[-1], a.ctypes.data, a.nbytes), "copy to device")
+    return bufs[-1]
+
+
+def ambientOcclusion(state, samples=16, radius=None, bias=None, disk=None, normal_depth=None, seed=0):
+    """Ambient occlusion of the current view (include/acgpt.h pt_ao_image): float32 [height, width] (row 0 = bottom), the share of
+    `samples` rays over each pixel's first hit that find nothing within `radius`; 1 where the pixel sees no surface.  radius defaults to a
+    quarter of the scene box's diagonal, bias (the rays' start above the surface) to a thousandth of it; disk: a (K, 2) pattern on the unit
+    disk instead of aoSamples(samples).  normal_depth: renderFeatures' second output for this view (an array, or a device pointer), rendered
+    here if not given."""
+    disk = _ao_disk(disk, samples, "ambientOcclusion")
+    radius, bias = _ao_reach(state, radius, bias, "ambientOcclusion")
+    h, w = int(state.params.height), int(state.params.width)
+    bufs = []
+    try:
+        nd = _ao_features(state, normal_depth, bufs, "ambientOcclusion")
+        bufs += _device_buffers(state, 1, max(w * h * 4, 4))
+        return _ao_image_call(state, nd, disk, _ao_params(disk, radius, bias, seed), bufs[-1])
+    finally:
+        _free_device_buffers(state, bufs)
+
+
+class AmbientOcclusion:
+    """Progressive ambient occlusion of a view (include/acgpt.h pt_ao_image with accumulate): every update(state) adds `samples` rays
+    per pixel under a new seed — the pattern turned by another angle per pixel — and returns the AO image of all of them so far, float32
+    [height, width].  The counts start over, silently, when the image size, the camera, the geometry or the reach differ from the last
+    update.  Owns its device buffer: close() frees it, and so does CleanAllTheThings for the context."""
+
+    def __init__(self, samples=16, radius=None, bias=None, disk=None):
+        self.disk = _ao_disk(disk, samples, "AmbientOcclusion")
+        self.radius, self.bias = radius, bias
+        self.calls = 0              # the next call's seed
+        self.total = 0              # rays per pixel so far
+        self._state = None
+        self._bufs = []             # visible
+        self._key = None
+        self._shape = None
+
+    def _bind(self, state):
+        if self._state is None:
+            self._state = state
+            state._temporal.append(self)
+        elif self._state is not state:
+            raise PathTracerError("AmbientOcclusion: bound to another PathTracerState")
+
+    def reset(self):
+        """The next update is a first one."""
+        self.calls, self.total = 0, 0
+
+    def update(self, state, normal_depth=None):
+        self._bind(state)
+        p = state.params
+        w, h = int(p.width), int(p.height)
+        radius, bias = _ao_reach(state, self.radius, self.bias, "AmbientOcclusion")
+        key = Convergence._key_of(state)[:-1] + (state._verts_serial, radius, bias)
+        if self._shape != (w, h):
+            _free_device_buffers(state, self._bufs)
+            self._bufs, self._shape = [], None
+            self._bufs = _device_buffers(state, 1, max(w * h * 4, 4))
+            self._shape, self._key = (w, h), None
+        if key != self._key:
+            self.reset()
+            self._key = key
+        K = self.disk.shape[0]
+        bufs = []
+        try:
+            nd = _ao_features(state, normal_depth, bufs, "AmbientOcclusion")
+            out = _ao_image_call(state, nd, self.disk, _ao_params(self.disk, radius, bias, self.calls, self.calls > 0, self.total + K), self._bufs[0])
+        finally:
+            _free_device_buffers(state, bufs)
+        self.calls += 1
+        self.total += K
+        return out
+
+    def visible(self):
+        """uint32 [height, width]: the rays that found nothing, of `total` per pixel"""
+        if self._state is None or not self.calls:
+            raise PathTracerError("AmbientOcclusion.visible: update(state) first")
+        w, h = self._shape
+        out = np.zeros((h, w), np.uint32)
+        _check(self._state.context, _native.hip().pt_copy_to_host(self._state.context, out.ctypes.data, self._bufs[0], out.nbytes), "copy to host")
+        return out
+
+    def close(self):
+        state = self._state
+        if state is None:
+            return
+        if state.context:
+            _free_device_buffers(state, self._bufs)
+        self._bufs, self._shape, self._key = [], None, None
+        self.reset()
+        if self in state._temporal:
+            state._temporal.remove(self)
+        self._state = None
+
+
+def _bake_ao_tensor(state, points, normals, disk, ap):
+    import torch
+    for t, name in ((points, "points"),) + (((normals, "normals"),) if normals is not None else ()):
+        if not _is_tensor(t):
+            raise PathTracerError("bakeAO: points and normals must both be tensors or both arrays")
+        if t.device.type != "cuda" or t.device.index != state._device:
+            raise PathTracerError("bakeAO: the %s are on %s, the context is on cuda:%d" % (name, t.device, state._device))
+        if t.dtype != torch.float32:
+            raise PathTracerError("bakeAO: the %s must be float32, got %s" % (name, t.dtype))
+        if t.dim() != 2 or t.shape[1] != (3 if normals is not None else 8) or t.shape[0] != points.shape[0]:
+            raise PathTracerError("bakeAO: expected an (n, 8) tensor of records or (n, 3) points and normals, got shape %s" % (tuple(t.shape),))
+    if normals is None and not points.is_contiguous():
+        raise PathTracerError("bakeAO: the records must be contiguous (nothing is copied)")
+    n = int(points.shape[0])
+    with torch.cuda.device(points.device):
+        rec = points
+        if normals is not None:
+            rec = torch.zeros((n, 8), dtype=torch.float32, device=points.device)      # the records the library reads, built by torch
+            rec[:, 0:3] = points
+            rec[:, 4:7] = normals
+        visible = torch.empty((n,), dtype=torch.int32, device=points.device)
+        ao = torch.empty((n,), dtype=torch.float32, device=points.device)
+        torch.cuda.current_stream().synchronize()      # the records' producer and the allocations; the call below returns synchronised
+    _check(state.context, _native.hip().pt_ao_points(state.context, rec.data_ptr() if n else None, n, disk.ctypes.data, C.byref(ap),
+                                                     visible.data_ptr() if n else None, ao.data_ptr() if n else None), "pt_ao_points")
+    return ao
+
+
+def bakeAO(state, points, normals=None, samples=64, radius=None, bias=None, disk=None, seed=0):
+    """Ambient occlusion at n surface points (include/acgpt.h pt_ao_points): the share of `samples` rays over the hemisphere of each
+    point's normal that find nothing within `radius`.  points, normals: (n, 3) each — or, with normals None, points is the (n, 8) array
+    of records the library reads: P.xyz, unused, N.xyz, unused.  The normals are used as they are (unit length is the caller's
+    business); a point with a non-finite component or a zero normal comes out fully open.
+
+    NumPy arrays (or anything np.asarray takes) go to the device and a float32 (n,) array comes back.  Float32 torch tensors on the
+    context's device stay there and a float32 tensor on that device comes back: an (n, 8) tensor of records must be contiguous, nothing
+    is copied and its data_ptr() goes straight in; (n, 3) points and normals are put into records by torch.  torch's current stream is
+    synchronised before the call, and the call returns synchronised."""
+    disk = _ao_disk(disk, samples, "bakeAO")
+    if _is_tensor(points) or _is_tensor(normals):
+        radius, bias = _ao_reach(state, radius, bias, "bakeAO")
+        return _bake_ao_tensor(state, points, normals, disk, _ao_params(disk, radius, bias, seed))
+    P = np.asarray(points)
+    N = None if normals is None else np.asarray(normals)
+    if P.ndim != 2 or P.shape[1] != (8 if N is None else 3) or (N is not None and N.shape != P.shape):
+        raise PathTracerError("bakeAO: expected an (n, 8) array of records or (n, 3) points and normals, got shapes %s and %s" % (P.shape, None if N is None else N.shape))
+    if P.dtype.kind not in "fiu" or (N is not None and N.dtype.kind not in "fiu"):
+        raise PathTracerError("bakeAO: points and normals must be numbers, got %s" % P.dtype)
+    n = P.shape[0]
+    out = np.zeros(n, np.float32)
+    if n == 0:
+        return out
+    radius, bias = _ao_reach(state, radius, bias, "bakeAO")
+    rec = np.zeros((n, 8), np.float32)
+    if N is None:
+        rec[:] = P
+    else:
+        rec[:, 0:3] = P
+        rec[:, 4:7] = N
+    L = _native.hip()
+    bufs = _device_buffers(state, 3, rec.nbytes)
+    try:
+        _check(state.context, L.pt_copy_to_device(state.context, bufs[0], rec.ctypes.data, rec.nbytes), "copy to device")
+        ap = _ao_params(disk, radius, bias, seed)
+        _check(state.context, L.pt_ao_points(state.context, bufs[0], n, disk.ctypes.data, C.byref(ap), bufs[1], bufs[2]), "pt_ao_points")
+        _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[2], out.nbytes), "copy to host")
+    finally:
+        _free_device_buffers(state, bufs)
+    return out
+
+
+def vertexNormals(verts, idx):
+    """Area-weighted vertex normals, float32 (n_verts, 3): the sum of cross(v1 - v0, v2 - v0) over the triangles at a vertex (the cross
+    product's length is twice the area), normalised; (0, 0, 0) at a vertex no triangle with an area uses."""
+    v = np.asarray(verts, np.float64).reshape(len(verts), -1)[:, :3]
+    t = np.asarray(idx, np.int64).reshape(-1, 3)
+    c = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+    acc = np.zeros_like(v)
+    for k in range(3):
+        np.add.at(acc, t[:, k], c)
+    length = np.sqrt((acc * acc).sum(axis=1, keepdims=True))
+    return np.where(length > 0.0, acc / np.where(length > 0.0, length, 1.0), 0.0).astype(np.float32)
+
+
+def bakeVertexAO(state, samples=64, radius=None, bias=None, disk=None, seed=0):
+    """One ambient-occlusion value per vertex of the scene as it stands (after updateVertices: the moved one), float32 (n_verts,): bakeAO
+    at the vertices with their area-weighted normals.  A vertex no triangle uses comes out 1."""
+    if state._scene_verts is None:
+        raise PathTracerError("bakeVertexAO: no scene (buildTheAccelarationStructure first)")
+    verts = state._scene_verts[:, :3]
+    return bakeAO(state, verts, vertexNormals(verts, state._scene_idx), samples=samples, radius=radius, bias=bias, disk=disk, seed=seed)
 
 
 # pt_firefly_params' defaults (include/acgpt.h; DESIGN.md section 20 has the calibration)

@@ -424,6 +424,55 @@ typedef struct { float t; uint32_t prim; float u, v; float nx, ny, nz; uint32_t 
 int pt_query_closest(pt_ctx* ctx, const float* rays, size_t n, pt_hit* hits);
 int pt_query_any(pt_ctx* ctx, const float* rays, size_t n, uint8_t* occluded);
 
+/* ---- ambient occlusion traced on the device (opt-in; nothing above changes) -----------------------------------------------------
+ * The share of the hemisphere over a surface point that is open within `radius`: K rays per point, generated, traced with
+ * pt_query_any's walk and counted inside one kernel, so no ray reaches memory.  pt_ao_points takes the points from a device array
+ * (baking: vertices, texels, probes), pt_ao_image from pt_render_features' second output (an AO pass of the current view).  Both
+ * enqueue on the context's stream and return synchronised, act on rank 0 of a pt_create_multi context, never write the accumulation
+ * buffer, the frame buffer or pt_stats, and walk the node array the scene holds exactly as pt_query_any does
+ * (pt_bvh_info.device_bytes does not change).  No atomics: two calls give the same bits.
+ *
+ *   points        DEVICE, 16-byte aligned, n records of two float4: {P.xyz, unused} {N.xyz, unused}.  N is a unit normal as the caller
+ *                 has it; it is not renormalised.
+ *   normal_depth  DEVICE, float4[w*h]: pt_render_features' second output for the view in params, of which the call reads width, height
+ *                 and the camera, nothing else.  n = w * h, the point of pixel p = y * w + x is P = eye + t * dir per component (one
+ *                 multiply, one add), dir the direction pt_render_features traced (the same expression: the same bits),
+ *                 t = normal_depth.w, N = normal_depth.xyz.
+ *   disk          HOST, K pairs (x, y) with x * x + y * y <= 1 in fp32: the sample pattern, the caller's.  The library copies it into a
+ *                 small buffer the context keeps (pt_destroy frees it).
+ *   visible       DEVICE uint32[n], 4-byte aligned: the rays that found nothing, 0..K per call
+ *   ao            DEVICE float[n], 4-byte aligned, or NULL: visible / total_samples
+ *
+ * Per point i, all fp32, evaluated left to right as written, no fused multiply-add (tests/ao_ref.py is the NumPy statement, equal bit
+ * for bit):
+ *   no surface  a non-finite component of P or N, N = (0, 0, 0), or (image form) normal_depth.w < 0: count = K, nothing is traced
+ *   hash        h = tea4(i, seed)  (four rounds of TEA over (i, seed), the first word; the renderer's own seed function)
+ *   rotation    a = float(h & 0xFFFF) * 2^-16;  a2 = a * a;  den = 1 + a2;  c = (1 - a2) / den;  s = (a + a) / den;  then
+ *               q = (h >> 16) & 3 quarter turns, exactly: q = 1: (c, s) <- (-s, c);  q = 2: (-c, -s);  q = 3: (s, -c)
+ *   frame       sg = copysignf(1, N.z);  A = -1 / (sg + N.z);  B = N.x * N.y * A;                             (Duff et al. 2017)
+ *               T = (1 + sg * N.x * N.x * A, sg * B, -sg * N.x);  S = (B, sg + N.y * N.y * A, -N.y)
+ *   origin      o = P + bias * N per component
+ *   ray k       x' = c * x_k - s * y_k;  y' = s * x_k + c * y_k;  z = sqrtf(fmaxf(0, (1 - x' * x') - y' * y'));
+ *               d = (x' * T + y' * S) + z * N per component;  the ray {o, d, tmin 0, tmax radius} under pt_query_any's rules, its miss
+ *               before any traversal included;  count += not occluded
+ *   outputs     visible[i] = count, or visible[i] += count when accumulate is set;  ao[i] = float(visible[i]) / float(total_samples),
+ *               one IEEE division, of the value just stored
+ * A progressive caller passes accumulate = 1, its call index as seed and its running sum of samples as total_samples.
+ * n == 0 (or an empty image) is a no-op success.  Refused, with the context left usable: a null context, params, input, disk, ao
+ * parameters or visible; an input that is not 16-byte or an output that is not 4-byte aligned; n > 0x7FFFFFFF; samples outside
+ * 1..256; a radius that is not positive and finite; a bias that is negative or not finite; total_samples < samples; a non-zero reserved
+ * field; a disk point outside the unit disk or not finite; an output that overlaps the input or the other output; a context without
+ * a scene.                                                                                                                          */
+typedef struct { uint32_t samples;        /* K: rays per point in this call, 1..256 */
+                 float    radius;         /* reach of a ray, > 0, finite */
+                 float    bias;           /* origin offset along the normal, >= 0, finite */
+                 uint32_t seed;           /* second word of the per-point hash; a progressive caller passes its call index */
+                 uint32_t accumulate;     /* 0: visible[i] = count;  non-zero: visible[i] += count */
+                 uint32_t total_samples;  /* divisor of `ao`: the caller's running sum of `samples`, this call included; >= samples */
+                 uint32_t reserved[2];    /* must be 0 */ } pt_ao_params;   /* 32 bytes */
+int pt_ao_points(pt_ctx* ctx, const float* points, size_t n, const float* disk, const pt_ao_params* ao_params, uint32_t* visible, float* ao);
+int pt_ao_image(pt_ctx* ctx, const pt_params* params, const float* normal_depth, const float* disk, const pt_ao_params* ao_params, uint32_t* visible, float* ao);
+
 /* ---- denoised preview (opt-in; nothing above changes) -------------------------------------------------------------------------
  * Both calls enqueue on the context's stream and return synchronised, cover the whole image (pt_set_partition does not apply), act
  * on rank 0 of a pt_create_multi context, and never write the accumulation buffer, the frame buffer or pt_stats.  A caller of the
