@@ -1,13 +1,17 @@
-// capi_query.hip — the entry points of include/acgpt.h that answer ray queries in device memory: pt_query_closest, pt_query_any, and
-// the ambient-occlusion stage on top of them: pt_ao_points, pt_ao_image.
-// Host code only; the kernels are in query.hip and ao.hip.  The context and what the units share: context.h.
+// capi_query.hip — the entry points of include/acgpt.h that answer queries in device memory: pt_query_closest, pt_query_any, the
+// ambient-occlusion stage on top of them: pt_ao_points, pt_ao_image, and the closest-point query pt_query_nearest (with its counting
+// twin of include/acgpt_test.h).
+// Host code only; the kernels are in query.hip, ao.hip and nearest.hip.  The context and what the units share: context.h.
 #include <cmath>
 
+#include "../../include/acgpt_test.h"
 #include "context.h"
 #include "ao.h"
+#include "nearest.h"
 #include "query.h"
 
 static_assert(sizeof(pt_hit) == 32, "pt_hit: a change of this layout bumps pt_abi_version");
+static_assert(sizeof(pt_nearest) == 32, "pt_nearest: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_ao_params) == 32, "pt_ao_params: a change of this layout bumps pt_abi_version");
 
 // The node array the scene holds, as pt_render_features picks it: fp16 centre / half-extent nodes for the default variants, fp32
@@ -53,6 +57,43 @@ PT_API int pt_query_any(pt_ctx* c, const float* rays, size_t n, uint8_t* occlude
     if (int rc = query_prepare(c, "pt_query_any", rays, n, occluded, 1, false, &fmt)) return rc < 0 ? 0 : rc;
     Range range("pt_query_any");
     CK(c, ptd::launch_query_any(fmt, device_scene(c), c->stack_entries, (const float4*)rays, (uint32_t)n, occluded, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- closest point ---------------------------------------------------------------------------------------------------------------
+// every refusal of pt_query_nearest before any device work, in pt_query_closest's order.  Returns 0 to go on, 1 refused, -1 nothing to do.
+static int nearest_prepare(pt_ctx* c, const char* fn, const float* points, size_t n, const void* out, const void* visits, bool with_visits, int* fmt)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (n == 0) return -1;
+    if (!points || !out || (with_visits && !visits)) return fail(c, f + "null argument");
+    if (n > 0x7FFFFFFFull) return fail(c, f + "too many points (2^31 - 1 per call)");
+    if (((uintptr_t)points & 15u) || ((uintptr_t)out & 15u) || ((uintptr_t)visits & 7u)) return fail(c, f + "the point and record arrays must be 16-byte aligned");
+    if (spans_overlap(points, n * 16u, out, n * sizeof(pt_nearest))) return fail(c, f + "the output overlaps the points");
+    if (with_visits && (spans_overlap(points, n * 16u, visits, n * 8u) || spans_overlap(out, n * sizeof(pt_nearest), visits, n * 8u)))
+        return fail(c, f + "the visit counts overlap another array");
+    return query_node_format(c, f, fmt);
+}
+
+PT_API int pt_query_nearest(pt_ctx* c, const float* points, size_t n, pt_nearest* out)
+{
+    int fmt = 0;
+    if (int rc = nearest_prepare(c, "pt_query_nearest", points, n, out, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_nearest");
+    CK(c, ptd::launch_query_nearest(fmt, device_scene(c), c->stack_entries, ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)points,
+                                    (uint32_t)n, (float4*)out, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_debug_nearest_visits(pt_ctx* c, const float* points, size_t n, pt_nearest* out, uint32_t* visits)
+{
+    int fmt = 0;
+    if (int rc = nearest_prepare(c, "pt_debug_nearest_visits", points, n, out, visits, true, &fmt)) return rc < 0 ? 0 : rc;
+    CK(c, ptd::launch_nearest_visits(fmt, device_scene(c), c->stack_entries, ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)points,
+                                     (uint32_t)n, (float4*)out, (uint2*)visits, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

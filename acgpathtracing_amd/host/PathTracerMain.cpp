@@ -16,6 +16,7 @@
 //              [--tonemap linear|reinhard|aces] [--exposure auto|<EV>] [--out-hdr file.pfm]
 //              [--until-error E [--until-permille P] [--error-floor F] [--error-out file.pfm]]
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
+//              [--nearest x,y,z[,radius] ...]
 //              [--ao K[,radius[,bias]] --ao-out file.pfm [--ao-frames n]]
 // --ao K[,radius[,bias]] with --ao-out: once the scene is set and before the first frame, the ambient occlusion of the view
 // (pt_render_features + pt_ao_image): K rays per pixel (1..256) and call over --ao-frames calls (default 1; call j has seed j and
@@ -27,6 +28,12 @@
 // {"pick": [x, y], "hit": true, "t": .., "prim": .., "material": "<newmtl name>", "position": [eye + t * dir], "normal": [..]}, on a
 // miss {"pick": [x, y], "hit": false}.  Floats are printed with nine digits: they read back as the same fp32 values.  A pixel
 // outside the image is refused with exit status 2.  The frames are the same with or without it.
+// --nearest x,y,z[,radius] (repeatable): once the scene is set and before the first frame, the closest surface point to (x, y, z) within
+// radius (no limit if not given), by pt_query_nearest in one call, one JSON line each: {"nearest": [x, y, z], "found": true,
+// "distance": .., "triangle": .., "material": "<newmtl name>", "point": [..], "u": .., "v": ..} (u, v the weights of the triangle's second
+// and third vertex at the point), {"nearest": [x, y, z], "found": false} if nothing lies within the radius.  Floats are printed with
+// nine digits.  A coordinate that is not finite or a radius that is negative or no number is refused with exit status 2.  The frames
+// are the same with or without it.
 // --bloom (with --tonemap or --exposure): the image the display transform shows goes through pt_bloom first.  threshold is in display
 // units, multiples of exposed white, and is divided by the exposure (and so are the default knee, half the threshold, and the
 // clamp, none); an automatic exposure is metered on the image without its glare and then applied as a manual one.  --out-hdr gets
@@ -619,6 +626,34 @@ static void pickPixels(PathTracerState& state, const TinyObjWrapper& obj, const 
     fflush(stdout);
 }
 
+// --nearest: every point in one call of pt_query_nearest; one JSON line per point
+static void nearestPoints(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<float4>& points)
+{
+    const size_t n = points.size();
+    void* d_points = nullptr; void* d_out = nullptr;
+    std::vector<pt_nearest> out(n);
+    std::string err;
+    if (pt_device_malloc(state.context, &d_points, n * 16) != 0 || pt_device_malloc(state.context, &d_out, n * sizeof(pt_nearest)) != 0 ||
+        pt_copy_to_device(state.context, d_points, points.data(), n * 16) != 0 ||
+        pt_query_nearest(state.context, (const float*)d_points, n, (pt_nearest*)d_out) != 0 ||
+        pt_copy_to_host(state.context, out.data(), d_out, n * sizeof(pt_nearest)) != 0)
+        err = pt_last_error(state.context);
+    if (d_points) pt_device_free(state.context, d_points);
+    if (d_out) pt_device_free(state.context, d_out);
+    if (!err.empty()) throw Exception("nearest: " + err);
+    const std::vector<std::string>& names = obj.getMaterialNames();
+    for (size_t i = 0; i < n; i++) {
+        const pt_nearest& r = out[i];
+        const float4& q = points[i];
+        if (r.prim == 0xFFFFFFFFu) { printf("{\"nearest\": [%.9g, %.9g, %.9g], \"found\": false}\n", q.x, q.y, q.z); continue; }
+        std::string name = r.material < names.size() ? names[r.material] : std::string();
+        for (size_t k = 0; k < name.size(); k++) if (name[k] == '"' || name[k] == '\\' || (unsigned char)name[k] < 0x20) name[k] = '_';
+        printf("{\"nearest\": [%.9g, %.9g, %.9g], \"found\": true, \"distance\": %.9g, \"triangle\": %u, \"material\": \"%s\", \"point\": [%.9g, %.9g, %.9g], \"u\": %.9g, \"v\": %.9g}\n",
+               q.x, q.y, q.z, r.distance, r.prim, name.c_str(), r.cx, r.cy, r.cz, r.u, r.v);
+    }
+    fflush(stdout);
+}
+
 // --ao: the default sample pattern (pathtracer.aoSamples restated: the same double operations, the same fp32 pull-in)
 static std::vector<float> aoSamples(int K)
 {
@@ -680,6 +715,7 @@ int main(int argc, char** argv)
     std::string objfilepath, out = "frame.png", keys, save_accum, restore_accum, history_out, history_in, move;
     std::vector<std::string> material_edits;
     std::vector<int2> picks;
+    std::vector<float4> nearest;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false, move_history = false, no_area_light = false;
     std::string env_path, tonemap, exposure_arg, out_hdr, error_out, ao_out;
@@ -767,6 +803,12 @@ int main(int argc, char** argv)
         else if (a == "--ao-out") ao_out = next();
         else if (a == "--ao-frames") { ao_frames = atoi(next()); if (ao_frames < 1 || ao_frames > 65536) { std::cerr << "--ao-frames takes 1 to 65536" << std::endl; return 2; } }
         else if (a == "--pick") { int2 px; if (sscanf(next(), "%d,%d", &px.x, &px.y) != 2) { std::cerr << "--pick x,y" << std::endl; return 2; } picks.push_back(px); }
+        else if (a == "--nearest") {
+            float4 q = make_float4(0.0f, 0.0f, 0.0f, INFINITY);
+            const int got = sscanf(next(), "%f,%f,%f,%f", &q.x, &q.y, &q.z, &q.w);
+            if (got < 3 || !std::isfinite(q.x) || !std::isfinite(q.y) || !std::isfinite(q.z) || !(q.w >= 0.0f)) { std::cerr << "--nearest x,y,z[,radius]: finite coordinates, a radius >= 0" << std::endl; return 2; }
+            nearest.push_back(q);
+        }
         else if (a == "--materials") {
             const std::string m = next();
             if (m == "reference") material_model = PT_MATERIALS_REFERENCE;
@@ -886,6 +928,7 @@ int main(int argc, char** argv)
         if (no_area_light) state.params.areaLight.emission = {0.0f, 0.0f, 0.0f};
         std::cout << "Launch Initialized" << std::endl;
         if (!picks.empty()) { std::cout.flush(); pickPixels(state, obj, picks); }
+        if (!nearest.empty()) { std::cout.flush(); nearestPoints(state, obj, nearest); }
         if (ao_samples > 0) ambientOcclusion(state, ao_samples, ao_radius, ao_bias, ao_frames, ao_out);
         HistoryFile history;
         if (!history_in.empty()) {              // refused before any frame is rendered

@@ -700,6 +700,110 @@ def queryRays(state, rays, any_hit=False):
     return {k: np.ascontiguousarray(out[k]) for k in HIT_DTYPE.names}
 
 
+# ------------------------------------------------------------------ closest point ----
+NEAREST_DTYPE = np.dtype([("distance", np.float32), ("prim", np.uint32), ("u", np.float32), ("v", np.float32), ("point", np.float32, 3), ("material", np.uint32)])      # pt_nearest
+assert NEAREST_DTYPE.itemsize == 32
+
+
+def _query_nearest_tensor(state, points):
+    import torch
+    if points.device.type != "cuda" or points.device.index != state._device:
+        raise PathTracerError("queryNearest: the points are on %s, the context is on cuda:%d" % (points.device, state._device))
+    if points.dtype != torch.float32:
+        raise PathTracerError("queryNearest: the points must be float32, got %s" % points.dtype)
+    if points.dim() != 2 or points.shape[1] != 4:
+        raise PathTracerError("queryNearest: expected an (n, 4) tensor {x, y, z, max_radius}, got shape %s" % (tuple(points.shape),))
+    if not points.is_contiguous():
+        raise PathTracerError("queryNearest: the points must be contiguous (nothing is copied)")
+    n = int(points.shape[0])
+    with torch.cuda.device(points.device):
+        out = torch.empty((n, 8), dtype=torch.float32, device=points.device)
+        torch.cuda.current_stream().synchronize()      # the points' producer and the allocation; the call below returns synchronised
+    _check(state.context, _native.hip().pt_query_nearest(state.context, points.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_nearest")
+    return {"distance": out[:, 0], "prim": out[:, 1].view(torch.int32), "u": out[:, 2], "v": out[:, 3], "point": out[:, 4:7], "material": out[:, 7].view(torch.int32)}
+
+
+def queryNearest(state, points, max_radius=float("inf")):
+    """The closest surface point of the scene on the GPU to each query point (include/acgpt.h pt_query_nearest).
+
+    A NumPy array (or anything np.asarray takes) of shape (n, 3), or (n, 4) with a search radius per point in the fourth column — (n, 3)
+    points all get max_radius —, goes to the device and the answer comes back: a dict of arrays distance (n,) float32 (-1 where nothing
+    lies within the radius), prim (n,) uint32 (the triangle's index in the scene's order, 0xFFFFFFFF), u, v (n,) the weights of v1 and
+    v2 at the closest point, point (n, 3) the closest point, material (n,) uint32.
+
+    A torch tensor must be (n, 4) float32 {x, y, z, max_radius}, contiguous and on the context's device; nothing is copied, its data_ptr()
+    goes straight in, and the answer is torch tensors on that device: views of one (n, 8) float32 tensor, prim and material as int32
+    (-1 on a miss).  torch's current stream is synchronised before the call, and the call returns synchronised."""
+    if _is_tensor(points):
+        return _query_nearest_tensor(state, points)
+    p = np.asarray(points)
+    if p.ndim != 2 or p.shape[1] not in (3, 4):
+        raise PathTracerError("queryNearest: expected an (n, 3) or (n, 4) array, got shape %s" % (p.shape,))
+    if p.dtype.kind not in "fiu":
+        raise PathTracerError("queryNearest: the points must be numbers, got %s" % p.dtype)
+    if p.shape[1] == 3:
+        radius = float(max_radius)
+        if not radius >= 0.0:
+            raise PathTracerError("queryNearest: max_radius must be non-negative, got %r" % (max_radius,))
+        q = np.empty((p.shape[0], 4), np.float32)
+        q[:, 0:3] = p
+        q[:, 3] = radius
+    else:
+        q = np.ascontiguousarray(p, np.float32)
+    n = q.shape[0]
+    out = np.zeros(n, NEAREST_DTYPE)
+    if n:
+        L = _native.hip()
+        bufs = _device_buffers(state, 2, out.nbytes)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], q.ctypes.data, q.nbytes), "copy to device")
+            _check(state.context, L.pt_query_nearest(state.context, bufs[0], n, bufs[1]), "pt_query_nearest")
+            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    return {k: np.ascontiguousarray(out[k]) for k in NEAREST_DTYPE.names}
+
+
+def distanceFieldPoints(resolution, lo, hi):
+    """Cell centres of an (nz, ny, nx) grid over the box [lo, hi], float32 (nz * ny * nx, 3), x fastest: centre i of an axis is
+    lo + (i + 0.5) * ((hi - lo) / n), computed in float64 and rounded once."""
+    try:
+        nz, ny, nx = (int(r) for r in resolution)
+    except (TypeError, ValueError):
+        raise PathTracerError("bakeDistanceField: resolution is (nz, ny, nx), got %r" % (resolution,))
+    if min(nz, ny, nx) < 1 or nz * ny * nx > 0x7FFFFFFF:
+        raise PathTracerError("bakeDistanceField: every side of the grid must be at least 1 and the grid at most 2^31 - 1 cells, got %r" % (resolution,))
+    lo, hi = np.asarray(lo, np.float64).reshape(-1), np.asarray(hi, np.float64).reshape(-1)
+    if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all()):
+        raise PathTracerError("bakeDistanceField: bounds must be finite (lo xyz, hi xyz) with hi >= lo, got %r, %r" % (lo.tolist(), hi.tolist()))
+    axes = [lo[k] + (np.arange(m) + 0.5) * ((hi[k] - lo[k]) / m) for k, m in ((0, nx), (1, ny), (2, nz))]
+    pts = np.empty((nz, ny, nx, 3), np.float32)
+    pts[..., 0] = axes[0][None, None, :]
+    pts[..., 1] = axes[1][None, :, None]
+    pts[..., 2] = axes[2][:, None, None]
+    return pts.reshape(-1, 3)
+
+
+def bakeDistanceField(state, resolution, bounds=None, max_radius=float("inf"), return_prims=False):
+    """The unsigned distance from the centre of every cell of an (nz, ny, nx) grid to the scene's surface (queryNearest on
+    distanceFieldPoints): float32 [nz, ny, nx], -1 where nothing lies within max_radius.  bounds: (lo xyz, hi xyz) of the grid, the
+    scene box if not given.  The points go to the device x fastest, so the 64 queries of a wave are neighbours.  return_prims: also the
+    closest triangle's index per cell, uint32 [nz, ny, nx] (0xFFFFFFFF where nothing is found)."""
+    if bounds is None:
+        info = getBvhInfo(state)
+        lo, hi = [float(x) for x in info.scene_lo], [float(x) for x in info.scene_hi]
+    else:
+        try:
+            lo, hi = bounds
+        except (TypeError, ValueError):
+            raise PathTracerError("bakeDistanceField: bounds is (lo xyz, hi xyz), got %r" % (bounds,))
+    pts = distanceFieldPoints(resolution, lo, hi)
+    got = queryNearest(state, pts, max_radius)
+    shape = tuple(int(r) for r in resolution)
+    dist = got["distance"].reshape(shape)
+    return (dist, got["prim"].reshape(shape)) if return_prims else dist
+
+
 # ------------------------------------------------------------------ ambient occlusion ----
 def aoSamples(K):
     """The default sample pattern of the ambient-occlusion calls: K points of a Vogel spiral on the unit disk, float32 (K, 2):

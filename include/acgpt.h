@@ -424,6 +424,45 @@ typedef struct { float t; uint32_t prim; float u, v; float nx, ny, nz; uint32_t 
 int pt_query_closest(pt_ctx* ctx, const float* rays, size_t n, pt_hit* hits);
 int pt_query_any(pt_ctx* ctx, const float* rays, size_t n, uint8_t* occluded);
 
+/* ---- closest-point queries on the device (opt-in; nothing above changes) ----------------------------------------------------------
+ * The other question a scene on the GPU answers beside ray casts: how far is a point from the surface, and where is the nearest surface
+ * point — clearance and collision checks, snapping and projection onto the mesh, distance-field baking, proximity shading, sensor
+ * models.  Points and results stay in DEVICE memory, 16-byte aligned.  The call enqueues on the context's stream and returns
+ * synchronised, acts on rank 0 of a pt_create_multi context, never writes the accumulation buffer, the frame buffer or pt_stats, and
+ * walks the node array the scene holds exactly as pt_query_closest does (pt_bvh_info.device_bytes does not change).  No atomics: two
+ * calls give the same bits.
+ *
+ *   points    n records of 4 floats {x, y, z, max_radius}
+ *   out       n records of 32 bytes (pt_nearest)
+ *   d2        the squared distance from the point q to a triangle, all fp32, every multiply, add and division on its own, evaluated
+ *             as written, no fused multiply-add (tests/nearest_ref.py is the NumPy statement, equal bit for bit).  With the vectors the
+ *             build stores for the triangle, ab = e1 = v1 - v0 and ac = e2 = v2 - v0 (one fp32 subtraction per component), the region
+ *             test of Ericson, Real-Time Collision Detection 5.1.5:
+ *               ap = q - v0;   d1 = dot(ab, ap);  d2_ = dot(ac, ap);     dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z
+ *               bp = ap - ab;  d3 = dot(ab, bp);  d4 = dot(ac, bp);
+ *               cp = ap - ac;  d5 = dot(ab, cp);  d6 = dot(ac, cp);
+ *               vc = d1 d4 - d3 d2_;  vb = d5 d2_ - d1 d6;  va = d3 d6 - d5 d4;  e43 = d4 - d3;  e56 = d5 - d6
+ *             the first region that holds, in this order, gives the weights (v, w) of v1 and v2:
+ *               vertex A  d1 <= 0 and d2_ <= 0                   (0, 0)
+ *               vertex B  d3 >= 0 and d4 <= d3                   (1, 0)
+ *               edge AB   vc <= 0 and d1 >= 0 and d3 <= 0        (t, 0),          t = d1 / (d1 - d3)
+ *               vertex C  d6 >= 0 and d5 <= d6                   (0, 1)
+ *               edge AC   vb <= 0 and d2_ >= 0 and d6 <= 0       (0, t),          t = d2_ / (d2_ - d6)
+ *               edge BC   va <= 0 and e43 >= 0 and e56 >= 0      (1 - t, t),      t = e43 / (e43 + e56)
+ *               face      otherwise                              (vb t, vc t),    t = 1 / ((va + vb) + vc)
+ *             then the closest point c = (v0 + ab v) + ac w per component, s = q - c, d2 = dot(s, s).  One IEEE division per triangle.
+ *   candidate a triangle with d2 <= max_radius * max_radius, the product taken in fp32; max_radius = +inf is allowed and its square
+ *             is +inf.  A NaN d2 (a degenerate triangle can give one) is no candidate.
+ *   answer    the candidate with the smallest d2; ties go to the lowest triangle index in the caller's index-buffer order
+ *   found     distance = sqrtf(d2) of the winner, one IEEE square root; prim its index; u, v the weights (v, w) above: the closest point
+ *             is (1 - u - v) v0 + u v1 + v v2; (cx, cy, cz) the point c as computed above; material the triangle's material id
+ *   a miss before any traversal: a non-finite coordinate, a NaN or negative max_radius, a scene without triangles
+ *   miss      {distance -1, prim 0xFFFFFFFF, u 0, v 0, c (0, 0, 0), material 0xFFFFFFFF}: pt_hit's pattern
+ * n == 0 is a no-op success.  Refused, with the context left usable: n > 0x7FFFFFFF, a null points or out pointer with n > 0, an array
+ * that is not 16-byte aligned, an output that overlaps the points, a context without a scene.                                         */
+typedef struct { float distance; uint32_t prim; float u, v; float cx, cy, cz; uint32_t material; } pt_nearest;   /* 32 bytes */
+int pt_query_nearest(pt_ctx* ctx, const float* points, size_t n, pt_nearest* out);
+
 /* ---- ambient occlusion traced on the device (opt-in; nothing above changes) -----------------------------------------------------
  * The share of the hemisphere over a surface point that is open within `radius`: K rays per point, generated, traced with
  * pt_query_any's walk and counted inside one kernel, so no ray reaches memory.  pt_ao_points takes the points from a device array

@@ -100,6 +100,9 @@ int pt_debug_environment(pt_ctx* ctx, int op, const float* in, size_t n, float* 
  *   op 0: {wo[3], alpha, ior, bsdf, u1, u2, u3} -> {wi[3], weight[3], pdf, lobe (0 ended, 1 reflection, 2 transmission)}
  *   op 1: {wo[3], wi[3], alpha, ior, bsdf} -> {f[3], pdf}.  HOST arrays. */
 int pt_debug_microfacet(pt_ctx* ctx, int op, const float* in, size_t n, float* out);
+/* pt_query_nearest (same arguments, same records, same refusals) from a kernel instantiation that also counts: visits[2 i] = inner
+ * nodes query i visited, visits[2 i + 1] = triangles it tested.  visits: DEVICE, 8-byte aligned, 2 n words.  tools/nearest_timing.py. */
+int pt_debug_nearest_visits(pt_ctx* ctx, const float* points, size_t n, pt_nearest* out, uint32_t* visits);
 /* Sorted (morton, triangle) pairs of the last build, HOST outputs of n_tris. */
 int pt_read_morton(pt_ctx* ctx, uint32_t* codes_sorted, uint32_t* prims_sorted);
 

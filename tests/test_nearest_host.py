@@ -1,0 +1,244 @@
+"""pt_query_nearest without a GPU: the NumPy statement of the record (tests/nearest_ref.py) on hand-checked points and against a
+float64 brute force, the tie rule, the points that are a miss before any traversal, the radius rule, the point sets' found and
+not-found shares on the Cornell fixtures, and the argument checks of queryNearest and bakeDistanceField that need no device."""
+import os
+
+import numpy as np
+import pytest
+
+import acgpathtracing_amd as pt
+from acgpathtracing_amd import _build, _native
+import nearest_ref as nr
+
+F = np.float32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# The largest |fp32 - float64| of the distance over _random_pairs() below, measured once on the CPU (the figure DESIGN.md section 24
+# quotes), and the bound the test holds the fp32 statement to: four times that.
+DIST_MEASURED = 1.15e-6
+DIST_BOUND = 4.0 * DIST_MEASURED
+
+TRI = (np.array([[0, 0, 0, 1], [4, 0, 0, 1], [0, 4, 0, 1]], np.float32), np.array([0, 1, 2], np.uint32))
+
+
+def _one(q, r=np.inf, verts=TRI[0], idx=TRI[1], mats=(0x05000007,)):
+    rec = nr.nearest_records(nr.with_radius(np.array([q], np.float32), r), verts, idx, np.array(mats, np.uint32))
+    return rec[0], rec.view(np.float32)[0]
+
+
+def test_hand_checked_points_of_one_triangle():
+    """A = (0, 0, 0), B = (4, 0, 0), C = (0, 4, 0); every value below is exact in fp32"""
+    cases = [
+        # q, distance, (u, v), closest point
+        ((1, 1, 2), 2.0, (0.25, 0.25), (1, 1, 0)),             # over the face
+        ((1, 2, -3), 3.0, (0.25, 0.5), (1, 2, 0)),             # under the face
+        ((2, -3, 0), 3.0, (0.5, 0.0), (2, 0, 0)),              # beside edge AB
+        ((-3, 1, 4), 5.0, (0.0, 0.25), (0, 1, 0)),             # beside edge AC, off the plane
+        ((4, 4, 0), float(np.sqrt(F(8.0))), (0.5, 0.5), (2, 2, 0)),      # beside edge BC
+        ((-3, -4, 0), 5.0, (0.0, 0.0), (0, 0, 0)),             # beyond A
+        ((7, -4, 0), 5.0, (1.0, 0.0), (4, 0, 0)),              # beyond B
+        ((-4, 7, 0), 5.0, (0.0, 1.0), (0, 4, 0)),              # beyond C
+        ((1, 1, 0), 0.0, (0.25, 0.25), (1, 1, 0)),             # on the triangle
+        ((2, 0, 0), 0.0, (0.5, 0.0), (2, 0, 0)),               # on edge AB
+        ((2, 2, 0), 0.0, (0.5, 0.5), (2, 2, 0)),               # on edge BC
+        ((0, 0, 0), 0.0, (0.0, 0.0), (0, 0, 0)),               # A itself
+        ((4, 0, 0), 0.0, (1.0, 0.0), (4, 0, 0)),               # B itself
+        ((0, 4, 0), 0.0, (0.0, 1.0), (0, 4, 0)),               # C itself
+    ]
+    for q, dist, uv, c in cases:
+        u32, f = _one(q)
+        assert f[0] == F(dist), (q, f[0])
+        assert u32[1] == 0 and u32[7] == 7, q                  # the material id without the flags above bit 24
+        assert (f[2], f[3]) == uv, (q, f[2], f[3])
+        assert tuple(f[4:7]) == c, (q, f[4:7])
+    assert pt.NEAREST_DTYPE.itemsize == 32 and [pt.NEAREST_DTYPE.fields[k][1] for k in pt.NEAREST_DTYPE.names] == [0, 4, 8, 12, 16, 28]
+    assert np.array_equal(nr.miss_records(1)[0], np.array([0xBF800000, 0xFFFFFFFF, 0, 0, 0, 0, 0, 0xFFFFFFFF], np.uint32))
+
+
+def _random_pairs(n=8192, seed=11):
+    """Random triangles of edge ~1 around points up to 10 from the origin (area at least 0.1), each with a point 0 .. 8 from a random
+    point of the triangle's neighbourhood or over its inside: every region of the test gets its share"""
+    rng = np.random.default_rng(seed)
+    centre = rng.uniform(-10.0, 10.0, (n, 3))
+    v = [(centre + rng.uniform(-1.0, 1.0, (n, 3))).astype(np.float32) for _ in range(3)]
+    away = rng.normal(size=(n, 3))
+    away /= np.sqrt((away * away).sum(axis=1, keepdims=True))
+    q = centre + rng.uniform(-1.5, 1.5, (n, 3)) + away * rng.uniform(0.0, 8.0, (n, 1)) * (rng.random((n, 1)) < 0.5)
+    # a third of the points over the triangle's inside instead, up to 8 off its plane on either side: the face region
+    b = rng.random((n, 2)); fold = b.sum(axis=1) > 1.0; b[fold] = 1.0 - b[fold]
+    e1, e2 = v[1].astype(np.float64) - v[0], v[2].astype(np.float64) - v[0]
+    unit = np.cross(e1, e2); unit /= np.maximum(np.linalg.norm(unit, axis=1, keepdims=True), 1e-30)
+    over = v[0] + b[:, 0:1] * e1 + b[:, 1:2] * e2 + unit * rng.uniform(-8.0, 8.0, (n, 1))
+    q = np.where(rng.random((n, 1)) < 1.0 / 3.0, over, q).astype(np.float32)
+    nrm = np.cross(v[1].astype(np.float64) - v[0], v[2].astype(np.float64) - v[0])
+    keep = np.linalg.norm(nrm, axis=1) >= 0.2
+    return q[keep], v[0][keep], v[1][keep], v[2][keep]
+
+
+def test_fp32_distance_against_float64():
+    q, v0, v1, v2 = _random_pairs()
+    assert q.shape[0] >= 4000
+    d2, v, w, c = nr.closest_on_triangle(q, v0, v1 - v0, v2 - v0)
+    assert d2.dtype == np.float32 and c.dtype == np.float32 and v.dtype == np.float32
+    dist = np.sqrt(d2)
+    dist64, c64 = nr.closest_f64(q, v0, v1, v2)
+    # every region is exercised: vertex, edge and face answers all occur
+    kinds = {"vertex": ((v == 0) | (v == 1)) & ((w == 0) | (w == 1)), "face": (v > 0) & (w > 0) & (v + w < 1)}
+    kinds["edge"] = ~kinds["vertex"] & ~kinds["face"]
+    assert all(k.mean() > 0.1 for k in kinds.values()), {k: m.mean() for k, m in kinds.items()}
+    # float64 is the same algorithm; an independent check of it: no sampled point of the triangle is closer
+    rng = np.random.default_rng(5)
+    b = rng.random((64, 2)); fold = b.sum(axis=1) > 1; b[fold] = 1 - b[fold]
+    a64, e1, e2 = v0.astype(np.float64), v1.astype(np.float64) - v0, v2.astype(np.float64) - v0
+    for bu, bv in b:
+        s = a64 + bu * e1 + bv * e2 - q
+        assert (np.sqrt((s * s).sum(axis=1)) >= dist64 - 1e-12).all()
+    worst = np.abs(dist - dist64).max()
+    print("largest |fp32 - float64| distance deviation over %d pairs: %.3e (bound %.3e)" % (q.shape[0], worst, DIST_BOUND))
+    assert worst <= DIST_BOUND
+    assert worst >= DIST_MEASURED / 4.0          # the figure quoted is this set's, not a stale one
+    assert np.abs(c - c64).max() <= 1e-3         # the point moves along the surface with the weights; no measured bound, a mix-up is O(1)
+
+
+def test_ties_go_to_the_lowest_triangle_index():
+    """Two triangles sharing the edge (0,0,0)-(0,4,0), a point over the edge: d2 to both is the same bits.  Whichever order the index
+    buffer lists them in, triangle 0 wins."""
+    verts = np.array([[0, 0, 0, 1], [4, 0, 0, 1], [0, 4, 0, 1], [-4, 0, 0, 1]], np.float32)
+    q = np.array([[0.0, 1.0, 3.0]], np.float32)
+    for idx in (np.array([0, 1, 2, 0, 2, 3], np.uint32), np.array([0, 2, 3, 0, 1, 2], np.uint32)):
+        v0, e1, e2 = nr.records_of_scene(verts, idx)
+        d2 = nr.closest_on_triangle(q[:, None], v0[None], e1[None], e2[None])[0][0]
+        assert d2[0].view(np.uint32) == d2[1].view(np.uint32) and d2[0] == F(9.0)
+        rec = nr.nearest_records(nr.with_radius(q, np.inf), verts, idx, np.array([3, 4], np.uint32))
+        assert rec[0, 1] == 0 and rec[0, 7] == 3 and rec.view(np.float32)[0, 0] == F(3.0)
+
+
+def test_points_that_miss_before_any_traversal():
+    good = np.array([1.0, 1.0, 2.0, 50.0], np.float32)
+    bad, why = nr.bad_points(good)
+    assert bad.shape[0] == 9 + 4
+    ok = nr.searchable(bad)
+    assert not ok.any(), [w for w, k in zip(why, ok) if k]
+    rec = nr.nearest_records(bad, TRI[0], TRI[1], np.zeros(1, np.uint32))
+    assert np.array_equal(rec, nr.miss_records(bad.shape[0]))
+    allowed = np.array([good, good, good], np.float32)
+    allowed[1, 3] = np.inf
+    allowed[2, 3] = -0.0                 # a radius of zero, whatever its sign bit
+    assert nr.searchable(allowed).all()
+    rec = nr.nearest_records(allowed, TRI[0], TRI[1], np.zeros(1, np.uint32))
+    assert rec[0, 1] == 0 and rec[1, 1] == 0 and rec[2, 1] == 0xFFFFFFFF
+    # a scene without triangles: all misses
+    rec = nr.nearest_records(allowed, TRI[0], np.zeros(0, np.uint32), np.zeros(0, np.uint32))
+    assert np.array_equal(rec, nr.miss_records(3))
+
+
+def test_radius_rule():
+    q = (1, 1, 2)                                    # distance 2, d2 = 4
+    assert _one(q, 2.0)[0][1] == 0                   # d2 <= r * r: the rim counts
+    assert _one(q, np.nextafter(F(2.0), F(0.0)))[0][1] == 0xFFFFFFFF
+    assert _one(q, np.inf)[1][0] == F(2.0)
+    assert _one(q, 1e30)[1][0] == F(2.0)             # r * r overflows to +inf: everything is a candidate
+    assert _one((1, 1, 0), 0.0)[1][0] == F(0.0) and _one((1, 1, 0), 0.0)[0][1] == 0          # r = 0 on a surface point
+    assert _one((1, 1, 1e-3), 0.0)[0][1] == 0xFFFFFFFF
+    # the radius picks among candidates, it does not change the winner
+    verts = np.array([[0, 0, 0, 1], [4, 0, 0, 1], [0, 4, 0, 1], [0, 0, 9, 1], [4, 0, 9, 1], [0, 4, 9, 1]], np.float32)
+    idx = np.arange(6, dtype=np.uint32)
+    for r, prim in ((np.inf, 0), (8.0, 0), (2.0, 0), (1.5, 0xFFFFFFFF)):
+        assert _one((1, 1, 2), r, verts, idx, (0, 1))[0][1] == prim
+    assert _one((1, 1, 6), 3.5, verts, idx, (0, 1))[0][1] == 1
+
+
+@pytest.fixture(scope="module")
+def cornell_sets():
+    """scene -> name -> (points, records at +inf, records at the set's finite radius): computed once, shared, never written"""
+    out = {}
+    for scene in ("cornell_box.obj", "cornell_box_diffuse.obj"):
+        obj = pt.TinyObjWrapper(os.path.join(pt.SCENES, scene))
+        cam = pt.initCamera()
+        cam.setAspectRatio(np.float32(97) / np.float32(61))
+        camera = (cam.eye(),) + tuple(cam.UVWFrame())
+        verts, idx, mats = obj.getVerticesFloat(), obj.getIndexBuffer(), obj.getMaterialIndices()
+        out[scene] = {}
+        for name in nr.POINT_SETS:
+            pts = nr.point_set(name, verts, idx, camera)
+            rec = [nr.nearest_records(nr.with_radius(pts, r), verts, idx, mats) for r in (np.inf, nr.set_radius(name, verts, idx))]
+            for a in [pts] + rec:
+                a.setflags(write=False)
+            out[scene][name] = (pts, rec[0], rec[1])
+    return out
+
+
+@pytest.mark.parametrize("scene", ["cornell_box.obj", "cornell_box_diffuse.obj"])
+def test_point_sets_find_and_miss_on_the_reference(cornell_sets, scene):
+    """The shares the GPU tests rely on, by the brute force alone: with each set's finite radius at least a quarter of its points find
+    something and at least a tenth find nothing, and the winners are at least eight different triangles; without a radius every
+    point finds something."""
+    obj = pt.TinyObjWrapper(os.path.join(pt.SCENES, scene))
+    lo, hi = nr.scene_box(obj.getVerticesFloat(), obj.getIndexBuffer())
+    for name in nr.POINT_SETS:
+        pts, rec_inf, rec_r = cornell_sets[scene][name]
+        assert pts.shape == (nr.SET_SIZE, 3) and pts.dtype == np.float32 and np.isfinite(pts).all()
+        assert (rec_inf[:, 1] != 0xFFFFFFFF).all(), name
+        found = rec_r[:, 1] != 0xFFFFFFFF
+        print("%s %s: %.3f found within the finite radius, %d distinct winners" % (scene, name, found.mean(), np.unique(rec_r[found, 1]).size))
+        assert found.mean() >= 0.25 and (~found).mean() >= 0.10, (name, found.mean())
+        assert np.unique(rec_r[found, 1]).size >= 8 and np.unique(rec_inf[:, 1]).size >= 8, name
+        # where both find something it is the same record: the radius only decides whether
+        assert np.array_equal(rec_r[found], rec_inf[found]), name
+        f = rec_inf.view(np.float32)
+        assert (f[:, 2] >= 0).all() and (f[:, 3] >= 0).all() and (f[:, 2] + f[:, 3] <= 1.0 + 1e-6).all()
+        if name == "surface":           # on the surface or within rounding of it, or far outside (a ray that hit nothing)
+            d = f[:, 0]
+            assert ((d <= 1e-3) | (d > 100.0)).all() and (d <= 1e-3).mean() >= 0.5
+        if name == "shell":
+            diag = float(np.sqrt(((hi - lo) ** 2).sum()))
+            assert (f[:, 0] > 8.5 * diag).all()
+        if name == "wall_planes":
+            on_face = ((pts == lo) | (pts == hi)).any(axis=1)
+            assert on_face.all() and (f[:, 0] == 0).mean() >= 0.1 and ((pts < lo) | (pts > hi)).any(axis=1).mean() >= 0.25
+
+
+def test_build_lists_and_abi():
+    assert "nearest.hip" in _build.HIP_SOURCES and "nearest.h" in _build.HIP_HEADERS
+    for name in ("nearest.hip", "nearest.h", "capi_query.hip"):
+        assert name not in _build.KERNEL_SOURCES            # pt_kernel_source_hash() does not move
+    assert "pt_query_nearest" in _native.ABI_SYMBOLS and "pt_debug_nearest_visits" in _native.TEST_SYMBOLS
+    assert _native.ABI_VERSION == 4
+    hdr = open(os.path.join(ROOT, "include", "acgpt.h")).read()
+    assert "int pt_query_nearest(pt_ctx* ctx, const float* points, size_t n, pt_nearest* out);" in hdr
+
+
+def test_querynearest_argument_checks_need_no_device():
+    state = pt.PathTracerState()              # no context: every refusal below comes before the library is touched
+    for bad in (np.zeros((4, 5), np.float32), np.zeros(4, np.float32), np.zeros((2, 4, 1), np.float32), [[1, 2]]):
+        with pytest.raises(pt.PathTracerError, match="expected an"):
+            pt.queryNearest(state, bad)
+    with pytest.raises(pt.PathTracerError, match="numbers"):
+        pt.queryNearest(state, np.zeros((2, 3), np.complex64))
+    for bad in (-1.0, float("nan")):
+        with pytest.raises(pt.PathTracerError, match="max_radius"):
+            pt.queryNearest(state, np.zeros((2, 3), np.float32), bad)
+    empty = pt.queryNearest(state, np.zeros((0, 3), np.float32))
+    assert sorted(empty) == ["distance", "material", "point", "prim", "u", "v"]
+    assert empty["distance"].shape == (0,) and empty["point"].shape == (0, 3) and empty["prim"].dtype == np.uint32
+    assert pt.queryNearest(state, np.zeros((0, 4), np.float32), 2.0)["u"].shape == (0,)
+    torch = pytest.importorskip("torch")
+    with pytest.raises(pt.PathTracerError, match="the context is on"):
+        pt.queryNearest(state, torch.zeros((4, 4), dtype=torch.float32))
+
+
+def test_distance_field_grid_order_and_bounds():
+    pts = pt.distanceFieldPoints((2, 3, 4), (0.0, 10.0, 100.0), (4.0, 13.0, 102.0))
+    assert pts.shape == (24, 3) and pts.dtype == np.float32
+    g = pts.reshape(2, 3, 4, 3)
+    assert np.array_equal(g[0, 0, :, 0], [0.5, 1.5, 2.5, 3.5]) and np.array_equal(g[0, :, 0, 1], [10.5, 11.5, 12.5]) and np.array_equal(g[:, 0, 0, 2], [100.5, 101.5])
+    assert np.array_equal(pts[1] - pts[0], [1, 0, 0]) and np.array_equal(pts[4] - pts[0], [0, 1, 0]) and np.array_equal(pts[12] - pts[0], [0, 0, 1])      # x fastest
+    one = pt.distanceFieldPoints((1, 1, 1), (2, 2, 2), (2, 2, 2))          # a box of no extent is a point
+    assert np.array_equal(one, [[2, 2, 2]])
+    state = pt.PathTracerState()
+    for res in ((0, 4, 4), (4, 4), 7, (4, -1, 4), (2048, 2048, 2048)):
+        with pytest.raises(pt.PathTracerError, match="resolution|grid"):
+            pt.bakeDistanceField(state, res, bounds=((0, 0, 0), (1, 1, 1)))
+    for bounds in (((0, 0, 0), (1, 1, -1)), ((0, 0), (1, 1)), ((0, 0, 0), (1, 1, np.inf)), ((0, 0, np.nan), (1, 1, 1)), 5):
+        with pytest.raises(pt.PathTracerError, match="bounds"):
+            pt.bakeDistanceField(state, (2, 2, 2), bounds=bounds)
