@@ -405,7 +405,9 @@ int pt_trace_any(pt_ctx* ctx, const float* rays, size_t n, uint8_t* hit_out);
  *   same hits t and prim equal pt_trace_closest's, occluded equals pt_trace_any's, on every ray, as bits.
  *   nodes     the rays walk the node array the scene holds — the fp16 centre / half-extent nodes of a default scene, else the fp32
  *             nodes: pt_render_features' choice —, so pt_bvh_info.device_bytes is the same before and after a call (except under a
- *             variant forced onto another format by pt_set_tuning, which brings the fp32 nodes back as pt_trace_closest does).
+ *             variant forced onto another format by pt_set_tuning, which brings the fp32 nodes back as pt_trace_closest does: the first
+ *             call adds 64 B per node, later calls nothing; pt_update_vertices releases them and the next call brings them again).
+ *   empty     a scene without triangles (pt_set_scene with n_tris = 0) is a scene: every ray gets the miss record and occluded 0.
  *   a miss before any traversal: a non-finite origin or direction component, a NaN tmin or tmax, !(tmax > tmin), a scene without
  *             triangles.  (A zero direction needs no rule of its own: the triangle test rejects a zero determinant.)
  *   miss      {t -1, prim 0xFFFFFFFF, u 0, v 0, n (0, 0, 0), material 0xFFFFFFFF}; occluded 0
@@ -429,8 +431,10 @@ int pt_query_any(pt_ctx* ctx, const float* rays, size_t n, uint8_t* occluded);
  * point — clearance and collision checks, snapping and projection onto the mesh, distance-field baking, proximity shading, sensor
  * models.  Points and results stay in DEVICE memory, 16-byte aligned.  The call enqueues on the context's stream and returns
  * synchronised, acts on rank 0 of a pt_create_multi context, never writes the accumulation buffer, the frame buffer or pt_stats, and
- * walks the node array the scene holds exactly as pt_query_closest does (pt_bvh_info.device_bytes does not change).  No atomics: two
- * calls give the same bits.
+ * walks the node array the scene holds exactly as pt_query_closest does (pt_bvh_info.device_bytes does not change, except under a
+ * variant forced by pt_set_tuning onto a format the queries do not walk: there the first call brings the fp32 nodes, 64 B per node,
+ * which stay until the next pt_set_scene or pt_update_vertices).  No atomics: two calls give the same bits.  A scene without triangles
+ * (pt_set_scene with n_tris = 0) answers every point with the miss record, at max_radius = +inf too.
  *
  *   points    n records of 4 floats {x, y, z, max_radius}
  *   out       n records of 32 bytes (pt_nearest)
@@ -469,7 +473,9 @@ int pt_query_nearest(pt_ctx* ctx, const float* points, size_t n, pt_nearest* out
  * (baking: vertices, texels, probes), pt_ao_image from pt_render_features' second output (an AO pass of the current view).  Both
  * enqueue on the context's stream and return synchronised, act on rank 0 of a pt_create_multi context, never write the accumulation
  * buffer, the frame buffer or pt_stats, and walk the node array the scene holds exactly as pt_query_any does
- * (pt_bvh_info.device_bytes does not change).  No atomics: two calls give the same bits.
+ * (pt_bvh_info.device_bytes does not change, with pt_query_any's exception: a variant forced onto a format the queries do not walk gets
+ * the fp32 nodes on the first call).  No atomics: two calls give the same bits.  On a scene without triangles (pt_set_scene with
+ * n_tris = 0) no ray is occluded: visible counts every sample, ao is samples / total_samples.
  *
  *   points        DEVICE, 16-byte aligned, n records of two float4: {P.xyz, unused} {N.xyz, unused}.  N is a unit normal as the caller
  *                 has it; it is not renormalised.
