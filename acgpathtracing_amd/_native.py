@@ -143,6 +143,7 @@ assert C.sizeof(ConvergenceParams) == 16 and C.sizeof(ConvergenceInfo) == 32 + 4
 assert C.sizeof(FireflyParams) == 16 and C.sizeof(FireflyInfo) == 40
 assert C.sizeof(BloomParams) == 24 and C.sizeof(BloomInfo) == 40
 assert C.sizeof(AoParams) == 32
+QUERY_MULTI_MAX = 8                                                # PT_QUERY_MULTI_MAX
 BLOOM_MAX_LEVELS = 8                                               # pt_bloom_params.levels
 
 # every symbol include/acgpt.h declares (the drop-in boundary) ...
@@ -150,7 +151,7 @@ ABI_SYMBOLS = [
     "pt_create", "pt_create_multi", "pt_device_count", "pt_destroy", "pt_last_error", "pt_set_scene", "pt_set_build_mode", "pt_scene_handle", "pt_get_bvh_info",
     "pt_launch", "pt_launch_frames", "pt_resolve_framebuffer", "pt_set_partition", "pt_set_sample_chunks", "pt_set_light_mode", "pt_set_math_mode", "pt_set_scratch_limit", "pt_set_tuning",
     "pt_variant_name", "pt_variant_kernel", "pt_kernel_source_hash", "pt_set_stream", "pt_get_stats",
-    "pt_trace_closest", "pt_trace_any", "pt_query_closest", "pt_query_any", "pt_query_nearest", "pt_ao_points", "pt_ao_image", "pt_render_features", "pt_denoise", "pt_temporal_blend", "pt_temporal_blend_motion", "pt_update_vertices", "pt_update_materials", "pt_set_environment",
+    "pt_trace_closest", "pt_trace_any", "pt_query_closest", "pt_query_any", "pt_query_multi", "pt_query_nearest", "pt_ao_points", "pt_ao_image", "pt_render_features", "pt_denoise", "pt_temporal_blend", "pt_temporal_blend_motion", "pt_update_vertices", "pt_update_materials", "pt_set_environment",
     "pt_set_material_model", "pt_display_transform", "pt_convergence_update", "pt_firefly_filter", "pt_bloom",
     "pt_device_malloc", "pt_device_free", "pt_device_memset", "pt_copy_to_host", "pt_copy_to_device",
     "pt_host_malloc_mapped", "pt_host_free_mapped", "pt_abi_version",
@@ -235,6 +236,7 @@ def hip():
     L.pt_trace_any.argtypes = [vp, vp, sz, vp]; L.pt_trace_any.restype = C.c_int
     L.pt_query_closest.argtypes = [vp, vp, sz, vp]; L.pt_query_closest.restype = C.c_int
     L.pt_query_any.argtypes = [vp, vp, sz, vp]; L.pt_query_any.restype = C.c_int
+    L.pt_query_multi.argtypes = [vp, vp, sz, C.c_uint32, vp, vp]; L.pt_query_multi.restype = C.c_int
     L.pt_query_nearest.argtypes = [vp, vp, sz, vp]; L.pt_query_nearest.restype = C.c_int
     L.pt_debug_nearest_visits.argtypes = [vp, vp, sz, vp, vp]; L.pt_debug_nearest_visits.restype = C.c_int
     L.pt_ao_points.argtypes = [vp, vp, sz, vp, C.POINTER(AoParams), vp, vp]; L.pt_ao_points.restype = C.c_int

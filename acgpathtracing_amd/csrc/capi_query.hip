@@ -1,12 +1,13 @@
 // capi_query.hip — the entry points of include/acgpt.h that answer queries in device memory: pt_query_closest, pt_query_any, the
-// ambient-occlusion stage on top of them: pt_ao_points, pt_ao_image, and the closest-point query pt_query_nearest (with its counting
-// twin of include/acgpt_test.h).
-// Host code only; the kernels are in query.hip, ao.hip and nearest.hip.  The context and what the units share: context.h.
+// ordered multi-hit query pt_query_multi, the ambient-occlusion stage on top of them: pt_ao_points, pt_ao_image, and the
+// closest-point query pt_query_nearest (with its counting twin of include/acgpt_test.h).
+// Host code only; the kernels are in query.hip, multihit.hip, ao.hip and nearest.hip.  The context and what the units share: context.h.
 #include <cmath>
 
 #include "../../include/acgpt_test.h"
 #include "context.h"
 #include "ao.h"
+#include "multihit.h"
 #include "nearest.h"
 #include "query.h"
 
@@ -57,6 +58,33 @@ PT_API int pt_query_any(pt_ctx* c, const float* rays, size_t n, uint8_t* occlude
     if (int rc = query_prepare(c, "pt_query_any", rays, n, occluded, 1, false, &fmt)) return rc < 0 ? 0 : rc;
     Range range("pt_query_any");
     CK(c, ptd::launch_query_any(fmt, device_scene(c), c->stack_entries, (const float4*)rays, (uint32_t)n, occluded, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- the first hits in order, and their number -----------------------------------------------------------------------------------
+static_assert(PT_QUERY_MULTI_MAX == ptd::kMultiMaxHits, "PT_QUERY_MULTI_MAX is the size of the kernel's largest list");
+
+PT_API int pt_query_multi(pt_ctx* c, const float* rays, size_t n, uint32_t max_hits, pt_hit* hits, uint32_t* counts)
+{
+    const std::string f = "pt_query_multi: ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (n == 0) return 0;
+    if (max_hits > PT_QUERY_MULTI_MAX) return fail(c, f + "max_hits must be at most " + std::to_string(PT_QUERY_MULTI_MAX));
+    if ((max_hits != 0u) != (hits != nullptr)) return fail(c, f + "hits goes with max_hits: both or neither");
+    if (!hits && !counts) return fail(c, f + "nothing to write (hits and counts are both null)");
+    if (!rays) return fail(c, f + "null argument");
+    if (n > 0x7FFFFFFFull) return fail(c, f + "too many rays (2^31 - 1 per call)");
+    if (((uintptr_t)rays & 15u) || ((uintptr_t)hits & 15u) || ((uintptr_t)counts & 3u))
+        return fail(c, f + "the ray and hit arrays must be 16-byte aligned, the counts 4-byte aligned");
+    const size_t hit_bytes = n * (size_t)max_hits * sizeof(pt_hit);      // n < 2^31, max_hits <= 8: below 2^39
+    if (hits && spans_overlap(rays, n * 32u, hits, hit_bytes)) return fail(c, f + "hits overlaps the rays");
+    if (counts && spans_overlap(rays, n * 32u, counts, n * 4u)) return fail(c, f + "counts overlaps the rays");
+    if (hits && counts && spans_overlap(hits, hit_bytes, counts, n * 4u)) return fail(c, f + "counts overlaps hits");
+    int fmt = 0;
+    if (int rc = query_node_format(c, f, &fmt)) return rc;
+    Range range("pt_query_multi");
+    CK(c, ptd::launch_query_multi(fmt, device_scene(c), c->stack_entries, (const float4*)rays, (uint32_t)n, max_hits, (float4*)hits, counts, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -16,7 +16,7 @@
 //              [--tonemap linear|reinhard|aces] [--exposure auto|<EV>] [--out-hdr file.pfm]
 //              [--until-error E [--until-permille P] [--error-floor F] [--error-out file.pfm]]
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
-//              [--nearest x,y,z[,radius] ...]
+//              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...]
 //              [--ao K[,radius[,bias]] --ao-out file.pfm [--ao-frames n]]
 // --ao K[,radius[,bias]] with --ao-out: once the scene is set and before the first frame, the ambient occlusion of the view
 // (pt_render_features + pt_ao_image): K rays per pixel (1..256) and call over --ao-frames calls (default 1; call j has seed j and
@@ -28,6 +28,10 @@
 // {"pick": [x, y], "hit": true, "t": .., "prim": .., "material": "<newmtl name>", "position": [eye + t * dir], "normal": [..]}, on a
 // miss {"pick": [x, y], "hit": false}.  Floats are printed with nine digits: they read back as the same fp32 values.  A pixel
 // outside the image is refused with exit status 2.  The frames are the same with or without it.
+// --pick-all x,y[,k] (repeatable): --pick's camera ray, and everything it goes through (pt_query_multi with counts, one call): one JSON
+// line each, {"pick_all": [x, y], "count": <triangles the ray crosses inside the interval>, "hits": [<the first k of them in order of
+// (t, prim), k = 1..8, default 4, each with --pick's fields t, prim, material, position, normal>]}.  A pixel outside the image or a k
+// outside 1..8 is refused with exit status 2.  The frames are the same with or without it.
 // --nearest x,y,z[,radius] (repeatable): once the scene is set and before the first frame, the closest surface point to (x, y, z) within
 // radius (no limit if not given), by pt_query_nearest in one call, one JSON line each: {"nearest": [x, y, z], "found": true,
 // "distance": .., "triangle": .., "material": "<newmtl name>", "point": [..], "u": .., "v": ..} (u, v the weights of the triangle's second
@@ -626,6 +630,57 @@ static void pickPixels(PathTracerState& state, const TinyObjWrapper& obj, const 
     fflush(stdout);
 }
 
+// --pick-all: --pick's rays through pt_query_multi in one call, at the largest k asked for; one JSON line per pixel with its own k
+struct PickAll { int x, y, k; };
+static void pickAllPixels(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<PickAll>& picks)
+{
+    const pt_params& p = state.params;
+    const size_t n = picks.size();
+    uint32_t kmax = 1;
+    std::vector<float> rays(n * 8);
+    const float3 eye = make_float3(p.cameraEye.x, p.cameraEye.y, p.cameraEye.z);
+    const float3 U = make_float3(p.cameraU.x, p.cameraU.y, p.cameraU.z), V = make_float3(p.cameraV.x, p.cameraV.y, p.cameraV.z),
+                 W = make_float3(p.cameraW.x, p.cameraW.y, p.cameraW.z);
+    for (size_t i = 0; i < n; i++) {
+        const float dx = 2.0f * (((float)picks[i].x + 0.5f) / (float)p.width) - 1.0f;
+        const float dy = 2.0f * (((float)picks[i].y + 0.5f) / (float)p.height) - 1.0f;
+        const float3 dir = normalize(dx * U + dy * V + W);
+        const float r[8] = {eye.x, eye.y, eye.z, dir.x, dir.y, dir.z, 0.01f, 1e16f};      // pickPixels' ray
+        memcpy(&rays[8 * i], r, sizeof(r));
+        if ((uint32_t)picks[i].k > kmax) kmax = (uint32_t)picks[i].k;
+    }
+    void* d_rays = nullptr; void* d_hits = nullptr; void* d_counts = nullptr;
+    std::vector<pt_hit> hits(n * kmax);
+    std::vector<uint32_t> counts(n);
+    std::string err;
+    if (pt_device_malloc(state.context, &d_rays, n * 32) != 0 || pt_device_malloc(state.context, &d_hits, hits.size() * sizeof(pt_hit)) != 0 ||
+        pt_device_malloc(state.context, &d_counts, n * 4) != 0 ||
+        pt_copy_to_device(state.context, d_rays, rays.data(), n * 32) != 0 ||
+        pt_query_multi(state.context, (const float*)d_rays, n, kmax, (pt_hit*)d_hits, (uint32_t*)d_counts) != 0 ||
+        pt_copy_to_host(state.context, hits.data(), d_hits, hits.size() * sizeof(pt_hit)) != 0 ||
+        pt_copy_to_host(state.context, counts.data(), d_counts, n * 4) != 0)
+        err = pt_last_error(state.context);
+    if (d_rays) pt_device_free(state.context, d_rays);
+    if (d_hits) pt_device_free(state.context, d_hits);
+    if (d_counts) pt_device_free(state.context, d_counts);
+    if (!err.empty()) throw Exception("pick-all: " + err);
+    const std::vector<std::string>& names = obj.getMaterialNames();
+    for (size_t i = 0; i < n; i++) {
+        const float* r = &rays[8 * i];
+        printf("{\"pick_all\": [%d, %d], \"count\": %u, \"hits\": [", picks[i].x, picks[i].y, counts[i]);
+        for (int j = 0; j < picks[i].k; j++) {
+            const pt_hit& h = hits[i * kmax + (size_t)j];
+            if (h.prim == 0xFFFFFFFFu) break;
+            std::string name = h.material < names.size() ? names[h.material] : std::string();
+            for (size_t k = 0; k < name.size(); k++) if (name[k] == '"' || name[k] == '\\' || (unsigned char)name[k] < 0x20) name[k] = '_';
+            printf("%s{\"t\": %.9g, \"prim\": %u, \"material\": \"%s\", \"position\": [%.9g, %.9g, %.9g], \"normal\": [%.9g, %.9g, %.9g]}", j ? ", " : "",
+                   h.t, h.prim, name.c_str(), r[0] + h.t * r[3], r[1] + h.t * r[4], r[2] + h.t * r[5], h.nx, h.ny, h.nz);
+        }
+        printf("]}\n");
+    }
+    fflush(stdout);
+}
+
 // --nearest: every point in one call of pt_query_nearest; one JSON line per point
 static void nearestPoints(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<float4>& points)
 {
@@ -715,6 +770,7 @@ int main(int argc, char** argv)
     std::string objfilepath, out = "frame.png", keys, save_accum, restore_accum, history_out, history_in, move;
     std::vector<std::string> material_edits;
     std::vector<int2> picks;
+    std::vector<PickAll> pickAlls;
     std::vector<float4> nearest;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false, move_history = false, no_area_light = false;
@@ -802,6 +858,12 @@ int main(int argc, char** argv)
         }
         else if (a == "--ao-out") ao_out = next();
         else if (a == "--ao-frames") { ao_frames = atoi(next()); if (ao_frames < 1 || ao_frames > 65536) { std::cerr << "--ao-frames takes 1 to 65536" << std::endl; return 2; } }
+        else if (a == "--pick-all") {
+            PickAll pa; pa.k = 4;
+            const int got = sscanf(next(), "%d,%d,%d", &pa.x, &pa.y, &pa.k);
+            if (got < 2 || pa.k < 1 || pa.k > PT_QUERY_MULTI_MAX) { std::cerr << "--pick-all x,y[,k] with k = 1.." << PT_QUERY_MULTI_MAX << std::endl; return 2; }
+            pickAlls.push_back(pa);
+        }
         else if (a == "--pick") { int2 px; if (sscanf(next(), "%d,%d", &px.x, &px.y) != 2) { std::cerr << "--pick x,y" << std::endl; return 2; } picks.push_back(px); }
         else if (a == "--nearest") {
             float4 q = make_float4(0.0f, 0.0f, 0.0f, INFINITY);
@@ -836,6 +898,8 @@ int main(int argc, char** argv)
         }
     }
     if (use_bloom && !display) { std::cerr << "--bloom needs --tonemap or --exposure" << std::endl; return 2; }
+    for (const PickAll& px : pickAlls)
+        if (px.x < 0 || px.y < 0 || px.x >= width || px.y >= height) { std::cerr << "--pick-all: pixel " << px.x << "," << px.y << " is outside the " << width << " x " << height << " image" << std::endl; return 2; }
     for (const int2& px : picks)
         if (px.x < 0 || px.y < 0 || px.x >= width || px.y >= height) { std::cerr << "--pick: pixel " << px.x << "," << px.y << " is outside the " << width << " x " << height << " image" << std::endl; return 2; }
     if ((ao_samples > 0) != !ao_out.empty()) { std::cerr << "--ao and --ao-out go together" << std::endl; return 2; }
@@ -928,6 +992,7 @@ int main(int argc, char** argv)
         if (no_area_light) state.params.areaLight.emission = {0.0f, 0.0f, 0.0f};
         std::cout << "Launch Initialized" << std::endl;
         if (!picks.empty()) { std::cout.flush(); pickPixels(state, obj, picks); }
+        if (!pickAlls.empty()) { std::cout.flush(); pickAllPixels(state, obj, pickAlls); }
         if (!nearest.empty()) { std::cout.flush(); nearestPoints(state, obj, nearest); }
         if (ao_samples > 0) ambientOcclusion(state, ao_samples, ao_radius, ao_bias, ao_frames, ao_out);
         HistoryFile history;

@@ -700,6 +700,142 @@ def queryRays(state, rays, any_hit=False):
     return {k: np.ascontiguousarray(out[k]) for k in HIT_DTYPE.names}
 
 
+# ------------------------------------------------------------------ the first hits in order ----
+MULTI_KEYS = ("t", "prim", "u", "v", "normal", "material")
+
+
+def _multi_args(what, max_hits, counts):
+    try:
+        k = int(max_hits)
+    except (TypeError, ValueError):
+        raise PathTracerError("%s: max_hits is a number 0..%d, got %r" % (what, _native.QUERY_MULTI_MAX, max_hits))
+    if k != max_hits or k < 0 or k > _native.QUERY_MULTI_MAX:
+        raise PathTracerError("%s: max_hits must be 0..%d, got %r" % (what, _native.QUERY_MULTI_MAX, max_hits))
+    if k == 0 and not counts:
+        raise PathTracerError("%s: max_hits = 0 leaves only the counts to ask for (counts=True)" % what)
+    return k
+
+
+def _query_multi_tensor(state, rays, k, counts):
+    import torch
+    if rays.device.type != "cuda" or rays.device.index != state._device:
+        raise PathTracerError("queryRaysMulti: the rays are on %s, the context is on cuda:%d" % (rays.device, state._device))
+    if rays.dtype != torch.float32:
+        raise PathTracerError("queryRaysMulti: the rays must be float32, got %s" % rays.dtype)
+    if rays.dim() != 2 or rays.shape[1] != 8:
+        raise PathTracerError("queryRaysMulti: expected an (n, 8) tensor, got shape %s" % (tuple(rays.shape),))
+    if not rays.is_contiguous():
+        raise PathTracerError("queryRaysMulti: the rays must be contiguous (nothing is copied)")
+    n = int(rays.shape[0])
+    with torch.cuda.device(rays.device):
+        out = torch.empty((n, k, 8), dtype=torch.float32, device=rays.device)
+        cnt = torch.empty((n,), dtype=torch.int32, device=rays.device) if counts else None
+        torch.cuda.current_stream().synchronize()      # the rays' producer and the allocations; the call below returns synchronised
+    _check(state.context, _native.hip().pt_query_multi(state.context, rays.data_ptr() if n else None, n, k, out.data_ptr() if n and k else None,
+                                                       cnt.data_ptr() if n and counts else None), "pt_query_multi")
+    got = {"t": out[:, :, 0], "prim": out[:, :, 1].view(torch.int32), "u": out[:, :, 2], "v": out[:, :, 3], "normal": out[:, :, 4:7],
+           "material": out[:, :, 7].view(torch.int32)}
+    if counts:
+        got["count"] = cnt
+    return got
+
+
+def queryRaysMulti(state, rays, max_hits=4, counts=False):
+    """The first max_hits surfaces each ray goes through, in order, and how many it crosses in all (include/acgpt.h pt_query_multi).
+    rays: queryRays' (n, 8) float32 records.  max_hits: 0..8.  counts: also the total number of triangles the ray hits inside its
+    interval, not clamped to max_hits; it makes the walk visit everything the ray crosses.  max_hits=0, counts=True asks for the
+    counts alone.
+
+    A NumPy array (or anything np.asarray takes) goes to the device and the answer comes back: a dict of (n, max_hits) arrays t float32
+    (-1 past the ray's last hit), prim uint32 (0xFFFFFFFF there), u, v the barycentrics of v1 and v2, normal (n, max_hits, 3) facing the
+    ray's origin, material uint32, plus count (n,) uint32 when asked.  Column j is the ray's j-th hit in ascending (t, prim); column 0
+    is queryRays' answer.  The counts are the triangle test's and not watertight: a ray through an edge or vertex that triangles share
+    may count that crossing 0, 1 or more times.
+
+    A torch tensor must be float32, contiguous and on the context's device; nothing is copied, its data_ptr() goes straight in, and
+    the answer is torch tensors on that device: views of one (n, max_hits, 8) float32 tensor, prim and material as int32 (-1 past the
+    last hit), count int32.  torch's current stream is synchronised before the call, and the call returns synchronised."""
+    k = _multi_args("queryRaysMulti", max_hits, counts)
+    if _is_tensor(rays):
+        return _query_multi_tensor(state, rays, k, bool(counts))
+    r = np.asarray(rays)
+    if r.ndim != 2 or r.shape[1] != 8:
+        raise PathTracerError("queryRaysMulti: expected an (n, 8) array, got shape %s" % (r.shape,))
+    if r.dtype.kind not in "fiu":
+        raise PathTracerError("queryRaysMulti: the rays must be numbers, got %s" % r.dtype)
+    r = np.ascontiguousarray(r, np.float32)
+    n = r.shape[0]
+    out = np.zeros((n, k), HIT_DTYPE)
+    cnt = np.zeros(n, np.uint32)
+    if n:
+        L = _native.hip()
+        bufs, d_hits, d_counts = _device_buffers(state, 1, r.nbytes), None, None
+        try:
+            if k:
+                bufs += _device_buffers(state, 1, out.nbytes)
+                d_hits = bufs[-1]
+            if counts:
+                bufs += _device_buffers(state, 1, cnt.nbytes)
+                d_counts = bufs[-1]
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], r.ctypes.data, r.nbytes), "copy to device")
+            _check(state.context, L.pt_query_multi(state.context, bufs[0], n, k, d_hits, d_counts), "pt_query_multi")
+            if k:
+                _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, d_hits, out.nbytes), "copy to host")
+            if counts:
+                _check(state.context, L.pt_copy_to_host(state.context, cnt.ctypes.data, d_counts, cnt.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    got = {"t": out["t"], "prim": out["prim"], "u": out["uv"][..., 0], "v": out["uv"][..., 1], "normal": out["normal"], "material": out["material"]}
+    got = {key: np.ascontiguousarray(val) for key, val in got.items()}
+    if counts:
+        got["count"] = cnt
+    return got
+
+
+INSIDE_DIRECTIONS = ((0.5377, 0.2673, 0.7996), (-0.6124, 0.7071, 0.3536), (0.3015, -0.9045, 0.3015))
+
+
+def _inside_rays(what, points, directions):
+    """The (n * m, 8) float32 rays of pointsInside, point-major: ray i * m + j leaves point i along direction j, tmin 0, tmax +inf."""
+    p = np.asarray(points)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise PathTracerError("%s: expected (n, 3) points, got shape %s" % (what, p.shape))
+    if p.dtype.kind not in "fiu":
+        raise PathTracerError("%s: the points must be numbers, got %s" % (what, p.dtype))
+    d = np.asarray(INSIDE_DIRECTIONS if directions is None else directions)
+    if d.ndim != 2 or d.shape[1] != 3 or d.dtype.kind not in "fiu":
+        raise PathTracerError("%s: expected (m, 3) directions, got %r" % (what, directions))
+    if d.shape[0] % 2 != 1:
+        raise PathTracerError("%s: an odd number of directions makes a majority, got %d" % (what, d.shape[0]))
+    d = d.astype(np.float32)
+    if not (np.isfinite(d).all() and (d != 0).any(axis=1).all()):
+        raise PathTracerError("%s: every direction must be finite and not zero" % what)
+    n, m = p.shape[0], d.shape[0]
+    if n * m > 0x7FFFFFFF:
+        raise PathTracerError("%s: %d points x %d directions is more than 2^31 - 1 rays" % (what, n, m))
+    rays = np.empty((n, m, 8), np.float32)
+    rays[:, :, 0:3] = p.astype(np.float32)[:, None, :]
+    rays[:, :, 3:6] = d[None, :, :]
+    rays[:, :, 6] = 0.0
+    rays[:, :, 7] = np.inf
+    return rays.reshape(n * m, 8), n, m
+
+
+def pointsInside(state, points, directions=None, return_counts=False):
+    """Which of the points lie inside the scene's surface, by the parity of crossings (queryRaysMulti, counts alone): one ray per point
+    and direction with tmin 0 and tmax +inf, a point is inside by one ray if the ray crosses an odd number of triangles, and inside if
+    most of its rays say so.  directions: an odd number of them, (m, 3); by default three generic ones, INSIDE_DIRECTIONS.  Returns a
+    bool array (n,), and with return_counts also the crossing counts, uint32 (n, m).
+
+    The answer means something only where the mesh is closed: a ray that leaves through a hole counts one crossing too few.  The Cornell
+    box's shell is open to the front.  The counts are not watertight either (include/acgpt.h): a ray through a shared edge or vertex
+    may miscount, which is what the vote over several generic directions is for."""
+    rays, n, m = _inside_rays("pointsInside", points, directions)
+    cnt = queryRaysMulti(state, rays, max_hits=0, counts=True)["count"].reshape(n, m)
+    inside = 2 * ((cnt & 1) != 0).sum(axis=1) > m
+    return (inside, cnt) if return_counts else inside
+
+
 # ------------------------------------------------------------------ closest point ----
 NEAREST_DTYPE = np.dtype([("distance", np.float32), ("prim", np.uint32), ("u", np.float32), ("v", np.float32), ("point", np.float32, 3), ("material", np.uint32)])      # pt_nearest
 assert NEAREST_DTYPE.itemsize == 32
@@ -784,11 +920,13 @@ def distanceFieldPoints(resolution, lo, hi):
     return pts.reshape(-1, 3)
 
 
-def bakeDistanceField(state, resolution, bounds=None, max_radius=float("inf"), return_prims=False):
-    """The unsigned distance from the centre of every cell of an (nz, ny, nx) grid to the scene's surface (queryNearest on
+def bakeDistanceField(state, resolution, bounds=None, max_radius=float("inf"), return_prims=False, signed=False):
+    """The distance from the centre of every cell of an (nz, ny, nx) grid to the scene's surface (queryNearest on
     distanceFieldPoints): float32 [nz, ny, nx], -1 where nothing lies within max_radius.  bounds: (lo xyz, hi xyz) of the grid, the
     scene box if not given.  The points go to the device x fastest, so the 64 queries of a wave are neighbours.  return_prims: also the
-    closest triangle's index per cell, uint32 [nz, ny, nx] (0xFFFFFFFF where nothing is found)."""
+    closest triangle's index per cell, uint32 [nz, ny, nx] (0xFFFFFFFF where nothing is found).  The distance is unsigned unless
+    signed=True, which negates it at the cells that pointsInside calls inside (its default directions; closed meshes only), and leaves
+    the -1 of a cell that found nothing as it is."""
     if bounds is None:
         info = getBvhInfo(state)
         lo, hi = [float(x) for x in info.scene_lo], [float(x) for x in info.scene_hi]
@@ -801,6 +939,9 @@ def bakeDistanceField(state, resolution, bounds=None, max_radius=float("inf"), r
     got = queryNearest(state, pts, max_radius)
     shape = tuple(int(r) for r in resolution)
     dist = got["distance"].reshape(shape)
+    if signed:
+        inside = pointsInside(state, pts).reshape(shape) & (dist >= 0.0)
+        dist = np.where(inside, -dist, dist)
     return (dist, got["prim"].reshape(shape)) if return_prims else dist
 
 

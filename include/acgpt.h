@@ -426,6 +426,35 @@ typedef struct { float t; uint32_t prim; float u, v; float nx, ny, nz; uint32_t 
 int pt_query_closest(pt_ctx* ctx, const float* rays, size_t n, pt_hit* hits);
 int pt_query_any(pt_ctx* ctx, const float* rays, size_t n, uint8_t* occluded);
 
+/* ---- the first hits of a ray in order, and how many there are (opt-in; nothing above changes) --------------------------------------
+ * What a ray hits after its first hit: entry and exit pairs for thickness and penetration depth, x-ray and layered picking, multi-echo
+ * range sensors, inside / outside by the parity of crossings.  One walk per ray instead of one pt_query_closest call per layer, which
+ * also loses every second triangle that ties in t.  pt_query_closest's rays, rules and memory: DEVICE arrays, 16-byte aligned (counts
+ * 4-byte), the call enqueues on the context's stream and returns synchronised, acts on rank 0 of a pt_create_multi context, never
+ * writes the accumulation buffer, the frame buffer or pt_stats, walks the node array the scene holds (pt_bvh_info.device_bytes as for
+ * pt_query_closest) and uses no atomics: two calls give the same bits.
+ *
+ *   a hit     a triangle that the triangle test accepts inside the open interval (tmin, tmax): exactly what pt_query_closest could
+ *             return for that interval.  Each triangle counts once.
+ *   hits      null with max_hits == 0, or n * max_hits records (1 <= max_hits <= PT_QUERY_MULTI_MAX), ray-major: record j of ray i is
+ *             hits[i * max_hits + j].  A ray's records are its hits in ascending (t, prim): t compared as floats, equal t to the lower
+ *             triangle index.  Each is pt_query_closest's full record (u, v in plain fp32, the normal towards the origin, the
+ *             material); the slots past the ray's last hit hold the miss record.  Record 0 equals pt_query_closest's, bit for bit.
+ *   counts    null, or n words: the number of hits of the ray in the interval, not clamped to max_hits.  0 for a miss before any
+ *             traversal (pt_query_closest's list) and in a scene without triangles.
+ *   the walk  with counts nothing can be pruned at a hit: the walk is cut at the ray's tmax only, and costs what the ray crosses.
+ *             Without counts it is also cut behind the last kept hit once max_hits are known (widened so that a triangle that ties
+ *             with that hit and has a lower index is still reached).  The hits are the same either way.
+ *   NOT WATERTIGHT.  The counts are the triangle test's: Moeller-Trumbore per triangle, with no shared-edge rule.  A ray through an
+ *             edge or a vertex that triangles share may count that crossing 0, 1 or several times (of 642 rays from the centre of a
+ *             1 280-triangle icosphere through its own vertices, 186 count 0 and some count up to 6); rays in generic directions
+ *             count every crossing once.  Parity tests should vote over several directions (pathtracer.pointsInside).
+ * n == 0 is a no-op success.  Refused, with the context left usable: n > 0x7FFFFFFF, hits and counts both null, hits null with
+ * max_hits != 0 or the reverse, max_hits > PT_QUERY_MULTI_MAX, a null or misaligned rays or output pointer with n > 0, an output that
+ * overlaps the rays or the other output, a context without a scene.                                                                   */
+#define PT_QUERY_MULTI_MAX 8
+int pt_query_multi(pt_ctx* ctx, const float* rays, size_t n, uint32_t max_hits, pt_hit* hits, uint32_t* counts);
+
 /* ---- closest-point queries on the device (opt-in; nothing above changes) ----------------------------------------------------------
  * The other question a scene on the GPU answers beside ray casts: how far is a point from the surface, and where is the nearest surface
  * point — clearance and collision checks, snapping and projection onto the mesh, distance-field baking, proximity shading, sensor
