@@ -51,6 +51,13 @@ class Stats(C.Structure):
                 ("math_mode", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class TreeInfo(C.Structure):
+    """pt_tree_info of include/acgpt_test.h (pt_debug_read_tree; not part of the ABI)"""
+    _fields_ = [("n_tris", C.c_uint32), ("n_nodes", C.c_uint32), ("max_depth", C.c_uint32), ("mode", C.c_int32), ("pad_abs", C.c_float),
+                ("hspace", C.c_float * 8), ("scene_lo", C.c_float * 3), ("scene_hi", C.c_float * 3),
+                ("n_wrecs", C.c_uint32), ("n_wnodes", C.c_uint32), ("wide_depth", C.c_uint32), ("held", C.c_uint32)]
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("n_tris", C.c_uint32), ("n_nodes", C.c_uint32), ("max_depth", C.c_uint32), ("stack_entries", C.c_uint32),
                 ("scene_lo", C.c_float * 3), ("scene_hi", C.c_float * 3), ("build_ms", C.c_float),
@@ -157,7 +164,7 @@ ABI_SYMBOLS = [
     "pt_host_malloc_mapped", "pt_host_free_mapped", "pt_abi_version",
 ]
 # ... and include/acgpt_test.h (test hooks and diagnostics; same library)
-TEST_SYMBOLS = ["pt_bench_traversal", "pt_selftest", "pt_debug_wave_times", "pt_debug_queue_progress", "pt_debug_window_moves", "pt_debug_queue_order", "pt_debug_pixel_classes", "pt_debug_row_spans", "pt_read_morton", "pt_debug_environment", "pt_debug_microfacet", "pt_debug_nearest_visits"]
+TEST_SYMBOLS = ["pt_bench_traversal", "pt_selftest", "pt_debug_wave_times", "pt_debug_queue_progress", "pt_debug_window_moves", "pt_debug_queue_order", "pt_debug_pixel_classes", "pt_debug_row_spans", "pt_read_morton", "pt_debug_environment", "pt_debug_microfacet", "pt_debug_nearest_visits", "pt_debug_read_tree"]
 
 _hip = None
 _host = None
@@ -264,6 +271,7 @@ def hip():
     L.pt_debug_wave_times.argtypes = [vp, vp, sz]; L.pt_debug_wave_times.restype = C.c_int
     L.pt_debug_queue_progress.argtypes = [vp, vp]; L.pt_debug_queue_progress.restype = C.c_int
     L.pt_read_morton.argtypes = [vp, vp, vp]; L.pt_read_morton.restype = C.c_int
+    L.pt_debug_read_tree.argtypes = [vp, C.c_int, vp, sz, C.POINTER(TreeInfo)]; L.pt_debug_read_tree.restype = C.c_int
     L.pt_debug_window_moves.argtypes = [vp, vp]; L.pt_debug_window_moves.restype = C.c_int
     if hasattr(L, "pt_debug_node_order"):      # experiments library only
         L.pt_debug_node_order.argtypes = [vp, C.c_int]; L.pt_debug_node_order.restype = C.c_int

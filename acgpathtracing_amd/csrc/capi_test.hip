@@ -176,3 +176,33 @@ PT_API int pt_read_morton(pt_ctx* c, uint32_t* codes_sorted, uint32_t* prims_sor
     if (!ptd::read_morton(c->bvh, c->stream, codes_sorted, prims_sorted, err)) return fail(c, "pt_read_morton: " + err);
     return 0;
 }
+
+// The scene's tree as the device holds it (tests/tree_ref.py): device-to-host copies only, nothing is built or released.
+PT_API int pt_debug_read_tree(pt_ctx* c, int what, void* out, size_t capacity_bytes, pt_tree_info* info)
+{
+    if (!c) return fail(nullptr, "pt_debug_read_tree: null context");
+    if (what < 0 || what > 6) return fail(c, "pt_debug_read_tree: what = 0 (info only) .. 6");
+    if (what == 0 ? !info : !out) return fail(c, "pt_debug_read_tree: null argument");
+    if (!c->scene_kept || c->bvh.n_tris == 0) return fail(c, "pt_debug_read_tree: no scene (pt_set_scene with triangles first)");
+    const ptd::LbvhResult& b = c->bvh;
+    const void* src[7] = {nullptr, b.nodes, b.hnodes, b.hcnodes, b.wrecs, b.tris, b.shade};
+    const size_t bytes[7] = {0, (size_t)b.n_nodes * sizeof(ptd::BvhNode), (size_t)b.n_nodes * sizeof(ptd::HNode), (size_t)b.n_nodes * sizeof(ptd::HNode),
+                             (size_t)b.n_wrecs * 48u, (size_t)b.n_tris * sizeof(ptd::TriRecord), (size_t)b.n_tris * sizeof(float4)};
+    if (what != 0) {
+        if (!src[what]) return fail(c, "pt_debug_read_tree: array " + std::to_string(what) + " is not held");
+        if (capacity_bytes < bytes[what])
+            return fail(c, "pt_debug_read_tree: capacity " + std::to_string(capacity_bytes) + " bytes, the array has " + std::to_string(bytes[what]));
+        CK(c, hipSetDevice(c->device));
+        CK(c, hipStreamSynchronize(c->stream));
+        CK(c, hipMemcpy(out, src[what], bytes[what], hipMemcpyDeviceToHost));
+    }
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->n_tris = b.n_tris; info->n_nodes = b.n_nodes; info->max_depth = b.max_depth; info->mode = b.mode; info->pad_abs = b.pad_abs;
+        memcpy(info->hspace, &b.hspace, sizeof(info->hspace));
+        for (int k = 0; k < 3; k++) { info->scene_lo[k] = b.scene_lo[k]; info->scene_hi[k] = b.scene_hi[k]; }
+        info->n_wrecs = b.n_wrecs; info->n_wnodes = b.n_wnodes; info->wide_depth = b.wide_depth;
+        for (int w = 1; w <= 6; w++) if (src[w]) info->held |= 1u << (w - 1);
+    }
+    return 0;
+}

@@ -10,8 +10,9 @@
 //                 per block in a fixed order; the host adds the block partials in block order
 //
 // The expressions for records, padded boxes and normals are the build's own (lbvh_build.hip k_prepare, record_aabb,
-// k_gather_leaves); lbvh_build.hip keeps them file-local, so the few lines are restated here and tests/test_gpu_update.py pins
-// every bit against a fresh build.  Unions are exact, so the boxes do not depend on the order the threads arrive in.
+// k_gather_leaves); lbvh_build.hip keeps them file-local, so the few lines are restated here.  tests/test_gpu_update.py pins every
+// answer and image bit against a fresh build; the node bits themselves — every box the exact union of the records below it — are
+// pinned by tests/test_gpu_tree.py (test_refit).  Unions are exact, so the boxes do not depend on the order the threads arrive in.
 #include "refit.h"
 #include "pt_device.h"
 #include <algorithm>

@@ -105,6 +105,24 @@ int pt_debug_microfacet(pt_ctx* ctx, int op, const float* in, size_t n, float* o
 int pt_debug_nearest_visits(pt_ctx* ctx, const float* points, size_t n, pt_nearest* out, uint32_t* visits);
 /* Sorted (morton, triangle) pairs of the last build, HOST outputs of n_tris. */
 int pt_read_morton(pt_ctx* ctx, uint32_t* codes_sorted, uint32_t* prims_sorted);
+/* What the scene's tree is made of, as the device holds it right now (tests/tree_ref.py validates it node by node).  Not part of the
+ * ABI (pt_abi_version stays as it is): a plain struct of this header. */
+typedef struct pt_tree_info {
+    uint32_t n_tris, n_nodes, max_depth;
+    int32_t  mode;                  /* the build mode the tree was made with (0 Karras, 1 PLOC, 2 PLOC + reinsertion) */
+    float    pad_abs;               /* absolute pad of the triangle boxes */
+    float    hspace[8];             /* cx, cy, cz, inv_scale, isx, isy, isz, pad_ : the space of the fp16 planes */
+    float    scene_lo[3], scene_hi[3];
+    uint32_t n_wrecs, n_wnodes, wide_depth;
+    uint32_t held;                  /* bit (what - 1) set: array `what` below is on the device */
+} pt_tree_info;
+/* Copies one array of the scene's tree to the HOST, as it is held right now: what = 0 info only (out may be NULL); 1 fp32 nodes
+ * (64 B each, n_nodes); 2 fp16 {lo, hi} nodes (32 B); 3 fp16 {centre, half extent} nodes (32 B; inner child references are byte
+ * offsets); 4 four-wide records (48 B, n_wrecs); 5 triangle records (48 B, n_tris, Morton order); 6 shade records (16 B, n_tris).
+ * Never allocates, never brings an array into existence and leaves pt_get_bvh_info().device_bytes as it is: an array that is not held,
+ * a capacity below the array's size, a missing scene or a null argument is refused.  info may be NULL (what != 0).  A
+ * pt_create_multi context reads rank 0. */
+int pt_debug_read_tree(pt_ctx* ctx, int what, void* out, size_t capacity_bytes, pt_tree_info* info);
 
 #ifdef __cplusplus
 }
