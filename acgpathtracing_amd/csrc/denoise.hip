@@ -54,14 +54,26 @@ __device__ __forceinline__ float4 dn_albedo(const float4& alb, bool hit)
 {
     return hit ? make_float4(fmaxf(alb.x, kDnAlbedoFloor), fmaxf(alb.y, kDnAlbedoFloor), fmaxf(alb.z, kDnAlbedoFloor), 0.0f) : make_float4(1.0f, 1.0f, 1.0f, 0.0f);
 }
-// w_n and the depth term of the exponent for a tap q of p (zden = sigma_z * step * t_p); false when exactly one of them misses
-__device__ __forceinline__ bool dn_geometry(const float4& ndp, const float4& ndq, bool hp, float zden, float& wn, float& ez)
+// Invalid inputs (include/acgpt.h, "invalid inputs" under pt_denoise).  The rules below only add comparisons and selects: where none
+// fires, every expression is the one it always was, in the same order.
+// A source pixel is unusable if a demodulated channel is not finite or |l(c)| > 2^60 (NaN included): it is never a tap, and its own
+// output is its accumulation rgb.  Between the passes the flag travels as var = -1 in cv.w (a usable var is >= 0 and finite).
+constexpr float kDnMaxLum = 1152921504606846976.0f;      // 2^60
+__device__ __forceinline__ bool dn_usable(float r, float g, float b, float l)
+{
+    return isfinite(r) && isfinite(g) && isfinite(b) && fabsf(l) <= kDnMaxLum;
+}
+// w_n and the depth term of the exponent for a tap q of p (zden = sigma_z * step * t_p, zok: it is neither zero nor not finite); false
+// when exactly one of them misses, or when !zok and t_q != t_p (with t_q == t_p the depth term is then 0)
+__device__ __forceinline__ bool dn_zok(float zden) { return zden != 0.0f && isfinite(zden); }
+__device__ __forceinline__ bool dn_geometry(const float4& ndp, const float4& ndq, bool hp, float zden, bool zok, float& wn, float& ez)
 {
     const bool hq = dn_hit(ndq);
-    if (hp != hq) return false;
+    if (hp != hq || (hp && !zok && !(ndq.w == ndp.w))) return false;
     wn = 1.0f; ez = 0.0f;
     if (hp) {
-        ez = fabsf(ndp.w - ndq.w) / zden;
+        const float z = fabsf(ndp.w - ndq.w) / zden;
+        ez = zok ? z : 0.0f;
         float c = fmaxf(ndp.x * ndq.x + ndp.y * ndq.y + ndp.z * ndq.z, 0.0f);
 #pragma unroll
         for (int k = 0; k < kDnNormalSquarings; k++) c = c * c;
@@ -86,7 +98,9 @@ k_dn_variance(const float4* __restrict__ accum, const float4* __restrict__ albed
     const float4 ap = dn_albedo(albedo[p], hp), cp4 = accum[p];
     const float cr = cp4.x / ap.x, cg = cp4.y / ap.y, cb = cp4.z / ap.z;
     const float lp = image_lum(cr, cg, cb);
+    if (!dn_usable(cr, cg, cb, lp)) { cv[p] = make_float4(cr, cg, cb, -1.0f); return; }
     const float zden = kDnSigmaZ * 1.0f * ndp.w;
+    const bool zok = dn_zok(zden);
     float sw = 0.0f, s1 = 0.0f, s2 = 0.0f;
     for (int dy = -2; dy <= 2; dy++) {
         const int yq = (int)y + dy;
@@ -96,29 +110,38 @@ k_dn_variance(const float4* __restrict__ accum, const float4* __restrict__ albed
             if (xq < 0 || xq >= (int)w) continue;
             const uint32_t q = (uint32_t)yq * w + (uint32_t)xq;
             const float4 ndq = nd[q];
-            float wn, ez;
-            if (!dn_geometry(ndp, ndq, hp, zden, wn, ez)) continue;
             const float4 aq = dn_albedo(albedo[q], hp), c4 = accum[q];
-            const float dl = image_lum(c4.x / aq.x, c4.y / aq.y, c4.z / aq.z) - lp;
+            const float qr = c4.x / aq.x, qg = c4.y / aq.y, qb = c4.z / aq.z;
+            const float lq = image_lum(qr, qg, qb);
+            float wn, ez;
+            if (!dn_geometry(ndp, ndq, hp, zden, zok, wn, ez) || !dn_usable(qr, qg, qb, lq)) continue;      // one branch per tap
+            const float dl = lq - lp;
             const float wq = wn * expf(-ez);
             sw += wq; s1 += wq * dl; s2 += wq * (dl * dl);
         }
     }
-    const float m1 = s1 / sw, m2 = s2 / sw;        // sw > 0: the centre tap has weight ~1
-    cv[p] = make_float4(cr, cg, cb, fmaxf(m2 - m1 * m1, 0.0f));
+    const float m1 = s1 / sw, m2 = s2 / sw;        // sw > 0: the centre tap has weight ~1, unless the normal is zero, NaN or short
+    const float var = fmaxf(m2 - m1 * m1, 0.0f);
+    cv[p] = make_float4(cr, cg, cb, sw > 0.0f && isfinite(var) ? var : 0.0f);
 }
 
-// one iteration at `step`; LAST: remodulate with max(albedo_p, 0.01) and write {rgb, 1}, else {c', var'}
+// one iteration at `step`; LAST: remodulate with max(albedo_p, 0.01) and write {rgb, 1}, else {c', var'}; an unusable pixel
+// (cv.w < 0) stays as it is, and LAST writes its accumulation rgb
 template <bool LAST>
 __global__ void __launch_bounds__(256)
-k_dn_atrous(const float4* __restrict__ cv, const float4* __restrict__ nd, const float4* __restrict__ albedo, uint32_t w, uint32_t h, int step,
-            float4* __restrict__ out)
+k_dn_atrous(const float4* __restrict__ cv, const float4* __restrict__ nd, const float4* __restrict__ albedo, const float4* __restrict__ accum,
+            uint32_t w, uint32_t h, int step, float4* __restrict__ out)
 {
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
     if (x >= w || y >= h) return;
     const uint32_t p = y * w + x;
     const float4 ndp = nd[p], cvp = cv[p];
     const bool hp = dn_hit(ndp);
+    if (cvp.w < 0.0f) {
+        if (LAST) { const float4 c = accum[p]; out[p] = make_float4(c.x, c.y, c.z, 1.0f); }
+        else out[p] = cvp;
+        return;
+    }
     // g(var)_p: 3x3 {1/4, 1/2, 1/4}^2 at distance 1, renormalised at the borders
     float gs = 0.0f, gw = 0.0f;
     for (int dy = -1; dy <= 1; dy++) {
@@ -128,13 +151,16 @@ k_dn_atrous(const float4* __restrict__ cv, const float4* __restrict__ nd, const 
             const int xq = (int)x + dx;
             if (xq < 0 || xq >= (int)w) continue;
             const float k = kDnG[dx + 1] * kDnG[dy + 1];
-            gs += k * cv[(uint32_t)yq * w + (uint32_t)xq].w;
-            gw += k;
+            const float vq = cv[(uint32_t)yq * w + (uint32_t)xq].w;
+            const bool use = !(vq < 0.0f);              // selects, not a branch: an unusable neighbour adds an exact zero
+            gs += use ? k * vq : 0.0f;
+            gw += use ? k : 0.0f;
         }
     }
     const float lden = kDnSigmaL * sqrtf(gs / gw) + 1e-6f;
     const float lp = image_lum(cvp.x, cvp.y, cvp.z);
     const float zden = kDnSigmaZ * (float)step * ndp.w;
+    const bool zok = dn_zok(zden);
     float sk = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
     for (int dy = -2; dy <= 2; dy++) {
         const int yq = (int)y + dy * step;
@@ -144,9 +170,9 @@ k_dn_atrous(const float4* __restrict__ cv, const float4* __restrict__ nd, const 
             if (xq < 0 || xq >= (int)w) continue;
             const uint32_t q = (uint32_t)yq * w + (uint32_t)xq;
             const float4 ndq = nd[q];
-            float wn, ez;
-            if (!dn_geometry(ndp, ndq, hp, zden, wn, ez)) continue;
             const float4 c = cv[q];
+            float wn, ez;
+            if (!dn_geometry(ndp, ndq, hp, zden, zok, wn, ez) || c.w < 0.0f) continue;       // one branch per tap
             const float el = fabsf(lp - image_lum(c.x, c.y, c.z)) / lden;
             const float k = kDnH[dx + 2] * kDnH[dy + 2] * wn * expf(-(ez + el));
             sk += k;
@@ -154,12 +180,15 @@ k_dn_atrous(const float4* __restrict__ cv, const float4* __restrict__ nd, const 
             sv += (k * k) * c.w;
         }
     }
-    const float r = sr / sk, g = sg / sk, b = sb / sk;      // sk > 0: the centre tap's k is 9/64 * n_p.n_p^128
+    float r = sr / sk, g = sg / sk, b = sb / sk;            // sk > 0: the centre tap's k is 9/64 * n_p.n_p^128
+    float var = sv / (sk * sk);
+    // no weight at all (a zero, NaN or short normal) or a sum that left fp32: the pixel keeps c_p and var_p for this pass
+    if (!(sk > 0.0f && isfinite(r) && isfinite(g) && isfinite(b) && isfinite(var))) { r = cvp.x; g = cvp.y; b = cvp.z; var = cvp.w; }
     if (LAST) {
         const float4 ap = dn_albedo(albedo[p], hp);
         out[p] = make_float4(r * ap.x, g * ap.y, b * ap.z, 1.0f);
     } else {
-        out[p] = make_float4(r, g, b, sv / (sk * sk));
+        out[p] = make_float4(r, g, b, var);
     }
 }
 
@@ -186,8 +215,8 @@ hipError_t launch_denoise(const float4* accum, const float4* albedo_prim, const 
     float4* dst = scratch1;
     for (uint32_t i = 0; i < iterations && e == hipSuccess; i++) {
         const int step = 1 << i;
-        if (i + 1 == iterations) k_dn_atrous<true><<<pl.grid, pl.block, 0, stream>>>(src, normal_depth, albedo_prim, w, h, step, out);
-        else k_dn_atrous<false><<<pl.grid, pl.block, 0, stream>>>(src, normal_depth, albedo_prim, w, h, step, dst);
+        if (i + 1 == iterations) k_dn_atrous<true><<<pl.grid, pl.block, 0, stream>>>(src, normal_depth, albedo_prim, accum, w, h, step, out);
+        else k_dn_atrous<false><<<pl.grid, pl.block, 0, stream>>>(src, normal_depth, albedo_prim, accum, w, h, step, dst);
         e = hipGetLastError();
         float4* t = src; src = dst; dst = t;
     }

@@ -39,7 +39,10 @@ k_tp_blend(const float4* __restrict__ accum, const float4* __restrict__ albedo_p
     const float4 c = accum[p], ndp = normal_depth[p];
     const uint32_t prim = __float_as_uint(albedo_prim[p].w);
     float4 o = make_float4(c.x, c.y, c.z, N);                          // the pass-through
-    if (prev.hist && ndp.w >= 0.0f && prim < n_tris && bsdf[prim] == (uint8_t)PT_BSDF_DIFFUSE) {
+    // Invalid inputs (include/acgpt.h): a non-finite accumulation pixel passes through, a non-finite history tap is not accepted,
+    // the clip leaves non-finite neighbours out, a blend that left fp32 passes through.  Comparisons and selects only: where none
+    // fires, every expression below is the one it always was.
+    if (prev.hist && isfinite(c.x) && isfinite(c.y) && isfinite(c.z) && ndp.w >= 0.0f && prim < n_tris && bsdf[prim] == (uint8_t)PT_BSDF_DIFFUSE) {
         const f3 dir = pixel_centre_dir(x, y, w, h, U, V, W);      // the ray k_dn_features traced (denoise.hip)
         f3 hit = mk(eye) + ndp.w * dir;
         bool moved_ok = true;
@@ -94,6 +97,7 @@ k_tp_blend(const float4* __restrict__ accum, const float4* __restrict__ albedo_p
                         if (!(nq.x * ndp.x + nq.y * ndp.y + nq.z * ndp.z > 0.0f)) continue;    // the other side of the plane
                         const float wq = (tx ? ax : 1.0f - ax) * wy;
                         const float4 hq = prev.hist[q];
+                        if (!(isfinite(hq.x) && isfinite(hq.y) && isfinite(hq.z) && isfinite(hq.w))) continue;   // a poisoned tap
                         a += wq;
                         hr += wq * hq.x; hg += wq * hq.y; hb += wq * hq.z;
                         hn += wq * hq.w;
@@ -115,6 +119,7 @@ k_tp_blend(const float4* __restrict__ accum, const float4* __restrict__ albedo_p
                                 const int xq = (int)x + nx;
                                 if (xq < 0 || xq >= (int)w) continue;
                                 const float4 cq = accum[(uint32_t)yq * w + (uint32_t)xq];
+                                if (!(isfinite(cq.x) && isfinite(cq.y) && isfinite(cq.z))) continue;
                                 s1r += cq.x; s1g += cq.y; s1b += cq.z;
                                 s2r += cq.x * cq.x; s2g += cq.y * cq.y; s2b += cq.z * cq.z;
                                 k += 1.0f;
@@ -122,14 +127,16 @@ k_tp_blend(const float4* __restrict__ accum, const float4* __restrict__ albedo_p
                         }
                         const float g = mo.gamma;
                         const float mr = s1r / k, mg = s1g / k, mb = s1b / k;
-                        const float sr = sqrtf(fmaxf(0.0f, s2r / k - mr * mr)), sg = sqrtf(fmaxf(0.0f, s2g / k - mg * mg)),
-                                    sb = sqrtf(fmaxf(0.0f, s2b / k - mb * mb));
+                        const float vr = s2r / k - mr * mr, vg = s2g / k - mg * mg, vb = s2b / k - mb * mb;
+                        const float sr = isfinite(vr) ? sqrtf(fmaxf(0.0f, vr)) : 0.0f, sg = isfinite(vg) ? sqrtf(fmaxf(0.0f, vg)) : 0.0f,
+                                    sb = isfinite(vb) ? sqrtf(fmaxf(0.0f, vb)) : 0.0f;
                         h0 = fminf(fmaxf(h0, mr - g * sr), mr + g * sr);
                         h1 = fminf(fmaxf(h1, mg - g * sg), mg + g * sg);
                         h2 = fminf(fmaxf(h2, mb - g * sb), mb + g * sb);
                     }
                     const float den = n + N;
-                    o = make_float4((n * h0 + N * c.x) / den, (n * h1 + N * c.y) / den, (n * h2 + N * c.z) / den, den);
+                    const float4 b = make_float4((n * h0 + N * c.x) / den, (n * h1 + N * c.y) / den, (n * h2 + N * c.z) / den, den);
+                    if (isfinite(b.x) && isfinite(b.y) && isfinite(b.z)) o = b;
                 }
             }
         }

@@ -582,8 +582,19 @@ int pt_ao_image(pt_ctx* ctx, const pt_params* params, const float* normal_depth,
  *   output   c' * a_p after the last iteration, alpha 1
  *   sigma_z = 0.01, sigma_n = 128, sigma_l = 5: the best of a sweep (sigma_z 0.002 ... 1, sigma_l 1 ... 16) on the CPU oracle's Cornell
  *   box at 128 x 128, 8 samples per pixel against 8192 (tests/test_denoise_host.py): the MSE falls 7.0-fold.
- * The context keeps two float4[w*h] scratch buffers ({c, var}, ping-pong), grown on demand and freed by pt_destroy.  No atomics: two
- * calls give the same bits, and so do the two math modes.                                                                        */
+ *   invalid inputs (comparisons and selects only: where no rule fires, the arithmetic above is untouched and so are its bits):
+ *            a source pixel is UNUSABLE if a channel of c_p is not finite or |l(c_p)| > 2^60 (a NaN l included; below 2^60 the
+ *            squares and their sums stay finite).  An unusable pixel is skipped as a tap q in the variance pre-pass, in every iteration
+ *            and in the 3x3 blur of var, and its own output is its accumulation rgb as bits, alpha 1.
+ *            If sigma_z * s * t_p is zero or not finite, z = 0 for taps with t_q == t_p and every other tap is skipped.
+ *            max(0, n_p . n_q) and max(0, M2 - M1^2) are fmaxf: 0 for a NaN.  max(albedo_p, 0.01) likewise: 0.01 for a NaN albedo.
+ *            If after a pass the sum of weights is not > 0, or c' or var' is not finite, the pixel keeps c_p and var_p for that pass
+ *            (the pre-pass: var_p = 0): a zero, NaN or short normal, or a sum that left fp32.
+ *            normal_depth.w NaN is a miss (not >= 0); +0 and -0 are hits.
+ *            So, with a finite albedo: every output pixel is finite unless its own accumulation pixel is not, and a pixel farther than
+ *            2 * (2^iterations - 1) + 2 from every invalid pixel has the bits it has without them.
+ * The context keeps two float4[w*h] scratch buffers ({c, var}, ping-pong; var = -1 marks an unusable pixel), grown on demand and freed
+ * by pt_destroy.  No atomics: two calls give the same bits, and so do the two math modes.                                          */
 int pt_render_features(pt_ctx* ctx, const pt_params* params, float* albedo_prim, float* normal_depth);
 int pt_denoise(pt_ctx* ctx, const pt_params* params, const float* albedo_prim, const float* normal_depth, float* out_rgba, uint32_t iterations);
 
@@ -620,6 +631,13 @@ int pt_denoise(pt_ctx* ctx, const pt_params* params, const float* albedo_prim, c
  *   count    n = (m < cap) ? m : cap — a times the accepted taps' mean count, so a partly accepted footprint counts for less;
  *            a > 0 and n > 0, or the pass-through
  *   blend    h = (r, g, b) / a;  out.rgb = (n * h + N * c) / (n + N) per channel;  out.w = n + N
+ *   invalid inputs (comparisons and selects only: where no rule fires, the bits above are untouched):
+ *            a pixel whose accumulation rgb is not finite takes the pass-through {c, N} as bits;
+ *            a tap whose history rgb or count is not finite is not accepted, exactly like a tap on another triangle;
+ *            a blend whose rgb is not finite (a finite history or accumulation near FLT_MAX times its count) is the pass-through.
+ *            So every output pixel is finite unless its own accumulation pixel is not, a poisoned history heals on the next call (a
+ *            non-finite history pixel reaches no output), and only the pixels whose footprint holds an invalid pixel change at all.
+ *            A NaN in normal_depth fails its comparison (a miss, a rejected tap, a footprint outside): the pass-through.
  * PT_TEMPORAL_HISTORY_CAP = 256 is the default cap (pathtracer.TemporalHistory, acgpt_main --history-in), from a sweep on the CPU
  * oracle's Cornell box at 128 x 128 (tests/test_temporal_host.py): a 256-spp history and an 8-spp accumulation 10 degrees of orbit
  * away, against 8192 spp, lose 5.1x of the MSE at any cap >= 256; with a converged history, caps 128 ... 256 are best (the bilinear
@@ -655,6 +673,9 @@ int pt_temporal_blend(pt_ctx* ctx, const pt_params* params, uint32_t accum_sampl
  *   clip     (clip_gamma > 0) before the blend, per channel: over the 3 x 3 neighbourhood of p in the accumulation, taps inside the
  *            image, dy outer, dx inner, k taps: mu = sum c / k, sigma = sqrtf(max(0, sum c^2 / k - mu^2));
  *            h = min(max(h, mu - gamma sigma), mu + gamma sigma)
+ *   invalid inputs: pt_temporal_blend's rules, and in the clip a neighbour whose rgb is not all finite is left out of the moments (k
+ *            counts the rest; the pixel itself is finite, so k >= 1); if sum c^2 / k - mu^2 is not finite, sigma = 0.  The bounds are
+ *            then never NaN.  An invalid accumulation pixel therefore reaches its 3 x 3 neighbours through the clip and no further.
  * PT_TEMPORAL_CLIP_GAMMA is the default clip (pathtracer.TemporalHistory(motion=True) when the positions differ between the views,
  * acgpt_main --move-history), the best gamma at cap 256 of a sweep on the CPU oracle (tests/test_motion_host.py).
  * The index buffer is read on the device: the first call with vertex arrays uploads it, as the first pt_update_vertices does (the same

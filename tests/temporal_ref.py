@@ -2,7 +2,11 @@
 
 Everything is fp32 in the operation order of csrc/temporal.hip, taps ty-major, so that the GPU result agrees with this one bit for
 bit: the kernel has no transcendental, and the ray directions are those of denoise_ref.pixel_rays, which pt_render_features matches
-exactly.  A rejected tap adds nothing here, as it is skipped there.  Images are [h, w, 4] float32 with row 0 at the bottom."""
+exactly.  A rejected tap adds nothing here, as it is skipped there.  Images are [h, w, 4] float32 with row 0 at the bottom.
+
+dtype=np.float64 evaluates the same formulas from the same fp32 inputs in double precision.  The rules for invalid inputs are those
+of include/acgpt.h: a non-finite accumulation pixel passes through, a non-finite history tap is not accepted, a blend that is not
+finite passes through.  No expression here leaves the treatment of a NaN to a library's maximum or minimum."""
 import ctypes as C
 
 import numpy as np
@@ -56,7 +60,7 @@ def _dot(a, b):
     return a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1] + a[..., 2] * b[..., 2]
 
 
-def blend(accum, albedo, nd, camera, n_samples, bsdf, cap, prev=None):
+def blend(accum, albedo, nd, camera, n_samples, bsdf, cap, prev=None, dtype=np.float32):
     """The output of pt_temporal_blend and where history was taken.
 
     accum, albedo, nd: [h, w, 4] of the current view; camera: (eye, U, V, W); n_samples: N; bsdf: uint8 per triangle; cap: the
@@ -64,8 +68,11 @@ def blend(accum, albedo, nd, camera, n_samples, bsdf, cap, prev=None):
     [h, w] bool: the pixel blended history in, i.e. it is not the pass-through)."""
     accum, albedo, nd = (np.ascontiguousarray(a, np.float32) for a in (accum, albedo, nd))
     h, w = accum.shape[:2]
+    F = np.dtype(dtype).type
+    prim = albedo[..., 3].view(np.uint32)
+    accum, nd = accum.astype(dtype), nd.astype(dtype)
     N = F(n_samples)
-    cap = F(cap)
+    cap = F(np.float32(cap))
     out = accum.copy()
     out[..., 3] = N
     took = np.zeros((h, w), bool)
@@ -73,15 +80,17 @@ def blend(accum, albedo, nd, camera, n_samples, bsdf, cap, prev=None):
         return out, took
     (eye_p, U_p, V_p, W_p), hist, alb_p, nd_p = prev
     hist, alb_p, nd_p = (np.ascontiguousarray(a, np.float32) for a in (hist, alb_p, nd_p))
+    prim_p = alb_p[..., 3].view(np.uint32)
+    hist, nd_p = hist.astype(dtype), nd_p.astype(dtype)
     hp, wp = hist.shape[:2]
-    eye, U, V, W = (np.asarray(v, np.float32) for v in camera)
-    eye_p, U_p, V_p, W_p = (np.asarray(v, np.float32) for v in (eye_p, U_p, V_p, W_p))
-    prim = albedo[..., 3].view(np.uint32)
+    eye, U, V, W = (np.asarray(v, np.float32).astype(dtype) for v in camera)
+    eye_p, U_p, V_p, W_p = (np.asarray(v, np.float32).astype(dtype) for v in (eye_p, U_p, V_p, W_p))
     bsdf = np.asarray(bsdf, np.uint8)
     valid = (nd[..., 3] >= 0) & (prim < bsdf.size)
     valid[valid] = bsdf[prim[valid]] == BSDF_DIFFUSE
+    valid &= np.isfinite(accum[..., :3]).all(axis=-1)              # a non-finite accumulation pixel: the pass-through
     with np.errstate(all="ignore"):
-        d = dr.pixel_rays(w, h, eye, U, V, W)[:, 3:6].reshape(h, w, 3)
+        d = dr.pixel_rays(w, h, eye, U, V, W, dtype)[:, 3:6].reshape(h, w, 3)
         v = (eye[None, None, :] + nd[..., 3:4] * d) - eye_p[None, None, :]
         s = _dot(v, W_p) / _dot(W_p, W_p)
         valid &= s > 0
@@ -94,8 +103,7 @@ def blend(accum, albedo, nd, camera, n_samples, bsdf, cap, prev=None):
         x0f, y0f = np.floor(fx), np.floor(fy)
         ax, ay = fx - x0f, fy - y0f
         x0, y0 = x0f.astype(np.int64), y0f.astype(np.int64)
-        a = np.zeros((h, w), np.float32); r = np.zeros((h, w, 3), np.float32); m = np.zeros((h, w), np.float32)
-        prim_p = alb_p[..., 3].view(np.uint32)
+        a = np.zeros((h, w), dtype); r = np.zeros((h, w, 3), dtype); m = np.zeros((h, w), dtype)
         for ty in range(2):
             yq = y0 + ty
             wy = ay if ty else F(1.0) - ay
@@ -108,6 +116,7 @@ def blend(accum, albedo, nd, camera, n_samples, bsdf, cap, prev=None):
                 ok &= (nq[..., 0] * nd[..., 0] + nq[..., 1] * nd[..., 1] + nq[..., 2] * nd[..., 2]) > F(0.0)
                 wq = (ax if tx else F(1.0) - ax) * wy
                 hq = hist[yc, xc]
+                ok &= np.isfinite(hq).all(axis=-1)                 # a poisoned tap is not accepted
                 a = np.where(ok, a + wq, a)
                 r = np.where(ok[..., None], r + wq[..., None] * hq[..., :3], r)
                 m = np.where(ok, m + wq * hq[..., 3], m)
@@ -115,6 +124,7 @@ def blend(accum, albedo, nd, camera, n_samples, bsdf, cap, prev=None):
         took = valid & (a > 0) & (n > 0)
         den = n + N
         rgb = (n[..., None] * (r / a[..., None]) + N * accum[..., :3]) / den[..., None]
+        took &= np.isfinite(rgb).all(axis=-1)                      # a blend that left the number format: the pass-through
     out[took, :3] = rgb[took]
     out[took, 3] = den[took]
     return out, took
