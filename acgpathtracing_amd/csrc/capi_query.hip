@@ -1,7 +1,8 @@
 // capi_query.hip — the entry points of include/acgpt.h that answer queries in device memory: pt_query_closest, pt_query_any, the
 // ordered multi-hit query pt_query_multi, the ambient-occlusion stage on top of them: pt_ao_points, pt_ao_image, and the
-// closest-point query pt_query_nearest (with its counting twin of include/acgpt_test.h).
-// Host code only; the kernels are in query.hip, multihit.hip, ao.hip and nearest.hip.  The context and what the units share: context.h.
+// closest-point query pt_query_nearest and the box-overlap queries pt_query_overlap, pt_query_overlap_any (each with its counting
+// twin of include/acgpt_test.h).
+// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip and overlap.hip.  The context and what the units share: context.h.
 #include <cmath>
 
 #include "../../include/acgpt_test.h"
@@ -9,6 +10,7 @@
 #include "ao.h"
 #include "multihit.h"
 #include "nearest.h"
+#include "overlap.h"
 #include "query.h"
 
 static_assert(sizeof(pt_hit) == 32, "pt_hit: a change of this layout bumps pt_abi_version");
@@ -122,6 +124,77 @@ PT_API int pt_debug_nearest_visits(pt_ctx* c, const float* points, size_t n, pt_
     if (int rc = nearest_prepare(c, "pt_debug_nearest_visits", points, n, out, visits, true, &fmt)) return rc < 0 ? 0 : rc;
     CK(c, ptd::launch_nearest_visits(fmt, device_scene(c), c->stack_entries, ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)points,
                                      (uint32_t)n, (float4*)out, (uint2*)visits, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- box overlap -----------------------------------------------------------------------------------------------------------------
+static_assert(PT_QUERY_OVERLAP_MAX == ptd::kOverlapMaxPrims, "PT_QUERY_OVERLAP_MAX is the size of the kernel's largest list");
+
+// One output array of an overlap call: bytes per box, the alignment it needs (a mask), whether the call cannot do without it.
+struct OverlapOut { const void* p; size_t bytes_per_box; uintptr_t align_mask; bool required; const char* name; };
+
+// every refusal of the three calls before any device work, in pt_query_multi's order.  list: the call has max_prims and prims
+// (outs[0] is prims).  Returns 0 to go on, 1 refused, -1 nothing to do (n == 0).
+static int overlap_prepare(pt_ctx* c, const char* fn, const float* boxes, size_t n, bool list, uint32_t max_prims, const OverlapOut* outs, int n_outs, int* fmt)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (n == 0) return -1;
+    if (list) {
+        if (max_prims > PT_QUERY_OVERLAP_MAX) return fail(c, f + "max_prims must be at most " + std::to_string(PT_QUERY_OVERLAP_MAX));
+        if ((max_prims != 0u) != (outs[0].p != nullptr)) return fail(c, f + "prims goes with max_prims: both or neither");
+        if (!outs[0].p && !outs[1].p) return fail(c, f + "nothing to write (prims and counts are both null)");
+    }
+    if (!boxes) return fail(c, f + "null argument");
+    for (int k = 0; k < n_outs; k++)
+        if (outs[k].required && !outs[k].p) return fail(c, f + "null argument");
+    if (n > 0x7FFFFFFFull) return fail(c, f + "too many boxes (2^31 - 1 per call)");
+    if ((uintptr_t)boxes & 15u) return fail(c, f + "the boxes must be 16-byte aligned");
+    for (int k = 0; k < n_outs; k++)
+        if ((uintptr_t)outs[k].p & outs[k].align_mask) return fail(c, f + outs[k].name + " must be " + std::to_string(outs[k].align_mask + 1u) + "-byte aligned");
+    for (int k = 0; k < n_outs; k++) {
+        if (!outs[k].p) continue;
+        if (spans_overlap(boxes, n * 32u, outs[k].p, n * outs[k].bytes_per_box)) return fail(c, f + outs[k].name + " overlaps the boxes");
+        for (int j = 0; j < k; j++)
+            if (outs[j].p && spans_overlap(outs[j].p, n * outs[j].bytes_per_box, outs[k].p, n * outs[k].bytes_per_box))
+                return fail(c, f + outs[k].name + " overlaps " + outs[j].name);
+    }
+    return query_node_format(c, f, fmt);
+}
+
+PT_API int pt_query_overlap(pt_ctx* c, const float* boxes, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts)
+{
+    // n < 2^31, max_prims <= 8: the byte counts stay below 2^36
+    const OverlapOut outs[2] = {{prims, (size_t)max_prims * 4u, 15u, false, "prims"}, {counts, 4u, 3u, false, "counts"}};
+    int fmt = 0;
+    if (int rc = overlap_prepare(c, "pt_query_overlap", boxes, n, true, max_prims, outs, 2, &fmt)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_overlap");
+    CK(c, ptd::launch_query_overlap(fmt, device_scene(c), c->stack_entries, ptd::overlap_scene_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)boxes,
+                                    (uint32_t)n, max_prims, prims, counts, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_query_overlap_any(pt_ctx* c, const float* boxes, size_t n, uint8_t* hit)
+{
+    const OverlapOut outs[1] = {{hit, 1u, 0u, true, "hit"}};
+    int fmt = 0;
+    if (int rc = overlap_prepare(c, "pt_query_overlap_any", boxes, n, false, 0u, outs, 1, &fmt)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_overlap_any");
+    CK(c, ptd::launch_query_overlap_any(fmt, device_scene(c), c->stack_entries, ptd::overlap_scene_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)boxes,
+                                        (uint32_t)n, hit, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_debug_overlap_visits(pt_ctx* c, const float* boxes, size_t n, uint32_t* counts, uint32_t* visits)
+{
+    const OverlapOut outs[2] = {{counts, 4u, 3u, true, "counts"}, {visits, 8u, 7u, true, "visits"}};
+    int fmt = 0;
+    if (int rc = overlap_prepare(c, "pt_debug_overlap_visits", boxes, n, false, 0u, outs, 2, &fmt)) return rc < 0 ? 0 : rc;
+    CK(c, ptd::launch_overlap_visits(fmt, device_scene(c), c->stack_entries, ptd::overlap_scene_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)boxes,
+                                     (uint32_t)n, counts, (uint2*)visits, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -16,7 +16,7 @@
 //              [--tonemap linear|reinhard|aces] [--exposure auto|<EV>] [--out-hdr file.pfm]
 //              [--until-error E [--until-permille P] [--error-floor F] [--error-out file.pfm]]
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
-//              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...]
+//              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k] ...]
 //              [--ao K[,radius[,bias]] --ao-out file.pfm [--ao-frames n]]
 // --ao K[,radius[,bias]] with --ao-out: once the scene is set and before the first frame, the ambient occlusion of the view
 // (pt_render_features + pt_ao_image): K rays per pixel (1..256) and call over --ao-frames calls (default 1; call j has seed j and
@@ -38,6 +38,11 @@
 // and third vertex at the point), {"nearest": [x, y, z], "found": false} if nothing lies within the radius.  Floats are printed with
 // nine digits.  A coordinate that is not finite or a radius that is negative or no number is refused with exit status 2.  The frames
 // are the same with or without it.
+// --overlap cx,cy,cz,hx,hy,hz[,k] (repeatable): once the scene is set and before the first frame, the triangles that overlap the
+// axis-aligned box of centre (cx, cy, cz) and half extent (hx, hy, hz), by pt_query_overlap in one call per k, one JSON line each:
+// {"overlap": [cx, cy, cz, hx, hy, hz], "count": <triangles that overlap the box>, "triangles": [<the k lowest indices among them,
+// k = 0..8, default 8>], "materials": ["<newmtl name>" per listed triangle]}.  A value that is not finite, a negative half extent or a
+// k outside 0..8 is refused with exit status 2.  The frames are the same with or without it.
 // --bloom (with --tonemap or --exposure): the image the display transform shows goes through pt_bloom first.  threshold is in display
 // units, multiples of exposed white, and is divided by the exposure (and so are the default knee, half the threshold, and the
 // clamp, none); an automatic exposure is metered on the image without its glare and then applied as a manual one.  --out-hdr gets
@@ -681,6 +686,60 @@ static void pickAllPixels(PathTracerState& state, const TinyObjWrapper& obj, con
     fflush(stdout);
 }
 
+// --overlap: the boxes of one k in one call of pt_query_overlap; one JSON line per box, in the order given
+struct OverlapBox { float v[8]; uint32_t k; };
+static void overlapBoxes(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<OverlapBox>& boxes)
+{
+    const size_t n = boxes.size();
+    std::vector<uint32_t> counts(n, 0u), prims(n * 8, 0xFFFFFFFFu);
+    for (uint32_t k = 0; k <= 8u; k++) {
+        std::vector<size_t> which;
+        std::vector<float> recs;
+        for (size_t i = 0; i < n; i++)
+            if (boxes[i].k == k) { which.push_back(i); recs.insert(recs.end(), boxes[i].v, boxes[i].v + 8); }
+        const size_t m = which.size();
+        if (m == 0) continue;
+        void* d_boxes = nullptr; void* d_prims = nullptr; void* d_counts = nullptr;
+        std::vector<uint32_t> c(m), p(m * (k ? k : 1u));
+        std::string err;
+        if (pt_device_malloc(state.context, &d_boxes, m * 32) != 0 || pt_device_malloc(state.context, &d_counts, m * 4) != 0 ||
+            (k != 0 && pt_device_malloc(state.context, &d_prims, m * k * 4) != 0) ||
+            pt_copy_to_device(state.context, d_boxes, recs.data(), m * 32) != 0 ||
+            pt_query_overlap(state.context, (const float*)d_boxes, m, k, (uint32_t*)d_prims, (uint32_t*)d_counts) != 0 ||
+            pt_copy_to_host(state.context, c.data(), d_counts, m * 4) != 0 ||
+            (k != 0 && pt_copy_to_host(state.context, p.data(), d_prims, m * k * 4) != 0))
+            err = pt_last_error(state.context);
+        if (d_boxes) pt_device_free(state.context, d_boxes);
+        if (d_prims) pt_device_free(state.context, d_prims);
+        if (d_counts) pt_device_free(state.context, d_counts);
+        if (!err.empty()) throw Exception("overlap: " + err);
+        for (size_t j = 0; j < m; j++) {
+            counts[which[j]] = c[j];
+            for (uint32_t e = 0; e < k; e++) prims[which[j] * 8 + e] = p[j * k + e];
+        }
+    }
+    const std::vector<std::string>& names = obj.getMaterialNames();
+    const std::vector<uint32_t> mats = obj.getMaterialIndices();
+    for (size_t i = 0; i < n; i++) {
+        const float* b = boxes[i].v;
+        printf("{\"overlap\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"count\": %u, \"triangles\": [", b[0], b[1], b[2], b[3], b[4], b[5], counts[i]);
+        std::string mat_list;
+        bool first = true;
+        for (uint32_t e = 0; e < boxes[i].k; e++) {
+            const uint32_t t = prims[i * 8 + e];
+            if (t == 0xFFFFFFFFu) break;
+            const uint32_t id = t < mats.size() ? mats[t] : 0xFFFFFFFFu;
+            std::string name = id < names.size() ? names[id] : std::string();
+            for (size_t k = 0; k < name.size(); k++) if (name[k] == '"' || name[k] == '\\' || (unsigned char)name[k] < 0x20) name[k] = '_';
+            printf("%s%u", first ? "" : ", ", t);
+            mat_list += std::string(first ? "" : ", ") + "\"" + name + "\"";
+            first = false;
+        }
+        printf("], \"materials\": [%s]}\n", mat_list.c_str());
+    }
+    fflush(stdout);
+}
+
 // --nearest: every point in one call of pt_query_nearest; one JSON line per point
 static void nearestPoints(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<float4>& points)
 {
@@ -772,6 +831,7 @@ int main(int argc, char** argv)
     std::vector<int2> picks;
     std::vector<PickAll> pickAlls;
     std::vector<float4> nearest;
+    std::vector<OverlapBox> overlaps;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false, move_history = false, no_area_light = false;
     std::string env_path, tonemap, exposure_arg, out_hdr, error_out, ao_out;
@@ -870,6 +930,16 @@ int main(int argc, char** argv)
             const int got = sscanf(next(), "%f,%f,%f,%f", &q.x, &q.y, &q.z, &q.w);
             if (got < 3 || !std::isfinite(q.x) || !std::isfinite(q.y) || !std::isfinite(q.z) || !(q.w >= 0.0f)) { std::cerr << "--nearest x,y,z[,radius]: finite coordinates, a radius >= 0" << std::endl; return 2; }
             nearest.push_back(q);
+        }
+        else if (a == "--overlap") {
+            OverlapBox b = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, 8u};
+            int k = 8;
+            const int got = sscanf(next(), "%f,%f,%f,%f,%f,%f,%d", &b.v[0], &b.v[1], &b.v[2], &b.v[3], &b.v[4], &b.v[5], &k);
+            bool ok = got >= 6 && k >= 0 && k <= 8;
+            for (int j = 0; j < 6; j++) ok = ok && std::isfinite(b.v[j]) && (j < 3 || b.v[j] >= 0.0f);
+            if (!ok) { std::cerr << "--overlap cx,cy,cz,hx,hy,hz[,k]: finite values, half extents >= 0, k = 0..8" << std::endl; return 2; }
+            b.k = (uint32_t)k;
+            overlaps.push_back(b);
         }
         else if (a == "--materials") {
             const std::string m = next();
@@ -994,6 +1064,7 @@ int main(int argc, char** argv)
         if (!picks.empty()) { std::cout.flush(); pickPixels(state, obj, picks); }
         if (!pickAlls.empty()) { std::cout.flush(); pickAllPixels(state, obj, pickAlls); }
         if (!nearest.empty()) { std::cout.flush(); nearestPoints(state, obj, nearest); }
+        if (!overlaps.empty()) { std::cout.flush(); overlapBoxes(state, obj, overlaps); }
         if (ao_samples > 0) ambientOcclusion(state, ao_samples, ao_radius, ao_bias, ao_frames, ao_out);
         HistoryFile history;
         if (!history_in.empty()) {              // refused before any frame is rendered

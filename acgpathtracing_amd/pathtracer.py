@@ -945,6 +945,185 @@ def bakeDistanceField(state, resolution, bounds=None, max_radius=float("inf"), r
     return (dist, got["prim"].reshape(shape)) if return_prims else dist
 
 
+# ------------------------------------------------------------------ box overlap ----
+def _overlap_args(what, max_prims, counts):
+    try:
+        k = int(max_prims)
+    except (TypeError, ValueError):
+        raise PathTracerError("%s: max_prims is a number 0..%d, got %r" % (what, _native.QUERY_OVERLAP_MAX, max_prims))
+    if k != max_prims or k < 0 or k > _native.QUERY_OVERLAP_MAX:
+        raise PathTracerError("%s: max_prims must be 0..%d, got %r" % (what, _native.QUERY_OVERLAP_MAX, max_prims))
+    if k == 0 and not counts:
+        raise PathTracerError("%s: max_prims = 0 leaves only the counts to ask for (counts=True)" % what)
+    return k
+
+
+def _overlap_boxes(what, centres, half_extents):
+    """The (n, 8) float32 records {cx, cy, cz, hx, hy, hz, 0, 0} of the NumPy arguments: (n, 8) records as they are, or (n, 3) centres
+    with half extents that broadcast against them"""
+    c = np.asarray(centres)
+    if c.dtype.kind not in "fiu":
+        raise PathTracerError("%s: the boxes must be numbers, got %s" % (what, c.dtype))
+    if c.ndim == 2 and c.shape[1] == 8:
+        if half_extents is not None:
+            raise PathTracerError("%s: (n, 8) records carry their half extents; half_extents must be None" % what)
+        return np.ascontiguousarray(c, np.float32)
+    if c.ndim != 2 or c.shape[1] != 3:
+        raise PathTracerError("%s: expected (n, 3) centres or (n, 8) records, got shape %s" % (what, c.shape))
+    if half_extents is None:
+        raise PathTracerError("%s: (n, 3) centres need half_extents" % what)
+    h = np.asarray(half_extents)
+    if h.dtype.kind not in "fiu":
+        raise PathTracerError("%s: the half extents must be numbers, got %s" % (what, h.dtype))
+    try:
+        h = np.broadcast_to(h.astype(np.float32), c.shape)
+    except ValueError:
+        raise PathTracerError("%s: half_extents of shape %s do not broadcast against %s centres" % (what, h.shape, c.shape))
+    if not (h >= 0.0).all():
+        raise PathTracerError("%s: every half extent must be non-negative" % what)
+    b = np.zeros((c.shape[0], 8), np.float32)
+    b[:, 0:3] = c
+    b[:, 3:6] = h
+    return b
+
+
+def _overlap_tensor(what, state, boxes, half_extents):
+    import torch
+    if half_extents is not None:
+        raise PathTracerError("%s: a tensor is (n, 8) records that carry their half extents; half_extents must be None" % what)
+    if boxes.device.type != "cuda" or boxes.device.index != state._device:
+        raise PathTracerError("%s: the boxes are on %s, the context is on cuda:%d" % (what, boxes.device, state._device))
+    if boxes.dtype != torch.float32:
+        raise PathTracerError("%s: the boxes must be float32, got %s" % (what, boxes.dtype))
+    if boxes.dim() != 2 or boxes.shape[1] != 8:
+        raise PathTracerError("%s: expected an (n, 8) tensor {cx, cy, cz, hx, hy, hz, 0, 0}, got shape %s" % (what, tuple(boxes.shape)))
+    if not boxes.is_contiguous():
+        raise PathTracerError("%s: the boxes must be contiguous (nothing is copied)" % what)
+    return torch
+
+
+def queryOverlap(state, centres, half_extents=None, max_prims=8, counts=True):
+    """Which triangles of the scene on the GPU overlap each axis-aligned box (include/acgpt.h pt_query_overlap).  max_prims: 0..8, how
+    many triangle indices to return per box; counts: also the number of overlapping triangles, not clamped to max_prims.  max_prims=0,
+    counts=True asks for the counts alone.
+
+    NumPy (or anything np.asarray takes): (n, 3) centres with half_extents (n, 3), (3,) or a number, broadcast; or (n, 8) records
+    {cx, cy, cz, hx, hy, hz, 0, 0} with half_extents=None.  A half extent may be 0.  They go to the device and the answer comes back:
+    a dict of prim (n, max_prims) uint32, the lowest indices among the overlapping triangles, ascending, 0xFFFFFFFF past the last one,
+    and count (n,) uint32 when asked.
+
+    A torch tensor must be (n, 8) float32 records, contiguous and on the context's device; nothing is copied, its data_ptr() goes
+    straight in, and the answer is torch tensors on that device, prim and count as int32 (-1 past the last triangle).  torch's current
+    stream is synchronised before the call, and the call returns synchronised."""
+    k = _overlap_args("queryOverlap", max_prims, counts)
+    L = _native.hip()
+    if _is_tensor(centres):
+        torch = _overlap_tensor("queryOverlap", state, centres, half_extents)
+        n = int(centres.shape[0])
+        with torch.cuda.device(centres.device):
+            out = torch.empty((n, k), dtype=torch.int32, device=centres.device)
+            cnt = torch.empty((n,), dtype=torch.int32, device=centres.device) if counts else None
+            torch.cuda.current_stream().synchronize()      # the boxes' producer and the allocations; the call below returns synchronised
+        _check(state.context, L.pt_query_overlap(state.context, centres.data_ptr() if n else None, n, k, out.data_ptr() if n and k else None,
+                                                 cnt.data_ptr() if n and counts else None), "pt_query_overlap")
+        got = {"prim": out}
+        if counts:
+            got["count"] = cnt
+        return got
+    b = _overlap_boxes("queryOverlap", centres, half_extents)
+    n = b.shape[0]
+    out = np.full((n, k), 0xFFFFFFFF, np.uint32)
+    cnt = np.zeros(n, np.uint32)
+    if n:
+        bufs, d_prims, d_counts = _device_buffers(state, 1, b.nbytes), None, None
+        try:
+            if k:
+                bufs += _device_buffers(state, 1, out.nbytes)
+                d_prims = bufs[-1]
+            if counts:
+                bufs += _device_buffers(state, 1, cnt.nbytes)
+                d_counts = bufs[-1]
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], b.ctypes.data, b.nbytes), "copy to device")
+            _check(state.context, L.pt_query_overlap(state.context, bufs[0], n, k, d_prims, d_counts), "pt_query_overlap")
+            if k:
+                _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, d_prims, out.nbytes), "copy to host")
+            if counts:
+                _check(state.context, L.pt_copy_to_host(state.context, cnt.ctypes.data, d_counts, cnt.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    got = {"prim": out}
+    if counts:
+        got["count"] = cnt
+    return got
+
+
+def queryOverlapAny(state, centres, half_extents=None):
+    """Does any triangle of the scene overlap each box (include/acgpt.h pt_query_overlap_any): queryOverlap's arguments, a bool array
+    (n,), or a bool tensor for a tensor.  A box's walk ends at the first triangle it accepts."""
+    L = _native.hip()
+    if _is_tensor(centres):
+        torch = _overlap_tensor("queryOverlapAny", state, centres, half_extents)
+        n = int(centres.shape[0])
+        with torch.cuda.device(centres.device):
+            out = torch.empty((n,), dtype=torch.uint8, device=centres.device)
+            torch.cuda.current_stream().synchronize()
+        _check(state.context, L.pt_query_overlap_any(state.context, centres.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_overlap_any")
+        return out.view(torch.bool)
+    b = _overlap_boxes("queryOverlapAny", centres, half_extents)
+    n = b.shape[0]
+    out = np.zeros(n, np.uint8)
+    if n:
+        bufs = _device_buffers(state, 2, b.nbytes)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], b.ctypes.data, b.nbytes), "copy to device")
+            _check(state.context, L.pt_query_overlap_any(state.context, bufs[0], n, bufs[1]), "pt_query_overlap_any")
+            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    return out.view(np.bool_)
+
+
+def occupancyBoxes(resolution, lo, hi):
+    """The cells of an (nz, ny, nx) grid over the box [lo, hi] as (nz * ny * nx, 8) float32 box records, x fastest: the centres are
+    distanceFieldPoints', the half extent is half a cell, (hi - lo) / (2 n) per axis computed in float64 and rounded UP to float32, so
+    that the cells' union covers the grid."""
+    try:
+        pts = distanceFieldPoints(resolution, lo, hi)
+    except PathTracerError as e:
+        raise PathTracerError(str(e).replace("bakeDistanceField", "bakeOccupancy"))
+    nz, ny, nx = (int(r) for r in resolution)
+    lo, hi = np.asarray(lo, np.float64).reshape(-1), np.asarray(hi, np.float64).reshape(-1)
+    half64 = 0.5 * (hi - lo) / np.array([nx, ny, nz], np.float64)
+    half = half64.astype(np.float32)
+    half = np.where(half.astype(np.float64) < half64, np.nextafter(half, np.float32(np.inf)), half).astype(np.float32)
+    b = np.zeros((pts.shape[0], 8), np.float32)
+    b[:, 0:3] = pts
+    b[:, 3:6] = half
+    return b
+
+
+def bakeOccupancy(state, resolution, bounds=None, counts=False):
+    """Conservative voxelisation: which cells of an (nz, ny, nx) grid does the scene's surface touch.  The cells are occupancyBoxes' —
+    centres from distanceFieldPoints, x fastest, so the 64 boxes of a wave are neighbours; half extent half a cell — and go through
+    queryOverlapAny: a bool [nz, ny, nx] grid.  counts=True goes through queryOverlap with max_prims = 0 instead and returns how many
+    triangles touch each cell, uint32 [nz, ny, nx].  bounds: (lo xyz, hi xyz) of the grid, the scene box if not given.  A cell is
+    occupied iff a triangle overlaps it by include/acgpt.h's closed conditions, so a triangle in a face between two cells occupies
+    both."""
+    if bounds is None:
+        info = getBvhInfo(state)
+        lo, hi = [float(x) for x in info.scene_lo], [float(x) for x in info.scene_hi]
+    else:
+        try:
+            lo, hi = bounds
+        except (TypeError, ValueError):
+            raise PathTracerError("bakeOccupancy: bounds is (lo xyz, hi xyz), got %r" % (bounds,))
+    boxes = occupancyBoxes(resolution, lo, hi)
+    shape = tuple(int(r) for r in resolution)
+    if counts:
+        return queryOverlap(state, boxes, max_prims=0, counts=True)["count"].reshape(shape)
+    return queryOverlapAny(state, boxes).reshape(shape)
+
+
 # ------------------------------------------------------------------ ambient occlusion ----
 def aoSamples(K):
     """The default sample pattern of the ambient-occlusion calls: K points of a Vogel spiral on the unit disk, float32 (K, 2):

@@ -496,6 +496,46 @@ int pt_query_multi(pt_ctx* ctx, const float* rays, size_t n, uint32_t max_hits, 
 typedef struct { float distance; uint32_t prim; float u, v; float cx, cy, cz; uint32_t material; } pt_nearest;   /* 32 bytes */
 int pt_query_nearest(pt_ctx* ctx, const float* points, size_t n, pt_nearest* out);
 
+/* ---- box-overlap queries on the device (opt-in; nothing above changes) ------------------------------------------------------------
+ * The third question a scene on the GPU answers beside ray casts and closest points: which triangles lie in a region of space — the
+ * broad phase of collision checks, box selection, "is this cell empty" for navigation and probe placement, conservative voxelisation.
+ * pt_query_multi's memory and call rules: DEVICE arrays, boxes and prims 16-byte aligned, counts 4-byte, hit any alignment; the call
+ * enqueues on the context's stream and returns synchronised, acts on rank 0 of a pt_create_multi context, never writes the accumulation
+ * buffer, the frame buffer or pt_stats, walks the node array the scene holds (pt_bvh_info.device_bytes as for pt_query_closest) and
+ * uses no atomics: two calls give the same bits.
+ *
+ *   boxes     n records of 8 floats {cx, cy, cz, hx, hy, hz, 0, 0}: centre and half extent of an axis-aligned box.  The last two
+ *             floats are reserved and ignored.  A half extent of 0 (or -0) on any axis is allowed: a rectangle, a segment, a point.
+ *   overlap   a triangle overlaps the box iff all 13 conditions below hold: the separating-axis test of Akenine-Moeller (Fast 3D
+ *             Triangle-Box Overlap Testing) in keep form.  All fp32, every operation on its own, evaluated as written, no fused
+ *             multiply-add (tests/overlap_ref.py is the NumPy statement, equal bit for bit), on the vectors the build stores for the
+ *             triangle, v0, e1 = v1 - v0, e2 = v2 - v0, with c the centre, h the half extent, dot and cross as written under
+ *             pt_query_closest, fmin3 / fmax3 = fminf / fmaxf applied twice (they ignore a NaN operand):
+ *               p0 = v0 - c;  p1 = p0 + e1;  p2 = p0 + e2                                                       (per component)
+ *               box faces, k in x, y, z:  fmin3(p0[k], p1[k], p2[k]) <= h[k]  and  fmax3(p0[k], p1[k], p2[k]) >= -h[k]
+ *               triangle plane:           n = cross(e1, e2);  d = dot(n, p0);  r = (h.x |n.x| + h.y |n.y|) + h.z |n.z|;
+ *                                         d <= r  and  d >= -r
+ *               nine edge axes, f in (e1, e2 - e1, e2), i in x, y, z, j = i + 1, k = i + 2 cyclic:
+ *                                         s_m = p_m[k] f[j] - p_m[j] f[k]  (m = 0, 1, 2);  r = h[j] |f[k]| + h[k] |f[j]|
+ *                                         fmin3(s_0, s_1, s_2) <= r  and  fmax3(s_0, s_1, s_2) >= -r
+ *             The conditions are closed: touching is overlap.  A NaN r, or three NaN s, fails its condition.  A zero-area triangle
+ *             is tested like any other; its zero axes separate nothing.
+ *   counts    null, or n words: the number of triangles that overlap box i, not clamped to max_prims
+ *   prims     null with max_prims == 0, or n * max_prims words (1 <= max_prims <= PT_QUERY_OVERLAP_MAX), box-major:
+ *             prims[i * max_prims + j] is the j-th lowest index, in the caller's index-buffer order, among the triangles that overlap
+ *             box i, ascending; the slots past the last one hold 0xFFFFFFFF.  The walk is the same with and without counts: the lowest
+ *             indices are known only when every overlapping triangle has been seen.
+ *   hit       pt_query_overlap_any: one byte per box, 1 iff counts[i] would be non-zero.  A box's walk ends at its first accepted
+ *             triangle.
+ *   a miss before any traversal: a non-finite centre or half extent, a negative or NaN half extent, a scene without triangles.  It
+ *             gives count 0, prims all 0xFFFFFFFF, hit 0.
+ * n == 0 is a no-op success.  Refused, with the context left usable: n > 0x7FFFFFFF, prims and counts both null, prims null with
+ * max_prims != 0 or the reverse, max_prims > PT_QUERY_OVERLAP_MAX, a null or misaligned boxes or output pointer with n > 0, an output
+ * that overlaps the boxes or the other output, a context without a scene.                                                             */
+#define PT_QUERY_OVERLAP_MAX 8
+int pt_query_overlap(pt_ctx* ctx, const float* boxes, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts);
+int pt_query_overlap_any(pt_ctx* ctx, const float* boxes, size_t n, uint8_t* hit);
+
 /* ---- ambient occlusion traced on the device (opt-in; nothing above changes) -----------------------------------------------------
  * The share of the hemisphere over a surface point that is open within `radius`: K rays per point, generated, traced with
  * pt_query_any's walk and counted inside one kernel, so no ray reaches memory.  pt_ao_points takes the points from a device array
