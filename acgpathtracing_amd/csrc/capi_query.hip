@@ -1,8 +1,8 @@
 // capi_query.hip — the entry points of include/acgpt.h that answer queries in device memory: pt_query_closest, pt_query_any, the
 // ordered multi-hit query pt_query_multi, the ambient-occlusion stage on top of them: pt_ao_points, pt_ao_image, and the
-// closest-point query pt_query_nearest and the box-overlap queries pt_query_overlap, pt_query_overlap_any (each with its counting
-// twin of include/acgpt_test.h).
-// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip and overlap.hip.  The context and what the units share: context.h.
+// closest-point query pt_query_nearest, the box-overlap queries pt_query_overlap, pt_query_overlap_any and the swept-sphere casts
+// pt_query_sweep, pt_query_sweep_any (each with its counting twin of include/acgpt_test.h).
+// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, overlap.hip and sweep.hip.  The context and what the units share: context.h.
 #include <cmath>
 
 #include "../../include/acgpt_test.h"
@@ -12,9 +12,11 @@
 #include "nearest.h"
 #include "overlap.h"
 #include "query.h"
+#include "sweep.h"
 
 static_assert(sizeof(pt_hit) == 32, "pt_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_nearest) == 32, "pt_nearest: a change of this layout bumps pt_abi_version");
+static_assert(sizeof(pt_sweep_hit) == 32, "pt_sweep_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_ao_params) == 32, "pt_ao_params: a change of this layout bumps pt_abi_version");
 
 // The node array the scene holds, as pt_render_features picks it: fp16 centre / half-extent nodes for the default variants, fp32
@@ -195,6 +197,57 @@ PT_API int pt_debug_overlap_visits(pt_ctx* c, const float* boxes, size_t n, uint
     if (int rc = overlap_prepare(c, "pt_debug_overlap_visits", boxes, n, false, 0u, outs, 2, &fmt)) return rc < 0 ? 0 : rc;
     CK(c, ptd::launch_overlap_visits(fmt, device_scene(c), c->stack_entries, ptd::overlap_scene_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)boxes,
                                      (uint32_t)n, counts, (uint2*)visits, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- swept spheres ---------------------------------------------------------------------------------------------------------------
+// every refusal of the three calls before any device work, in pt_query_nearest's order.  out_bytes: bytes of output per sweep.
+// Returns 0 to go on, 1 refused, -1 nothing to do (n == 0).
+static int sweep_prepare(pt_ctx* c, const char* fn, const float* sweeps, size_t n, const void* out, size_t out_bytes, bool out_aligned, const void* visits,
+                         bool with_visits, int* fmt)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (n == 0) return -1;
+    if (!sweeps || !out || (with_visits && !visits)) return fail(c, f + "null argument");
+    if (n > 0x7FFFFFFFull) return fail(c, f + "too many sweeps (2^31 - 1 per call)");
+    if (((uintptr_t)sweeps & 15u) || (out_aligned && ((uintptr_t)out & 15u)) || ((uintptr_t)visits & 7u))
+        return fail(c, f + "the sweep and hit arrays must be 16-byte aligned");
+    if (spans_overlap(sweeps, n * 32u, out, n * out_bytes)) return fail(c, f + "the output overlaps the sweeps");
+    if (with_visits && (spans_overlap(sweeps, n * 32u, visits, n * 8u) || spans_overlap(out, n * out_bytes, visits, n * 8u)))
+        return fail(c, f + "the visit counts overlap another array");
+    return query_node_format(c, f, fmt);
+}
+
+PT_API int pt_query_sweep(pt_ctx* c, const float* sweeps, size_t n, pt_sweep_hit* hits)
+{
+    int fmt = 0;
+    if (int rc = sweep_prepare(c, "pt_query_sweep", sweeps, n, hits, sizeof(pt_sweep_hit), true, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_sweep");
+    CK(c, ptd::launch_query_sweep(fmt, device_scene(c), c->stack_entries, ptd::sweep_scene_scale(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)sweeps,
+                                  (uint32_t)n, (float4*)hits, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_query_sweep_any(pt_ctx* c, const float* sweeps, size_t n, uint8_t* blocked)
+{
+    int fmt = 0;
+    if (int rc = sweep_prepare(c, "pt_query_sweep_any", sweeps, n, blocked, 1, false, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_sweep_any");
+    CK(c, ptd::launch_query_sweep_any(fmt, device_scene(c), c->stack_entries, ptd::sweep_scene_scale(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)sweeps,
+                                      (uint32_t)n, blocked, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_debug_sweep_visits(pt_ctx* c, const float* sweeps, size_t n, pt_sweep_hit* hits, uint32_t* visits)
+{
+    int fmt = 0;
+    if (int rc = sweep_prepare(c, "pt_debug_sweep_visits", sweeps, n, hits, sizeof(pt_sweep_hit), true, visits, true, &fmt)) return rc < 0 ? 0 : rc;
+    CK(c, ptd::launch_sweep_visits(fmt, device_scene(c), c->stack_entries, ptd::sweep_scene_scale(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)sweeps,
+                                   (uint32_t)n, (float4*)hits, (uint2*)visits, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

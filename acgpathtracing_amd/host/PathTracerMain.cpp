@@ -17,6 +17,7 @@
 //              [--until-error E [--until-permille P] [--error-floor F] [--error-out file.pfm]]
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
 //              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k] ...]
+//              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...]
 //              [--ao K[,radius[,bias]] --ao-out file.pfm [--ao-frames n]]
 // --ao K[,radius[,bias]] with --ao-out: once the scene is set and before the first frame, the ambient occlusion of the view
 // (pt_render_features + pt_ao_image): K rays per pixel (1..256) and call over --ao-frames calls (default 1; call j has seed j and
@@ -43,6 +44,13 @@
 // {"overlap": [cx, cy, cz, hx, hy, hz], "count": <triangles that overlap the box>, "triangles": [<the k lowest indices among them,
 // k = 0..8, default 8>], "materials": ["<newmtl name>" per listed triangle]}.  A value that is not finite, a negative half extent or a
 // k outside 0..8 is refused with exit status 2.  The frames are the same with or without it.
+// --sweep ox,oy,oz,dx,dy,dz,r[,tmax] (repeatable): once the scene is set and before the first frame, how far the sphere of radius r
+// whose centre starts at o travels along d before it touches the scene (t in units of |d|, at most tmax, default unbounded), all in
+// one call of pt_query_sweep, one JSON line each: {"sweep": [ox, oy, oz, dx, dy, dz, r], "tmax": <tmax or null>, "hit": true, "t": ...,
+// "triangle": <index>, "material": "<newmtl name>", "point": [x, y, z], "u": ..., "v": ...} (the contact point on the triangle and the
+// weights of its second and third vertex there), {"sweep": [...], "tmax": ..., "hit": false} if nothing is touched.  Floats are printed
+// with nine digits.  A value that is not finite (tmax may be inf), a negative radius or a negative tmax is refused with exit status 2.
+// The frames are the same with or without it.
 // --bloom (with --tonemap or --exposure): the image the display transform shows goes through pt_bloom first.  threshold is in display
 // units, multiples of exposed white, and is divided by the exposure (and so are the default knee, half the threshold, and the
 // clamp, none); an automatic exposure is metered on the image without its glare and then applied as a manual one.  --out-hdr gets
@@ -740,6 +748,37 @@ static void overlapBoxes(PathTracerState& state, const TinyObjWrapper& obj, cons
     fflush(stdout);
 }
 
+// --sweep: every sweep in one call of pt_query_sweep; one JSON line per sweep
+struct SweepArg { float v[8]; };
+static void sweepSpheres(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<SweepArg>& sweeps)
+{
+    const size_t n = sweeps.size();
+    void* d_sweeps = nullptr; void* d_out = nullptr;
+    std::vector<pt_sweep_hit> out(n);
+    std::string err;
+    if (pt_device_malloc(state.context, &d_sweeps, n * 32) != 0 || pt_device_malloc(state.context, &d_out, n * sizeof(pt_sweep_hit)) != 0 ||
+        pt_copy_to_device(state.context, d_sweeps, sweeps.data(), n * 32) != 0 ||
+        pt_query_sweep(state.context, (const float*)d_sweeps, n, (pt_sweep_hit*)d_out) != 0 ||
+        pt_copy_to_host(state.context, out.data(), d_out, n * sizeof(pt_sweep_hit)) != 0)
+        err = pt_last_error(state.context);
+    if (d_sweeps) pt_device_free(state.context, d_sweeps);
+    if (d_out) pt_device_free(state.context, d_out);
+    if (!err.empty()) throw Exception("sweep: " + err);
+    const std::vector<std::string>& names = obj.getMaterialNames();
+    for (size_t i = 0; i < n; i++) {
+        const pt_sweep_hit& r = out[i];
+        const float* q = sweeps[i].v;
+        printf("{\"sweep\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"tmax\": ", q[0], q[1], q[2], q[3], q[4], q[5], q[6]);
+        if (std::isfinite(q[7])) printf("%.9g", q[7]); else printf("null");
+        if (r.prim == 0xFFFFFFFFu) { printf(", \"hit\": false}\n"); continue; }
+        std::string name = r.material < names.size() ? names[r.material] : std::string();
+        for (size_t k = 0; k < name.size(); k++) if (name[k] == '"' || name[k] == '\\' || (unsigned char)name[k] < 0x20) name[k] = '_';
+        printf(", \"hit\": true, \"t\": %.9g, \"triangle\": %u, \"material\": \"%s\", \"point\": [%.9g, %.9g, %.9g], \"u\": %.9g, \"v\": %.9g}\n",
+               r.t, r.prim, name.c_str(), r.cx, r.cy, r.cz, r.u, r.v);
+    }
+    fflush(stdout);
+}
+
 // --nearest: every point in one call of pt_query_nearest; one JSON line per point
 static void nearestPoints(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<float4>& points)
 {
@@ -832,6 +871,7 @@ int main(int argc, char** argv)
     std::vector<PickAll> pickAlls;
     std::vector<float4> nearest;
     std::vector<OverlapBox> overlaps;
+    std::vector<SweepArg> sweeps;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false, move_history = false, no_area_light = false;
     std::string env_path, tonemap, exposure_arg, out_hdr, error_out, ao_out;
@@ -940,6 +980,14 @@ int main(int argc, char** argv)
             if (!ok) { std::cerr << "--overlap cx,cy,cz,hx,hy,hz[,k]: finite values, half extents >= 0, k = 0..8" << std::endl; return 2; }
             b.k = (uint32_t)k;
             overlaps.push_back(b);
+        }
+        else if (a == "--sweep") {
+            SweepArg w = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, INFINITY}};
+            const int got = sscanf(next(), "%f,%f,%f,%f,%f,%f,%f,%f", &w.v[0], &w.v[1], &w.v[2], &w.v[3], &w.v[4], &w.v[5], &w.v[6], &w.v[7]);
+            bool ok = got >= 7 && w.v[6] >= 0.0f && w.v[7] >= 0.0f;
+            for (int j = 0; j < 7; j++) ok = ok && std::isfinite(w.v[j]);
+            if (!ok) { std::cerr << "--sweep ox,oy,oz,dx,dy,dz,r[,tmax]: finite values, a radius >= 0, a tmax >= 0" << std::endl; return 2; }
+            sweeps.push_back(w);
         }
         else if (a == "--materials") {
             const std::string m = next();
@@ -1065,6 +1113,7 @@ int main(int argc, char** argv)
         if (!pickAlls.empty()) { std::cout.flush(); pickAllPixels(state, obj, pickAlls); }
         if (!nearest.empty()) { std::cout.flush(); nearestPoints(state, obj, nearest); }
         if (!overlaps.empty()) { std::cout.flush(); overlapBoxes(state, obj, overlaps); }
+        if (!sweeps.empty()) { std::cout.flush(); sweepSpheres(state, obj, sweeps); }
         if (ao_samples > 0) ambientOcclusion(state, ao_samples, ao_radius, ao_bias, ao_frames, ao_out);
         HistoryFile history;
         if (!history_in.empty()) {              // refused before any frame is rendered

@@ -1124,6 +1124,130 @@ def bakeOccupancy(state, resolution, bounds=None, counts=False):
     return queryOverlapAny(state, boxes).reshape(shape)
 
 
+# ------------------------------------------------------------------ swept spheres ----
+SWEEP_DTYPE = np.dtype([("t", np.float32), ("prim", np.uint32), ("u", np.float32), ("v", np.float32), ("point", np.float32, 3), ("material", np.uint32)])      # pt_sweep_hit
+assert SWEEP_DTYPE.itemsize == 32
+
+
+def _sweep_records(origins_or_sweeps, directions, radius, tmax):
+    """The (n, 8) float32 records {o, d, radius, tmax} of a NumPy call, every refusal before any device work."""
+    p = np.asarray(origins_or_sweeps)
+    if p.dtype.kind not in "fiu":
+        raise PathTracerError("querySweep: the sweeps must be numbers, got %s" % p.dtype)
+    if directions is None:
+        if p.ndim != 2 or p.shape[1] != 8:
+            raise PathTracerError("querySweep: expected an (n, 8) array {o, d, radius, tmax}, or (n, 3) origins with directions, got shape %s" % (p.shape,))
+        if radius is not None:
+            raise PathTracerError("querySweep: the radius is in the seventh column of (n, 8) sweeps; radius= goes with origins and directions")
+        return np.ascontiguousarray(p, np.float32)
+    d = np.asarray(directions)
+    if p.ndim != 2 or p.shape[1] != 3 or d.shape != p.shape or d.dtype.kind not in "fiu":
+        raise PathTracerError("querySweep: expected (n, 3) origins and as many directions, got shapes %s and %s" % (p.shape, d.shape))
+    if radius is None:
+        raise PathTracerError("querySweep: origins and directions need a radius")
+    s = np.empty((p.shape[0], 8), np.float32)
+    s[:, 0:3], s[:, 3:6] = p, d
+    for k, val, what in ((6, radius, "radius"), (7, tmax, "tmax")):
+        a = np.asarray(val, np.float64)
+        if a.ndim not in (0, 1) or (a.ndim == 1 and a.shape[0] != p.shape[0]):
+            raise PathTracerError("querySweep: %s is one number or one per sweep, got shape %s" % (what, a.shape))
+        if not (a >= 0.0).all() or (k == 6 and np.isinf(a).any()):
+            raise PathTracerError("querySweep: %s must be non-negative%s, got %r" % (what, " and finite" if k == 6 else "", val))
+        s[:, k] = a
+    return s
+
+
+def _sweep_tensor(state, sweeps, directions, radius):
+    import torch
+    if directions is not None or radius is not None:
+        raise PathTracerError("querySweep: a tensor holds whole records (n, 8) {o, d, radius, tmax}; directions and radius go with arrays")
+    if sweeps.device.type != "cuda" or sweeps.device.index != state._device:
+        raise PathTracerError("querySweep: the sweeps are on %s, the context is on cuda:%d" % (sweeps.device, state._device))
+    if sweeps.dtype != torch.float32:
+        raise PathTracerError("querySweep: the sweeps must be float32, got %s" % sweeps.dtype)
+    if sweeps.dim() != 2 or sweeps.shape[1] != 8:
+        raise PathTracerError("querySweep: expected an (n, 8) tensor {o, d, radius, tmax}, got shape %s" % (tuple(sweeps.shape),))
+    if not sweeps.is_contiguous():
+        raise PathTracerError("querySweep: the sweeps must be contiguous (nothing is copied)")
+    return torch
+
+
+def querySweep(state, origins_or_sweeps, directions=None, radius=None, tmax=float("inf"), any_hit=False):
+    """How far a sphere travels before it touches the scene on the GPU, and where (include/acgpt.h pt_query_sweep): the centre moves along
+    o + t d for 0 <= t <= tmax, t in units of |d|.
+
+    NumPy (or anything np.asarray takes): (n, 8) records {o, d, radius, tmax}, or (n, 3) origins with (n, 3) directions, a radius (one
+    number or one per sweep) and tmax.  The answer is a dict of arrays t (n,) float32 (-1 on a miss), prim (n,) uint32 (0xFFFFFFFF), u, v
+    the weights of v1 and v2 at the contact point, point (n, 3) the contact point on the triangle, material (n,) uint32.  sweepContacts
+    turns it into centres and normals.  any_hit=True asks pt_query_sweep_any instead and returns a bool array (n,): blocked or not.
+
+    A torch tensor must be (n, 8) float32, contiguous and on the context's device; nothing is copied, its data_ptr() goes straight in, and
+    the answer is torch tensors on that device: views of one (n, 8) float32 tensor, prim and material as int32 (-1 on a miss), or a bool
+    tensor with any_hit.  torch's current stream is synchronised before the call, and the call returns synchronised."""
+    L = _native.hip()
+    if _is_tensor(origins_or_sweeps):
+        x = origins_or_sweeps
+        torch = _sweep_tensor(state, x, directions, radius)
+        n = int(x.shape[0])
+        with torch.cuda.device(x.device):
+            out = torch.empty((n,), dtype=torch.uint8, device=x.device) if any_hit else torch.empty((n, 8), dtype=torch.float32, device=x.device)
+            torch.cuda.current_stream().synchronize()      # the sweeps' producer and the allocation; the call below returns synchronised
+        if any_hit:
+            _check(state.context, L.pt_query_sweep_any(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_sweep_any")
+            return out.view(torch.bool)
+        _check(state.context, L.pt_query_sweep(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_sweep")
+        return {"t": out[:, 0], "prim": out[:, 1].view(torch.int32), "u": out[:, 2], "v": out[:, 3], "point": out[:, 4:7], "material": out[:, 7].view(torch.int32)}
+    s = _sweep_records(origins_or_sweeps, directions, radius, tmax)
+    n = s.shape[0]
+    out = np.zeros(n, np.uint8) if any_hit else np.zeros(n, SWEEP_DTYPE)
+    if n:
+        bufs = _device_buffers(state, 2, s.nbytes)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], s.ctypes.data, s.nbytes), "copy to device")
+            if any_hit:
+                _check(state.context, L.pt_query_sweep_any(state.context, bufs[0], n, bufs[1]), "pt_query_sweep_any")
+            else:
+                _check(state.context, L.pt_query_sweep(state.context, bufs[0], n, bufs[1]), "pt_query_sweep")
+            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    if any_hit:
+        return out.view(np.bool_)
+    return {k: np.ascontiguousarray(out[k]) for k in SWEEP_DTYPE.names}
+
+
+def sweepContacts(result, sweeps):
+    """What a slide-and-step controller needs of querySweep's answer: (centres, normals, start_overlap) — the sphere's centre at impact
+    o + d * t (n, 3), the unit contact normal (centre - point) / |centre - point| (n, 3), from the surface towards the centre, and where
+    the sphere touched the scene before it moved, t == 0 (n,) bool.  A miss has NaN centres and normals; a centre on the surface itself
+    (radius 0, or a start overlap with the centre on a triangle) has a zero normal.  sweeps: the (n, 8) records the result answers; arrays
+    with arrays, tensors with tensors."""
+    if _is_tensor(sweeps):
+        import torch
+        if sweeps.dim() != 2 or sweeps.shape[1] != 8 or result["t"].shape[0] != sweeps.shape[0]:
+            raise PathTracerError("sweepContacts: expected the (n, 8) sweeps of the result, got shape %s" % (tuple(sweeps.shape),))
+        t = result["t"]
+        hit = t >= 0
+        centre = sweeps[:, 0:3] + sweeps[:, 3:6] * t[:, None]
+        diff = centre - result["point"]
+        length = torch.sqrt((diff * diff).sum(dim=1, keepdim=True))
+        normal = torch.where(length > 0, diff / torch.where(length > 0, length, torch.ones_like(length)), torch.zeros_like(diff))
+        nan = torch.full_like(centre, float("nan"))
+        return torch.where(hit[:, None], centre, nan), torch.where(hit[:, None], normal, nan), t == 0
+    s = np.asarray(sweeps, np.float32)
+    t = np.asarray(result["t"], np.float32)
+    if s.ndim != 2 or s.shape[1] != 8 or t.shape != (s.shape[0],):
+        raise PathTracerError("sweepContacts: expected the (n, 8) sweeps of the result, got shape %s" % (s.shape,))
+    hit = t >= 0
+    with np.errstate(all="ignore"):
+        centre = s[:, 0:3] + s[:, 3:6] * t[:, None]
+        diff = centre - np.asarray(result["point"], np.float32)
+        length = np.sqrt((diff * diff).sum(axis=1, keepdims=True))
+        normal = np.where(length > 0, diff / np.where(length > 0, length, np.float32(1.0)), np.float32(0.0))
+    nan = np.float32(np.nan)
+    return np.where(hit[:, None], centre, nan).astype(np.float32), np.where(hit[:, None], normal, nan).astype(np.float32), t == 0
+
+
 # ------------------------------------------------------------------ ambient occlusion ----
 def aoSamples(K):
     """The default sample pattern of the ambient-occlusion calls: K points of a Vogel spiral on the unit disk, float32 (K, 2):

@@ -536,6 +536,58 @@ int pt_query_nearest(pt_ctx* ctx, const float* points, size_t n, pt_nearest* out
 int pt_query_overlap(pt_ctx* ctx, const float* boxes, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts);
 int pt_query_overlap_any(pt_ctx* ctx, const float* boxes, size_t n, uint8_t* hit);
 
+/* ---- swept-sphere casts on the device (opt-in; nothing above changes) --------------------------------------------------------------
+ * How far a ball of radius r travels along a direction before it touches the mesh, and where it touches: the sphere cast of physics
+ * and robotics libraries — continuous collision, character and camera controllers, path clearance of a round robot, thick rays and
+ * beam-width sensors.  pt_query_nearest's memory and call rules: DEVICE arrays, 16-byte aligned (blocked: any alignment); the call
+ * enqueues on the context's stream and returns synchronised, acts on rank 0 of a pt_create_multi context, never writes the accumulation
+ * buffer, the frame buffer or pt_stats, walks the node array the scene holds (pt_bvh_info.device_bytes as for pt_query_closest) and
+ * uses no atomics: two calls give the same bits.
+ *
+ *   sweeps    n records of 8 floats {ox, oy, oz, dx, dy, dz, radius, tmax}.  The sphere's centre moves along o + t d for
+ *             0 <= t <= tmax, closed at both ends.  d is not normalised and t is in units of its length.  tmax = +inf and radius = 0
+ *             are allowed.
+ *   time of impact of one triangle: the entry of the centre line into the triangle's Minkowski sum with the sphere — a start-overlap
+ *             test, three vertex spheres, three edge cylinders, two offset faces —, the smallest candidate t below.  All fp32, every
+ *             operation on its own, evaluated as written, no fused multiply-add, IEEE division and square root (tests/sweep_ref.py
+ *             is the NumPy statement, equal bit for bit), on the vectors the build stores for the triangle, v0, e1 = v1 - v0,
+ *             e2 = v2 - v0; dot and cross as written under pt_query_closest; x + y * s for vectors is per component, one multiply
+ *             and one add; dd = dot(d, d), rr = r * r:
+ *               start overlap   d2 of pt_query_nearest's closest_on_triangle at o; d2 <= rr: candidate t = 0
+ *               vertex P in (v0, v0 + e1, v0 + e2):
+ *                               m = o - P;  t0 = (-dot(m, d)) / dd;  mp = m + d * t0;  q = (rr - dot(mp, mp)) / dd;  t = t0 - sqrt(q);
+ *                               candidate iff q >= 0 and t >= 0
+ *               edge (A, E) in ((v0, e1), (v0, e2), (v0 + e1, e2 - e1)):
+ *                               m = o - A;  ee = dot(E, E);  md = dot(m, E);  nd = dot(d, E);
+ *                               mp = m - E * (md / ee);  dp = d - E * (nd / ee);  a = dot(dp, dp);
+ *                               t0 = (-dot(mp, dp)) / a;  mq = mp + dp * t0;  q = (rr - dot(mq, mq)) / a;
+ *                               t = t0 - sqrt(q);  s = md + t * nd;
+ *                               candidate iff q >= 0, t >= 0 and 0 <= s <= ee
+ *               face            n = cross(e1, e2);  nn = dot(n, n);  m = o - v0;  s0 = dot(n, m);
+ *                               t = ((s0 >= 0 ? r : -r) * sqrt(nn) - s0) / dot(n, d);  w = m + d * t;
+ *                               u = dot(cross(w, e2), n) / nn;  v = dot(cross(e1, w), n) / nn;
+ *                               candidate iff t >= 0, u >= 0, v >= 0 and u + v <= 1
+ *             The residuals mp, mq are projected before they are squared: the textbook b^2 - a c loses the contact to cancellation
+ *             (DESIGN.md section 28).  Every compare is false on a NaN, so a NaN anywhere makes that feature no candidate: a
+ *             degenerate triangle keeps the features that are defined, and with d = 0 only the start overlap can answer.
+ *   the answer over all triangles, the smallest finite time of impact t <= tmax; ties go to the lowest index in the caller's index-buffer
+ *             order.  The walk's boxes only prune; the winner is decided by the test above alone.
+ *   hits      per sweep {t, prim, u, v, cx, cy, cz, material}: the time of impact, the winning triangle, then pt_query_nearest's
+ *             weights of v1 and v2 and closest point, from closest_on_triangle evaluated once on the winner at the centre
+ *             o + d * t (one multiply and one add per component), and the triangle's material id.  The contact normal is the caller's
+ *             (centre - c) / r.  A miss is {-1, 0xFFFFFFFF, 0, 0, 0, 0, 0, 0xFFFFFFFF}.
+ *   blocked   pt_query_sweep_any: one byte per sweep, 1 iff some triangle has a time of impact t <= tmax (iff hits[i].t >= 0).  A
+ *             sweep's walk ends at its first such triangle: "can the ball move along this segment".
+ *   a miss before any traversal: a non-finite component of o or d, a radius that is NaN, negative or infinite, a NaN or negative
+ *             tmax, a scene without triangles.
+ * Not watertight at shared edges: neighbouring triangles compute a shared edge's cylinder (and a shared vertex's sphere) from their own
+ * stored vectors, and the two times may differ in their last bits; the smaller wins, whichever triangle it belongs to.
+ * n == 0 is a no-op success.  Refused, with the context left usable: n > 0x7FFFFFFF, a null pointer, a misaligned sweeps or hits array,
+ * an output that overlaps the sweeps, a context without a scene.                                                                       */
+typedef struct { float t; uint32_t prim; float u, v; float cx, cy, cz; uint32_t material; } pt_sweep_hit;   /* 32 bytes */
+int pt_query_sweep(pt_ctx* ctx, const float* sweeps, size_t n, pt_sweep_hit* hits);
+int pt_query_sweep_any(pt_ctx* ctx, const float* sweeps, size_t n, uint8_t* blocked);
+
 /* ---- ambient occlusion traced on the device (opt-in; nothing above changes) -----------------------------------------------------
  * The share of the hemisphere over a surface point that is open within `radius`: K rays per point, generated, traced with
  * pt_query_any's walk and counted inside one kernel, so no ray reaches memory.  pt_ao_points takes the points from a device array
