@@ -76,6 +76,7 @@ static int create_one(pt_ctx** out, int device_id)
     pt_ctx* c = new pt_ctx();
     c->device = device_id;
     c->n_cus = prop.multiProcessorCount;
+    c->cu_lds_bytes = prop.maxSharedMemoryPerMultiProcessor;
     memset(&c->stats, 0, sizeof(c->stats));
     if (hipStreamCreate(&c->own_stream) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
         c->d_queue.reserve(8, c->own_stream) != hipSuccess || c->d_counters.reserve((size_t)ptd::kCounterWords, c->own_stream) != hipSuccess) {
@@ -129,7 +130,7 @@ PT_API int pt_create_multi(pt_ctx** out, const int* device_ids, int n_devices)
             delete m;
             return 1;
         }
-        c->rank = i; c->world = n_devices;
+        c->rank = i; c->world = n_devices; c->in_group = true;
         m->ranks.push_back(c);
     }
     if (!m->rehearsal) {
@@ -186,9 +187,13 @@ static void destroy_one(pt_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     ptd::free_lbvh(c->bvh);
     ptd::env_free(c->env);
-    const hipEvent_t ev0 = c->ev0, ev1 = c->ev1;
-    const hipStream_t own_stream = c->own_stream;
+    if (c->small_stream) (void)hipStreamSynchronize(c->small_stream);
+    const hipEvent_t ev0 = c->ev0, ev1 = c->ev1, small_fork = c->small_fork, small_join = c->small_join;
+    const hipStream_t own_stream = c->own_stream, small_stream = c->small_stream;
     delete c;
+    if (small_fork) (void)hipEventDestroy(small_fork);
+    if (small_join) (void)hipEventDestroy(small_join);
+    if (small_stream) (void)hipStreamDestroy(small_stream);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     if (own_stream) (void)hipStreamDestroy(own_stream);
@@ -1132,11 +1137,31 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
     const uint32_t blocks_needed = (waves_needed + wpb - 1) / wpb;
     if (grid > blocks_needed) grid = blocks_needed;
     if (grid < 1) grid = 1;
+    uint32_t total_waves = grid * wpb;
+    // The small-scene path (render_small.hip) stands in for the library's own choice of the default kernel, never for a variant
+    // pt_set_tuning named: light mode 0, no map, the reference material model, no rank of a pt_create_multi group, a tree whose references fit 16 bits and whose
+    // nodes fit a CU's LDS twice beside the stacks of 20 waves.  Per CU one 1024-thread and one 256-thread workgroup, each grid
+    // no larger than the work; the waves of both are numbered through (fold-slot scratch).
+    uint32_t small_big = 0u, small_little = 0u;
+    {
+        const int mode = c->small_mode;      // pt_debug_small_kernel: 1 = off, 2 / 3 = one of the two grids alone
+        if (mode != 1 && c->variant_auto && variant == ptd::kDefaultVariant && c->tune_blocks_per_cu == 0 && c->light_mode == 0 && !env &&
+            c->material_model == PT_MATERIALS_REFERENCE && !c->in_group && c->bvh.hcnodes != nullptr &&
+            ptd::small_eligible(c->bvh.n_nodes, c->bvh.n_tris, c->stack_entries, c->cu_lds_bytes)) {
+            const uint32_t big_wpb = (uint32_t)ptd::kSmallBigThreads / 64u, little_wpb = (uint32_t)ptd::kSmallLittleThreads / 64u;
+            small_big = std::max(1u, std::min((uint32_t)c->n_cus, (waves_needed + big_wpb - 1u) / big_wpb));
+            small_little = std::max(1u, std::min((uint32_t)c->n_cus, (waves_needed + little_wpb - 1u) / little_wpb));
+            if (mode == 2) small_little = 0u;
+            if (mode == 3) small_big = 0u;
+            total_waves = small_big * big_wpb + small_little * little_wpb;
+        }
+    }
+    const bool small = small_big + small_little != 0u;
     {   // a small launch wants small grants: a wave that has fetched its last grant works it off alone, so the launch ends one grant's
         // worth of work after the queue is empty.  The reference's own start-up workload in one launch (512 x 512 x 128 spp: 4.2 M items,
         // 820 per wave) with grants of 256 had a third of the items handed out in the first 60 us and its last wave finishing 1.9 ms after the
         // median one (5.2 ms a launch where eight fused steps take 2.8 each, profiles/r04_wave_timeline_c0.txt): keep >= 16 grants per wave.
-        const uint32_t per_wave = a.total_samples / (grid * wpb);
+        const uint32_t per_wave = a.total_samples / total_waves;
         uint32_t cap = 1u << a.chunk_shift;                         // never below one (pixel, sub-frame) group
         while (cap * 2u * 16u <= per_wave) cap *= 2u;
         if (const char* e = getenv("ACGPT_GRANT")) { const uint32_t v = (uint32_t)atoi(e); if (v >= 1u && v <= (64u << a.chunk_shift)) { a.grant = v; cap = v; } }     // sweeps (a grant is decoded by 64 lanes, one group each: <= 64 groups)
@@ -1144,7 +1169,7 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
     }
 
     if (a.chunk_shift) {   // fold slots for every wave of the grid
-        CK(c, c->d_wave_scratch.reserve((size_t)grid * wpb * ((size_t)ptd::kRenderFoldSlots << a.chunk_shift) * 3, c->stream));
+        CK(c, c->d_wave_scratch.reserve((size_t)total_waves * ((size_t)ptd::kRenderFoldSlots << a.chunk_shift) * 3, c->stream));
         a.wave_scratch = c->d_wave_scratch.p;
     }
     {   // kernels whose LDS stack is capped keep deeper entries here
@@ -1159,8 +1184,25 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
     }
     CK(c, hipMemsetAsync(c->d_queue.p, 0, 8 * sizeof(uint32_t), c->stream));
     CK(c, hipMemsetAsync(c->d_counters.p, 0, (size_t)ptd::kCounterWords * sizeof(unsigned long long), c->stream));
+    if (small && !c->small_stream) {
+        CK(c, hipStreamCreateWithFlags(&c->small_stream, hipStreamNonBlocking));
+        CK(c, hipEventCreateWithFlags(&c->small_fork, hipEventDisableTiming));
+        CK(c, hipEventCreateWithFlags(&c->small_join, hipEventDisableTiming));
+    }
     CK(c, hipEventRecord(c->ev0, c->stream));
-    { Range range("acgpt: render megakernel (launch_batch)"); CK(c, ptd::launch_render(variant, c->math_mode, a, grid, c->stream, &ea, &ga)); }
+    if (small) {
+        // the 1024-thread grid first, on the context's stream; the 256-thread grid on the second stream, behind the memsets above and
+        // joined again ahead of ev1 and k_finalize.  Neither grid waits for the other: both take work from the queue until it is empty.
+        Range range("acgpt: render small-scene kernels (launch_batch)");
+        CK(c, hipEventRecord(c->small_fork, c->stream));
+        CK(c, hipStreamWaitEvent(c->small_stream, c->small_fork, 0));
+        if (small_big) CK(c, ptd::launch_render_small(ptd::kSmallBigThreads, c->math_mode, a, 0u, small_big, c->stream));
+        if (small_little) CK(c, ptd::launch_render_small(ptd::kSmallLittleThreads, c->math_mode, a, small_big * ((uint32_t)ptd::kSmallBigThreads / 64u), small_little, c->small_stream));
+        CK(c, hipEventRecord(c->small_join, c->small_stream));
+        CK(c, hipStreamWaitEvent(c->stream, c->small_join, 0));
+    } else {
+        Range range("acgpt: render megakernel (launch_batch)"); CK(c, ptd::launch_render(variant, c->math_mode, a, grid, c->stream, &ea, &ga));
+    }
     CK(c, hipEventRecord(c->ev1, c->stream));
     { Range range("acgpt: k_finalize"); CK(c, ptd::launch_finalize(a, c->stream)); }
     unsigned long long h[8], h_tail[2] = {0, 0};      // h_tail: culled camera rays; experiments build: workgroups of a wavefront kernel that gave up
@@ -1183,7 +1225,8 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
     c->stats.trav_lane_steps = h[5];
     c->stats.shade_wave_rounds = h[6];
     c->stats.shade_lane_rounds = h[7];
-    c->stats.grid_blocks = grid;
+    c->stats.grid_blocks = small ? small_big + small_little : grid;
+    c->small_last = !small ? 0 : (small_big && small_little) ? 1 : small_big ? 2 : 3;
     c->stats.variant = (uint32_t)variant;
     c->stats.math_mode = (uint32_t)(c->math_mode != 0 && ptd::render_variant_has_fast_math(variant) ? PT_MATH_FAST : PT_MATH_IEEE);
     c->stats.kernel_ms = ms;

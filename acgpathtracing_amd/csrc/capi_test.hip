@@ -4,6 +4,7 @@
 #include "../../include/acgpt_test.h"
 #include "context.h"
 #include "selftest.h"
+#include "small_ref.h"
 
 PT_API int pt_bench_traversal(pt_ctx* c, const float* rays, size_t n, int repeats, int node_format, float* t_out, uint32_t* prim_out, float* ms_out,
                               uint64_t* counters_out)
@@ -137,6 +138,40 @@ PT_API int pt_debug_window_moves(pt_ctx* c, uint64_t* out)
     if (!c || !out) return fail(c, "pt_debug_window_moves: null argument");
     CK(c, hipSetDevice(c->device));
     CK(c, hipMemcpy(out, c->d_counters.p + ptd::kWindowMoves, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- the small-scene path (render_small.hip) ----
+PT_API int pt_debug_small_kernel(pt_ctx* c, int mode)
+{
+    if (!c || mode < 0 || mode > 3) return fail(c, "pt_debug_small_kernel: 0 = automatic, 1 = off, 2 = the 1024-thread grid alone, 3 = the 256-thread grid alone");
+    c->small_mode = mode;
+    return 0;
+}
+
+PT_API int pt_debug_small_kernel_path(pt_ctx* c) { return c ? c->small_last : -1; }
+
+// no context, no GPU: the 16-bit references of small_ref.h for n 32-bit ones
+PT_API int pt_debug_small_ref(const int32_t* refs, size_t n, uint16_t* encoded, int32_t* decoded, int32_t* local)
+{
+    if (!refs || !encoded || !decoded || !local) return 1;
+    for (size_t i = 0; i < n; i++) {
+        encoded[i] = ptd::small_ref_encode(refs[i]);
+        decoded[i] = ptd::small_ref_decode(encoded[i]);
+        local[i] = ptd::small_ref_local(refs[i]);
+    }
+    return 0;
+}
+
+// no context, no GPU: out = {LDS bytes of the 1024-thread workgroup, of the 256-thread workgroup, eligible (0 / 1), node limit, triangle limit}
+PT_API int pt_debug_small_budget(uint32_t n_nodes, uint32_t n_tris, uint32_t stack_entries, uint64_t cu_lds_bytes, uint64_t* out)
+{
+    if (!out) return 1;
+    out[0] = ptd::small_lds_bytes(ptd::kSmallBigThreads, stack_entries, n_nodes);
+    out[1] = ptd::small_lds_bytes(ptd::kSmallLittleThreads, stack_entries, n_nodes);
+    out[2] = ptd::small_eligible(n_nodes, n_tris, stack_entries, (size_t)cu_lds_bytes) ? 1u : 0u;
+    out[3] = ptd::kSmallMaxNodes;
+    out[4] = ptd::kSmallMaxTris;
     return 0;
 }
 

@@ -21,6 +21,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "environment.h"
 #include "lbvh_build.h"
 #include "render_megakernel.h"
+#include "render_small.h"
 
 #define PT_API extern "C" __attribute__((visibility("default")))
 
@@ -78,10 +79,18 @@ struct pt_ctx {
     DevBuf<uint32_t> d_queue;                 // 8 shard heads
     DevBuf<unsigned long long> d_counters;    // ptd::kCounterWords counters
     int rank = 0, world = 1;
+    bool in_group = false;                    // a rank of a pt_create_multi group (rank 0 included)
     int chunks = 0;                           // sample chunks per pixel: 0 = automatic, else 1/2/4/8/16
     DevBuf<float4> d_frame_sums;              // [pixel][sub-frame] of a frame batch
     DevBuf<float> d_wave_scratch;             // fold slots of every wave of the grid
     DevBuf<uint32_t> d_stack_ovf;             // stack entries beyond a kernel's LDS cap
+    // the small-scene path (render_small.hip): the 256-thread grid runs on a stream of its own beside the 1024-thread grid on `stream`;
+    // small_fork / small_join order it behind the launch's memsets and ahead of ev1.  Created on the first launch that takes the path.
+    hipStream_t small_stream = nullptr;
+    hipEvent_t small_fork = nullptr, small_join = nullptr;
+    size_t cu_lds_bytes = 0;                  // hipDeviceProp_t::maxSharedMemoryPerMultiProcessor: what the path's LDS budget is held against
+    int small_mode = 0;                       // pt_debug_small_kernel: 0 automatic, 1 off, 2 / 3 the 1024- / 256-thread grid alone
+    int small_last = 0;                       // what the last launch ran: 0 the variant table's kernel, 1 both grids, 2 / 3 one of them
     size_t scratch_limit = (size_t)1 << 30;   // a frame batch is cut into launches whose frame sums fit
     // division constants of the tile order, valid for (div_width, div_world_n): built and verified once per image width
     uint32_t div_width = 0; int div_world_n = 0; ptd::FastDiv div_cols = {0, 0, 0}, div_world = {0, 0, 0};

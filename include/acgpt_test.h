@@ -81,6 +81,22 @@ int pt_debug_row_spans(const pt_params* params, const float* box_lo, const float
 /* Diagnostic, one value of the last launch: a windowed-stack kernel's moves of stack entries between the LDS window and global
  * memory (wave-level events; 0 for the kernels that keep the whole stack in LDS). */
 int pt_debug_window_moves(pt_ctx* ctx, uint64_t* out);
+/* The small-scene path (csrc/render_small.hip): where the library chose the default kernel itself, light mode 0, no map, the reference
+ * material model, a context of its own (no pt_create_multi group), and the scene's fp16 nodes fit a CU's LDS twice beside the stacks of 20 waves, a launch runs one 1024-thread
+ * and one 256-thread workgroup per CU that read the nodes from LDS.  mode 0: automatic (default); 1: off, the variant table's kernel
+ * as before; 2 / 3: the 1024- / 256-thread grid alone.  Same image bits and counters in every mode; pt_stats.variant stays the variant the path stands in for. */
+int pt_debug_small_kernel(pt_ctx* ctx, int mode);
+/* ... and what the context's last launch ran: 0 the variant table's kernel, 1 both grids, 2 / 3 the 1024- / 256-thread grid alone. */
+int pt_debug_small_kernel_path(pt_ctx* ctx);
+/* The path's 16-bit node references (csrc/small_ref.h), no context, no GPU: for each of n 32-bit references as the tree holds them
+ * (byte offset of an inner node, ~slot of a triangle, 0x7FFFFFFF for "nothing") the 16-bit entry, what it decodes to, and the
+ * sign-extended entry the kernel works on.  HOST arrays of n. */
+int pt_debug_small_ref(const int32_t* refs, size_t n, uint16_t* encoded, int32_t* decoded, int32_t* local);
+/* ... and its LDS budget: out[0], out[1] = dynamic LDS bytes of the 1024- and the 256-thread workgroup for a tree of n_nodes nodes and
+ * stack_entries entries per lane, out[2] = 1 when such a scene with n_tris triangles is eligible on a CU with cu_lds_bytes of LDS (one
+ * workgroup of each kind fits, a second 256-thread one beside them does not, references fit 16 bits), out[3], out[4] = the node and
+ * triangle limits of the references. */
+int pt_debug_small_budget(uint32_t n_nodes, uint32_t n_tris, uint32_t stack_entries, uint64_t cu_lds_bytes, uint64_t* out);
 #ifdef ACGPT_EXPERIMENTS
 /* Experiments library only: walk a renumbered copy of the fp16 nodes (0: the build's order; 1: the two children of a node in one 64-byte
  * line; 2: depth first).  Same bits; an A/B of the memory system on large scenes (profiles/r04_ab_node_order.txt). */
