@@ -25,11 +25,13 @@ CU_LDS = 160 * 1024                                       # MI355X: LDS of a CU
 
 
 class Ctx:
-    def __init__(self, verts, idx, mats, mat_ids, math=FAST):
+    def __init__(self, verts, idx, mats, mat_ids, math=FAST, build_mode=None):
         self.L = L = _native.hip()
         self.ctx = C.c_void_p()
         assert L.pt_create(C.byref(self.ctx), 0) == 0
         assert L.pt_set_math_mode(self.ctx, math) == 0
+        if build_mode is not None:
+            assert L.pt_set_build_mode(self.ctx, build_mode) == 0
         self.verts, self.idx = np.ascontiguousarray(verts, np.float32), np.ascontiguousarray(idx, np.uint32)
         self.mid = np.ascontiguousarray(mat_ids, np.uint32)
         self.mats = (_native.Material * len(mats))(*mats)
