@@ -166,7 +166,8 @@ ABI_SYMBOLS = [
 ]
 # ... and include/acgpt_test.h (test hooks and diagnostics; same library)
 TEST_SYMBOLS = ["pt_bench_traversal", "pt_selftest", "pt_debug_wave_times", "pt_debug_queue_progress", "pt_debug_window_moves", "pt_debug_queue_order", "pt_debug_pixel_classes", "pt_debug_row_spans", "pt_read_morton", "pt_debug_environment", "pt_debug_microfacet", "pt_debug_nearest_visits", "pt_debug_overlap_visits", "pt_debug_sweep_visits", "pt_debug_read_tree",
-                "pt_debug_small_kernel", "pt_debug_small_kernel_path", "pt_debug_small_ref", "pt_debug_small_budget"]
+                "pt_debug_small_kernel", "pt_debug_small_kernel_path", "pt_debug_small_ref", "pt_debug_small_budget",
+                "pt_debug_small_shape", "pt_debug_small_float_budget", "pt_debug_small_staged"]
 
 _hip = None
 _host = None
@@ -285,6 +286,9 @@ def hip():
     L.pt_debug_small_kernel_path.argtypes = [vp]; L.pt_debug_small_kernel_path.restype = C.c_int
     L.pt_debug_small_ref.argtypes = [vp, sz, vp, vp, vp]; L.pt_debug_small_ref.restype = C.c_int
     L.pt_debug_small_budget.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, vp]; L.pt_debug_small_budget.restype = C.c_int
+    L.pt_debug_small_shape.argtypes = [vp, C.c_int]; L.pt_debug_small_shape.restype = C.c_int
+    L.pt_debug_small_float_budget.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, vp]; L.pt_debug_small_float_budget.restype = C.c_int
+    L.pt_debug_small_staged.argtypes = [vp, vp, sz]; L.pt_debug_small_staged.restype = C.c_int
     if hasattr(L, "pt_debug_node_order"):      # experiments library only
         L.pt_debug_node_order.argtypes = [vp, C.c_int]; L.pt_debug_node_order.restype = C.c_int
     if hasattr(L, "pt_debug_wf"):      # experiments library only

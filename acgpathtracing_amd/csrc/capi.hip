@@ -1157,6 +1157,7 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
         }
     }
     const bool small = small_big + small_little != 0u;
+    int small_shape = ptd::kSmallShapeNone;
     {   // a small launch wants small grants: a wave that has fetched its last grant works it off alone, so the launch ends one grant's
         // worth of work after the queue is empty.  The reference's own start-up workload in one launch (512 x 512 x 128 spp: 4.2 M items,
         // 820 per wave) with grants of 256 had a third of the items handed out in the first 60 us and its last wave finishing 1.9 ms after the
@@ -1196,8 +1197,16 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
         Range range("acgpt: render small-scene kernels (launch_batch)");
         CK(c, hipEventRecord(c->small_fork, c->stream));
         CK(c, hipStreamWaitEvent(c->small_stream, c->small_fork, 0));
-        if (small_big) CK(c, ptd::launch_render_small(ptd::kSmallBigThreads, c->math_mode, a, 0u, small_big, c->stream));
-        if (small_little) CK(c, ptd::launch_render_small(ptd::kSmallLittleThreads, c->math_mode, a, small_big * ((uint32_t)ptd::kSmallBigThreads / 64u), small_little, c->small_stream));
+        // Which shape: the 1024-thread workgroup with the nodes as fp32 and the 256-thread workgroup without a copy where that budget
+        // fits the CU (20 of the pairs small_eligible admits miss it by KB rounding), the fp16 copy in both otherwise.
+        const ptd::SmallFloatBudget fb = ptd::small_float_budget(c->stack_entries, c->bvh.n_nodes, c->cu_lds_bytes);
+        const char* const env_half = getenv("ACGPT_SMALL_FP16");      // A/B of the two shapes under bench.py, as ACGPT_GRANT above
+        const bool f32 = fb.fits && !c->small_force_half && !(env_half && env_half[0] == '1');
+        small_shape = f32 ? ptd::kSmallShapeFloat : ptd::kSmallShapeHalf;
+        const size_t big_lds = f32 ? fb.big : ptd::small_lds_bytes(ptd::kSmallBigThreads, c->stack_entries, c->bvh.n_nodes);
+        const size_t little_lds = f32 ? fb.little_request : ptd::small_lds_bytes(ptd::kSmallLittleThreads, c->stack_entries, c->bvh.n_nodes);
+        if (small_big) CK(c, ptd::launch_render_small(ptd::kSmallBigThreads, c->math_mode, f32 ? ptd::kSmallNodesFloatLds : ptd::kSmallNodesHalfLds, big_lds, a, 0u, small_big, c->stream));
+        if (small_little) CK(c, ptd::launch_render_small(ptd::kSmallLittleThreads, c->math_mode, f32 ? ptd::kSmallNodesHalfGlobal : ptd::kSmallNodesHalfLds, little_lds, a, small_big * ((uint32_t)ptd::kSmallBigThreads / 64u), small_little, c->small_stream));
         CK(c, hipEventRecord(c->small_join, c->small_stream));
         CK(c, hipStreamWaitEvent(c->stream, c->small_join, 0));
     } else {
@@ -1227,6 +1236,7 @@ static int launch_batch(pt_ctx* c, const pt_params* p, uint32_t n_frames)
     c->stats.shade_lane_rounds = h[7];
     c->stats.grid_blocks = small ? small_big + small_little : grid;
     c->small_last = !small ? 0 : (small_big && small_little) ? 1 : small_big ? 2 : 3;
+    c->small_shape_last = small_shape;
     c->stats.variant = (uint32_t)variant;
     c->stats.math_mode = (uint32_t)(c->math_mode != 0 && ptd::render_variant_has_fast_math(variant) ? PT_MATH_FAST : PT_MATH_IEEE);
     c->stats.kernel_ms = ms;

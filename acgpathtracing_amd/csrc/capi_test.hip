@@ -175,6 +175,41 @@ PT_API int pt_debug_small_budget(uint32_t n_nodes, uint32_t n_tris, uint32_t sta
     return 0;
 }
 
+// force: 0 the fp32 shape where its budget fits (default), 1 the fp16 two-copy shape always, -1 leave as it is.  Returns the shape of the last launch.
+PT_API int pt_debug_small_shape(pt_ctx* c, int force)
+{
+    if (!c) return -1;
+    if (force < -1 || force > 1) { fail(c, "pt_debug_small_shape: force = -1 (ask only), 0 (automatic) or 1 (the fp16 shape)"); return -1; }
+    if (force >= 0) c->small_force_half = force;
+    return c->small_shape_last;
+}
+
+// no context, no GPU: out = {LDS bytes of the 1024-thread workgroup with fp32 nodes, of the 256-thread workgroup without nodes, what the
+// 256-thread launch asks for, fits (0 / 1)}
+PT_API int pt_debug_small_float_budget(uint32_t n_nodes, uint32_t stack_entries, uint64_t cu_lds_bytes, uint64_t* out)
+{
+    if (!out) return 1;
+    const ptd::SmallFloatBudget b = ptd::small_float_budget(stack_entries, n_nodes, (size_t)cu_lds_bytes);
+    out[0] = b.big; out[1] = b.little; out[2] = b.little_request; out[3] = b.fits ? 1u : 0u;
+    return 0;
+}
+
+// the kernel's own staging function over the scene's fp16 nodes, into a HOST buffer of 64 bytes a node
+PT_API int pt_debug_small_staged(pt_ctx* c, void* out, size_t capacity_bytes)
+{
+    if (!c || !out) return fail(c, "pt_debug_small_staged: null argument");
+    const ptd::LbvhResult& b = c->bvh;
+    if (!c->scene_kept || b.n_tris == 0 || !b.hcnodes) return fail(c, "pt_debug_small_staged: no fp16 nodes held (pt_set_scene with triangles first)");
+    if (b.n_nodes > ptd::kSmallMaxNodes) return fail(c, "pt_debug_small_staged: more nodes than the 16-bit references reach");
+    const size_t bytes = (size_t)b.n_nodes * ptd::kSmallFloatNodeBytes;
+    if (capacity_bytes < bytes) return fail(c, "pt_debug_small_staged: capacity " + std::to_string(capacity_bytes) + " bytes, the staged nodes take " + std::to_string(bytes));
+    CK(c, hipSetDevice(c->device));
+    const uint32_t no_input = 0u;      // the nodes are on the device already
+    return device_round_trip(c, "pt_debug_small_staged", &no_input, sizeof(no_input), out, bytes, nullptr, 0, [&](void*, void* d_out, void*) {
+        return ptd::launch_small_stage_f32(b.hcnodes, b.n_nodes, d_out, c->stream);
+    });
+}
+
 #ifdef ACGPT_EXPERIMENTS
 // experiments build only: renumber the resident fp16 nodes (0: the build's order, 1: sibling pairs share a 64-byte line, 2: depth first)
 namespace ptd { bool reorder_records_dfs(LbvhResult& r, hipStream_t stream, std::string& err); }      // lbvh_experiments.inc

@@ -91,6 +91,8 @@ struct pt_ctx {
     size_t cu_lds_bytes = 0;                  // hipDeviceProp_t::maxSharedMemoryPerMultiProcessor: what the path's LDS budget is held against
     int small_mode = 0;                       // pt_debug_small_kernel: 0 automatic, 1 off, 2 / 3 the 1024- / 256-thread grid alone
     int small_last = 0;                       // what the last launch ran: 0 the variant table's kernel, 1 both grids, 2 / 3 one of them
+    int small_force_half = 0;                 // pt_debug_small_shape: 1 keeps the fp16 two-copy shape where the fp32 shape would fit
+    int small_shape_last = 0;                 // ptd::kSmallShape* of the last launch
     size_t scratch_limit = (size_t)1 << 30;   // a frame batch is cut into launches whose frame sums fit
     // division constants of the tile order, valid for (div_width, div_world_n): built and verified once per image width
     uint32_t div_width = 0; int div_world_n = 0; ptd::FastDiv div_cols = {0, 0, 0}, div_world = {0, 0, 0};

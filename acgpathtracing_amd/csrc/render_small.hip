@@ -24,6 +24,13 @@
 //   together: 2 x N x 32  +  20 waves x 64 lanes x S x 2 B  +  20 books of 320 B  +  2 LCG tables of 256 B.
 // Cornell boxes (N = 1263, S = 24): 94 944 + 54 240 = 149 184 B of the CU's 163 840: one of each fits, and a second 256-thread
 // workgroup (54 240 B more) does not, so a CU never holds two small workgroups in the place of the large one.
+//
+// That is the fp16 shape (kSmallShapeHalf), which decides whether a scene takes the path at all.  Inside the path a launch takes the
+// fp32 shape (kSmallShapeFloat, render_small.h) where its budget fits (small_float_budget):
+//   1024-thread workgroup: 16 x (S x 128 + 320)  +  N x 64  +  256      nodes as fp32: the visit's fp16 -> fp32 conversions done once, at staging
+//    256-thread workgroup:  4 x (S x 128 + 320)  +  256                 no copy: the fp16 nodes from global memory, as variant 7 reads them
+// Cornell boxes: 135 360 + 13 824 = 149 184 B, the same sum.  The 256-thread launch asks for more than it lays out — just over half
+// of what the large workgroup leaves free — so that a second one never fits beside the first.
 #include "render_common.h"
 #include "render_small.h"
 #include "small_ref.h"
@@ -49,7 +56,44 @@ __device__ __forceinline__ void small_node(const char* p, uint4& a, uint4& b)
     a = make_uint4(va.x, va.y, va.z, va.w); b = make_uint4(vb.x, vb.y, vb.z, vb.w);
 }
 
+
+// ---- kSmallNodesFloatLds: the nodes as fp32 ----
+// Each 16-byte half of an HNode {cx | hx << 16, cy | hy << 16, cz | hz << 16, child} becomes two 16-byte records,
+// {(float)cx, (float)cy, (float)cz, child in the local form of small_ref.h} and {(float)hx, (float)hy, (float)hz, 0}: a node is 64
+// bytes, at node << 2 from the same 16-bit reference.  The conversion is exact, so fma((float)h, mul, add) on the staged float is
+// the fma slab_hc does on the half.  The one staging code of the kernel and of pt_debug_small_staged.
+__device__ __forceinline__ void small_stage_f32(uint4* dst, const uint4* src, uint32_t n_halves, uint32_t first, uint32_t stride)
+{
+    for (uint32_t i = first; i < n_halves; i += stride) {
+        const uint4 v = src[i];
+        const half2_t hx = __builtin_bit_cast(half2_t, v.x), hy = __builtin_bit_cast(half2_t, v.y), hz = __builtin_bit_cast(half2_t, v.z);
+        dst[2u * i] = make_uint4(__float_as_uint((float)hx.x), __float_as_uint((float)hy.x), __float_as_uint((float)hz.x), (uint32_t)small_ref_local((int)v.w));
+        dst[2u * i + 1u] = make_uint4(__float_as_uint((float)hx.y), __float_as_uint((float)hy.y), __float_as_uint((float)hz.y), 0u);
+    }
+}
+// the four records of a staged node as four ds_read_b128 (small_node's reason for the LDS-typed pointer holds here too)
+__device__ __forceinline__ void small_node_f32(const char* p, uint4& ca, uint4& ha, uint4& cb, uint4& hb)
+{
+    const __attribute__((address_space(3))) small_v4u* q = (const __attribute__((address_space(3))) small_v4u*)p;
+    const small_v4u v0 = q[0], v1 = q[1], v2 = q[2], v3 = q[3];
+    ca = make_uint4(v0.x, v0.y, v0.z, v0.w); ha = make_uint4(v1.x, v1.y, v1.z, v1.w);
+    cb = make_uint4(v2.x, v2.y, v2.z, v2.w); hb = make_uint4(v3.x, v3.y, v3.z, v3.w);
+}
+// slab_hc (pt_device.h) on the staged floats, operation for operation: the conservativeness proof (pt_selftest op 19) is of this formula
+__device__ __forceinline__ void slab_hc_f32(const uint4& c, const uint4& h, const f3& mul, const f3& add, float rtmin, float& tn, float& tf)
+{
+    const float cx = __builtin_fmaf(__uint_as_float(c.x), mul.x, add.x), cy = __builtin_fmaf(__uint_as_float(c.y), mul.y, add.y), cz = __builtin_fmaf(__uint_as_float(c.z), mul.z, add.z);
+    const float ex = __builtin_fmaf(__uint_as_float(h.x), fabsf(mul.x), 0.0f), ey = __builtin_fmaf(__uint_as_float(h.y), fabsf(mul.y), 0.0f), ez = __builtin_fmaf(__uint_as_float(h.z), fabsf(mul.z), 0.0f);
+    tn = fmaxf(fmaxf(cx - ex, cy - ey), fmaxf(cz - ez, rtmin));
+    tf = fminf(fminf(cx + ex, cy + ey), cz + ez) * kFarWiden;
+}
+
 #include "render_small.inc"
+
+__global__ void __launch_bounds__(256) k_small_stage_f32(const uint4* src, uint32_t n_halves, uint4* dst)
+{
+    small_stage_f32(dst, src, n_halves, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
 
 constexpr size_t kSmallFixedPerWave = (size_t)kBookDwords * 4u, kSmallFixedPerGroup = 256u;
 constexpr size_t kSmallWaves = (size_t)(kSmallBigThreads + kSmallLittleThreads) / 64u;
@@ -76,30 +120,63 @@ bool small_eligible(uint32_t n_nodes, uint32_t n_tris, uint32_t stack_entries, s
     return big + 2u * little > cu_lds_bytes;                         // ... and a second 256-thread workgroup beside them must not
 }
 
-typedef void (*SmallKernel)(const SmallArgsBox);
-static SmallKernel small_kernel(int threads, int math)
+SmallFloatBudget small_float_budget(uint32_t stack_entries, uint32_t n_nodes, size_t cu_lds_bytes)
 {
-    if (threads == kSmallBigThreads) return math != 0 ? k_render_small<kSmallBigThreads, 1> : k_render_small<kSmallBigThreads, 0>;
-    return math != 0 ? k_render_small<kSmallLittleThreads, 1> : k_render_small<kSmallLittleThreads, 0>;
-}
-const char* small_kernel_name(int threads, int math)
-{
-    if (threads == kSmallBigThreads) return math != 0 ? "k_render_small<1024, 1>" : "k_render_small<1024, 0>";
-    return math != 0 ? "k_render_small<256, 1>" : "k_render_small<256, 0>";
+    const auto kb = [](size_t b) { return (b + 1023u) & ~(size_t)1023u; };
+    const auto bare = [&](int threads) { return (size_t)threads / 64u * ((size_t)stack_entries * 64u * sizeof(uint16_t) + kSmallFixedPerWave) + kSmallFixedPerGroup; };
+    SmallFloatBudget b;
+    b.big = bare(kSmallBigThreads) + (size_t)n_nodes * kSmallFloatNodeBytes;
+    b.little = bare(kSmallLittleThreads);
+    b.fits = kb(b.big) + kb(b.little) <= cu_lds_bytes;
+    // just over half of what the 1024-thread workgroup leaves free, in 16-byte steps: two of them are more than is left
+    const size_t half_free = b.big < cu_lds_bytes ? (((cu_lds_bytes - b.big) / 2u + 16u) & ~(size_t)15u) : 0u;
+    b.little_request = b.little > half_free ? b.little : half_free;
+    return b;
 }
 
-hipError_t launch_render_small(int threads, int math, const RenderArgs& args, uint32_t wave0, uint32_t grid_blocks, hipStream_t stream)
+typedef void (*SmallKernel)(const SmallArgsBox);
+static SmallKernel small_kernel(int threads, int math, int nodes)
+{
+    if (threads == kSmallBigThreads) {
+        if (nodes == kSmallNodesFloatLds) return math != 0 ? k_render_small<kSmallBigThreads, 1, kSmallNodesFloatLds> : k_render_small<kSmallBigThreads, 0, kSmallNodesFloatLds>;
+        if (nodes == kSmallNodesHalfLds) return math != 0 ? k_render_small<kSmallBigThreads, 1, kSmallNodesHalfLds> : k_render_small<kSmallBigThreads, 0, kSmallNodesHalfLds>;
+        return nullptr;
+    }
+    if (nodes == kSmallNodesHalfGlobal) return math != 0 ? k_render_small<kSmallLittleThreads, 1, kSmallNodesHalfGlobal> : k_render_small<kSmallLittleThreads, 0, kSmallNodesHalfGlobal>;
+    if (nodes == kSmallNodesHalfLds) return math != 0 ? k_render_small<kSmallLittleThreads, 1, kSmallNodesHalfLds> : k_render_small<kSmallLittleThreads, 0, kSmallNodesHalfLds>;
+    return nullptr;
+}
+const char* small_kernel_name(int threads, int math, int nodes)
+{
+    static const char* const names[2][2][3] = {
+        {{"k_render_small<1024, 0, 0>", "k_render_small<1024, 0, 1>", ""}, {"k_render_small<1024, 1, 0>", "k_render_small<1024, 1, 1>", ""}},
+        {{"k_render_small<256, 0, 0>", "", "k_render_small<256, 0, 2>"}, {"k_render_small<256, 1, 0>", "", "k_render_small<256, 1, 2>"}}};
+    if (nodes < 0 || nodes > 2) return "";
+    return names[threads == kSmallBigThreads ? 0 : 1][math != 0 ? 1 : 0][nodes];
+}
+
+hipError_t launch_render_small(int threads, int math, int nodes, size_t lds, const RenderArgs& args, uint32_t wave0, uint32_t grid_blocks, hipStream_t stream)
 {
     if ((threads != kSmallBigThreads && threads != kSmallLittleThreads) || grid_blocks == 0u) return hipErrorInvalidValue;
     if (args.n_lds_nodes < 1u || args.n_lds_nodes > kSmallMaxNodes || args.scene.n_tris > kSmallMaxTris || args.scene.hcnodes == nullptr) return hipErrorInvalidValue;
-    const SmallKernel k = small_kernel(threads, math);
-    const size_t lds = small_lds_bytes(threads, args.stack_entries, args.n_lds_nodes);
+    const SmallKernel k = small_kernel(threads, math, nodes);
+    if (k == nullptr) return hipErrorInvalidValue;
+    // never less LDS than the kernel lays out: stacks, books and LCG table, and the copy of the nodes in the form it stages
+    const size_t node_bytes = nodes == kSmallNodesHalfLds ? sizeof(HNode) : nodes == kSmallNodesFloatLds ? kSmallFloatNodeBytes : 0u;
+    if (lds < small_lds_bytes(threads, args.stack_entries, 0u) + (size_t)args.n_lds_nodes * node_bytes) return hipErrorInvalidValue;
     hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     SmallArgsBox box;
     box.a[0] = args;
     box.wave0 = wave0;
     hipLaunchKernelGGL(k, dim3(grid_blocks), dim3(threads), lds, stream, box);
+    return hipGetLastError();
+}
+
+hipError_t launch_small_stage_f32(const HNode* hcnodes, uint32_t n_nodes, void* out, hipStream_t stream)
+{
+    if (hcnodes == nullptr || out == nullptr || n_nodes < 1u || n_nodes > kSmallMaxNodes) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_small_stage_f32, dim3((n_nodes * 2u + 255u) / 256u), dim3(256), 0, stream, (const uint4*)hcnodes, n_nodes * 2u, (uint4*)out);
     return hipGetLastError();
 }
 

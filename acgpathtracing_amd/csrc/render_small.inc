@@ -8,7 +8,11 @@
 //   * the wave's number in the grid (fold-slot scratch) starts at B.wave0, so that two launches can share one RenderArgs.
 // LDS of a workgroup, in this order: lane stacks (waves x stack_entries x 128 B), nodes (n_lds_nodes x 32 B), LCG table (256 B),
 // fold books (waves x kBookDwords x 4 B) — small_lds_bytes() in render_small.hip.
-template <int THREADS, int MATH>
+// NODES (render_small.h) says where the nodes are.  kSmallNodesHalfLds is the above.  kSmallNodesFloatLds: the copy holds every fp16
+// number as the float it converts to (small_stage_f32: n_lds_nodes x 64 B, a node at node << 2), a visit is four ds_read_b128 and
+// slab_hc_f32, whose twelve v_fma_f32 give the bits of slab_hc's twelve v_fma_mix_f32 at full rate.  kSmallNodesHalfGlobal: no copy;
+// a visit reads the fp16 node from sc.hcnodes as variant 7 does and halves an inner child's byte offset on the way to the stack.
+template <int THREADS, int MATH, int NODES>
 __global__ void __launch_bounds__(THREADS, 5)
 k_render_small(const SmallArgsBox B)
 {
@@ -24,12 +28,15 @@ k_render_small(const SmallArgsBox B)
     const DeviceScene sc = A.scene;
     // the nodes behind the stacks, 32 bytes apart as in global memory; a child word becomes its local form on the way in
     const char* const lds_nodes = (const char*)(lds_dyn + WAVES * (entries * 32u));
-    {
+    if constexpr (NODES == kSmallNodesHalfLds) {
         uint4* dst = (uint4*)(lds_dyn + WAVES * (entries * 32u));
         const uint4* src = (const uint4*)sc.hcnodes;
         for (uint32_t i = threadIdx.x; i < A.n_lds_nodes * 2u; i += THREADS) { uint4 v = src[i]; v.w = (uint32_t)small_ref_local((int)v.w); dst[i] = v; }
+    } else if constexpr (NODES == kSmallNodesFloatLds) {
+        small_stage_f32((uint4*)(lds_dyn + WAVES * (entries * 32u)), (const uint4*)sc.hcnodes, A.n_lds_nodes * 2u, threadIdx.x, THREADS);
     }
-    uint32_t* const lcg_skip = lds_dyn + WAVES * (entries * 32u) + A.n_lds_nodes * 8u;
+    constexpr uint32_t NODE_DWORDS = NODES == kSmallNodesHalfLds ? 8u : NODES == kSmallNodesFloatLds ? 16u : 0u;      // of the copy in LDS
+    uint32_t* const lcg_skip = lds_dyn + WAVES * (entries * 32u) + A.n_lds_nodes * NODE_DWORDS;
     if (threadIdx.x < 32u) { lcg_skip[2u * threadIdx.x] = A.lcg_mul[threadIdx.x]; lcg_skip[2u * threadIdx.x + 1u] = A.lcg_add[threadIdx.x]; }
     const WaveBook book = wave_book(lcg_skip + 64u + wave * kBookDwords, lane);
     __syncthreads();
@@ -175,11 +182,27 @@ k_render_small(const SmallArgsBox B)
             for (int visit = 0; visit < INNER; visit++)
             if ((uint32_t)node < (uint32_t)kSmallSentinel) {
                 float n0, f0, n1, f1;
-                uint4 qa, qb;
-                small_node(lds_nodes + ((uint32_t)node << 1), qa, qb);
-                const int c0 = (int)qa.w, c1 = (int)qb.w;
-                slab_hc(qa.x, qa.y, qa.z, rinv, gro, rtmin, n0, f0);
-                slab_hc(qb.x, qb.y, qb.z, rinv, gro, rtmin, n1, f1);
+                int c0, c1;
+                if constexpr (NODES == kSmallNodesFloatLds) {
+                    uint4 ca, ha, cb, hb;
+                    small_node_f32(lds_nodes + ((uint32_t)node << 2), ca, ha, cb, hb);
+                    c0 = (int)ca.w; c1 = (int)cb.w;
+                    slab_hc_f32(ca, ha, rinv, gro, rtmin, n0, f0);
+                    slab_hc_f32(cb, hb, rinv, gro, rtmin, n1, f1);
+                } else if constexpr (NODES == kSmallNodesHalfGlobal) {
+                    // as variant 7 reads them; min(c >> 1, c) is small_ref_local(c) for every word a node holds: ~slot stays, a byte offset is halved
+                    const uint4* np = (const uint4*)((const char*)sc.hcnodes + (size_t)((uint32_t)node << 1));
+                    const uint4 qa = np[0], qb = np[1];
+                    c0 = min((int)qa.w >> 1, (int)qa.w); c1 = min((int)qb.w >> 1, (int)qb.w);
+                    slab_hc(qa.x, qa.y, qa.z, rinv, gro, rtmin, n0, f0);
+                    slab_hc(qb.x, qb.y, qb.z, rinv, gro, rtmin, n1, f1);
+                } else {
+                    uint4 qa, qb;
+                    small_node(lds_nodes + ((uint32_t)node << 1), qa, qb);
+                    c0 = (int)qa.w; c1 = (int)qb.w;
+                    slab_hc(qa.x, qa.y, qa.z, rinv, gro, rtmin, n0, f0);
+                    slab_hc(qb.x, qb.y, qb.z, rinv, gro, rtmin, n1, f1);
+                }
                 f0 = fminf(f0, best_t * kTieWiden);
                 f1 = fminf(f1, best_t * kTieWiden);
                 const bool h0 = n0 <= f0, h1 = n1 <= f1;

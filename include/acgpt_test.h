@@ -97,6 +97,21 @@ int pt_debug_small_ref(const int32_t* refs, size_t n, uint16_t* encoded, int32_t
  * workgroup of each kind fits, a second 256-thread one beside them does not, references fit 16 bits), out[3], out[4] = the node and
  * triangle limits of the references. */
 int pt_debug_small_budget(uint32_t n_nodes, uint32_t n_tris, uint32_t stack_entries, uint64_t cu_lds_bytes, uint64_t* out);
+/* Inside the path a launch has one of two shapes.  2: the 1024-thread workgroup holds the nodes as fp32 (64 bytes a node: every fp16
+ * number converted once, at staging, instead of at every visit) and the 256-thread workgroup holds no copy and reads the fp16 nodes
+ * from global memory; taken where that budget fits the CU.  1: both workgroups hold the fp16 nodes, as described above; the fallback.
+ * Returns the shape of the context's last launch (0: it did not take the path; -1: bad argument), and sets which to take from now on:
+ * force 0 automatic (default), 1 the fp16 shape always, -1 no change.  Same image bits and counters either way. */
+int pt_debug_small_shape(pt_ctx* ctx, int force);
+/* ... the budget of shape 2, no context, no GPU: out[0] = LDS bytes of the 1024-thread workgroup (stacks, books, LCG table, n_nodes x
+ * 64), out[1] = of the 256-thread workgroup (stacks, books, LCG table), out[2] = what the 256-thread launch asks for: out[1] padded
+ * to just over half of what the 1024-thread workgroup leaves free, so that out[0] + 2 x out[2] > cu_lds_bytes and a CU never holds
+ * two of them, out[3] = 1 when out[0] and out[1], each counted up to a whole KB, fit cu_lds_bytes together. */
+int pt_debug_small_float_budget(uint32_t n_nodes, uint32_t stack_entries, uint64_t cu_lds_bytes, uint64_t* out);
+/* ... and the fp32 nodes as the 1024-thread workgroup stages them, by the kernel's own staging function run over the scene's fp16
+ * nodes: 64 bytes a node into a HOST buffer; per child {(float) centre x, y, z, child reference in the 16-bit local form} and
+ * {(float) half extent x, y, z, 0}. */
+int pt_debug_small_staged(pt_ctx* ctx, void* out, size_t capacity_bytes);
 #ifdef ACGPT_EXPERIMENTS
 /* Experiments library only: walk a renumbered copy of the fp16 nodes (0: the build's order; 1: the two children of a node in one 64-byte
  * line; 2: depth first).  Same bits; an A/B of the memory system on large scenes (profiles/r04_ab_node_order.txt). */
