@@ -165,7 +165,7 @@ ABI_SYMBOLS = [
     "pt_host_malloc_mapped", "pt_host_free_mapped", "pt_abi_version",
 ]
 # ... and include/acgpt_test.h (test hooks and diagnostics; same library)
-TEST_SYMBOLS = ["pt_bench_traversal", "pt_selftest", "pt_debug_wave_times", "pt_debug_queue_progress", "pt_debug_window_moves", "pt_debug_queue_order", "pt_debug_pixel_classes", "pt_debug_row_spans", "pt_read_morton", "pt_debug_environment", "pt_debug_microfacet", "pt_debug_nearest_visits", "pt_debug_overlap_visits", "pt_debug_sweep_visits", "pt_debug_read_tree",
+TEST_SYMBOLS = ["pt_bench_traversal", "pt_selftest", "pt_debug_wave_times", "pt_debug_queue_progress", "pt_debug_window_moves", "pt_debug_queue_order", "pt_debug_pixel_classes", "pt_debug_row_spans", "pt_read_morton", "pt_debug_environment", "pt_debug_environment_tables", "pt_debug_microfacet", "pt_debug_nearest_visits", "pt_debug_overlap_visits", "pt_debug_sweep_visits", "pt_debug_read_tree",
                 "pt_debug_small_kernel", "pt_debug_small_kernel_path", "pt_debug_small_ref", "pt_debug_small_budget",
                 "pt_debug_small_shape", "pt_debug_small_float_budget", "pt_debug_small_staged"]
 
@@ -268,6 +268,7 @@ def hip():
     L.pt_update_materials.argtypes = [vp, vp, sz, vp, sz, C.POINTER(UpdateInfo)]; L.pt_update_materials.restype = C.c_int
     L.pt_set_environment.argtypes = [vp, vp, C.c_uint32, C.c_uint32, Float3]; L.pt_set_environment.restype = C.c_int
     L.pt_debug_environment.argtypes = [vp, C.c_int, vp, sz, vp]; L.pt_debug_environment.restype = C.c_int
+    L.pt_debug_environment_tables.argtypes = [vp, vp, vp, vp, vp, vp]; L.pt_debug_environment_tables.restype = C.c_int
     L.pt_set_material_model.argtypes = [vp, C.c_int]; L.pt_set_material_model.restype = C.c_int
     L.pt_display_transform.argtypes = [vp, vp, sz, C.POINTER(DisplayParams), vp, vp, C.POINTER(DisplayInfo)]; L.pt_display_transform.restype = C.c_int
     L.pt_convergence_update.argtypes = [vp, C.POINTER(PathTraceParams), C.c_uint32, C.POINTER(ConvergenceParams), vp, vp, vp, C.POINTER(ConvergenceInfo)]

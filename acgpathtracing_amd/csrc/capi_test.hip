@@ -77,6 +77,25 @@ PT_API int pt_debug_environment(pt_ctx* c, int op, const float* in, size_t n, fl
     });
 }
 
+// The map's tables as the device holds them (environment.hip builds them): device-to-host copies only, no kernel, nothing is built.
+PT_API int pt_debug_environment_tables(pt_ctx* c, float* texels, float* marginal, float* conditional, float* info2, uint32_t* dims2)
+{
+    if (!c) { fail(nullptr, "pt_debug_environment_tables: null context"); return -1; }
+    const ptd::EnvDevice& e = c->env;
+    const bool set = e.w != 0u && e.texels != nullptr;
+    if (dims2) { dims2[0] = set ? e.w : 0u; dims2[1] = set ? e.h : 0u; }
+    if (!set) return 0;
+    const size_t n = (size_t)e.w * e.h;
+    hipError_t rc = hipSetDevice(c->device);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(c->stream);
+    if (rc == hipSuccess && texels) rc = hipMemcpy(texels, e.texels, n * sizeof(float4), hipMemcpyDeviceToHost);
+    if (rc == hipSuccess && marginal) rc = hipMemcpy(marginal, e.marginal, (size_t)e.h * sizeof(float), hipMemcpyDeviceToHost);
+    if (rc == hipSuccess && conditional) rc = hipMemcpy(conditional, e.conditional, n * sizeof(float), hipMemcpyDeviceToHost);
+    if (rc != hipSuccess) { fail(c, std::string("pt_debug_environment_tables: ") + hipGetErrorString(rc)); return -1; }
+    if (info2) { info2[0] = e.total; info2[1] = e.pdf_scale; }
+    return 1;
+}
+
 PT_API int pt_debug_microfacet(pt_ctx* c, int op, const float* in, size_t n, float* out)
 {
     static const int out_dw[2] = {8, 4};

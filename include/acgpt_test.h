@@ -126,6 +126,13 @@ int pt_debug_wf(pt_ctx* ctx, uint64_t* out);
  * queries, HOST arrays.  op 0: unit direction {x, y, z} -> {r, g, b, texel index (-1 without a map)}; op 1: direction -> solid-angle
  * pdf of the map's sampling; op 2: {u1, u2} in [0, 1)^2 -> {x, y, z, pdf} of the sampled direction (pdf 0: nothing to sample). */
 int pt_debug_environment(pt_ctx* ctx, int op, const float* in, size_t n, float* out);
+/* The tables of the context's map as the device holds them right now (csrc/environment.hip builds them), copied to HOST arrays:
+ * texels float[h][w][4] = {r, g, b with the scale applied, the sampling weight the kernel wrote}, marginal float[h], conditional
+ * float[h][w], info2 = {total weight, pdf_scale}.  A NULL pointer skips that array.  Device-to-host copies after a stream
+ * synchronisation only: no kernel, nothing is built or released.  dims2 (may be NULL) = {width, height}, {0, 0} without a map.
+ * Returns 1 when a map is set and the arrays were filled, 0 when none is (the arrays are left alone), -1 for a null context or a
+ * failed copy (the text is in pt_last_error).  A pt_create_multi context reads rank 0.  tests/test_gpu_env_wide.py. */
+int pt_debug_environment_tables(pt_ctx* ctx, float* texels, float* marginal, float* conditional, float* info2, uint32_t* dims2);
 /* The microfacet BSDF of pt_set_material_model(1) (csrc/pt_microfacet.h) in the context's math mode, for n items of 9 floats,
  * normal (0, 0, 1) face-forwarded to wo (wo.z < 0: leaving a dielectric's inside):
  *   op 0: {wo[3], alpha, ior, bsdf, u1, u2, u3} -> {wi[3], weight[3], pdf, lobe (0 ended, 1 reflection, 2 transmission)}

@@ -207,14 +207,13 @@ def test_black_map_changes_no_bit(math):
 
 
 # ---- 3. a constant map is what a camera facing away sees --------------------------------------------------------------------------
-@pytest.mark.parametrize("classes", [1, 0])
-@pytest.mark.parametrize("light", [0, 1])
-def test_constant_map_is_seen_exactly(classes, light):
+def constant_map_is_seen_exactly(classes, light, shape=(4, 8)):
+    """the test below for a map of `shape` (h, w); tests/test_gpu_env_wide.py runs it with a map wider than the scan's workgroup"""
     c = Ctx.box(light=light)
     try:
         assert c.L.pt_debug_pixel_classes(c.ctx, classes) == 0
         col = np.array([0.25, 1.5, 3.0], np.float32)
-        assert c.env(np.broadcast_to(col, (4, 8, 3))) == 0
+        assert c.env(np.broadcast_to(col, shape + (3,))) == 0
         p = make_params(96, 64, 8, 6, True, True)
         W = p.cameraW
         p.cameraW = _native.Float3(-W.x, -W.y, -W.z)             # looking away from the box
@@ -226,6 +225,12 @@ def test_constant_map_is_seen_exactly(classes, light):
         assert st.culled_rays == 96 * 64 * 8
     finally:
         c.close()
+
+
+@pytest.mark.parametrize("classes", [1, 0])
+@pytest.mark.parametrize("light", [0, 1])
+def test_constant_map_is_seen_exactly(classes, light):
+    constant_map_is_seen_exactly(classes, light)
 
 
 # ---- 4. furnace ------------------------------------------------------------------------------------------------------------------
@@ -241,11 +246,11 @@ def _sphere_mask(c, p):
     return np.all(img[..., :3] == 0.0, axis=-1)
 
 
-@pytest.mark.parametrize("light,dl,is_", [(0, False, True), (0, False, False), (0, True, True), (1, True, True), (1, False, True), (1, True, False), (1, False, False)])
-def test_furnace(light, dl, is_):
+def furnace(light, dl, is_, shape=(16, 32)):
+    """the test below under a white map of `shape` (h, w)"""
     c = Ctx.sphere(light=light)
     try:
-        assert c.env(np.ones((16, 32, 3), np.float32)) == 0
+        assert c.env(np.ones(shape + (3,), np.float32)) == 0
         p = _sphere_params(spp=64, depth=8, dl=dl, is_=is_)
         mask = _sphere_mask(c, p)
         assert mask.sum() > 800
@@ -257,6 +262,11 @@ def test_furnace(light, dl, is_):
         assert bg.size > 0
     finally:
         c.close()
+
+
+@pytest.mark.parametrize("light,dl,is_", [(0, False, True), (0, False, False), (0, True, True), (1, True, True), (1, False, True), (1, True, False), (1, False, False)])
+def test_furnace(light, dl, is_):
+    furnace(light, dl, is_)
 
 
 # ---- 5. MIS: light sampling of the map and BSDF sampling converge to the same image -------------------------------------------------
@@ -286,11 +296,11 @@ def test_map_light_sampling_agrees_with_bsdf_sampling_and_wins():
 
 
 # ---- 6. frame batches and partitions -------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("light", [0, 1])
-def test_batches_and_partitions_with_a_map(light):
+def batches_and_partitions_with_a_map(light, img):
+    """the test below with the map img"""
     c = Ctx.box(light=light)
     try:
-        assert c.env(_sky()) == 0
+        assert c.env(img) == 0
         p = make_params(96, 64, 8, 6, True, True)
         single, _ = c.render(p, frames=3)
         batch, _ = c.render(p, frames=3, batch=True)
@@ -305,6 +315,11 @@ def test_batches_and_partitions_with_a_map(light):
         assert np.array_equal(parts[..., :3].view(np.uint32), whole[..., :3].view(np.uint32))
     finally:
         c.close()
+
+
+@pytest.mark.parametrize("light", [0, 1])
+def test_batches_and_partitions_with_a_map(light):
+    batches_and_partitions_with_a_map(light, _sky())
 
 
 # ---- 7. refusals keep the previous map; the map outlives a scene change -------------------------------------------------------------
