@@ -1,8 +1,9 @@
 // capi_query.hip — the entry points of include/acgpt.h that answer queries in device memory: pt_query_closest, pt_query_any, the
 // ordered multi-hit query pt_query_multi, the ambient-occlusion stage on top of them: pt_ao_points, pt_ao_image, and the
 // closest-point query pt_query_nearest, the box-overlap queries pt_query_overlap, pt_query_overlap_any and the swept-sphere casts
-// pt_query_sweep, pt_query_sweep_any (each with its counting twin of include/acgpt_test.h).
-// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, overlap.hip and sweep.hip.  The context and what the units share: context.h.
+// pt_query_sweep, pt_query_sweep_any and the triangle-against-mesh queries pt_query_triangles, pt_query_triangles_any (each with its
+// counting twin of include/acgpt_test.h).
+// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, overlap.hip, sweep.hip and tritri.hip.  The context and what the units share: context.h.
 #include <cmath>
 
 #include "../../include/acgpt_test.h"
@@ -13,6 +14,7 @@
 #include "overlap.h"
 #include "query.h"
 #include "sweep.h"
+#include "tritri.h"
 
 static_assert(sizeof(pt_hit) == 32, "pt_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_nearest) == 32, "pt_nearest: a change of this layout bumps pt_abi_version");
@@ -137,8 +139,10 @@ static_assert(PT_QUERY_OVERLAP_MAX == ptd::kOverlapMaxPrims, "PT_QUERY_OVERLAP_M
 struct OverlapOut { const void* p; size_t bytes_per_box; uintptr_t align_mask; bool required; const char* name; };
 
 // every refusal of the three calls before any device work, in pt_query_multi's order.  list: the call has max_prims and prims
-// (outs[0] is prims).  Returns 0 to go on, 1 refused, -1 nothing to do (n == 0).
-static int overlap_prepare(pt_ctx* c, const char* fn, const float* boxes, size_t n, bool list, uint32_t max_prims, const OverlapOut* outs, int n_outs, int* fmt)
+// (outs[0] is prims).  The triangle queries share it: what names the input records ("boxes") and in_bytes, the bytes of one.
+// Returns 0 to go on, 1 refused, -1 nothing to do (n == 0).
+static int overlap_prepare(pt_ctx* c, const char* fn, const float* boxes, size_t n, bool list, uint32_t max_prims, const OverlapOut* outs, int n_outs, int* fmt,
+                           const char* what = "boxes", size_t in_bytes = 32u)
 {
     const std::string f = std::string(fn) + ": ";
     if (!c) return fail(nullptr, f + "null context");
@@ -151,13 +155,13 @@ static int overlap_prepare(pt_ctx* c, const char* fn, const float* boxes, size_t
     if (!boxes) return fail(c, f + "null argument");
     for (int k = 0; k < n_outs; k++)
         if (outs[k].required && !outs[k].p) return fail(c, f + "null argument");
-    if (n > 0x7FFFFFFFull) return fail(c, f + "too many boxes (2^31 - 1 per call)");
-    if ((uintptr_t)boxes & 15u) return fail(c, f + "the boxes must be 16-byte aligned");
+    if (n > 0x7FFFFFFFull) return fail(c, f + "too many " + what + " (2^31 - 1 per call)");
+    if ((uintptr_t)boxes & 15u) return fail(c, f + "the " + what + " must be 16-byte aligned");
     for (int k = 0; k < n_outs; k++)
         if ((uintptr_t)outs[k].p & outs[k].align_mask) return fail(c, f + outs[k].name + " must be " + std::to_string(outs[k].align_mask + 1u) + "-byte aligned");
     for (int k = 0; k < n_outs; k++) {
         if (!outs[k].p) continue;
-        if (spans_overlap(boxes, n * 32u, outs[k].p, n * outs[k].bytes_per_box)) return fail(c, f + outs[k].name + " overlaps the boxes");
+        if (spans_overlap(boxes, n * in_bytes, outs[k].p, n * outs[k].bytes_per_box)) return fail(c, f + outs[k].name + " overlaps the " + what);
         for (int j = 0; j < k; j++)
             if (outs[j].p && spans_overlap(outs[j].p, n * outs[j].bytes_per_box, outs[k].p, n * outs[k].bytes_per_box))
                 return fail(c, f + outs[k].name + " overlaps " + outs[j].name);
@@ -197,6 +201,47 @@ PT_API int pt_debug_overlap_visits(pt_ctx* c, const float* boxes, size_t n, uint
     if (int rc = overlap_prepare(c, "pt_debug_overlap_visits", boxes, n, false, 0u, outs, 2, &fmt)) return rc < 0 ? 0 : rc;
     CK(c, ptd::launch_overlap_visits(fmt, device_scene(c), c->stack_entries, ptd::overlap_scene_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)boxes,
                                      (uint32_t)n, counts, (uint2*)visits, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- triangle against mesh -------------------------------------------------------------------------------------------------------
+static_assert(PT_QUERY_TRIANGLES_MAX == ptd::kTrianglesMaxPrims, "PT_QUERY_TRIANGLES_MAX is the size of the kernel's largest list");
+static_assert(PT_QUERY_TRIANGLES_MAX == PT_QUERY_OVERLAP_MAX, "overlap_prepare names one limit for both");
+
+// The three calls refuse what pt_query_overlap's refuse, in the same order (overlap_prepare); a query is 48 bytes.
+PT_API int pt_query_triangles(pt_ctx* c, const float* tris, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts)
+{
+    // n < 2^31, max_prims <= 8: the byte counts stay below 2^37
+    const OverlapOut outs[2] = {{prims, (size_t)max_prims * 4u, 15u, false, "prims"}, {counts, 4u, 3u, false, "counts"}};
+    int fmt = 0;
+    if (int rc = overlap_prepare(c, "pt_query_triangles", tris, n, true, max_prims, outs, 2, &fmt, "triangles", 48u)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_triangles");
+    CK(c, ptd::launch_query_triangles(fmt, device_scene(c), c->stack_entries, ptd::overlap_scene_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)tris,
+                                      (uint32_t)n, max_prims, prims, counts, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_query_triangles_any(pt_ctx* c, const float* tris, size_t n, uint8_t* hit)
+{
+    const OverlapOut outs[1] = {{hit, 1u, 0u, true, "hit"}};
+    int fmt = 0;
+    if (int rc = overlap_prepare(c, "pt_query_triangles_any", tris, n, false, 0u, outs, 1, &fmt, "triangles", 48u)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_triangles_any");
+    CK(c, ptd::launch_query_triangles_any(fmt, device_scene(c), c->stack_entries, ptd::overlap_scene_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)tris,
+                                          (uint32_t)n, hit, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_debug_triangles_visits(pt_ctx* c, const float* tris, size_t n, uint32_t* counts, uint32_t* visits)
+{
+    const OverlapOut outs[2] = {{counts, 4u, 3u, true, "counts"}, {visits, 8u, 7u, true, "visits"}};
+    int fmt = 0;
+    if (int rc = overlap_prepare(c, "pt_debug_triangles_visits", tris, n, false, 0u, outs, 2, &fmt, "triangles", 48u)) return rc < 0 ? 0 : rc;
+    CK(c, ptd::launch_triangles_visits(fmt, device_scene(c), c->stack_entries, ptd::overlap_scene_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)tris,
+                                       (uint32_t)n, counts, (uint2*)visits, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -16,7 +16,7 @@
 //              [--tonemap linear|reinhard|aces] [--exposure auto|<EV>] [--out-hdr file.pfm]
 //              [--until-error E [--until-permille P] [--error-floor F] [--error-out file.pfm]]
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
-//              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k] ...]
+//              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k] ...] [--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k] ...]
 //              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...]
 //              [--ao K[,radius[,bias]] --ao-out file.pfm [--ao-frames n]]
 // --ao K[,radius[,bias]] with --ao-out: once the scene is set and before the first frame, the ambient occlusion of the view
@@ -44,6 +44,10 @@
 // {"overlap": [cx, cy, cz, hx, hy, hz], "count": <triangles that overlap the box>, "triangles": [<the k lowest indices among them,
 // k = 0..8, default 8>], "materials": ["<newmtl name>" per listed triangle]}.  A value that is not finite, a negative half extent or a
 // k outside 0..8 is refused with exit status 2.  The frames are the same with or without it.
+// --intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k] (repeatable): once the scene is set and before the first frame, the scene triangles that
+// intersect the triangle of these three vertices, by pt_query_triangles in one call per k, one JSON line each: {"intersect": [the nine
+// coordinates], "count": <scene triangles that intersect it>, "triangles": [<the k lowest indices among them, k = 0..8, default 8>]}.
+// A coordinate that is not finite or a k outside 0..8 is refused with exit status 2.  The frames are the same with or without it.
 // --sweep ox,oy,oz,dx,dy,dz,r[,tmax] (repeatable): once the scene is set and before the first frame, how far the sphere of radius r
 // whose centre starts at o travels along d before it touches the scene (t in units of |d|, at most tmax, default unbounded), all in
 // one call of pt_query_sweep, one JSON line each: {"sweep": [ox, oy, oz, dx, dy, dz, r], "tmax": <tmax or null>, "hit": true, "t": ...,
@@ -748,6 +752,48 @@ static void overlapBoxes(PathTracerState& state, const TinyObjWrapper& obj, cons
     fflush(stdout);
 }
 
+// --intersect: the triangles of one k in one call of pt_query_triangles; one JSON line per triangle, in the order given
+struct IntersectTri { float v[12]; uint32_t k; };
+static void intersectTriangles(PathTracerState& state, const std::vector<IntersectTri>& tris)
+{
+    const size_t n = tris.size();
+    std::vector<uint32_t> counts(n, 0u), prims(n * 8, 0xFFFFFFFFu);
+    for (uint32_t k = 0; k <= 8u; k++) {
+        std::vector<size_t> which;
+        std::vector<float> recs;
+        for (size_t i = 0; i < n; i++)
+            if (tris[i].k == k) { which.push_back(i); recs.insert(recs.end(), tris[i].v, tris[i].v + 12); }
+        const size_t m = which.size();
+        if (m == 0) continue;
+        void* d_tris = nullptr; void* d_prims = nullptr; void* d_counts = nullptr;
+        std::vector<uint32_t> c(m), p(m * (k ? k : 1u));
+        std::string err;
+        if (pt_device_malloc(state.context, &d_tris, m * 48) != 0 || pt_device_malloc(state.context, &d_counts, m * 4) != 0 ||
+            (k != 0 && pt_device_malloc(state.context, &d_prims, m * k * 4) != 0) ||
+            pt_copy_to_device(state.context, d_tris, recs.data(), m * 48) != 0 ||
+            pt_query_triangles(state.context, (const float*)d_tris, m, k, (uint32_t*)d_prims, (uint32_t*)d_counts) != 0 ||
+            pt_copy_to_host(state.context, c.data(), d_counts, m * 4) != 0 ||
+            (k != 0 && pt_copy_to_host(state.context, p.data(), d_prims, m * k * 4) != 0))
+            err = pt_last_error(state.context);
+        if (d_tris) pt_device_free(state.context, d_tris);
+        if (d_prims) pt_device_free(state.context, d_prims);
+        if (d_counts) pt_device_free(state.context, d_counts);
+        if (!err.empty()) throw Exception("intersect: " + err);
+        for (size_t j = 0; j < m; j++) {
+            counts[which[j]] = c[j];
+            for (uint32_t e = 0; e < k; e++) prims[which[j] * 8 + e] = p[j * k + e];
+        }
+    }
+    for (size_t i = 0; i < n; i++) {
+        const float* a = tris[i].v;
+        printf("{\"intersect\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"count\": %u, \"triangles\": [", a[0], a[1], a[2], a[4], a[5], a[6], a[8],
+               a[9], a[10], counts[i]);
+        for (uint32_t e = 0; e < tris[i].k && prims[i * 8 + e] != 0xFFFFFFFFu; e++) printf("%s%u", e ? ", " : "", prims[i * 8 + e]);
+        printf("]}\n");
+    }
+    fflush(stdout);
+}
+
 // --sweep: every sweep in one call of pt_query_sweep; one JSON line per sweep
 struct SweepArg { float v[8]; };
 static void sweepSpheres(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<SweepArg>& sweeps)
@@ -871,6 +917,7 @@ int main(int argc, char** argv)
     std::vector<PickAll> pickAlls;
     std::vector<float4> nearest;
     std::vector<OverlapBox> overlaps;
+    std::vector<IntersectTri> intersects;
     std::vector<SweepArg> sweeps;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false, move_history = false, no_area_light = false;
@@ -980,6 +1027,17 @@ int main(int argc, char** argv)
             if (!ok) { std::cerr << "--overlap cx,cy,cz,hx,hy,hz[,k]: finite values, half extents >= 0, k = 0..8" << std::endl; return 2; }
             b.k = (uint32_t)k;
             overlaps.push_back(b);
+        }
+        else if (a == "--intersect") {
+            IntersectTri t = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, 8u};
+            int k = 8;
+            float* v = t.v;
+            const int got = sscanf(next(), "%f,%f,%f,%f,%f,%f,%f,%f,%f,%d", &v[0], &v[1], &v[2], &v[4], &v[5], &v[6], &v[8], &v[9], &v[10], &k);
+            bool ok = got >= 9 && k >= 0 && k <= 8;
+            for (int j = 0; j < 12; j++) ok = ok && std::isfinite(v[j]);
+            if (!ok) { std::cerr << "--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k]: finite coordinates, k = 0..8" << std::endl; return 2; }
+            t.k = (uint32_t)k;
+            intersects.push_back(t);
         }
         else if (a == "--sweep") {
             SweepArg w = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, INFINITY}};
@@ -1113,6 +1171,7 @@ int main(int argc, char** argv)
         if (!pickAlls.empty()) { std::cout.flush(); pickAllPixels(state, obj, pickAlls); }
         if (!nearest.empty()) { std::cout.flush(); nearestPoints(state, obj, nearest); }
         if (!overlaps.empty()) { std::cout.flush(); overlapBoxes(state, obj, overlaps); }
+        if (!intersects.empty()) { std::cout.flush(); intersectTriangles(state, intersects); }
         if (!sweeps.empty()) { std::cout.flush(); sweepSpheres(state, obj, sweeps); }
         if (ao_samples > 0) ambientOcclusion(state, ao_samples, ao_radius, ao_bias, ao_frames, ao_out);
         HistoryFile history;

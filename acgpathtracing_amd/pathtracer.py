@@ -1124,6 +1124,198 @@ def bakeOccupancy(state, resolution, bounds=None, counts=False):
     return queryOverlapAny(state, boxes).reshape(shape)
 
 
+# ------------------------------------------------------------------ triangle against mesh ----
+def _triangle_records(what, triangles):
+    """The (n, 12) float32 records {a0.xyz, 0, a1.xyz, 0, a2.xyz, 0} of the NumPy argument: (n, 3, 3) or (n, 9) vertices, or (n, 12)
+    records as they are"""
+    t = np.asarray(triangles)
+    if t.dtype.kind not in "fiu":
+        raise PathTracerError("%s: the triangles must be numbers, got %s" % (what, t.dtype))
+    if t.ndim == 2 and t.shape[1] == 12:
+        return np.ascontiguousarray(t, np.float32)
+    if not ((t.ndim == 3 and t.shape[1:] == (3, 3)) or (t.ndim == 2 and t.shape[1] == 9)):
+        raise PathTracerError("%s: expected (n, 3, 3) or (n, 9) vertices or (n, 12) records, got shape %s" % (what, t.shape))
+    r = np.zeros((t.shape[0], 3, 4), np.float32)
+    r[:, :, :3] = t.reshape(-1, 3, 3)
+    return r.reshape(-1, 12)
+
+
+def _triangle_tensor(what, state, tris):
+    import torch
+    if tris.device.type != "cuda" or tris.device.index != state._device:
+        raise PathTracerError("%s: the triangles are on %s, the context is on cuda:%d" % (what, tris.device, state._device))
+    if tris.dtype != torch.float32:
+        raise PathTracerError("%s: the triangles must be float32, got %s" % (what, tris.dtype))
+    if tris.dim() != 2 or tris.shape[1] != 12:
+        raise PathTracerError("%s: expected an (n, 12) tensor {a0.xyz, 0, a1.xyz, 0, a2.xyz, 0}, got shape %s" % (what, tuple(tris.shape)))
+    if not tris.is_contiguous():
+        raise PathTracerError("%s: the triangles must be contiguous (nothing is copied)" % what)
+    return torch
+
+
+def queryTriangles(state, triangles, max_prims=8, counts=True):
+    """Which triangles of the scene on the GPU intersect each triangle of the caller's (include/acgpt.h pt_query_triangles): the narrow
+    phase of mesh-to-mesh collision.  max_prims: 0..8, how many scene triangle indices to return per query; counts: also the number
+    of intersecting scene triangles, not clamped to max_prims.  max_prims=0, counts=True asks for the counts alone.  Touching counts
+    as intersecting; a triangle with a non-finite coordinate intersects nothing.
+
+    NumPy (or anything np.asarray takes): (n, 3, 3) or (n, 9) vertices, or (n, 12) records {a0.xyz, 0, a1.xyz, 0, a2.xyz, 0}
+    (triangleRecords makes them from a mesh).  They go to the device and the answer comes back: a dict of prim (n, max_prims) uint32,
+    the lowest indices among the intersecting triangles, ascending, 0xFFFFFFFF past the last one, and count (n,) uint32 when asked.
+
+    A torch tensor must be (n, 12) float32 records, contiguous and on the context's device; nothing is copied, its data_ptr() goes
+    straight in, and the answer is torch tensors on that device, prim and count as int32 (-1 past the last triangle).  torch's current
+    stream is synchronised before the call, and the call returns synchronised."""
+    k = _overlap_args("queryTriangles", max_prims, counts)
+    L = _native.hip()
+    if _is_tensor(triangles):
+        torch = _triangle_tensor("queryTriangles", state, triangles)
+        n = int(triangles.shape[0])
+        with torch.cuda.device(triangles.device):
+            out = torch.empty((n, k), dtype=torch.int32, device=triangles.device)
+            cnt = torch.empty((n,), dtype=torch.int32, device=triangles.device) if counts else None
+            torch.cuda.current_stream().synchronize()      # the triangles' producer and the allocations; the call below returns synchronised
+        _check(state.context, L.pt_query_triangles(state.context, triangles.data_ptr() if n else None, n, k, out.data_ptr() if n and k else None,
+                                                   cnt.data_ptr() if n and counts else None), "pt_query_triangles")
+        got = {"prim": out}
+        if counts:
+            got["count"] = cnt
+        return got
+    r = _triangle_records("queryTriangles", triangles)
+    n = r.shape[0]
+    out = np.full((n, k), 0xFFFFFFFF, np.uint32)
+    cnt = np.zeros(n, np.uint32)
+    if n:
+        bufs, d_prims, d_counts = _device_buffers(state, 1, r.nbytes), None, None
+        try:
+            if k:
+                bufs += _device_buffers(state, 1, out.nbytes)
+                d_prims = bufs[-1]
+            if counts:
+                bufs += _device_buffers(state, 1, cnt.nbytes)
+                d_counts = bufs[-1]
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], r.ctypes.data, r.nbytes), "copy to device")
+            _check(state.context, L.pt_query_triangles(state.context, bufs[0], n, k, d_prims, d_counts), "pt_query_triangles")
+            if k:
+                _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, d_prims, out.nbytes), "copy to host")
+            if counts:
+                _check(state.context, L.pt_copy_to_host(state.context, cnt.ctypes.data, d_counts, cnt.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    got = {"prim": out}
+    if counts:
+        got["count"] = cnt
+    return got
+
+
+def queryTrianglesAny(state, triangles):
+    """Does any triangle of the scene intersect each triangle (include/acgpt.h pt_query_triangles_any): queryTriangles' argument, a bool
+    array (n,), or a bool tensor for a tensor.  A query's walk ends at the first scene triangle it accepts."""
+    L = _native.hip()
+    if _is_tensor(triangles):
+        torch = _triangle_tensor("queryTrianglesAny", state, triangles)
+        n = int(triangles.shape[0])
+        with torch.cuda.device(triangles.device):
+            out = torch.empty((n,), dtype=torch.uint8, device=triangles.device)
+            torch.cuda.current_stream().synchronize()
+        _check(state.context, L.pt_query_triangles_any(state.context, triangles.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_triangles_any")
+        return out.view(torch.bool)
+    r = _triangle_records("queryTrianglesAny", triangles)
+    n = r.shape[0]
+    out = np.zeros(n, np.uint8)
+    if n:
+        bufs = _device_buffers(state, 2, r.nbytes)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], r.ctypes.data, r.nbytes), "copy to device")
+            _check(state.context, L.pt_query_triangles_any(state.context, bufs[0], n, bufs[1]), "pt_query_triangles_any")
+            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    return out.view(np.bool_)
+
+
+def _posed_records(what, vertices, indices, poses):
+    """(P, T, 12) float32 records of a mesh under P poses (poses None: the mesh as it is, P = 1).  Tensors in, a tensor out."""
+    tensors = _is_tensor(vertices)
+    if tensors:
+        import torch
+        v = vertices
+        if v.dim() != 2 or v.shape[1] not in (3, 4) or not v.dtype.is_floating_point:
+            raise PathTracerError("%s: expected (V, 3) or (V, 4) floating-point vertices, got %s %s" % (what, tuple(v.shape), v.dtype))
+        v = v[:, :3].to(torch.float32)
+        idx = indices if _is_tensor(indices) else torch.as_tensor(np.asarray(indices).astype(np.int64), device=v.device)
+        if idx.dtype.is_floating_point or idx.numel() % 3:
+            raise PathTracerError("%s: the indices are whole numbers, three per triangle" % what)
+        idx = idx.to(device=v.device, dtype=torch.int64).reshape(-1, 3)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= v.shape[0]):
+            raise PathTracerError("%s: an index is outside the %d vertices" % (what, v.shape[0]))
+        if poses is None:
+            moved = v[None]
+        else:
+            p = poses if _is_tensor(poses) else torch.as_tensor(np.asarray(poses, np.float32))
+            if p.dim() not in (2, 3) or tuple(p.shape[-2:]) not in ((3, 4), (4, 4)):
+                raise PathTracerError("%s: a pose is a 3 x 4 or 4 x 4 matrix, got shape %s" % (what, tuple(p.shape)))
+            p = p.to(device=v.device, dtype=torch.float32).reshape(-1, p.shape[-2], 4)
+            moved = torch.matmul(v[None], p[:, :3, :3].transpose(1, 2)) + p[:, None, :3, 3]
+        rec = torch.zeros((moved.shape[0], idx.shape[0], 3, 4), dtype=torch.float32, device=v.device)
+        rec[..., :3] = moved[:, idx]
+        return rec.reshape(moved.shape[0], idx.shape[0], 12)
+    v = np.asarray(vertices)
+    if v.dtype.kind not in "fiu" or v.ndim != 2 or v.shape[1] not in (3, 4):
+        raise PathTracerError("%s: expected (V, 3) or (V, 4) vertices, got %s %s" % (what, v.shape, v.dtype))
+    v = v[:, :3].astype(np.float32)
+    idx = np.asarray(indices)
+    if idx.dtype.kind not in "iu" or idx.size % 3:
+        raise PathTracerError("%s: the indices are whole numbers, three per triangle" % what)
+    idx = idx.astype(np.int64).reshape(-1, 3)
+    if idx.size and (idx.min() < 0 or idx.max() >= v.shape[0]):
+        raise PathTracerError("%s: an index is outside the %d vertices" % (what, v.shape[0]))
+    if poses is None:
+        moved = v[None]
+    else:
+        p = np.asarray(poses)
+        if p.dtype.kind not in "fiu" or p.ndim not in (2, 3) or p.shape[-2:] not in ((3, 4), (4, 4)):
+            raise PathTracerError("%s: a pose is a 3 x 4 or 4 x 4 matrix, got shape %s" % (what, p.shape))
+        p = p.astype(np.float32).reshape(-1, p.shape[-2], 4)
+        moved = (np.matmul(v[None], p[:, :3, :3].transpose(0, 2, 1)) + p[:, None, :3, 3]).astype(np.float32)
+    rec = np.zeros((moved.shape[0], idx.shape[0], 3, 4), np.float32)
+    rec[..., :3] = moved[:, idx]
+    return rec.reshape(moved.shape[0], idx.shape[0], 12)
+
+
+def triangleRecords(vertices, indices, pose=None):
+    """The (T, 12) float32 records queryTriangles takes, of a mesh: vertices (V, 3) or (V, 4), indices (T, 3) or flat, optionally moved
+    by a 3 x 4 or 4 x 4 pose (x -> R x + t, in float32).  NumPy arrays give an array; torch tensors are transformed with torch ops on
+    their device and give a tensor there."""
+    if pose is not None and (pose.dim() if _is_tensor(pose) else np.ndim(pose)) != 2:
+        raise PathTracerError("triangleRecords: a pose is a 3 x 4 or 4 x 4 matrix (meshCollisions takes several)")
+    rec = _posed_records("triangleRecords", vertices, indices, pose)
+    return rec.reshape(-1, 12)
+
+
+def meshCollisions(state, vertices, indices, poses=None, pairs=False):
+    """P poses of one mesh against the scene on the GPU.  poses: (P, 3, 4) or (P, 4, 4) (or one matrix, or None for the mesh as it is).
+    By default one queryTrianglesAny call over the P x T records, reduced per pose: a bool (P,), does the mesh in this pose touch the
+    scene.  pairs=True asks queryTriangles instead and returns a dict: pairs (m, 3), the (pose, mesh triangle, scene triangle) triples
+    of the lists, and counts (P, T), the number of scene triangles each mesh triangle intersects — where it is above 8 that triangle's
+    list was cut.  Arrays for arrays, tensors for tensors."""
+    rec = _posed_records("meshCollisions", vertices, indices, poses)
+    P, T = int(rec.shape[0]), int(rec.shape[1])
+    flat = rec.reshape(P * T, 12)
+    if not pairs:
+        return queryTrianglesAny(state, flat).reshape(P, T).any(1)
+    got = queryTriangles(state, flat, max_prims=_native.QUERY_TRIANGLES_MAX, counts=True)
+    prim = got["prim"]
+    if _is_tensor(prim):
+        import torch
+        row, col = torch.nonzero(prim >= 0, as_tuple=True)
+        triples = torch.stack([row // max(T, 1), row % max(T, 1), prim[row, col].to(torch.int64)], dim=1)
+    else:
+        row, col = np.nonzero(prim != 0xFFFFFFFF)
+        triples = np.stack([row // max(T, 1), row % max(T, 1), prim[row, col].astype(np.int64)], axis=1)
+    return {"pairs": triples, "counts": got["count"].reshape(P, T)}
+
+
 # ------------------------------------------------------------------ swept spheres ----
 SWEEP_DTYPE = np.dtype([("t", np.float32), ("prim", np.uint32), ("u", np.float32), ("v", np.float32), ("point", np.float32, 3), ("material", np.uint32)])      # pt_sweep_hit
 assert SWEEP_DTYPE.itemsize == 32

@@ -536,6 +536,53 @@ int pt_query_nearest(pt_ctx* ctx, const float* points, size_t n, pt_nearest* out
 int pt_query_overlap(pt_ctx* ctx, const float* boxes, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts);
 int pt_query_overlap_any(pt_ctx* ctx, const float* boxes, size_t n, uint8_t* hit);
 
+/* ---- triangle-against-mesh intersection queries on the device (opt-in; nothing above changes) --------------------------------------
+ * Which triangles of the scene does a triangle of the caller's intersect: the narrow phase of mesh-to-mesh collision, for the thing
+ * that actually moves through a scene — a robot link, a tool, a character hull — where pt_query_overlap answers only for its boxes.
+ * pt_query_overlap's memory and call rules, word for word: DEVICE arrays, tris and prims 16-byte aligned, counts 4-byte, hit any
+ * alignment; the call enqueues on the context's stream and returns synchronised, acts on rank 0 of a pt_create_multi context, never
+ * writes the accumulation buffer, the frame buffer or pt_stats, walks the node array the scene holds (pt_bvh_info.device_bytes as for
+ * pt_query_closest) and uses no atomics: two calls give the same bits.
+ *
+ *   tris      n records of 12 floats {a0.xyz, 0, a1.xyz, 0, a2.xyz, 0}: the three vertices of a query triangle.  The fourth float of
+ *             each vertex is reserved and ignored.
+ *   intersect a scene triangle intersects the query triangle iff all 20 conditions below hold: a separating-axis test in keep form.
+ *             All fp32, every operation on its own, evaluated as written, no fused multiply-add (tests/tritri_ref.py is the NumPy
+ *             statement, equal bit for bit), on the vectors the build stores for the scene triangle, v0, e1 = v1 - v0, e2 = v2 - v0;
+ *             dot and cross as written under pt_query_closest, fmin3 / fmax3 = fminf / fmaxf applied twice (they ignore a NaN
+ *             operand), vector sums and differences per component:
+ *               w1 = v0 + e1;  w2 = v0 + e2
+ *               boxes, k in x, y, z:  fmin3(v0[k], w1[k], w2[k]) <= fmax3(a0[k], a1[k], a2[k])  and
+ *                                     fmax3(v0[k], w1[k], w2[k]) >= fmin3(a0[k], a1[k], a2[k])
+ *               f1 = a1 - a0;  f2 = a2 - a0;  p0 = v0 - a0;  p1 = p0 + e1;  p2 = p0 + e2
+ *               axis(L):  s_m = dot(L, p_m)  (m = 0, 1, 2);  t1 = dot(L, f1);  t2 = dot(L, f2);
+ *                         fmin3(s_0, s_1, s_2) <= fmax3(0, t1, t2)  and  fmax3(s_0, s_1, s_2) >= fmin3(0, t1, t2)
+ *               nA = cross(f1, f2);  nB = cross(e1, e2)
+ *               17 axes:  nA;  nB;  cross(a, b) for a in (f1, f2 - f1, f2) and b in (e1, e2 - e1, e2);
+ *                         cross(nA, a) for the three a;  cross(nB, b) for the three b
+ *             The three box conditions compare coordinates as they are, without a subtraction: a pair that is kept has bounding
+ *             boxes that overlap exactly, which is what lets the walk prune by boxes.  The six in-plane axes cross(n, edge) are
+ *             what separates two coplanar triangles: the other eleven are all parallel to the common normal there.  The conditions
+ *             are closed: touching is intersecting.  Three NaN s fail their condition; a NaN t is ignored.
+ *             A zero-area triangle on either side (a segment, a point) is tested like any other.  The test then never misses an
+ *             intersection, but it may keep a pair that is apart within a common plane: a segment's own in-plane normal is not
+ *             among the axes, since its n = 0 makes cross(n, edge) = 0.  For exact segment queries use pt_query_any.
+ *   counts    null, or n words: the number of scene triangles that intersect query triangle i, not clamped to max_prims
+ *   prims     null with max_prims == 0, or n * max_prims words (1 <= max_prims <= PT_QUERY_TRIANGLES_MAX), query-major:
+ *             prims[i * max_prims + j] is the j-th lowest index, in the caller's index-buffer order, among the triangles that
+ *             intersect query i, ascending; the slots past the last one hold 0xFFFFFFFF.
+ *   hit       pt_query_triangles_any: one byte per query, 1 iff counts[i] would be non-zero.  A query's walk ends at its first
+ *             accepted triangle.
+ *   a miss before any traversal: any of the nine coordinates non-finite, a scene without triangles.  It gives count 0, prims all
+ *             0xFFFFFFFF, hit 0.
+ * The walk's boxes only prune; which pairs intersect is decided by the test above alone.
+ * n == 0 is a no-op success.  Refused, with the context left usable: n > 0x7FFFFFFF, prims and counts both null, prims null with
+ * max_prims != 0 or the reverse, max_prims > PT_QUERY_TRIANGLES_MAX, a null or misaligned tris or output pointer with n > 0, an output
+ * that overlaps the triangles or the other output, a context without a scene.                                                         */
+#define PT_QUERY_TRIANGLES_MAX 8
+int pt_query_triangles(pt_ctx* ctx, const float* tris, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts);
+int pt_query_triangles_any(pt_ctx* ctx, const float* tris, size_t n, uint8_t* hit);
+
 /* ---- swept-sphere casts on the device (opt-in; nothing above changes) --------------------------------------------------------------
  * How far a ball of radius r travels along a direction before it touches the mesh, and where it touches: the sphere cast of physics
  * and robotics libraries — continuous collision, character and camera controllers, path clearance of a round robot, thick rays and
