@@ -58,6 +58,12 @@ class TreeInfo(C.Structure):
                 ("n_wrecs", C.c_uint32), ("n_wnodes", C.c_uint32), ("wide_depth", C.c_uint32), ("held", C.c_uint32)]
 
 
+class BuildStats(C.Structure):
+    """pt_build_stats of include/acgpt_test.h (pt_debug_build_stats; not part of the ABI)"""
+    _fields_ = [("opt_area_before", C.c_float), ("opt_area_after", C.c_float), ("opt_ms", C.c_float),
+                ("opt_passes", C.c_uint32), ("build_iterations", C.c_uint32), ("mode", C.c_int32)]
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("n_tris", C.c_uint32), ("n_nodes", C.c_uint32), ("max_depth", C.c_uint32), ("stack_entries", C.c_uint32),
                 ("scene_lo", C.c_float * 3), ("scene_hi", C.c_float * 3), ("build_ms", C.c_float),
@@ -166,7 +172,7 @@ ABI_SYMBOLS = [
     "pt_host_malloc_mapped", "pt_host_free_mapped", "pt_abi_version",
 ]
 # ... and include/acgpt_test.h (test hooks and diagnostics; same library)
-TEST_SYMBOLS = ["pt_bench_traversal", "pt_selftest", "pt_debug_wave_times", "pt_debug_queue_progress", "pt_debug_window_moves", "pt_debug_queue_order", "pt_debug_pixel_classes", "pt_debug_row_spans", "pt_read_morton", "pt_debug_environment", "pt_debug_environment_tables", "pt_debug_microfacet", "pt_debug_nearest_visits", "pt_debug_overlap_visits", "pt_debug_sweep_visits", "pt_debug_triangles_visits", "pt_debug_read_tree",
+TEST_SYMBOLS = ["pt_bench_traversal", "pt_selftest", "pt_debug_wave_times", "pt_debug_queue_progress", "pt_debug_window_moves", "pt_debug_queue_order", "pt_debug_pixel_classes", "pt_debug_row_spans", "pt_read_morton", "pt_debug_environment", "pt_debug_environment_tables", "pt_debug_microfacet", "pt_debug_nearest_visits", "pt_debug_overlap_visits", "pt_debug_sweep_visits", "pt_debug_triangles_visits", "pt_debug_read_tree", "pt_debug_build_stats",
                 "pt_debug_small_kernel", "pt_debug_small_kernel_path", "pt_debug_small_ref", "pt_debug_small_budget",
                 "pt_debug_small_shape", "pt_debug_small_float_budget", "pt_debug_small_staged"]
 
@@ -286,6 +292,7 @@ def hip():
     L.pt_debug_queue_progress.argtypes = [vp, vp]; L.pt_debug_queue_progress.restype = C.c_int
     L.pt_read_morton.argtypes = [vp, vp, vp]; L.pt_read_morton.restype = C.c_int
     L.pt_debug_read_tree.argtypes = [vp, C.c_int, vp, sz, C.POINTER(TreeInfo)]; L.pt_debug_read_tree.restype = C.c_int
+    L.pt_debug_build_stats.argtypes = [vp, C.POINTER(BuildStats)]; L.pt_debug_build_stats.restype = C.c_int
     L.pt_debug_window_moves.argtypes = [vp, vp]; L.pt_debug_window_moves.restype = C.c_int
     L.pt_debug_small_kernel.argtypes = [vp, C.c_int]; L.pt_debug_small_kernel.restype = C.c_int
     L.pt_debug_small_kernel_path.argtypes = [vp]; L.pt_debug_small_kernel_path.restype = C.c_int

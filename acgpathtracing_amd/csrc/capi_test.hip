@@ -295,3 +295,16 @@ PT_API int pt_debug_read_tree(pt_ctx* c, int what, void* out, size_t capacity_by
     }
     return 0;
 }
+
+// What the last build recorded about itself (tests/build_ref.py holds it to the references): plain reads of the context, no device call.
+PT_API int pt_debug_build_stats(pt_ctx* c, pt_build_stats* out)
+{
+    if (!c) return fail(nullptr, "pt_debug_build_stats: null context");
+    if (!out) return fail(c, "pt_debug_build_stats: null argument");
+    if (!c->scene_kept || c->bvh.n_tris == 0) return fail(c, "pt_debug_build_stats: no scene (pt_set_scene with triangles first)");
+    const ptd::LbvhResult& b = c->bvh;
+    memset(out, 0, sizeof(*out));
+    out->opt_area_before = b.opt_area_before; out->opt_area_after = b.opt_area_after; out->opt_ms = b.opt_ms;
+    out->opt_passes = b.opt_passes; out->build_iterations = b.build_iterations; out->mode = b.mode;
+    return 0;
+}

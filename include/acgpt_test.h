@@ -172,6 +172,18 @@ typedef struct pt_tree_info {
  * a capacity below the array's size, a missing scene or a null argument is refused.  info may be NULL (what != 0).  A
  * pt_create_multi context reads rank 0. */
 int pt_debug_read_tree(pt_ctx* ctx, int what, void* out, size_t capacity_bytes, pt_tree_info* info);
+/* What the last build recorded about itself (tests/build_ref.py holds each figure to a sequential reference).  Not part of the ABI
+ * (pt_abi_version stays as it is). */
+typedef struct pt_build_stats {
+    float    opt_area_before, opt_area_after;   /* build mode 2: sum of the inner nodes' surface areas before / after the optimisation; 0 where none ran */
+    float    opt_ms;                            /* host time of the optimisation */
+    uint32_t opt_passes;                        /* passes of the host insertion / rounds of the device reinsertion that ran */
+    uint32_t build_iterations;                  /* PLOC merge rounds (modes 1 and 2) */
+    int32_t  mode;                              /* the build mode the tree was made with */
+} pt_build_stats;
+/* Fills *out from the context alone: no device call, nothing built or released.  Refused, with *out left as it is: a null context, a
+ * null out, no scene. */
+int pt_debug_build_stats(pt_ctx* ctx, pt_build_stats* out);
 
 #ifdef __cplusplus
 }
