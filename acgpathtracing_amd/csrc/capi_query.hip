@@ -1,9 +1,9 @@
 // capi_query.hip — the entry points of include/acgpt.h that answer queries in device memory: pt_query_closest, pt_query_any, the
 // ordered multi-hit query pt_query_multi, the ambient-occlusion stage on top of them: pt_ao_points, pt_ao_image, and the
 // closest-point query pt_query_nearest, the box-overlap queries pt_query_overlap, pt_query_overlap_any and the swept-sphere casts
-// pt_query_sweep, pt_query_sweep_any and the triangle-against-mesh queries pt_query_triangles, pt_query_triangles_any (each with its
-// counting twin of include/acgpt_test.h).
-// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, overlap.hip, sweep.hip and tritri.hip.  The context and what the units share: context.h.
+// pt_query_sweep, pt_query_sweep_any, the triangle-against-mesh queries pt_query_triangles, pt_query_triangles_any and the
+// segment-to-mesh distance query pt_query_segments (each with its counting twin of include/acgpt_test.h).
+// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, overlap.hip, sweep.hip, tritri.hip and segment.hip.  The context and what the units share: context.h.
 #include <cmath>
 
 #include "../../include/acgpt_test.h"
@@ -13,12 +13,14 @@
 #include "nearest.h"
 #include "overlap.h"
 #include "query.h"
+#include "segment.h"
 #include "sweep.h"
 #include "tritri.h"
 
 static_assert(sizeof(pt_hit) == 32, "pt_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_nearest) == 32, "pt_nearest: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_sweep_hit) == 32, "pt_sweep_hit: a change of this layout bumps pt_abi_version");
+static_assert(sizeof(pt_segment_hit) == 32, "pt_segment_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_ao_params) == 32, "pt_ao_params: a change of this layout bumps pt_abi_version");
 
 // The node array the scene holds, as pt_render_features picks it: fp16 centre / half-extent nodes for the default variants, fp32
@@ -242,6 +244,45 @@ PT_API int pt_debug_triangles_visits(pt_ctx* c, const float* tris, size_t n, uin
     if (int rc = overlap_prepare(c, "pt_debug_triangles_visits", tris, n, false, 0u, outs, 2, &fmt, "triangles", 48u)) return rc < 0 ? 0 : rc;
     CK(c, ptd::launch_triangles_visits(fmt, device_scene(c), c->stack_entries, ptd::overlap_scene_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)tris,
                                        (uint32_t)n, counts, (uint2*)visits, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- segment to mesh -------------------------------------------------------------------------------------------------------------
+// every refusal of pt_query_segments before any device work, in pt_query_nearest's order; a segment is 32 bytes.  Returns 0 to go on,
+// 1 refused, -1 nothing to do.
+static int segments_prepare(pt_ctx* c, const char* fn, const float* segments, size_t n, const void* out, const void* visits, bool with_visits, int* fmt)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (n == 0) return -1;
+    if (!segments || !out || (with_visits && !visits)) return fail(c, f + "null argument");
+    if (n > 0x7FFFFFFFull) return fail(c, f + "too many segments (2^31 - 1 per call)");
+    if (((uintptr_t)segments & 15u) || ((uintptr_t)out & 15u) || ((uintptr_t)visits & 7u)) return fail(c, f + "the segment and record arrays must be 16-byte aligned");
+    if (spans_overlap(segments, n * 32u, out, n * sizeof(pt_segment_hit))) return fail(c, f + "the output overlaps the segments");
+    if (with_visits && (spans_overlap(segments, n * 32u, visits, n * 8u) || spans_overlap(out, n * sizeof(pt_segment_hit), visits, n * 8u)))
+        return fail(c, f + "the visit counts overlap another array");
+    return query_node_format(c, f, fmt);
+}
+
+PT_API int pt_query_segments(pt_ctx* c, const float* segments, size_t n, pt_segment_hit* out)
+{
+    int fmt = 0;
+    if (int rc = segments_prepare(c, "pt_query_segments", segments, n, out, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_segments");
+    CK(c, ptd::launch_query_segments(fmt, device_scene(c), c->stack_entries, ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)segments,
+                                     (uint32_t)n, (float4*)out, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_debug_segments_visits(pt_ctx* c, const float* segments, size_t n, pt_segment_hit* out, uint32_t* visits, uint32_t flags)
+{
+    if (c && flags > ptd::kSegmentNoAxes) return fail(c, "pt_debug_segments_visits: flags must be 0 or 1");
+    int fmt = 0;
+    if (int rc = segments_prepare(c, "pt_debug_segments_visits", segments, n, out, visits, true, &fmt)) return rc < 0 ? 0 : rc;
+    CK(c, ptd::launch_segments_visits(fmt, device_scene(c), c->stack_entries, ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)segments,
+                                      (uint32_t)n, (float4*)out, (uint2*)visits, flags, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

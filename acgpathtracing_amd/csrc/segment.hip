@@ -1,0 +1,349 @@
+// segment.hip — the kernels behind pt_query_segments (include/acgpt.h).
+//
+//   k_query_segments<FMT, COUNT>   one segment per lane from a device array: the closest triangle within max_radius, then the record
+//                                  (distance, triangle, parameter on the segment, feature, point on the triangle, material).  COUNT also
+//                                  writes how many inner nodes the lane visited and how many triangles it tested, and takes the flag
+//                                  that switches bound (b) off (the test hook's instantiation).
+//
+// The shape is nearest.hip's: FMT 11 walks the fp16 centre / half-extent nodes, FMT 0 the fp32 nodes; the walk is ordered by a lower
+// bound of the squared distance from the segment to each child box, and the leaves run the segment-to-triangle statement.  256-lane
+// workgroups over a one-dimensional grid, the LDS lane stack of query.hip (stack_entries * 64 words per wave).  A segment is two
+// 16-byte loads and a record two 16-byte stores per lane.  Lanes past n and lanes whose segment is a miss before any traversal stay in
+// the wave, inactive.  No atomics: two calls give the same bits.
+// Built with -ffp-contract=off: the statement is evaluated as written, and tests/segment_ref.py mirrors it operation for operation.
+// The box bounds are outside that contract (they only prune) and use explicit fused multiply-adds.
+#include "segment.h"
+
+namespace ptd {
+
+extern __shared__ uint32_t segment_lds[];
+
+// nearest.hip's closest_on_triangle, operation for operation (pt_query_nearest's d2 and closest point): features 0 and 1.
+__device__ __forceinline__ float seg_closest_on_triangle(const f3& q, const f3& v0, const f3& ab, const f3& ac, f3& c)
+{
+    const f3 ap = q - v0;
+    const float d1 = dot(ab, ap), d2 = dot(ac, ap);
+    const f3 bp = ap - ab;
+    const float d3 = dot(ab, bp), d4 = dot(ac, bp);
+    const f3 cp = ap - ac;
+    const float d5 = dot(ab, cp), d6 = dot(ac, cp);
+    const float vc = d1 * d4 - d3 * d2;
+    const float vb = d5 * d2 - d1 * d6;
+    const float va = d3 * d6 - d5 * d4;
+    const float e43 = d4 - d3, e56 = d5 - d6;
+    const bool at_a = d1 <= 0.0f && d2 <= 0.0f;
+    const bool at_b = d3 >= 0.0f && d4 <= d3;
+    const bool on_ab = vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f;
+    const bool at_c = d6 >= 0.0f && d5 <= d6;
+    const bool on_ac = vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f;
+    const bool on_bc = va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f;
+    float num = 1.0f, den = (va + vb) + vc;
+    if (on_bc) { num = e43; den = e43 + e56; }
+    if (on_ac) { num = d2; den = d2 - d6; }
+    if (on_ab) { num = d1; den = d1 - d3; }
+    const float t = num / den;
+    float v = vb * t, w = vc * t;
+    if (on_bc) { v = 1.0f - t; w = t; }
+    if (on_ac) { v = 0.0f; w = t; }
+    if (at_c) { v = 0.0f; w = 1.0f; }
+    if (on_ab) { v = t; w = 0.0f; }
+    if (at_b) { v = 1.0f; w = 0.0f; }
+    if (at_a) { v = 0.0f; w = 0.0f; }
+    c = mk((v0.x + ab.x * v) + ac.x * w, (v0.y + ab.y * v) + ac.y * w, (v0.z + ab.z * v) + ac.z * w);
+    const f3 s = q - c;
+    return dot(s, s);
+}
+
+// Selects, not fminf / fmaxf: a -0 stays a -0 and a NaN a NaN, as in the NumPy statement.
+__device__ __forceinline__ float clamp01(float q)
+{
+    q = q < 0.0f ? 0.0f : q;
+    return q > 1.0f ? 1.0f : q;
+}
+
+// The segment {p0, d} (a = dot(d, d)) against the edge {A, E}: Ericson, Real-Time Collision Detection 5.1.9.  The cases — a segment
+// or an edge without length, parallel lines, the edge parameter leaving [0, 1] and the re-projection that follows — are compares
+// applied as selects on numerators and denominators, so a wave's lanes run one instruction stream and an edge costs two divisions:
+// s0 on the segment, then either t on the edge (tnom / e, inside [0, 1]) or the re-projected s (t clamped to an end).  Every
+// denominator a select keeps is > 0.  s: the parameter on the segment, c: the point on the edge.
+__device__ __forceinline__ float segment_edge(const f3& p0, const f3& d, float a, const f3& A, const f3& E, float& s, f3& c)
+{
+    const f3 r = p0 - A;
+    const float e = dot(E, E), b = dot(d, E), cc = dot(d, r), f = dot(E, r);
+    const bool a_ok = a > 0.0f, e_ok = e > 0.0f;
+    const float den = a * e - b * b;
+    const bool both = a_ok && e_ok && den > 0.0f;
+    const bool only_a = a_ok && !e_ok;
+    float num1 = only_a ? -cc : 0.0f, den1 = only_a ? a : 1.0f;
+    if (both) { num1 = b * f - cc * e; den1 = den; }
+    const float s0 = clamp01(num1 / den1);
+    const float tnom = b * s0 + f;
+    const bool lo = e_ok && tnom < 0.0f, hi = e_ok && tnom > e, out = lo || hi;
+    float num2 = e_ok ? tnom : 0.0f, den2 = e_ok ? e : 1.0f;
+    if (lo) num2 = -cc;
+    if (hi) num2 = b - cc;
+    if (out) den2 = a;
+    if (out && !a_ok) { num2 = 0.0f; den2 = 1.0f; }
+    const float q2 = clamp01(num2 / den2);
+    s = out ? q2 : s0;
+    const float t = lo ? 0.0f : (hi ? 1.0f : q2);
+    const f3 ps = mk(p0.x + d.x * s, p0.y + d.y * s, p0.z + d.z * s);
+    c = mk(A.x + E.x * t, A.y + E.y * t, A.z + E.z * t);
+    const f3 w = ps - c;
+    return dot(w, w);
+}
+
+struct SegPoint { float d2, s, feature; f3 c; };
+
+// Take candidate k if its d2 is smaller (ties stay with the lower feature); a NaN is no candidate.  The empty statement and the
+// barrier close one sub-test before the next starts: left to itself the compiler runs the five side by side and keeps their state
+// live together (tritri.hip's fold).
+template <bool FULL>
+__device__ __forceinline__ void seg_take(SegPoint& best, float d2, float s, float feature, const f3& c)
+{
+    const bool take = d2 < best.d2 || (best.d2 != best.d2 && d2 == d2);
+    best.d2 = take ? d2 : best.d2;
+    if (FULL) {
+        best.s = take ? s : best.s;
+        best.feature = take ? feature : best.feature;
+        best.c = mk(take ? c.x : best.c.x, take ? c.y : best.c.y, take ? c.z : best.c.z);
+    }
+    asm volatile("" : "+v"(best.d2));
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// The statement of include/acgpt.h: six sub-tests in the order of their feature numbers.  FULL = false is the walk's: d2 alone, the
+// same operations on the same inputs, so the same bits.
+template <bool FULL>
+__device__ __forceinline__ SegPoint segment_triangle(const f3& p0, const f3& p1, const f3& d, float a, const f3& v0, const f3& e1, const f3& e2)
+{
+    SegPoint best;
+    f3 c;
+    float s = 0.0f;
+    best.d2 = seg_closest_on_triangle(p0, v0, e1, e2, best.c);
+    best.s = 0.0f; best.feature = 0.0f;
+    asm volatile("" : "+v"(best.d2));
+    __builtin_amdgcn_sched_barrier(0);
+    float d2 = seg_closest_on_triangle(p1, v0, e1, e2, c);
+    seg_take<FULL>(best, d2, 1.0f, 1.0f, c);
+    d2 = segment_edge(p0, d, a, v0, e1, s, c);
+    seg_take<FULL>(best, d2, s, 2.0f, c);
+    d2 = segment_edge(p0, d, a, v0, e2, s, c);
+    seg_take<FULL>(best, d2, s, 3.0f, c);
+    d2 = segment_edge(p0, d, a, v0 + e1, e2 - e1, s, c);
+    seg_take<FULL>(best, d2, s, 4.0f, c);
+    // feature 5: a two-sided Moeller-Trumbore test of {p0, d} against the triangle in plain multiplies and adds (not tri_test, whose
+    // fused operations NumPy cannot mirror)
+    const f3 pv = cross(d, e2);
+    float det = dot(e1, pv);
+    const f3 tv = p0 - v0;
+    float U = dot(tv, pv);
+    const f3 qv = cross(tv, e1);
+    float V = dot(d, qv), T = dot(e2, qv);
+    if (det < 0.0f) { det = -det; U = -U; V = -V; T = -T; }
+    const bool crosses = det > 0.0f && U >= 0.0f && V >= 0.0f && U + V <= det && T >= 0.0f && T <= det;
+    best.d2 = crosses ? 0.0f : best.d2;
+    if (FULL) {
+        const float sx = T / det;
+        best.s = crosses ? sx : best.s;
+        best.feature = crosses ? 5.0f : best.feature;
+        best.c = mk(crosses ? p0.x + d.x * sx : best.c.x, crosses ? p0.y + d.y * sx : best.c.y, crosses ? p0.z + d.z * sx : best.c.z);
+    }
+    return best;
+}
+
+// What a lane keeps of its segment for the box bounds: the midpoint (relative to HSpace's centre for FMT 11), the half extent of the
+// segment's own box, and the three axes n_i = normalize(d x axis_i) — n_x = (0, d.z, -d.y) / |.|, n_y = (-d.z, 0, d.x) / |.|,
+// n_z = (d.y, -d.x, 0) / |.|, two components each.  An axis whose cross product has no usable length (a segment along a coordinate
+// axis, a point, a length whose square leaves fp32's range) has both components 0 and contributes 0.
+struct SegBound { f3 m, hd; float xy, xz, yx, yz, zx, zy; };
+
+__device__ __forceinline__ void axis_pair(float u, float v, float& nu, float& nv)
+{
+    const float l2 = __builtin_fmaf(u, u, v * v);
+    const float inv = (l2 > 1e-30f && l2 < 1e30f) ? __builtin_amdgcn_rsqf(l2) : 0.0f;
+    nu = u * inv; nv = v * inv;
+}
+
+// Lower bound of the squared distance from the segment to a box with centre offset t = c - m and half extent h: the larger of
+//   (a) the point bound of nearest.hip from the midpoint with h enlarged per axis by |d| / 2 — the box against the segment's box;
+//   (b) per axis n_i the separation |t . n_i| - sum_j h_j |n_i,j|, clamped at 0 and squared: n_i is perpendicular to d, so the segment
+//       projects onto a point, and a projection onto a unit vector cannot lengthen a distance.
+__device__ __forceinline__ float segment_box_bound(const f3& t, const f3& h, const SegBound& sb)
+{
+    const float ex = fmaxf(fabsf(t.x) - h.x - sb.hd.x, 0.0f), ey = fmaxf(fabsf(t.y) - h.y - sb.hd.y, 0.0f), ez = fmaxf(fabsf(t.z) - h.z - sb.hd.z, 0.0f);
+    const float ba = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
+    const float sx = fabsf(__builtin_fmaf(t.y, sb.xy, t.z * sb.xz)) - __builtin_fmaf(h.y, fabsf(sb.xy), h.z * fabsf(sb.xz));
+    const float sy = fabsf(__builtin_fmaf(t.x, sb.yx, t.z * sb.yz)) - __builtin_fmaf(h.x, fabsf(sb.yx), h.z * fabsf(sb.yz));
+    const float sz = fabsf(__builtin_fmaf(t.x, sb.zx, t.y * sb.zy)) - __builtin_fmaf(h.x, fabsf(sb.zx), h.y * fabsf(sb.zy));
+    const float sm = fmaxf(fmaxf(sx, sy), fmaxf(sz, 0.0f));
+    return fmaxf(ba, sm * sm);
+}
+//   FMT 11: per axis t = c * is - (m - centre), h * is (c, h the fp16 centre and half extent: world = g * is + centre): v_fma_mix_f32
+//           decodes.  An empty child has h < 0.
+//   FMT 0:  t = (lo + hi) / 2 - m, h = (hi - lo) / 2 from the fp32 planes.  An empty child has lo = +inf.
+// A NaN for an empty child, which no threshold admits.
+__device__ __forceinline__ float seg_bound_hc(uint32_t px, uint32_t py, uint32_t pz, const SegBound& sb, const HSpace& hs)
+{
+    const half2_t hx = __builtin_bit_cast(half2_t, px), hy = __builtin_bit_cast(half2_t, py), hz = __builtin_bit_cast(half2_t, pz);
+    const f3 t = mk(__builtin_fmaf((float)hx.x, hs.isx, -sb.m.x), __builtin_fmaf((float)hy.x, hs.isy, -sb.m.y), __builtin_fmaf((float)hz.x, hs.isz, -sb.m.z));
+    const f3 h = mk((float)hx.y * hs.isx, (float)hy.y * hs.isy, (float)hz.y * hs.isz);
+    const float b = segment_box_bound(t, h, sb);
+    return (float)hx.y < 0.0f ? __builtin_nanf("") : b;
+}
+__device__ __forceinline__ float seg_bound_f32(const SegBound& sb, float lx, float ly, float lz, float hx, float hy, float hz)
+{
+    const f3 t = mk(__builtin_fmaf(0.5f, lx + hx, -sb.m.x), __builtin_fmaf(0.5f, ly + hy, -sb.m.y), __builtin_fmaf(0.5f, lz + hz, -sb.m.z));
+    const f3 h = mk(0.5f * (hx - lx), 0.5f * (hy - ly), 0.5f * (hz - lz));
+    const float b = segment_box_bound(t, h, sb);
+    return lx <= hx ? b : __builtin_nanf("");
+}
+
+struct SegBest { float d2; int slot; uint32_t prim; };
+
+// One segment per lane through the two-child BVH: traverse_nearest's walk (nearest.hip) with the segment's bound and statement.  thr
+// is min(best d2, r2) widened (segment.h): a child is entered iff its bound is at most thr and it is not empty; of two such children
+// the nearer is entered and the other pushed.  A visit pushes at most one reference and descends one level, so max_depth + 1 entries
+// hold here too, and a popped reference is entered without a second look at its own box: an entry is one word.  The boxes only prune:
+// the winner is decided by the statement, d2 <= r2, smallest d2, ties to the lowest triangle index, whatever order the walk reaches
+// the triangles in.
+template <int FMT, bool COUNT>
+__device__ __forceinline__ void traverse_segments(const DeviceScene& sc, const LaneStack& st, bool active, const f3& p0, const f3& p1, const f3& d, float a,
+                                                  const SegBound& sb, float r2, float abs_term, SegBest& best, uint2& visits)
+{
+    best.d2 = INFINITY; best.slot = -1; best.prim = 0xFFFFFFFFu;
+    float thr = r2 * kNearRel + abs_term;
+    int sp = 0;
+    int node = (active && sc.n_tris != 0u) ? 0 : kSentinel;
+    while (node != kSentinel) {
+        if (node >= 0) {
+            float b0, b1;
+            int c0, c1;
+            if (FMT == 11) {
+                // child references of inner nodes are byte offsets into hcnodes; a leaf is ~slot
+                const uint4* np = (const uint4*)((const char*)sc.hcnodes + (size_t)(uint32_t)node);
+                const uint4 qa = np[0], qb = np[1];
+                b0 = seg_bound_hc(qa.x, qa.y, qa.z, sb, sc.hspace);
+                b1 = seg_bound_hc(qb.x, qb.y, qb.z, sb, sc.hspace);
+                c0 = (int)qa.w; c1 = (int)qb.w;
+            } else {
+                // child 0: lo (a.x a.y a.z) hi (a.w b.x b.y); child 1: lo (b.z b.w c.x) hi (c.y c.z c.w)
+                const BvhNode* np = sc.nodes + node;
+                const float4 na = np->a, nb = np->b, nc = np->c;
+                const int4 ch = np->d;
+                b0 = seg_bound_f32(sb, na.x, na.y, na.z, na.w, nb.x, nb.y);
+                b1 = seg_bound_f32(sb, nb.z, nb.w, nc.x, nc.y, nc.z, nc.w);
+                c0 = ch.x; c1 = ch.y;
+            }
+            if (COUNT) visits.x++;
+            const bool h0 = b0 <= thr, h1 = b1 <= thr;          // false for an empty child's NaN
+            if (h0 && h1) {
+                const bool first0 = b0 <= b1;
+                st.push(sp, first0 ? c1 : c0);
+                sp++;
+                node = first0 ? c0 : c1;
+            } else if (h0) {
+                node = c0;
+            } else if (h1) {
+                node = c1;
+            } else {
+                if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
+            }
+        } else {
+            const int slot = ~node;
+            const TriRecord* tp = sc.tris + slot;
+            const float4 r0 = tp->r0, r1 = tp->r1, r2_ = tp->r2;
+            const SegPoint p = segment_triangle<false>(p0, p1, d, a, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2_.x));
+            const uint32_t prim = __float_as_uint(r2_.y);
+            if (COUNT) visits.y++;
+            if (p.d2 <= r2 && (p.d2 < best.d2 || (p.d2 == best.d2 && prim < best.prim))) {
+                best.d2 = p.d2; best.slot = slot; best.prim = prim;
+                thr = p.d2 * kNearRel + abs_term;
+            }
+            if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
+        }
+    }
+}
+
+template <int FMT, bool COUNT>
+__global__ void __launch_bounds__(256)
+k_query_segments(const DeviceScene sc, uint32_t stack_entries, float abs_term, const float4* __restrict__ segments, uint32_t n, float4* __restrict__ out,
+                 uint2* __restrict__ visits_out, uint32_t flags)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;      // n <= 2^31 - 1: the grid's last lane is below 2^31 + 255
+    LaneStack st;
+    st.base = segment_lds + (threadIdx.x >> 6) * (stack_entries * 64u) + (threadIdx.x & 63u);
+    // segment i of the array, or an inert one for a lane past n.  ok: the lane has a segment and the segment can find something —
+    // every coordinate and every component of d finite, max_radius >= 0 and no NaN (include/acgpt.h: "a miss before any traversal").
+    // The eighth float is loaded with its float4 and never used.
+    f3 p0 = mk(0.0f), p1 = mk(0.0f), d = mk(0.0f);
+    float r2 = 0.0f;
+    bool ok = false;
+    if (i < n) {
+        const float4 g0 = segments[2ull * i], g1 = segments[2ull * i + 1ull];
+        p0 = mk(g0.x, g0.y, g0.z);
+        p1 = mk(g1.x, g1.y, g1.z);
+        d = p1 - p0;
+        r2 = g0.w * g0.w;
+        ok = __builtin_isfinite(g0.x) && __builtin_isfinite(g0.y) && __builtin_isfinite(g0.z) && __builtin_isfinite(g1.x) && __builtin_isfinite(g1.y) &&
+             __builtin_isfinite(g1.z) && __builtin_isfinite(d.x) && __builtin_isfinite(d.y) && __builtin_isfinite(d.z) && g0.w >= 0.0f;   // false when max_radius is a NaN
+        if (!ok) { p0 = mk(0.0f); p1 = mk(0.0f); d = mk(0.0f); }
+    }
+    const float a = dot(d, d);
+    // the bounds' view of the segment and the lane's absolute term (segment.h)
+    SegBound sb;
+    sb.m = mk(__builtin_fmaf(0.5f, d.x, p0.x), __builtin_fmaf(0.5f, d.y, p0.y), __builtin_fmaf(0.5f, d.z, p0.z));
+    if (FMT == 11) sb.m = mk(sb.m.x - sc.hspace.cx, sb.m.y - sc.hspace.cy, sb.m.z - sc.hspace.cz);
+    sb.hd = mk(0.5f * fabsf(d.x), 0.5f * fabsf(d.y), 0.5f * fabsf(d.z));
+    axis_pair(d.z, -d.y, sb.xy, sb.xz);
+    axis_pair(-d.z, d.x, sb.yx, sb.yz);
+    axis_pair(d.y, -d.x, sb.zx, sb.zy);
+    if (COUNT && (flags & kSegmentNoAxes)) { sb.xy = sb.xz = sb.yx = sb.yz = sb.zx = sb.zy = 0.0f; }
+    const float qs = fmaxf(fmaxf(fmaxf(fabsf(p0.x), fabsf(p0.y)), fmaxf(fabsf(p0.z), fabsf(p1.x))), fmaxf(fabsf(p1.y), fabsf(p1.z)));
+    const float lane_abs = segment_abs_term(abs_term, qs);
+    SegBest best;
+    uint2 visits = make_uint2(0u, 0u);
+    traverse_segments<FMT, COUNT>(sc, st, ok, p0, p1, d, a, sb, r2, lane_abs, best, visits);
+    if (i >= n) return;
+    float4 o0 = make_float4(-1.0f, __uint_as_float(0xFFFFFFFFu), 0.0f, 0.0f), o1 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
+    if (ok && best.slot >= 0) {
+        // the winner's triangle once more: the same statement on the same inputs gives the same bits, and the walk carries three
+        // registers for its best candidate instead of nine
+        const TriRecord* tp = sc.tris + best.slot;
+        const float4 r0 = tp->r0, r1 = tp->r1, r2_ = tp->r2;
+        const SegPoint p = segment_triangle<true>(p0, p1, d, a, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2_.x));
+        const float4 sr = sc.shade[best.slot];
+        o0 = make_float4(sqrtf(p.d2), __uint_as_float(best.prim), p.s, p.feature);
+        o1 = make_float4(p.c.x, p.c.y, p.c.z, __uint_as_float(__float_as_uint(sr.w) & kShadeMatMask));
+    }
+    out[2ull * i] = o0;
+    out[2ull * i + 1ull] = o1;
+    if (COUNT) visits_out[i] = visits;
+}
+
+template <typename K>
+static hipError_t launch_segments(K kernel, const DeviceScene& sc, uint32_t stack_entries, float abs_term, const float4* segments, uint32_t n, float4* out,
+                                  uint2* visits, uint32_t flags, hipStream_t stream)
+{
+    const size_t lds = (size_t)(256 / 64) * stack_entries * 64u * sizeof(uint32_t);
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    kernel<<<(n + 255u) / 256u, 256, lds, stream>>>(sc, stack_entries, abs_term, segments, n, out, visits, flags);
+    return hipGetLastError();
+}
+
+hipError_t launch_query_segments(int fmt, const DeviceScene& sc, uint32_t stack_entries, float abs_term, const float4* segments, uint32_t n, float4* out,
+                                 hipStream_t stream)
+{
+    if (fmt == 11) return launch_segments(k_query_segments<11, false>, sc, stack_entries, abs_term, segments, n, out, nullptr, 0u, stream);
+    return launch_segments(k_query_segments<0, false>, sc, stack_entries, abs_term, segments, n, out, nullptr, 0u, stream);
+}
+
+hipError_t launch_segments_visits(int fmt, const DeviceScene& sc, uint32_t stack_entries, float abs_term, const float4* segments, uint32_t n, float4* out,
+                                  uint2* visits, uint32_t flags, hipStream_t stream)
+{
+    if (fmt == 11) return launch_segments(k_query_segments<11, true>, sc, stack_entries, abs_term, segments, n, out, visits, flags, stream);
+    return launch_segments(k_query_segments<0, true>, sc, stack_entries, abs_term, segments, n, out, visits, flags, stream);
+}
+
+}  // namespace ptd

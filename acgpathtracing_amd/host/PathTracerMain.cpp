@@ -17,7 +17,7 @@
 //              [--until-error E [--until-permille P] [--error-floor F] [--error-out file.pfm]]
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
 //              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k] ...] [--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k] ...]
-//              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...]
+//              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...] [--clearance x0,y0,z0,x1,y1,z1[,radius] ...]
 //              [--ao K[,radius[,bias]] --ao-out file.pfm [--ao-frames n]]
 // --ao K[,radius[,bias]] with --ao-out: once the scene is set and before the first frame, the ambient occlusion of the view
 // (pt_render_features + pt_ao_image): K rays per pixel (1..256) and call over --ao-frames calls (default 1; call j has seed j and
@@ -55,6 +55,14 @@
 // weights of its second and third vertex there), {"sweep": [...], "tmax": ..., "hit": false} if nothing is touched.  Floats are printed
 // with nine digits.  A value that is not finite (tmax may be inf), a negative radius or a negative tmax is refused with exit status 2.
 // The frames are the same with or without it.
+// --clearance x0,y0,z0,x1,y1,z1[,radius] (repeatable): once the scene is set and before the first frame, how far the segment from
+// (x0, y0, z0) to (x1, y1, z1) is from the scene and where the two come closest, all in one call of pt_query_segments with no limit on
+// the distance, one JSON line each: {"clearance": [the six coordinates], "radius": r, "found": true, "distance": .., "clear": <distance
+// - radius: negative where a capsule of that radius penetrates>, "triangle": .., "material": "<newmtl name>", "s": <parameter of the
+// closest point on the segment>, "feature": <0, 1 an end; 2, 3, 4 an edge of the triangle; 5 the segment crosses it>, "on_segment":
+// [..], "point": [<on the triangle>]}, {"clearance": [..], "radius": r, "found": false} for a scene without triangles.  radius
+// defaults to 0.  Floats are printed with nine digits.  A coordinate that is not finite or a radius that is negative or no number is
+// refused with exit status 2.  The frames are the same with or without it.
 // --bloom (with --tonemap or --exposure): the image the display transform shows goes through pt_bloom first.  threshold is in display
 // units, multiples of exposed white, and is divided by the exposure (and so are the default knee, half the threshold, and the
 // clamp, none); an automatic exposure is metered on the image without its glare and then applied as a manual one.  --out-hdr gets
@@ -825,6 +833,39 @@ static void sweepSpheres(PathTracerState& state, const TinyObjWrapper& obj, cons
     fflush(stdout);
 }
 
+// --clearance: every segment in one call of pt_query_segments; one JSON line per segment
+struct ClearanceSegment { float g[8]; float radius; };
+static void clearanceSegments(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<ClearanceSegment>& segs)
+{
+    const size_t n = segs.size();
+    void* d_segs = nullptr; void* d_out = nullptr;
+    std::vector<float> in(n * 8);
+    for (size_t i = 0; i < n; i++) for (int k = 0; k < 8; k++) in[i * 8 + k] = segs[i].g[k];
+    std::vector<pt_segment_hit> out(n);
+    std::string err;
+    if (pt_device_malloc(state.context, &d_segs, n * 32) != 0 || pt_device_malloc(state.context, &d_out, n * sizeof(pt_segment_hit)) != 0 ||
+        pt_copy_to_device(state.context, d_segs, in.data(), n * 32) != 0 ||
+        pt_query_segments(state.context, (const float*)d_segs, n, (pt_segment_hit*)d_out) != 0 ||
+        pt_copy_to_host(state.context, out.data(), d_out, n * sizeof(pt_segment_hit)) != 0)
+        err = pt_last_error(state.context);
+    if (d_segs) pt_device_free(state.context, d_segs);
+    if (d_out) pt_device_free(state.context, d_out);
+    if (!err.empty()) throw Exception("clearance: " + err);
+    const std::vector<std::string>& names = obj.getMaterialNames();
+    for (size_t i = 0; i < n; i++) {
+        const pt_segment_hit& r = out[i];
+        const float* g = segs[i].g;
+        printf("{\"clearance\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"radius\": %.9g, ", g[0], g[1], g[2], g[4], g[5], g[6], segs[i].radius);
+        if (r.prim == 0xFFFFFFFFu) { printf("\"found\": false}\n"); continue; }
+        std::string name = r.material < names.size() ? names[r.material] : std::string();
+        for (size_t k = 0; k < name.size(); k++) if (name[k] == '"' || name[k] == '\\' || (unsigned char)name[k] < 0x20) name[k] = '_';
+        const float px = g[0] + (g[4] - g[0]) * r.s, py = g[1] + (g[5] - g[1]) * r.s, pz = g[2] + (g[6] - g[2]) * r.s;
+        printf("\"found\": true, \"distance\": %.9g, \"clear\": %.9g, \"triangle\": %u, \"material\": \"%s\", \"s\": %.9g, \"feature\": %d, \"on_segment\": [%.9g, %.9g, %.9g], \"point\": [%.9g, %.9g, %.9g]}\n",
+               r.distance, r.distance - segs[i].radius, r.prim, name.c_str(), r.s, (int)r.feature, px, py, pz, r.cx, r.cy, r.cz);
+    }
+    fflush(stdout);
+}
+
 // --nearest: every point in one call of pt_query_nearest; one JSON line per point
 static void nearestPoints(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<float4>& points)
 {
@@ -916,6 +957,7 @@ int main(int argc, char** argv)
     std::vector<int2> picks;
     std::vector<PickAll> pickAlls;
     std::vector<float4> nearest;
+    std::vector<ClearanceSegment> clearances;
     std::vector<OverlapBox> overlaps;
     std::vector<IntersectTri> intersects;
     std::vector<SweepArg> sweeps;
@@ -1017,6 +1059,15 @@ int main(int argc, char** argv)
             const int got = sscanf(next(), "%f,%f,%f,%f", &q.x, &q.y, &q.z, &q.w);
             if (got < 3 || !std::isfinite(q.x) || !std::isfinite(q.y) || !std::isfinite(q.z) || !(q.w >= 0.0f)) { std::cerr << "--nearest x,y,z[,radius]: finite coordinates, a radius >= 0" << std::endl; return 2; }
             nearest.push_back(q);
+        }
+        else if (a == "--clearance") {
+            ClearanceSegment cs = {{0.0f, 0.0f, 0.0f, INFINITY, 0.0f, 0.0f, 0.0f, 0.0f}, 0.0f};
+            float* g = cs.g;
+            const int got = sscanf(next(), "%f,%f,%f,%f,%f,%f,%f", &g[0], &g[1], &g[2], &g[4], &g[5], &g[6], &cs.radius);
+            bool fine = got >= 6 && cs.radius >= 0.0f && std::isfinite(cs.radius);
+            for (int k = 0; k < 7; k++) if (k != 3 && !std::isfinite(g[k])) fine = false;
+            if (!fine) { std::cerr << "--clearance x0,y0,z0,x1,y1,z1[,radius]: finite coordinates, a finite radius >= 0" << std::endl; return 2; }
+            clearances.push_back(cs);
         }
         else if (a == "--overlap") {
             OverlapBox b = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, 8u};
@@ -1170,6 +1221,7 @@ int main(int argc, char** argv)
         if (!picks.empty()) { std::cout.flush(); pickPixels(state, obj, picks); }
         if (!pickAlls.empty()) { std::cout.flush(); pickAllPixels(state, obj, pickAlls); }
         if (!nearest.empty()) { std::cout.flush(); nearestPoints(state, obj, nearest); }
+        if (!clearances.empty()) { std::cout.flush(); clearanceSegments(state, obj, clearances); }
         if (!overlaps.empty()) { std::cout.flush(); overlapBoxes(state, obj, overlaps); }
         if (!intersects.empty()) { std::cout.flush(); intersectTriangles(state, intersects); }
         if (!sweeps.empty()) { std::cout.flush(); sweepSpheres(state, obj, sweeps); }

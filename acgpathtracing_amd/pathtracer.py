@@ -945,6 +945,103 @@ def bakeDistanceField(state, resolution, bounds=None, max_radius=float("inf"), r
     return (dist, got["prim"].reshape(shape)) if return_prims else dist
 
 
+# ------------------------------------------------------------------ segment to mesh ----
+SEGMENT_HIT_DTYPE = np.dtype([("distance", np.float32), ("prim", np.uint32), ("s", np.float32), ("feature", np.float32), ("point", np.float32, 3), ("material", np.uint32)])      # pt_segment_hit
+assert SEGMENT_HIT_DTYPE.itemsize == 32
+
+
+def _query_segments_tensor(state, segments):
+    import torch
+    if segments.device.type != "cuda" or segments.device.index != state._device:
+        raise PathTracerError("querySegments: the segments are on %s, the context is on cuda:%d" % (segments.device, state._device))
+    if segments.dtype != torch.float32:
+        raise PathTracerError("querySegments: the segments must be float32, got %s" % segments.dtype)
+    if segments.dim() != 2 or segments.shape[1] != 8:
+        raise PathTracerError("querySegments: expected an (n, 8) tensor {p0, max_radius, p1, ignored}, got shape %s" % (tuple(segments.shape),))
+    if not segments.is_contiguous():
+        raise PathTracerError("querySegments: the segments must be contiguous (nothing is copied)")
+    n = int(segments.shape[0])
+    with torch.cuda.device(segments.device):
+        out = torch.empty((n, 8), dtype=torch.float32, device=segments.device)
+        torch.cuda.current_stream().synchronize()      # the segments' producer and the allocation; the call below returns synchronised
+    _check(state.context, _native.hip().pt_query_segments(state.context, segments.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_segments")
+    return {"distance": out[:, 0], "prim": out[:, 1].view(torch.int32), "s": out[:, 2], "feature": out[:, 3], "point": out[:, 4:7], "material": out[:, 7].view(torch.int32)}
+
+
+def _segment_records(what, segments, max_radius):
+    """(n, 8) float32 {p0, max_radius | p1, 0} from an (n, 6) array {p0, p1} and one radius, or the (n, 8) array itself"""
+    g = np.asarray(segments)
+    if g.ndim != 2 or g.shape[1] not in (6, 8):
+        raise PathTracerError("%s: expected an (n, 6) or (n, 8) array, got shape %s" % (what, g.shape))
+    if g.dtype.kind not in "fiu":
+        raise PathTracerError("%s: the segments must be numbers, got %s" % (what, g.dtype))
+    if g.shape[1] == 8:
+        return np.ascontiguousarray(g, np.float32)
+    radius = float(max_radius)
+    if not radius >= 0.0:
+        raise PathTracerError("%s: max_radius must be non-negative, got %r" % (what, max_radius))
+    q = np.zeros((g.shape[0], 8), np.float32)
+    q[:, 0:3] = g[:, 0:3]
+    q[:, 3] = radius
+    q[:, 4:7] = g[:, 3:6]
+    return q
+
+
+def querySegments(state, segments, max_radius=float("inf")):
+    """How far each line segment is from the scene on the GPU, and where the two come closest (include/acgpt.h pt_query_segments).
+
+    A NumPy array (or anything np.asarray takes) of shape (n, 6) {p0 xyz, p1 xyz} — every segment gets max_radius — or (n, 8)
+    {p0 xyz, max_radius, p1 xyz, ignored} goes to the device and the answer comes back: a dict of arrays distance (n,) float32 (0 where
+    the segment passes through a triangle, -1 where nothing lies within the radius), prim (n,) uint32 (the triangle's index in the
+    scene's order, 0xFFFFFFFF), s (n,) the parameter of the closest point on the segment (p0 + (p1 - p0) s), feature (n,) float32
+    (0, 1: an end of the segment; 2, 3, 4: an edge of the triangle; 5: the segment crosses it), point (n, 3) the closest point on the
+    triangle, material (n,) uint32.
+
+    A torch tensor must be (n, 8) float32, contiguous and on the context's device; nothing is copied, its data_ptr() goes straight in,
+    and the answer is torch tensors on that device: views of one (n, 8) float32 tensor, prim and material as int32 (-1 on a miss).
+    torch's current stream is synchronised before the call, and the call returns synchronised."""
+    if _is_tensor(segments):
+        return _query_segments_tensor(state, segments)
+    q = _segment_records("querySegments", segments, max_radius)
+    n = q.shape[0]
+    out = np.zeros(n, SEGMENT_HIT_DTYPE)
+    if n:
+        L = _native.hip()
+        bufs = _device_buffers(state, 2, out.nbytes)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], q.ctypes.data, q.nbytes), "copy to device")
+            _check(state.context, L.pt_query_segments(state.context, bufs[0], n, bufs[1]), "pt_query_segments")
+            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    return {k: np.ascontiguousarray(out[k]) for k in SEGMENT_HIT_DTYPE.names}
+
+
+def capsuleClearance(state, p0, p1, radius):
+    """The clearance of capsules with axes p0 -> p1, (n, 3) each, and radius (one number or (n,)) from the scene: querySegments with no
+    limit on the distance.  Returns a dict: clearance (n,) float32 = distance - radius (negative: the capsule penetrates by that much;
+    -radius where its axis passes through the surface; +inf for a scene without triangles), prim (n,) uint32, on_axis (n, 3) and
+    on_mesh (n, 3) float32 the witness points — on_mesh - on_axis is the direction to push the mesh away in —, s (n,) and feature (n,)
+    as querySegments gives them."""
+    a, b = np.asarray(p0), np.asarray(p1)
+    if a.ndim != 2 or a.shape[1] != 3 or b.shape != a.shape:
+        raise PathTracerError("capsuleClearance: expected two (n, 3) arrays, got shapes %s and %s" % (a.shape, b.shape))
+    if a.dtype.kind not in "fiu" or b.dtype.kind not in "fiu":
+        raise PathTracerError("capsuleClearance: the end points must be numbers, got %s and %s" % (a.dtype, b.dtype))
+    r = np.asarray(radius)
+    if r.dtype.kind not in "fiu" or r.shape not in ((), (a.shape[0],)):
+        raise PathTracerError("capsuleClearance: radius is one number or one per capsule, got %r" % (radius,))
+    r = np.broadcast_to(r.astype(np.float32), (a.shape[0],))
+    if not (np.isfinite(r).all() and (r >= 0).all()):
+        raise PathTracerError("capsuleClearance: every radius must be finite and non-negative")
+    a, b = a.astype(np.float32), b.astype(np.float32)
+    got = querySegments(state, np.concatenate([a, b], axis=1))
+    found = got["prim"] != 0xFFFFFFFF
+    clearance = np.where(found, got["distance"] - r, np.float32(np.inf)).astype(np.float32)
+    on_axis = (a + (b - a) * got["s"][:, None]).astype(np.float32)
+    return {"clearance": clearance, "prim": got["prim"], "on_axis": on_axis, "on_mesh": got["point"], "s": got["s"], "feature": got["feature"]}
+
+
 # ------------------------------------------------------------------ box overlap ----
 def _overlap_args(what, max_prims, counts):
     try:

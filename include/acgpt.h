@@ -635,6 +635,67 @@ typedef struct { float t; uint32_t prim; float u, v; float cx, cy, cz; uint32_t 
 int pt_query_sweep(pt_ctx* ctx, const float* sweeps, size_t n, pt_sweep_hit* hits);
 int pt_query_sweep_any(pt_ctx* ctx, const float* sweeps, size_t n, uint8_t* blocked);
 
+/* ---- segment-to-mesh distance on the device (opt-in; nothing above changes) --------------------------------------------------------
+ * How far a line segment is from the surface and where the two come closest: the clearance query of motion planning.  A capsule (robot
+ * link, cable, tool shaft, limb) clears the mesh by this distance minus its radius, and the closest pair is the direction to push away
+ * in; a segment that passes THROUGH a triangle has distance 0, which no sampling of pt_query_nearest along the axis finds.
+ * pt_query_nearest's memory and call rules: DEVICE arrays, 16-byte aligned; the call enqueues on the context's stream and returns
+ * synchronised, acts on rank 0 of a pt_create_multi context, never writes the accumulation buffer, the frame buffer or pt_stats, walks
+ * the node array the scene holds (pt_bvh_info.device_bytes does not change, with pt_query_nearest's one exception) and uses no
+ * atomics: two calls give the same bits.  A scene without triangles answers every segment with the miss record.
+ *
+ *   segments  n records of 8 floats {p0.x, p0.y, p0.z, max_radius | p1.x, p1.y, p1.z, ignored}.  The eighth float is never read into a
+ *             decision: a NaN there changes nothing.
+ *   out       n records of 32 bytes (pt_segment_hit)
+ *   d2        the squared distance from the segment to a triangle, all fp32, every multiply, add and division on its own, evaluated as
+ *             written, no fused multiply-add (tests/segment_ref.py is the NumPy statement, equal bit for bit).  With the vectors the
+ *             build stores for the triangle, v0, e1 = v1 - v0, e2 = v2 - v0, and d = p1 - p0 (one subtraction per component),
+ *             a = dot(d, d), dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z, six sub-tests, each giving (d2, s, c): the squared distance,
+ *             the parameter on the segment and the point on the triangle.
+ *               feature 0   pt_query_nearest's closest_on_triangle at p0, exactly: its d2 and c; s = 0
+ *               feature 1   the same at p1 as given in the record (not p0 + d); s = 1
+ *               feature 2   segment against the edge {A, E} = {v0, e1}
+ *               feature 3   {v0, e2}
+ *               feature 4   {fl(v0 + e1), fl(e2 - e1)}, one operation per component
+ *               feature 5   the segment crosses the triangle
+ *             Features 2 to 4, Ericson, Real-Time Collision Detection 5.1.9, with every case a select:
+ *               r = p0 - A;  e = dot(E, E);  b = dot(d, E);  c_ = dot(d, r);  f = dot(E, r);  den = a e - b b
+ *               (num1, den1) = (b f - c_ e, den)  if a > 0 and e > 0 and den > 0
+ *                              (-c_, a)           if a > 0 and not e > 0
+ *                              (0, 1)             otherwise (a segment without length; parallel lines)
+ *               s0 = clamp01(num1 / den1);   clamp01(q): q < 0 ? 0 : q, then q > 1 ? 1 : q (a -0 stays, a NaN stays)
+ *               tnom = b s0 + f;   lo = e > 0 and tnom < 0;   hi = e > 0 and tnom > e
+ *               (num2, den2) = (tnom, e) if e > 0, else (0, 1);  lo: (-c_, a);  hi: (b - c_, a);  (lo or hi) and not a > 0: (0, 1)
+ *               q2 = clamp01(num2 / den2);   s = (lo or hi) ? q2 : s0;   t = lo ? 0 : hi ? 1 : q2
+ *               p~ = p0 + d s;  c = A + E t (a product, then a sum, per component);  d2 = dot(p~ - c, p~ - c)
+ *             Two IEEE divisions per edge; every denominator a select keeps is > 0.
+ *             Feature 5, a two-sided Moeller-Trumbore test in plain multiplies and adds, cross(a, b).x = a.y b.z - a.z b.y:
+ *               pv = cross(d, e2);  det = dot(e1, pv);  tv = p0 - v0;  U = dot(tv, pv);  qv = cross(tv, e1);  V = dot(d, qv);
+ *               T = dot(e2, qv);  det < 0: det, U, V, T change sign
+ *               accepted iff det > 0 and U >= 0 and V >= 0 and U + V <= det and 0 <= T <= det;
+ *               then d2 = 0 exactly, s = T / det, c = p0 + d s
+ *             Among features 0 to 4 the smallest d2 wins, ties to the lower feature; a NaN d2 is no candidate (a feature replaces the
+ *             running one iff its d2 is smaller, or the running d2 is a NaN and its own is not).  An accepted crossing overrides them.
+ *             Nine divisions per triangle.
+ *   candidate a triangle with d2 <= max_radius * max_radius, the product taken in fp32; max_radius = +inf is allowed and its square
+ *             is +inf.  A NaN d2 is no candidate.
+ *   answer    the candidate with the smallest d2; ties go to the lowest triangle index in the caller's index-buffer order
+ *   found     distance = sqrtf(d2) of the winner, one IEEE square root; prim its index; s and feature the winner's, the feature number
+ *             stored as a float; (cx, cy, cz) the winner's point c on the triangle (for feature 5 the crossing point p0 + d s);
+ *             material the triangle's material id.  The point on the segment is p0 + (p1 - p0) s.
+ *   a miss before any traversal: a non-finite coordinate of p0 or p1, a non-finite component of d (finite ends whose difference
+ *             overflows), a NaN or negative max_radius, a scene without triangles
+ *   miss      {distance -1, prim 0xFFFFFFFF, s 0, feature 0, c (0, 0, 0), material 0xFFFFFFFF}: pt_hit's pattern
+ * Not watertight in d2 at shared edges: neighbouring triangles compute a shared edge from their own stored vectors; the smaller d2
+ * wins, ties to the lower index.  Products of four lengths (den, the va, vb, vc of features 0 and 1, the crossing test's U, V, T)
+ * leave fp32's range when edge length times segment length times the distance between them passes about 1e19 squared; such a
+ * sub-test yields a NaN or fails and silently stops being a candidate.
+ * n == 0 is a no-op success.  Refused, with the context left usable, in pt_query_nearest's order: a null context, a null segments or
+ * out pointer with n > 0, n > 0x7FFFFFFF, an array that is not 16-byte aligned, an output that overlaps the segments, a context
+ * without a scene.                                                                                                                     */
+typedef struct { float distance; uint32_t prim; float s, feature; float cx, cy, cz; uint32_t material; } pt_segment_hit;   /* 32 bytes */
+int pt_query_segments(pt_ctx* ctx, const float* segments, size_t n, pt_segment_hit* out);
+
 /* ---- ambient occlusion traced on the device (opt-in; nothing above changes) -----------------------------------------------------
  * The share of the hemisphere over a surface point that is open within `radius`: K rays per point, generated, traced with
  * pt_query_any's walk and counted inside one kernel, so no ray reaches memory.  pt_ao_points takes the points from a device array

@@ -152,6 +152,11 @@ int pt_debug_sweep_visits(pt_ctx* ctx, const float* sweeps, size_t n, pt_sweep_h
  * instantiation that also counts its work: visits[2 i] = inner nodes query i visited, visits[2 i + 1] = triangles it tested.  counts:
  * DEVICE, n words; visits: DEVICE, 8-byte aligned, 2 n words; neither may be null.  tools/triangles_timing.py. */
 int pt_debug_triangles_visits(pt_ctx* ctx, const float* tris, size_t n, uint32_t* counts, uint32_t* visits);
+/* pt_query_segments (same records, same refusals) from a kernel instantiation that also counts: visits[2 i] = inner nodes segment i
+ * visited, visits[2 i + 1] = triangles it tested.  visits: DEVICE, 8-byte aligned, 2 n words.  flags: 0, or 1 to switch off the walk's
+ * second box bound (the three axes perpendicular to the segment), which changes the counts and never the records; anything else is
+ * refused.  tools/segments_timing.py. */
+int pt_debug_segments_visits(pt_ctx* ctx, const float* segments, size_t n, pt_segment_hit* out, uint32_t* visits, uint32_t flags);
 /* Sorted (morton, triangle) pairs of the last build, HOST outputs of n_tris. */
 int pt_read_morton(pt_ctx* ctx, uint32_t* codes_sorted, uint32_t* prims_sorted);
 /* What the scene's tree is made of, as the device holds it right now (tests/tree_ref.py validates it node by node).  Not part of the
