@@ -1,9 +1,10 @@
 // capi_query.hip — the entry points of include/acgpt.h that answer queries in device memory: pt_query_closest, pt_query_any, the
 // ordered multi-hit query pt_query_multi, the ambient-occlusion stage on top of them: pt_ao_points, pt_ao_image, and the
 // closest-point query pt_query_nearest, the box-overlap queries pt_query_overlap, pt_query_overlap_any and the swept-sphere casts
-// pt_query_sweep, pt_query_sweep_any, the triangle-against-mesh queries pt_query_triangles, pt_query_triangles_any and the
-// segment-to-mesh distance query pt_query_segments (each with its counting twin of include/acgpt_test.h).
-// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, overlap.hip, sweep.hip, tritri.hip and segment.hip.  The context and what the units share: context.h.
+// pt_query_sweep, pt_query_sweep_any, the triangle-against-mesh queries pt_query_triangles, pt_query_triangles_any, the
+// segment-to-mesh distance query pt_query_segments and the K-closest and within-radius queries pt_query_nearest_k,
+// pt_query_within_any (each with its counting twin of include/acgpt_test.h).
+// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip and segment.hip.  The context and what the units share: context.h.
 #include <cmath>
 
 #include "../../include/acgpt_test.h"
@@ -11,6 +12,7 @@
 #include "ao.h"
 #include "multihit.h"
 #include "nearest.h"
+#include "nearest_k.h"
 #include "overlap.h"
 #include "query.h"
 #include "segment.h"
@@ -130,6 +132,72 @@ PT_API int pt_debug_nearest_visits(pt_ctx* c, const float* points, size_t n, pt_
     if (int rc = nearest_prepare(c, "pt_debug_nearest_visits", points, n, out, visits, true, &fmt)) return rc < 0 ? 0 : rc;
     CK(c, ptd::launch_nearest_visits(fmt, device_scene(c), c->stack_entries, ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)points,
                                      (uint32_t)n, (float4*)out, (uint2*)visits, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- the K closest triangles, anything within a radius ----------------------------------------------------------------------------
+static_assert(PT_QUERY_NEAREST_MAX == ptd::kNearestMaxK, "PT_QUERY_NEAREST_MAX is the size of the kernel's largest list");
+
+// every refusal of the two calls and their twin before any device work, in pt_query_nearest's order with pt_query_multi's additions.
+// list: the call has max_k, out and counts; otherwise it has hit.  visits: null unless with_visits.  Returns 0 to go on, 1 refused,
+// -1 nothing to do (n == 0).
+static int nearest_k_prepare(pt_ctx* c, const char* fn, const float* points, size_t n, bool list, uint32_t max_k, const void* out, const void* counts,
+                             const void* hit, const void* visits, bool with_visits, int* fmt)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (n == 0) return -1;
+    if (list) {
+        if (max_k > PT_QUERY_NEAREST_MAX) return fail(c, f + "max_k must be at most " + std::to_string(PT_QUERY_NEAREST_MAX));
+        if ((max_k != 0u) != (out != nullptr)) return fail(c, f + "out goes with max_k: both or neither");
+        if (!out && !counts) return fail(c, f + "nothing to write (out and counts are both null)");
+    }
+    if (!points || (!list && !hit) || (with_visits && !visits)) return fail(c, f + "null argument");
+    if (n > 0x7FFFFFFFull) return fail(c, f + "too many points (2^31 - 1 per call)");
+    if (((uintptr_t)points & 15u) || ((uintptr_t)out & 15u) || ((uintptr_t)counts & 3u) || ((uintptr_t)visits & 7u))
+        return fail(c, f + "the point and record arrays must be 16-byte aligned, the counts 4-byte aligned");
+    // n < 2^31, max_k <= 8: the byte counts stay below 2^39
+    const struct { const void* p; size_t bytes; const char* name; } spans[5] = {
+        {points, n * 16u, "the points"}, {out, n * (size_t)max_k * sizeof(pt_nearest), "out"}, {counts, n * 4u, "counts"}, {hit, n, "hit"}, {visits, n * 8u, "the visit counts"}};
+    for (int k = 1; k < 5; k++) {
+        if (!spans[k].p) continue;
+        for (int j = 0; j < k; j++)
+            if (spans[j].p && spans_overlap(spans[j].p, spans[j].bytes, spans[k].p, spans[k].bytes))
+                return fail(c, f + spans[k].name + " overlaps " + spans[j].name);
+    }
+    return query_node_format(c, f, fmt);
+}
+
+PT_API int pt_query_nearest_k(pt_ctx* c, const float* points, size_t n, uint32_t max_k, pt_nearest* out, uint32_t* counts)
+{
+    int fmt = 0;
+    if (int rc = nearest_k_prepare(c, "pt_query_nearest_k", points, n, true, max_k, out, counts, nullptr, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_nearest_k");
+    CK(c, ptd::launch_query_nearest_k(fmt, device_scene(c), c->stack_entries, ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)points,
+                                      (uint32_t)n, max_k, (float4*)out, counts, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_query_within_any(pt_ctx* c, const float* points, size_t n, uint8_t* hit)
+{
+    int fmt = 0;
+    if (int rc = nearest_k_prepare(c, "pt_query_within_any", points, n, false, 0u, nullptr, nullptr, hit, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_within_any");
+    CK(c, ptd::launch_query_within_any(fmt, device_scene(c), c->stack_entries, ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)points,
+                                       (uint32_t)n, hit, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_debug_nearest_k_visits(pt_ctx* c, const float* points, size_t n, uint32_t max_k, pt_nearest* out, uint32_t* counts, uint8_t* hit, uint32_t* visits)
+{
+    if (c && hit && (max_k != 0u || out || counts)) return fail(c, "pt_debug_nearest_k_visits: hit goes with max_k 0 and no out or counts");
+    int fmt = 0;
+    if (int rc = nearest_k_prepare(c, "pt_debug_nearest_k_visits", points, n, hit == nullptr, max_k, out, counts, hit, visits, true, &fmt)) return rc < 0 ? 0 : rc;
+    CK(c, ptd::launch_nearest_k_visits(fmt, device_scene(c), c->stack_entries, ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)points,
+                                       (uint32_t)n, max_k, (float4*)out, counts, hit, (uint2*)visits, hit ? 1u : 0u, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -18,6 +18,7 @@
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
 //              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k] ...] [--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k] ...]
 //              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...] [--clearance x0,y0,z0,x1,y1,z1[,radius] ...]
+//              [--nearest-k x,y,z,k[,radius] ...] [--within x,y,z,radius ...]
 //              [--ao K[,radius[,bias]] --ao-out file.pfm [--ao-frames n]]
 // --ao K[,radius[,bias]] with --ao-out: once the scene is set and before the first frame, the ambient occlusion of the view
 // (pt_render_features + pt_ao_image): K rays per pixel (1..256) and call over --ao-frames calls (default 1; call j has seed j and
@@ -39,6 +40,14 @@
 // and third vertex at the point), {"nearest": [x, y, z], "found": false} if nothing lies within the radius.  Floats are printed with
 // nine digits.  A coordinate that is not finite or a radius that is negative or no number is refused with exit status 2.  The frames
 // are the same with or without it.
+// --nearest-k x,y,z,k[,radius] (repeatable): once the scene is set and before the first frame, the k closest triangles (k = 1..8) of the
+// point within the radius (default: no limit) in order, by pt_query_nearest_k with counts in one call per k, one JSON line each:
+// {"nearest_k": [x, y, z], "k": k, "count": <triangles within the radius>, "list": [{"distance": .., "triangle": .., "material":
+// "<newmtl name>", "point": [..], "u": .., "v": ..} per listed triangle, closest first]}.  Floats are printed with nine digits.  A
+// coordinate that is not finite, a k outside 1..8 or a radius that is negative or no number is refused with exit status 2.
+// --within x,y,z,radius (repeatable): whether anything of the scene lies within the radius of the point, all in one call of
+// pt_query_within_any, one JSON line each: {"within": [x, y, z], "radius": r, "hit": true or false}.  The same refusals.  The frames
+// are the same with or without either.
 // --overlap cx,cy,cz,hx,hy,hz[,k] (repeatable): once the scene is set and before the first frame, the triangles that overlap the
 // axis-aligned box of centre (cx, cy, cz) and half extent (hx, hy, hz), by pt_query_overlap in one call per k, one JSON line each:
 // {"overlap": [cx, cy, cz, hx, hy, hz], "count": <triangles that overlap the box>, "triangles": [<the k lowest indices among them,
@@ -894,6 +903,75 @@ static void nearestPoints(PathTracerState& state, const TinyObjWrapper& obj, con
     fflush(stdout);
 }
 
+// --nearest-k: the points of one k in one call of pt_query_nearest_k, with counts; one JSON line per point, in the order given
+struct NearestKPoint { float4 q; uint32_t k; };
+static void nearestKPoints(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<NearestKPoint>& points)
+{
+    const std::vector<std::string>& names = obj.getMaterialNames();
+    std::vector<std::string> lines(points.size());
+    for (uint32_t k = 1; k <= PT_QUERY_NEAREST_MAX; k++) {
+        std::vector<size_t> which;
+        std::vector<float4> in;
+        for (size_t i = 0; i < points.size(); i++) if (points[i].k == k) { which.push_back(i); in.push_back(points[i].q); }
+        const size_t n = in.size();
+        if (n == 0) continue;
+        void* d_points = nullptr; void* d_out = nullptr; void* d_counts = nullptr;
+        std::vector<pt_nearest> out(n * k);
+        std::vector<uint32_t> counts(n);
+        std::string err;
+        if (pt_device_malloc(state.context, &d_points, n * 16) != 0 || pt_device_malloc(state.context, &d_out, n * k * sizeof(pt_nearest)) != 0 ||
+            pt_device_malloc(state.context, &d_counts, n * 4) != 0 || pt_copy_to_device(state.context, d_points, in.data(), n * 16) != 0 ||
+            pt_query_nearest_k(state.context, (const float*)d_points, n, k, (pt_nearest*)d_out, (uint32_t*)d_counts) != 0 ||
+            pt_copy_to_host(state.context, out.data(), d_out, n * k * sizeof(pt_nearest)) != 0 ||
+            pt_copy_to_host(state.context, counts.data(), d_counts, n * 4) != 0)
+            err = pt_last_error(state.context);
+        if (d_points) pt_device_free(state.context, d_points);
+        if (d_out) pt_device_free(state.context, d_out);
+        if (d_counts) pt_device_free(state.context, d_counts);
+        if (!err.empty()) throw Exception("nearest-k: " + err);
+        char buf[512];
+        for (size_t i = 0; i < n; i++) {
+            const float4& q = in[i];
+            snprintf(buf, sizeof buf, "{\"nearest_k\": [%.9g, %.9g, %.9g], \"k\": %u, \"count\": %u, \"list\": [", q.x, q.y, q.z, k, counts[i]);
+            std::string line = buf;
+            for (uint32_t j = 0; j < k; j++) {
+                const pt_nearest& r = out[i * k + j];
+                if (r.prim == 0xFFFFFFFFu) break;
+                std::string name = r.material < names.size() ? names[r.material] : std::string();
+                for (size_t c = 0; c < name.size(); c++) if (name[c] == '"' || name[c] == '\\' || (unsigned char)name[c] < 0x20) name[c] = '_';
+                snprintf(buf, sizeof buf, "%s{\"distance\": %.9g, \"triangle\": %u, \"material\": \"", j ? ", " : "", r.distance, r.prim);
+                line += buf;
+                line += name;
+                snprintf(buf, sizeof buf, "\", \"point\": [%.9g, %.9g, %.9g], \"u\": %.9g, \"v\": %.9g}", r.cx, r.cy, r.cz, r.u, r.v);
+                line += buf;
+            }
+            lines[which[i]] = line + "]}";
+        }
+    }
+    for (const std::string& l : lines) printf("%s\n", l.c_str());
+    fflush(stdout);
+}
+
+// --within: every point in one call of pt_query_within_any; one JSON line per point
+static void withinPoints(PathTracerState& state, const std::vector<float4>& points)
+{
+    const size_t n = points.size();
+    void* d_points = nullptr; void* d_hit = nullptr;
+    std::vector<uint8_t> hit(n);
+    std::string err;
+    if (pt_device_malloc(state.context, &d_points, n * 16) != 0 || pt_device_malloc(state.context, &d_hit, n) != 0 ||
+        pt_copy_to_device(state.context, d_points, points.data(), n * 16) != 0 ||
+        pt_query_within_any(state.context, (const float*)d_points, n, (uint8_t*)d_hit) != 0 ||
+        pt_copy_to_host(state.context, hit.data(), d_hit, n) != 0)
+        err = pt_last_error(state.context);
+    if (d_points) pt_device_free(state.context, d_points);
+    if (d_hit) pt_device_free(state.context, d_hit);
+    if (!err.empty()) throw Exception("within: " + err);
+    for (size_t i = 0; i < n; i++)
+        printf("{\"within\": [%.9g, %.9g, %.9g], \"radius\": %.9g, \"hit\": %s}\n", points[i].x, points[i].y, points[i].z, points[i].w, hit[i] ? "true" : "false");
+    fflush(stdout);
+}
+
 // --ao: the default sample pattern (pathtracer.aoSamples restated: the same double operations, the same fp32 pull-in)
 static std::vector<float> aoSamples(int K)
 {
@@ -957,6 +1035,8 @@ int main(int argc, char** argv)
     std::vector<int2> picks;
     std::vector<PickAll> pickAlls;
     std::vector<float4> nearest;
+    std::vector<NearestKPoint> nearestKs;
+    std::vector<float4> withins;
     std::vector<ClearanceSegment> clearances;
     std::vector<OverlapBox> overlaps;
     std::vector<IntersectTri> intersects;
@@ -1059,6 +1139,22 @@ int main(int argc, char** argv)
             const int got = sscanf(next(), "%f,%f,%f,%f", &q.x, &q.y, &q.z, &q.w);
             if (got < 3 || !std::isfinite(q.x) || !std::isfinite(q.y) || !std::isfinite(q.z) || !(q.w >= 0.0f)) { std::cerr << "--nearest x,y,z[,radius]: finite coordinates, a radius >= 0" << std::endl; return 2; }
             nearest.push_back(q);
+        }
+        else if (a == "--nearest-k") {
+            NearestKPoint p = {make_float4(0.0f, 0.0f, 0.0f, INFINITY), 0u};
+            float kf = 0.0f;
+            const int got = sscanf(next(), "%f,%f,%f,%f,%f", &p.q.x, &p.q.y, &p.q.z, &kf, &p.q.w);
+            if (got < 4 || !std::isfinite(p.q.x) || !std::isfinite(p.q.y) || !std::isfinite(p.q.z) || !(kf >= 1.0f && kf <= (float)PT_QUERY_NEAREST_MAX) || kf != std::floor(kf) || !(p.q.w >= 0.0f)) {
+                std::cerr << "--nearest-k x,y,z,k[,radius]: finite coordinates, k = 1..8, a radius >= 0" << std::endl; return 2;
+            }
+            p.k = (uint32_t)kf;
+            nearestKs.push_back(p);
+        }
+        else if (a == "--within") {
+            float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            const int got = sscanf(next(), "%f,%f,%f,%f", &q.x, &q.y, &q.z, &q.w);
+            if (got < 4 || !std::isfinite(q.x) || !std::isfinite(q.y) || !std::isfinite(q.z) || !(q.w >= 0.0f)) { std::cerr << "--within x,y,z,radius: finite coordinates, a radius >= 0" << std::endl; return 2; }
+            withins.push_back(q);
         }
         else if (a == "--clearance") {
             ClearanceSegment cs = {{0.0f, 0.0f, 0.0f, INFINITY, 0.0f, 0.0f, 0.0f, 0.0f}, 0.0f};
@@ -1221,6 +1317,8 @@ int main(int argc, char** argv)
         if (!picks.empty()) { std::cout.flush(); pickPixels(state, obj, picks); }
         if (!pickAlls.empty()) { std::cout.flush(); pickAllPixels(state, obj, pickAlls); }
         if (!nearest.empty()) { std::cout.flush(); nearestPoints(state, obj, nearest); }
+        if (!nearestKs.empty()) { std::cout.flush(); nearestKPoints(state, obj, nearestKs); }
+        if (!withins.empty()) { std::cout.flush(); withinPoints(state, withins); }
         if (!clearances.empty()) { std::cout.flush(); clearanceSegments(state, obj, clearances); }
         if (!overlaps.empty()) { std::cout.flush(); overlapBoxes(state, obj, overlaps); }
         if (!intersects.empty()) { std::cout.flush(); intersectTriangles(state, intersects); }

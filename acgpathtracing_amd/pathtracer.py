@@ -945,6 +945,192 @@ def bakeDistanceField(state, resolution, bounds=None, max_radius=float("inf"), r
     return (dist, got["prim"].reshape(shape)) if return_prims else dist
 
 
+# ------------------------------------------------------------------ the K closest triangles, anything within a radius ----
+def _nearest_k_args(what, k, counts):
+    try:
+        kk = int(k)
+    except (TypeError, ValueError):
+        raise PathTracerError("%s: k is a number 0..%d, got %r" % (what, _native.QUERY_NEAREST_MAX, k))
+    if kk != k or kk < 0 or kk > _native.QUERY_NEAREST_MAX:
+        raise PathTracerError("%s: k must be 0..%d, got %r" % (what, _native.QUERY_NEAREST_MAX, k))
+    if kk == 0 and not counts:
+        raise PathTracerError("%s: k = 0 leaves only the counts to ask for (counts=True)" % what)
+    return kk
+
+
+def _point_records(what, points, max_radius):
+    """(n, 4) float32 {x, y, z, max_radius} from an (n, 3) array and one radius, or the (n, 4) array itself"""
+    p = np.asarray(points)
+    if p.ndim != 2 or p.shape[1] not in (3, 4):
+        raise PathTracerError("%s: expected an (n, 3) or (n, 4) array, got shape %s" % (what, p.shape))
+    if p.dtype.kind not in "fiu":
+        raise PathTracerError("%s: the points must be numbers, got %s" % (what, p.dtype))
+    if p.shape[1] == 4:
+        return np.ascontiguousarray(p, np.float32)
+    try:
+        radius = float(max_radius)
+    except (TypeError, ValueError):
+        raise PathTracerError("%s: the radius is one number, got %r" % (what, max_radius))
+    if not radius >= 0.0:
+        raise PathTracerError("%s: the radius must be non-negative, got %r" % (what, max_radius))
+    q = np.empty((p.shape[0], 4), np.float32)
+    q[:, 0:3] = p
+    q[:, 3] = radius
+    return q
+
+
+def _point_tensor(what, state, points):
+    import torch
+    if points.device.type != "cuda" or points.device.index != state._device:
+        raise PathTracerError("%s: the points are on %s, the context is on cuda:%d" % (what, points.device, state._device))
+    if points.dtype != torch.float32:
+        raise PathTracerError("%s: the points must be float32, got %s" % (what, points.dtype))
+    if points.dim() != 2 or points.shape[1] != 4:
+        raise PathTracerError("%s: expected an (n, 4) tensor {x, y, z, max_radius}, got shape %s" % (what, tuple(points.shape)))
+    if not points.is_contiguous():
+        raise PathTracerError("%s: the points must be contiguous (nothing is copied)" % what)
+    return int(points.shape[0])
+
+
+def queryNearestK(state, points, k=4, max_radius=float("inf"), counts=False):
+    """The k closest triangles of the scene on the GPU to each query point, in order, and how many lie within the radius
+    (include/acgpt.h pt_query_nearest_k).  points: queryNearest's — (n, 3) with max_radius for all, or (n, 4) with a radius per point
+    in the fourth column.  k: 0..8.  counts: also the number of triangles within the radius, not clamped to k; it makes the walk
+    visit everything the ball holds.  k=0, counts=True asks for the counts alone.
+
+    A NumPy array (or anything np.asarray takes) goes to the device and the answer comes back: a dict of (n, k) arrays of
+    queryNearest's fields — distance float32 (-1 past the point's last candidate), prim uint32 (0xFFFFFFFF there), u, v, point
+    (n, k, 3), material uint32 —, plus count (n,) uint32 when asked.  Column j is the point's j-th candidate in ascending (squared
+    distance, prim); column 0 is queryNearest's answer.
+
+    A torch tensor must be (n, 4) float32, contiguous and on the context's device; nothing is copied, its data_ptr() goes straight in,
+    and the answer is torch tensors on that device: views of one (n, k, 8) float32 tensor, prim and material as int32 (-1 past the
+    last candidate), count int32.  torch's current stream is synchronised before the call, and the call returns synchronised."""
+    kk = _nearest_k_args("queryNearestK", k, counts)
+    if _is_tensor(points):
+        import torch
+        L = _native.hip()
+        n = _point_tensor("queryNearestK", state, points)
+        with torch.cuda.device(points.device):
+            out = torch.empty((n, kk, 8), dtype=torch.float32, device=points.device)
+            cnt = torch.empty((n,), dtype=torch.int32, device=points.device) if counts else None
+            torch.cuda.current_stream().synchronize()      # the points' producer and the allocations; the call below returns synchronised
+        _check(state.context, L.pt_query_nearest_k(state.context, points.data_ptr() if n else None, n, kk, out.data_ptr() if n and kk else None,
+                                                   cnt.data_ptr() if n and counts else None), "pt_query_nearest_k")
+        got = {"distance": out[:, :, 0], "prim": out[:, :, 1].view(torch.int32), "u": out[:, :, 2], "v": out[:, :, 3], "point": out[:, :, 4:7],
+               "material": out[:, :, 7].view(torch.int32)}
+        if counts:
+            got["count"] = cnt
+        return got
+    q = _point_records("queryNearestK", points, max_radius)
+    n = q.shape[0]
+    out = np.zeros((n, kk), NEAREST_DTYPE)
+    cnt = np.zeros(n, np.uint32)
+    if n:
+        L = _native.hip()
+        bufs, d_out, d_counts = _device_buffers(state, 1, q.nbytes), None, None
+        try:
+            if kk:
+                bufs += _device_buffers(state, 1, out.nbytes)
+                d_out = bufs[-1]
+            if counts:
+                bufs += _device_buffers(state, 1, cnt.nbytes)
+                d_counts = bufs[-1]
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], q.ctypes.data, q.nbytes), "copy to device")
+            _check(state.context, L.pt_query_nearest_k(state.context, bufs[0], n, kk, d_out, d_counts), "pt_query_nearest_k")
+            if kk:
+                _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, d_out, out.nbytes), "copy to host")
+            if counts:
+                _check(state.context, L.pt_copy_to_host(state.context, cnt.ctypes.data, d_counts, cnt.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    got = {key: np.ascontiguousarray(out[key]) for key in NEAREST_DTYPE.names}
+    if counts:
+        got["count"] = cnt
+    return got
+
+
+def queryWithinAny(state, points, radius=None):
+    """Whether anything of the scene lies within the radius of each point (include/acgpt.h pt_query_within_any): the clearance check
+    of a spherical probe, answered at the first triangle found instead of by a search for the closest.  points: (n, 3) with radius
+    for all — a number >= 0, required —, or (n, 4) with a radius per point in the fourth column (radius stays None).  Returns (n,)
+    bool.  A torch tensor must be (n, 4) float32, contiguous and on the context's device; nothing is copied and the answer is a torch
+    bool tensor on that device."""
+    if _is_tensor(points):
+        import torch
+        L = _native.hip()
+        if radius is not None:
+            raise PathTracerError("queryWithinAny: a tensor carries its radii in the fourth column; radius must stay None")
+        n = _point_tensor("queryWithinAny", state, points)
+        with torch.cuda.device(points.device):
+            hit = torch.empty((n,), dtype=torch.uint8, device=points.device)
+            torch.cuda.current_stream().synchronize()
+        _check(state.context, L.pt_query_within_any(state.context, points.data_ptr() if n else None, n, hit.data_ptr() if n else None), "pt_query_within_any")
+        return hit != 0
+    p = np.asarray(points)
+    if p.ndim == 2 and p.shape[1] == 3 and radius is None:
+        raise PathTracerError("queryWithinAny: (n, 3) points need a radius")
+    if p.ndim == 2 and p.shape[1] == 4 and radius is not None:
+        raise PathTracerError("queryWithinAny: (n, 4) points carry their radii in the fourth column; radius must stay None")
+    q = _point_records("queryWithinAny", p, radius)
+    n = q.shape[0]
+    hit = np.zeros(n, np.uint8)
+    if n:
+        L = _native.hip()
+        bufs = _device_buffers(state, 2, q.nbytes)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], q.ctypes.data, q.nbytes), "copy to device")
+            _check(state.context, L.pt_query_within_any(state.context, bufs[0], n, bufs[1]), "pt_query_within_any")
+            _check(state.context, L.pt_copy_to_host(state.context, hit.ctypes.data, bufs[1], hit.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    return hit != 0
+
+
+def _sphere_contact_args(centres, radius, max_contacts):
+    c = np.asarray(centres)
+    if c.ndim != 2 or c.shape[1] != 3:
+        raise PathTracerError("sphereContacts: expected (n, 3) centres, got shape %s" % (c.shape,))
+    if c.dtype.kind not in "fiu":
+        raise PathTracerError("sphereContacts: the centres must be numbers, got %s" % c.dtype)
+    r = np.asarray(radius)
+    if r.dtype.kind not in "fiu" or r.shape not in ((), (c.shape[0],)):
+        raise PathTracerError("sphereContacts: radius is one number or one per ball, got %r" % (radius,))
+    r = np.broadcast_to(r.astype(np.float32), (c.shape[0],))
+    if not (np.isfinite(r).all() and (r >= 0).all()):
+        raise PathTracerError("sphereContacts: every radius must be finite and non-negative")
+    try:
+        k = int(max_contacts)
+    except (TypeError, ValueError):
+        raise PathTracerError("sphereContacts: max_contacts is a number 1..%d, got %r" % (_native.QUERY_NEAREST_MAX, max_contacts))
+    if k != max_contacts or k < 1 or k > _native.QUERY_NEAREST_MAX:
+        raise PathTracerError("sphereContacts: max_contacts must be 1..%d, got %r" % (_native.QUERY_NEAREST_MAX, max_contacts))
+    q = np.empty((c.shape[0], 4), np.float32)
+    q[:, 0:3] = c
+    q[:, 3] = r
+    return q, k
+
+
+def sphereContacts(state, centres, radius, max_contacts=8):
+    """The contact manifold of balls against the scene: every triangle within radius of a centre is a contact, the closest
+    max_contacts (1..8) of them are listed (queryNearestK with counts).  centres: (n, 3); radius: one number or (n,).  Returns a dict
+    of arrays, one row per ball and one column per contact, closest first: point (n, k, 3) float32 the point on the mesh, normal
+    (n, k, 3) the unit direction from it to the centre (zero where the centre lies on the triangle, and past the last contact),
+    penetration (n, k) float32 = radius - distance (>= 0 at a contact up to the rounding of the difference; NaN past the last
+    contact), prim and material (n, k) uint32 (0xFFFFFFFF past the last contact), count (n,) uint32 the number of triangles within
+    the radius: count > max_contacts flags a truncated manifold.  Triangles in one plane give one contact each: merge them by
+    normal if the solver wants one contact per wall."""
+    q, k = _sphere_contact_args(centres, radius, max_contacts)
+    got = queryNearestK(state, q, k=k, counts=True)
+    found = got["prim"] != 0xFFFFFFFF
+    dist = got["distance"]
+    away = q[:, None, 0:3] - got["point"]
+    with np.errstate(all="ignore"):
+        normal = np.where((found & (dist > 0))[..., None], away / dist[..., None], np.float32(0.0)).astype(np.float32)
+    penetration = np.where(found, q[:, None, 3] - dist, np.float32(np.nan)).astype(np.float32)
+    return {"point": got["point"], "normal": normal, "penetration": penetration, "prim": got["prim"], "material": got["material"], "count": got["count"]}
+
+
 # ------------------------------------------------------------------ segment to mesh ----
 SEGMENT_HIT_DTYPE = np.dtype([("distance", np.float32), ("prim", np.uint32), ("s", np.float32), ("feature", np.float32), ("point", np.float32, 3), ("material", np.uint32)])      # pt_segment_hit
 assert SEGMENT_HIT_DTYPE.itemsize == 32

@@ -696,6 +696,45 @@ int pt_query_sweep_any(pt_ctx* ctx, const float* sweeps, size_t n, uint8_t* bloc
 typedef struct { float distance; uint32_t prim; float s, feature; float cx, cy, cz; uint32_t material; } pt_segment_hit;   /* 32 bytes */
 int pt_query_segments(pt_ctx* ctx, const float* segments, size_t n, pt_segment_hit* out);
 
+/* ---- the K closest triangles of a point, and "is anything within r" (opt-in; nothing above changes) ------------------------------
+ * pt_query_nearest answers with one triangle.  A ball resting in a corner touches three walls and needs all three contacts; a point
+ * whose closest feature is an edge or a vertex ties between two to six triangles, of which pt_query_nearest names the lowest index
+ * only — and the triangles at the winning feature are what a pseudonormal sign, a contact manifold or a blend over the nearest
+ * surfaces needs.  pt_query_nearest_k lists the first max_k candidates in order and counts them all (the sphere form of
+ * pt_query_overlap's count); pt_query_within_any answers the clearance check "is anything within r of this point" with one byte,
+ * leaving at the first candidate instead of searching for the closest.  pt_query_nearest's memory and call rules: DEVICE arrays,
+ * points and out 16-byte aligned, counts 4-byte, hit any alignment; the call enqueues on the context's stream and returns
+ * synchronised, acts on rank 0 of a pt_create_multi context, never writes the accumulation buffer, the frame buffer or pt_stats,
+ * walks the node array the scene holds (pt_bvh_info.device_bytes does not change, with pt_query_nearest's one exception) and uses no
+ * atomics: two calls give the same bits.
+ *
+ *   points    pt_query_nearest's: n records of 4 floats {x, y, z, max_radius}
+ *   d2        pt_query_nearest's, word for word: the closest_on_triangle statement above in plain fp32, one IEEE division per
+ *             triangle, no fused multiply-add
+ *   candidate pt_query_nearest's: a triangle with d2 <= max_radius * max_radius, the product taken in fp32 (+inf squared is +inf); a
+ *             NaN d2 is no candidate.  Each triangle is a candidate at most once.
+ *   a miss before any traversal: pt_query_nearest's — a non-finite coordinate, a NaN or negative max_radius, a scene without triangles
+ *   out       null with max_k == 0, or n * max_k records (1 <= max_k <= PT_QUERY_NEAREST_MAX), point-major: record j of point i is
+ *             out[i * max_k + j], its j-th candidate in ascending (d2, prim): d2 compared as floats, equal d2 to the lower triangle
+ *             index.  Each is pt_query_nearest's full 32-byte record (distance = sqrtf(d2), prim, the weights, the point c, the
+ *             material), computed once from the kept triangle by the same statement; the slots past the point's last candidate hold
+ *             the miss record.  Record 0 equals pt_query_nearest's on the same point, bit for bit.
+ *   counts    null, or n words: the number of candidates of point i, not clamped to max_k.  0 for a miss before any traversal.
+ *             max_radius = +inf with counts is legal: it counts every triangle whose d2 is not a NaN, and walks the whole tree.
+ *   the walk  with counts nothing can be pruned at a candidate: the walk is cut at max_radius only and costs what the ball holds.
+ *             Without counts it is also cut at the d2 of entry max_k - 1 once that entry is filled (widened as pt_query_nearest's
+ *             cut is, and closed, so that a triangle that ties with the last kept entry and has a lower index is still reached).
+ *             The records are the same either way.
+ *   hit       (pt_query_within_any) one byte per point: 1 iff counts[i] would be non-zero, else 0.  The point's walk ends at its
+ *             first candidate.
+ * n == 0 is a no-op success.  Refused, with the context left usable, in pt_query_nearest's order with pt_query_multi's additions: a
+ * null context, max_k > PT_QUERY_NEAREST_MAX, out null with max_k != 0 or the reverse, out and counts both null, a null points (or
+ * hit) pointer with n > 0, n > 0x7FFFFFFF, a misaligned points, out or counts pointer, an output that overlaps the points or the
+ * other output, a context without a scene.                                                                                           */
+#define PT_QUERY_NEAREST_MAX 8
+int pt_query_nearest_k(pt_ctx* ctx, const float* points, size_t n, uint32_t max_k, pt_nearest* out, uint32_t* counts);
+int pt_query_within_any(pt_ctx* ctx, const float* points, size_t n, uint8_t* hit);
+
 /* ---- ambient occlusion traced on the device (opt-in; nothing above changes) -----------------------------------------------------
  * The share of the hemisphere over a surface point that is open within `radius`: K rays per point, generated, traced with
  * pt_query_any's walk and counted inside one kernel, so no ray reaches memory.  pt_ao_points takes the points from a device array

@@ -157,6 +157,10 @@ int pt_debug_triangles_visits(pt_ctx* ctx, const float* tris, size_t n, uint32_t
  * second box bound (the three axes perpendicular to the segment), which changes the counts and never the records; anything else is
  * refused.  tools/segments_timing.py. */
 int pt_debug_segments_visits(pt_ctx* ctx, const float* segments, size_t n, pt_segment_hit* out, uint32_t* visits, uint32_t flags);
+/* pt_query_nearest_k (hit null: same records, same counts, same refusals) or pt_query_within_any (hit given; max_k must be 0 and
+ * out and counts null) from kernel instantiations that also count: visits[2 i] = inner nodes point i visited, visits[2 i + 1] =
+ * triangles it tested.  visits: DEVICE, 8-byte aligned, 2 n words, never null.  tools/nearest_k_timing.py. */
+int pt_debug_nearest_k_visits(pt_ctx* ctx, const float* points, size_t n, uint32_t max_k, pt_nearest* out, uint32_t* counts, uint8_t* hit, uint32_t* visits);
 /* Sorted (morton, triangle) pairs of the last build, HOST outputs of n_tris. */
 int pt_read_morton(pt_ctx* ctx, uint32_t* codes_sorted, uint32_t* prims_sorted);
 /* What the scene's tree is made of, as the device holds it right now (tests/tree_ref.py validates it node by node).  Not part of the
