@@ -158,6 +158,7 @@ PT_API int pt_device_count(pt_ctx* c) { return !c ? 0 : (c->multi ? (int)c->mult
 static void free_scene(pt_ctx* c)
 {
     ptd::free_lbvh(c->bvh);
+    ptd::free_winding(c->winding);
     c->d_mats.release(); c->d_alpha.release(); c->d_lights.release(); c->d_tri_bsdf.release(); c->d_idx.release();
     c->n_mats = 0; c->n_lights = 0; c->light_area = 0.0f;
     c->scene_kept = false; c->kept_n_verts = 0;
@@ -186,6 +187,7 @@ static void destroy_one(pt_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     ptd::free_lbvh(c->bvh);
+    ptd::free_winding(c->winding);
     ptd::env_free(c->env);
     if (c->small_stream) (void)hipStreamSynchronize(c->small_stream);
     const hipEvent_t ev0 = c->ev0, ev1 = c->ev1, small_fork = c->small_fork, small_join = c->small_join;
@@ -427,6 +429,17 @@ PT_API int pt_get_bvh_info(pt_ctx* c, pt_bvh_info* out)
     return 0;
 }
 
+// plain reads of the context: nothing is built or released
+PT_API int pt_get_winding_info(pt_ctx* c, pt_winding_info* out)
+{
+    if (!c || !out) return fail(c, "pt_get_winding_info: null argument");
+    memset(out, 0, sizeof(*out));
+    out->built = c->winding.built ? 1u : 0u;
+    out->n_nodes = c->winding.n_nodes;
+    out->bytes = (uint64_t)ptd::winding_bytes(c->winding);
+    return 0;
+}
+
 // ---- in-place vertex updates (pt_update_vertices; kernels in refit.hip) -----------------------------------------------------------
 // the scene's index buffer on the device, for pt_update_vertices and pt_temporal_blend_motion: uploaded on the first call of either,
 // counted in device_bytes from then on, freed with the scene
@@ -476,6 +489,7 @@ static int update_one(pt_ctx* c, const float* verts_xyzw, size_t n_verts, int mo
     std::string err;
     if (c->build_area < 0.0 && !ptd::refit_tree_area(c->bvh, c->stream, c->build_area, err)) return fail(c, "pt_update_vertices: " + err);
     double area = 1.0;
+    ptd::free_winding(c->winding);      // the records are about to change: back on pt_query_winding's next call
     if (!ptd::refit_lbvh(c->bvh, verts_xyzw, n_verts, c->d_idx.p, c->stream, area, err)) return fail(c, "pt_update_vertices: " + err);
     const float ratio = c->build_area > 0.0 ? (float)(area / c->build_area) : 1.0f;
     if (mode == PT_UPDATE_AUTO && ratio > PT_UPDATE_AUTO_AREA_RATIO) {

@@ -3,8 +3,8 @@
 // closest-point query pt_query_nearest, the box-overlap queries pt_query_overlap, pt_query_overlap_any and the swept-sphere casts
 // pt_query_sweep, pt_query_sweep_any, the triangle-against-mesh queries pt_query_triangles, pt_query_triangles_any, the
 // segment-to-mesh distance query pt_query_segments and the K-closest and within-radius queries pt_query_nearest_k,
-// pt_query_within_any (each with its counting twin of include/acgpt_test.h).
-// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip and segment.hip.  The context and what the units share: context.h.
+// pt_query_within_any and the generalised winding number pt_query_winding (each with its counting twin of include/acgpt_test.h).
+// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip, segment.hip and winding.hip.  The context and what the units share: context.h.
 #include <cmath>
 
 #include "../../include/acgpt_test.h"
@@ -198,6 +198,53 @@ PT_API int pt_debug_nearest_k_visits(pt_ctx* c, const float* points, size_t n, u
     if (int rc = nearest_k_prepare(c, "pt_debug_nearest_k_visits", points, n, hit == nullptr, max_k, out, counts, hit, visits, true, &fmt)) return rc < 0 ? 0 : rc;
     CK(c, ptd::launch_nearest_k_visits(fmt, device_scene(c), c->stack_entries, ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)points,
                                        (uint32_t)n, max_k, (float4*)out, counts, hit, (uint2*)visits, hit ? 1u : 0u, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- generalised winding numbers ---------------------------------------------------------------------------------------------------
+static_assert(sizeof(pt_winding_info) == 16, "pt_winding_info: a change of this layout bumps pt_abi_version");
+
+// every refusal of pt_query_winding and its twin before any device work, in pt_query_nearest's order with a bad beta after n == 0 and
+// the overlaps last; then the moments, built on the first call after the scene or its vertices changed.  Returns 0 to go on, 1
+// refused or failed, -1 nothing to do.
+static int winding_prepare(pt_ctx* c, const char* fn, const float* points, size_t n, float beta, const void* out, const void* visits, bool with_visits)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (n == 0) return -1;
+    if (!(beta >= 1.0f)) return fail(c, f + "beta must be at least 1 (+inf: the exact sum)");
+    if (!points || !out || (with_visits && !visits)) return fail(c, f + "null argument");
+    if (n > 0x7FFFFFFFull) return fail(c, f + "too many points (2^31 - 1 per call)");
+    if (((uintptr_t)points & 15u) || ((uintptr_t)out & 3u) || ((uintptr_t)visits & 7u))
+        return fail(c, f + "the points must be 16-byte aligned, the output 4-byte aligned");
+    if (spans_overlap(points, n * 16u, out, n * 4u)) return fail(c, f + "the output overlaps the points");
+    if (with_visits && (spans_overlap(points, n * 16u, visits, n * 8u) || spans_overlap(out, n * 4u, visits, n * 8u)))
+        return fail(c, f + "the visit counts overlap another array");
+    int fmt = 0;
+    if (int rc = query_node_format(c, f, &fmt)) return rc;
+    if (c->bvh.n_tris != 0u && !c->winding.built) {
+        Range range("acgpt: winding moments");
+        std::string err;
+        if (!ptd::build_winding(c->bvh, c->stream, c->winding, err)) return fail(c, f + err);
+    }
+    return 0;
+}
+
+PT_API int pt_query_winding(pt_ctx* c, const float* points, size_t n, float beta, float* out)
+{
+    if (int rc = winding_prepare(c, "pt_query_winding", points, n, beta, out, nullptr, false)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_winding");
+    CK(c, ptd::launch_query_winding(c->winding, c->bvh.tris, c->bvh.n_tris, c->stack_entries, beta * beta, (const float4*)points, (uint32_t)n, out, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_debug_winding_visits(pt_ctx* c, const float* points, size_t n, float beta, float* out, uint32_t* visits)
+{
+    if (int rc = winding_prepare(c, "pt_debug_winding_visits", points, n, beta, out, visits, true)) return rc < 0 ? 0 : rc;
+    CK(c, ptd::launch_winding_visits(c->winding, c->bvh.tris, c->bvh.n_tris, c->stack_entries, beta * beta, (const float4*)points, (uint32_t)n, out,
+                                     (uint2*)visits, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

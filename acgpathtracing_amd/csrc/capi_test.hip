@@ -296,6 +296,20 @@ PT_API int pt_debug_read_tree(pt_ctx* c, int what, void* out, size_t capacity_by
     return 0;
 }
 
+// pt_query_winding's moments as the device holds them (tests/winding_ref.py): a device-to-host copy only, nothing is built or released.
+PT_API int pt_debug_read_winding(pt_ctx* c, void* out, size_t capacity_bytes)
+{
+    if (!c) return fail(nullptr, "pt_debug_read_winding: null context");
+    if (!out) return fail(c, "pt_debug_read_winding: null argument");
+    if (!c->winding.built) return fail(c, "pt_debug_read_winding: the moments are not built (pt_query_winding builds them)");
+    const size_t bytes = (size_t)c->winding.n_nodes * sizeof(ptd::WindMoment);
+    if (capacity_bytes < bytes) return fail(c, "pt_debug_read_winding: capacity " + std::to_string(capacity_bytes) + " bytes, the moments take " + std::to_string(bytes));
+    CK(c, hipSetDevice(c->device));
+    CK(c, hipStreamSynchronize(c->stream));
+    CK(c, hipMemcpy(out, c->winding.moments, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // What the last build recorded about itself (tests/build_ref.py holds it to the references): plain reads of the context, no device call.
 PT_API int pt_debug_build_stats(pt_ctx* c, pt_build_stats* out)
 {

@@ -22,6 +22,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "lbvh_build.h"
 #include "render_megakernel.h"
 #include "render_small.h"
+#include "winding.h"
 
 #define PT_API extern "C" __attribute__((visibility("default")))
 
@@ -118,6 +119,8 @@ struct pt_ctx {
     std::vector<uint32_t> kept_idx, kept_mat_ids;
     std::vector<pt_material> kept_mats;
     DevBuf<uint32_t> d_idx;
+    ptd::WindingTree winding;                 // pt_query_winding's far-field moments: built on its first call per scene or vertex update, kept across
+                                              // material edits, freed with the scene (capi.hip free_scene, update_one); not counted in device_bytes
     double build_area = -1.0;                 // inner-node area sum over the root's at the last build (refit_tree_area; < 0: not taken yet)
     pt_stats stats;
     uint64_t scene_serial = 0;

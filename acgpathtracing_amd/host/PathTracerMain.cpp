@@ -18,7 +18,7 @@
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
 //              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k] ...] [--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k] ...]
 //              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...] [--clearance x0,y0,z0,x1,y1,z1[,radius] ...]
-//              [--nearest-k x,y,z,k[,radius] ...] [--within x,y,z,radius ...]
+//              [--nearest-k x,y,z,k[,radius] ...] [--within x,y,z,radius ...] [--winding x,y,z[,beta] ...]
 //              [--ao K[,radius[,bias]] --ao-out file.pfm [--ao-frames n]]
 // --ao K[,radius[,bias]] with --ao-out: once the scene is set and before the first frame, the ambient occlusion of the view
 // (pt_render_features + pt_ao_image): K rays per pixel (1..256) and call over --ao-frames calls (default 1; call j has seed j and
@@ -48,6 +48,11 @@
 // --within x,y,z,radius (repeatable): whether anything of the scene lies within the radius of the point, all in one call of
 // pt_query_within_any, one JSON line each: {"within": [x, y, z], "radius": r, "hit": true or false}.  The same refusals.  The frames
 // are the same with or without either.
+// --winding x,y,z[,beta] (repeatable): once the scene is set and before the first frame, the generalised winding number of the mesh at
+// the point (pt_query_winding, one call per point; beta >= 1, default PT_WINDING_BETA_DEFAULT, inf for the exact sum), one JSON line
+// each: {"winding": [x, y, z], "beta": b, "w": .., "inside": true or false} (inside: w > 0.5; an infinite beta is printed as the
+// string "inf").  A coordinate that is not finite or a beta below 1 or no number is refused with exit status 2.  The frames are the
+// same with or without it.
 // --overlap cx,cy,cz,hx,hy,hz[,k] (repeatable): once the scene is set and before the first frame, the triangles that overlap the
 // axis-aligned box of centre (cx, cy, cz) and half extent (hx, hy, hz), by pt_query_overlap in one call per k, one JSON line each:
 // {"overlap": [cx, cy, cz, hx, hy, hz], "count": <triangles that overlap the box>, "triangles": [<the k lowest indices among them,
@@ -972,6 +977,30 @@ static void withinPoints(PathTracerState& state, const std::vector<float4>& poin
     fflush(stdout);
 }
 
+// --winding: one call of pt_query_winding per point (each has its own beta, in .w); one JSON line per point
+static void windingPoints(PathTracerState& state, const std::vector<float4>& points)
+{
+    void* d_point = nullptr; void* d_w = nullptr;
+    std::string err;
+    std::vector<float> w(points.size(), 0.0f);
+    if (pt_device_malloc(state.context, &d_point, 16) != 0 || pt_device_malloc(state.context, &d_w, 4) != 0) err = pt_last_error(state.context);
+    for (size_t i = 0; i < points.size() && err.empty(); i++)
+        if (pt_copy_to_device(state.context, d_point, &points[i], 16) != 0 ||
+            pt_query_winding(state.context, (const float*)d_point, 1, points[i].w, (float*)d_w) != 0 ||
+            pt_copy_to_host(state.context, &w[i], d_w, 4) != 0)
+            err = pt_last_error(state.context);
+    if (d_point) pt_device_free(state.context, d_point);
+    if (d_w) pt_device_free(state.context, d_w);
+    if (!err.empty()) throw Exception("winding: " + err);
+    for (size_t i = 0; i < points.size(); i++) {
+        char beta[32];
+        if (std::isinf(points[i].w)) snprintf(beta, sizeof(beta), "\"inf\""); else snprintf(beta, sizeof(beta), "%.9g", points[i].w);
+        printf("{\"winding\": [%.9g, %.9g, %.9g], \"beta\": %s, \"w\": %.9g, \"inside\": %s}\n", points[i].x, points[i].y, points[i].z, beta, w[i],
+               w[i] > 0.5f ? "true" : "false");
+    }
+    fflush(stdout);
+}
+
 // --ao: the default sample pattern (pathtracer.aoSamples restated: the same double operations, the same fp32 pull-in)
 static std::vector<float> aoSamples(int K)
 {
@@ -1037,6 +1066,7 @@ int main(int argc, char** argv)
     std::vector<float4> nearest;
     std::vector<NearestKPoint> nearestKs;
     std::vector<float4> withins;
+    std::vector<float4> windings;
     std::vector<ClearanceSegment> clearances;
     std::vector<OverlapBox> overlaps;
     std::vector<IntersectTri> intersects;
@@ -1155,6 +1185,12 @@ int main(int argc, char** argv)
             const int got = sscanf(next(), "%f,%f,%f,%f", &q.x, &q.y, &q.z, &q.w);
             if (got < 4 || !std::isfinite(q.x) || !std::isfinite(q.y) || !std::isfinite(q.z) || !(q.w >= 0.0f)) { std::cerr << "--within x,y,z,radius: finite coordinates, a radius >= 0" << std::endl; return 2; }
             withins.push_back(q);
+        }
+        else if (a == "--winding") {
+            float4 q = make_float4(0.0f, 0.0f, 0.0f, PT_WINDING_BETA_DEFAULT);
+            const int got = sscanf(next(), "%f,%f,%f,%f", &q.x, &q.y, &q.z, &q.w);
+            if (got < 3 || !std::isfinite(q.x) || !std::isfinite(q.y) || !std::isfinite(q.z) || !(q.w >= 1.0f)) { std::cerr << "--winding x,y,z[,beta]: finite coordinates, a beta >= 1 (inf: the exact sum)" << std::endl; return 2; }
+            windings.push_back(q);
         }
         else if (a == "--clearance") {
             ClearanceSegment cs = {{0.0f, 0.0f, 0.0f, INFINITY, 0.0f, 0.0f, 0.0f, 0.0f}, 0.0f};
@@ -1319,6 +1355,7 @@ int main(int argc, char** argv)
         if (!nearest.empty()) { std::cout.flush(); nearestPoints(state, obj, nearest); }
         if (!nearestKs.empty()) { std::cout.flush(); nearestKPoints(state, obj, nearestKs); }
         if (!withins.empty()) { std::cout.flush(); withinPoints(state, withins); }
+        if (!windings.empty()) { std::cout.flush(); windingPoints(state, windings); }
         if (!clearances.empty()) { std::cout.flush(); clearanceSegments(state, obj, clearances); }
         if (!overlaps.empty()) { std::cout.flush(); overlapBoxes(state, obj, overlaps); }
         if (!intersects.empty()) { std::cout.flush(); intersectTriangles(state, intersects); }

@@ -821,7 +821,7 @@ def _inside_rays(what, points, directions):
     return rays.reshape(n * m, 8), n, m
 
 
-def pointsInside(state, points, directions=None, return_counts=False):
+def pointsInside(state, points, directions=None, return_counts=False, method="parity", beta=_native.WINDING_BETA_DEFAULT, threshold=0.5):
     """Which of the points lie inside the scene's surface, by the parity of crossings (queryRaysMulti, counts alone): one ray per point
     and direction with tmin 0 and tmax +inf, a point is inside by one ray if the ray crosses an odd number of triangles, and inside if
     most of its rays say so.  directions: an odd number of them, (m, 3); by default three generic ones, INSIDE_DIRECTIONS.  Returns a
@@ -829,7 +829,26 @@ def pointsInside(state, points, directions=None, return_counts=False):
 
     The answer means something only where the mesh is closed: a ray that leaves through a hole counts one crossing too few.  The Cornell
     box's shell is open to the front.  The counts are not watertight either (include/acgpt.h): a ray through a shared edge or vertex
-    may miscount, which is what the vote over several generic directions is for."""
+    may miscount, which is what the vote over several generic directions is for.
+
+    method="winding" asks the generalised winding number instead (queryWinding with beta): inside where w > threshold.  It stays
+    usable on a mesh with holes, where a hole of solid angle omega lowers the inside value by omega / 4 pi; directions is not used,
+    and return_counts returns the winding numbers, float32 (n,), in place of the counts."""
+    if method == "winding":
+        p = np.asarray(points)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise PathTracerError("pointsInside: expected (n, 3) points, got shape %s" % (p.shape,))
+        try:
+            thr = float(threshold)
+        except (TypeError, ValueError):
+            raise PathTracerError("pointsInside: threshold is one number, got %r" % (threshold,))
+        if thr != thr:
+            raise PathTracerError("pointsInside: threshold is a NaN")
+        w = queryWinding(state, p, beta)
+        inside = w > np.float32(thr)
+        return (inside, w) if return_counts else inside
+    if method != "parity":
+        raise PathTracerError("pointsInside: method is \"parity\" or \"winding\", got %r" % (method,))
     rays, n, m = _inside_rays("pointsInside", points, directions)
     cnt = queryRaysMulti(state, rays, max_hits=0, counts=True)["count"].reshape(n, m)
     inside = 2 * ((cnt & 1) != 0).sum(axis=1) > m
@@ -926,7 +945,10 @@ def bakeDistanceField(state, resolution, bounds=None, max_radius=float("inf"), r
     scene box if not given.  The points go to the device x fastest, so the 64 queries of a wave are neighbours.  return_prims: also the
     closest triangle's index per cell, uint32 [nz, ny, nx] (0xFFFFFFFF where nothing is found).  The distance is unsigned unless
     signed=True, which negates it at the cells that pointsInside calls inside (its default directions; closed meshes only), and leaves
-    the -1 of a cell that found nothing as it is."""
+    the -1 of a cell that found nothing as it is.  signed="winding" takes the sign from the generalised winding number instead
+    (pointsInside(method="winding"), its default beta and threshold), which holds on meshes with holes."""
+    if signed not in (False, True, "winding"):
+        raise PathTracerError("bakeDistanceField: signed is False, True or \"winding\", got %r" % (signed,))
     if bounds is None:
         info = getBvhInfo(state)
         lo, hi = [float(x) for x in info.scene_lo], [float(x) for x in info.scene_hi]
@@ -940,9 +962,69 @@ def bakeDistanceField(state, resolution, bounds=None, max_radius=float("inf"), r
     shape = tuple(int(r) for r in resolution)
     dist = got["distance"].reshape(shape)
     if signed:
-        inside = pointsInside(state, pts).reshape(shape) & (dist >= 0.0)
+        inside = (pointsInside(state, pts, method="winding") if signed == "winding" else pointsInside(state, pts)).reshape(shape) & (dist >= 0.0)
         dist = np.where(inside, -dist, dist)
     return (dist, got["prim"].reshape(shape)) if return_prims else dist
+
+
+# ------------------------------------------------------------------ generalised winding numbers ----
+def _winding_beta(beta):
+    try:
+        b = float(beta)
+    except (TypeError, ValueError):
+        raise PathTracerError("queryWinding: beta is one number, got %r" % (beta,))
+    if not b >= 1.0:
+        raise PathTracerError("queryWinding: beta must be at least 1 (inf: the exact sum), got %r" % (beta,))
+    return b
+
+
+def queryWinding(state, points, beta=_native.WINDING_BETA_DEFAULT):
+    """The generalised winding number of the scene's mesh at each point (include/acgpt.h pt_query_winding): 1 inside and 0 outside a
+    closed, outward-wound mesh, degrading smoothly where the mesh has holes, so that w > 0.5 stays an inside test.  beta >= 1 is the
+    accuracy knob: a subtree further away than beta times its radius is taken as one dipole; inf is the exact sum over every
+    triangle.
+
+    A NumPy array (or anything np.asarray takes) of shape (n, 3), or (n, 4) whose fourth column is ignored (queryNearest's points
+    serve both), goes to the device and float32 (n,) comes back; a point with a non-finite coordinate gets a NaN.  A torch tensor
+    must be (n, 4) float32, contiguous and on the context's device; nothing is copied, its data_ptr() goes straight in, and the answer
+    is a float32 tensor on that device.  torch's current stream is synchronised before the call, and the call returns synchronised."""
+    b = _winding_beta(beta)
+    if _is_tensor(points):
+        import torch
+        n = _point_tensor("queryWinding", state, points)
+        with torch.cuda.device(points.device):
+            out = torch.empty((n,), dtype=torch.float32, device=points.device)
+            torch.cuda.current_stream().synchronize()      # the points' producer and the allocation; the call below returns synchronised
+        _check(state.context, _native.hip().pt_query_winding(state.context, points.data_ptr() if n else None, n, b, out.data_ptr() if n else None),
+               "pt_query_winding")
+        return out
+    p = np.asarray(points)
+    if p.ndim != 2 or p.shape[1] not in (3, 4):
+        raise PathTracerError("queryWinding: expected an (n, 3) or (n, 4) array, got shape %s" % (p.shape,))
+    if p.dtype.kind not in "fiu":
+        raise PathTracerError("queryWinding: the points must be numbers, got %s" % p.dtype)
+    n = p.shape[0]
+    q = np.zeros((n, 4), np.float32)
+    q[:, 0:3] = p[:, 0:3]
+    out = np.zeros(n, np.float32)
+    if n:
+        L = _native.hip()
+        bufs = _device_buffers(state, 2, q.nbytes)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], q.ctypes.data, q.nbytes), "copy to device")
+            _check(state.context, L.pt_query_winding(state.context, bufs[0], n, b, bufs[1]), "pt_query_winding")
+            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    return out
+
+
+def getWindingInfo(state):
+    """What pt_query_winding holds on the device for the scene: {"built": bool, "bytes": int, "n_nodes": int}.  The moments are built on
+    the first queryWinding after the scene or its vertices changed and are not part of getBvhInfo().device_bytes."""
+    w = _native.WindingInfo()
+    _check(state.context, _native.hip().pt_get_winding_info(state.context, C.byref(w)), "pt_get_winding_info")
+    return {"built": bool(w.built), "bytes": int(w.bytes), "n_nodes": int(w.n_nodes)}
 
 
 # ------------------------------------------------------------------ the K closest triangles, anything within a radius ----

@@ -735,6 +735,51 @@ int pt_query_segments(pt_ctx* ctx, const float* segments, size_t n, pt_segment_h
 int pt_query_nearest_k(pt_ctx* ctx, const float* points, size_t n, uint32_t max_k, pt_nearest* out, uint32_t* counts);
 int pt_query_within_any(pt_ctx* ctx, const float* points, size_t n, uint8_t* hit);
 
+/* ---- generalised winding numbers (opt-in; nothing above changes) -------------------------------------------------------------------
+ * Whether a point is inside the mesh, for meshes that are not watertight: w(q) = (1 / 4 pi) sum_t Omega_t(q), the signed solid angle
+ * the mesh subtends at q (Jacobson et al. 2013; Barill et al. 2018).  A closed, outward-wound mesh gives 1 inside and 0 outside; a
+ * hole of solid angle omega lowers the inside value by omega / 4 pi, so w > 0.5 stays a usable inside test where crossing parity
+ * (pt_query_multi's counts) is wrong for every ray that leaves through the hole.  pt_query_nearest's memory and call rules: DEVICE
+ * arrays, points 16-byte aligned, out 4-byte aligned; the call enqueues on the context's stream and returns synchronised, acts on
+ * rank 0 of a pt_create_multi context, never writes the accumulation buffer, the frame buffer or pt_stats and uses no atomics in the
+ * walk: two calls give the same bits.
+ *
+ *   points    pt_query_nearest's layout: n records of 4 floats {x, y, z, unused}; the fourth float is ignored
+ *   out       n floats: out[i] = w(q_i).  A triangle is what the scene's record holds, as for pt_query_nearest: v0, e1 = v1 - v0 and
+ *             e2 = v2 - v0 in fp32, its vertices v0, v0 + e1, v0 + e2.  With a, b, c the triangle's vertices minus q,
+ *               Omega_t = 2 atan2(a . (b x c), |a||b||c| + (a . b)|c| + (b . c)|a| + (c . a)|b|).
+ *             A point with a non-finite coordinate gets a NaN without traversal; a scene without triangles answers 0; on the surface
+ *             itself the value is unspecified but finite.
+ *   beta      the accuracy knob.  Every inner node carries the first-order moments of its subtree: p, the area-weighted centroid
+ *             of its triangles; r2, the squared distance from p to the farthest corner of the exact box of its vertices; N, the sum
+ *             of the triangles' area-weighted normals.  A node's whole subtree is replaced by its dipole iff d2 > beta2 * r2, evaluated
+ *             in fp32 exactly as written: beta2 = beta * beta computed in float on the host, dx = px - qx (likewise y, z),
+ *             d2 = (dx * dx + dy * dy) + dz * dz, no contraction.  The dipole contributes N . (p - q) / (d2 * sqrt(d2)) in units of
+ *             Omega.  The test is made for the root first, then for every inner child before it is entered; leaves are always exact
+ *             solid angles.  beta = +inf is legal and is the exact sum over every triangle (inf * 0 is a NaN and the comparison is
+ *             false).  PT_WINDING_BETA_DEFAULT is the paper's value: on an icosphere of 320 triangles, first order at beta = 2 is off
+ *             by at most 0.024.
+ *   moments   fp32, per triangle from its record {v0, e1, e2}: n2 = e1 x e2, N_t = 0.5 n2, A_t = 0.5 sqrt(n2 . n2), centroid
+ *             c_t = v0 + (e1 + e2) / 3, S_t = A_t c_t.  Per node, child 0 then child 1: N = N0 + N1, A = A0 + A1, S = S0 + S1; lo and
+ *             hi the exact min and max of the vertices below it (v0, v0 + e1, v0 + e2, without the builder's pad).  p = S / A (IEEE
+ *             division; the box centre 0.5 (lo + hi) where A is 0), r2 = sum over the axes of max(p - lo, hi - p)^2.  The two-child
+ *             order makes every sum deterministic whatever the schedule.  csrc/winding.h; tests/winding_ref.py restates it.
+ *   lifetime  the moments (96 bytes per node: the 32-byte records and the 64-byte records the walk reads) are built on the first
+ *             pt_query_winding after pt_set_scene or pt_update_vertices, kept across calls and across pt_update_materials and freed
+ *             with the scene.  They do NOT count in pt_bvh_info.device_bytes; pt_get_winding_info reports them.  A failed build
+ *             leaves the context usable and nothing half-built.
+ * n == 0 is a no-op success.  Refused, with the context left usable, in pt_query_nearest's order: a null context, beta < 1 or NaN, a
+ * null points or out pointer with n > 0, n > 0x7FFFFFFF, a misaligned pointer, an out that overlaps the points, a context without a
+ * scene.                                                                                                                            */
+#define PT_WINDING_BETA_DEFAULT 2.0f
+typedef struct pt_winding_info {
+    uint32_t built;      /* 1 while the moments are on the device */
+    uint32_t n_nodes;    /* nodes they cover (0 while not built) */
+    uint64_t bytes;      /* device memory they hold (0 while not built) */
+} pt_winding_info;
+int pt_query_winding(pt_ctx* ctx, const float* points, size_t n, float beta, float* out);
+int pt_get_winding_info(pt_ctx* ctx, pt_winding_info* out);
+
 /* ---- ambient occlusion traced on the device (opt-in; nothing above changes) -----------------------------------------------------
  * The share of the hemisphere over a surface point that is open within `radius`: K rays per point, generated, traced with
  * pt_query_any's walk and counted inside one kernel, so no ray reaches memory.  pt_ao_points takes the points from a device array

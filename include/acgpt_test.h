@@ -161,6 +161,13 @@ int pt_debug_segments_visits(pt_ctx* ctx, const float* segments, size_t n, pt_se
  * out and counts null) from kernel instantiations that also count: visits[2 i] = inner nodes point i visited, visits[2 i + 1] =
  * triangles it tested.  visits: DEVICE, 8-byte aligned, 2 n words, never null.  tools/nearest_k_timing.py. */
 int pt_debug_nearest_k_visits(pt_ctx* ctx, const float* points, size_t n, uint32_t max_k, pt_nearest* out, uint32_t* counts, uint8_t* hit, uint32_t* visits);
+/* pt_query_winding (same bits, same refusals) from a kernel instantiation that also counts: visits[2 i] = dipoles point i took,
+ * visits[2 i + 1] = triangles it evaluated.  visits: DEVICE, 8-byte aligned, 2 n words, never null.  tools/winding_timing.py. */
+int pt_debug_winding_visits(pt_ctx* ctx, const float* points, size_t n, float beta, float* out, uint32_t* visits);
+/* pt_query_winding's moments to the HOST as the device holds them: n_nodes records of 32 bytes {p[3], r2, N[3], A} in the scene's
+ * node numbering (pt_debug_read_tree's).  Never builds them: refused while they are not built (pt_get_winding_info), and on a
+ * capacity below their size, a null context or a null out. */
+int pt_debug_read_winding(pt_ctx* ctx, void* out, size_t capacity_bytes);
 /* Sorted (morton, triangle) pairs of the last build, HOST outputs of n_tris. */
 int pt_read_morton(pt_ctx* ctx, uint32_t* codes_sorted, uint32_t* prims_sorted);
 /* What the scene's tree is made of, as the device holds it right now (tests/tree_ref.py validates it node by node).  Not part of the
