@@ -4,7 +4,7 @@
 // pt_query_sweep, pt_query_sweep_any, the triangle-against-mesh queries pt_query_triangles, pt_query_triangles_any, the
 // segment-to-mesh distance query pt_query_segments and the K-closest and within-radius queries pt_query_nearest_k,
 // pt_query_within_any and the generalised winding number pt_query_winding (each with its counting twin of include/acgpt_test.h).
-// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip, segment.hip and winding.hip.  The context and what the units share: context.h.
+// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip, segment.hip, tridist.hip and winding.hip.  The context and what the units share: context.h.
 #include <cmath>
 
 #include "../../include/acgpt_test.h"
@@ -16,6 +16,7 @@
 #include "overlap.h"
 #include "query.h"
 #include "segment.h"
+#include "tridist.h"
 #include "sweep.h"
 #include "tritri.h"
 
@@ -23,6 +24,7 @@ static_assert(sizeof(pt_hit) == 32, "pt_hit: a change of this layout bumps pt_ab
 static_assert(sizeof(pt_nearest) == 32, "pt_nearest: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_sweep_hit) == 32, "pt_sweep_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_segment_hit) == 32, "pt_segment_hit: a change of this layout bumps pt_abi_version");
+static_assert(sizeof(pt_triangle_distance_hit) == 48, "pt_triangle_distance_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_ao_params) == 32, "pt_ao_params: a change of this layout bumps pt_abi_version");
 
 // The node array the scene holds, as pt_render_features picks it: fp16 centre / half-extent nodes for the default variants, fp32
@@ -398,6 +400,45 @@ PT_API int pt_debug_segments_visits(pt_ctx* c, const float* segments, size_t n, 
     if (int rc = segments_prepare(c, "pt_debug_segments_visits", segments, n, out, visits, true, &fmt)) return rc < 0 ? 0 : rc;
     CK(c, ptd::launch_segments_visits(fmt, device_scene(c), c->stack_entries, ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)segments,
                                       (uint32_t)n, (float4*)out, (uint2*)visits, flags, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- triangle to mesh distance ----------------------------------------------------------------------------------------------------
+// every refusal of pt_query_triangle_distance before any device work, in pt_query_segments' order; a query is 48 bytes and so is a
+// record.  Returns 0 to go on, 1 refused, -1 nothing to do.
+static int triangle_distance_prepare(pt_ctx* c, const char* fn, const float* tris, size_t n, const void* out, const void* visits, bool with_visits, int* fmt)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (n == 0) return -1;
+    if (!tris || !out || (with_visits && !visits)) return fail(c, f + "null argument");
+    if (n > 0x7FFFFFFFull) return fail(c, f + "too many triangles (2^31 - 1 per call)");
+    if (((uintptr_t)tris & 15u) || ((uintptr_t)out & 15u) || ((uintptr_t)visits & 7u)) return fail(c, f + "the triangle and record arrays must be 16-byte aligned");
+    if (spans_overlap(tris, n * 48u, out, n * sizeof(pt_triangle_distance_hit))) return fail(c, f + "the output overlaps the triangles");
+    if (with_visits && (spans_overlap(tris, n * 48u, visits, n * 8u) || spans_overlap(out, n * sizeof(pt_triangle_distance_hit), visits, n * 8u)))
+        return fail(c, f + "the visit counts overlap another array");
+    return query_node_format(c, f, fmt);
+}
+
+PT_API int pt_query_triangle_distance(pt_ctx* c, const float* tris, size_t n, pt_triangle_distance_hit* out)
+{
+    int fmt = 0;
+    if (int rc = triangle_distance_prepare(c, "pt_query_triangle_distance", tris, n, out, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_triangle_distance");
+    CK(c, ptd::launch_query_triangle_distance(fmt, device_scene(c), c->stack_entries, ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)tris,
+                                              (uint32_t)n, (float4*)out, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_debug_triangle_distance_visits(pt_ctx* c, const float* tris, size_t n, pt_triangle_distance_hit* out, uint32_t* visits, uint32_t flags)
+{
+    if (c && flags > ptd::kTriDistNoPlane) return fail(c, "pt_debug_triangle_distance_visits: flags must be 0 or 1");
+    int fmt = 0;
+    if (int rc = triangle_distance_prepare(c, "pt_debug_triangle_distance_visits", tris, n, out, visits, true, &fmt)) return rc < 0 ? 0 : rc;
+    CK(c, ptd::launch_triangle_distance_visits(fmt, device_scene(c), c->stack_entries, ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)tris,
+                                               (uint32_t)n, (float4*)out, (uint2*)visits, flags, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -18,6 +18,7 @@
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
 //              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k] ...] [--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k] ...]
 //              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...] [--clearance x0,y0,z0,x1,y1,z1[,radius] ...]
+//              [--tri-distance x0,y0,z0,x1,y1,z1,x2,y2,z2[,radius] ...]
 //              [--nearest-k x,y,z,k[,radius] ...] [--within x,y,z,radius ...] [--winding x,y,z[,beta] ...]
 //              [--ao K[,radius[,bias]] --ao-out file.pfm [--ao-frames n]]
 // --ao K[,radius[,bias]] with --ao-out: once the scene is set and before the first frame, the ambient occlusion of the view
@@ -77,6 +78,14 @@
 // [..], "point": [<on the triangle>]}, {"clearance": [..], "radius": r, "found": false} for a scene without triangles.  radius
 // defaults to 0.  Floats are printed with nine digits.  A coordinate that is not finite or a radius that is negative or no number is
 // refused with exit status 2.  The frames are the same with or without it.
+// --tri-distance x0,y0,z0,x1,y1,z1,x2,y2,z2[,radius] (repeatable): once the scene is set and before the first frame, how far the
+// triangle with these vertices is from the scene and where the two come closest, all in one call of pt_query_triangle_distance, one
+// JSON line each: {"tri_distance": [the nine coordinates], "radius": <radius or null>, "found": true, "distance": .., "triangle": ..,
+// "material": "<newmtl name>", "feature": <0..2 a vertex of the query; 3..5 a vertex of the scene triangle; 6..14 an edge pair; 15..17
+// a query edge crosses the scene triangle; 18..20 a scene edge crosses the query>, "on_query": [<on the query triangle>], "point": [<on
+// the scene triangle>]}, {"tri_distance": [..], "radius": .., "found": false} if nothing lies within the radius (default: no limit).
+// Floats are printed with nine digits.  Fewer than nine or more than ten numbers, a coordinate that is not finite or a radius that is
+// negative or no number is refused with exit status 2.  The frames are the same with or without it.
 // --bloom (with --tonemap or --exposure): the image the display transform shows goes through pt_bloom first.  threshold is in display
 // units, multiples of exposed white, and is divided by the exposure (and so are the default knee, half the threshold, and the
 // clamp, none); an automatic exposure is metered on the image without its glare and then applied as a manual one.  --out-hdr gets
@@ -880,6 +889,39 @@ static void clearanceSegments(PathTracerState& state, const TinyObjWrapper& obj,
     fflush(stdout);
 }
 
+// --tri-distance: every triangle in one call of pt_query_triangle_distance; one JSON line per triangle
+struct DistanceTriangle { float g[12]; bool limited; };
+static void triangleDistances(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<DistanceTriangle>& tris)
+{
+    const size_t n = tris.size();
+    void* d_tris = nullptr; void* d_out = nullptr;
+    std::vector<float> in(n * 12);
+    for (size_t i = 0; i < n; i++) for (int k = 0; k < 12; k++) in[i * 12 + k] = tris[i].g[k];
+    std::vector<pt_triangle_distance_hit> out(n);
+    std::string err;
+    if (pt_device_malloc(state.context, &d_tris, n * 48) != 0 || pt_device_malloc(state.context, &d_out, n * sizeof(pt_triangle_distance_hit)) != 0 ||
+        pt_copy_to_device(state.context, d_tris, in.data(), n * 48) != 0 ||
+        pt_query_triangle_distance(state.context, (const float*)d_tris, n, (pt_triangle_distance_hit*)d_out) != 0 ||
+        pt_copy_to_host(state.context, out.data(), d_out, n * sizeof(pt_triangle_distance_hit)) != 0)
+        err = pt_last_error(state.context);
+    if (d_tris) pt_device_free(state.context, d_tris);
+    if (d_out) pt_device_free(state.context, d_out);
+    if (!err.empty()) throw Exception("tri-distance: " + err);
+    const std::vector<std::string>& names = obj.getMaterialNames();
+    for (size_t i = 0; i < n; i++) {
+        const pt_triangle_distance_hit& r = out[i];
+        const float* g = tris[i].g;
+        printf("{\"tri_distance\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"radius\": ", g[0], g[1], g[2], g[4], g[5], g[6], g[8], g[9], g[10]);
+        if (tris[i].limited && std::isfinite(g[3])) printf("%.9g, ", g[3]); else printf("null, ");
+        if (r.prim == 0xFFFFFFFFu) { printf("\"found\": false}\n"); continue; }
+        std::string name = r.material < names.size() ? names[r.material] : std::string();
+        for (size_t k = 0; k < name.size(); k++) if (name[k] == '"' || name[k] == '\\' || (unsigned char)name[k] < 0x20) name[k] = '_';
+        printf("\"found\": true, \"distance\": %.9g, \"triangle\": %u, \"material\": \"%s\", \"feature\": %d, \"on_query\": [%.9g, %.9g, %.9g], \"point\": [%.9g, %.9g, %.9g]}\n",
+               r.distance, r.prim, name.c_str(), (int)r.feature, r.qx, r.qy, r.qz, r.cx, r.cy, r.cz);
+    }
+    fflush(stdout);
+}
+
 // --nearest: every point in one call of pt_query_nearest; one JSON line per point
 static void nearestPoints(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<float4>& points)
 {
@@ -1068,6 +1110,7 @@ int main(int argc, char** argv)
     std::vector<float4> withins;
     std::vector<float4> windings;
     std::vector<ClearanceSegment> clearances;
+    std::vector<DistanceTriangle> triDistances;
     std::vector<OverlapBox> overlaps;
     std::vector<IntersectTri> intersects;
     std::vector<SweepArg> sweeps;
@@ -1200,6 +1243,22 @@ int main(int argc, char** argv)
             for (int k = 0; k < 7; k++) if (k != 3 && !std::isfinite(g[k])) fine = false;
             if (!fine) { std::cerr << "--clearance x0,y0,z0,x1,y1,z1[,radius]: finite coordinates, a finite radius >= 0" << std::endl; return 2; }
             clearances.push_back(cs);
+        }
+        else if (a == "--tri-distance") {
+            DistanceTriangle dt = {{0.0f, 0.0f, 0.0f, INFINITY, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, false};
+            float* g = dt.g;
+            const char* text = next();
+            int used = 0;
+            int got = sscanf(text, "%f,%f,%f,%f,%f,%f,%f,%f,%f%n", &g[0], &g[1], &g[2], &g[4], &g[5], &g[6], &g[8], &g[9], &g[10], &used);
+            bool fine = got == 9;
+            if (fine && text[used] != '\0') {                  // a tenth number, the radius, and nothing behind it
+                int more = 0;
+                fine = sscanf(text + used, ",%f%n", &g[3], &more) == 1 && text[used + more] == '\0' && g[3] >= 0.0f;
+                dt.limited = true;
+            }
+            for (int k = 0; k < 11; k++) if (k != 3 && k != 7 && !std::isfinite(g[k])) fine = false;
+            if (!fine) { std::cerr << "--tri-distance x0,y0,z0,x1,y1,z1,x2,y2,z2[,radius]: nine finite coordinates, a radius >= 0" << std::endl; return 2; }
+            triDistances.push_back(dt);
         }
         else if (a == "--overlap") {
             OverlapBox b = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, 8u};
@@ -1357,6 +1416,7 @@ int main(int argc, char** argv)
         if (!withins.empty()) { std::cout.flush(); withinPoints(state, withins); }
         if (!windings.empty()) { std::cout.flush(); windingPoints(state, windings); }
         if (!clearances.empty()) { std::cout.flush(); clearanceSegments(state, obj, clearances); }
+        if (!triDistances.empty()) { std::cout.flush(); triangleDistances(state, obj, triDistances); }
         if (!overlaps.empty()) { std::cout.flush(); overlapBoxes(state, obj, overlaps); }
         if (!intersects.empty()) { std::cout.flush(); intersectTriangles(state, intersects); }
         if (!sweeps.empty()) { std::cout.flush(); sweepSpheres(state, obj, sweeps); }

@@ -1681,6 +1681,99 @@ def meshCollisions(state, vertices, indices, poses=None, pairs=False):
     return {"pairs": triples, "counts": got["count"].reshape(P, T)}
 
 
+# ------------------------------------------------------------------ triangle to mesh distance ----
+TRIANGLE_DISTANCE_DTYPE = np.dtype([("distance", np.float32), ("prim", np.uint32), ("feature", np.float32), ("material", np.uint32), ("on_query", np.float32, 3),
+                                    ("pad0", np.float32), ("point", np.float32, 3), ("pad1", np.float32)])      # pt_triangle_distance_hit
+assert TRIANGLE_DISTANCE_DTYPE.itemsize == 48
+
+
+def _checked_radius(what, max_radius):
+    radius = float(max_radius)
+    if not radius >= 0.0:
+        raise PathTracerError("%s: max_radius must be non-negative, got %r" % (what, max_radius))
+    return radius
+
+
+def queryTriangleDistance(state, triangles, max_radius=float("inf")):
+    """How far each triangle of the caller's is from the scene on the GPU, and where the two come closest (include/acgpt.h
+    pt_query_triangle_distance): the distance query of mesh-to-mesh clearance.
+
+    NumPy (or anything np.asarray takes): (n, 3, 3) or (n, 9) vertices — every triangle gets max_radius — or (n, 12) records
+    {a0.xyz, max_radius, a1.xyz, ignored, a2.xyz, ignored} as they are.  They go to the device and the answer comes back: a dict of
+    arrays distance (n,) float32 (0 where the two intersect, -1 where nothing lies within the radius), prim (n,) uint32 (the scene
+    triangle's index in the scene's order, 0xFFFFFFFF), feature (n,) float32 (0..2: a vertex of the query; 3..5: a vertex of the scene
+    triangle; 6..14: an edge pair; 15..17: a query edge crosses the scene triangle; 18..20: a scene edge crosses the query), material
+    (n,) uint32, on_query (n, 3) the closest point on the query triangle and point (n, 3) the closest point on the scene.
+
+    A torch tensor must be (n, 12) float32 records, contiguous and on the context's device; nothing is copied, its data_ptr() goes
+    straight in, and the answer is torch tensors on that device: views of one (n, 12) float32 tensor, prim and material as int32 (-1
+    on a miss).  torch's current stream is synchronised before the call, and the call returns synchronised."""
+    L = _native.hip()
+    if _is_tensor(triangles):
+        torch = _triangle_tensor("queryTriangleDistance", state, triangles)
+        n = int(triangles.shape[0])
+        with torch.cuda.device(triangles.device):
+            out = torch.empty((n, 12), dtype=torch.float32, device=triangles.device)
+            torch.cuda.current_stream().synchronize()      # the triangles' producer and the allocation; the call below returns synchronised
+        _check(state.context, L.pt_query_triangle_distance(state.context, triangles.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_triangle_distance")
+        return {"distance": out[:, 0], "prim": out[:, 1].view(torch.int32), "feature": out[:, 2], "material": out[:, 3].view(torch.int32), "on_query": out[:, 4:7],
+                "point": out[:, 8:11]}
+    r = _triangle_records("queryTriangleDistance", triangles)
+    if np.asarray(triangles).shape[-1] != 12:
+        r[:, 3] = _checked_radius("queryTriangleDistance", max_radius)
+    n = r.shape[0]
+    out = np.zeros(n, TRIANGLE_DISTANCE_DTYPE)
+    if n:
+        bufs = _device_buffers(state, 2, out.nbytes)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], r.ctypes.data, r.nbytes), "copy to device")
+            _check(state.context, L.pt_query_triangle_distance(state.context, bufs[0], n, bufs[1]), "pt_query_triangle_distance")
+            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    return {k: np.ascontiguousarray(out[k]) for k in ("distance", "prim", "feature", "material", "on_query", "point")}
+
+
+def meshClearance(state, vertices, indices, poses=None, max_radius=float("inf")):
+    """How close P poses of one mesh come to the scene on the GPU, and where.  poses: (P, 3, 4) or (P, 4, 4) (or one matrix, or None for
+    the mesh as it is).  One queryTriangleDistance call over the P x T records (triangleRecords' with max_radius in the fourth
+    column), reduced per pose to its closest pair.  Returns a dict, one row per pose: clearance (P,) float32 (0 where the mesh touches
+    the scene, +inf where nothing lies within max_radius), query_triangle (P,) int64 the mesh triangle of the closest pair (ties to
+    the lowest; -1 where there is none), prim (P,) the scene triangle (0xFFFFFFFF, or -1 in a tensor, where there is none), on_query
+    (P, 3) and on_mesh (P, 3) the closest points on the posed mesh and on the scene — on_mesh - on_query is the direction to push the
+    scene away in.  Arrays for arrays, tensors for tensors."""
+    radius = _checked_radius("meshClearance", max_radius)
+    rec = _posed_records("meshClearance", vertices, indices, poses)
+    P, T = int(rec.shape[0]), int(rec.shape[1])
+    rec[:, :, 3] = radius
+    got = queryTriangleDistance(state, rec.reshape(P * T, 12))
+    dist = got["distance"].reshape(P, T)
+    if _is_tensor(dist):
+        import torch
+        inf = torch.full_like(dist, float("inf"))
+        d = torch.where(dist >= 0, dist, inf)
+        if T == 0:
+            zeros = torch.zeros((P, 3), dtype=torch.float32, device=dist.device)
+            return {"clearance": torch.full((P,), float("inf"), dtype=torch.float32, device=dist.device), "query_triangle": torch.full((P,), -1, dtype=torch.int64, device=dist.device),
+                    "prim": torch.full((P,), -1, dtype=torch.int32, device=dist.device), "on_query": zeros, "on_mesh": zeros.clone()}
+        best = d.min(dim=1).values
+        cols = torch.arange(T, device=dist.device)[None].expand(P, T)
+        tri = torch.where(d == best[:, None], cols, torch.full_like(cols, T)).min(dim=1).values      # the lowest mesh triangle among the ties
+        found = torch.isfinite(best)
+        row = torch.arange(P, device=dist.device) * T + tri
+        return {"clearance": best, "query_triangle": torch.where(found, tri, torch.full_like(tri, -1)), "prim": got["prim"][row],
+                "on_query": got["on_query"][row], "on_mesh": got["point"][row]}
+    d = np.where(dist >= 0, dist, np.float32(np.inf)).astype(np.float32)
+    if T == 0:
+        return {"clearance": np.full(P, np.inf, np.float32), "query_triangle": np.full(P, -1, np.int64), "prim": np.full(P, 0xFFFFFFFF, np.uint32),
+                "on_query": np.zeros((P, 3), np.float32), "on_mesh": np.zeros((P, 3), np.float32)}
+    tri = d.argmin(axis=1)                                 # the first (lowest) mesh triangle among the ties
+    row = np.arange(P) * T + tri
+    best = d[np.arange(P), tri]
+    return {"clearance": best, "query_triangle": np.where(np.isfinite(best), tri, -1).astype(np.int64), "prim": got["prim"][row], "on_query": got["on_query"][row],
+            "on_mesh": got["point"][row]}
+
+
 # ------------------------------------------------------------------ swept spheres ----
 SWEEP_DTYPE = np.dtype([("t", np.float32), ("prim", np.uint32), ("u", np.float32), ("v", np.float32), ("point", np.float32, 3), ("material", np.uint32)])      # pt_sweep_hit
 assert SWEEP_DTYPE.itemsize == 32

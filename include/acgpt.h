@@ -696,6 +696,64 @@ int pt_query_sweep_any(pt_ctx* ctx, const float* sweeps, size_t n, uint8_t* bloc
 typedef struct { float distance; uint32_t prim; float s, feature; float cx, cy, cz; uint32_t material; } pt_segment_hit;   /* 32 bytes */
 int pt_query_segments(pt_ctx* ctx, const float* segments, size_t n, pt_segment_hit* out);
 
+/* ---- triangle-to-mesh distance on the device (opt-in; nothing above changes) -------------------------------------------------------
+ * How far a triangle is from the surface and where the two come closest: the distance query of PQP and FCL for a mesh that moves
+ * through the scene (a robot link, a tool, a character hull), which pt_query_triangles only answers with "intersects: yes / no".
+ * pt_query_segments on the moving mesh's edges misses a scene edge that pierces a query face (it reports a positive distance for an
+ * intersecting pair) and a scene vertex that is closest to the interior of a query face.
+ * pt_query_segments' memory and call rules: DEVICE arrays, 16-byte aligned; the call enqueues on the context's stream and returns
+ * synchronised, acts on rank 0 of a pt_create_multi context, never writes the accumulation buffer, the frame buffer or pt_stats, walks
+ * the node array the scene holds (pt_bvh_info.device_bytes does not change, with pt_query_nearest's one exception) and uses no
+ * atomics: two calls give the same bits.  A scene without triangles answers every query with the miss record.
+ *
+ *   tris      n records of 12 floats {a0.x, a0.y, a0.z, max_radius | a1.x, a1.y, a1.z, ignored | a2.x, a2.y, a2.z, ignored}:
+ *             pt_query_triangles' layout with the radius in the fourth float.  The eighth and twelfth float are never read into a
+ *             decision: a NaN there changes nothing.
+ *   out       n records of 48 bytes (pt_triangle_distance_hit)
+ *   d2        the squared distance from the query triangle to a scene triangle, all fp32, every multiply, add and division on its own,
+ *             evaluated as written, no fused multiply-add (tests/tridist_ref.py is the NumPy statement, equal bit for bit).  With the
+ *             vectors the build stores for the scene triangle, v0, e1, e2, one operation per component in
+ *               f1 = a1 - a0;  f2 = a2 - a0;  g = a2 - a1;  w1 = fl(v0 + e1);  w2 = fl(v0 + e2);  h = fl(e2 - e1)
+ *             the query's edges are Q0 = {a0, f1}, Q1 = {a0, f2}, Q2 = {a1, g} and the scene triangle's S0 = {v0, e1}, S1 = {v0, e2},
+ *             S2 = {w1, h} (pt_query_segments' own edge order).  Twenty-one sub-tests, each giving (d2, q, c): the squared distance,
+ *             the point on the query triangle and the point on the scene triangle.
+ *               features 0, 1, 2     pt_query_nearest's closest_on_triangle(a_i; v0, e1, e2), exactly, at a0, a1, a2 as given in the
+ *                                    record: its d2 and c; q = a_i
+ *               features 3, 4, 5     closest_on_triangle(b_j; a0, f1, f2) for b = (v0, w1, w2): its d2; q its closest point, c = b_j
+ *               features 6 + 3 i + j the segment section's edge statement, verbatim, of the segment Q_i = {P, D} with a = dot(D, D)
+ *                                    against the edge S_j = {A, E}: its d2; q = P + D s (a product, then a sum, per component), c its
+ *                                    point A + E t on the edge
+ *               features 15, 16, 17  the segment section's crossing test of Q_i against {v0, e1, e2}; accepted: d2 = 0 exactly,
+ *                                    s = T / det, q = c = P + D s
+ *               features 18, 19, 20  the same crossing test of S_j against {a0, f1, f2}: q = c = A + E s
+ *             Among features 0 to 14 the smallest d2 wins, ties to the lower feature; a NaN d2 is no candidate (a feature replaces the
+ *             running one iff its d2 is smaller, or the running d2 is a NaN and its own is not).  An accepted crossing overrides
+ *             them; of several accepted crossings the lowest feature number gives the record.  Computing d2 alone costs 24 IEEE
+ *             divisions per pair (6 + 18); the crossings' divisions are needed for the winner's record only.
+ *   candidate a triangle with d2 <= max_radius * max_radius, the product taken in fp32; max_radius = +inf is allowed and its square
+ *             is +inf.  A NaN d2 is no candidate.
+ *   answer    the candidate with the smallest d2; ties go to the lowest triangle index in the caller's index-buffer order
+ *   found     distance = sqrtf(d2) of the winner, one IEEE square root; prim its index; feature the winner's, the number stored as a
+ *             float; material the scene triangle's material id; (qx, qy, qz) the point on the query triangle and (cx, cy, cz) the
+ *             point on the scene triangle: c - q is the direction to push the query away from the scene along, and for a crossing
+ *             both are the crossing point
+ *   a miss before any traversal: a non-finite one of the nine coordinates, a non-finite component of a1 - a0, a2 - a0 or a2 - a1
+ *             (finite vertices whose difference overflows), a NaN or negative max_radius, a scene without triangles
+ *   miss      {distance -1, prim 0xFFFFFFFF, feature 0, material 0xFFFFFFFF | 0, 0, 0, 0 | 0, 0, 0, 0}
+ *   pad0, pad1 are written as 0 in every record.
+ * A query without area (a2 == a1: a segment; three equal vertices: a point) is a query like any other: its vertex and edge features
+ * answer, and its distance is at most pt_query_segments' and pt_query_nearest's on the same input.
+ * Not watertight in d2 at shared edges: neighbouring triangles compute a shared edge from their own stored vectors; the smaller d2
+ * wins, ties to the lower index.  Products of four lengths (den of the edge statement, the va, vb, vc of features 0 to 5, the
+ * crossing tests' U, V, T) leave fp32's range when edge length times edge length times the distance between them passes about 1e19
+ * squared; such a sub-test yields a NaN or fails and silently stops being a candidate.
+ * n == 0 is a no-op success.  Refused, with the context left usable, in pt_query_segments' order and with messages that start
+ * "pt_query_triangle_distance: ": a null context, a null tris or out pointer with n > 0, n > 0x7FFFFFFF ("too many triangles"), an
+ * array that is not 16-byte aligned, an output that overlaps the triangles, a context without a scene.                              */
+typedef struct { float distance; uint32_t prim; float feature; uint32_t material;
+                 float qx, qy, qz, pad0;  float cx, cy, cz, pad1; } pt_triangle_distance_hit;   /* 48 bytes */
+int pt_query_triangle_distance(pt_ctx* ctx, const float* tris, size_t n, pt_triangle_distance_hit* out);
+
 /* ---- the K closest triangles of a point, and "is anything within r" (opt-in; nothing above changes) ------------------------------
  * pt_query_nearest answers with one triangle.  A ball resting in a corner touches three walls and needs all three contacts; a point
  * whose closest feature is an edge or a vertex ties between two to six triangles, of which pt_query_nearest names the lowest index

@@ -157,6 +157,11 @@ int pt_debug_triangles_visits(pt_ctx* ctx, const float* tris, size_t n, uint32_t
  * second box bound (the three axes perpendicular to the segment), which changes the counts and never the records; anything else is
  * refused.  tools/segments_timing.py. */
 int pt_debug_segments_visits(pt_ctx* ctx, const float* segments, size_t n, pt_segment_hit* out, uint32_t* visits, uint32_t flags);
+/* pt_query_triangle_distance (same records, same refusals) from a kernel instantiation that also counts: visits[2 i] = inner nodes
+ * query i visited, visits[2 i + 1] = triangles it tested.  visits: DEVICE, 8-byte aligned, 2 n words.  flags: 0, or 1 to switch off the
+ * walk's second box bound (the separation along the query triangle's normal), which changes the counts and never the records;
+ * anything else is refused.  tools/tridist_timing.py. */
+int pt_debug_triangle_distance_visits(pt_ctx* ctx, const float* tris, size_t n, pt_triangle_distance_hit* out, uint32_t* visits, uint32_t flags);
 /* pt_query_nearest_k (hit null: same records, same counts, same refusals) or pt_query_within_any (hit given; max_k must be 0 and
  * out and counts null) from kernel instantiations that also count: visits[2 i] = inner nodes point i visited, visits[2 i + 1] =
  * triangles it tested.  visits: DEVICE, 8-byte aligned, 2 n words, never null.  tools/nearest_k_timing.py. */
