@@ -3,13 +3,15 @@
 // closest-point query pt_query_nearest, the box-overlap queries pt_query_overlap, pt_query_overlap_any and the swept-sphere casts
 // pt_query_sweep, pt_query_sweep_any, the triangle-against-mesh queries pt_query_triangles, pt_query_triangles_any, the
 // segment-to-mesh distance query pt_query_segments and the K-closest and within-radius queries pt_query_nearest_k,
-// pt_query_within_any and the generalised winding number pt_query_winding (each with its counting twin of include/acgpt_test.h).
-// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip, segment.hip, tridist.hip and winding.hip.  The context and what the units share: context.h.
+// pt_query_within_any and the generalised winding number pt_query_winding (each with its counting twin of include/acgpt_test.h),
+// and the complete lists in CSR form: pt_list_offsets, pt_query_overlap_lists, pt_query_triangles_lists.
+// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip, segment.hip, tridist.hip, winding.hip and lists.hip.  The context and what the units share: context.h.
 #include <cmath>
 
 #include "../../include/acgpt_test.h"
 #include "context.h"
 #include "ao.h"
+#include "lists.h"
 #include "multihit.h"
 #include "nearest.h"
 #include "nearest_k.h"
@@ -362,6 +364,108 @@ PT_API int pt_debug_triangles_visits(pt_ctx* c, const float* tris, size_t n, uin
     CK(c, ptd::launch_triangles_visits(fmt, device_scene(c), c->stack_entries, ptd::overlap_scene_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)tris,
                                        (uint32_t)n, counts, (uint2*)visits, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- complete lists in CSR form ---------------------------------------------------------------------------------------------------
+// counts -> offsets.  Needs no scene.  The refusals in the siblings' order; the total is judged after it has been computed.
+PT_API int pt_list_offsets(pt_ctx* c, const uint32_t* counts, size_t n, uint32_t* offsets, uint64_t* total)
+{
+    const std::string f = "pt_list_offsets: ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (total) *total = 0u;
+    if (n == 0 && !offsets) return 0;
+    if (!offsets || (n != 0 && !counts)) return fail(c, f + "null argument");
+    if (n > 0x7FFFFFFFull) return fail(c, f + "too many counts (2^31 - 1 per call)");
+    if (((uintptr_t)counts & 3u) || ((uintptr_t)offsets & 3u)) return fail(c, f + "counts and offsets must be 4-byte aligned");
+    if (n != 0 && spans_overlap(counts, n * 4u, offsets, (n + 1u) * 4u)) return fail(c, f + "offsets overlaps counts (the scan is not in place)");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, f + "hipSetDevice failed");
+    Range range("pt_list_offsets");
+    if (n == 0) {
+        CK(c, hipMemsetAsync(offsets, 0, 4u, c->stream));
+        CK(c, hipStreamSynchronize(c->stream));
+        return 0;
+    }
+    const size_t words = ptd::list_scratch_words(n);
+    CK(c, c->d_list_scratch.reserve(words, c->stream));
+    CK(c, ptd::launch_list_offsets(counts, (uint32_t)n, offsets, c->d_list_scratch.p, c->stream));
+    unsigned long long sum = 0ull;
+    CK(c, hipMemcpyAsync(&sum, c->d_list_scratch.p + (words - 1u), sizeof(sum), hipMemcpyDeviceToHost, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    if (total) *total = sum;
+    if (sum > 0xFFFFFFFFull) return fail(c, f + "the total " + std::to_string(sum) + " does not fit 32-bit offsets: split the batch");
+    return 0;
+}
+
+// every refusal of the two list calls before any device work, in pt_query_overlap's order.  what names the input records, in_bytes the
+// bytes of one.  Returns 0 to go on, 1 refused, -1 nothing to do (n == 0).
+static int lists_prepare(pt_ctx* c, const char* fn, const float* recs, size_t n, const uint32_t* offsets, const uint32_t* prims, size_t capacity,
+                         const uint32_t* found, int* fmt, const char* what, size_t in_bytes)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (n == 0) return -1;
+    if (!recs || !offsets || (!prims && capacity != 0)) return fail(c, f + "null argument");
+    if (n > 0x7FFFFFFFull) return fail(c, f + "too many " + what + " (2^31 - 1 per call)");
+    if ((uintptr_t)recs & 15u) return fail(c, f + "the " + what + " must be 16-byte aligned");
+    if (((uintptr_t)offsets & 3u) || ((uintptr_t)prims & 3u) || ((uintptr_t)found & 3u)) return fail(c, f + "offsets, prims and found must be 4-byte aligned");
+    if (capacity > ((size_t)-1 >> 2)) return fail(c, f + "capacity is more words than memory has");
+    const struct { const void* p; size_t bytes; const char* name; } spans[4] = {
+        {recs, n * in_bytes, what}, {offsets, (n + 1u) * 4u, "offsets"}, {capacity ? prims : nullptr, capacity * 4u, "prims"}, {found, n * 4u, "found"}};
+    for (int k = 1; k < 4; k++) {
+        if (!spans[k].p) continue;
+        for (int j = 0; j < k; j++)
+            if (spans[j].p && spans_overlap(spans[j].p, spans[j].bytes, spans[k].p, spans[k].bytes))
+                return fail(c, f + spans[k].name + " overlaps " + (j == 0 ? "the " : "") + spans[j].name);
+    }
+    return query_node_format(c, f, fmt);
+}
+
+// the flag is cleared, the lists are written, the flag is read after the sync; a raised flag is the call's failure, the lists stay
+template <typename Launch>
+static int lists_run(pt_ctx* c, const char* fn, Launch launch)
+{
+    CK(c, c->d_list_scratch.reserve(ptd::list_scratch_words(0), c->stream));
+    uint32_t* flag = (uint32_t*)c->d_list_scratch.p;
+    CK(c, hipMemsetAsync(flag, 0, sizeof(uint32_t), c->stream));
+    CK(c, launch(flag));
+    uint32_t raised = 0u;
+    CK(c, hipMemcpyAsync(&raised, flag, sizeof(raised), hipMemcpyDeviceToHost, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    if (raised) return fail(c, std::string(fn) + ": the offsets do not fit this scene and these queries (a slice is shorter than its list, or lies outside prims): "
+                                                 "count again and rebuild them with pt_list_offsets");
+    return 0;
+}
+
+PT_API int pt_query_overlap_lists(pt_ctx* c, const float* boxes, size_t n, const uint32_t* offsets, uint32_t* prims, size_t capacity, uint32_t* found)
+{
+    int fmt = 0;
+    if (int rc = lists_prepare(c, "pt_query_overlap_lists", boxes, n, offsets, prims, capacity, found, &fmt, "boxes", 32u)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_overlap_lists");
+    const uint32_t cap = capacity > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)capacity;      // no 32-bit offset reaches further
+    return lists_run(c, "pt_query_overlap_lists", [&](uint32_t* flag) {
+        return ptd::launch_overlap_lists(fmt, device_scene(c), c->stack_entries, ptd::overlap_scene_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)boxes,
+                                         (uint32_t)n, offsets, prims, cap, found, flag, c->list_phases, c->stream);
+    });
+}
+
+PT_API int pt_query_triangles_lists(pt_ctx* c, const float* tris, size_t n, const uint32_t* offsets, uint32_t* prims, size_t capacity, uint32_t* found)
+{
+    int fmt = 0;
+    if (int rc = lists_prepare(c, "pt_query_triangles_lists", tris, n, offsets, prims, capacity, found, &fmt, "triangles", 48u)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_triangles_lists");
+    const uint32_t cap = capacity > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)capacity;
+    return lists_run(c, "pt_query_triangles_lists", [&](uint32_t* flag) {
+        return ptd::launch_triangles_lists(fmt, device_scene(c), c->stack_entries, ptd::overlap_scene_term(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)tris,
+                                           (uint32_t)n, offsets, prims, cap, found, flag, c->list_phases, c->stream);
+    });
+}
+
+PT_API int pt_debug_list_phases(pt_ctx* c, uint32_t phases)
+{
+    if (!c) return fail(nullptr, "pt_debug_list_phases: null context");
+    if (phases > 7u || !(phases & ptd::kListPhaseAll)) return fail(c, "pt_debug_list_phases: phases is 1 (fill), 2 (sort) or 3 (both), plus 4 for no register list");
+    c->list_phases = phases;
     return 0;
 }
 

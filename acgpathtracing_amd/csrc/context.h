@@ -111,7 +111,10 @@ struct pt_ctx {
     DevBuf<float4> d_bloom_pyramid;                   // ... and its pyramid, all levels in one allocation
     StageBuf<ptd::ConvergenceState> d_convergence;    // pt_convergence_update's counts and record
     DevBuf<float2> d_ao_disk;                 // pt_ao_points / pt_ao_image: the caller's disk pattern of the last call (at most 256 pairs)
-    DevBuf<uint8_t> d_tri_bsdf;               // bsdfType per triangle (caller's order): pt_temporal_blend's, built on its first call per scene
+    DevBuf<unsigned long long> d_list_scratch;   // pt_list_offsets' tile sums and the list queries' mismatch flag (lists.h list_scratch_words); the
+                                              // context's, not the scene's: not counted in device_bytes
+    uint32_t list_phases = 3u;                // pt_debug_list_phases: fill | sort (ptd::kListPhaseAll), the product's
+    DevBuf<uint8_t> d_tri_bsdf;              // bsdfType per triangle (caller's order): pt_temporal_blend's, built on its first call per scene
     // what pt_update_vertices keeps of the last pt_set_scene: host copies of everything but the vertices, and after the first update
     // the index buffer on the device (freed with the scene)
     bool scene_kept = false;

@@ -1,0 +1,395 @@
+// lists.hip — the kernels behind pt_list_offsets, pt_query_overlap_lists and pt_query_triangles_lists (include/acgpt.h).
+//
+//   k_list_tile_sums / k_list_scan_tiles / k_list_add_back   the scan: counts -> offsets, 64-bit sums, three launches, no look-back
+//   k_fill_lists<FMT, Q, REG>   one query per lane (Q: a box or a triangle), the walk and the leaf test of overlap.hip / tritri.hip through
+//                          the shared device headers.  The lane reads its slice [lo, hi) of prims first.  A slice of at most
+//                          kListRegister words is the capped kernels' sorted register list, written once in the epilogue: ascending
+//                          already.  A longer slice is stored as the walk accepts, in walk order, and its surplus slots are filled
+//                          with 0xFFFFFFFF.  A lane whose slice is not lo <= hi <= capacity stores nothing.
+//   k_sort_lists           sorts every slice longer than kListRegister in place: each workgroup finds those of its 256 queries by
+//                          ballot and takes them one after the other, all 256 lanes on one list — the normalised bitonic network, whose
+//                          comparators all put the larger word at the higher index, so a length that is no power of two only skips the
+//                          comparators whose upper index is past the end.  Up to kListSortLds words in LDS, beyond that in global memory
+//                          with workgroup barriers between steps: one workgroup owns the whole list, so workgroup scope suffices.
+//
+// 256-lane workgroups over one-dimensional grids; the fill has overlap.hip's LDS lane stack (stack_entries * 64 words per wave).  No
+// atomics: the mismatch flag is a plain store of 1 by every lane that raises it.  Two calls give the same bits.  Built with
+// -ffp-contract=off like the units it shares the leaf tests with.
+#include "lists.h"
+#include "overlap_device.h"
+#include "tritri_device.h"
+
+namespace ptd {
+
+extern __shared__ uint32_t lists_lds[];
+
+typedef unsigned long long u64;
+
+// ---- the scan --------------------------------------------------------------------------------------------------------------------
+// Exclusive scan of one value per lane over the 256 lanes of the workgroup, in lane order (Hillis-Steele in LDS); total: the sum of
+// all.  s: 256 words of LDS, free again on return.
+__device__ __forceinline__ u64 block_scan_exclusive(u64 v, u64* s, u64& total)
+{
+    const uint32_t t = threadIdx.x;
+    s[t] = v;
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t d = 1u; d < 256u; d <<= 1) {
+        const u64 x = t >= d ? s[t - d] : 0ull;
+        __syncthreads();
+        s[t] += x;
+        __syncthreads();
+    }
+    const u64 inclusive = s[t];
+    total = s[255];
+    __syncthreads();
+    return inclusive - v;
+}
+
+// the lane's kListScanTile / 256 consecutive counts of tile blockIdx.x (0 past n) and their sum.  n <= 2^31 - 1: no index wraps.
+__device__ __forceinline__ u64 load_counts(const uint32_t* __restrict__ counts, uint32_t n, uint32_t (&c)[kListScanTile / 256u], uint32_t& first)
+{
+    first = blockIdx.x * kListScanTile + threadIdx.x * (kListScanTile / 256u);
+    u64 sum = 0ull;
+#pragma unroll
+    for (uint32_t j = 0; j < kListScanTile / 256u; j++) {
+        c[j] = first + j < n ? counts[first + j] : 0u;
+        sum += c[j];
+    }
+    return sum;
+}
+
+__global__ void __launch_bounds__(256)
+k_list_tile_sums(const uint32_t* __restrict__ counts, uint32_t n, u64* __restrict__ sums)
+{
+    __shared__ u64 s[256];
+    uint32_t c[kListScanTile / 256u], first;
+    u64 total;
+    (void)block_scan_exclusive(load_counts(counts, n, c, first), s, total);
+    if (threadIdx.x == 0u) sums[blockIdx.x] = total;
+}
+
+// One workgroup: sums[0 .. tiles) become their exclusive prefixes, sums[tiles] the total.  Lane t owns the run of `run` consecutive
+// tiles from t * run, run = ceil(tiles / kListScanRuns).
+__global__ void __launch_bounds__(256)
+k_list_scan_tiles(u64* sums, uint32_t tiles)
+{
+    __shared__ u64 s[256];
+    const uint32_t run = (tiles + kListScanRuns - 1u) / kListScanRuns;
+    const u64 lo = (u64)threadIdx.x * run, hi = lo + run < (u64)tiles ? lo + run : (u64)tiles;
+    u64 sum = 0ull;
+    for (u64 k = lo; k < hi; k++) sum += sums[k];
+    u64 total;
+    u64 prefix = block_scan_exclusive(sum, s, total);
+    for (u64 k = lo; k < hi; k++) {
+        const u64 v = sums[k];
+        sums[k] = prefix;
+        prefix += v;
+    }
+    if (threadIdx.x == 0u) sums[tiles] = total;
+}
+
+__global__ void __launch_bounds__(256)
+k_list_add_back(const uint32_t* __restrict__ counts, uint32_t n, const u64* __restrict__ sums, uint32_t* __restrict__ offsets)
+{
+    __shared__ u64 s[256];
+    uint32_t c[kListScanTile / 256u], first;
+    u64 total;
+    u64 prefix = block_scan_exclusive(load_counts(counts, n, c, first), s, total) + sums[blockIdx.x];
+    if (blockIdx.x == 0u && threadIdx.x == 0u) offsets[0] = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < kListScanTile / 256u; j++) {
+        prefix += c[j];
+        if (first + j < n) offsets[(size_t)first + j + 1u] = (uint32_t)prefix;
+    }
+}
+
+hipError_t launch_list_offsets(const uint32_t* counts, uint32_t n, uint32_t* offsets, unsigned long long* scratch, hipStream_t stream)
+{
+    if (n == 0u || n > 0x7FFFFFFFu) return hipErrorInvalidValue;
+    const uint32_t tiles = (n + kListScanTile - 1u) / kListScanTile;
+    u64* sums = scratch + 1;
+    k_list_tile_sums<<<tiles, 256, 0, stream>>>(counts, n, sums);
+    k_list_scan_tiles<<<1, 256, 0, stream>>>(sums, tiles);
+    k_list_add_back<<<tiles, 256, 0, stream>>>(counts, n, sums, offsets);
+    return hipGetLastError();
+}
+
+// ---- the queries -----------------------------------------------------------------------------------------------------------------
+// What the walk asks of a query: load() the record (false: a miss before any traversal, or a lane past n), prepare() the walk's
+// constants, admit a child box of either format, accept a triangle.  The statements are k_query_overlap's and k_query_triangles'.
+struct BoxQuery {
+    f3 c, h, thr, qc;
+    __device__ __forceinline__ bool load(const float4* __restrict__ boxes, uint32_t i, uint32_t n)
+    {
+        c = mk(0.0f); h = mk(0.0f);
+        if (i >= n) return false;
+        const float4 a = boxes[2ull * i], b = boxes[2ull * i + 1ull];
+        c = mk(a.x, a.y, a.z);
+        h = mk(a.w, b.x, b.y);
+        return __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z) && __builtin_isfinite(a.w) && __builtin_isfinite(b.x) &&
+               __builtin_isfinite(b.y) && a.w >= 0.0f && b.x >= 0.0f && b.y >= 0.0f;
+    }
+    __device__ __forceinline__ void prepare(const DeviceScene& sc, float scene_term)
+    {
+        thr = mk(h.x + (scene_term + (fabsf(c.x) + h.x) * kOverlapQuery), h.y + (scene_term + (fabsf(c.y) + h.y) * kOverlapQuery),
+                 h.z + (scene_term + (fabsf(c.z) + h.z) * kOverlapQuery));
+        qc = mk(c.x - sc.hspace.cx, c.y - sc.hspace.cy, c.z - sc.hspace.cz);
+    }
+    __device__ __forceinline__ bool admit_hc(uint32_t px, uint32_t py, uint32_t pz, const HSpace& hs) const { return child_admitted_hc(px, py, pz, qc, hs, thr); }
+    __device__ __forceinline__ bool admit_f32(float lx, float ly, float lz, float hx, float hy, float hz) const { return child_admitted_f32(c, lx, ly, lz, hx, hy, hz, thr); }
+    __device__ __forceinline__ bool accept(const f3& v0, const f3& e1, const f3& e2) const { return tri_box_overlap(c, h, v0, e1, e2); }
+};
+
+struct TriQuery {
+    f3 a0, f1, f2, qlo, qhi, thr, qc;
+    __device__ __forceinline__ bool load(const float4* __restrict__ tris, uint32_t i, uint32_t n)
+    {
+        f3 a1 = mk(0.0f), a2 = mk(0.0f);
+        a0 = mk(0.0f);
+        bool ok = false;
+        if (i < n) {
+            const float4 r0 = tris[3ull * i], r1 = tris[3ull * i + 1ull], r2 = tris[3ull * i + 2ull];
+            a0 = mk(r0.x, r0.y, r0.z);
+            a1 = mk(r1.x, r1.y, r1.z);
+            a2 = mk(r2.x, r2.y, r2.z);
+            ok = __builtin_isfinite(r0.x) && __builtin_isfinite(r0.y) && __builtin_isfinite(r0.z) && __builtin_isfinite(r1.x) && __builtin_isfinite(r1.y) &&
+                 __builtin_isfinite(r1.z) && __builtin_isfinite(r2.x) && __builtin_isfinite(r2.y) && __builtin_isfinite(r2.z);
+        }
+        qlo = mk(fmin3(a0.x, a1.x, a2.x), fmin3(a0.y, a1.y, a2.y), fmin3(a0.z, a1.z, a2.z));
+        qhi = mk(fmax3(a0.x, a1.x, a2.x), fmax3(a0.y, a1.y, a2.y), fmax3(a0.z, a1.z, a2.z));
+        f1 = a1 - a0;
+        f2 = a2 - a0;
+        return ok;
+    }
+    __device__ __forceinline__ void prepare(const DeviceScene& sc, float scene_term)
+    {
+        // FMT 11 only: the query box as centre and half extent (the halves are exact, the sum and the difference round once each)
+        const f3 c = mk(0.5f * qlo.x + 0.5f * qhi.x, 0.5f * qlo.y + 0.5f * qhi.y, 0.5f * qlo.z + 0.5f * qhi.z);
+        const f3 h = mk(0.5f * qhi.x - 0.5f * qlo.x, 0.5f * qhi.y - 0.5f * qlo.y, 0.5f * qhi.z - 0.5f * qlo.z);
+        thr = mk(h.x + (scene_term + (fabsf(c.x) + h.x) * kOverlapQuery), h.y + (scene_term + (fabsf(c.y) + h.y) * kOverlapQuery),
+                 h.z + (scene_term + (fabsf(c.z) + h.z) * kOverlapQuery));
+        qc = mk(c.x - sc.hspace.cx, c.y - sc.hspace.cy, c.z - sc.hspace.cz);
+    }
+    __device__ __forceinline__ bool admit_hc(uint32_t px, uint32_t py, uint32_t pz, const HSpace& hs) const { return child_admitted_hc(px, py, pz, qc, hs, thr); }
+    __device__ __forceinline__ bool admit_f32(float lx, float ly, float lz, float hx, float hy, float hz) const { return child_admitted_f32(qlo, qhi, lx, ly, lz, hx, hy, hz); }
+    __device__ __forceinline__ bool accept(const f3& v0, const f3& e1, const f3& e2) const { return tri_tri_intersect(a0, f1, f2, qlo, qhi, v0, e1, e2); }
+};
+
+// ---- the fill ----------------------------------------------------------------------------------------------------------------------
+// traverse_overlap's walk (overlap.hip says why max_depth + 1 stack entries suffice): of two admitted children the first is entered and
+// the second pushed; a popped reference is entered without a second look at its own box.  Which triangles are accepted is decided by
+// q.accept alone, so the set does not depend on the tree; the order of a long slice does, until k_sort_lists has run.
+// REG: kListRegister, or 0 for the measurement without the register list (every slice stored as the walk finds it).
+template <int FMT, class Q, uint32_t REG>
+__global__ void __launch_bounds__(256)
+k_fill_lists(const DeviceScene sc, uint32_t stack_entries, float scene_term, const float4* __restrict__ recs, uint32_t n, const uint32_t* __restrict__ offsets,
+             uint32_t* prims, uint32_t capacity, uint32_t* __restrict__ found, uint32_t* __restrict__ flag)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;      // n <= 2^31 - 1: the grid's last lane is below 2^31 + 255
+    LaneStack st;
+    st.base = lists_lds + (threadIdx.x >> 6) * (stack_entries * 64u) + (threadIdx.x & 63u);
+    Q q;
+    const bool active = q.load(recs, i, n);
+    q.prepare(sc, scene_term);
+    // the slice: m words from lo, or none where the offsets do not describe a slice inside prims
+    uint32_t lo = 0u, m = 0u;
+    bool fits = false;
+    if (i < n) {
+        lo = offsets[i];
+        const uint32_t hi = offsets[(size_t)i + 1u];
+        fits = lo <= hi && hi <= capacity;
+        m = fits ? hi - lo : 0u;
+    }
+    uint32_t* out = prims + lo;                 // read or written at j < m only: m == 0 where prims is null (capacity == 0)
+    const bool in_regs = m <= REG;
+    PrimList<kListRegister> L;
+#pragma unroll
+    for (uint32_t j = 0; j < kListRegister; j++) L.prim[j] = 0xFFFFFFFFu;
+    uint32_t count = 0u;
+    int sp = 0;
+    int node = (active && sc.n_tris != 0u) ? 0 : kSentinel;
+    while (node != kSentinel) {
+        if (node >= 0) {
+            bool h0, h1;
+            int c0, c1;
+            if (FMT == 11) {
+                // child references of inner nodes are byte offsets into hcnodes; a leaf is ~slot
+                const uint4* np = (const uint4*)((const char*)sc.hcnodes + (size_t)(uint32_t)node);
+                const uint4 qa = np[0], qb = np[1];
+                h0 = q.admit_hc(qa.x, qa.y, qa.z, sc.hspace);
+                h1 = q.admit_hc(qb.x, qb.y, qb.z, sc.hspace);
+                c0 = (int)qa.w; c1 = (int)qb.w;
+            } else {
+                // child 0: lo (a.x a.y a.z) hi (a.w b.x b.y); child 1: lo (b.z b.w c.x) hi (c.y c.z c.w)
+                const BvhNode* np = sc.nodes + node;
+                const float4 a = np->a, b = np->b, cc = np->c;
+                const int4 ch = np->d;
+                h0 = q.admit_f32(a.x, a.y, a.z, a.w, b.x, b.y);
+                h1 = q.admit_f32(b.z, b.w, cc.x, cc.y, cc.z, cc.w);
+                c0 = ch.x; c1 = ch.y;
+            }
+            if (h0 && h1) {
+                st.push(sp, c1);
+                sp++;
+                node = c0;
+            } else if (h0) {
+                node = c0;
+            } else if (h1) {
+                node = c1;
+            } else {
+                if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
+            }
+        } else {
+            const int slot = ~node;
+            const TriRecord* tp = sc.tris + slot;
+            const float4 r0 = tp->r0, r1 = tp->r1, r2 = tp->r2;
+            if (q.accept(mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x))) {
+                const uint32_t prim = __float_as_uint(r2.y);
+                if (in_regs) list_insert(L, kListRegister, prim);
+                else if (count < m) out[count] = prim;
+                count++;
+            }
+            if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
+        }
+    }
+    if (i >= n) return;
+    if (found) found[i] = count;
+    if (!fits || count > m) *flag = 1u;         // every writer stores the same word
+    if (in_regs) {
+#pragma unroll 1
+        for (uint32_t j = 0; j < m; j++) {
+            // the next word is entry 0; the rest move down one, so that no index depends on j.  Behind the indices: 0xFFFFFFFF
+            out[j] = L.prim[0];
+#pragma unroll
+            for (uint32_t k = 0; k + 1u < kListRegister; k++) L.prim[k] = L.prim[k + 1u];
+            L.prim[kListRegister - 1u] = 0xFFFFFFFFu;
+        }
+    } else {
+#pragma unroll 1
+        for (uint32_t j = count; j < m; j++) out[j] = 0xFFFFFFFFu;
+    }
+}
+
+// ---- the sort ----------------------------------------------------------------------------------------------------------------------
+// One compare-exchange: the larger word goes to the higher index.  i < l always; a comparator whose upper index is past the end is
+// skipped, which is what the network does with a list padded by words larger than all.
+__device__ __forceinline__ void compare_exchange(uint32_t* a, uint32_t i, uint32_t l, uint32_t m)
+{
+    if (l < m) {
+        const uint32_t x = a[i], y = a[l];
+        if (x > y) { a[i] = y; a[l] = x; }
+    }
+}
+
+// All 256 lanes sort a[0 .. m) ascending, m >= 2.  levels = ceil(log2 m); every step has 2^(levels - 1) comparators, dealt to the lanes
+// round robin, and a workgroup barrier behind it.  Level kb merges sorted blocks of 2^(kb - 1) into blocks of 2^kb: its first step
+// compares word r of a block with word 2^kb - 1 - r, the steps after it words 2^jb apart, jb = kb - 2 .. 0.  Index arithmetic stays
+// below 2^32 for every m a 32-bit offset can describe.
+__device__ __forceinline__ void bitonic_sort(uint32_t* a, uint32_t m)
+{
+    const uint32_t levels = 32u - (uint32_t)__builtin_clz(m - 1u);
+    const uint32_t half = 1u << (levels - 1u);
+#pragma unroll 1
+    for (uint32_t kb = 1u; kb <= levels; kb++) {
+        const uint32_t flip = (2u << (kb - 1u)) - 1u;
+#pragma unroll 1
+        for (uint32_t t = threadIdx.x; t < half; t += 256u) {
+            const uint32_t i = ((t >> (kb - 1u)) << (kb - 1u) << 1) + (t & (flip >> 1));
+            compare_exchange(a, i, i ^ flip, m);
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (uint32_t jb = kb - 1u; jb-- != 0u;) {
+            const uint32_t j = 1u << jb;
+#pragma unroll 1
+            for (uint32_t t = threadIdx.x; t < half; t += 256u) {
+                const uint32_t i = ((t >> jb) << jb << 1) + (t & (j - 1u));
+                compare_exchange(a, i, i + j, m);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_sort_lists(const uint32_t* __restrict__ offsets, uint32_t n, uint32_t* prims, uint32_t capacity, uint32_t sorted_up_to)
+{
+    __shared__ uint32_t keys[kListSortLds];
+    __shared__ u64 wanted[4];
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool want = false;
+    if (i < n) {
+        const uint32_t lo = offsets[i], hi = offsets[(size_t)i + 1u];
+        want = lo <= hi && hi <= capacity && hi - lo > sorted_up_to;      // the slices k_fill_lists stored in walk order
+    }
+    const u64 mask = vote(want);
+    if ((threadIdx.x & 63u) == 0u) wanted[threadIdx.x >> 6] = mask;
+    __syncthreads();
+    // every lane reads the same four masks, so the loops and the barriers inside them are uniform over the workgroup
+#pragma unroll 1
+    for (uint32_t w = 0; w < 4u; w++) {
+        u64 left = wanted[w];
+#pragma unroll 1
+        while (left != 0ull) {
+            const uint32_t b = (uint32_t)__builtin_ctzll(left);
+            left &= left - 1ull;
+            const size_t qi = (size_t)blockIdx.x * 256u + w * 64u + b;
+            const uint32_t lo = offsets[qi], m = offsets[qi + 1u] - lo;
+            uint32_t* a = prims + lo;
+            if (m <= kListSortLds) {
+                for (uint32_t t = threadIdx.x; t < m; t += 256u) keys[t] = a[t];
+                __syncthreads();
+                bitonic_sort(keys, m);
+                for (uint32_t t = threadIdx.x; t < m; t += 256u) a[t] = keys[t];
+                __syncthreads();
+            } else {
+                bitonic_sort(a, m);
+            }
+        }
+    }
+}
+
+template <int FMT, class Q, uint32_t REG>
+static hipError_t launch_fill(const DeviceScene& sc, uint32_t stack_entries, float scene_term, const float4* recs, uint32_t n, const uint32_t* offsets,
+                              uint32_t* prims, uint32_t capacity, uint32_t* found, uint32_t* flag, uint32_t phases, hipStream_t stream)
+{
+    if (phases & kListPhaseFill) {
+        const size_t lds = (size_t)(256 / 64) * stack_entries * 64u * sizeof(uint32_t);
+        auto kernel = k_fill_lists<FMT, Q, REG>;
+        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        kernel<<<(n + 255u) / 256u, 256, lds, stream>>>(sc, stack_entries, scene_term, recs, n, offsets, prims, capacity, found, flag);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    // a slice of one word is sorted as it is
+    if (phases & kListPhaseSort) k_sort_lists<<<(n + 255u) / 256u, 256, 0, stream>>>(offsets, n, prims, capacity, REG ? REG : 1u);
+    return hipGetLastError();
+}
+
+template <int FMT, class Q>
+static hipError_t launch_fill_phases(const DeviceScene& sc, uint32_t stack_entries, float scene_term, const float4* recs, uint32_t n, const uint32_t* offsets,
+                                     uint32_t* prims, uint32_t capacity, uint32_t* found, uint32_t* flag, uint32_t phases, hipStream_t stream)
+{
+    if (phases & kListPhaseNoRegisters) return launch_fill<FMT, Q, 0u>(sc, stack_entries, scene_term, recs, n, offsets, prims, capacity, found, flag, phases, stream);
+    return launch_fill<FMT, Q, kListRegister>(sc, stack_entries, scene_term, recs, n, offsets, prims, capacity, found, flag, phases, stream);
+}
+
+hipError_t launch_overlap_lists(int fmt, const DeviceScene& sc, uint32_t stack_entries, float scene_term, const float4* boxes, uint32_t n, const uint32_t* offsets,
+                                uint32_t* prims, uint32_t capacity, uint32_t* found, uint32_t* flag, uint32_t phases, hipStream_t stream)
+{
+    if (n == 0u || n > 0x7FFFFFFFu || (!prims && capacity != 0u)) return hipErrorInvalidValue;
+    if (fmt == 11) return launch_fill_phases<11, BoxQuery>(sc, stack_entries, scene_term, boxes, n, offsets, prims, capacity, found, flag, phases, stream);
+    return launch_fill_phases<0, BoxQuery>(sc, stack_entries, scene_term, boxes, n, offsets, prims, capacity, found, flag, phases, stream);
+}
+
+hipError_t launch_triangles_lists(int fmt, const DeviceScene& sc, uint32_t stack_entries, float scene_term, const float4* tris, uint32_t n, const uint32_t* offsets,
+                                  uint32_t* prims, uint32_t capacity, uint32_t* found, uint32_t* flag, uint32_t phases, hipStream_t stream)
+{
+    if (n == 0u || n > 0x7FFFFFFFu || (!prims && capacity != 0u)) return hipErrorInvalidValue;
+    if (fmt == 11) return launch_fill_phases<11, TriQuery>(sc, stack_entries, scene_term, tris, n, offsets, prims, capacity, found, flag, phases, stream);
+    return launch_fill_phases<0, TriQuery>(sc, stack_entries, scene_term, tris, n, offsets, prims, capacity, found, flag, phases, stream);
+}
+
+}  // namespace ptd

@@ -17,6 +17,7 @@
 // mirrors it operation for operation.  The child boxes of the fp16 nodes are outside that contract (they only prune) and use explicit
 // fused multiply-adds.
 #include "tritri.h"
+#include "tritri_device.h"
 
 namespace ptd {
 
@@ -24,99 +25,8 @@ extern __shared__ uint32_t tritri_lds[];
 
 enum { kList = 0, kAny = 1, kVisits = 2 };
 
-__device__ __forceinline__ float fmin3(float a, float b, float c) { return fminf(fminf(a, b), c); }
-__device__ __forceinline__ float fmax3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-
-// One separating axis L in keep form.  The scene triangle's vertices relative to a0 are p0, p1, p2; the query triangle's are 0, f1, f2.
-// Three NaN s fail the condition; a NaN t is ignored by fmin3 / fmax3, which always have the 0 to return.
-__device__ __forceinline__ bool axis_keeps(const f3& L, const f3& p0, const f3& p1, const f3& p2, const f3& f1, const f3& f2)
-{
-    const float s0 = dot(L, p0), s1 = dot(L, p1), s2 = dot(L, p2);
-    const float t1 = dot(L, f1), t2 = dot(L, f2);
-    return (fmin3(s0, s1, s2) <= fmax3(0.0f, t1, t2)) & (fmax3(s0, s1, s2) >= fmin3(0.0f, t1, t2));
-}
-
-// The running conjunction of the conditions, kept in a vector register and closed after every axis.  Left to itself the compiler keeps
-// all 40 lane masks in scalar registers and combines them at the end: 106 SGPRs, with kernel arguments spilled to make room, and 20
-// more VGPRs for the axes it computes ahead.  The empty statement pins the select; the barrier keeps the next axis from starting early.
-__device__ __forceinline__ void fold(uint32_t& keep, bool c)
-{
-    keep = c ? keep : 0u;
-    asm volatile("" : "+v"(keep));
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-// The three axes cross(a, b) of one edge a of the query triangle against the scene triangle's edges b in (e1, e2 - e1, e2)
-__device__ __forceinline__ bool edge_keeps(const f3& a, const f3& e1, const f3& e21, const f3& e2, const f3& p0, const f3& p1, const f3& p2, const f3& f1, const f3& f2)
-{
-    return axis_keeps(cross(a, e1), p0, p1, p2, f1, f2) & axis_keeps(cross(a, e21), p0, p1, p2, f1, f2) & axis_keeps(cross(a, e2), p0, p1, p2, f1, f2);
-}
-
-// Does the scene triangle {v0, v0 + e1, v0 + e2} intersect the query triangle {a0, a0 + f1, a0 + f2}, whose bounding box is [qlo, qhi]:
-// the separating-axis test in keep form, on the record's own vectors.  Three box conditions on the coordinates as they are, then 17
-// axes: the two normals, the nine products of an edge of each, and per triangle the three in-plane normals of its edges, without which
-// two coplanar triangles always intersect.  The 20 conditions are closed (touching intersects) and combined without a branch, so a
-// wave's lanes run one instruction stream.
-__device__ __forceinline__ bool tri_tri_intersect(const f3& a0, const f3& f1, const f3& f2, const f3& qlo, const f3& qhi, const f3& v0, const f3& e1, const f3& e2)
-{
-    const f3 w1 = v0 + e1, w2 = v0 + e2;
-    const bool boxes = (fmin3(v0.x, w1.x, w2.x) <= qhi.x) & (fmax3(v0.x, w1.x, w2.x) >= qlo.x) &
-                       (fmin3(v0.y, w1.y, w2.y) <= qhi.y) & (fmax3(v0.y, w1.y, w2.y) >= qlo.y) &
-                       (fmin3(v0.z, w1.z, w2.z) <= qhi.z) & (fmax3(v0.z, w1.z, w2.z) >= qlo.z);
-    const f3 p0 = v0 - a0, p1 = p0 + e1, p2 = p0 + e2;
-    const f3 f21 = f2 - f1, e21 = e2 - e1;
-    const f3 nA = cross(f1, f2), nB = cross(e1, e2);
-    uint32_t keep = boxes ? 1u : 0u;
-    fold(keep, axis_keeps(nA, p0, p1, p2, f1, f2));
-    fold(keep, axis_keeps(nB, p0, p1, p2, f1, f2));
-    fold(keep, edge_keeps(f1, e1, e21, e2, p0, p1, p2, f1, f2));
-    fold(keep, edge_keeps(f21, e1, e21, e2, p0, p1, p2, f1, f2));
-    fold(keep, edge_keeps(f2, e1, e21, e2, p0, p1, p2, f1, f2));
-    fold(keep, axis_keeps(cross(nA, f1), p0, p1, p2, f1, f2));
-    fold(keep, axis_keeps(cross(nA, f21), p0, p1, p2, f1, f2));
-    fold(keep, axis_keeps(cross(nA, f2), p0, p1, p2, f1, f2));
-    fold(keep, axis_keeps(cross(nB, e1), p0, p1, p2, f1, f2));
-    fold(keep, axis_keeps(cross(nB, e21), p0, p1, p2, f1, f2));
-    fold(keep, axis_keeps(cross(nB, e2), p0, p1, p2, f1, f2));
-    return keep != 0u;
-}
-
-// FMT 11, overlap.hip's child_admitted_hc: the per-axis gap between the query box's centre and one child box through HSpace, two
-// v_fma_mix_f32 and a max per axis; NaN for an empty child (g_h < 0), which no compare admits.  qc = c - centre of HSpace.
-__device__ __forceinline__ bool child_admitted_hc(uint32_t px, uint32_t py, uint32_t pz, const f3& qc, const HSpace& hs, const f3& thr)
-{
-    const half2_t hx = __builtin_bit_cast(half2_t, px), hy = __builtin_bit_cast(half2_t, py), hz = __builtin_bit_cast(half2_t, pz);
-    const float tx = __builtin_fmaf((float)hx.x, hs.isx, -qc.x), ty = __builtin_fmaf((float)hy.x, hs.isy, -qc.y), tz = __builtin_fmaf((float)hz.x, hs.isz, -qc.z);
-    float ex = fmaxf(__builtin_fmaf((float)hx.y, -hs.isx, fabsf(tx)), 0.0f);
-    const float ey = fmaxf(__builtin_fmaf((float)hy.y, -hs.isy, fabsf(ty)), 0.0f);
-    const float ez = fmaxf(__builtin_fmaf((float)hz.y, -hs.isz, fabsf(tz)), 0.0f);
-    ex = (float)hx.y < 0.0f ? __builtin_nanf("") : ex;
-    return (ex <= thr.x) & (ey <= thr.y) & (ez <= thr.z);
-}
-// FMT 0: the child's planes against the query box's, as they are.  An empty child has lo = +inf, which no finite qhi admits.
-__device__ __forceinline__ bool child_admitted_f32(const f3& qlo, const f3& qhi, float lx, float ly, float lz, float hx, float hy, float hz)
-{
-    return (lx <= qhi.x) & (hx >= qlo.x) & (ly <= qhi.y) & (hy >= qlo.y) & (lz <= qhi.z) & (hz >= qlo.z);
-}
-
-// overlap.hip's list: the lane's lowest triangle indices so far, ascending.  An empty entry is 0xFFFFFFFF, which is no triangle's
-// index and sorts behind every one.  N = 0 leaves nothing behind.
-template <int N>
-struct PrimList { uint32_t prim[N ? N : 1]; };
-
-// Insert prim among the first max_prims entries; what falls off the end is dropped.  Every triangle sits in one leaf, so no index
-// comes twice.
-template <int N>
-__device__ __forceinline__ void list_insert(PrimList<N>& L, uint32_t max_prims, uint32_t prim)
-{
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        const uint32_t lp = L.prim[j];
-        const bool sw = (uint32_t)j < max_prims && prim < lp;
-        L.prim[j] = sw ? prim : lp;
-        prim = sw ? lp : prim;
-    }
-}
+// axis_keeps, fold, tri_tri_intersect, the child-box admission of both formats and the sorted register list: tritri_device.h,
+// which lists.hip shares.
 
 // One query triangle per lane through the two-child BVH, as traverse_overlap walks a box: of two admitted children the first is
 // entered and the second pushed, so a visit pushes at most one reference per level and max_depth + 1 stack entries suffice; a popped

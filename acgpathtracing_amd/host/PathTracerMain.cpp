@@ -16,7 +16,7 @@
 //              [--tonemap linear|reinhard|aces] [--exposure auto|<EV>] [--out-hdr file.pfm]
 //              [--until-error E [--until-permille P] [--error-floor F] [--error-out file.pfm]]
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
-//              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k] ...] [--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k] ...]
+//              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k|,all] ...] [--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k|,all] ...]
 //              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...] [--clearance x0,y0,z0,x1,y1,z1[,radius] ...]
 //              [--tri-distance x0,y0,z0,x1,y1,z1,x2,y2,z2[,radius] ...]
 //              [--nearest-k x,y,z,k[,radius] ...] [--within x,y,z,radius ...] [--winding x,y,z[,beta] ...]
@@ -58,11 +58,14 @@
 // axis-aligned box of centre (cx, cy, cz) and half extent (hx, hy, hz), by pt_query_overlap in one call per k, one JSON line each:
 // {"overlap": [cx, cy, cz, hx, hy, hz], "count": <triangles that overlap the box>, "triangles": [<the k lowest indices among them,
 // k = 0..8, default 8>], "materials": ["<newmtl name>" per listed triangle]}.  A value that is not finite, a negative half extent or a
-// k outside 0..8 is refused with exit status 2.  The frames are the same with or without it.
+// k outside 0..8 is refused with exit status 2.  The frames are the same with or without it.  With "all" in place of k the line is the
+// same and "triangles" holds every overlapping triangle, ascending: pt_query_overlap counts, pt_list_offsets makes the offsets,
+// pt_query_overlap_lists fills the list.
 // --intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k] (repeatable): once the scene is set and before the first frame, the scene triangles that
 // intersect the triangle of these three vertices, by pt_query_triangles in one call per k, one JSON line each: {"intersect": [the nine
 // coordinates], "count": <scene triangles that intersect it>, "triangles": [<the k lowest indices among them, k = 0..8, default 8>]}.
 // A coordinate that is not finite or a k outside 0..8 is refused with exit status 2.  The frames are the same with or without it.
+// "all" in place of k lists every intersecting scene triangle, through pt_query_triangles_lists as --overlap does.
 // --sweep ox,oy,oz,dx,dy,dz,r[,tmax] (repeatable): once the scene is set and before the first frame, how far the sphere of radius r
 // whose centre starts at o travels along d before it touches the scene (t in units of |d|, at most tmax, default unbounded), all in
 // one call of pt_query_sweep, one JSON line each: {"sweep": [ox, oy, oz, dx, dy, dz, r], "tmax": <tmax or null>, "hit": true, "t": ...,
@@ -729,6 +732,43 @@ static void pickAllPixels(PathTracerState& state, const TinyObjWrapper& obj, con
     fflush(stdout);
 }
 
+// The complete lists of m records of rec_bytes each, for --overlap / --intersect with "all": the counts, pt_list_offsets, the
+// allocation, the fill.  Returns the error, or an empty string with offsets (m + 1) and prims (offsets[m]) filled.
+static const uint32_t kListAll = 9u;      // the k that stands for "all"
+static bool wantsAll(std::string& text)
+{
+    if (text.size() < 4 || text.compare(text.size() - 4, 4, ",all") != 0) return false;
+    text.resize(text.size() - 4);
+    return true;
+}
+static std::string completeLists(PathTracerState& state, const std::vector<float>& recs, size_t m, size_t rec_bytes,
+                                 int (*count)(pt_ctx*, const float*, size_t, uint32_t, uint32_t*, uint32_t*),
+                                 int (*fill)(pt_ctx*, const float*, size_t, const uint32_t*, uint32_t*, size_t, uint32_t*),
+                                 std::vector<uint32_t>& offsets, std::vector<uint32_t>& prims)
+{
+    void* d_recs = nullptr; void* d_counts = nullptr; void* d_offsets = nullptr; void* d_prims = nullptr;
+    uint64_t total = 0;
+    offsets.assign(m + 1, 0u);
+    std::string err;
+    if (pt_device_malloc(state.context, &d_recs, m * rec_bytes) != 0 || pt_device_malloc(state.context, &d_counts, m * 4) != 0 ||
+        pt_device_malloc(state.context, &d_offsets, (m + 1) * 4) != 0 || pt_copy_to_device(state.context, d_recs, recs.data(), m * rec_bytes) != 0 ||
+        count(state.context, (const float*)d_recs, m, 0u, nullptr, (uint32_t*)d_counts) != 0 ||
+        pt_list_offsets(state.context, (const uint32_t*)d_counts, m, (uint32_t*)d_offsets, &total) != 0 ||
+        pt_copy_to_host(state.context, offsets.data(), d_offsets, (m + 1) * 4) != 0)
+        err = pt_last_error(state.context);
+    prims.assign(err.empty() ? (size_t)total : 0u, 0xFFFFFFFFu);
+    if (err.empty() &&
+        ((total != 0 && pt_device_malloc(state.context, &d_prims, (size_t)total * 4) != 0) ||
+         fill(state.context, (const float*)d_recs, m, (const uint32_t*)d_offsets, (uint32_t*)d_prims, (size_t)total, nullptr) != 0 ||
+         (total != 0 && pt_copy_to_host(state.context, prims.data(), d_prims, (size_t)total * 4) != 0)))
+        err = pt_last_error(state.context);
+    if (d_recs) pt_device_free(state.context, d_recs);
+    if (d_counts) pt_device_free(state.context, d_counts);
+    if (d_offsets) pt_device_free(state.context, d_offsets);
+    if (d_prims) pt_device_free(state.context, d_prims);
+    return err;
+}
+
 // --overlap: the boxes of one k in one call of pt_query_overlap; one JSON line per box, in the order given
 struct OverlapBox { float v[8]; uint32_t k; };
 static void overlapBoxes(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<OverlapBox>& boxes)
@@ -761,6 +801,23 @@ static void overlapBoxes(PathTracerState& state, const TinyObjWrapper& obj, cons
             for (uint32_t e = 0; e < k; e++) prims[which[j] * 8 + e] = p[j * k + e];
         }
     }
+    // the boxes that ask for every triangle: their complete lists, box by box
+    std::vector<std::vector<uint32_t> > whole(n);
+    {
+        std::vector<size_t> which;
+        std::vector<float> recs;
+        for (size_t i = 0; i < n; i++)
+            if (boxes[i].k == kListAll) { which.push_back(i); recs.insert(recs.end(), boxes[i].v, boxes[i].v + 8); }
+        if (!which.empty()) {
+            std::vector<uint32_t> offsets, all;
+            const std::string err = completeLists(state, recs, which.size(), 32, pt_query_overlap, pt_query_overlap_lists, offsets, all);
+            if (!err.empty()) throw Exception("overlap: " + err);
+            for (size_t j = 0; j < which.size(); j++) {
+                whole[which[j]].assign(all.begin() + offsets[j], all.begin() + offsets[j + 1]);
+                counts[which[j]] = offsets[j + 1] - offsets[j];
+            }
+        }
+    }
     const std::vector<std::string>& names = obj.getMaterialNames();
     const std::vector<uint32_t> mats = obj.getMaterialIndices();
     for (size_t i = 0; i < n; i++) {
@@ -768,8 +825,9 @@ static void overlapBoxes(PathTracerState& state, const TinyObjWrapper& obj, cons
         printf("{\"overlap\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"count\": %u, \"triangles\": [", b[0], b[1], b[2], b[3], b[4], b[5], counts[i]);
         std::string mat_list;
         bool first = true;
-        for (uint32_t e = 0; e < boxes[i].k; e++) {
-            const uint32_t t = prims[i * 8 + e];
+        const bool all = boxes[i].k == kListAll;
+        for (uint32_t e = 0; e < (all ? (uint32_t)whole[i].size() : boxes[i].k); e++) {
+            const uint32_t t = all ? whole[i][e] : prims[i * 8 + e];
             if (t == 0xFFFFFFFFu) break;
             const uint32_t id = t < mats.size() ? mats[t] : 0xFFFFFFFFu;
             std::string name = id < names.size() ? names[id] : std::string();
@@ -815,11 +873,31 @@ static void intersectTriangles(PathTracerState& state, const std::vector<Interse
             for (uint32_t e = 0; e < k; e++) prims[which[j] * 8 + e] = p[j * k + e];
         }
     }
+    // the triangles that ask for every scene triangle: their complete lists
+    std::vector<std::vector<uint32_t> > whole(n);
+    {
+        std::vector<size_t> which;
+        std::vector<float> recs;
+        for (size_t i = 0; i < n; i++)
+            if (tris[i].k == kListAll) { which.push_back(i); recs.insert(recs.end(), tris[i].v, tris[i].v + 12); }
+        if (!which.empty()) {
+            std::vector<uint32_t> offsets, all;
+            const std::string err = completeLists(state, recs, which.size(), 48, pt_query_triangles, pt_query_triangles_lists, offsets, all);
+            if (!err.empty()) throw Exception("intersect: " + err);
+            for (size_t j = 0; j < which.size(); j++) {
+                whole[which[j]].assign(all.begin() + offsets[j], all.begin() + offsets[j + 1]);
+                counts[which[j]] = offsets[j + 1] - offsets[j];
+            }
+        }
+    }
     for (size_t i = 0; i < n; i++) {
         const float* a = tris[i].v;
         printf("{\"intersect\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"count\": %u, \"triangles\": [", a[0], a[1], a[2], a[4], a[5], a[6], a[8],
                a[9], a[10], counts[i]);
-        for (uint32_t e = 0; e < tris[i].k && prims[i * 8 + e] != 0xFFFFFFFFu; e++) printf("%s%u", e ? ", " : "", prims[i * 8 + e]);
+        if (tris[i].k == kListAll)
+            for (size_t e = 0; e < whole[i].size(); e++) printf("%s%u", e ? ", " : "", whole[i][e]);
+        else
+            for (uint32_t e = 0; e < tris[i].k && prims[i * 8 + e] != 0xFFFFFFFFu; e++) printf("%s%u", e ? ", " : "", prims[i * 8 + e]);
         printf("]}\n");
     }
     fflush(stdout);
@@ -1263,10 +1341,13 @@ int main(int argc, char** argv)
         else if (a == "--overlap") {
             OverlapBox b = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, 8u};
             int k = 8;
-            const int got = sscanf(next(), "%f,%f,%f,%f,%f,%f,%d", &b.v[0], &b.v[1], &b.v[2], &b.v[3], &b.v[4], &b.v[5], &k);
-            bool ok = got >= 6 && k >= 0 && k <= 8;
+            std::string text = next();
+            const bool all = wantsAll(text);
+            const int got = sscanf(text.c_str(), "%f,%f,%f,%f,%f,%f,%d", &b.v[0], &b.v[1], &b.v[2], &b.v[3], &b.v[4], &b.v[5], &k);
+            bool ok = (all ? got == 6 : got >= 6) && k >= 0 && k <= 8;
+            if (all) k = (int)kListAll;
             for (int j = 0; j < 6; j++) ok = ok && std::isfinite(b.v[j]) && (j < 3 || b.v[j] >= 0.0f);
-            if (!ok) { std::cerr << "--overlap cx,cy,cz,hx,hy,hz[,k]: finite values, half extents >= 0, k = 0..8" << std::endl; return 2; }
+            if (!ok) { std::cerr << "--overlap cx,cy,cz,hx,hy,hz[,k]: finite values, half extents >= 0, k = 0..8 or all" << std::endl; return 2; }
             b.k = (uint32_t)k;
             overlaps.push_back(b);
         }
@@ -1274,10 +1355,13 @@ int main(int argc, char** argv)
             IntersectTri t = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, 8u};
             int k = 8;
             float* v = t.v;
-            const int got = sscanf(next(), "%f,%f,%f,%f,%f,%f,%f,%f,%f,%d", &v[0], &v[1], &v[2], &v[4], &v[5], &v[6], &v[8], &v[9], &v[10], &k);
-            bool ok = got >= 9 && k >= 0 && k <= 8;
+            std::string text = next();
+            const bool all = wantsAll(text);
+            const int got = sscanf(text.c_str(), "%f,%f,%f,%f,%f,%f,%f,%f,%f,%d", &v[0], &v[1], &v[2], &v[4], &v[5], &v[6], &v[8], &v[9], &v[10], &k);
+            bool ok = (all ? got == 9 : got >= 9) && k >= 0 && k <= 8;
+            if (all) k = (int)kListAll;
             for (int j = 0; j < 12; j++) ok = ok && std::isfinite(v[j]);
-            if (!ok) { std::cerr << "--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k]: finite coordinates, k = 0..8" << std::endl; return 2; }
+            if (!ok) { std::cerr << "--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k]: finite coordinates, k = 0..8 or all" << std::endl; return 2; }
             t.k = (uint32_t)k;
             intersects.push_back(t);
         }

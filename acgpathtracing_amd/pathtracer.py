@@ -1599,6 +1599,94 @@ def queryTrianglesAny(state, triangles):
     return out.view(np.bool_)
 
 
+# ------------------------------------------------------------------ complete lists in CSR form ----
+def _list_total(state, what, d_counts, n, d_offsets):
+    """pt_list_offsets on device pointers: the total, or PathTracerError where it does not fit 32-bit offsets"""
+    L = _native.hip()
+    total = C.c_uint64(0)
+    rc = L.pt_list_offsets(state.context, d_counts, n, d_offsets, C.byref(total))
+    if rc != 0 and total.value > 0xFFFFFFFF:
+        raise PathTracerError("%s: the lists hold %d indices in all, more than 32-bit offsets describe (2^32 - 1): split the batch into "
+                              "several calls" % (what, total.value))
+    _check(state.context, rc, "pt_list_offsets")
+    return int(total.value)
+
+
+def _query_lists(what, state, recs, count_call, lists_call):
+    """The four steps on records that are an (n, w) float32 array or a device tensor: count, offsets, allocate, fill"""
+    L = _native.hip()
+    if _is_tensor(recs):
+        import torch
+        n = int(recs.shape[0])
+        with torch.cuda.device(recs.device):
+            cnt = torch.empty((n,), dtype=torch.int32, device=recs.device)
+            off = torch.zeros((n + 1,), dtype=torch.int32, device=recs.device)
+            torch.cuda.current_stream().synchronize()      # the records' producer and the allocations; every call below returns synchronised
+            total = 0
+            if n:
+                _check(state.context, count_call(state.context, recs.data_ptr(), n, 0, None, cnt.data_ptr()), what + " (counts)")
+                total = _list_total(state, what, cnt.data_ptr(), n, off.data_ptr())
+            prim = torch.empty((total,), dtype=torch.int32, device=recs.device)
+            torch.cuda.current_stream().synchronize()
+            if n:
+                _check(state.context, lists_call(state.context, recs.data_ptr(), n, off.data_ptr(), prim.data_ptr() if total else None, total, None), what)
+            return {"offsets": off.to(torch.int64) & 0xFFFFFFFF, "prim": prim, "count": cnt}
+    n = recs.shape[0]
+    cnt, off = np.zeros(n, np.uint32), np.zeros(n + 1, np.uint32)
+    prim = np.zeros(0, np.uint32)
+    if n:
+        bufs = _device_buffers(state, 1, recs.nbytes) + _device_buffers(state, 1, cnt.nbytes) + _device_buffers(state, 1, off.nbytes)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], recs.ctypes.data, recs.nbytes), "copy to device")
+            _check(state.context, count_call(state.context, bufs[0], n, 0, None, bufs[1]), what + " (counts)")
+            total = _list_total(state, what, bufs[1], n, bufs[2])
+            prim = np.zeros(total, np.uint32)
+            if total:
+                bufs += _device_buffers(state, 1, prim.nbytes)
+            _check(state.context, lists_call(state.context, bufs[0], n, bufs[2], bufs[3] if total else None, total, None), what)
+            _check(state.context, L.pt_copy_to_host(state.context, cnt.ctypes.data, bufs[1], cnt.nbytes), "copy to host")
+            _check(state.context, L.pt_copy_to_host(state.context, off.ctypes.data, bufs[2], off.nbytes), "copy to host")
+            if total:
+                _check(state.context, L.pt_copy_to_host(state.context, prim.ctypes.data, bufs[3], prim.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    return {"offsets": off, "prim": prim, "count": cnt}
+
+
+def queryOverlapLists(state, centres, half_extents=None):
+    """Every triangle of the scene on the GPU that overlaps each axis-aligned box, not the first 8 (include/acgpt.h
+    pt_query_overlap_lists): queryOverlap's boxes, and the lists in compressed-sparse-row form.  One call counts (pt_query_overlap with
+    max_prims = 0), pt_list_offsets turns the counts into offsets, the result is allocated, a second walk fills it.
+
+    Returns a dict: offsets (n + 1,), prim (offsets[n],) and count (n,).  Box i's triangles are prim[offsets[i]:offsets[i + 1]], in
+    the caller's index-buffer order, ascending, whatever tree the scene has; count[i] is their number.  NumPy input gives uint32
+    arrays.  A torch tensor — (n, 8) float32 records, contiguous, on the context's device — goes in by data_ptr() without a copy and
+    comes back as tensors allocated by torch on that device: prim and count int32, offsets int64.
+
+    Lists of more than 2^32 - 1 indices in all raise PathTracerError naming the total: split the batch."""
+    L = _native.hip()
+    if _is_tensor(centres):
+        _overlap_tensor("queryOverlapLists", state, centres, half_extents)
+        recs = centres
+    else:
+        recs = _overlap_boxes("queryOverlapLists", centres, half_extents)
+    return _query_lists("pt_query_overlap_lists", state, recs, L.pt_query_overlap, L.pt_query_overlap_lists)
+
+
+def queryTrianglesLists(state, triangles):
+    """Every triangle of the scene on the GPU that intersects each triangle of the caller's, not the first 8 (include/acgpt.h
+    pt_query_triangles_lists): queryTriangles' triangles, queryOverlapLists' result — a dict of offsets (n + 1,), prim (offsets[n],)
+    and count (n,), query i's scene triangles in prim[offsets[i]:offsets[i + 1]], ascending.  Arrays for arrays, tensors for an
+    (n, 12) float32 tensor on the context's device, which is not copied."""
+    L = _native.hip()
+    if _is_tensor(triangles):
+        _triangle_tensor("queryTrianglesLists", state, triangles)
+        recs = triangles
+    else:
+        recs = _triangle_records("queryTrianglesLists", triangles)
+    return _query_lists("pt_query_triangles_lists", state, recs, L.pt_query_triangles, L.pt_query_triangles_lists)
+
+
 def _posed_records(what, vertices, indices, poses):
     """(P, T, 12) float32 records of a mesh under P poses (poses None: the mesh as it is, P = 1).  Tensors in, a tensor out."""
     tensors = _is_tensor(vertices)
@@ -1663,10 +1751,23 @@ def meshCollisions(state, vertices, indices, poses=None, pairs=False):
     By default one queryTrianglesAny call over the P x T records, reduced per pose: a bool (P,), does the mesh in this pose touch the
     scene.  pairs=True asks queryTriangles instead and returns a dict: pairs (m, 3), the (pose, mesh triangle, scene triangle) triples
     of the lists, and counts (P, T), the number of scene triangles each mesh triangle intersects — where it is above 8 that triangle's
-    list was cut.  Arrays for arrays, tensors for tensors."""
+    list was cut.  pairs="all" goes through queryTrianglesLists and returns the same dict with every triple, none cut, ordered by pose, mesh
+    triangle and scene triangle.  Arrays for arrays, tensors for tensors."""
+    if isinstance(pairs, str) and pairs != "all":
+        raise PathTracerError("meshCollisions: pairs is False, True or \"all\", got %r" % (pairs,))
     rec = _posed_records("meshCollisions", vertices, indices, poses)
     P, T = int(rec.shape[0]), int(rec.shape[1])
     flat = rec.reshape(P * T, 12)
+    if isinstance(pairs, str):
+        got = queryTrianglesLists(state, flat)
+        if _is_tensor(got["prim"]):
+            import torch
+            row = torch.repeat_interleave(torch.arange(P * T, device=got["prim"].device), got["count"].to(torch.int64))
+            triples = torch.stack([row // max(T, 1), row % max(T, 1), got["prim"].to(torch.int64)], dim=1)
+        else:
+            row = np.repeat(np.arange(P * T, dtype=np.int64), got["count"].astype(np.int64))
+            triples = np.stack([row // max(T, 1), row % max(T, 1), got["prim"].astype(np.int64)], axis=1)
+        return {"pairs": triples, "counts": got["count"].reshape(P, T)}
     if not pairs:
         return queryTrianglesAny(state, flat).reshape(P, T).any(1)
     got = queryTriangles(state, flat, max_prims=_native.QUERY_TRIANGLES_MAX, counts=True)

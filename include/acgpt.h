@@ -583,6 +583,57 @@ int pt_query_overlap_any(pt_ctx* ctx, const float* boxes, size_t n, uint8_t* hit
 int pt_query_triangles(pt_ctx* ctx, const float* tris, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts);
 int pt_query_triangles_any(pt_ctx* ctx, const float* tris, size_t n, uint8_t* hit);
 
+/* ---- complete result lists in compressed-sparse-row form (opt-in; nothing above changes) --------------------------------------------
+ * pt_query_overlap and pt_query_triangles give a count and at most 8 indices.  These three calls give every index: a selection box,
+ * the narrow phase behind a broad phase, the triangles of each cell of a voxeliser.  The caller's sequence:
+ *     pt_query_overlap(ctx, boxes, n, 0, NULL, counts);                      the number per query (unchanged code)
+ *     pt_list_offsets(ctx, counts, n, offsets, &total);                      counts -> offsets
+ *     allocate total words;
+ *     pt_query_overlap_lists(ctx, boxes, n, offsets, prims, total, NULL);    query i's list is prims[offsets[i] .. offsets[i + 1])
+ * and the same with pt_query_triangles / pt_query_triangles_lists.  Nothing is allocated behind the caller's back but one small
+ * scratch buffer the context owns (the scan's tile sums and one flag word: 8 bytes per 2048 counts, grown on demand, freed by
+ * pt_destroy, not part of pt_bvh_info.device_bytes, which describes the scene).
+ *
+ * pt_list_offsets: offsets[0] = 0, offsets[i + 1] = offsets[i] + counts[i].
+ *   counts    n DEVICE words, 4-byte aligned
+ *   offsets   n + 1 DEVICE words, 4-byte aligned, not overlapping counts (the scan is not in place)
+ *   total     a HOST pointer or null: receives the sum of all counts as 64 bits
+ * All arithmetic is integer (the sums are 64-bit inside), so any schedule gives the same bits.  n == 0 with a non-null offsets writes
+ * the single 0 and *total = 0.  A sum above 0xFFFFFFFF is refused after it has been computed: *total is set, so that the caller can
+ * split the batch; offsets is then unspecified.  Also refused, with the context left usable: n > 0x7FFFFFFF, a null or misaligned
+ * pointer with n > 0 (a null offsets with n == 0 is a no-op success), offsets overlapping counts, a null context.  The call needs no
+ * scene; it enqueues on the context's stream, returns synchronised, and acts on rank 0 of a pt_create_multi context.
+ *
+ * pt_query_overlap_lists / pt_query_triangles_lists:
+ *   boxes, tris   exactly the records of pt_query_overlap / pt_query_triangles.  Which triangles belong to a query is decided by the
+ *             same 13 / 20 conditions and the same misses before any traversal, word for word.
+ *   offsets   n + 1 DEVICE words, 4-byte aligned: the slices.  Normally pt_list_offsets' of the counts of these queries on this scene.
+ *   prims     capacity DEVICE words, 4-byte aligned (null is allowed with capacity == 0).  prims[offsets[i] .. offsets[i + 1]) receives
+ *             every accepted triangle index of query i, in the caller's index-buffer order, ascending.  Ascending is part of the
+ *             contract and does not depend on the tree: the lists are equal after pt_update_vertices in refit and in rebuild mode,
+ *             under every build mode and under both node formats.
+ *   capacity  the number of words prims holds.  A query whose slice does not satisfy offsets[i] <= offsets[i + 1] <= capacity writes
+ *             nothing and raises the mismatch flag.  No word outside the slices is ever written, whatever offsets contains: stale
+ *             offsets cannot write out of bounds.
+ *   found     null, or n DEVICE words, 4-byte aligned: the number of triangles accepted on this walk, which is what counts would be.
+ *   A slice longer than the number found holds 0xFFFFFFFF in its surplus slots, after the indices: offsets taken from counts plus a
+ *   margin are accepted without a flag if and only if every slice is at least as long as its list.  A slice shorter than the number
+ *   found has unspecified contents; the writes still stay inside the slice, and the query raises the mismatch flag.
+ *   When any query raised the flag the call returns non-zero after the lists have been written and found is complete; pt_last_error
+ *   says that the offsets do not fit this scene and these queries.  The context stays usable.  (The flag is one device word in the
+ *   context's scratch: cleared before the launch, set by a plain store of 1 — no atomic, every writer stores the same value — and read
+ *   after the sync.)
+ * Everything else is pt_query_overlap's: DEVICE arrays, boxes / tris 16-byte aligned; the call enqueues on the context's stream and
+ * returns synchronised, acts on rank 0 of a pt_create_multi context, never writes the accumulation buffer, the frame buffer or
+ * pt_stats, and two calls give the same bits.  n == 0 is a no-op success.  Refused, with the context left usable: n > 0x7FFFFFFF, a
+ * null boxes / tris, offsets or prims with n > 0 (prims may be null with capacity == 0), a misaligned pointer, any two of the four
+ * spans (records, offsets, prims, found) overlapping, a context without a scene.                                                     */
+int pt_list_offsets(pt_ctx* ctx, const uint32_t* counts, size_t n, uint32_t* offsets, uint64_t* total);
+int pt_query_overlap_lists(pt_ctx* ctx, const float* boxes, size_t n, const uint32_t* offsets,
+                           uint32_t* prims, size_t capacity, uint32_t* found);
+int pt_query_triangles_lists(pt_ctx* ctx, const float* tris, size_t n, const uint32_t* offsets,
+                             uint32_t* prims, size_t capacity, uint32_t* found);
+
 /* ---- swept-sphere casts on the device (opt-in; nothing above changes) --------------------------------------------------------------
  * How far a ball of radius r travels along a direction before it touches the mesh, and where it touches: the sphere cast of physics
  * and robotics libraries — continuous collision, character and camera controllers, path clearance of a round robot, thick rays and

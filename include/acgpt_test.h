@@ -173,6 +173,11 @@ int pt_debug_winding_visits(pt_ctx* ctx, const float* points, size_t n, float be
  * node numbering (pt_debug_read_tree's).  Never builds them: refused while they are not built (pt_get_winding_info), and on a
  * capacity below their size, a null context or a null out. */
 int pt_debug_read_winding(pt_ctx* ctx, void* out, size_t capacity_bytes);
+/* Which parts of pt_query_overlap_lists / pt_query_triangles_lists run on this context from now on, for timing them apart
+ * (tools/lists_timing.py): 1 the fill alone (long slices stay in walk order), 2 the sort alone (of what prims holds), 3 both (the
+ * default, the product), plus 4 for a fill that keeps no sorted register list, so that every slice of two words or more goes through
+ * the sort.  3 and 7 give the same lists.  Anything else is refused. */
+int pt_debug_list_phases(pt_ctx* ctx, uint32_t phases);
 /* Sorted (morton, triangle) pairs of the last build, HOST outputs of n_tris. */
 int pt_read_morton(pt_ctx* ctx, uint32_t* codes_sorted, uint32_t* prims_sorted);
 /* What the scene's tree is made of, as the device holds it right now (tests/tree_ref.py validates it node by node).  Not part of the
