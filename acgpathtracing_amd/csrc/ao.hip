@@ -7,17 +7,16 @@
 // the node array the scene holds.  IMAGE false: the point is a device record {P, N}, lane i of a one-dimensional grid is point i.
 // IMAGE true: the point is pixel (x, y)'s first hit, P = eye + t * pixel_centre_dir, {N, t} = normal_depth[y * w + x]; a wave is an
 // 8 x 8 pixel tile, so that its 64 origins are neighbours on screen and mostly on one surface.  256-lane workgroups, the LDS lane
-// stack of query_stack (stack_entries * 64 words per wave).  The K disk points are the same for every lane: `disk[k]` with a
+// stack of query_launch.h (stack_entries * 64 words per wave).  The K disk points are the same for every lane: `disk[k]` with a
 // wave-uniform k is a scalar load.  Lanes without a point and points that are no surface stay in the wave, inactive; a wave without
 // any surface traces nothing.  No atomics: two calls give the same bits.
 // Built with -ffp-contract=off: every expression is evaluated as written, and tests/ao_ref.py mirrors it operation for operation.
 #include "ao.h"
 #include "image_common.h"
+#include "query_launch.h"
 #include "traverse_hc.h"
 
 namespace ptd {
-
-extern __shared__ uint32_t ao_lds[];
 
 __device__ __forceinline__ bool finite3(const f3& v) { return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z); }
 
@@ -26,8 +25,7 @@ __global__ void __launch_bounds__(256)
 k_ao(const DeviceScene sc, uint32_t stack_entries, const float4* __restrict__ src, uint32_t n, const AoView view, uint32_t tiles_x,
      const float2* __restrict__ disk, const AoArgs a, uint32_t* __restrict__ visible, float* __restrict__ ao)
 {
-    LaneStack st;
-    st.base = ao_lds + (threadIdx.x >> 6) * (stack_entries * 64u) + (threadIdx.x & 63u);
+    const LaneStack st = lane_stack(stack_entries);
 
     // ---- the lane's point -------------------------------------------------------------------------------------------------------
     uint32_t i;
@@ -98,23 +96,13 @@ k_ao(const DeviceScene sc, uint32_t stack_entries, const float4* __restrict__ sr
     if (ao) ao[i] = (float)v / (float)a.total_samples;
 }
 
-template <typename K, typename... A>
-static hipError_t launch_ao(K kernel, uint32_t stack_entries, uint32_t blocks, hipStream_t stream, A... args)
-{
-    const size_t lds = (size_t)(256 / 64) * stack_entries * 64u * sizeof(uint32_t);
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    kernel<<<blocks, 256, lds, stream>>>(args...);
-    return hipGetLastError();
-}
-
 hipError_t launch_ao_points(int fmt, const DeviceScene& sc, uint32_t stack_entries, const float4* points, uint32_t n, const float2* disk, const AoArgs& args,
                             uint32_t* visible, float* ao, hipStream_t stream)
 {
     const AoView none = {};
     const uint32_t blocks = (n + 255u) / 256u;
-    if (fmt == 11) return launch_ao(k_ao<11, false>, stack_entries, blocks, stream, sc, stack_entries, points, n, none, 0u, disk, args, visible, ao);
-    return launch_ao(k_ao<0, false>, stack_entries, blocks, stream, sc, stack_entries, points, n, none, 0u, disk, args, visible, ao);
+    if (fmt == 11) return launch_lane_stack_blocks(k_ao<11, false>, stack_entries, blocks, stream, sc, stack_entries, points, n, none, 0u, disk, args, visible, ao);
+    return launch_lane_stack_blocks(k_ao<0, false>, stack_entries, blocks, stream, sc, stack_entries, points, n, none, 0u, disk, args, visible, ao);
 }
 
 hipError_t launch_ao_image(int fmt, const DeviceScene& sc, uint32_t stack_entries, const AoView& view, const float4* normal_depth, const float2* disk,
@@ -123,8 +111,8 @@ hipError_t launch_ao_image(int fmt, const DeviceScene& sc, uint32_t stack_entrie
     const uint32_t tiles_x = (view.w + 7u) / 8u, tiles_y = (view.h + 7u) / 8u;      // w * h <= 2^31 - 1: at most 2^28 + ... tiles
     const uint32_t blocks = (uint32_t)(((uint64_t)tiles_x * tiles_y + 3u) / 4u);
     const uint32_t n = view.w * view.h;
-    if (fmt == 11) return launch_ao(k_ao<11, true>, stack_entries, blocks, stream, sc, stack_entries, normal_depth, n, view, tiles_x, disk, args, visible, ao);
-    return launch_ao(k_ao<0, true>, stack_entries, blocks, stream, sc, stack_entries, normal_depth, n, view, tiles_x, disk, args, visible, ao);
+    if (fmt == 11) return launch_lane_stack_blocks(k_ao<11, true>, stack_entries, blocks, stream, sc, stack_entries, normal_depth, n, view, tiles_x, disk, args, visible, ao);
+    return launch_lane_stack_blocks(k_ao<0, true>, stack_entries, blocks, stream, sc, stack_entries, normal_depth, n, view, tiles_x, disk, args, visible, ao);
 }
 
 }  // namespace ptd

@@ -5,7 +5,7 @@
 // segment-to-mesh distance query pt_query_segments and the K-closest and within-radius queries pt_query_nearest_k,
 // pt_query_within_any and the generalised winding number pt_query_winding (each with its counting twin of include/acgpt_test.h),
 // and the complete lists in CSR form: pt_list_offsets, pt_query_overlap_lists, pt_query_triangles_lists.
-// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip, segment.hip, tridist.hip, winding.hip and lists.hip.  The context and what the units share: context.h.
+// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip, segment.hip, tridist.hip, winding.hip and lists.hip; their one walk, leaf routine and launch are in bvh_walk.h, closest_point.h and query_launch.h.  The context and what the units share: context.h.
 #include <cmath>
 
 #include "../../include/acgpt_test.h"

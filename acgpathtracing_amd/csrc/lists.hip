@@ -16,12 +16,11 @@
 // atomics: the mismatch flag is a plain store of 1 by every lane that raises it.  Two calls give the same bits.  Built with
 // -ffp-contract=off like the units it shares the leaf tests with.
 #include "lists.h"
-#include "overlap_device.h"
-#include "tritri_device.h"
+#include "bvh_walk.h"
+#include "overlap_device.h"      // BoxQuery, AdmitBoth, the sorted register list
+#include "tritri_device.h"       // TriQuery
 
 namespace ptd {
-
-extern __shared__ uint32_t lists_lds[];
 
 typedef unsigned long long u64;
 
@@ -115,71 +114,34 @@ hipError_t launch_list_offsets(const uint32_t* counts, uint32_t n, uint32_t* off
     return hipGetLastError();
 }
 
-// ---- the queries -----------------------------------------------------------------------------------------------------------------
-// What the walk asks of a query: load() the record (false: a miss before any traversal, or a lane past n), prepare() the walk's
-// constants, admit a child box of either format, accept a triangle.  The statements are k_query_overlap's and k_query_triangles'.
-struct BoxQuery {
-    f3 c, h, thr, qc;
-    __device__ __forceinline__ bool load(const float4* __restrict__ boxes, uint32_t i, uint32_t n)
-    {
-        c = mk(0.0f); h = mk(0.0f);
-        if (i >= n) return false;
-        const float4 a = boxes[2ull * i], b = boxes[2ull * i + 1ull];
-        c = mk(a.x, a.y, a.z);
-        h = mk(a.w, b.x, b.y);
-        return __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z) && __builtin_isfinite(a.w) && __builtin_isfinite(b.x) &&
-               __builtin_isfinite(b.y) && a.w >= 0.0f && b.x >= 0.0f && b.y >= 0.0f;
-    }
-    __device__ __forceinline__ void prepare(const DeviceScene& sc, float scene_term)
-    {
-        thr = mk(h.x + (scene_term + (fabsf(c.x) + h.x) * kOverlapQuery), h.y + (scene_term + (fabsf(c.y) + h.y) * kOverlapQuery),
-                 h.z + (scene_term + (fabsf(c.z) + h.z) * kOverlapQuery));
-        qc = mk(c.x - sc.hspace.cx, c.y - sc.hspace.cy, c.z - sc.hspace.cz);
-    }
-    __device__ __forceinline__ bool admit_hc(uint32_t px, uint32_t py, uint32_t pz, const HSpace& hs) const { return child_admitted_hc(px, py, pz, qc, hs, thr); }
-    __device__ __forceinline__ bool admit_f32(float lx, float ly, float lz, float hx, float hy, float hz) const { return child_admitted_f32(c, lx, ly, lz, hx, hy, hz, thr); }
-    __device__ __forceinline__ bool accept(const f3& v0, const f3& e1, const f3& e2) const { return tri_box_overlap(c, h, v0, e1, e2); }
-};
-
-struct TriQuery {
-    f3 a0, f1, f2, qlo, qhi, thr, qc;
-    __device__ __forceinline__ bool load(const float4* __restrict__ tris, uint32_t i, uint32_t n)
-    {
-        f3 a1 = mk(0.0f), a2 = mk(0.0f);
-        a0 = mk(0.0f);
-        bool ok = false;
-        if (i < n) {
-            const float4 r0 = tris[3ull * i], r1 = tris[3ull * i + 1ull], r2 = tris[3ull * i + 2ull];
-            a0 = mk(r0.x, r0.y, r0.z);
-            a1 = mk(r1.x, r1.y, r1.z);
-            a2 = mk(r2.x, r2.y, r2.z);
-            ok = __builtin_isfinite(r0.x) && __builtin_isfinite(r0.y) && __builtin_isfinite(r0.z) && __builtin_isfinite(r1.x) && __builtin_isfinite(r1.y) &&
-                 __builtin_isfinite(r1.z) && __builtin_isfinite(r2.x) && __builtin_isfinite(r2.y) && __builtin_isfinite(r2.z);
-        }
-        qlo = mk(fmin3(a0.x, a1.x, a2.x), fmin3(a0.y, a1.y, a2.y), fmin3(a0.z, a1.z, a2.z));
-        qhi = mk(fmax3(a0.x, a1.x, a2.x), fmax3(a0.y, a1.y, a2.y), fmax3(a0.z, a1.z, a2.z));
-        f1 = a1 - a0;
-        f2 = a2 - a0;
-        return ok;
-    }
-    __device__ __forceinline__ void prepare(const DeviceScene& sc, float scene_term)
-    {
-        // FMT 11 only: the query box as centre and half extent (the halves are exact, the sum and the difference round once each)
-        const f3 c = mk(0.5f * qlo.x + 0.5f * qhi.x, 0.5f * qlo.y + 0.5f * qhi.y, 0.5f * qlo.z + 0.5f * qhi.z);
-        const f3 h = mk(0.5f * qhi.x - 0.5f * qlo.x, 0.5f * qhi.y - 0.5f * qlo.y, 0.5f * qhi.z - 0.5f * qlo.z);
-        thr = mk(h.x + (scene_term + (fabsf(c.x) + h.x) * kOverlapQuery), h.y + (scene_term + (fabsf(c.y) + h.y) * kOverlapQuery),
-                 h.z + (scene_term + (fabsf(c.z) + h.z) * kOverlapQuery));
-        qc = mk(c.x - sc.hspace.cx, c.y - sc.hspace.cy, c.z - sc.hspace.cz);
-    }
-    __device__ __forceinline__ bool admit_hc(uint32_t px, uint32_t py, uint32_t pz, const HSpace& hs) const { return child_admitted_hc(px, py, pz, qc, hs, thr); }
-    __device__ __forceinline__ bool admit_f32(float lx, float ly, float lz, float hx, float hy, float hz) const { return child_admitted_f32(qlo, qhi, lx, ly, lz, hx, hy, hz); }
-    __device__ __forceinline__ bool accept(const f3& v0, const f3& e1, const f3& e2) const { return tri_tri_intersect(a0, f1, f2, qlo, qhi, v0, e1, e2); }
-};
-
 // ---- the fill ----------------------------------------------------------------------------------------------------------------------
-// traverse_overlap's walk (overlap.hip says why max_depth + 1 stack entries suffice): of two admitted children the first is entered and
-// the second pushed; a popped reference is entered without a second look at its own box.  Which triangles are accepted is decided by
-// q.accept alone, so the set does not depend on the tree; the order of a long slice does, until k_sort_lists has run.
+// overlap.hip's walk (bvh_walk.h): of two admitted children the first is entered and the second pushed.  Which triangles are accepted is
+// decided by q.accept alone, so the set does not depend on the tree; the order of a long slice does, until k_sort_lists has run.
+// in_regs: the slice fits the register list, which the epilogue writes; otherwise out[0 .. m) is stored as the walk accepts.
+template <class Q>
+struct FillWalk : AdmitBoth<Q> {
+    PrimList<kListRegister>& L;      // the kernel's: its epilogue writes the words
+    uint32_t* out;
+    uint32_t m, count;
+    bool in_regs;
+    __device__ __forceinline__ FillWalk(const Q& q_, PrimList<kListRegister>& L_, uint32_t* out_, uint32_t m_, bool in_regs_)
+        : AdmitBoth<Q>(q_), L(L_), out(out_), m(m_), count(0u), in_regs(in_regs_)
+    {
+#pragma unroll
+        for (uint32_t j = 0; j < kListRegister; j++) L.prim[j] = 0xFFFFFFFFu;
+    }
+    __device__ __forceinline__ bool leaf(int, const float4& r0, const float4& r1, const float4& r2)
+    {
+        if (this->q.accept(mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x))) {
+            const uint32_t prim = __float_as_uint(r2.y);
+            if (in_regs) list_insert(L, kListRegister, prim);
+            else if (count < m) out[count] = prim;
+            count++;
+        }
+        return false;
+    }
+};
+
 // REG: kListRegister, or 0 for the measurement without the register list (every slice stored as the walk finds it).
 template <int FMT, class Q, uint32_t REG>
 __global__ void __launch_bounds__(256)
@@ -187,8 +149,7 @@ k_fill_lists(const DeviceScene sc, uint32_t stack_entries, float scene_term, con
              uint32_t* prims, uint32_t capacity, uint32_t* __restrict__ found, uint32_t* __restrict__ flag)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;      // n <= 2^31 - 1: the grid's last lane is below 2^31 + 255
-    LaneStack st;
-    st.base = lists_lds + (threadIdx.x >> 6) * (stack_entries * 64u) + (threadIdx.x & 63u);
+    const LaneStack st = lane_stack(stack_entries);
     Q q;
     const bool active = q.load(recs, i, n);
     q.prepare(sc, scene_term);
@@ -204,55 +165,10 @@ k_fill_lists(const DeviceScene sc, uint32_t stack_entries, float scene_term, con
     uint32_t* out = prims + lo;                 // read or written at j < m only: m == 0 where prims is null (capacity == 0)
     const bool in_regs = m <= REG;
     PrimList<kListRegister> L;
-#pragma unroll
-    for (uint32_t j = 0; j < kListRegister; j++) L.prim[j] = 0xFFFFFFFFu;
-    uint32_t count = 0u;
-    int sp = 0;
-    int node = (active && sc.n_tris != 0u) ? 0 : kSentinel;
-    while (node != kSentinel) {
-        if (node >= 0) {
-            bool h0, h1;
-            int c0, c1;
-            if (FMT == 11) {
-                // child references of inner nodes are byte offsets into hcnodes; a leaf is ~slot
-                const uint4* np = (const uint4*)((const char*)sc.hcnodes + (size_t)(uint32_t)node);
-                const uint4 qa = np[0], qb = np[1];
-                h0 = q.admit_hc(qa.x, qa.y, qa.z, sc.hspace);
-                h1 = q.admit_hc(qb.x, qb.y, qb.z, sc.hspace);
-                c0 = (int)qa.w; c1 = (int)qb.w;
-            } else {
-                // child 0: lo (a.x a.y a.z) hi (a.w b.x b.y); child 1: lo (b.z b.w c.x) hi (c.y c.z c.w)
-                const BvhNode* np = sc.nodes + node;
-                const float4 a = np->a, b = np->b, cc = np->c;
-                const int4 ch = np->d;
-                h0 = q.admit_f32(a.x, a.y, a.z, a.w, b.x, b.y);
-                h1 = q.admit_f32(b.z, b.w, cc.x, cc.y, cc.z, cc.w);
-                c0 = ch.x; c1 = ch.y;
-            }
-            if (h0 && h1) {
-                st.push(sp, c1);
-                sp++;
-                node = c0;
-            } else if (h0) {
-                node = c0;
-            } else if (h1) {
-                node = c1;
-            } else {
-                if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
-            }
-        } else {
-            const int slot = ~node;
-            const TriRecord* tp = sc.tris + slot;
-            const float4 r0 = tp->r0, r1 = tp->r1, r2 = tp->r2;
-            if (q.accept(mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x))) {
-                const uint32_t prim = __float_as_uint(r2.y);
-                if (in_regs) list_insert(L, kListRegister, prim);
-                else if (count < m) out[count] = prim;
-                count++;
-            }
-            if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
-        }
-    }
+    FillWalk<Q> walk(q, L, out, m, in_regs);
+    uint2 visits = make_uint2(0u, 0u);
+    bvh_walk<FMT, false>(sc, st, active, walk, visits);
+    const uint32_t count = walk.count;
     if (i >= n) return;
     if (found) found[i] = count;
     if (!fits || count > m) *flag = 1u;         // every writer stores the same word
@@ -355,12 +271,8 @@ static hipError_t launch_fill(const DeviceScene& sc, uint32_t stack_entries, flo
                               uint32_t* prims, uint32_t capacity, uint32_t* found, uint32_t* flag, uint32_t phases, hipStream_t stream)
 {
     if (phases & kListPhaseFill) {
-        const size_t lds = (size_t)(256 / 64) * stack_entries * 64u * sizeof(uint32_t);
-        auto kernel = k_fill_lists<FMT, Q, REG>;
-        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        kernel<<<(n + 255u) / 256u, 256, lds, stream>>>(sc, stack_entries, scene_term, recs, n, offsets, prims, capacity, found, flag);
-        e = hipGetLastError();
+        const hipError_t e = launch_lane_stack(k_fill_lists<FMT, Q, REG>, stack_entries, n, stream, sc, stack_entries, scene_term, recs, n, offsets, prims, capacity,
+                                               found, flag);
         if (e != hipSuccess) return e;
     }
     // a slice of one word is sorted as it is

@@ -7,7 +7,7 @@
 //
 // FMT 11 walks the fp16 centre / half-extent nodes with the box test of traverse_hc.h, FMT 0 the fp32 nodes with the box test of
 // traverse<> (pt_device.h), restated here: the node array the scene holds.  256-lane workgroups over a one-dimensional grid, the LDS
-// lane stack of query.hip (stack_entries * 64 words per wave).  Lanes past n and lanes whose ray is a miss before any traversal stay
+// lane stack of query_launch.h (stack_entries * 64 words per wave).  Lanes past n and lanes whose ray is a miss before any traversal stay
 // in the wave, inactive.  No atomics: two calls give the same bits.
 //
 // The list lives in registers.  Every access to it has an index the compiler knows: the insertion is a chain of CAP
@@ -19,10 +19,9 @@
 // widening traverse_hc applies to its one hit: a triangle that ties with the last kept hit and has a lower index is still reached.
 // Built with -ffp-contract=off: the epilogue is k_query_closest's, evaluated as written.
 #include "multihit.h"
+#include "bvh_walk.h"
 
 namespace ptd {
-
-extern __shared__ uint32_t multihit_lds[];
 
 struct MultiRay { f3 o, d; float tmin, tmax; bool ok; };
 
@@ -69,90 +68,66 @@ __device__ __forceinline__ float list_insert(HitList<N>& L, uint32_t max_hits, f
     return last;
 }
 
-// One ray per lane through the two-child BVH.  Boxes only prune; the triangle test and the interval are traverse_hc's.  far_cut is
-// the ray's tmax widened (fmaxf: under tmax < 0 the product would move the cut inward); without COUNT it shrinks to the last kept
-// hit's t, widened by kTieWiden, once entry max_hits - 1 is filled.  Every triangle sits in one leaf, so each is counted once.
+// One ray per lane through the two-child BVH (bvh_walk.h).  Boxes only prune; the triangle test and the interval are traverse_hc's.
+// far_cut is the ray's tmax widened (fmaxf: under tmax < 0 the product would move the cut inward); without COUNT it shrinks to the last
+// kept hit's t, widened by kTieWiden, once entry max_hits - 1 is filled.  Every triangle sits in one leaf, so each is counted once.
 template <int FMT, int CAP, bool COUNT>
-__device__ __forceinline__ void traverse_multi(const DeviceScene& sc, const LaneStack& st, bool active, const f3& o, const f3& d, float tmin, float tmax,
-                                               uint32_t max_hits, HitList<CAP>& L, uint32_t& count)
-{
+struct MultiWalk {
+    f3 o, d, mul, add;
+    float tmin, tmax, far_cut;
+    uint32_t max_hits, count;
+    HitList<CAP>& L;      // the kernel's: its epilogue writes the records
+    __device__ __forceinline__ MultiWalk(const DeviceScene& sc, const f3& o_, const f3& d_, float tmin_, float tmax_, uint32_t max_hits_, HitList<CAP>& L_)
+        : o(o_), d(d_), tmin(tmin_), tmax(tmax_), far_cut(fmaxf(tmax_ * kTieWiden, tmax_)), max_hits(max_hits_), count(0u), L(L_)
+    {
 #pragma unroll
-    for (int j = 0; j < CAP; j++) { L.t[j] = INFINITY; L.slot[j] = -1; L.prim[j] = 0xFFFFFFFFu; }
-    count = 0u;
-    f3 mul, add;
-    if (FMT == 11) setup_ray_hc(o, d, sc.hspace, mul, add);
-    else { mul = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z); add = o; }
-    float far_cut = fmaxf(tmax * kTieWiden, tmax);
-    int sp = 0;
-    int node = (active && sc.n_tris != 0u) ? 0 : kSentinel;
-    while (node != kSentinel) {
-        if (node >= 0) {
-            float n0, f0, n1, f1;
-            int c0, c1;
-            bool e0 = false, e1 = false;      // an empty child box
-            if (FMT == 11) {
-                // child references of inner nodes are byte offsets into hcnodes; a leaf is ~slot
-                const uint4* np = (const uint4*)((const char*)sc.hcnodes + (size_t)(uint32_t)node);
-                const uint4 qa = np[0], qb = np[1];
-                slab_hc(qa.x, qa.y, qa.z, mul, add, tmin, n0, f0);
-                slab_hc(qb.x, qb.y, qb.z, mul, add, tmin, n1, f1);
-                c0 = (int)qa.w; c1 = (int)qb.w;
-            } else {
-                // child 0: lo (a.x a.y a.z) hi (a.w b.x b.y); child 1: lo (b.z b.w c.x) hi (c.y c.z c.w).  mul = 1 / d, add = o
-                const BvhNode* np = sc.nodes + node;
-                const float4 a = np->a, b = np->b, c = np->c;
-                const int4 ch = np->d;
-                const float x0 = (a.x - add.x) * mul.x, x1 = (a.w - add.x) * mul.x;
-                const float y0 = (a.y - add.y) * mul.y, y1 = (b.x - add.y) * mul.y;
-                const float z0 = (a.z - add.z) * mul.z, z1 = (b.y - add.z) * mul.z;
-                n0 = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), tmin));
-                f0 = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1)) * kFarWiden;
-                const float u0 = (b.z - add.x) * mul.x, u1 = (c.y - add.x) * mul.x;
-                const float v0 = (b.w - add.y) * mul.y, v1 = (c.z - add.y) * mul.y;
-                const float w0 = (c.x - add.z) * mul.z, w1 = (c.w - add.z) * mul.z;
-                n1 = fmaxf(fmaxf(fminf(u0, u1), fminf(v0, v1)), fmaxf(fminf(w0, w1), tmin));
-                f1 = fminf(fminf(fmaxf(u0, u1), fmaxf(v0, v1)), fmaxf(w0, w1)) * kFarWiden;
-                c0 = ch.x; c1 = ch.y;
-                // The one node of a single-triangle scene names its triangle in both children, the second under an empty box, lo = +inf
-                // and hi = -inf, whose slabs come out as (-inf, +inf): every ray "hits" it.  traverse<> tests the triangle twice and
-                // keeps one hit; a count must not.  (The fp16 nodes mark an empty child with a negative half extent, which slab_hc
-                // never hits.)
-                e0 = !(a.x <= a.w); e1 = !(b.z <= c.y);
-            }
-            f0 = fminf(f0, far_cut);
-            f1 = fminf(f1, far_cut);
-            const bool h0 = n0 <= f0 && !e0, h1 = n1 <= f1 && !e1;
-            if (h0 && h1) {
-                const bool first0 = n0 <= n1;
-                st.push(sp, first0 ? c1 : c0);
-                sp++;
-                node = first0 ? c0 : c1;
-            } else if (h0) {
-                node = c0;
-            } else if (h1) {
-                node = c1;
-            } else {
-                if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
-            }
-        } else {
-            const int slot = ~node;
-            const TriRecord* tp = sc.tris + slot;
-            const float4 r0 = tp->r0, r1 = tp->r1, r2 = tp->r2;
-            float t;
-            const bool ok = tri_test(o, d, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x), tmin, tmax, t);
-            if (ok) {
-                if (COUNT) count++;
-                if constexpr (CAP > 0) {
-                    const float last = list_insert(L, max_hits, t, slot, __float_as_uint(r2.y));
-                    // +inf while entry max_hits - 1 is empty: the cut stays at the ray's own.  The second product widens a negative t
-                    // (tmin < 0) outward, which t * kTieWiden alone would move inward
-                    if (!COUNT) far_cut = fminf(far_cut, fmaxf(last * kTieWiden, last * (2.0f - kTieWiden)));
-                }
-            }
-            if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
-        }
+        for (int j = 0; j < CAP; j++) { L.t[j] = INFINITY; L.slot[j] = -1; L.prim[j] = 0xFFFFFFFFu; }
+        if (FMT == 11) setup_ray_hc(o, d, sc.hspace, mul, add);
+        else { mul = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z); add = o; }
     }
-}
+    __device__ __forceinline__ void children_hc(const uint4& qa, const uint4& qb, const HSpace&, bool& h0, bool& h1, bool& first0) const
+    {
+        // an empty child has a negative half extent, which slab_hc never hits
+        float n0, f0, n1, f1;
+        slab_hc(qa.x, qa.y, qa.z, mul, add, tmin, n0, f0);
+        slab_hc(qb.x, qb.y, qb.z, mul, add, tmin, n1, f1);
+        admit_by_interval(n0, fminf(f0, far_cut), n1, fminf(f1, far_cut), h0, h1, first0);
+    }
+    __device__ __forceinline__ void children_f32(const float4& a, const float4& b, const float4& c, bool& h0, bool& h1, bool& first0) const
+    {
+        // the box test of traverse<> (pt_device.h), restated: mul = 1 / d, add = o
+        const float x0 = (a.x - add.x) * mul.x, x1 = (a.w - add.x) * mul.x;
+        const float y0 = (a.y - add.y) * mul.y, y1 = (b.x - add.y) * mul.y;
+        const float z0 = (a.z - add.z) * mul.z, z1 = (b.y - add.z) * mul.z;
+        const float n0 = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), tmin));
+        const float f0 = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1)) * kFarWiden;
+        const float u0 = (b.z - add.x) * mul.x, u1 = (c.y - add.x) * mul.x;
+        const float v0 = (b.w - add.y) * mul.y, v1 = (c.z - add.y) * mul.y;
+        const float w0 = (c.x - add.z) * mul.z, w1 = (c.w - add.z) * mul.z;
+        const float n1 = fmaxf(fmaxf(fminf(u0, u1), fminf(v0, v1)), fmaxf(fminf(w0, w1), tmin));
+        const float f1 = fminf(fminf(fmaxf(u0, u1), fmaxf(v0, v1)), fmaxf(w0, w1)) * kFarWiden;
+        admit_by_interval(n0, fminf(f0, far_cut), n1, fminf(f1, far_cut), h0, h1, first0);
+        // The one node of a single-triangle scene names its triangle in both children, the second under an empty box, lo = +inf
+        // and hi = -inf, whose slabs come out as (-inf, +inf): every ray "hits" it.  traverse<> tests the triangle twice and
+        // keeps one hit; a count must not.
+        h0 = h0 && a.x <= a.w; h1 = h1 && b.z <= c.y;
+    }
+    __device__ __forceinline__ bool leaf(int slot, const float4& r0, const float4& r1, const float4& r2)
+    {
+        float t;
+        const bool ok = tri_test(o, d, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x), tmin, tmax, t);
+        if (ok) {
+            if (COUNT) count++;
+            if constexpr (CAP > 0) {
+                const float last = list_insert(L, max_hits, t, slot, __float_as_uint(r2.y));
+                // +inf while entry max_hits - 1 is empty: the cut stays at the ray's own.  The second product widens a negative t
+                // (tmin < 0) outward, which t * kTieWiden alone would move inward
+                if (!COUNT) far_cut = fminf(far_cut, fmaxf(last * kTieWiden, last * (2.0f - kTieWiden)));
+            }
+        }
+        return false;
+    }
+};
 
 template <int FMT, int CAP, bool COUNT>
 __global__ void __launch_bounds__(256)
@@ -160,14 +135,14 @@ k_query_multi(const DeviceScene sc, uint32_t stack_entries, const float4* __rest
               uint32_t* __restrict__ counts)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;      // n <= 2^31 - 1: the grid's last lane is below 2^31 + 255
-    LaneStack st;
-    st.base = multihit_lds + (threadIdx.x >> 6) * (stack_entries * 64u) + (threadIdx.x & 63u);
+    const LaneStack st = lane_stack(stack_entries);
     const MultiRay r = load_multi_ray(rays, i, n);
     HitList<CAP> L;
-    uint32_t count;
-    traverse_multi<FMT, CAP, COUNT>(sc, st, r.ok, r.o, r.d, r.tmin, r.tmax, max_hits, L, count);
+    MultiWalk<FMT, CAP, COUNT> walk(sc, r.o, r.d, r.tmin, r.tmax, max_hits, L);
+    uint2 visits = make_uint2(0u, 0u);
+    bvh_walk<FMT, false>(sc, st, r.ok, walk, visits);
     if (i >= n) return;
-    if (COUNT) counts[i] = count;
+    if (COUNT) counts[i] = walk.count;
     if constexpr (CAP > 0) {
         float4* out = hits + 2ull * ((unsigned long long)i * max_hits);      // n * max_hits is formed in 64 bits
 #pragma unroll 1
@@ -207,12 +182,7 @@ template <int FMT, int CAP, bool COUNT>
 static hipError_t launch_multi(const DeviceScene& sc, uint32_t stack_entries, const float4* rays, uint32_t n, uint32_t max_hits, float4* hits, uint32_t* counts,
                                hipStream_t stream)
 {
-    const size_t lds = (size_t)(256 / 64) * stack_entries * 64u * sizeof(uint32_t);
-    auto kernel = k_query_multi<FMT, CAP, COUNT>;
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    kernel<<<(n + 255u) / 256u, 256, lds, stream>>>(sc, stack_entries, rays, n, max_hits, hits, counts);
-    return hipGetLastError();
+    return launch_lane_stack(k_query_multi<FMT, CAP, COUNT>, stack_entries, n, stream, sc, stack_entries, rays, n, max_hits, hits, counts);
 }
 
 template <int FMT>

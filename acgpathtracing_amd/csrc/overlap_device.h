@@ -1,6 +1,7 @@
 // overlap_device.h — the device functions the box-overlap query (overlap.hip) shares with the complete-list queries (lists.hip): the
-// triangle-box test, the child-box admission of both node formats and the sorted register list.  tritri_device.h takes fmin3 / fmax3,
-// child_admitted_hc and the list from here.  Moved out of overlap.hip word for word; include only from a unit built with
+// triangle-box test, the child-box admission of both node formats, the sorted register list, the query record BoxQuery and the
+// policies of the walk (bvh_walk.h) over a query record.  tritri_device.h takes fmin3 / fmax3, child_admitted_hc, the list and the
+// policies from here.  Include only from a unit built with
 // -ffp-contract=off (the triangle-box test is evaluated as written, and tests/overlap_ref.py mirrors it operation for operation).
 #pragma once
 #include "overlap.h"
@@ -85,5 +86,72 @@ __device__ __forceinline__ void list_insert(PrimList<N>& L, uint32_t max_prims, 
         prim = sw ? lp : prim;
     }
 }
+
+// What the walk asks of a query record Q (BoxQuery here, TriQuery in tritri_device.h): load() the record (false: a miss before any
+// traversal, or a lane past n), prepare() the walk's constants, admit a child box of either format, accept a triangle.
+struct BoxQuery {
+    f3 c, h, thr, qc;
+    __device__ __forceinline__ bool load(const float4* __restrict__ boxes, uint32_t i, uint32_t n)
+    {
+        c = mk(0.0f); h = mk(0.0f);
+        if (i >= n) return false;
+        const float4 a = boxes[2ull * i], b = boxes[2ull * i + 1ull];
+        c = mk(a.x, a.y, a.z);
+        h = mk(a.w, b.x, b.y);
+        return __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z) && __builtin_isfinite(a.w) && __builtin_isfinite(b.x) &&
+               __builtin_isfinite(b.y) && a.w >= 0.0f && b.x >= 0.0f && b.y >= 0.0f;
+    }
+    __device__ __forceinline__ void prepare(const DeviceScene& sc, float scene_term)
+    {
+        thr = mk(h.x + (scene_term + (fabsf(c.x) + h.x) * kOverlapQuery), h.y + (scene_term + (fabsf(c.y) + h.y) * kOverlapQuery),
+                 h.z + (scene_term + (fabsf(c.z) + h.z) * kOverlapQuery));
+        qc = mk(c.x - sc.hspace.cx, c.y - sc.hspace.cy, c.z - sc.hspace.cz);
+    }
+    __device__ __forceinline__ bool admit_hc(uint32_t px, uint32_t py, uint32_t pz, const HSpace& hs) const { return child_admitted_hc(px, py, pz, qc, hs, thr); }
+    __device__ __forceinline__ bool admit_f32(float lx, float ly, float lz, float hx, float hy, float hz) const { return child_admitted_f32(c, lx, ly, lz, hx, hy, hz, thr); }
+    __device__ __forceinline__ bool accept(const f3& v0, const f3& e1, const f3& e2) const { return tri_box_overlap(c, h, v0, e1, e2); }
+};
+
+// The admission of the walks that keep the tree's order (overlap, triangles, lists): a child is entered iff q admits its box; of two
+// admitted children the first is entered and the second pushed.
+template <class Q>
+struct AdmitBoth {
+    Q q;
+    __device__ __forceinline__ explicit AdmitBoth(const Q& q_) : q(q_) {}
+    __device__ __forceinline__ void children_hc(const uint4& qa, const uint4& qb, const HSpace& hs, bool& h0, bool& h1, bool& first0) const
+    {
+        h0 = q.admit_hc(qa.x, qa.y, qa.z, hs);
+        h1 = q.admit_hc(qb.x, qb.y, qb.z, hs);
+        first0 = true;
+    }
+    __device__ __forceinline__ void children_f32(const float4& a, const float4& b, const float4& c, bool& h0, bool& h1, bool& first0) const
+    {
+        h0 = q.admit_f32(a.x, a.y, a.z, a.w, b.x, b.y);
+        h1 = q.admit_f32(b.z, b.w, c.x, c.y, c.z, c.w);
+        first0 = true;
+    }
+};
+
+// The capped queries' policy: count what q accepts and keep the lowest max_prims indices in a list of CAP entries; ANY ends the lane at
+// the first accepted triangle.  The boxes only prune: which triangles are accepted is decided by q.accept alone.
+template <class Q, int CAP, bool ANY>
+struct PrimListWalk : AdmitBoth<Q> {
+    PrimList<CAP>& L;      // the kernel's: its epilogue writes the words
+    uint32_t max_prims, count;
+    __device__ __forceinline__ PrimListWalk(const Q& q_, uint32_t max_prims_, PrimList<CAP>& L_) : AdmitBoth<Q>(q_), L(L_), max_prims(max_prims_), count(0u)
+    {
+#pragma unroll
+        for (int j = 0; j < CAP; j++) L.prim[j] = 0xFFFFFFFFu;
+    }
+    __device__ __forceinline__ bool leaf(int, const float4& r0, const float4& r1, const float4& r2)
+    {
+        if (this->q.accept(mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x))) {
+            count++;
+            if (ANY) return true;
+            if constexpr (CAP > 0) list_insert(L, max_prims, __float_as_uint(r2.y));
+        }
+        return false;
+    }
+};
 
 }  // namespace ptd

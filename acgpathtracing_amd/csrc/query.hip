@@ -5,16 +5,15 @@
 //   k_query_any<FMT>       one ray per lane: one byte, 1 if any triangle is hit inside the interval
 //
 // FMT 11 walks the fp16 centre / half-extent nodes (traverse_hc.h), FMT 0 the fp32 nodes (traverse<>, pt_device.h): the node array the
-// scene holds.  256-lane workgroups over a one-dimensional grid, the LDS lane stack of k_dn_features (stack_entries * 64 words per
+// scene holds.  256-lane workgroups over a one-dimensional grid, the lane stack of query_launch.h (stack_entries * 64 words per
 // wave).  A ray is two 16-byte loads and a record two 16-byte stores per lane, 64 B each way; everything else is the traversal.  Lanes
 // past n and lanes whose ray is a miss before any traversal stay in the wave, inactive.  No atomics: two calls give the same bits.
 // Built with -ffp-contract=off: the epilogue is evaluated as written, and tests/query_ref.py mirrors it operation for operation.
 #include "query.h"
+#include "query_launch.h"
 #include "traverse_hc.h"
 
 namespace ptd {
-
-extern __shared__ uint32_t query_lds[];
 
 struct QueryRay { f3 o, d; float tmin, tmax; bool ok; };
 
@@ -34,19 +33,12 @@ __device__ __forceinline__ QueryRay load_query_ray(const float4* __restrict__ ra
     return r;
 }
 
-__device__ __forceinline__ LaneStack query_stack(uint32_t stack_entries)
-{
-    LaneStack st;
-    st.base = query_lds + (threadIdx.x >> 6) * (stack_entries * 64u) + (threadIdx.x & 63u);
-    return st;
-}
-
 template <int FMT>
 __global__ void __launch_bounds__(256)
 k_query_closest(const DeviceScene sc, uint32_t stack_entries, const float4* __restrict__ rays, uint32_t n, float4* __restrict__ hits)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;      // n <= 2^31 - 1: the grid's last lane is below 2^31 + 255
-    const LaneStack st = query_stack(stack_entries);
+    const LaneStack st = lane_stack(stack_entries);
     const QueryRay r = load_query_ray(rays, i, n);
     HitRec hit;
     if (FMT == 11) traverse_hc(sc, st, r.ok, r.o, r.d, r.tmin, r.tmax, hit);
@@ -79,7 +71,7 @@ __global__ void __launch_bounds__(256)
 k_query_any(const DeviceScene sc, uint32_t stack_entries, const float4* __restrict__ rays, uint32_t n, uint8_t* __restrict__ occluded)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const LaneStack st = query_stack(stack_entries);
+    const LaneStack st = lane_stack(stack_entries);
     const QueryRay r = load_query_ray(rays, i, n);
     bool found;
     if (FMT == 11) found = traverse_hc_any(sc, st, r.ok, r.o, r.d, r.tmin, r.tmax);
@@ -87,26 +79,16 @@ k_query_any(const DeviceScene sc, uint32_t stack_entries, const float4* __restri
     if (i < n) occluded[i] = found ? 1 : 0;
 }
 
-template <typename K, typename... A>
-static hipError_t launch_query(K kernel, uint32_t stack_entries, uint32_t n, hipStream_t stream, A... args)
-{
-    const size_t lds = (size_t)(256 / 64) * stack_entries * 64u * sizeof(uint32_t);
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    kernel<<<(n + 255u) / 256u, 256, lds, stream>>>(args...);
-    return hipGetLastError();
-}
-
 hipError_t launch_query_closest(int fmt, const DeviceScene& sc, uint32_t stack_entries, const float4* rays, uint32_t n, float4* hits, hipStream_t stream)
 {
-    if (fmt == 11) return launch_query(k_query_closest<11>, stack_entries, n, stream, sc, stack_entries, rays, n, hits);
-    return launch_query(k_query_closest<0>, stack_entries, n, stream, sc, stack_entries, rays, n, hits);
+    if (fmt == 11) return launch_lane_stack(k_query_closest<11>, stack_entries, n, stream, sc, stack_entries, rays, n, hits);
+    return launch_lane_stack(k_query_closest<0>, stack_entries, n, stream, sc, stack_entries, rays, n, hits);
 }
 
 hipError_t launch_query_any(int fmt, const DeviceScene& sc, uint32_t stack_entries, const float4* rays, uint32_t n, uint8_t* occluded, hipStream_t stream)
 {
-    if (fmt == 11) return launch_query(k_query_any<11>, stack_entries, n, stream, sc, stack_entries, rays, n, occluded);
-    return launch_query(k_query_any<0>, stack_entries, n, stream, sc, stack_entries, rays, n, occluded);
+    if (fmt == 11) return launch_lane_stack(k_query_any<11>, stack_entries, n, stream, sc, stack_entries, rays, n, occluded);
+    return launch_lane_stack(k_query_any<0>, stack_entries, n, stream, sc, stack_entries, rays, n, occluded);
 }
 
 }  // namespace ptd

@@ -7,17 +7,16 @@
 //
 // The shape is nearest.hip's: FMT 11 walks the fp16 centre / half-extent nodes, FMT 0 the fp32 nodes; the walk is ordered by a lower
 // bound of the squared distance from the segment to each child box, and the leaves run the segment-to-triangle statement.  256-lane
-// workgroups over a one-dimensional grid, the LDS lane stack of query.hip (stack_entries * 64 words per wave).  A segment is two
+// workgroups over a one-dimensional grid, the lane stack of query_launch.h (stack_entries * 64 words per wave).  A segment is two
 // 16-byte loads and a record two 16-byte stores per lane.  Lanes past n and lanes whose segment is a miss before any traversal stay in
 // the wave, inactive.  No atomics: two calls give the same bits.
 // Built with -ffp-contract=off: the statement is evaluated as written, and tests/segment_ref.py mirrors it operation for operation.
 // The box bounds are outside that contract (they only prune) and use explicit fused multiply-adds.
 #include "segment.h"
-#include "segment_device.h"      // seg_closest_on_triangle, clamp01, segment_edge: shared with tridist.hip
+#include "bvh_walk.h"
+#include "segment_device.h"      // closest_on_triangle (closest_point.h), clamp01, segment_edge: shared with tridist.hip
 
 namespace ptd {
-
-extern __shared__ uint32_t segment_lds[];
 
 struct SegPoint { float d2, s, feature; f3 c; };
 
@@ -46,13 +45,14 @@ __device__ __forceinline__ SegPoint segment_triangle(const f3& p0, const f3& p1,
     SegPoint best;
     f3 c;
     float s = 0.0f;
-    best.d2 = seg_closest_on_triangle(p0, v0, e1, e2, best.c);
+    const ClosestPoint c0 = closest_on_triangle(p0, v0, e1, e2);
+    best.d2 = c0.d2; best.c = c0.c;
     best.s = 0.0f; best.feature = 0.0f;
     asm volatile("" : "+v"(best.d2));
     __builtin_amdgcn_sched_barrier(0);
-    float d2 = seg_closest_on_triangle(p1, v0, e1, e2, c);
-    seg_take<FULL>(best, d2, 1.0f, 1.0f, c);
-    d2 = segment_edge(p0, d, a, v0, e1, s, c);
+    const ClosestPoint c1 = closest_on_triangle(p1, v0, e1, e2);
+    seg_take<FULL>(best, c1.d2, 1.0f, 1.0f, c1.c);
+    float d2 = segment_edge(p0, d, a, v0, e1, s, c);
     seg_take<FULL>(best, d2, s, 2.0f, c);
     d2 = segment_edge(p0, d, a, v0, e2, s, c);
     seg_take<FULL>(best, d2, s, 3.0f, c);
@@ -125,71 +125,37 @@ __device__ __forceinline__ float seg_bound_f32(const SegBound& sb, float lx, flo
     return lx <= hx ? b : __builtin_nanf("");
 }
 
-struct SegBest { float d2; int slot; uint32_t prim; };
-
-// One segment per lane through the two-child BVH: traverse_nearest's walk (nearest.hip) with the segment's bound and statement.  thr
-// is min(best d2, r2) widened (segment.h): a child is entered iff its bound is at most thr and it is not empty; of two such children
-// the nearer is entered and the other pushed.  A visit pushes at most one reference and descends one level, so max_depth + 1 entries
-// hold here too, and a popped reference is entered without a second look at its own box: an entry is one word.  The boxes only prune:
-// the winner is decided by the statement, d2 <= r2, smallest d2, ties to the lowest triangle index, whatever order the walk reaches
-// the triangles in.
-template <int FMT, bool COUNT>
-__device__ __forceinline__ void traverse_segments(const DeviceScene& sc, const LaneStack& st, bool active, const f3& p0, const f3& p1, const f3& d, float a,
-                                                  const SegBound& sb, float r2, float abs_term, SegBest& best, uint2& visits)
-{
-    best.d2 = INFINITY; best.slot = -1; best.prim = 0xFFFFFFFFu;
-    float thr = r2 * kNearRel + abs_term;
-    int sp = 0;
-    int node = (active && sc.n_tris != 0u) ? 0 : kSentinel;
-    while (node != kSentinel) {
-        if (node >= 0) {
-            float b0, b1;
-            int c0, c1;
-            if (FMT == 11) {
-                // child references of inner nodes are byte offsets into hcnodes; a leaf is ~slot
-                const uint4* np = (const uint4*)((const char*)sc.hcnodes + (size_t)(uint32_t)node);
-                const uint4 qa = np[0], qb = np[1];
-                b0 = seg_bound_hc(qa.x, qa.y, qa.z, sb, sc.hspace);
-                b1 = seg_bound_hc(qb.x, qb.y, qb.z, sb, sc.hspace);
-                c0 = (int)qa.w; c1 = (int)qb.w;
-            } else {
-                // child 0: lo (a.x a.y a.z) hi (a.w b.x b.y); child 1: lo (b.z b.w c.x) hi (c.y c.z c.w)
-                const BvhNode* np = sc.nodes + node;
-                const float4 na = np->a, nb = np->b, nc = np->c;
-                const int4 ch = np->d;
-                b0 = seg_bound_f32(sb, na.x, na.y, na.z, na.w, nb.x, nb.y);
-                b1 = seg_bound_f32(sb, nb.z, nb.w, nc.x, nc.y, nc.z, nc.w);
-                c0 = ch.x; c1 = ch.y;
-            }
-            if (COUNT) visits.x++;
-            const bool h0 = b0 <= thr, h1 = b1 <= thr;          // false for an empty child's NaN
-            if (h0 && h1) {
-                const bool first0 = b0 <= b1;
-                st.push(sp, first0 ? c1 : c0);
-                sp++;
-                node = first0 ? c0 : c1;
-            } else if (h0) {
-                node = c0;
-            } else if (h1) {
-                node = c1;
-            } else {
-                if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
-            }
-        } else {
-            const int slot = ~node;
-            const TriRecord* tp = sc.tris + slot;
-            const float4 r0 = tp->r0, r1 = tp->r1, r2_ = tp->r2;
-            const SegPoint p = segment_triangle<false>(p0, p1, d, a, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2_.x));
-            const uint32_t prim = __float_as_uint(r2_.y);
-            if (COUNT) visits.y++;
-            if (p.d2 <= r2 && (p.d2 < best.d2 || (p.d2 == best.d2 && prim < best.prim))) {
-                best.d2 = p.d2; best.slot = slot; best.prim = prim;
-                thr = p.d2 * kNearRel + abs_term;
-            }
-            if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
-        }
+// One segment per lane through the two-child BVH (bvh_walk.h): nearest.hip's walk with the segment's bound and statement.  thr is
+// min(best d2, r2) widened (segment.h): a child is entered iff its bound is at most thr and it is not empty; of two such children the
+// nearer is entered and the other pushed.  The boxes only prune: the winner is decided by the statement, d2 <= r2, smallest d2, ties to
+// the lowest triangle index, whatever order the walk reaches the triangles in.
+struct SegmentWalk {
+    f3 p0, p1, d;
+    float a;
+    SegBound sb;
+    float r2, abs_term, thr;
+    float d2; int slot; uint32_t prim;      // the best candidate so far
+    __device__ __forceinline__ SegmentWalk(const f3& p0_, const f3& p1_, const f3& d_, float a_, const SegBound& sb_, float r2_, float abs_term_)
+        : p0(p0_), p1(p1_), d(d_), a(a_), sb(sb_), r2(r2_), abs_term(abs_term_), thr(r2_ * kNearRel + abs_term_), d2(INFINITY), slot(-1), prim(0xFFFFFFFFu) {}
+    __device__ __forceinline__ void children_hc(const uint4& qa, const uint4& qb, const HSpace& hs, bool& h0, bool& h1, bool& first0) const
+    {
+        admit_by_bound(seg_bound_hc(qa.x, qa.y, qa.z, sb, hs), seg_bound_hc(qb.x, qb.y, qb.z, sb, hs), thr, h0, h1, first0);
     }
-}
+    __device__ __forceinline__ void children_f32(const float4& na, const float4& nb, const float4& nc, bool& h0, bool& h1, bool& first0) const
+    {
+        admit_by_bound(seg_bound_f32(sb, na.x, na.y, na.z, na.w, nb.x, nb.y), seg_bound_f32(sb, nb.z, nb.w, nc.x, nc.y, nc.z, nc.w), thr, h0, h1, first0);
+    }
+    __device__ __forceinline__ bool leaf(int slot_, const float4& r0, const float4& r1, const float4& r2_)
+    {
+        const SegPoint p = segment_triangle<false>(p0, p1, d, a, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2_.x));
+        const uint32_t prim_ = __float_as_uint(r2_.y);
+        if (p.d2 <= r2 && (p.d2 < d2 || (p.d2 == d2 && prim_ < prim))) {
+            d2 = p.d2; slot = slot_; prim = prim_;
+            thr = p.d2 * kNearRel + abs_term;
+        }
+        return false;
+    }
+};
 
 template <int FMT, bool COUNT>
 __global__ void __launch_bounds__(256)
@@ -197,8 +163,7 @@ k_query_segments(const DeviceScene sc, uint32_t stack_entries, float abs_term, c
                  uint2* __restrict__ visits_out, uint32_t flags)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;      // n <= 2^31 - 1: the grid's last lane is below 2^31 + 255
-    LaneStack st;
-    st.base = segment_lds + (threadIdx.x >> 6) * (stack_entries * 64u) + (threadIdx.x & 63u);
+    const LaneStack st = lane_stack(stack_entries);
     // segment i of the array, or an inert one for a lane past n.  ok: the lane has a segment and the segment can find something —
     // every coordinate and every component of d finite, max_radius >= 0 and no NaN (include/acgpt.h: "a miss before any traversal").
     // The eighth float is loaded with its float4 and never used.
@@ -227,9 +192,9 @@ k_query_segments(const DeviceScene sc, uint32_t stack_entries, float abs_term, c
     if (COUNT && (flags & kSegmentNoAxes)) { sb.xy = sb.xz = sb.yx = sb.yz = sb.zx = sb.zy = 0.0f; }
     const float qs = fmaxf(fmaxf(fmaxf(fabsf(p0.x), fabsf(p0.y)), fmaxf(fabsf(p0.z), fabsf(p1.x))), fmaxf(fabsf(p1.y), fabsf(p1.z)));
     const float lane_abs = segment_abs_term(abs_term, qs);
-    SegBest best;
+    SegmentWalk best(p0, p1, d, a, sb, r2, lane_abs);
     uint2 visits = make_uint2(0u, 0u);
-    traverse_segments<FMT, COUNT>(sc, st, ok, p0, p1, d, a, sb, r2, lane_abs, best, visits);
+    bvh_walk<FMT, COUNT>(sc, st, ok, best, visits);
     if (i >= n) return;
     float4 o0 = make_float4(-1.0f, __uint_as_float(0xFFFFFFFFu), 0.0f, 0.0f), o1 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
     if (ok && best.slot >= 0) {
@@ -247,29 +212,18 @@ k_query_segments(const DeviceScene sc, uint32_t stack_entries, float abs_term, c
     if (COUNT) visits_out[i] = visits;
 }
 
-template <typename K>
-static hipError_t launch_segments(K kernel, const DeviceScene& sc, uint32_t stack_entries, float abs_term, const float4* segments, uint32_t n, float4* out,
-                                  uint2* visits, uint32_t flags, hipStream_t stream)
-{
-    const size_t lds = (size_t)(256 / 64) * stack_entries * 64u * sizeof(uint32_t);
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    kernel<<<(n + 255u) / 256u, 256, lds, stream>>>(sc, stack_entries, abs_term, segments, n, out, visits, flags);
-    return hipGetLastError();
-}
-
 hipError_t launch_query_segments(int fmt, const DeviceScene& sc, uint32_t stack_entries, float abs_term, const float4* segments, uint32_t n, float4* out,
                                  hipStream_t stream)
 {
-    if (fmt == 11) return launch_segments(k_query_segments<11, false>, sc, stack_entries, abs_term, segments, n, out, nullptr, 0u, stream);
-    return launch_segments(k_query_segments<0, false>, sc, stack_entries, abs_term, segments, n, out, nullptr, 0u, stream);
+    if (fmt == 11) return launch_lane_stack(k_query_segments<11, false>, stack_entries, n, stream, sc, stack_entries, abs_term, segments, n, out, (uint2*)nullptr, 0u);
+    return launch_lane_stack(k_query_segments<0, false>, stack_entries, n, stream, sc, stack_entries, abs_term, segments, n, out, (uint2*)nullptr, 0u);
 }
 
 hipError_t launch_segments_visits(int fmt, const DeviceScene& sc, uint32_t stack_entries, float abs_term, const float4* segments, uint32_t n, float4* out,
                                   uint2* visits, uint32_t flags, hipStream_t stream)
 {
-    if (fmt == 11) return launch_segments(k_query_segments<11, true>, sc, stack_entries, abs_term, segments, n, out, visits, flags, stream);
-    return launch_segments(k_query_segments<0, true>, sc, stack_entries, abs_term, segments, n, out, visits, flags, stream);
+    if (fmt == 11) return launch_lane_stack(k_query_segments<11, true>, stack_entries, n, stream, sc, stack_entries, abs_term, segments, n, out, visits, flags);
+    return launch_lane_stack(k_query_segments<0, true>, stack_entries, n, stream, sc, stack_entries, abs_term, segments, n, out, visits, flags);
 }
 
 }  // namespace ptd

@@ -1,47 +1,13 @@
 // segment_device.h — the device functions the segment query (segment.hip) and the triangle-distance query (tridist.hip) share: the
-// closest point of a triangle to a point, the clamp and the segment-against-edge statement of include/acgpt.h's segment section.
+// closest point of a triangle to a point (closest_point.h: pt_query_nearest's own, features 0 and 1), the clamp and the
+// segment-against-edge statement of include/acgpt.h's segment section.
 // Evaluated as written (-ffp-contract=off); tests/segment_ref.py mirrors them operation for operation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "pt_device.h"
+#include "closest_point.h"
 
 namespace ptd {
-
-// nearest.hip's closest_on_triangle, operation for operation (pt_query_nearest's d2 and closest point): features 0 and 1.
-__device__ __forceinline__ float seg_closest_on_triangle(const f3& q, const f3& v0, const f3& ab, const f3& ac, f3& c)
-{
-    const f3 ap = q - v0;
-    const float d1 = dot(ab, ap), d2 = dot(ac, ap);
-    const f3 bp = ap - ab;
-    const float d3 = dot(ab, bp), d4 = dot(ac, bp);
-    const f3 cp = ap - ac;
-    const float d5 = dot(ab, cp), d6 = dot(ac, cp);
-    const float vc = d1 * d4 - d3 * d2;
-    const float vb = d5 * d2 - d1 * d6;
-    const float va = d3 * d6 - d5 * d4;
-    const float e43 = d4 - d3, e56 = d5 - d6;
-    const bool at_a = d1 <= 0.0f && d2 <= 0.0f;
-    const bool at_b = d3 >= 0.0f && d4 <= d3;
-    const bool on_ab = vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f;
-    const bool at_c = d6 >= 0.0f && d5 <= d6;
-    const bool on_ac = vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f;
-    const bool on_bc = va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f;
-    float num = 1.0f, den = (va + vb) + vc;
-    if (on_bc) { num = e43; den = e43 + e56; }
-    if (on_ac) { num = d2; den = d2 - d6; }
-    if (on_ab) { num = d1; den = d1 - d3; }
-    const float t = num / den;
-    float v = vb * t, w = vc * t;
-    if (on_bc) { v = 1.0f - t; w = t; }
-    if (on_ac) { v = 0.0f; w = t; }
-    if (at_c) { v = 0.0f; w = 1.0f; }
-    if (on_ab) { v = t; w = 0.0f; }
-    if (at_b) { v = 1.0f; w = 0.0f; }
-    if (at_a) { v = 0.0f; w = 0.0f; }
-    c = mk((v0.x + ab.x * v) + ac.x * w, (v0.y + ab.y * v) + ac.y * w, (v0.z + ab.z * v) + ac.z * w);
-    const f3 s = q - c;
-    return dot(s, s);
-}
 
 // Selects, not fminf / fmaxf: a -0 stays a -0 and a NaN a NaN, as in the NumPy statement.
 __device__ __forceinline__ float clamp01(float q)

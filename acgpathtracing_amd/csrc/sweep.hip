@@ -8,60 +8,18 @@
 //
 // FMT 11 walks the fp16 centre / half-extent nodes, FMT 0 the fp32 nodes: the node array the scene holds.  The walk is a slab test of
 // the centre line against each child box inflated by the radius (sweep.h: by a little more), clipped to [0, min(tmax, best t)] widened
-// (sweep.h), nearer child first.  256-lane workgroups over a one-dimensional grid, the LDS lane stack of query.hip (stack_entries * 64
+// (sweep.h), nearer child first.  256-lane workgroups over a one-dimensional grid, the lane stack of query_launch.h (stack_entries * 64
 // words per wave).  A sweep is one 32-byte load and a record two 16-byte stores per lane.  Lanes past n and lanes whose sweep is a
 // miss before any traversal stay in the wave, inactive.  No atomics: two calls give the same bits.
 // Built with -ffp-contract=off: the time of impact is evaluated as written, and tests/sweep_ref.py mirrors it operation for operation.
 // The box test is outside that contract (it only prunes) and uses explicit fused multiply-adds.
 #include "sweep.h"
+#include "bvh_walk.h"
+#include "closest_point.h"      // closest_on_triangle: the start-overlap test and the record's (u, v, c) are defined as pt_query_nearest's results
 
 #include <cfloat>
 
 namespace ptd {
-
-extern __shared__ uint32_t sweep_lds[];
-
-struct SweepPoint { float d2, v, w; f3 c; };
-
-// nearest.hip's closest_on_triangle, operation for operation (pt_query_nearest's d2, weights and closest point): the start-overlap test
-// and the record's (u, v, c) are defined as that function's results.
-__device__ __forceinline__ SweepPoint sweep_closest_on_triangle(const f3& q, const f3& v0, const f3& ab, const f3& ac)
-{
-    const f3 ap = q - v0;
-    const float d1 = dot(ab, ap), d2 = dot(ac, ap);
-    const f3 bp = ap - ab;
-    const float d3 = dot(ab, bp), d4 = dot(ac, bp);
-    const f3 cp = ap - ac;
-    const float d5 = dot(ab, cp), d6 = dot(ac, cp);
-    const float vc = d1 * d4 - d3 * d2;
-    const float vb = d5 * d2 - d1 * d6;
-    const float va = d3 * d6 - d5 * d4;
-    const float e43 = d4 - d3, e56 = d5 - d6;
-    const bool at_a = d1 <= 0.0f && d2 <= 0.0f;
-    const bool at_b = d3 >= 0.0f && d4 <= d3;
-    const bool on_ab = vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f;
-    const bool at_c = d6 >= 0.0f && d5 <= d6;
-    const bool on_ac = vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f;
-    const bool on_bc = va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f;
-    float num = 1.0f, den = (va + vb) + vc;
-    if (on_bc) { num = e43; den = e43 + e56; }
-    if (on_ac) { num = d2; den = d2 - d6; }
-    if (on_ab) { num = d1; den = d1 - d3; }
-    const float t = num / den;
-    float v = vb * t, w = vc * t;
-    if (on_bc) { v = 1.0f - t; w = t; }
-    if (on_ac) { v = 0.0f; w = t; }
-    if (at_c) { v = 0.0f; w = 1.0f; }
-    if (on_ab) { v = t; w = 0.0f; }
-    if (at_b) { v = 1.0f; w = 0.0f; }
-    if (at_a) { v = 0.0f; w = 0.0f; }
-    SweepPoint r;
-    r.v = v; r.w = w;
-    r.c = mk((v0.x + ab.x * v) + ac.x * w, (v0.y + ab.y * v) + ac.y * w, (v0.z + ab.z * v) + ac.z * w);
-    const f3 s = q - r.c;
-    r.d2 = dot(s, s);
-    return r;
-}
 
 // The three kinds of feature of the triangle's Minkowski sum with the sphere (include/acgpt.h states each operation).  Each lowers t
 // to its own time of entry when it is a candidate; every compare is false on a NaN, so a NaN anywhere leaves t as it was.  Selects on
@@ -114,7 +72,7 @@ __device__ __forceinline__ float sweep_triangle(const f3& o, const f3& d, float 
     sweep_edge(m0, e2, d, rr, t);
     sweep_edge(m1, e2 - e1, d, rr, t);
     sweep_face(m0, e1, e2, d, r, t);
-    const SweepPoint p = sweep_closest_on_triangle(o, v0, e1, e2);
+    const ClosestPoint p = closest_on_triangle(o, v0, e1, e2);
     if (p.d2 <= rr) t = 0.0f;
     return t;
 }
@@ -175,70 +133,42 @@ __device__ __forceinline__ void sweep_slab_f32(float lx, float ly, float lz, flo
     sweep_slab(c, e, s.inv, cut, !(lx <= hx), tn, tf);
 }
 
-struct SweepBest { float t; int slot; uint32_t prim; };
-
-// One sweep per lane through the two-child BVH.  A visit pushes at most one reference and descends one level, so the stack depth of
-// the ray walks (size_stack, capi.hip: max_depth + 1) holds here too.  A popped reference is entered without a second look at its
-// own box.  The boxes only prune: the winner is decided by the leaf test, t <= tmax, smallest t, ties to the lowest triangle index,
-// whatever order the walk reaches the triangles in.  ANY: leave at the first triangle with t <= tmax (best.slot >= 0 says so).
-template <int FMT, bool COUNT, bool ANY>
-__device__ __forceinline__ void traverse_sweep(const DeviceScene& sc, const LaneStack& st, bool active, const SweepRay& s, SweepBest& best, uint2& visits)
-{
-    best.t = INFINITY; best.slot = -1; best.prim = 0xFFFFFFFFu;
-    float cut = sweep_cut(s, s.tmax);
-    int sp = 0;
-    int node = (active && sc.n_tris != 0u) ? 0 : kSentinel;
-    while (node != kSentinel) {
-        if (node >= 0) {
-            float n0, f0, n1, f1;
-            int c0, c1;
-            if (FMT == 11) {
-                // child references of inner nodes are byte offsets into hcnodes; a leaf is ~slot
-                const uint4* np = (const uint4*)((const char*)sc.hcnodes + (size_t)(uint32_t)node);
-                const uint4 qa = np[0], qb = np[1];
-                sweep_slab_hc(qa.x, qa.y, qa.z, s, sc.hspace, cut, n0, f0);
-                sweep_slab_hc(qb.x, qb.y, qb.z, s, sc.hspace, cut, n1, f1);
-                c0 = (int)qa.w; c1 = (int)qb.w;
-            } else {
-                // child 0: lo (a.x a.y a.z) hi (a.w b.x b.y); child 1: lo (b.z b.w c.x) hi (c.y c.z c.w)
-                const BvhNode* np = sc.nodes + node;
-                const float4 a = np->a, b = np->b, c = np->c;
-                const int4 ch = np->d;
-                sweep_slab_f32(a.x, a.y, a.z, a.w, b.x, b.y, s, cut, n0, f0);
-                sweep_slab_f32(b.z, b.w, c.x, c.y, c.z, c.w, s, cut, n1, f1);
-                c0 = ch.x; c1 = ch.y;
-            }
-            if (COUNT) visits.x++;
-            const bool h0 = n0 <= f0, h1 = n1 <= f1;          // false for an empty child's NaN
-            if (h0 && h1) {
-                const bool first0 = n0 <= n1;
-                st.push(sp, first0 ? c1 : c0);
-                sp++;
-                node = first0 ? c0 : c1;
-            } else if (h0) {
-                node = c0;
-            } else if (h1) {
-                node = c1;
-            } else {
-                if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
-            }
-        } else {
-            const int slot = ~node;
-            const TriRecord* tp = sc.tris + slot;
-            const float4 r0 = tp->r0, r1 = tp->r1, r2 = tp->r2;
-            const float t = sweep_triangle(s.o, s.d, s.dd, s.r, s.rr, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x));
-            const uint32_t prim = __float_as_uint(r2.y);
-            if (COUNT) visits.y++;
-            if (ANY) {
-                if (t <= s.tmax) { best.slot = slot; node = kSentinel; continue; }
-            } else if (t <= s.tmax && (t < best.t || (t == best.t && prim < best.prim))) {
-                best.t = t; best.slot = slot; best.prim = prim;
-                cut = sweep_cut(s, t);
-            }
-            if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
-        }
+// One sweep per lane through the two-child BVH (bvh_walk.h: the stack depth, the one-word entries).  The boxes only prune: the winner
+// is decided by the leaf test, t <= tmax, smallest t, ties to the lowest triangle index, whatever order the walk reaches the triangles
+// in.  ANY: leave at the first triangle with t <= tmax (slot >= 0 says so).
+template <bool ANY>
+struct SweepWalk {
+    SweepRay s;
+    float cut;
+    float t; int slot; uint32_t prim;      // the best candidate so far
+    __device__ __forceinline__ explicit SweepWalk(const SweepRay& s_) : s(s_), cut(sweep_cut(s_, s_.tmax)), t(INFINITY), slot(-1), prim(0xFFFFFFFFu) {}
+    __device__ __forceinline__ void children_hc(const uint4& qa, const uint4& qb, const HSpace& hs, bool& h0, bool& h1, bool& first0) const
+    {
+        float n0, f0, n1, f1;
+        sweep_slab_hc(qa.x, qa.y, qa.z, s, hs, cut, n0, f0);
+        sweep_slab_hc(qb.x, qb.y, qb.z, s, hs, cut, n1, f1);
+        admit_by_interval(n0, f0, n1, f1, h0, h1, first0);
     }
-}
+    __device__ __forceinline__ void children_f32(const float4& a, const float4& b, const float4& c, bool& h0, bool& h1, bool& first0) const
+    {
+        float n0, f0, n1, f1;
+        sweep_slab_f32(a.x, a.y, a.z, a.w, b.x, b.y, s, cut, n0, f0);
+        sweep_slab_f32(b.z, b.w, c.x, c.y, c.z, c.w, s, cut, n1, f1);
+        admit_by_interval(n0, f0, n1, f1, h0, h1, first0);
+    }
+    __device__ __forceinline__ bool leaf(int slot_, const float4& r0, const float4& r1, const float4& r2)
+    {
+        const float t_ = sweep_triangle(s.o, s.d, s.dd, s.r, s.rr, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x));
+        const uint32_t prim_ = __float_as_uint(r2.y);
+        if (ANY) {
+            if (t_ <= s.tmax) { slot = slot_; return true; }
+        } else if (t_ <= s.tmax && (t_ < t || (t_ == t && prim_ < prim))) {
+            t = t_; slot = slot_; prim = prim_;
+            cut = sweep_cut(s, t_);
+        }
+        return false;
+    }
+};
 
 // sweep i of the array, or an inert one for a lane past n.  Returns whether the lane has a sweep that can touch something: o and d
 // finite, radius finite and >= 0, tmax >= 0 and no NaN (include/acgpt.h: "a miss before any traversal")
@@ -259,13 +189,12 @@ k_query_sweep(const DeviceScene sc, uint32_t stack_entries, float scene_scale, c
               uint2* __restrict__ visits_out)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;      // n <= 2^31 - 1: the grid's last lane is below 2^31 + 255
-    LaneStack st;
-    st.base = sweep_lds + (threadIdx.x >> 6) * (stack_entries * 64u) + (threadIdx.x & 63u);
+    const LaneStack st = lane_stack(stack_entries);
     SweepRay s;
     const bool ok = sweep_load(sweeps, i, n, scene_scale, sc.hspace, s);
-    SweepBest best;
+    SweepWalk<false> best(s);
     uint2 visits = make_uint2(0u, 0u);
-    traverse_sweep<FMT, COUNT, false>(sc, st, ok, s, best, visits);
+    bvh_walk<FMT, COUNT>(sc, st, ok, best, visits);
     if (i >= n) return;
     float4 o0 = make_float4(-1.0f, __uint_as_float(0xFFFFFFFFu), 0.0f, 0.0f), o1 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
     if (ok && best.slot >= 0) {
@@ -273,7 +202,7 @@ k_query_sweep(const DeviceScene sc, uint32_t stack_entries, float scene_scale, c
         const TriRecord* tp = sc.tris + best.slot;
         const float4 r0 = tp->r0, r1 = tp->r1, r2 = tp->r2;
         const f3 centre = mk(s.o.x + s.d.x * best.t, s.o.y + s.d.y * best.t, s.o.z + s.d.z * best.t);
-        const SweepPoint p = sweep_closest_on_triangle(centre, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x));
+        const ClosestPoint p = closest_on_triangle(centre, r0, r1, r2);
         const float4 sr = sc.shade[best.slot];
         o0 = make_float4(best.t, __uint_as_float(best.prim), p.v, p.w);
         o1 = make_float4(p.c.x, p.c.y, p.c.z, __uint_as_float(__float_as_uint(sr.w) & kShadeMatMask));
@@ -288,71 +217,37 @@ __global__ void __launch_bounds__(256)
 k_query_sweep_any(const DeviceScene sc, uint32_t stack_entries, float scene_scale, const float4* __restrict__ sweeps, uint32_t n, uint8_t* __restrict__ blocked)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    LaneStack st;
-    st.base = sweep_lds + (threadIdx.x >> 6) * (stack_entries * 64u) + (threadIdx.x & 63u);
+    const LaneStack st = lane_stack(stack_entries);
     SweepRay s;
     const bool ok = sweep_load(sweeps, i, n, scene_scale, sc.hspace, s);
-    SweepBest best;
+    SweepWalk<true> best(s);
     uint2 visits = make_uint2(0u, 0u);
-    traverse_sweep<FMT, false, true>(sc, st, ok, s, best, visits);
+    bvh_walk<FMT, false>(sc, st, ok, best, visits);
     if (i >= n) return;
     blocked[i] = (ok && best.slot >= 0) ? (uint8_t)1 : (uint8_t)0;
 }
 
-static size_t sweep_lds_bytes(uint32_t stack_entries) { return (size_t)(256 / 64) * stack_entries * 64u * sizeof(uint32_t); }
-
-template <typename K>
-static hipError_t launch_sweep(K kernel, const DeviceScene& sc, uint32_t stack_entries, float scene_scale, const float4* sweeps, uint32_t n, float4* out,
-                               uint2* visits, hipStream_t stream)
-{
-    const size_t lds = sweep_lds_bytes(stack_entries);
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    kernel<<<(n + 255u) / 256u, 256, lds, stream>>>(sc, stack_entries, scene_scale, sweeps, n, out, visits);
-    return hipGetLastError();
-}
-
-template <typename K>
-static hipError_t launch_sweep_any(K kernel, const DeviceScene& sc, uint32_t stack_entries, float scene_scale, const float4* sweeps, uint32_t n,
-                                   uint8_t* blocked, hipStream_t stream)
-{
-    const size_t lds = sweep_lds_bytes(stack_entries);
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    kernel<<<(n + 255u) / 256u, 256, lds, stream>>>(sc, stack_entries, scene_scale, sweeps, n, blocked);
-    return hipGetLastError();
-}
-
-float sweep_scene_scale(const float scene_lo[3], const float scene_hi[3])
-{
-    float s = 0.0f;
-    for (int k = 0; k < 3; k++) {
-        const float a = fabsf(scene_lo[k]), b = fabsf(scene_hi[k]);
-        if (a > s && a < INFINITY) s = a;
-        if (b > s && b < INFINITY) s = b;
-    }
-    return s;
-}
+float sweep_scene_scale(const float scene_lo[3], const float scene_hi[3]) { return scene_max_abs(scene_lo, scene_hi); }
 
 hipError_t launch_query_sweep(int fmt, const DeviceScene& sc, uint32_t stack_entries, float scene_scale, const float4* sweeps, uint32_t n, float4* out,
                               hipStream_t stream)
 {
-    if (fmt == 11) return launch_sweep(k_query_sweep<11, false>, sc, stack_entries, scene_scale, sweeps, n, out, nullptr, stream);
-    return launch_sweep(k_query_sweep<0, false>, sc, stack_entries, scene_scale, sweeps, n, out, nullptr, stream);
+    if (fmt == 11) return launch_lane_stack(k_query_sweep<11, false>, stack_entries, n, stream, sc, stack_entries, scene_scale, sweeps, n, out, (uint2*)nullptr);
+    return launch_lane_stack(k_query_sweep<0, false>, stack_entries, n, stream, sc, stack_entries, scene_scale, sweeps, n, out, (uint2*)nullptr);
 }
 
 hipError_t launch_query_sweep_any(int fmt, const DeviceScene& sc, uint32_t stack_entries, float scene_scale, const float4* sweeps, uint32_t n,
                                   uint8_t* blocked, hipStream_t stream)
 {
-    if (fmt == 11) return launch_sweep_any(k_query_sweep_any<11>, sc, stack_entries, scene_scale, sweeps, n, blocked, stream);
-    return launch_sweep_any(k_query_sweep_any<0>, sc, stack_entries, scene_scale, sweeps, n, blocked, stream);
+    if (fmt == 11) return launch_lane_stack(k_query_sweep_any<11>, stack_entries, n, stream, sc, stack_entries, scene_scale, sweeps, n, blocked);
+    return launch_lane_stack(k_query_sweep_any<0>, stack_entries, n, stream, sc, stack_entries, scene_scale, sweeps, n, blocked);
 }
 
 hipError_t launch_sweep_visits(int fmt, const DeviceScene& sc, uint32_t stack_entries, float scene_scale, const float4* sweeps, uint32_t n, float4* out,
                                uint2* visits, hipStream_t stream)
 {
-    if (fmt == 11) return launch_sweep(k_query_sweep<11, true>, sc, stack_entries, scene_scale, sweeps, n, out, visits, stream);
-    return launch_sweep(k_query_sweep<0, true>, sc, stack_entries, scene_scale, sweeps, n, out, visits, stream);
+    if (fmt == 11) return launch_lane_stack(k_query_sweep<11, true>, stack_entries, n, stream, sc, stack_entries, scene_scale, sweeps, n, out, visits);
+    return launch_lane_stack(k_query_sweep<0, true>, stack_entries, n, stream, sc, stack_entries, scene_scale, sweeps, n, out, visits);
 }
 
 }  // namespace ptd

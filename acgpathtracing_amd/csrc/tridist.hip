@@ -8,20 +8,19 @@
 //
 // The shape is segment.hip's: FMT 11 walks the fp16 centre / half-extent nodes, FMT 0 the fp32 nodes; the walk is ordered by a lower
 // bound of the squared distance from the query triangle to each child box, and the leaves run the triangle-to-triangle statement.
-// 256-lane workgroups over a one-dimensional grid, the LDS lane stack of query.hip (stack_entries * 64 words per wave).  A query is
+// 256-lane workgroups over a one-dimensional grid, the lane stack of query_launch.h (stack_entries * 64 words per wave).  A query is
 // three 16-byte loads and a record three 16-byte stores per lane.  Lanes past n and lanes whose query is a miss before any traversal
 // stay in the wave, inactive.  No atomics: two calls give the same bits.
 // Built with -ffp-contract=off: the statement is evaluated as written, and tests/tridist_ref.py mirrors it operation for operation.
 // The box bounds are outside that contract (they only prune) and use explicit fused multiply-adds.
 #include "tridist.h"
+#include "bvh_walk.h"
 #include "segment_device.h"
 
 namespace ptd {
 
-extern __shared__ uint32_t tridist_lds[];
-
 // What a lane keeps of its query triangle: the vertices as given and the three edge vectors, one subtraction per component.
-struct TriQuery { f3 a0, a1, a2, f1, f2, g; };
+struct TriDistQuery { f3 a0, a1, a2, f1, f2, g; };
 
 struct TriPair { float d2, feature; f3 q, c; };
 
@@ -80,28 +79,30 @@ __device__ __forceinline__ void tri_cross(TriPair& best, bool& crossed, float fe
 // the same operations on the same inputs, so the same bits.  The three query edges are loops that are not unrolled: the edge is
 // picked by selects on a wave-uniform counter, and one copy of three edge tests is what the registers hold.
 template <bool FULL>
-__device__ __forceinline__ TriPair triangle_triangle(const TriQuery& t, const f3& v0, const f3& e1, const f3& e2)
+__device__ __forceinline__ TriPair triangle_triangle(const TriDistQuery& t, const f3& v0, const f3& e1, const f3& e2)
 {
     TriPair best;
-    f3 c, q;
+    f3 c;
     float s = 0.0f;
     // features 0, 1, 2: the query's vertices against the scene triangle
-    best.d2 = seg_closest_on_triangle(t.a0, v0, e1, e2, best.c);
+    ClosestPoint cp = closest_on_triangle(t.a0, v0, e1, e2);
+    best.d2 = cp.d2; best.c = cp.c;
     best.q = t.a0; best.feature = 0.0f;
     asm volatile("" : "+v"(best.d2));
     __builtin_amdgcn_sched_barrier(0);
-    float d2 = seg_closest_on_triangle(t.a1, v0, e1, e2, c);
-    tri_take<FULL>(best, d2, 1.0f, t.a1, c);
-    d2 = seg_closest_on_triangle(t.a2, v0, e1, e2, c);
-    tri_take<FULL>(best, d2, 2.0f, t.a2, c);
+    cp = closest_on_triangle(t.a1, v0, e1, e2);
+    tri_take<FULL>(best, cp.d2, 1.0f, t.a1, cp.c);
+    cp = closest_on_triangle(t.a2, v0, e1, e2);
+    tri_take<FULL>(best, cp.d2, 2.0f, t.a2, cp.c);
     // features 3, 4, 5: the scene triangle's vertices against the query
     const f3 w1 = v0 + e1, w2 = v0 + e2, h = e2 - e1;
-    d2 = seg_closest_on_triangle(v0, t.a0, t.f1, t.f2, q);
-    tri_take<FULL>(best, d2, 3.0f, q, v0);
-    d2 = seg_closest_on_triangle(w1, t.a0, t.f1, t.f2, q);
-    tri_take<FULL>(best, d2, 4.0f, q, w1);
-    d2 = seg_closest_on_triangle(w2, t.a0, t.f1, t.f2, q);
-    tri_take<FULL>(best, d2, 5.0f, q, w2);
+    cp = closest_on_triangle(v0, t.a0, t.f1, t.f2);
+    tri_take<FULL>(best, cp.d2, 3.0f, cp.c, v0);
+    cp = closest_on_triangle(w1, t.a0, t.f1, t.f2);
+    tri_take<FULL>(best, cp.d2, 4.0f, cp.c, w1);
+    cp = closest_on_triangle(w2, t.a0, t.f1, t.f2);
+    tri_take<FULL>(best, cp.d2, 5.0f, cp.c, w2);
+    float d2;
     // features 6 + 3 i + j: query edge i against scene edge j, the segment query's own edge order on both sides
 #pragma unroll 1
     for (int i = 0; i < 3; i++) {
@@ -170,70 +171,36 @@ __device__ __forceinline__ float tri_bound_f32(const TriBound& tb, float lx, flo
     return lx <= hx ? b : __builtin_nanf("");
 }
 
-struct TriBest { float d2; int slot; uint32_t prim; };
-
-// One query per lane through the two-child BVH: traverse_segments' walk (segment.hip) with the triangle's bound and statement.  A child
-// is entered iff its bound is at most thr and it is not empty; of two such children the nearer is entered and the other pushed.  A
-// visit pushes at most one reference and descends one level, so max_depth + 1 entries hold here too.  The boxes only prune: the
-// winner is decided by the statement, d2 <= r2, smallest d2, ties to the lowest triangle index, whatever order the walk reaches the
-// triangles in.
-template <int FMT, bool COUNT>
-__device__ __forceinline__ void traverse_triangle_distance(const DeviceScene& sc, const LaneStack& st, bool active, const TriQuery& t, const TriBound& tb, float r2,
-                                                           float abs_term, TriBest& best, uint2& visits)
-{
-    best.d2 = INFINITY; best.slot = -1; best.prim = 0xFFFFFFFFu;
-    float thr = r2 * kNearRel + abs_term;
-    int sp = 0;
-    int node = (active && sc.n_tris != 0u) ? 0 : kSentinel;
-    while (node != kSentinel) {
-        if (node >= 0) {
-            float b0, b1;
-            int c0, c1;
-            if (FMT == 11) {
-                // child references of inner nodes are byte offsets into hcnodes; a leaf is ~slot
-                const uint4* np = (const uint4*)((const char*)sc.hcnodes + (size_t)(uint32_t)node);
-                const uint4 qa = np[0], qb = np[1];
-                b0 = tri_bound_hc(qa.x, qa.y, qa.z, tb, sc.hspace);
-                b1 = tri_bound_hc(qb.x, qb.y, qb.z, tb, sc.hspace);
-                c0 = (int)qa.w; c1 = (int)qb.w;
-            } else {
-                // child 0: lo (a.x a.y a.z) hi (a.w b.x b.y); child 1: lo (b.z b.w c.x) hi (c.y c.z c.w)
-                const BvhNode* np = sc.nodes + node;
-                const float4 na = np->a, nb = np->b, nc = np->c;
-                const int4 ch = np->d;
-                b0 = tri_bound_f32(tb, na.x, na.y, na.z, na.w, nb.x, nb.y);
-                b1 = tri_bound_f32(tb, nb.z, nb.w, nc.x, nc.y, nc.z, nc.w);
-                c0 = ch.x; c1 = ch.y;
-            }
-            if (COUNT) visits.x++;
-            const bool h0 = b0 <= thr, h1 = b1 <= thr;          // false for an empty child's NaN
-            if (h0 && h1) {
-                const bool first0 = b0 <= b1;
-                st.push(sp, first0 ? c1 : c0);
-                sp++;
-                node = first0 ? c0 : c1;
-            } else if (h0) {
-                node = c0;
-            } else if (h1) {
-                node = c1;
-            } else {
-                if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
-            }
-        } else {
-            const int slot = ~node;
-            const TriRecord* tp = sc.tris + slot;
-            const float4 r0 = tp->r0, r1 = tp->r1, r2_ = tp->r2;
-            const TriPair p = triangle_triangle<false>(t, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2_.x));
-            const uint32_t prim = __float_as_uint(r2_.y);
-            if (COUNT) visits.y++;
-            if (p.d2 <= r2 && (p.d2 < best.d2 || (p.d2 == best.d2 && prim < best.prim))) {
-                best.d2 = p.d2; best.slot = slot; best.prim = prim;
-                thr = p.d2 * kNearRel + abs_term;
-            }
-            if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
-        }
+// One query per lane through the two-child BVH (bvh_walk.h): segment.hip's walk with the triangle's bound and statement.  A child is
+// entered iff its bound is at most thr and it is not empty; of two such children the nearer is entered and the other pushed.  The
+// boxes only prune: the winner is decided by the statement, d2 <= r2, smallest d2, ties to the lowest triangle index, whatever order
+// the walk reaches the triangles in.
+struct TriDistWalk {
+    TriDistQuery t;
+    TriBound tb;
+    float r2, abs_term, thr;
+    float d2; int slot; uint32_t prim;      // the best candidate so far
+    __device__ __forceinline__ TriDistWalk(const TriDistQuery& t_, const TriBound& tb_, float r2_, float abs_term_)
+        : t(t_), tb(tb_), r2(r2_), abs_term(abs_term_), thr(r2_ * kNearRel + abs_term_), d2(INFINITY), slot(-1), prim(0xFFFFFFFFu) {}
+    __device__ __forceinline__ void children_hc(const uint4& qa, const uint4& qb, const HSpace& hs, bool& h0, bool& h1, bool& first0) const
+    {
+        admit_by_bound(tri_bound_hc(qa.x, qa.y, qa.z, tb, hs), tri_bound_hc(qb.x, qb.y, qb.z, tb, hs), thr, h0, h1, first0);
     }
-}
+    __device__ __forceinline__ void children_f32(const float4& na, const float4& nb, const float4& nc, bool& h0, bool& h1, bool& first0) const
+    {
+        admit_by_bound(tri_bound_f32(tb, na.x, na.y, na.z, na.w, nb.x, nb.y), tri_bound_f32(tb, nb.z, nb.w, nc.x, nc.y, nc.z, nc.w), thr, h0, h1, first0);
+    }
+    __device__ __forceinline__ bool leaf(int slot_, const float4& r0, const float4& r1, const float4& r2_)
+    {
+        const TriPair p = triangle_triangle<false>(t, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2_.x));
+        const uint32_t prim_ = __float_as_uint(r2_.y);
+        if (p.d2 <= r2 && (p.d2 < d2 || (p.d2 == d2 && prim_ < prim))) {
+            d2 = p.d2; slot = slot_; prim = prim_;
+            thr = p.d2 * kNearRel + abs_term;
+        }
+        return false;
+    }
+};
 
 template <int FMT, bool COUNT>
 __global__ void __launch_bounds__(256)
@@ -241,12 +208,11 @@ k_query_triangle_distance(const DeviceScene sc, uint32_t stack_entries, float ab
                           uint2* __restrict__ visits_out, uint32_t flags)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;      // n <= 2^31 - 1: the grid's last lane is below 2^31 + 255
-    LaneStack st;
-    st.base = tridist_lds + (threadIdx.x >> 6) * (stack_entries * 64u) + (threadIdx.x & 63u);
+    const LaneStack st = lane_stack(stack_entries);
     // query i of the array, or an inert one for a lane past n.  ok: the lane has a query and the query can find something — every
     // coordinate and every component of the three edge vectors finite, max_radius >= 0 and no NaN (include/acgpt.h: "a miss before
     // any traversal").  The eighth and twelfth float are loaded with their float4 and never used.
-    TriQuery t;
+    TriDistQuery t;
     t.a0 = t.a1 = t.a2 = t.f1 = t.f2 = t.g = mk(0.0f);
     float r2 = 0.0f;
     bool ok = false;
@@ -283,9 +249,9 @@ k_query_triangle_distance(const DeviceScene sc, uint32_t stack_entries, float ab
     if (FMT == 11) tb.m = mk(tb.m.x - sc.hspace.cx, tb.m.y - sc.hspace.cy, tb.m.z - sc.hspace.cz);
     const float qs = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(hi.x))), fmaxf(fabsf(hi.y), fabsf(hi.z)));
     const float lane_abs = segment_abs_term(abs_term, qs);
-    TriBest best;
+    TriDistWalk best(t, tb, r2, lane_abs);
     uint2 visits = make_uint2(0u, 0u);
-    traverse_triangle_distance<FMT, COUNT>(sc, st, ok, t, tb, r2, lane_abs, best, visits);
+    bvh_walk<FMT, COUNT>(sc, st, ok, best, visits);
     if (i >= n) return;
     float4 o0 = make_float4(-1.0f, __uint_as_float(0xFFFFFFFFu), 0.0f, __uint_as_float(0xFFFFFFFFu)), o1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), o2 = o1;
     if (ok && best.slot >= 0) {
@@ -305,29 +271,18 @@ k_query_triangle_distance(const DeviceScene sc, uint32_t stack_entries, float ab
     if (COUNT) visits_out[i] = visits;
 }
 
-template <typename K>
-static hipError_t launch_tridist(K kernel, const DeviceScene& sc, uint32_t stack_entries, float abs_term, const float4* tris, uint32_t n, float4* out,
-                                 uint2* visits, uint32_t flags, hipStream_t stream)
-{
-    const size_t lds = (size_t)(256 / 64) * stack_entries * 64u * sizeof(uint32_t);
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    kernel<<<(n + 255u) / 256u, 256, lds, stream>>>(sc, stack_entries, abs_term, tris, n, out, visits, flags);
-    return hipGetLastError();
-}
-
 hipError_t launch_query_triangle_distance(int fmt, const DeviceScene& sc, uint32_t stack_entries, float abs_term, const float4* tris, uint32_t n, float4* out,
                                           hipStream_t stream)
 {
-    if (fmt == 11) return launch_tridist(k_query_triangle_distance<11, false>, sc, stack_entries, abs_term, tris, n, out, nullptr, 0u, stream);
-    return launch_tridist(k_query_triangle_distance<0, false>, sc, stack_entries, abs_term, tris, n, out, nullptr, 0u, stream);
+    if (fmt == 11) return launch_lane_stack(k_query_triangle_distance<11, false>, stack_entries, n, stream, sc, stack_entries, abs_term, tris, n, out, (uint2*)nullptr, 0u);
+    return launch_lane_stack(k_query_triangle_distance<0, false>, stack_entries, n, stream, sc, stack_entries, abs_term, tris, n, out, (uint2*)nullptr, 0u);
 }
 
 hipError_t launch_triangle_distance_visits(int fmt, const DeviceScene& sc, uint32_t stack_entries, float abs_term, const float4* tris, uint32_t n, float4* out,
                                            uint2* visits, uint32_t flags, hipStream_t stream)
 {
-    if (fmt == 11) return launch_tridist(k_query_triangle_distance<11, true>, sc, stack_entries, abs_term, tris, n, out, visits, flags, stream);
-    return launch_tridist(k_query_triangle_distance<0, true>, sc, stack_entries, abs_term, tris, n, out, visits, flags, stream);
+    if (fmt == 11) return launch_lane_stack(k_query_triangle_distance<11, true>, stack_entries, n, stream, sc, stack_entries, abs_term, tris, n, out, visits, flags);
+    return launch_lane_stack(k_query_triangle_distance<0, true>, stack_entries, n, stream, sc, stack_entries, abs_term, tris, n, out, visits, flags);
 }
 
 }  // namespace ptd

@@ -8,7 +8,7 @@
 //                                       it tested (the test hook's instantiation).
 //
 // The shape is overlap.hip's: FMT 11 walks the fp16 centre / half-extent nodes, FMT 0 the fp32 nodes; 256-lane workgroups over a
-// one-dimensional grid, the LDS lane stack of query.hip (stack_entries * 64 words per wave), the sorted list in registers.  A query is
+// one-dimensional grid, the lane stack of query_launch.h (stack_entries * 64 words per wave), the sorted list in registers.  A query is
 // three 16-byte loads per lane.  Lanes past n and lanes whose triangle is a miss before any traversal stay in the wave, inactive.  No
 // atomics: two calls give the same bits.
 //
@@ -17,83 +17,19 @@
 // mirrors it operation for operation.  The child boxes of the fp16 nodes are outside that contract (they only prune) and use explicit
 // fused multiply-adds.
 #include "tritri.h"
+#include "bvh_walk.h"
 #include "tritri_device.h"
 
 namespace ptd {
 
-extern __shared__ uint32_t tritri_lds[];
-
 enum { kList = 0, kAny = 1, kVisits = 2 };
 
-// axis_keeps, fold, tri_tri_intersect, the child-box admission of both formats and the sorted register list: tritri_device.h,
-// which lists.hip shares.
-
-// One query triangle per lane through the two-child BVH, as traverse_overlap walks a box: of two admitted children the first is
-// entered and the second pushed, so a visit pushes at most one reference per level and max_depth + 1 stack entries suffice; a popped
-// reference is entered without a second look at its own box.  The boxes only prune: which pairs intersect is decided by
-// tri_tri_intersect alone, whatever order the walk reaches them in.
-template <int FMT, int CAP, int MODE>
-__device__ __forceinline__ void traverse_triangles(const DeviceScene& sc, const LaneStack& st, bool active, const f3& a0, const f3& f1, const f3& f2, const f3& qlo,
-                                                   const f3& qhi, float scene_term, uint32_t max_prims, PrimList<CAP>& L, uint32_t& count, uint2& visits)
-{
-#pragma unroll
-    for (int j = 0; j < CAP; j++) L.prim[j] = 0xFFFFFFFFu;
-    count = 0u;
-    // FMT 11 only: the query box as centre and half extent (the halves are exact, the sum and the difference round once each)
-    const f3 c = mk(0.5f * qlo.x + 0.5f * qhi.x, 0.5f * qlo.y + 0.5f * qhi.y, 0.5f * qlo.z + 0.5f * qhi.z);
-    const f3 h = mk(0.5f * qhi.x - 0.5f * qlo.x, 0.5f * qhi.y - 0.5f * qlo.y, 0.5f * qhi.z - 0.5f * qlo.z);
-    const f3 thr = mk(h.x + (scene_term + (fabsf(c.x) + h.x) * kOverlapQuery), h.y + (scene_term + (fabsf(c.y) + h.y) * kOverlapQuery),
-                      h.z + (scene_term + (fabsf(c.z) + h.z) * kOverlapQuery));
-    const f3 qc = mk(c.x - sc.hspace.cx, c.y - sc.hspace.cy, c.z - sc.hspace.cz);
-    int sp = 0;
-    int node = (active && sc.n_tris != 0u) ? 0 : kSentinel;
-    while (node != kSentinel) {
-        if (node >= 0) {
-            bool h0, h1;
-            int c0, c1;
-            if (FMT == 11) {
-                // child references of inner nodes are byte offsets into hcnodes; a leaf is ~slot
-                const uint4* np = (const uint4*)((const char*)sc.hcnodes + (size_t)(uint32_t)node);
-                const uint4 qa = np[0], qb = np[1];
-                h0 = child_admitted_hc(qa.x, qa.y, qa.z, qc, sc.hspace, thr);
-                h1 = child_admitted_hc(qb.x, qb.y, qb.z, qc, sc.hspace, thr);
-                c0 = (int)qa.w; c1 = (int)qb.w;
-            } else {
-                // child 0: lo (a.x a.y a.z) hi (a.w b.x b.y); child 1: lo (b.z b.w c.x) hi (c.y c.z c.w)
-                const BvhNode* np = sc.nodes + node;
-                const float4 a = np->a, b = np->b, cc = np->c;
-                const int4 ch = np->d;
-                h0 = child_admitted_f32(qlo, qhi, a.x, a.y, a.z, a.w, b.x, b.y);
-                h1 = child_admitted_f32(qlo, qhi, b.z, b.w, cc.x, cc.y, cc.z, cc.w);
-                c0 = ch.x; c1 = ch.y;
-            }
-            if (MODE == kVisits) visits.x++;
-            if (h0 && h1) {
-                st.push(sp, c1);
-                sp++;
-                node = c0;
-            } else if (h0) {
-                node = c0;
-            } else if (h1) {
-                node = c1;
-            } else {
-                if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
-            }
-        } else {
-            const int slot = ~node;
-            const TriRecord* tp = sc.tris + slot;
-            const float4 r0 = tp->r0, r1 = tp->r1, r2 = tp->r2;
-            const bool ok = tri_tri_intersect(a0, f1, f2, qlo, qhi, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x));
-            if (MODE == kVisits) visits.y++;
-            if (ok) {
-                count++;
-                if (MODE == kAny) { node = kSentinel; continue; }
-                if constexpr (CAP > 0) list_insert(L, max_prims, __float_as_uint(r2.y));
-            }
-            if (sp == 0) node = kSentinel; else { sp--; node = st.pop(sp); }
-        }
-    }
-}
+// axis_keeps, fold, tri_tri_intersect, the child-box admission of both formats, the sorted register list, the query record TriQuery and
+// the walk's policy PrimListWalk: tritri_device.h and overlap_device.h, which lists.hip shares.
+//
+// One query triangle per lane through the two-child BVH (bvh_walk.h), as overlap.hip walks a box: of two admitted children the first
+// is entered and the second pushed.  The boxes only prune: which pairs intersect is decided by tri_tri_intersect alone, whatever order
+// the walk reaches them in.
 
 // out8: the any byte per query (kAny).  prims / counts: the list and the number (kList; either may be null), counts alone (kVisits).
 template <int FMT, int CAP, int MODE>
@@ -102,26 +38,17 @@ k_query_triangles(const DeviceScene sc, uint32_t stack_entries, float scene_term
                   uint32_t* __restrict__ prims, uint32_t* __restrict__ counts, uint8_t* __restrict__ out8, uint2* __restrict__ visits_out)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;      // n <= 2^31 - 1: the grid's last lane is below 2^31 + 255
-    LaneStack st;
-    st.base = tritri_lds + (threadIdx.x >> 6) * (stack_entries * 64u) + (threadIdx.x & 63u);
+    const LaneStack st = lane_stack(stack_entries);
     // triangle i of the array, or an inert one for a lane past n.  ok: the lane has a triangle and its nine coordinates are finite
     // (include/acgpt.h: "a miss before any traversal").  The fourth float of each vertex is not looked at.
-    f3 a0 = mk(0.0f), a1 = mk(0.0f), a2 = mk(0.0f);
-    bool ok = false;
-    if (i < n) {
-        const float4 r0 = tris[3ull * i], r1 = tris[3ull * i + 1ull], r2 = tris[3ull * i + 2ull];
-        a0 = mk(r0.x, r0.y, r0.z);
-        a1 = mk(r1.x, r1.y, r1.z);
-        a2 = mk(r2.x, r2.y, r2.z);
-        ok = __builtin_isfinite(r0.x) && __builtin_isfinite(r0.y) && __builtin_isfinite(r0.z) && __builtin_isfinite(r1.x) && __builtin_isfinite(r1.y) &&
-             __builtin_isfinite(r1.z) && __builtin_isfinite(r2.x) && __builtin_isfinite(r2.y) && __builtin_isfinite(r2.z);
-    }
-    const f3 qlo = mk(fmin3(a0.x, a1.x, a2.x), fmin3(a0.y, a1.y, a2.y), fmin3(a0.z, a1.z, a2.z));
-    const f3 qhi = mk(fmax3(a0.x, a1.x, a2.x), fmax3(a0.y, a1.y, a2.y), fmax3(a0.z, a1.z, a2.z));
+    TriQuery q;
+    const bool ok = q.load(tris, i, n);
+    q.prepare(sc, scene_term);
     PrimList<CAP> L;
-    uint32_t count;
+    PrimListWalk<TriQuery, CAP, MODE == kAny> walk(q, max_prims, L);
     uint2 visits = make_uint2(0u, 0u);
-    traverse_triangles<FMT, CAP, MODE>(sc, st, ok, a0, a1 - a0, a2 - a0, qlo, qhi, scene_term, max_prims, L, count, visits);
+    bvh_walk<FMT, MODE == kVisits>(sc, st, ok, walk, visits);
+    const uint32_t count = walk.count;
     if (i >= n) return;
     if (MODE == kAny) { out8[i] = count != 0u ? 1 : 0; return; }
     if (counts) counts[i] = count;
@@ -143,12 +70,7 @@ template <int FMT, int CAP, int MODE>
 static hipError_t launch_triangles(const DeviceScene& sc, uint32_t stack_entries, float scene_term, const float4* tris, uint32_t n, uint32_t max_prims,
                                    uint32_t* prims, uint32_t* counts, uint8_t* out8, uint2* visits, hipStream_t stream)
 {
-    const size_t lds = (size_t)(256 / 64) * stack_entries * 64u * sizeof(uint32_t);
-    auto kernel = k_query_triangles<FMT, CAP, MODE>;
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    kernel<<<(n + 255u) / 256u, 256, lds, stream>>>(sc, stack_entries, scene_term, tris, n, max_prims, prims, counts, out8, visits);
-    return hipGetLastError();
+    return launch_lane_stack(k_query_triangles<FMT, CAP, MODE>, stack_entries, n, stream, sc, stack_entries, scene_term, tris, n, max_prims, prims, counts, out8, visits);
 }
 
 template <int FMT>

@@ -1,7 +1,7 @@
 // tritri_device.h — the device functions the triangle-against-mesh query (tritri.hip) shares with the complete-list queries
-// (lists.hip): the triangle-triangle test and the child-box admission of the fp32 nodes.  fmin3 / fmax3, child_admitted_hc (the fp16
-// nodes' admission, the same for a box and for a triangle's bounding box) and the sorted register list come from overlap_device.h.
-// Moved out of tritri.hip word for word; include only from a unit built with -ffp-contract=off (the test is evaluated as written, and
+// (lists.hip): the triangle-triangle test, the child-box admission of the fp32 nodes and the query record TriQuery.  fmin3 / fmax3,
+// child_admitted_hc (the fp16 nodes' admission, the same for a box and for a triangle's bounding box), the sorted register list and
+// the walk's policies come from overlap_device.h.  Include only from a unit built with -ffp-contract=off (the test is evaluated as written, and
 // tests/tritri_ref.py mirrors it operation for operation).
 #pragma once
 #include "tritri.h"
@@ -68,5 +68,41 @@ __device__ __forceinline__ bool child_admitted_f32(const f3& qlo, const f3& qhi,
 {
     return (lx <= qhi.x) & (hx >= qlo.x) & (ly <= qhi.y) & (hy >= qlo.y) & (lz <= qhi.z) & (hz >= qlo.z);
 }
+
+// The query record of the walk's policies (overlap_device.h says what they ask of it).
+struct TriQuery {
+    f3 a0, f1, f2, qlo, qhi, thr, qc;
+    __device__ __forceinline__ bool load(const float4* __restrict__ tris, uint32_t i, uint32_t n)
+    {
+        f3 a1 = mk(0.0f), a2 = mk(0.0f);
+        a0 = mk(0.0f);
+        bool ok = false;
+        if (i < n) {
+            const float4 r0 = tris[3ull * i], r1 = tris[3ull * i + 1ull], r2 = tris[3ull * i + 2ull];
+            a0 = mk(r0.x, r0.y, r0.z);
+            a1 = mk(r1.x, r1.y, r1.z);
+            a2 = mk(r2.x, r2.y, r2.z);
+            ok = __builtin_isfinite(r0.x) && __builtin_isfinite(r0.y) && __builtin_isfinite(r0.z) && __builtin_isfinite(r1.x) && __builtin_isfinite(r1.y) &&
+                 __builtin_isfinite(r1.z) && __builtin_isfinite(r2.x) && __builtin_isfinite(r2.y) && __builtin_isfinite(r2.z);
+        }
+        qlo = mk(fmin3(a0.x, a1.x, a2.x), fmin3(a0.y, a1.y, a2.y), fmin3(a0.z, a1.z, a2.z));
+        qhi = mk(fmax3(a0.x, a1.x, a2.x), fmax3(a0.y, a1.y, a2.y), fmax3(a0.z, a1.z, a2.z));
+        f1 = a1 - a0;
+        f2 = a2 - a0;
+        return ok;
+    }
+    __device__ __forceinline__ void prepare(const DeviceScene& sc, float scene_term)
+    {
+        // FMT 11 only: the query box as centre and half extent (the halves are exact, the sum and the difference round once each)
+        const f3 c = mk(0.5f * qlo.x + 0.5f * qhi.x, 0.5f * qlo.y + 0.5f * qhi.y, 0.5f * qlo.z + 0.5f * qhi.z);
+        const f3 h = mk(0.5f * qhi.x - 0.5f * qlo.x, 0.5f * qhi.y - 0.5f * qlo.y, 0.5f * qhi.z - 0.5f * qlo.z);
+        thr = mk(h.x + (scene_term + (fabsf(c.x) + h.x) * kOverlapQuery), h.y + (scene_term + (fabsf(c.y) + h.y) * kOverlapQuery),
+                 h.z + (scene_term + (fabsf(c.z) + h.z) * kOverlapQuery));
+        qc = mk(c.x - sc.hspace.cx, c.y - sc.hspace.cy, c.z - sc.hspace.cz);
+    }
+    __device__ __forceinline__ bool admit_hc(uint32_t px, uint32_t py, uint32_t pz, const HSpace& hs) const { return child_admitted_hc(px, py, pz, qc, hs, thr); }
+    __device__ __forceinline__ bool admit_f32(float lx, float ly, float lz, float hx, float hy, float hz) const { return child_admitted_f32(qlo, qhi, lx, ly, lz, hx, hy, hz); }
+    __device__ __forceinline__ bool accept(const f3& v0, const f3& e1, const f3& e2) const { return tri_tri_intersect(a0, f1, f2, qlo, qhi, v0, e1, e2); }
+};
 
 }  // namespace ptd

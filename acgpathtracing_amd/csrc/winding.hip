@@ -12,15 +12,14 @@
 //
 // The parent pass and the visit counter restate refit.hip's pattern (k_rf_parents, k_rf_refit) under this file's names.  The walk
 // reads the packed records and the triangle records only, so it is the same code for a scene that holds fp16 or fp32 nodes: the node
-// format matters to the build alone (Topo).  256-lane workgroups over a one-dimensional grid, the LDS lane stack of nearest.hip
+// format matters to the build alone (Topo).  256-lane workgroups over a one-dimensional grid, the lane stack of query_launch.h
 // (stack_entries * 64 words per wave); at most one push per visit, no box test, no ordering, no atomics: two calls give the same bits.
 // Built with -ffp-contract=off: the accept rule d2 > beta2 * r2 is evaluated in fp32 as written.
 #include "winding.h"
+#include "query_launch.h"
 #include <vector>
 
 namespace ptd {
-
-extern __shared__ uint32_t winding_lds[];
 
 namespace {
 
@@ -154,8 +153,7 @@ k_query_winding(const TriRecord* __restrict__ tris, const WindNode* __restrict__
                 float beta2, const float4* __restrict__ points, uint32_t n, float* __restrict__ out, uint2* __restrict__ visits_out)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;      // n <= 2^31 - 1: the grid's last lane is below 2^31 + 255
-    LaneStack st;
-    st.base = winding_lds + (threadIdx.x >> 6) * (stack_entries * 64u) + (threadIdx.x & 63u);
+    const LaneStack st = lane_stack(stack_entries);
     f3 q = mk(0.0f);
     bool ok = false;
     if (i < n) {
@@ -241,11 +239,7 @@ template <typename K>
 hipError_t launch_winding(K kernel, const WindingTree& w, const TriRecord* tris, uint32_t n_tris, uint32_t stack_entries, float beta2, const float4* points,
                           uint32_t n, float* out, uint2* visits, hipStream_t stream)
 {
-    const size_t lds = (size_t)(256 / 64) * stack_entries * 64u * sizeof(uint32_t);
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    kernel<<<(n + 255u) / 256u, 256, lds, stream>>>(tris, w.walk, w.root, w.built ? n_tris : 0u, stack_entries, beta2, points, n, out, visits);
-    return hipGetLastError();
+    return launch_lane_stack(kernel, stack_entries, n, stream, tris, w.walk, w.root, w.built ? n_tris : 0u, stack_entries, beta2, points, n, out, visits);
 }
 
 }  // namespace

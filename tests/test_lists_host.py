@@ -108,8 +108,8 @@ def test_ladder():
 
 
 def test_build_lists_header_and_bindings():
-    assert "lists.hip" in _build.HIP_SOURCES and {"lists.h", "overlap_device.h", "tritri_device.h"} <= set(_build.HIP_HEADERS)
-    for name in ("lists.hip", "lists.h", "overlap_device.h", "tritri_device.h", "overlap.hip", "tritri.hip", "capi_query.hip"):
+    assert "lists.hip" in _build.HIP_SOURCES and {"lists.h", "overlap_device.h", "tritri_device.h", "bvh_walk.h", "query_launch.h"} <= set(_build.HIP_HEADERS)
+    for name in ("lists.hip", "lists.h", "overlap_device.h", "tritri_device.h", "bvh_walk.h", "query_launch.h", "overlap.hip", "tritri.hip", "capi_query.hip"):
         assert name not in _build.KERNEL_SOURCES            # pt_kernel_source_hash() does not move
     assert _build.kernel_source_hash() == "0ae80f7fe3d9b38b"
     assert _native.ABI_VERSION == 4

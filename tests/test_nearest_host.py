@@ -199,8 +199,8 @@ def test_point_sets_find_and_miss_on_the_reference(cornell_sets, scene):
 
 
 def test_build_lists_and_abi():
-    assert "nearest.hip" in _build.HIP_SOURCES and "nearest.h" in _build.HIP_HEADERS
-    for name in ("nearest.hip", "nearest.h", "capi_query.hip"):
+    assert "nearest.hip" in _build.HIP_SOURCES and {"nearest.h", "bvh_walk.h", "closest_point.h", "query_launch.h"} <= set(_build.HIP_HEADERS)
+    for name in ("nearest.hip", "nearest.h", "bvh_walk.h", "closest_point.h", "query_launch.h", "capi_query.hip"):
         assert name not in _build.KERNEL_SOURCES            # pt_kernel_source_hash() does not move
     assert "pt_query_nearest" in _native.ABI_SYMBOLS and "pt_debug_nearest_visits" in _native.TEST_SYMBOLS
     assert _native.ABI_VERSION == 4

@@ -202,8 +202,8 @@ def test_tangent_triangles_find_scene_vertices_and_edge_pairs():
 
 
 def test_build_lists_and_abi():
-    assert "tridist.hip" in _build.HIP_SOURCES and "tridist.h" in _build.HIP_HEADERS and "segment_device.h" in _build.HIP_HEADERS
-    for name in ("tridist.hip", "tridist.h", "segment_device.h", "segment.hip", "capi_query.hip"):
+    assert "tridist.hip" in _build.HIP_SOURCES and {"tridist.h", "segment_device.h", "closest_point.h", "bvh_walk.h"} <= set(_build.HIP_HEADERS)
+    for name in ("tridist.hip", "tridist.h", "segment_device.h", "closest_point.h", "bvh_walk.h", "segment.hip", "capi_query.hip"):
         assert name not in _build.KERNEL_SOURCES            # pt_kernel_source_hash() does not move
     assert _build.kernel_source_hash() == "0ae80f7fe3d9b38b"
     assert "pt_query_triangle_distance" in _native.ABI_SYMBOLS and "pt_debug_triangle_distance_visits" in _native.TEST_SYMBOLS
