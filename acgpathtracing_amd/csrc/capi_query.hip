@@ -4,8 +4,9 @@
 // pt_query_sweep, pt_query_sweep_any, the triangle-against-mesh queries pt_query_triangles, pt_query_triangles_any, the
 // segment-to-mesh distance query pt_query_segments and the K-closest and within-radius queries pt_query_nearest_k,
 // pt_query_within_any and the generalised winding number pt_query_winding (each with its counting twin of include/acgpt_test.h),
-// and the complete lists in CSR form: pt_list_offsets, pt_query_overlap_lists, pt_query_triangles_lists.
-// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip, segment.hip, tridist.hip, winding.hip and lists.hip; their one walk, leaf routine and launch are in bvh_walk.h, closest_point.h and query_launch.h.  The context and what the units share: context.h.
+// the complete lists in CSR form: pt_list_offsets, pt_query_overlap_lists, pt_query_triangles_lists, and the posed-mesh queries
+// pt_set_query_mesh, pt_get_query_mesh, pt_pose_triangles, pt_query_poses_any, pt_query_poses_distance.
+// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip, segment.hip, tridist.hip, winding.hip, lists.hip and poses.hip; their one walk, leaf routine and launch are in bvh_walk.h, closest_point.h and query_launch.h.  The context and what the units share: context.h.
 #include <cmath>
 
 #include "../../include/acgpt_test.h"
@@ -16,6 +17,7 @@
 #include "nearest.h"
 #include "nearest_k.h"
 #include "overlap.h"
+#include "poses.h"
 #include "query.h"
 #include "segment.h"
 #include "tridist.h"
@@ -27,6 +29,7 @@ static_assert(sizeof(pt_nearest) == 32, "pt_nearest: a change of this layout bum
 static_assert(sizeof(pt_sweep_hit) == 32, "pt_sweep_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_segment_hit) == 32, "pt_segment_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_triangle_distance_hit) == 48, "pt_triangle_distance_hit: a change of this layout bumps pt_abi_version");
+static_assert(sizeof(pt_pose_distance_hit) == 48, "pt_pose_distance_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_ao_params) == 32, "pt_ao_params: a change of this layout bumps pt_abi_version");
 
 // The node array the scene holds, as pt_render_features picks it: fp16 centre / half-extent nodes for the default variants, fp32
@@ -545,6 +548,121 @@ PT_API int pt_debug_triangle_distance_visits(pt_ctx* c, const float* tris, size_
                                                (uint32_t)n, (float4*)out, (uint2*)visits, flags, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
+}
+
+// ---- posed-mesh queries ----------------------------------------------------------------------------------------------------------
+static_assert(ptd::kPoseMeshMaxTris == PT_QUERY_MESH_MAX, "PT_QUERY_MESH_MAX is pt_set_query_mesh's limit");
+
+PT_API int pt_set_query_mesh(pt_ctx* c, const float* tris, size_t ntris)
+{
+    const std::string f = "pt_set_query_mesh: ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (ntris != 0 && !tris) return fail(c, f + "null argument");
+    if (ntris > PT_QUERY_MESH_MAX) return fail(c, f + "too many triangles (2^20 per mesh)");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, f + "hipSetDevice failed");
+    // the allocation is the mesh's size exactly: the old one goes first (every call that used it has returned synchronised)
+    CK(c, hipStreamSynchronize(c->stream));
+    c->d_pose_mesh.release();
+    c->pose_mesh_tris = 0u;
+    if (ntris == 0) return 0;
+    CK(c, c->d_pose_mesh.reserve(3u * ntris, c->stream));
+    CK(c, hipMemcpyAsync(c->d_pose_mesh.p, tris, ntris * 48u, hipMemcpyHostToDevice, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    c->pose_mesh_tris = (uint32_t)ntris;
+    return 0;
+}
+
+PT_API int pt_get_query_mesh(pt_ctx* c, size_t* ntris, size_t* device_bytes)
+{
+    if (!c) return fail(nullptr, "pt_get_query_mesh: null context");
+    if (ntris) *ntris = c->pose_mesh_tris;
+    if (device_bytes) *device_bytes = c->d_pose_mesh.cap * sizeof(float4);
+    return 0;
+}
+
+// One array of a posed-mesh call: its bytes, the alignment it needs (a mask), whether the call cannot do without it.
+struct PoseSpan { const void* p; size_t bytes; uintptr_t align_mask; bool required; const char* name; };
+
+// every refusal of the posed-mesh calls before any device work, in the siblings' order; spans[0] is the poses.  Returns 0 to go on,
+// 1 refused, -1 nothing to do (P == 0).  per_pair: bytes of spans[k] are per posed triangle (pt_pose_triangles' output), known only
+// here, where P * T has been judged.
+static int poses_prepare(pt_ctx* c, const char* fn, size_t P, PoseSpan* spans, int n_spans, int per_pair, int* fmt)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (P == 0) return -1;
+    for (int k = 0; k < n_spans; k++)
+        if (spans[k].required && !spans[k].p) return fail(c, f + "null argument");
+    if (P > 0x7FFFFFFFull) return fail(c, f + "too many poses (2^31 - 1 per call)");
+    const size_t T = c->pose_mesh_tris;
+    if (P * T > 0x7FFFFFFFull) return fail(c, f + "too many posed triangles (2^31 - 1 per call): split the poses");      // P < 2^31, T <= 2^20
+    if (per_pair >= 0) spans[per_pair].bytes *= T;
+    for (int k = 0; k < n_spans; k++)
+        if ((uintptr_t)spans[k].p & spans[k].align_mask) return fail(c, f + spans[k].name + " must be " + std::to_string(spans[k].align_mask + 1u) + "-byte aligned");
+    for (int k = 1; k < n_spans; k++) {
+        if (!spans[k].p) continue;
+        for (int j = 0; j < k; j++)
+            if (spans[j].p && spans_overlap(spans[j].p, spans[j].bytes, spans[k].p, spans[k].bytes))
+                return fail(c, f + spans[k].name + " overlaps " + spans[j].name);
+    }
+    if (T == 0) return fail(c, f + "no query mesh (pt_set_query_mesh first)");
+    return query_node_format(c, f, fmt);
+}
+
+PT_API int pt_pose_triangles(pt_ctx* c, const float* poses, size_t P, float* tris_out)
+{
+    PoseSpan spans[2] = {{poses, P * 48u, 15u, true, "the poses"}, {tris_out, P * 48u, 15u, true, "tris_out"}};
+    int fmt = 0;
+    if (int rc = poses_prepare(c, "pt_pose_triangles", P, spans, 2, 1, &fmt)) return rc < 0 ? 0 : rc;
+    Range range("pt_pose_triangles");
+    CK(c, ptd::launch_pose_triangles(c->d_pose_mesh.p, c->pose_mesh_tris, (const float4*)poses, (uint32_t)P, (float4*)tris_out, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+static int poses_any_run(pt_ctx* c, const char* fn, const float* poses, size_t P, uint8_t* hit, uint32_t* first, uint32_t flags)
+{
+    PoseSpan spans[3] = {{poses, P * 48u, 15u, true, "the poses"}, {hit, P, 0u, true, "hit"}, {first, P * 4u, 3u, false, "first"}};
+    int fmt = 0;
+    if (int rc = poses_prepare(c, fn, P, spans, 3, -1, &fmt)) return rc < 0 ? 0 : rc;
+    Range range(fn);
+    CK(c, c->d_pose_words.reserve(P, c->stream));
+    CK(c, ptd::launch_poses_any(fmt, device_scene(c), c->stack_entries, ptd::overlap_scene_term(c->bvh.scene_lo, c->bvh.scene_hi), c->d_pose_mesh.p, c->pose_mesh_tris,
+                                (const float4*)poses, (uint32_t)P, (uint32_t*)c->d_pose_words.p, hit, first, flags, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+static int poses_distance_run(pt_ctx* c, const char* fn, const float* poses, size_t P, float max_radius, pt_pose_distance_hit* out, uint32_t flags)
+{
+    PoseSpan spans[2] = {{poses, P * 48u, 15u, true, "the poses"}, {out, P * sizeof(pt_pose_distance_hit), 15u, true, "out"}};
+    int fmt = 0;
+    if (int rc = poses_prepare(c, fn, P, spans, 2, -1, &fmt)) return rc < 0 ? 0 : rc;
+    Range range(fn);
+    CK(c, c->d_pose_words.reserve(P, c->stream));
+    CK(c, ptd::launch_poses_distance(fmt, device_scene(c), c->stack_entries, ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi), c->d_pose_mesh.p, c->pose_mesh_tris,
+                                     (const float4*)poses, (uint32_t)P, max_radius, c->d_pose_words.p, (float4*)out, flags, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_query_poses_any(pt_ctx* c, const float* poses, size_t P, uint8_t* hit, uint32_t* first)
+{
+    return poses_any_run(c, "pt_query_poses_any", poses, P, hit, first, 0u);
+}
+
+PT_API int pt_query_poses_distance(pt_ctx* c, const float* poses, size_t P, float max_radius, pt_pose_distance_hit* out)
+{
+    return poses_distance_run(c, "pt_query_poses_distance", poses, P, max_radius, out, 0u);
+}
+
+PT_API int pt_debug_query_poses(pt_ctx* c, const float* poses, size_t P, float max_radius, uint8_t* hit, uint32_t* first, pt_pose_distance_hit* out, uint32_t flags)
+{
+    const std::string f = "pt_debug_query_poses: ";
+    if (c && flags > (ptd::kPoseNoEarly | ptd::kPosePoseMajor)) return fail(c, f + "flags is 0..3 (1: no early look, 2: pose-major lanes)");
+    if (c && out && (hit || first)) return fail(c, f + "out goes alone, hit (and first) go without it");
+    if (out) return poses_distance_run(c, "pt_debug_query_poses", poses, P, max_radius, out, flags);
+    return poses_any_run(c, "pt_debug_query_poses", poses, P, hit, first, flags);
 }
 
 // ---- swept spheres ---------------------------------------------------------------------------------------------------------------

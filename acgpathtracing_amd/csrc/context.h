@@ -114,6 +114,9 @@ struct pt_ctx {
     DevBuf<unsigned long long> d_list_scratch;   // pt_list_offsets' tile sums and the list queries' mismatch flag (lists.h list_scratch_words); the
                                               // context's, not the scene's: not counted in device_bytes
     uint32_t list_phases = 3u;                // pt_debug_list_phases: fill | sort (ptd::kListPhaseAll), the product's
+    DevBuf<float4> d_pose_mesh;               // pt_set_query_mesh: pose_mesh_tris records of three float4; the context's, kept across scene changes,
+    uint32_t pose_mesh_tris = 0;              // not counted in device_bytes (pt_get_query_mesh reports it)
+    DevBuf<unsigned long long> d_pose_words;  // the posed-mesh queries' word or key per pose (poses.h)
     DevBuf<uint8_t> d_tri_bsdf;              // bsdfType per triangle (caller's order): pt_temporal_blend's, built on its first call per scene
     // what pt_update_vertices keeps of the last pt_set_scene: host copies of everything but the vertices, and after the first update
     // the index buffer on the device (freed with the scene)

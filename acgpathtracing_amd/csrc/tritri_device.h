@@ -91,6 +91,17 @@ struct TriQuery {
         f2 = a2 - a0;
         return ok;
     }
+    // load()'s record from three vertices in registers (poses.hip transforms them there).  False: a coordinate is not finite.
+    __device__ __forceinline__ bool set(const f3& a0_, const f3& a1, const f3& a2)
+    {
+        a0 = a0_;
+        qlo = mk(fmin3(a0.x, a1.x, a2.x), fmin3(a0.y, a1.y, a2.y), fmin3(a0.z, a1.z, a2.z));
+        qhi = mk(fmax3(a0.x, a1.x, a2.x), fmax3(a0.y, a1.y, a2.y), fmax3(a0.z, a1.z, a2.z));
+        f1 = a1 - a0;
+        f2 = a2 - a0;
+        return __builtin_isfinite(a0.x) && __builtin_isfinite(a0.y) && __builtin_isfinite(a0.z) && __builtin_isfinite(a1.x) && __builtin_isfinite(a1.y) &&
+               __builtin_isfinite(a1.z) && __builtin_isfinite(a2.x) && __builtin_isfinite(a2.y) && __builtin_isfinite(a2.z);
+    }
     __device__ __forceinline__ void prepare(const DeviceScene& sc, float scene_term)
     {
         // FMT 11 only: the query box as centre and half extent (the halves are exact, the sum and the difference round once each)

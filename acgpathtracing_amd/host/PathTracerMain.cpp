@@ -19,6 +19,7 @@
 //              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k|,all] ...] [--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k|,all] ...]
 //              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...] [--clearance x0,y0,z0,x1,y1,z1[,radius] ...]
 //              [--tri-distance x0,y0,z0,x1,y1,z1,x2,y2,z2[,radius] ...]
+//              [--collide mesh.obj[,tx,ty,tz[,radius]] ...]
 //              [--nearest-k x,y,z,k[,radius] ...] [--within x,y,z,radius ...] [--winding x,y,z[,beta] ...]
 //              [--ao K[,radius[,bias]] --ao-out file.pfm [--ao-frames n]]
 // --ao K[,radius[,bias]] with --ao-out: once the scene is set and before the first frame, the ambient occlusion of the view
@@ -967,6 +968,53 @@ static void clearanceSegments(PathTracerState& state, const TinyObjWrapper& obj,
     fflush(stdout);
 }
 
+// --collide mesh.obj[,tx,ty,tz[,radius]] (repeatable): a second OBJ as the query mesh of the posed-mesh queries (pt_set_query_mesh), moved by
+// the translation; one JSON line: does it touch the scene, the first mesh triangle that does, and with a radius the closest pair
+struct CollideMesh { std::string path; float t[3]; float radius; bool limited; };
+static void collideMeshes(PathTracerState& state, const std::vector<CollideMesh>& meshes)
+{
+    for (size_t i = 0; i < meshes.size(); i++) {
+        const CollideMesh& m = meshes[i];
+        TinyObjWrapper mesh(m.path);
+        const std::vector<float> v = mesh.getVerticesFloat();
+        const std::vector<uint32_t> idx = mesh.getIndexBuffer();
+        const size_t T = idx.size() / 3;
+        std::vector<float> recs(T * 12, 0.0f);
+        for (size_t k = 0; k < T * 3; k++) for (int c = 0; c < 3; c++) recs[k * 4 + c] = v[(size_t)idx[k] * 4 + c];
+        const float pose[12] = {1.0f, 0.0f, 0.0f, m.t[0], 0.0f, 1.0f, 0.0f, m.t[1], 0.0f, 0.0f, 1.0f, m.t[2]};
+        void* d_pose = nullptr; void* d_hit = nullptr; void* d_first = nullptr; void* d_out = nullptr;
+        uint8_t hit = 0; uint32_t first = 0xFFFFFFFFu;
+        pt_pose_distance_hit r;
+        std::string err;
+        if (T == 0) err = "the mesh has no triangles";
+        else if (pt_set_query_mesh(state.context, recs.data(), T) != 0 || pt_device_malloc(state.context, &d_pose, 48) != 0 || pt_device_malloc(state.context, &d_hit, 16) != 0 ||
+                 pt_device_malloc(state.context, &d_first, 16) != 0 || pt_device_malloc(state.context, &d_out, sizeof(r)) != 0 ||
+                 pt_copy_to_device(state.context, d_pose, pose, 48) != 0 ||
+                 pt_query_poses_any(state.context, (const float*)d_pose, 1, (uint8_t*)d_hit, (uint32_t*)d_first) != 0 ||
+                 pt_copy_to_host(state.context, &hit, d_hit, 1) != 0 || pt_copy_to_host(state.context, &first, d_first, 4) != 0 ||
+                 (m.limited && (pt_query_poses_distance(state.context, (const float*)d_pose, 1, m.radius, (pt_pose_distance_hit*)d_out) != 0 ||
+                                pt_copy_to_host(state.context, &r, d_out, sizeof(r)) != 0)))
+            err = pt_last_error(state.context);
+        if (d_pose) pt_device_free(state.context, d_pose);
+        if (d_hit) pt_device_free(state.context, d_hit);
+        if (d_first) pt_device_free(state.context, d_first);
+        if (d_out) pt_device_free(state.context, d_out);
+        if (!err.empty()) throw Exception("collide: " + err);
+        std::string name = m.path;
+        for (size_t k = 0; k < name.size(); k++) if (name[k] == '"' || name[k] == '\\' || (unsigned char)name[k] < 0x20) name[k] = '_';
+        printf("{\"collide\": {\"mesh\": \"%s\", \"triangles\": %zu, \"translation\": [%.9g, %.9g, %.9g], \"hit\": %d, \"first\": %lld", name.c_str(), T, m.t[0], m.t[1], m.t[2],
+               (int)hit, first == 0xFFFFFFFFu ? -1ll : (long long)first);
+        if (m.limited) {
+            const bool found = r.prim != 0xFFFFFFFFu;
+            printf(", \"radius\": %.9g, \"found\": %s, \"distance\": %.9g, \"query_triangle\": %lld, \"prim\": %lld, \"feature\": %d, \"on_query\": [%.9g, %.9g, %.9g], \"point\": [%.9g, %.9g, %.9g]",
+                   m.radius, found ? "true" : "false", r.distance, found ? (long long)r.query_triangle : -1ll, found ? (long long)r.prim : -1ll, (int)r.feature, r.qx, r.qy, r.qz,
+                   r.cx, r.cy, r.cz);
+        }
+        printf("}}\n");
+    }
+    fflush(stdout);
+}
+
 // --tri-distance: every triangle in one call of pt_query_triangle_distance; one JSON line per triangle
 struct DistanceTriangle { float g[12]; bool limited; };
 static void triangleDistances(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<DistanceTriangle>& tris)
@@ -1189,6 +1237,7 @@ int main(int argc, char** argv)
     std::vector<float4> windings;
     std::vector<ClearanceSegment> clearances;
     std::vector<DistanceTriangle> triDistances;
+    std::vector<CollideMesh> collides;
     std::vector<OverlapBox> overlaps;
     std::vector<IntersectTri> intersects;
     std::vector<SweepArg> sweeps;
@@ -1337,6 +1386,26 @@ int main(int argc, char** argv)
             for (int k = 0; k < 11; k++) if (k != 3 && k != 7 && !std::isfinite(g[k])) fine = false;
             if (!fine) { std::cerr << "--tri-distance x0,y0,z0,x1,y1,z1,x2,y2,z2[,radius]: nine finite coordinates, a radius >= 0" << std::endl; return 2; }
             triDistances.push_back(dt);
+        }
+        else if (a == "--collide") {
+            CollideMesh cm = {std::string(), {0.0f, 0.0f, 0.0f}, 0.0f, false};
+            const std::string text = next();
+            const size_t comma = text.find(',');
+            cm.path = text.substr(0, comma);
+            bool fine = !cm.path.empty();
+            if (fine && comma != std::string::npos) {
+                int used = 0;
+                const char* rest = text.c_str() + comma;
+                fine = sscanf(rest, ",%f,%f,%f%n", &cm.t[0], &cm.t[1], &cm.t[2], &used) == 3;
+                if (fine && rest[used] != '\0') {               // a fourth number, the radius, and nothing behind it
+                    int more = 0;
+                    fine = sscanf(rest + used, ",%f%n", &cm.radius, &more) == 1 && rest[used + more] == '\0' && cm.radius >= 0.0f;
+                    cm.limited = true;
+                }
+                for (int k = 0; k < 3; k++) if (!std::isfinite(cm.t[k])) fine = false;
+            }
+            if (!fine) { std::cerr << "--collide mesh.obj[,tx,ty,tz[,radius]]: a file, a finite translation, a radius >= 0" << std::endl; return 2; }
+            collides.push_back(cm);
         }
         else if (a == "--overlap") {
             OverlapBox b = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, 8u};
@@ -1501,6 +1570,7 @@ int main(int argc, char** argv)
         if (!windings.empty()) { std::cout.flush(); windingPoints(state, windings); }
         if (!clearances.empty()) { std::cout.flush(); clearanceSegments(state, obj, clearances); }
         if (!triDistances.empty()) { std::cout.flush(); triangleDistances(state, obj, triDistances); }
+        if (!collides.empty()) { std::cout.flush(); collideMeshes(state, collides); }
         if (!overlaps.empty()) { std::cout.flush(); overlapBoxes(state, obj, overlaps); }
         if (!intersects.empty()) { std::cout.flush(); intersectTriangles(state, intersects); }
         if (!sweeps.empty()) { std::cout.flush(); sweepSpheres(state, obj, sweeps); }

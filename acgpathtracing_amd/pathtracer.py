@@ -1752,7 +1752,8 @@ def meshCollisions(state, vertices, indices, poses=None, pairs=False):
     scene.  pairs=True asks queryTriangles instead and returns a dict: pairs (m, 3), the (pose, mesh triangle, scene triangle) triples
     of the lists, and counts (P, T), the number of scene triangles each mesh triangle intersects — where it is above 8 that triangle's
     list was cut.  pairs="all" goes through queryTrianglesLists and returns the same dict with every triple, none cut, ordered by pose, mesh
-    triangle and scene triangle.  Arrays for arrays, tensors for tensors."""
+    triangle and scene triangle.  Arrays for arrays, tensors for tensors.
+    setQueryMesh + queryPosesAny answer the yes / no per pose on the device, without the P x T records (posedTriangles gives those)."""
     if isinstance(pairs, str) and pairs != "all":
         raise PathTracerError("meshCollisions: pairs is False, True or \"all\", got %r" % (pairs,))
     rec = _posed_records("meshCollisions", vertices, indices, poses)
@@ -1842,7 +1843,8 @@ def meshClearance(state, vertices, indices, poses=None, max_radius=float("inf"))
     the scene, +inf where nothing lies within max_radius), query_triangle (P,) int64 the mesh triangle of the closest pair (ties to
     the lowest; -1 where there is none), prim (P,) the scene triangle (0xFFFFFFFF, or -1 in a tensor, where there is none), on_query
     (P, 3) and on_mesh (P, 3) the closest points on the posed mesh and on the scene — on_mesh - on_query is the direction to push the
-    scene away in.  Arrays for arrays, tensors for tensors."""
+    scene away in.  Arrays for arrays, tensors for tensors.
+    setQueryMesh + queryPosesDistance answer the closest pair per pose on the device, without the P x T records and their answers."""
     radius = _checked_radius("meshClearance", max_radius)
     rec = _posed_records("meshClearance", vertices, indices, poses)
     P, T = int(rec.shape[0]), int(rec.shape[1])
@@ -1873,6 +1875,164 @@ def meshClearance(state, vertices, indices, poses=None, max_radius=float("inf"))
     best = d[np.arange(P), tri]
     return {"clearance": best, "query_triangle": np.where(np.isfinite(best), tri, -1).astype(np.int64), "prim": got["prim"][row], "on_query": got["on_query"][row],
             "on_mesh": got["point"][row]}
+
+
+# ------------------------------------------------------------------ posed-mesh queries ----
+POSE_DISTANCE_DTYPE = np.dtype([("distance", np.float32), ("prim", np.uint32), ("feature", np.float32), ("material", np.uint32), ("on_query", np.float32, 3),
+                                ("query_triangle", np.uint32), ("point", np.float32, 3), ("pad1", np.float32)])      # pt_pose_distance_hit
+assert POSE_DISTANCE_DTYPE.itemsize == 48
+POSED_TRIANGLES_MAX = 0x7FFFFFFF      # posed triangles per call of the library; the wrappers split more over whole poses
+
+
+def setQueryMesh(state, vertices, indices):
+    """Register the mesh the posed-mesh queries move through the scene (include/acgpt.h pt_set_query_mesh): vertices (V, 3) or (V, 4),
+    indices (T, 3) or flat, in the mesh's own frame, with meshCollisions' checks.  The mesh is de-indexed on the host and copied to
+    device memory the context owns; it stays through scene changes, a second call replaces it, a mesh without triangles frees it.
+    Returns the number of triangles."""
+    rec = _posed_records("setQueryMesh", vertices, indices, None)
+    if _is_tensor(rec):
+        rec = rec.cpu().numpy()
+    rec = np.ascontiguousarray(rec.reshape(-1, 12), np.float32)
+    if rec.shape[0] > _native.QUERY_MESH_MAX:
+        raise PathTracerError("setQueryMesh: %d triangles, the limit is %d" % (rec.shape[0], _native.QUERY_MESH_MAX))
+    _check(state.context, _native.hip().pt_set_query_mesh(state.context, rec.ctypes.data if rec.shape[0] else None, rec.shape[0]), "pt_set_query_mesh")
+    return int(rec.shape[0])
+
+
+def getQueryMesh(state):
+    """The registered query mesh: a dict of triangles and device_bytes (0, 0 while there is none)."""
+    n, b = C.c_size_t(0), C.c_size_t(0)
+    _check(state.context, _native.hip().pt_get_query_mesh(state.context, C.byref(n), C.byref(b)), "pt_get_query_mesh")
+    return {"triangles": int(n.value), "device_bytes": int(b.value)}
+
+
+def _pose_records(what, state, poses):
+    """The poses as (P, 12) float32 rows of the 3 x 4 matrices.  NumPy (or anything np.asarray takes): (P, 3, 4), (P, 4, 4), (P, 12) or
+    one 3 x 4 or 4 x 4 matrix.  A torch tensor: float32 on the context's device, contiguous (P, 12) or (P, 3, 4), viewed and not
+    copied; (P, 4, 4) is sliced to its first three rows, which is a copy."""
+    if _is_tensor(poses):
+        import torch
+        if poses.device.type != "cuda" or poses.device.index != state._device:
+            raise PathTracerError("%s: the poses are on %s, the context is on cuda:%d" % (what, poses.device, state._device))
+        if poses.dtype != torch.float32:
+            raise PathTracerError("%s: the poses must be float32, got %s" % (what, poses.dtype))
+        shape = tuple(poses.shape)
+        if poses.dim() == 3 and shape[1:] == (4, 4):
+            return poses[:, :3, :].contiguous().view(-1, 12)
+        if not ((poses.dim() == 2 and shape[1] == 12) or (poses.dim() == 3 and shape[1:] == (3, 4))):
+            raise PathTracerError("%s: expected a (P, 12), (P, 3, 4) or (P, 4, 4) tensor, got shape %s" % (what, shape))
+        if not poses.is_contiguous():
+            raise PathTracerError("%s: the poses must be contiguous (nothing is copied)" % what)
+        return poses.view(-1, 12)
+    p = np.asarray(poses)
+    if p.dtype.kind not in "fiu":
+        raise PathTracerError("%s: the poses must be numbers, got %s" % (what, p.dtype))
+    if p.ndim == 2 and p.shape in ((3, 4), (4, 4)):
+        p = p[None]
+    if p.ndim == 2 and p.shape[1] == 12:
+        return np.ascontiguousarray(p, np.float32)
+    if p.ndim != 3 or p.shape[1:] not in ((3, 4), (4, 4)):
+        raise PathTracerError("%s: expected (P, 3, 4), (P, 4, 4) or (P, 12) poses or one matrix, got shape %s" % (what, p.shape))
+    return np.ascontiguousarray(p[:, :3, :], np.float32).reshape(-1, 12)
+
+
+def _pose_call(what, state, poses, outs, call, limit):
+    """Run call(d_poses, n, [d_out ...]) over the poses, split over whole poses so that no call has more than `limit` posed
+    triangles.  outs: one (row shape, numpy dtype, torch dtype name) per output, or None for one the caller does not want; a row is a
+    pose's share of the output.  Returns the outputs, arrays for an array and tensors for a tensor (None where not wanted)."""
+    recs = _pose_records(what, state, poses)
+    P = int(recs.shape[0])
+    T = getQueryMesh(state)["triangles"] if P or state.context else 0
+    step = max(1, int(limit) // max(T, 1))
+    L = _native.hip()
+    if _is_tensor(recs):
+        import torch
+        with torch.cuda.device(recs.device):
+            got = [None if o is None else torch.empty((P,) + tuple(o[0](T)), dtype=getattr(torch, o[2]), device=recs.device) for o in outs]
+            torch.cuda.current_stream().synchronize()      # the poses' producer and the allocations; every call below returns synchronised
+        for s in range(0, P, step):
+            n = min(P, s + step) - s
+            call(recs.data_ptr() + 48 * s, n, [None if g is None else g.data_ptr() + s * g[0].numel() * g.element_size() for g in got])
+        return got
+    got = [None if o is None else np.zeros((P,) + tuple(o[0](T)), o[1]) for o in outs]
+    if P:
+        bufs = _device_buffers(state, 1, recs.nbytes)
+        try:
+            ptrs = []
+            for g in got:
+                if g is not None and g.nbytes:
+                    bufs += _device_buffers(state, 1, g.nbytes)
+                ptrs.append(bufs[-1] if g is not None and g.nbytes else None)
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], recs.ctypes.data, recs.nbytes), "copy to device")
+            for s in range(0, P, step):
+                n = min(P, s + step) - s
+                call(bufs[0] + 48 * s, n, [None if d is None else d + s * (g.nbytes // P) for d, g in zip(ptrs, got)])
+            for d, g in zip(ptrs, got):
+                if d is not None:
+                    _check(state.context, L.pt_copy_to_host(state.context, g.ctypes.data, d, g.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    return got
+
+
+def posedTriangles(state, poses, _limit=POSED_TRIANGLES_MAX):
+    """The query mesh under every pose (include/acgpt.h pt_pose_triangles): (P, T, 12) float32 records {a0.xyz, 0, a1.xyz, 0, a2.xyz,
+    0}, what queryTriangles, queryTrianglesLists and queryTriangleDistance take once reshaped to (P * T, 12).  The transform is the
+    header's statement, x' = ((m[0] x + m[1] y) + m[2] z) + m[3] in float32 in that order, so the records are the bits the posed-mesh
+    queries test.  Poses: _pose_records' forms; an array for arrays, a tensor on the device for a tensor."""
+    L = _native.hip()
+
+    def call(d_poses, n, d_outs):
+        _check(state.context, L.pt_pose_triangles(state.context, d_poses, n, d_outs[0]), "pt_pose_triangles")
+    return _pose_call("posedTriangles", state, poses, [(lambda T: (T, 12), np.float32, "float32")], call, _limit)[0]
+
+
+def queryPosesAny(state, poses, first=False, _limit=POSED_TRIANGLES_MAX):
+    """Does the query mesh (setQueryMesh) touch the scene on the GPU in each pose (include/acgpt.h pt_query_poses_any): a bool (P,).
+    first=True returns (hit, first): first (P,) is the lowest mesh triangle index that intersects the scene, uint32 with 0xFFFFFFFF
+    where there is none (int32 with -1 in a tensor).  One call, one byte per pose: the P x T posed triangles are formed in registers,
+    and a pose that is decided stops costing walks.
+
+    Poses: NumPy (P, 3, 4), (P, 4, 4), (P, 12) or one matrix, answered with arrays; or a float32 tensor on the context's device,
+    contiguous (P, 12) or (P, 3, 4), which goes in by data_ptr() without a copy and is answered with tensors ((P, 4, 4) is sliced,
+    which copies).  More than 2^31 - 1 posed triangles are split over whole poses."""
+    L = _native.hip()
+
+    def call(d_poses, n, d_outs):
+        _check(state.context, L.pt_query_poses_any(state.context, d_poses, n, d_outs[0], d_outs[1]), "pt_query_poses_any")
+    hit, fst = _pose_call("queryPosesAny", state, poses, [(lambda T: (), np.uint8, "uint8"), (lambda T: (), np.uint32, "int32") if first else None], call, _limit)
+    if _is_tensor(hit):
+        import torch
+        hit = hit.view(torch.bool)
+    else:
+        hit = hit.view(np.bool_)
+    return (hit, fst) if first else hit
+
+
+def queryPosesDistance(state, poses, max_radius=float("inf"), _limit=POSED_TRIANGLES_MAX):
+    """How close the query mesh (setQueryMesh) comes to the scene on the GPU in each pose, and where (include/acgpt.h
+    pt_query_poses_distance).  Returns meshClearance's dict, one row per pose: clearance (P,) float32 (0 where the mesh touches the
+    scene, +inf where nothing lies within max_radius), query_triangle (P,) int64 the mesh triangle of the closest pair (the smallest
+    squared distance, ties to the lowest index; -1 where there is none), prim (P,) the scene triangle (0xFFFFFFFF, or -1 in a tensor,
+    where there is none), feature (P,), material (P,), on_query (P, 3) and on_mesh (P, 3) the closest points on the posed mesh and on
+    the scene.  Poses as queryPosesAny takes them; arrays for arrays, tensors for a tensor."""
+    radius = _checked_radius("queryPosesDistance", max_radius)
+    L = _native.hip()
+
+    def call(d_poses, n, d_outs):
+        _check(state.context, L.pt_query_poses_distance(state.context, d_poses, n, radius, d_outs[0]), "pt_query_poses_distance")
+    out = _pose_call("queryPosesDistance", state, poses, [(lambda T: (12,), np.float32, "float32")], call, _limit)[0]
+    if _is_tensor(out):
+        import torch
+        found = out[:, 0] >= 0
+        tri = out[:, 7].view(torch.int32).to(torch.int64)
+        return {"clearance": torch.where(found, out[:, 0], torch.full_like(out[:, 0], float("inf"))), "query_triangle": tri,
+                "prim": out[:, 1].view(torch.int32), "feature": out[:, 2], "material": out[:, 3].view(torch.int32), "on_query": out[:, 4:7], "on_mesh": out[:, 8:11]}
+    rec = out.reshape(-1).view(POSE_DISTANCE_DTYPE)
+    found = rec["distance"] >= 0
+    return {"clearance": np.where(found, rec["distance"], np.float32(np.inf)).astype(np.float32), "query_triangle": np.where(found, rec["query_triangle"].astype(np.int64), -1),
+            "prim": np.ascontiguousarray(rec["prim"]), "feature": np.ascontiguousarray(rec["feature"]), "material": np.ascontiguousarray(rec["material"]),
+            "on_query": np.ascontiguousarray(rec["on_query"]), "on_mesh": np.ascontiguousarray(rec["point"])}
 
 
 # ------------------------------------------------------------------ swept spheres ----

@@ -805,6 +805,64 @@ typedef struct { float distance; uint32_t prim; float feature; uint32_t material
                  float qx, qy, qz, pad0;  float cx, cy, cz, pad1; } pt_triangle_distance_hit;   /* 48 bytes */
 int pt_query_triangle_distance(pt_ctx* ctx, const float* tris, size_t n, pt_triangle_distance_hit* out);
 
+/* ---- posed-mesh queries on the device (opt-in; nothing above changes) --------------------------------------------------------------
+ * The per-pose part of "a mesh that moves through the scene, tested in many poses": the mesh is registered once, P poses go in, one
+ * byte or one closest pair per pose comes out.  The P x T posed records and the P x T per-triangle answers that
+ * pt_query_triangles_any / pt_query_triangle_distance would need are never materialised, a pose that is decided stops costing walks,
+ * and a C caller needs no loop of its own.
+ *
+ * pt_set_query_mesh   tris: a HOST pointer to ntris records of 12 floats in pt_query_triangles' layout {a0.xyz, . | a1.xyz, . |
+ *             a2.xyz, .}, in the mesh's own frame; the fourth floats are ignored.  The records are copied into device memory the
+ *             context owns.  The mesh is independent of the scene: it survives pt_set_scene, pt_update_vertices and
+ *             pt_update_materials.  A second call replaces it; ntris == 0 frees it.  ntris <= PT_QUERY_MESH_MAX (2^20).  Its memory
+ *             is not part of pt_bvh_info.device_bytes; pt_get_query_mesh reports the mesh (either output may be null).  Refused: a
+ *             null context, a null tris with ntris > 0, ntris above the limit ("too many triangles").
+ *
+ *   pose      12 floats, a row-major 3 x 4 matrix m.  The posed vertex of (x, y, z) is
+ *               x' = ((m[0] * x + m[1] * y) + m[2]  * z) + m[3]
+ *               y' = ((m[4] * x + m[5] * y) + m[6]  * z) + m[7]
+ *               z' = ((m[8] * x + m[9] * y) + m[10] * z) + m[11]
+ *             all fp32, every multiply and add on its own in exactly that order, no fused multiply-add (tests/poses_ref.py is the
+ *             NumPy statement, equal bit for bit).  Any matrix is allowed: scale, shear, mirror, singular.  This statement is what
+ *             makes every answer below bit-defined: the posed triangle (p, t) is these nine numbers, wherever they are formed.
+ *   poses     P poses; DEVICE, 16-byte aligned.
+ *
+ * pt_pose_triangles   writes the P x T posed records, pose-major (record p * T + t), in pt_query_triangles' layout with the three
+ *             fourth floats 0: what pt_query_triangles_lists and the other per-triangle queries take.  tris_out: DEVICE, 16-byte
+ *             aligned, P * T records of 48 bytes.
+ *
+ * pt_query_poses_any  hit[p] = 1 iff pt_query_triangles_any answers 1 for at least one posed triangle of pose p, else 0.  first is
+ *             optional: first[p] = the lowest mesh triangle index for which pt_query_triangles_any answers 1, 0xFFFFFFFF where there
+ *             is none.  hit: DEVICE, P bytes; first: DEVICE, 4-byte aligned, P words, or null.
+ *
+ * pt_query_poses_distance   out[p]: the closest pair of pose p within max_radius.  A mesh triangle is a candidate of its pose iff
+ *             pt_query_triangle_distance finds something for its posed triangle with that max_radius (d2 <= max_radius^2 as that
+ *             section decides it).  The winner is the candidate with the smallest SQUARED distance — that section's d2 of the
+ *             record's pair, before the square root —, ties to the lowest mesh triangle index.  (This is d2, not the rounded
+ *             distance: an argmin over the sqrtf'd distances can differ where two d2 round to one distance.)  The record is, bit for
+ *             bit, pt_query_triangle_distance's record for that one posed triangle with that radius, with query_triangle = the mesh
+ *             triangle's index in the place of pad0.  A pose without a candidate gets the miss record {distance -1, prim 0xFFFFFFFF,
+ *             feature 0, material 0xFFFFFFFF | 0, 0, 0, query_triangle 0xFFFFFFFF | 0, 0, 0, 0}.  A non-finite pose entry, and a
+ *             transform that overflows, make posed triangles "a miss before any traversal" by the rules above, for both queries; a
+ *             NaN or negative max_radius makes every pose a miss (it is not refused).  out: DEVICE, 16-byte aligned, P records.
+ *
+ * The calls enqueue on the context's stream and return synchronised, act on rank 0 of a pt_create_multi context, never write the
+ * accumulation buffer, the frame buffer or pt_stats, and keep one 8-byte word per pose of scratch in the context (not counted in
+ * device_bytes).  Inside, lanes of different workgroups meet in that word through order-independent atomic minima only and never wait
+ * for one another: two calls give the same bits.
+ * P == 0 is a no-op success.  Refused, with the context left usable, in this order and with messages that start "<entry point>: ": a
+ * null context; a null required argument; P > 0x7FFFFFFF ("too many poses"); P * T > 0x7FFFFFFF ("too many posed triangles (2^31 - 1
+ * per call): split the poses"); a poses, tris_out or out array that is not 16-byte aligned, a first that is not 4-byte aligned; any
+ * two of the arrays overlapping; no query mesh ("pt_set_query_mesh first"); a context without a scene.                             */
+#define PT_QUERY_MESH_MAX 1048576u
+typedef struct { float distance; uint32_t prim; float feature; uint32_t material;
+                 float qx, qy, qz; uint32_t query_triangle;  float cx, cy, cz, pad1; } pt_pose_distance_hit;   /* 48 bytes */
+int pt_set_query_mesh(pt_ctx* ctx, const float* tris, size_t ntris);
+int pt_get_query_mesh(pt_ctx* ctx, size_t* ntris, size_t* device_bytes);
+int pt_pose_triangles(pt_ctx* ctx, const float* poses, size_t P, float* tris_out);
+int pt_query_poses_any(pt_ctx* ctx, const float* poses, size_t P, uint8_t* hit, uint32_t* first);
+int pt_query_poses_distance(pt_ctx* ctx, const float* poses, size_t P, float max_radius, pt_pose_distance_hit* out);
+
 /* ---- the K closest triangles of a point, and "is anything within r" (opt-in; nothing above changes) ------------------------------
  * pt_query_nearest answers with one triangle.  A ball resting in a corner touches three walls and needs all three contacts; a point
  * whose closest feature is an edge or a vertex ties between two to six triangles, of which pt_query_nearest names the lowest index

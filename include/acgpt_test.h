@@ -162,6 +162,12 @@ int pt_debug_segments_visits(pt_ctx* ctx, const float* segments, size_t n, pt_se
  * walk's second box bound (the separation along the query triangle's normal), which changes the counts and never the records;
  * anything else is refused.  tools/tridist_timing.py. */
 int pt_debug_triangle_distance_visits(pt_ctx* ctx, const float* tris, size_t n, pt_triangle_distance_hit* out, uint32_t* visits, uint32_t flags);
+/* pt_query_poses_distance (out given; hit and first must be null) or pt_query_poses_any (out null; hit given, first optional), with
+ * the same answers and the same refusals, from launches that take flags: bit 0 switches the early look at the pose's word and the
+ * shrinking radius off, so that every lane walks as the per-triangle kernels do; bit 1 deals the lanes pose-major (consecutive lanes
+ * on consecutive triangles of one pose) instead of triangle-major (all poses' triangle 0 first, the product's order).  Neither changes an output bit.  max_radius is read with out only.  Anything above 3 is
+ * refused.  tools/poses_timing.py. */
+int pt_debug_query_poses(pt_ctx* ctx, const float* poses, size_t P, float max_radius, uint8_t* hit, uint32_t* first, pt_pose_distance_hit* out, uint32_t flags);
 /* pt_query_nearest_k (hit null: same records, same counts, same refusals) or pt_query_within_any (hit given; max_k must be 0 and
  * out and counts null) from kernel instantiations that also count: visits[2 i] = inner nodes point i visited, visits[2 i + 1] =
  * triangles it tested.  visits: DEVICE, 8-byte aligned, 2 n words, never null.  tools/nearest_k_timing.py. */
