@@ -5,8 +5,9 @@
 // segment-to-mesh distance query pt_query_segments and the K-closest and within-radius queries pt_query_nearest_k,
 // pt_query_within_any and the generalised winding number pt_query_winding (each with its counting twin of include/acgpt_test.h),
 // the complete lists in CSR form: pt_list_offsets, pt_query_overlap_lists, pt_query_triangles_lists, and the posed-mesh queries
-// pt_set_query_mesh, pt_get_query_mesh, pt_pose_triangles, pt_query_poses_any, pt_query_poses_distance.
-// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip, segment.hip, tridist.hip, winding.hip, lists.hip and poses.hip; their one walk, leaf routine and launch are in bvh_walk.h, closest_point.h and query_launch.h.  The context and what the units share: context.h.
+// pt_set_query_mesh, pt_get_query_mesh, pt_pose_triangles, pt_query_poses_any, pt_query_poses_distance, and the translating-triangle
+// casts pt_query_triangle_cast, pt_query_triangle_cast_any, pt_query_poses_cast.
+// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip, segment.hip, tridist.hip, winding.hip, lists.hip, poses.hip and tricast.hip; their one walk, leaf routine and launch are in bvh_walk.h, closest_point.h and query_launch.h.  The context and what the units share: context.h.
 #include <cmath>
 
 #include "../../include/acgpt_test.h"
@@ -22,6 +23,7 @@
 #include "segment.h"
 #include "tridist.h"
 #include "sweep.h"
+#include "tricast.h"
 #include "tritri.h"
 
 static_assert(sizeof(pt_hit) == 32, "pt_hit: a change of this layout bumps pt_abi_version");
@@ -30,6 +32,7 @@ static_assert(sizeof(pt_sweep_hit) == 32, "pt_sweep_hit: a change of this layout
 static_assert(sizeof(pt_segment_hit) == 32, "pt_segment_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_triangle_distance_hit) == 48, "pt_triangle_distance_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_pose_distance_hit) == 48, "pt_pose_distance_hit: a change of this layout bumps pt_abi_version");
+static_assert(sizeof(pt_triangle_cast_hit) == 32, "pt_triangle_cast_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_ao_params) == 32, "pt_ao_params: a change of this layout bumps pt_abi_version");
 
 // The node array the scene holds, as pt_render_features picks it: fp16 centre / half-extent nodes for the default variants, fp32
@@ -714,6 +717,81 @@ PT_API int pt_debug_sweep_visits(pt_ctx* c, const float* sweeps, size_t n, pt_sw
                                    (uint32_t)n, (float4*)hits, (uint2*)visits, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
+}
+
+// ---- translating-triangle casts ---------------------------------------------------------------------------------------------------
+// every refusal of the three per-triangle calls before any device work, in pt_query_triangle_distance's order; a cast is 64 bytes.
+// out_bytes: bytes of output per cast.  Returns 0 to go on, 1 refused, -1 nothing to do (n == 0).
+static int triangle_cast_prepare(pt_ctx* c, const char* fn, const float* casts, size_t n, const void* out, size_t out_bytes, bool out_aligned, const void* visits,
+                                 bool with_visits, int* fmt)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (n == 0) return -1;
+    if (!casts || !out || (with_visits && !visits)) return fail(c, f + "null argument");
+    if (n > 0x7FFFFFFFull) return fail(c, f + "too many casts (2^31 - 1 per call)");
+    if (((uintptr_t)casts & 15u) || (out_aligned && ((uintptr_t)out & 15u))) return fail(c, f + "the cast and hit arrays must be 16-byte aligned");
+    if ((uintptr_t)visits & 7u) return fail(c, f + "the visit counts must be 8-byte aligned");
+    if (spans_overlap(casts, n * 64u, out, n * out_bytes)) return fail(c, f + "the output overlaps the casts");
+    if (with_visits && (spans_overlap(casts, n * 64u, visits, n * 8u) || spans_overlap(out, n * out_bytes, visits, n * 8u)))
+        return fail(c, f + "the visit counts overlap another array");
+    return query_node_format(c, f, fmt);
+}
+
+PT_API int pt_query_triangle_cast(pt_ctx* c, const float* casts, size_t n, pt_triangle_cast_hit* hits)
+{
+    int fmt = 0;
+    if (int rc = triangle_cast_prepare(c, "pt_query_triangle_cast", casts, n, hits, sizeof(pt_triangle_cast_hit), true, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_triangle_cast");
+    CK(c, ptd::launch_query_triangle_cast(fmt, device_scene(c), c->stack_entries, ptd::cast_scene_scale(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)casts,
+                                          (uint32_t)n, (float4*)hits, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_query_triangle_cast_any(pt_ctx* c, const float* casts, size_t n, uint8_t* blocked)
+{
+    int fmt = 0;
+    if (int rc = triangle_cast_prepare(c, "pt_query_triangle_cast_any", casts, n, blocked, 1, false, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_triangle_cast_any");
+    CK(c, ptd::launch_query_triangle_cast_any(fmt, device_scene(c), c->stack_entries, ptd::cast_scene_scale(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)casts,
+                                              (uint32_t)n, blocked, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_debug_triangle_cast_visits(pt_ctx* c, const float* casts, size_t n, pt_triangle_cast_hit* hits, uint32_t* visits)
+{
+    int fmt = 0;
+    if (int rc = triangle_cast_prepare(c, "pt_debug_triangle_cast_visits", casts, n, hits, sizeof(pt_triangle_cast_hit), true, visits, true, &fmt)) return rc < 0 ? 0 : rc;
+    CK(c, ptd::launch_triangle_cast_visits(fmt, device_scene(c), c->stack_entries, ptd::cast_scene_scale(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)casts,
+                                           (uint32_t)n, (float4*)hits, (uint2*)visits, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+static int poses_cast_run(pt_ctx* c, const char* fn, const float* poses, const float* motions, size_t P, pt_triangle_cast_hit* out, uint32_t flags)
+{
+    PoseSpan spans[3] = {{poses, P * 48u, 15u, true, "the poses"}, {motions, P * 16u, 15u, true, "the motions"}, {out, P * sizeof(pt_triangle_cast_hit), 15u, true, "out"}};
+    int fmt = 0;
+    if (int rc = poses_prepare(c, fn, P, spans, 3, -1, &fmt)) return rc < 0 ? 0 : rc;
+    Range range(fn);
+    CK(c, c->d_pose_words.reserve(P, c->stream));
+    CK(c, ptd::launch_poses_cast(fmt, device_scene(c), c->stack_entries, ptd::cast_scene_scale(c->bvh.scene_lo, c->bvh.scene_hi), c->d_pose_mesh.p, c->pose_mesh_tris,
+                                 (const float4*)poses, (const float4*)motions, (uint32_t)P, c->d_pose_words.p, (float4*)out, flags, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_query_poses_cast(pt_ctx* c, const float* poses, const float* motions, size_t P, pt_triangle_cast_hit* out)
+{
+    return poses_cast_run(c, "pt_query_poses_cast", poses, motions, P, out, 0u);
+}
+
+PT_API int pt_debug_query_poses_cast(pt_ctx* c, const float* poses, const float* motions, size_t P, pt_triangle_cast_hit* out, uint32_t flags)
+{
+    if (c && flags > (ptd::kPoseNoEarly | ptd::kPosePoseMajor)) return fail(c, "pt_debug_query_poses_cast: flags is 0..3 (1: no early look, 2: pose-major lanes)");
+    return poses_cast_run(c, "pt_debug_query_poses_cast", poses, motions, P, out, flags);
 }
 
 // ---- ambient occlusion ----------------------------------------------------------------------------------------------------------

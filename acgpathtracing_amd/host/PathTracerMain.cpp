@@ -17,6 +17,7 @@
 //              [--until-error E [--until-permille P] [--error-floor F] [--error-out file.pfm]]
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
 //              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k|,all] ...] [--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k|,all] ...]
+//              [--cast x0,y0,z0,x1,y1,z1,x2,y2,z2,dx,dy,dz[,tmax] ...] [--cast-mesh mesh.obj,dx,dy,dz[,tmax] ...]
 //              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...] [--clearance x0,y0,z0,x1,y1,z1[,radius] ...]
 //              [--tri-distance x0,y0,z0,x1,y1,z1,x2,y2,z2[,radius] ...]
 //              [--collide mesh.obj[,tx,ty,tz[,radius]] ...]
@@ -74,6 +75,14 @@
 // weights of its second and third vertex there), {"sweep": [...], "tmax": ..., "hit": false} if nothing is touched.  Floats are printed
 // with nine digits.  A value that is not finite (tmax may be inf), a negative radius or a negative tmax is refused with exit status 2.
 // The frames are the same with or without it.
+// --cast x0,y0,z0,x1,y1,z1,x2,y2,z2,dx,dy,dz[,tmax] (repeatable): how far the triangle of these three vertices translates along d before it
+// first touches the scene (t in units of |d|, at most tmax, default unbounded), all in one call of pt_query_triangle_cast, one JSON line
+// each: {"cast": [the twelve numbers], "tmax": <tmax or null>, "hit": true, "t": ..., "triangle": <index>, "feature": <0..15>,
+// "material": "<newmtl name>", "point": [x, y, z]}, or {"cast": [...], "tmax": ..., "hit": false}.  A value that is not finite (tmax may
+// be inf) or a negative tmax is refused with exit status 2.
+// --cast-mesh mesh.obj,dx,dy,dz[,tmax] (repeatable): the same for a whole second OBJ, as it is, by pt_set_query_mesh and
+// pt_query_poses_cast: {"cast_mesh": "<path>", "triangles": T, "motion": [dx, dy, dz], "tmax": ..., "hit": true, "t": ..., "triangle":
+// <scene triangle>, "feature": .., "query_triangle": <the mesh triangle that touches first>, "material": .., "point": [..]}.
 // --clearance x0,y0,z0,x1,y1,z1[,radius] (repeatable): once the scene is set and before the first frame, how far the segment from
 // (x0, y0, z0) to (x1, y1, z1) is from the scene and where the two come closest, all in one call of pt_query_segments with no limit on
 // the distance, one JSON line each: {"clearance": [the six coordinates], "radius": r, "found": true, "distance": .., "clear": <distance
@@ -935,6 +944,79 @@ static void sweepSpheres(PathTracerState& state, const TinyObjWrapper& obj, cons
     fflush(stdout);
 }
 
+// --cast: every translating triangle in one call of pt_query_triangle_cast; one JSON line per cast
+struct CastArg { float v[16]; };
+static void printCastHit(const pt_triangle_cast_hit& r, const std::vector<std::string>& names, bool posed)
+{
+    if (r.prim == 0xFFFFFFFFu) { printf(", \"hit\": false}\n"); return; }
+    std::string name = r.material < names.size() ? names[r.material] : std::string();
+    for (size_t k = 0; k < name.size(); k++) if (name[k] == '"' || name[k] == '\\' || (unsigned char)name[k] < 0x20) name[k] = '_';
+    printf(", \"hit\": true, \"t\": %.9g, \"triangle\": %u, \"feature\": %d, ", r.t, r.prim, (int)r.feature);
+    if (posed) printf("\"query_triangle\": %u, ", r.query_triangle);
+    printf("\"material\": \"%s\", \"point\": [%.9g, %.9g, %.9g]}\n", name.c_str(), r.cx, r.cy, r.cz);
+}
+static void castTriangles(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<CastArg>& casts)
+{
+    const size_t n = casts.size();
+    void* d_casts = nullptr; void* d_out = nullptr;
+    std::vector<pt_triangle_cast_hit> out(n);
+    std::string err;
+    if (pt_device_malloc(state.context, &d_casts, n * 64) != 0 || pt_device_malloc(state.context, &d_out, n * sizeof(pt_triangle_cast_hit)) != 0 ||
+        pt_copy_to_device(state.context, d_casts, casts.data(), n * 64) != 0 ||
+        pt_query_triangle_cast(state.context, (const float*)d_casts, n, (pt_triangle_cast_hit*)d_out) != 0 ||
+        pt_copy_to_host(state.context, out.data(), d_out, n * sizeof(pt_triangle_cast_hit)) != 0)
+        err = pt_last_error(state.context);
+    if (d_casts) pt_device_free(state.context, d_casts);
+    if (d_out) pt_device_free(state.context, d_out);
+    if (!err.empty()) throw Exception("cast: " + err);
+    for (size_t i = 0; i < n; i++) {
+        const float* q = casts[i].v;
+        printf("{\"cast\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"tmax\": ", q[0], q[1], q[2], q[4], q[5], q[6], q[8], q[9], q[10],
+               q[12], q[13], q[14]);
+        if (std::isfinite(q[3])) printf("%.9g", q[3]); else printf("null");
+        printCastHit(out[i], obj.getMaterialNames(), false);
+    }
+    fflush(stdout);
+}
+
+// --cast-mesh mesh.obj,dx,dy,dz[,tmax] (repeatable): a second OBJ as the query mesh (pt_set_query_mesh), as it is, moving along d; one
+// JSON line: how far it gets (pt_query_poses_cast) and which of its triangles touches what first
+struct CastMesh { std::string path; float d[3]; float tmax; };
+static void castMeshes(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<CastMesh>& meshes)
+{
+    for (size_t i = 0; i < meshes.size(); i++) {
+        const CastMesh& m = meshes[i];
+        TinyObjWrapper mesh(m.path);
+        const std::vector<float> v = mesh.getVerticesFloat();
+        const std::vector<uint32_t> idx = mesh.getIndexBuffer();
+        const size_t T = idx.size() / 3;
+        std::vector<float> recs(T * 12, 0.0f);
+        for (size_t k = 0; k < T * 3; k++) for (int c = 0; c < 3; c++) recs[k * 4 + c] = v[(size_t)idx[k] * 4 + c];
+        const float pose[12] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f};
+        const float motion[4] = {m.d[0], m.d[1], m.d[2], m.tmax};
+        void* d_pose = nullptr; void* d_motion = nullptr; void* d_out = nullptr;
+        pt_triangle_cast_hit r;
+        std::string err;
+        if (T == 0) err = "the mesh has no triangles";
+        else if (pt_set_query_mesh(state.context, recs.data(), T) != 0 || pt_device_malloc(state.context, &d_pose, 48) != 0 || pt_device_malloc(state.context, &d_motion, 16) != 0 ||
+                 pt_device_malloc(state.context, &d_out, sizeof(r)) != 0 || pt_copy_to_device(state.context, d_pose, pose, 48) != 0 ||
+                 pt_copy_to_device(state.context, d_motion, motion, 16) != 0 ||
+                 pt_query_poses_cast(state.context, (const float*)d_pose, (const float*)d_motion, 1, (pt_triangle_cast_hit*)d_out) != 0 ||
+                 pt_copy_to_host(state.context, &r, d_out, sizeof(r)) != 0)
+            err = pt_last_error(state.context);
+        if (d_pose) pt_device_free(state.context, d_pose);
+        if (d_motion) pt_device_free(state.context, d_motion);
+        if (d_out) pt_device_free(state.context, d_out);
+        if (!err.empty()) throw Exception("cast-mesh: " + err);
+        std::string name = m.path;
+        for (size_t k = 0; k < name.size(); k++) if (name[k] == '"' || name[k] == '\\' || (unsigned char)name[k] < 0x20) name[k] = '_';
+        printf("{\"cast_mesh\": \"%s\", \"triangles\": %zu, \"motion\": [%.9g, %.9g, %.9g], \"tmax\": ", name.c_str(), T, m.d[0], m.d[1], m.d[2]);
+        if (std::isfinite(m.tmax)) printf("%.9g", m.tmax); else printf("null");
+        printCastHit(r, obj.getMaterialNames(), true);
+    }
+    fflush(stdout);
+}
+
 // --clearance: every segment in one call of pt_query_segments; one JSON line per segment
 struct ClearanceSegment { float g[8]; float radius; };
 static void clearanceSegments(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<ClearanceSegment>& segs)
@@ -1241,6 +1323,8 @@ int main(int argc, char** argv)
     std::vector<OverlapBox> overlaps;
     std::vector<IntersectTri> intersects;
     std::vector<SweepArg> sweeps;
+    std::vector<CastArg> casts;
+    std::vector<CastMesh> castMeshList;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
     bool zero_copy = false, move_history = false, no_area_light = false;
     std::string env_path, tonemap, exposure_arg, out_hdr, error_out, ao_out;
@@ -1442,6 +1526,34 @@ int main(int argc, char** argv)
             if (!ok) { std::cerr << "--sweep ox,oy,oz,dx,dy,dz,r[,tmax]: finite values, a radius >= 0, a tmax >= 0" << std::endl; return 2; }
             sweeps.push_back(w);
         }
+        else if (a == "--cast") {
+            CastArg w = {{0.0f, 0.0f, 0.0f, INFINITY, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};
+            float* v = w.v;
+            const int got = sscanf(next(), "%f,%f,%f,%f,%f,%f,%f,%f,%f,%f,%f,%f,%f", &v[0], &v[1], &v[2], &v[4], &v[5], &v[6], &v[8], &v[9], &v[10], &v[12], &v[13], &v[14], &v[3]);
+            bool ok = got >= 12 && v[3] >= 0.0f;
+            for (int j = 0; j < 15; j++) ok = ok && (j == 3 || std::isfinite(v[j]));
+            if (!ok) { std::cerr << "--cast x0,y0,z0,x1,y1,z1,x2,y2,z2,dx,dy,dz[,tmax]: finite values, a tmax >= 0" << std::endl; return 2; }
+            casts.push_back(w);
+        }
+        else if (a == "--cast-mesh") {
+            CastMesh cm = {std::string(), {0.0f, 0.0f, 0.0f}, INFINITY};
+            const std::string text = next();
+            const size_t comma = text.find(',');
+            cm.path = text.substr(0, comma);
+            bool fine = !cm.path.empty() && comma != std::string::npos;
+            if (fine) {
+                int used = 0;
+                const char* rest = text.c_str() + comma;
+                fine = sscanf(rest, ",%f,%f,%f%n", &cm.d[0], &cm.d[1], &cm.d[2], &used) == 3;
+                if (fine && rest[used] != '\0') {               // a fourth number, tmax, and nothing behind it
+                    int more = 0;
+                    fine = sscanf(rest + used, ",%f%n", &cm.tmax, &more) == 1 && rest[used + more] == '\0' && cm.tmax >= 0.0f;
+                }
+                for (int k = 0; k < 3; k++) if (!std::isfinite(cm.d[k])) fine = false;
+            }
+            if (!fine) { std::cerr << "--cast-mesh mesh.obj,dx,dy,dz[,tmax]: a file, a finite motion, a tmax >= 0" << std::endl; return 2; }
+            castMeshList.push_back(cm);
+        }
         else if (a == "--materials") {
             const std::string m = next();
             if (m == "reference") material_model = PT_MATERIALS_REFERENCE;
@@ -1574,6 +1686,8 @@ int main(int argc, char** argv)
         if (!overlaps.empty()) { std::cout.flush(); overlapBoxes(state, obj, overlaps); }
         if (!intersects.empty()) { std::cout.flush(); intersectTriangles(state, intersects); }
         if (!sweeps.empty()) { std::cout.flush(); sweepSpheres(state, obj, sweeps); }
+        if (!casts.empty()) { std::cout.flush(); castTriangles(state, obj, casts); }
+        if (!castMeshList.empty()) { std::cout.flush(); castMeshes(state, obj, castMeshList); }
         if (ao_samples > 0) ambientOcclusion(state, ao_samples, ao_radius, ao_bias, ao_frames, ao_out);
         HistoryFile history;
         if (!history_in.empty()) {              // refused before any frame is rendered

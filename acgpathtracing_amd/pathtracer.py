@@ -2159,6 +2159,243 @@ def sweepContacts(result, sweeps):
     return np.where(hit[:, None], centre, nan).astype(np.float32), np.where(hit[:, None], normal, nan).astype(np.float32), t == 0
 
 
+# ------------------------------------------------------------------ translating-triangle casts ----
+TRIANGLE_CAST_DTYPE = np.dtype([("t", np.float32), ("prim", np.uint32), ("feature", np.float32), ("query_triangle", np.uint32), ("point", np.float32, 3),
+                                ("material", np.uint32)])      # pt_triangle_cast_hit
+assert TRIANGLE_CAST_DTYPE.itemsize == 32
+
+
+def _cast_records(what, casts, directions, tmax):
+    """The (n, 16) float32 records {a0, tmax | a1, . | a2, . | d, .} of a NumPy call, every refusal before any device work."""
+    p = np.asarray(casts)
+    if p.dtype.kind not in "fiu":
+        raise PathTracerError("%s: the casts must be numbers, got %s" % (what, p.dtype))
+    if directions is None:
+        if p.ndim != 2 or p.shape[1] != 16:
+            raise PathTracerError("%s: expected an (n, 16) array {a0, tmax, a1, ., a2, ., d, .}, or triangles with directions, got shape %s" % (what, p.shape))
+        return np.ascontiguousarray(p, np.float32)
+    if p.ndim == 3 and p.shape[1:] == (3, 3):
+        tri = p.astype(np.float32)
+    elif p.ndim == 2 and p.shape[1] == 9:
+        tri = p.astype(np.float32).reshape(-1, 3, 3)
+    elif p.ndim == 2 and p.shape[1] == 12:
+        tri = p.astype(np.float32).reshape(-1, 3, 4)[:, :, :3]
+    else:
+        raise PathTracerError("%s: expected (n, 3, 3), (n, 9) or (n, 12) triangles with directions, got shape %s" % (what, p.shape))
+    n = tri.shape[0]
+    d = np.asarray(directions)
+    if d.dtype.kind not in "fiu" or d.shape not in ((3,), (n, 3)):
+        raise PathTracerError("%s: expected one direction (3,) or one per triangle (n, 3), got shape %s" % (what, d.shape))
+    a = np.asarray(tmax, np.float64)
+    if a.ndim not in (0, 1) or (a.ndim == 1 and a.shape[0] != n):
+        raise PathTracerError("%s: tmax is one number or one per cast, got shape %s" % (what, a.shape))
+    if not (a >= 0.0).all():
+        raise PathTracerError("%s: tmax must be non-negative, got %r" % (what, tmax))
+    s = np.zeros((n, 16), np.float32)
+    s[:, 0:3], s[:, 4:7], s[:, 8:11] = tri[:, 0], tri[:, 1], tri[:, 2]
+    s[:, 12:15] = d
+    s[:, 3] = a
+    return s
+
+
+def _cast_tensor(what, state, x, width, name):
+    import torch
+    if x.device.type != "cuda" or x.device.index != state._device:
+        raise PathTracerError("%s: the %s are on %s, the context is on cuda:%d" % (what, name, x.device, state._device))
+    if x.dtype != torch.float32:
+        raise PathTracerError("%s: the %s must be float32, got %s" % (what, name, x.dtype))
+    if x.dim() != 2 or x.shape[1] != width:
+        raise PathTracerError("%s: expected an (n, %d) tensor of %s, got shape %s" % (what, width, name, tuple(x.shape)))
+    if not x.is_contiguous():
+        raise PathTracerError("%s: the %s must be contiguous (nothing is copied)" % (what, name))
+    return torch
+
+
+def _cast_columns(out):
+    if _is_tensor(out):
+        import torch
+        return {"t": out[:, 0], "prim": out[:, 1].view(torch.int32), "feature": out[:, 2], "query_triangle": out[:, 3].view(torch.int32), "point": out[:, 4:7],
+                "material": out[:, 7].view(torch.int32)}
+    return {k: np.ascontiguousarray(out[k]) for k in TRIANGLE_CAST_DTYPE.names}
+
+
+def queryTriangleCast(state, casts_or_triangles, directions=None, tmax=float("inf"), any_hit=False):
+    """How far a triangle translates along d before it first touches the scene on the GPU, and where (include/acgpt.h
+    pt_query_triangle_cast): the triangle occupies a_i + t d for 0 <= t <= tmax, t in units of |d|.
+
+    NumPy (or anything np.asarray takes): (n, 16) records {a0, tmax | a1, . | a2, . | d, .}, or (n, 3, 3), (n, 9) or (n, 12) triangles
+    with directions (3,) or (n, 3) and tmax (one number or one per cast).  The answer is a dict of arrays t (n,) float32 (-1 on a miss,
+    0 on a start overlap), prim (n,) uint32 (0xFFFFFFFF), feature (n,) float32 (0..2: a corner of the query meets the scene triangle;
+    3..5: a corner of the scene triangle meets the query; 6..14: edge 3 i + j, an edge pair; 15: start overlap), query_triangle (n,)
+    uint32 (0 here), point (n, 3) the contact in world space (zero on a start overlap), material (n,) uint32.  castContacts turns it
+    into normals.  any_hit=True asks pt_query_triangle_cast_any instead and returns a bool array (n,): blocked or not.
+
+    A torch tensor must be (n, 16) float32, contiguous and on the context's device; nothing is copied, its data_ptr() goes straight in,
+    and the answer is torch tensors on that device: views of one (n, 8) float32 tensor, prim, query_triangle and material as int32
+    (-1 on a miss), or a bool tensor with any_hit.  torch's current stream is synchronised before the call, and the call returns
+    synchronised."""
+    L = _native.hip()
+    if _is_tensor(casts_or_triangles):
+        x = casts_or_triangles
+        if directions is not None:
+            raise PathTracerError("queryTriangleCast: a tensor holds whole records (n, 16); directions go with arrays")
+        torch = _cast_tensor("queryTriangleCast", state, x, 16, "casts")
+        n = int(x.shape[0])
+        with torch.cuda.device(x.device):
+            out = torch.empty((n,), dtype=torch.uint8, device=x.device) if any_hit else torch.empty((n, 8), dtype=torch.float32, device=x.device)
+            torch.cuda.current_stream().synchronize()      # the casts' producer and the allocation; the call below returns synchronised
+        if any_hit:
+            _check(state.context, L.pt_query_triangle_cast_any(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_triangle_cast_any")
+            return out.view(torch.bool)
+        _check(state.context, L.pt_query_triangle_cast(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_triangle_cast")
+        return _cast_columns(out)
+    s = _cast_records("queryTriangleCast", casts_or_triangles, directions, tmax)
+    n = s.shape[0]
+    out = np.zeros(n, np.uint8) if any_hit else np.zeros(n, TRIANGLE_CAST_DTYPE)
+    if n:
+        bufs = _device_buffers(state, 2, s.nbytes)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], s.ctypes.data, s.nbytes), "copy to device")
+            if any_hit:
+                _check(state.context, L.pt_query_triangle_cast_any(state.context, bufs[0], n, bufs[1]), "pt_query_triangle_cast_any")
+            else:
+                _check(state.context, L.pt_query_triangle_cast(state.context, bufs[0], n, bufs[1]), "pt_query_triangle_cast")
+            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    return out.view(np.bool_) if any_hit else _cast_columns(out)
+
+
+def _motion_records(what, motions, P):
+    m = np.asarray(motions)
+    if m.dtype.kind not in "fiu" or m.shape not in ((P, 4), (P, 3), (4,), (3,)):
+        raise PathTracerError("%s: expected (P, 4) motions {d, tmax}, (P, 3) directions or one of either, got shape %s" % (what, m.shape))
+    out = np.full((P, 4), np.inf, np.float32)
+    out[:, :m.shape[-1]] = m
+    return out
+
+
+def queryPosesCast(state, poses, motions):
+    """How far the query mesh (setQueryMesh) translates from each pose before it first touches the scene on the GPU, and where
+    (include/acgpt.h pt_query_poses_cast).  motions: (P, 4) {d, tmax} in the world frame, applied after the pose ((P, 3): tmax = +inf;
+    one row for all poses).  Returns queryTriangleCast's dict, one row per pose, with query_triangle the mesh triangle that touches
+    first (the smallest t, ties to the lowest index; 0xFFFFFFFF, or -1 in a tensor, where nothing is touched).  The P x T posed
+    triangles are formed in registers.  Poses as queryPosesAny takes them; with a poses tensor the motions are a (P, 4) float32 tensor on
+    the same device, and the answer is tensors."""
+    L = _native.hip()
+    recs = _pose_records("queryPosesCast", state, poses)
+    P = int(recs.shape[0])
+    if _is_tensor(recs):
+        if not _is_tensor(motions):
+            raise PathTracerError("queryPosesCast: tensor poses take a (P, 4) tensor of motions")
+        torch = _cast_tensor("queryPosesCast", state, motions, 4, "motions")
+        if int(motions.shape[0]) != P:
+            raise PathTracerError("queryPosesCast: %d poses and %d motions" % (P, int(motions.shape[0])))
+        with torch.cuda.device(recs.device):
+            out = torch.empty((P, 8), dtype=torch.float32, device=recs.device)
+            torch.cuda.current_stream().synchronize()
+        _check(state.context, L.pt_query_poses_cast(state.context, recs.data_ptr() if P else None, motions.data_ptr() if P else None, P, out.data_ptr() if P else None),
+               "pt_query_poses_cast")
+        return _cast_columns(out)
+    m = _motion_records("queryPosesCast", motions, P)
+    out = np.zeros(P, TRIANGLE_CAST_DTYPE)
+    if P:
+        bufs = _device_buffers(state, 3, recs.nbytes)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], recs.ctypes.data, recs.nbytes), "copy to device")
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[1], m.ctypes.data, m.nbytes), "copy to device")
+            _check(state.context, L.pt_query_poses_cast(state.context, bufs[0], bufs[1], P, bufs[2]), "pt_query_poses_cast")
+            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[2], out.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    return _cast_columns(out)
+
+
+def meshCast(state, vertices, indices, poses, motions):
+    """queryPosesCast by the materialising route, kept for comparison: the P x T posed triangles are formed on the host by the header's
+    statement (x' = ((m[0] x + m[1] y) + m[2] z) + m[3], float32, in that order), cast with one queryTriangleCast call and reduced per
+    pose to the smallest t, ties to the lowest mesh triangle.  NumPy only.  The same dict, the same bits."""
+    rec = _posed_records("meshCast", vertices, indices, None)[0].reshape(-1, 3, 4)[:, :, :3]
+    p = _pose_records("meshCast", state, poses).reshape(-1, 3, 4)
+    P, T = p.shape[0], rec.shape[0]
+    m = _motion_records("meshCast", motions, P)
+    out = np.zeros(P, TRIANGLE_CAST_DTYPE)
+    out["t"], out["prim"], out["query_triangle"], out["material"] = -1.0, 0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF
+    if P and T:
+        casts = np.zeros((P, T, 16), np.float32)
+        with np.errstate(all="ignore"):
+            x, y, z = rec[None, :, :, 0], rec[None, :, :, 1], rec[None, :, :, 2]
+            for j in range(3):
+                m0, m1, m2, m3 = (p[:, j, c, None, None] for c in range(4))
+                casts[:, :, j:12:4] = ((m0 * x + m1 * y) + m2 * z) + m3
+        casts[:, :, 3] = m[:, None, 3]
+        casts[:, :, 12:15] = m[:, None, 0:3]
+        got = queryTriangleCast(state, casts.reshape(P * T, 16))
+        t = got["t"].reshape(P, T)
+        key = np.where(t >= 0, t, np.float32(np.inf))
+        tri = key.argmin(axis=1)                           # the first (lowest) mesh triangle among the ties
+        found = (t >= 0).any(axis=1)
+        row = np.arange(P) * T + tri
+        for k in ("t", "prim", "feature", "point", "material"):
+            out[k][found] = got[k][row][found]
+        out["query_triangle"][found] = tri[found]
+    return _cast_columns(out)
+
+
+def castContacts(result, casts, vertices, indices):
+    """What a slide-and-step controller needs of queryTriangleCast's answer: (normals, start_overlap) — the unit contact normal (n, 3)
+    by the winning feature, facing against d: the scene triangle's normal (features 0..2), the query triangle's (3..5), or cross(D, E)
+    of the two edges that met (6 + 3 i + j: the query's edge i of (a1 - a0, a2 - a0, a2 - a1), the scene triangle's edge j of (v1 - v0,
+    v2 - v0, v2 - v1)); and where the triangle touched the scene before it moved, t == 0 with feature 15 (n,) bool.  A miss has NaN
+    normals, a start overlap and a degenerate feature a zero normal.  casts: the (n, 16) records the result answers; vertices, indices:
+    the scene's.  NumPy; tensors are read back."""
+    def host(a):
+        return a.cpu().numpy() if _is_tensor(a) else np.asarray(a)
+    s = host(casts).astype(np.float64)
+    t, feature, prim = host(result["t"]), host(result["feature"]), host(result["prim"]).astype(np.int64) & 0xFFFFFFFF
+    if s.ndim != 2 or s.shape[1] != 16 or t.shape != (s.shape[0],):
+        raise PathTracerError("castContacts: expected the (n, 16) casts of the result, got shape %s" % (s.shape,))
+    v = host(vertices).astype(np.float64).reshape(-1, 4)[:, :3] if host(vertices).ndim == 1 else host(vertices).astype(np.float64)[:, :3]
+    idx = host(indices).astype(np.int64).reshape(-1, 3)
+    hit = t >= 0
+    tri = v[idx[np.where(hit, prim, 0)]] if idx.shape[0] else np.zeros((s.shape[0], 3, 3))
+    a0, a1, a2, d = s[:, 0:3], s[:, 4:7], s[:, 8:11], s[:, 12:15]
+    q_edges = np.stack([a1 - a0, a2 - a0, a2 - a1], axis=1)
+    s_edges = np.stack([tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], tri[:, 2] - tri[:, 1]], axis=1)
+    f = np.where(hit, feature, 15).astype(np.int64)
+    k = np.clip(f - 6, 0, 8)
+    rows = np.arange(s.shape[0])
+    normal = np.where((f <= 2)[:, None], np.cross(s_edges[:, 0], s_edges[:, 1]),
+                      np.where((f <= 5)[:, None], np.cross(q_edges[:, 0], q_edges[:, 1]), np.cross(q_edges[rows, k // 3], s_edges[rows, k % 3])))
+    normal = np.where((f == 15)[:, None], 0.0, normal)
+    with np.errstate(all="ignore"):
+        length = np.sqrt((normal * normal).sum(axis=1, keepdims=True))
+        normal = np.where(length > 0, normal / np.where(length > 0, length, 1.0), 0.0)
+        normal = np.where(((normal * d).sum(axis=1) > 0)[:, None], -normal, normal)
+    return np.where(hit[:, None], normal, np.nan).astype(np.float32), hit & (f == 15)
+
+
+def advanceUntilContact(state, poses):
+    """Step the query mesh (setQueryMesh) along a polyline of K poses until it first touches the scene: leg k moves the mesh in pose k
+    by the translation from pose k to pose k + 1 (the rotation changes between the legs, not within one).  All K - 1 legs are one
+    queryPosesCast call with tmax = 1.  Returns a dict: leg (the first blocked leg, -1 when the whole path is free), t (its time of
+    impact in [0, 1]; 1 when free), pose (3, 4) float32 (where the mesh stops: pose `leg` moved by t of the leg; the last pose when
+    free) and contact (queryPosesCast's row of that leg, None when free)."""
+    p = np.asarray(_pose_records("advanceUntilContact", state, poses.cpu().numpy() if _is_tensor(poses) else poses)).reshape(-1, 3, 4)
+    if p.shape[0] < 2:
+        raise PathTracerError("advanceUntilContact: a path has at least two poses, got %d" % p.shape[0])
+    motions = np.ones((p.shape[0] - 1, 4), np.float32)
+    motions[:, 0:3] = p[1:, :, 3] - p[:-1, :, 3]
+    got = queryPosesCast(state, p[:-1], motions)
+    blocked = np.flatnonzero(got["t"] >= 0)
+    if blocked.size == 0:
+        return {"leg": -1, "t": 1.0, "pose": p[-1].copy(), "contact": None}
+    k = int(blocked[0])
+    pose = p[k].copy()
+    pose[:, 3] = pose[:, 3] + motions[k, 0:3] * got["t"][k]
+    return {"leg": k, "t": float(got["t"][k]), "pose": pose, "contact": {name: got[name][k] for name in got}}
+
+
 # ------------------------------------------------------------------ ambient occlusion ----
 def aoSamples(K):
     """The default sample pattern of the ambient-occlusion calls: K points of a Vogel spiral on the unit disk, float32 (K, 2):

@@ -863,6 +863,69 @@ int pt_pose_triangles(pt_ctx* ctx, const float* poses, size_t P, float* tris_out
 int pt_query_poses_any(pt_ctx* ctx, const float* poses, size_t P, uint8_t* hit, uint32_t* first);
 int pt_query_poses_distance(pt_ctx* ctx, const float* poses, size_t P, float max_radius, pt_pose_distance_hit* out);
 
+/* ---- translating-mesh casts: time of impact of a moving triangle or posed mesh (opt-in; nothing above changes) -------------------
+ * The queries above that take a mesh of the caller's are discrete: does it intersect in this pose, how far away is it in this pose.
+ * Sampled along a motion they tunnel through a thin wall between two free poses.  These are the shape cast for a shape that is a mesh:
+ * how far can this triangle, or this whole posed mesh, translate along d before it first touches the scene, and where.
+ *
+ *   casts     n records of 16 floats {a0.xyz, tmax | a1.xyz, . | a2.xyz, . | d.xyz, .}; DEVICE, 16-byte aligned.  The dotted floats
+ *             are never read into a decision.  The triangle occupies a_i + t d for 0 <= t <= tmax, closed at both ends; d is not
+ *             normalised (t is in units of |d|); tmax = +inf is allowed and stands for the largest finite t.
+ *   hits      n records of 32 bytes; DEVICE, 16-byte aligned.  blocked: n bytes, DEVICE, any alignment.
+ *   motions   pt_query_poses_cast: P records {d.xyz, tmax} in the WORLD frame, applied after the pose's transform; DEVICE, 16-byte
+ *             aligned.
+ *
+ * The time of impact of one pair.  All arithmetic is fp32, every operation on its own, no fused multiply-add, IEEE division, on the
+ * stored v0, e1, e2 of the scene triangle, with dot and cross as written under pt_query_closest (tests/tricast_ref.py is the NumPy
+ * statement, equal bit for bit).  f1 = a1 - a0, f2 = a2 - a0, g = a2 - a1; w1 = v0 + e1, w2 = v0 + e2, h = e2 - e1; the query's edges
+ * Q0 = {a0, f1}, Q1 = {a0, f2}, Q2 = {a1, g}, the scene triangle's S0 = {v0, e1}, S1 = {v0, e2}, S2 = {w1, h}; qlo, qhi and slo, shi
+ * the fmin3 / fmax3 boxes of the query's and of the scene triangle's three corners (a0, a1, a2 and v0, w1, w2).
+ *
+ *   ray(o, r; p, k1, k2)   pv = cross(r, k2); det = dot(k1, pv); tv = o - p; U = dot(tv, pv); qv = cross(tv, k1); V = dot(r, qv);
+ *                          T = dot(k2, qv); where det < 0: det, U, V, T change sign.
+ *                          accepted iff det > 0, U >= 0, V >= 0, U + V <= det, T >= 0;  t = T / det + 0  (the + 0 turns a -0 into +0)
+ *   features 0, 1, 2       ray(a_i, d; v0, e1, e2);  c = a_i + d t;  guard: c inside [slo - eps, shi + eps]
+ *   features 3, 4, 5       ray(b_j, -d; a0, f1, f2) with b = (v0, w1, w2);  c = b_j;  guard: b_j - d t inside [qlo - eps, qhi + eps]
+ *   features 6 + 3 i + j   Q_i = {P, D} against S_j = {A, E}:  n = cross(D, E); det = dot(d, n); w = A - P; T = dot(w, n);
+ *                          S = dot(d, cross(w, E)); G = dot(d, cross(w, D)); where det < 0: det, T, S, G change sign.
+ *                          accepted iff det > 0, 0 <= S <= det, 0 <= G <= det, T >= 0;  t = T / det + 0;  c = A + E (G / det)
+ *                          guard: c - d t inside [qlo - eps, qhi + eps]
+ *   feature 15             the 20 conditions of pt_query_triangles hold at t = 0 (start overlap): t = 0, c = (0, 0, 0); it overrides
+ *                          the others
+ *   eps = 2^-16 * (largest |component| of v0, w1, w2  +  largest |component| of a0, a1, a2);  "inside" is six closed compares, each
+ *   bound one fp32 subtraction or addition.
+ *
+ * A feature is a candidate iff it is accepted, its guard holds and t <= tmax; every compare is false on a NaN, and t = +inf is no
+ * candidate.  Within a pair the smallest t wins, ties to the lower feature; over the scene the smallest t wins, ties to the lowest
+ * triangle index in the caller's order.  The guards tie every candidate's contact to both triangles' boxes within eps, whatever the
+ * angle: a near-singular det makes t noise, and a contact that noise has carried off both boxes is no contact.
+ * The record: t; prim; feature (the winning feature's number as a float); query_triangle (0 in the per-triangle calls); the contact
+ * c in world space (for features 0..2 the query's corner at t, for 3..5 the scene triangle's corner, for 6..14 the point of the scene
+ * edge; zero for a start overlap); material.  A miss is {-1, 0xFFFFFFFF, 0, 0 | 0, 0, 0, 0xFFFFFFFF}.  A miss before any traversal: a
+ * non-finite coordinate of the query or of d; a non-finite f1, f2 or g; a NaN or negative tmax; a scene without triangles.
+ * blocked[i] = 1 iff hits[i].t >= 0; its walk leaves at the first candidate.  With d = 0 only feature 15 can answer.
+ * Not seen: a triangle that slides exactly within a scene triangle's plane has every det = 0, so such a motion is reported only as a
+ * start overlap (in-plane sliding contacts are out of scope); likewise an edge sliding along a parallel edge.  Products of four
+ * lengths leave fp32's range as under pt_query_triangle_distance; such a feature silently stops being a candidate.
+ *
+ * pt_query_poses_cast   out[p] is, bit for bit, pt_query_triangle_cast's record for one posed triangle of pt_pose_triangles with
+ *             {tmax, d} = motions[p]: the one with the smallest t, ties to the lowest mesh triangle index, which is stored in
+ *             query_triangle.  A pose without a candidate gets the miss record with query_triangle 0xFFFFFFFF.  A non-finite motion,
+ *             like a non-finite pose entry, makes the pose a miss.
+ *
+ * Memory and call rules are pt_query_triangle_distance's (per triangle) and pt_query_poses_distance's (posed): the calls enqueue on the
+ * context's stream and return synchronised, act on rank 0 of a pt_create_multi context, never write the accumulation buffer, the frame
+ * buffer or pt_stats, and leave device_bytes unchanged.  The per-triangle calls use no atomics; the posed call uses the 8-byte word per
+ * pose with order-independent minima only.  Two calls give the same bits.  n == 0 and P == 0 are no-op successes.  Refused, with the
+ * context left usable, in the siblings' order and with messages that start "<entry point>: ": a null context; a null argument;
+ * n > 0x7FFFFFFF ("too many casts") or the posed calls' two limits; an array that is not 16-byte aligned; arrays that overlap; no
+ * query mesh (posed); a context without a scene.                                                                                  */
+typedef struct { float t; uint32_t prim; float feature; uint32_t query_triangle;
+                 float cx, cy, cz; uint32_t material; } pt_triangle_cast_hit;   /* 32 bytes */
+int pt_query_triangle_cast(pt_ctx* ctx, const float* casts, size_t n, pt_triangle_cast_hit* hits);
+int pt_query_triangle_cast_any(pt_ctx* ctx, const float* casts, size_t n, uint8_t* blocked);
+int pt_query_poses_cast(pt_ctx* ctx, const float* poses, const float* motions, size_t P, pt_triangle_cast_hit* out);
+
 /* ---- the K closest triangles of a point, and "is anything within r" (opt-in; nothing above changes) ------------------------------
  * pt_query_nearest answers with one triangle.  A ball resting in a corner touches three walls and needs all three contacts; a point
  * whose closest feature is an edge or a vertex ties between two to six triangles, of which pt_query_nearest names the lowest index

@@ -168,6 +168,14 @@ int pt_debug_triangle_distance_visits(pt_ctx* ctx, const float* tris, size_t n, 
  * on consecutive triangles of one pose) instead of triangle-major (all poses' triangle 0 first, the product's order).  Neither changes an output bit.  max_radius is read with out only.  Anything above 3 is
  * refused.  tools/poses_timing.py. */
 int pt_debug_query_poses(pt_ctx* ctx, const float* poses, size_t P, float max_radius, uint8_t* hit, uint32_t* first, pt_pose_distance_hit* out, uint32_t flags);
+/* pt_query_triangle_cast (same arguments, same records, same refusals) from a kernel instantiation that also counts: visits[2 i] =
+ * inner nodes cast i visited, visits[2 i + 1] = triangles it tested.  visits: DEVICE, 8-byte aligned, 2 n words.
+ * tools/tricast_timing.py. */
+int pt_debug_triangle_cast_visits(pt_ctx* ctx, const float* casts, size_t n, pt_triangle_cast_hit* hits, uint32_t* visits);
+/* pt_query_poses_cast (same answers, same refusals) from launches that take pt_debug_query_poses' flags: bit 0 switches the early look
+ * at the pose's word and the shrinking tmax off, bit 1 deals the lanes pose-major.  Neither changes an output bit.  Anything above 3
+ * is refused. */
+int pt_debug_query_poses_cast(pt_ctx* ctx, const float* poses, const float* motions, size_t P, pt_triangle_cast_hit* out, uint32_t flags);
 /* pt_query_nearest_k (hit null: same records, same counts, same refusals) or pt_query_within_any (hit given; max_k must be 0 and
  * out and counts null) from kernel instantiations that also count: visits[2 i] = inner nodes point i visited, visits[2 i + 1] =
  * triangles it tested.  visits: DEVICE, 8-byte aligned, 2 n words, never null.  tools/nearest_k_timing.py. */
