@@ -6,8 +6,9 @@
 // pt_query_within_any and the generalised winding number pt_query_winding (each with its counting twin of include/acgpt_test.h),
 // the complete lists in CSR form: pt_list_offsets, pt_query_overlap_lists, pt_query_triangles_lists, and the posed-mesh queries
 // pt_set_query_mesh, pt_get_query_mesh, pt_pose_triangles, pt_query_poses_any, pt_query_poses_distance, and the translating-triangle
-// casts pt_query_triangle_cast, pt_query_triangle_cast_any, pt_query_poses_cast.
-// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip, segment.hip, tridist.hip, winding.hip, lists.hip, poses.hip and tricast.hip; their one walk, leaf routine and launch are in bvh_walk.h, closest_point.h and query_launch.h.  The context and what the units share: context.h.
+// casts pt_query_triangle_cast, pt_query_triangle_cast_any, pt_query_poses_cast, and the oriented-box overlap queries
+// pt_query_overlap_oriented, pt_query_overlap_oriented_any, pt_query_overlap_oriented_lists with pt_pose_boxes.
+// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, tritri.hip, segment.hip, tridist.hip, winding.hip, lists.hip, poses.hip, tricast.hip and oriented.hip; their one walk, leaf routine and launch are in bvh_walk.h, closest_point.h and query_launch.h.  The context and what the units share: context.h.
 #include <cmath>
 
 #include "../../include/acgpt_test.h"
@@ -17,6 +18,7 @@
 #include "multihit.h"
 #include "nearest.h"
 #include "nearest_k.h"
+#include "oriented.h"
 #include "overlap.h"
 #include "poses.h"
 #include "query.h"
@@ -472,6 +474,87 @@ PT_API int pt_debug_list_phases(pt_ctx* c, uint32_t phases)
     if (!c) return fail(nullptr, "pt_debug_list_phases: null context");
     if (phases > 7u || !(phases & ptd::kListPhaseAll)) return fail(c, "pt_debug_list_phases: phases is 1 (fill), 2 (sort) or 3 (both), plus 4 for no register list");
     c->list_phases = phases;
+    return 0;
+}
+
+// ---- oriented-box overlap ---------------------------------------------------------------------------------------------------------
+// The three calls refuse what pt_query_overlap's and pt_query_overlap_lists' refuse, in the same order (overlap_prepare, lists_prepare);
+// a record is 64 bytes.
+static float oriented_term(pt_ctx* c) { return ptd::oriented_scene_term(c->bvh.scene_lo, c->bvh.scene_hi); }
+
+PT_API int pt_query_overlap_oriented(pt_ctx* c, const float* boxes, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts)
+{
+    // n < 2^31, max_prims <= 8: the byte counts stay below 2^37
+    const OverlapOut outs[2] = {{prims, (size_t)max_prims * 4u, 15u, false, "prims"}, {counts, 4u, 3u, false, "counts"}};
+    int fmt = 0;
+    if (int rc = overlap_prepare(c, "pt_query_overlap_oriented", boxes, n, true, max_prims, outs, 2, &fmt, "boxes", 64u)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_overlap_oriented");
+    CK(c, ptd::launch_query_oriented(fmt, device_scene(c), c->stack_entries, oriented_term(c), (const float4*)boxes, (uint32_t)n, max_prims, prims, counts, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_query_overlap_oriented_any(pt_ctx* c, const float* boxes, size_t n, uint8_t* hit)
+{
+    const OverlapOut outs[1] = {{hit, 1u, 0u, true, "hit"}};
+    int fmt = 0;
+    if (int rc = overlap_prepare(c, "pt_query_overlap_oriented_any", boxes, n, false, 0u, outs, 1, &fmt, "boxes", 64u)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_overlap_oriented_any");
+    CK(c, ptd::launch_query_oriented_any(fmt, device_scene(c), c->stack_entries, oriented_term(c), (const float4*)boxes, (uint32_t)n, hit, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+static int oriented_visits_run(pt_ctx* c, const char* fn, const float* boxes, size_t n, uint32_t* counts, uint32_t* visits, bool cross)
+{
+    const OverlapOut outs[2] = {{counts, 4u, 3u, true, "counts"}, {visits, 8u, 7u, true, "visits"}};
+    int fmt = 0;
+    if (int rc = overlap_prepare(c, fn, boxes, n, false, 0u, outs, 2, &fmt, "boxes", 64u)) return rc < 0 ? 0 : rc;
+    CK(c, ptd::launch_oriented_visits(fmt, device_scene(c), c->stack_entries, oriented_term(c), (const float4*)boxes, (uint32_t)n, counts, (uint2*)visits, cross, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_debug_overlap_oriented_visits(pt_ctx* c, const float* boxes, size_t n, uint32_t* counts, uint32_t* visits)
+{
+    return oriented_visits_run(c, "pt_debug_overlap_oriented_visits", boxes, n, counts, visits, false);
+}
+
+PT_API int pt_debug_overlap_oriented_visits_cross(pt_ctx* c, const float* boxes, size_t n, uint32_t* counts, uint32_t* visits)
+{
+    return oriented_visits_run(c, "pt_debug_overlap_oriented_visits_cross", boxes, n, counts, visits, true);
+}
+
+PT_API int pt_query_overlap_oriented_lists(pt_ctx* c, const float* boxes, size_t n, const uint32_t* offsets, uint32_t* prims, size_t capacity, uint32_t* found)
+{
+    int fmt = 0;
+    if (int rc = lists_prepare(c, "pt_query_overlap_oriented_lists", boxes, n, offsets, prims, capacity, found, &fmt, "boxes", 64u)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_overlap_oriented_lists");
+    const uint32_t cap = capacity > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)capacity;      // no 32-bit offset reaches further
+    return lists_run(c, "pt_query_overlap_oriented_lists", [&](uint32_t* flag) {
+        return ptd::launch_oriented_lists(fmt, device_scene(c), c->stack_entries, oriented_term(c), (const float4*)boxes, (uint32_t)n, offsets, prims, cap, found, flag,
+                                          c->list_phases, c->stream);
+    });
+}
+
+// poses -> oriented-box records.  Needs neither a scene nor a query mesh.  The refusals in the posed calls' order.
+PT_API int pt_pose_boxes(pt_ctx* c, const float* poses, size_t P, const float local_box[6], float* boxes_out)
+{
+    const std::string f = "pt_pose_boxes: ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (P == 0) return 0;
+    if (!poses || !local_box || !boxes_out) return fail(c, f + "null argument");
+    if (P > 0x7FFFFFFFull) return fail(c, f + "too many poses (2^31 - 1 per call)");
+    for (int k = 0; k < 6; k++)
+        if (!std::isfinite(local_box[k]) || (k >= 3 && !(local_box[k] >= 0.0f))) return fail(c, f + "local_box must be finite, its half extent non-negative");
+    if ((uintptr_t)poses & 15u) return fail(c, f + "the poses must be 16-byte aligned");
+    if ((uintptr_t)boxes_out & 15u) return fail(c, f + "boxes_out must be 16-byte aligned");
+    if (spans_overlap(poses, P * 48u, boxes_out, P * 64u)) return fail(c, f + "boxes_out overlaps the poses");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, f + "hipSetDevice failed");
+    Range range("pt_pose_boxes");
+    CK(c, ptd::launch_pose_boxes((const float4*)poses, (uint32_t)P, local_box[0], local_box[1], local_box[2], local_box[3], local_box[4], local_box[5], (float4*)boxes_out,
+                                 c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 

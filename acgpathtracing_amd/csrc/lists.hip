@@ -1,7 +1,9 @@
-// lists.hip — the kernels behind pt_list_offsets, pt_query_overlap_lists and pt_query_triangles_lists (include/acgpt.h).
+// lists.hip — the kernels behind pt_list_offsets, pt_query_overlap_lists, pt_query_triangles_lists and pt_query_overlap_oriented_lists
+// (include/acgpt.h).
 //
 //   k_list_tile_sums / k_list_scan_tiles / k_list_add_back   the scan: counts -> offsets, 64-bit sums, three launches, no look-back
-//   k_fill_lists<FMT, Q, REG>   one query per lane (Q: a box or a triangle), the walk and the leaf test of overlap.hip / tritri.hip through
+//   k_fill_lists<FMT, Q, REG>   (k_fill_oriented<FMT, REG> for the oriented boxes of oriented_device.h: the same body, fill_lists)
+//                          one query per lane (Q: a box, a triangle or an oriented box), the walk and the leaf test of overlap.hip / tritri.hip through
 //                          the shared device headers.  The lane reads its slice [lo, hi) of prims first.  A slice of at most
 //                          kListRegister words is the capped kernels' sorted register list, written once in the epilogue: ascending
 //                          already.  A longer slice is stored as the walk accepts, in walk order, and its surplus slots are filled
@@ -15,10 +17,13 @@
 // 256-lane workgroups over one-dimensional grids; the fill has overlap.hip's LDS lane stack (stack_entries * 64 words per wave).  No
 // atomics: the mismatch flag is a plain store of 1 by every lane that raises it.  Two calls give the same bits.  Built with
 // -ffp-contract=off like the units it shares the leaf tests with.
+#include <type_traits>
+
 #include "lists.h"
 #include "bvh_walk.h"
 #include "overlap_device.h"      // BoxQuery, AdmitBoth, the sorted register list
 #include "tritri_device.h"       // TriQuery
+#include "oriented_device.h"     // OBoxQuery
 
 namespace ptd {
 
@@ -142,11 +147,12 @@ struct FillWalk : AdmitBoth<Q> {
     }
 };
 
-// REG: kListRegister, or 0 for the measurement without the register list (every slice stored as the walk finds it).
+// REG: kListRegister, or 0 for the measurement without the register list (every slice stored as the walk finds it).  The body of the
+// fill kernels: k_fill_lists for boxes and triangles, k_fill_oriented for oriented boxes.
 template <int FMT, class Q, uint32_t REG>
-__global__ void __launch_bounds__(256)
-k_fill_lists(const DeviceScene sc, uint32_t stack_entries, float scene_term, const float4* __restrict__ recs, uint32_t n, const uint32_t* __restrict__ offsets,
-             uint32_t* prims, uint32_t capacity, uint32_t* __restrict__ found, uint32_t* __restrict__ flag)
+__device__ __forceinline__ void fill_lists(const DeviceScene& sc, uint32_t stack_entries, float scene_term, const float4* __restrict__ recs, uint32_t n,
+                                           const uint32_t* __restrict__ offsets, uint32_t* prims, uint32_t capacity, uint32_t* __restrict__ found,
+                                           uint32_t* __restrict__ flag)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;      // n <= 2^31 - 1: the grid's last lane is below 2^31 + 255
     const LaneStack st = lane_stack(stack_entries);
@@ -185,6 +191,23 @@ k_fill_lists(const DeviceScene sc, uint32_t stack_entries, float scene_term, con
 #pragma unroll 1
         for (uint32_t j = count; j < m; j++) out[j] = 0xFFFFFFFFu;
     }
+}
+
+template <int FMT, class Q, uint32_t REG>
+__global__ void __launch_bounds__(256)
+k_fill_lists(const DeviceScene sc, uint32_t stack_entries, float scene_term, const float4* __restrict__ recs, uint32_t n, const uint32_t* __restrict__ offsets,
+             uint32_t* prims, uint32_t capacity, uint32_t* __restrict__ found, uint32_t* __restrict__ flag)
+{
+    fill_lists<FMT, Q, REG>(sc, stack_entries, scene_term, recs, n, offsets, prims, capacity, found, flag);
+}
+
+// The same fill for the 64-byte records of pt_query_overlap_oriented_lists (oriented_device.h), under a name of its own.
+template <int FMT, uint32_t REG>
+__global__ void __launch_bounds__(256)
+k_fill_oriented(const DeviceScene sc, uint32_t stack_entries, float scene_term, const float4* __restrict__ recs, uint32_t n, const uint32_t* __restrict__ offsets,
+                uint32_t* prims, uint32_t capacity, uint32_t* __restrict__ found, uint32_t* __restrict__ flag)
+{
+    fill_lists<FMT, OBoxQuery, REG>(sc, stack_entries, scene_term, recs, n, offsets, prims, capacity, found, flag);
 }
 
 // ---- the sort ----------------------------------------------------------------------------------------------------------------------
@@ -271,8 +294,11 @@ static hipError_t launch_fill(const DeviceScene& sc, uint32_t stack_entries, flo
                               uint32_t* prims, uint32_t capacity, uint32_t* found, uint32_t* flag, uint32_t phases, hipStream_t stream)
 {
     if (phases & kListPhaseFill) {
-        const hipError_t e = launch_lane_stack(k_fill_lists<FMT, Q, REG>, stack_entries, n, stream, sc, stack_entries, scene_term, recs, n, offsets, prims, capacity,
-                                               found, flag);
+        hipError_t e;
+        if constexpr (std::is_same<Q, OBoxQuery>::value)
+            e = launch_lane_stack(k_fill_oriented<FMT, REG>, stack_entries, n, stream, sc, stack_entries, scene_term, recs, n, offsets, prims, capacity, found, flag);
+        else
+            e = launch_lane_stack(k_fill_lists<FMT, Q, REG>, stack_entries, n, stream, sc, stack_entries, scene_term, recs, n, offsets, prims, capacity, found, flag);
         if (e != hipSuccess) return e;
     }
     // a slice of one word is sorted as it is
@@ -294,6 +320,14 @@ hipError_t launch_overlap_lists(int fmt, const DeviceScene& sc, uint32_t stack_e
     if (n == 0u || n > 0x7FFFFFFFu || (!prims && capacity != 0u)) return hipErrorInvalidValue;
     if (fmt == 11) return launch_fill_phases<11, BoxQuery>(sc, stack_entries, scene_term, boxes, n, offsets, prims, capacity, found, flag, phases, stream);
     return launch_fill_phases<0, BoxQuery>(sc, stack_entries, scene_term, boxes, n, offsets, prims, capacity, found, flag, phases, stream);
+}
+
+hipError_t launch_oriented_lists(int fmt, const DeviceScene& sc, uint32_t stack_entries, float scene_term, const float4* boxes, uint32_t n, const uint32_t* offsets,
+                                 uint32_t* prims, uint32_t capacity, uint32_t* found, uint32_t* flag, uint32_t phases, hipStream_t stream)
+{
+    if (n == 0u || n > 0x7FFFFFFFu || (!prims && capacity != 0u)) return hipErrorInvalidValue;
+    if (fmt == 11) return launch_fill_phases<11, OBoxQuery>(sc, stack_entries, scene_term, boxes, n, offsets, prims, capacity, found, flag, phases, stream);
+    return launch_fill_phases<0, OBoxQuery>(sc, stack_entries, scene_term, boxes, n, offsets, prims, capacity, found, flag, phases, stream);
 }
 
 hipError_t launch_triangles_lists(int fmt, const DeviceScene& sc, uint32_t stack_entries, float scene_term, const float4* tris, uint32_t n, const uint32_t* offsets,

@@ -16,7 +16,7 @@
 //              [--tonemap linear|reinhard|aces] [--exposure auto|<EV>] [--out-hdr file.pfm]
 //              [--until-error E [--until-permille P] [--error-floor F] [--error-out file.pfm]]
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
-//              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k|,all] ...] [--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k|,all] ...]
+//              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k|,all] ...] [--overlap-oriented cx,cy,cz,hx,hy,hz,qw,qx,qy,qz[,k|,all] ...] [--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k|,all] ...]
 //              [--cast x0,y0,z0,x1,y1,z1,x2,y2,z2,dx,dy,dz[,tmax] ...] [--cast-mesh mesh.obj,dx,dy,dz[,tmax] ...]
 //              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...] [--clearance x0,y0,z0,x1,y1,z1[,radius] ...]
 //              [--tri-distance x0,y0,z0,x1,y1,z1,x2,y2,z2[,radius] ...]
@@ -63,6 +63,9 @@
 // k outside 0..8 is refused with exit status 2.  The frames are the same with or without it.  With "all" in place of k the line is the
 // same and "triangles" holds every overlapping triangle, ascending: pt_query_overlap counts, pt_list_offsets makes the offsets,
 // pt_query_overlap_lists fills the list.
+// --overlap-oriented cx,cy,cz,hx,hy,hz,qw,qx,qy,qz[,k] (repeatable): the same for the oriented box whose axes are the columns of the
+// rotation of the quaternion (qw, qx, qy, qz), normalised in double here, by pt_query_overlap_oriented and
+// pt_query_overlap_oriented_lists: {"overlap_oriented": [the ten numbers, the quaternion normalised], "count", "triangles", "materials"}.
 // --intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k] (repeatable): once the scene is set and before the first frame, the scene triangles that
 // intersect the triangle of these three vertices, by pt_query_triangles in one call per k, one JSON line each: {"intersect": [the nine
 // coordinates], "count": <scene triangles that intersect it>, "triangles": [<the k lowest indices among them, k = 0..8, default 8>]}.
@@ -779,33 +782,37 @@ static std::string completeLists(PathTracerState& state, const std::vector<float
     return err;
 }
 
-// --overlap: the boxes of one k in one call of pt_query_overlap; one JSON line per box, in the order given
-struct OverlapBox { float v[8]; uint32_t k; };
-static void overlapBoxes(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<OverlapBox>& boxes)
+// --overlap: the boxes of one k in one call of pt_query_overlap; one JSON line per box, in the order given.  --overlap-oriented: the
+// same through pt_query_overlap_oriented and pt_query_overlap_oriented_lists on records of 16 floats; the line names the ten numbers
+// of the argument, the quaternion as it was normalised.
+struct OverlapBox { float v[16]; uint32_t k; double arg[10]; };
+static void overlapBoxes(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<OverlapBox>& boxes, bool oriented = false)
 {
     const size_t n = boxes.size();
+    const size_t W = oriented ? 16 : 8, B = 4 * W;      // floats and bytes of a record
+    const char* what = oriented ? "overlap-oriented: " : "overlap: ";
     std::vector<uint32_t> counts(n, 0u), prims(n * 8, 0xFFFFFFFFu);
     for (uint32_t k = 0; k <= 8u; k++) {
         std::vector<size_t> which;
         std::vector<float> recs;
         for (size_t i = 0; i < n; i++)
-            if (boxes[i].k == k) { which.push_back(i); recs.insert(recs.end(), boxes[i].v, boxes[i].v + 8); }
+            if (boxes[i].k == k) { which.push_back(i); recs.insert(recs.end(), boxes[i].v, boxes[i].v + W); }
         const size_t m = which.size();
         if (m == 0) continue;
         void* d_boxes = nullptr; void* d_prims = nullptr; void* d_counts = nullptr;
         std::vector<uint32_t> c(m), p(m * (k ? k : 1u));
         std::string err;
-        if (pt_device_malloc(state.context, &d_boxes, m * 32) != 0 || pt_device_malloc(state.context, &d_counts, m * 4) != 0 ||
+        if (pt_device_malloc(state.context, &d_boxes, m * B) != 0 || pt_device_malloc(state.context, &d_counts, m * 4) != 0 ||
             (k != 0 && pt_device_malloc(state.context, &d_prims, m * k * 4) != 0) ||
-            pt_copy_to_device(state.context, d_boxes, recs.data(), m * 32) != 0 ||
-            pt_query_overlap(state.context, (const float*)d_boxes, m, k, (uint32_t*)d_prims, (uint32_t*)d_counts) != 0 ||
+            pt_copy_to_device(state.context, d_boxes, recs.data(), m * B) != 0 ||
+            (oriented ? pt_query_overlap_oriented : pt_query_overlap)(state.context, (const float*)d_boxes, m, k, (uint32_t*)d_prims, (uint32_t*)d_counts) != 0 ||
             pt_copy_to_host(state.context, c.data(), d_counts, m * 4) != 0 ||
             (k != 0 && pt_copy_to_host(state.context, p.data(), d_prims, m * k * 4) != 0))
             err = pt_last_error(state.context);
         if (d_boxes) pt_device_free(state.context, d_boxes);
         if (d_prims) pt_device_free(state.context, d_prims);
         if (d_counts) pt_device_free(state.context, d_counts);
-        if (!err.empty()) throw Exception("overlap: " + err);
+        if (!err.empty()) throw Exception(what + err);
         for (size_t j = 0; j < m; j++) {
             counts[which[j]] = c[j];
             for (uint32_t e = 0; e < k; e++) prims[which[j] * 8 + e] = p[j * k + e];
@@ -817,11 +824,12 @@ static void overlapBoxes(PathTracerState& state, const TinyObjWrapper& obj, cons
         std::vector<size_t> which;
         std::vector<float> recs;
         for (size_t i = 0; i < n; i++)
-            if (boxes[i].k == kListAll) { which.push_back(i); recs.insert(recs.end(), boxes[i].v, boxes[i].v + 8); }
+            if (boxes[i].k == kListAll) { which.push_back(i); recs.insert(recs.end(), boxes[i].v, boxes[i].v + W); }
         if (!which.empty()) {
             std::vector<uint32_t> offsets, all;
-            const std::string err = completeLists(state, recs, which.size(), 32, pt_query_overlap, pt_query_overlap_lists, offsets, all);
-            if (!err.empty()) throw Exception("overlap: " + err);
+            const std::string err = completeLists(state, recs, which.size(), B, oriented ? pt_query_overlap_oriented : pt_query_overlap,
+                                                  oriented ? pt_query_overlap_oriented_lists : pt_query_overlap_lists, offsets, all);
+            if (!err.empty()) throw Exception(what + err);
             for (size_t j = 0; j < which.size(); j++) {
                 whole[which[j]].assign(all.begin() + offsets[j], all.begin() + offsets[j + 1]);
                 counts[which[j]] = offsets[j + 1] - offsets[j];
@@ -832,7 +840,12 @@ static void overlapBoxes(PathTracerState& state, const TinyObjWrapper& obj, cons
     const std::vector<uint32_t> mats = obj.getMaterialIndices();
     for (size_t i = 0; i < n; i++) {
         const float* b = boxes[i].v;
-        printf("{\"overlap\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"count\": %u, \"triangles\": [", b[0], b[1], b[2], b[3], b[4], b[5], counts[i]);
+        if (oriented) {
+            const double* q = boxes[i].arg;
+            printf("{\"overlap_oriented\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.17g, %.17g, %.17g, %.17g], \"count\": %u, \"triangles\": [", q[0], q[1], q[2], q[3],
+                   q[4], q[5], q[6], q[7], q[8], q[9], counts[i]);
+        } else
+            printf("{\"overlap\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"count\": %u, \"triangles\": [", b[0], b[1], b[2], b[3], b[4], b[5], counts[i]);
         std::string mat_list;
         bool first = true;
         const bool all = boxes[i].k == kListAll;
@@ -1320,7 +1333,7 @@ int main(int argc, char** argv)
     std::vector<ClearanceSegment> clearances;
     std::vector<DistanceTriangle> triDistances;
     std::vector<CollideMesh> collides;
-    std::vector<OverlapBox> overlaps;
+    std::vector<OverlapBox> overlaps, oriented_overlaps;
     std::vector<IntersectTri> intersects;
     std::vector<SweepArg> sweeps;
     std::vector<CastArg> casts;
@@ -1492,7 +1505,7 @@ int main(int argc, char** argv)
             collides.push_back(cm);
         }
         else if (a == "--overlap") {
-            OverlapBox b = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, 8u};
+            OverlapBox b = {{0.0f}, 8u, {0.0}};
             int k = 8;
             std::string text = next();
             const bool all = wantsAll(text);
@@ -1503,6 +1516,35 @@ int main(int argc, char** argv)
             if (!ok) { std::cerr << "--overlap cx,cy,cz,hx,hy,hz[,k]: finite values, half extents >= 0, k = 0..8 or all" << std::endl; return 2; }
             b.k = (uint32_t)k;
             overlaps.push_back(b);
+        }
+        else if (a == "--overlap-oriented") {
+            OverlapBox b = {{0.0f}, 8u, {0.0}};
+            int k = 8;
+            std::string text = next();
+            const bool all = wantsAll(text);
+            double* q = b.arg;
+            const int got = sscanf(text.c_str(), "%lf,%lf,%lf,%lf,%lf,%lf,%lf,%lf,%lf,%lf,%d", &q[0], &q[1], &q[2], &q[3], &q[4], &q[5], &q[6], &q[7], &q[8], &q[9], &k);
+            bool ok = (all ? got == 10 : got >= 10) && k >= 0 && k <= 8;
+            if (all) k = (int)kListAll;
+            for (int j = 0; j < 10; j++) ok = ok && std::isfinite((float)q[j]) && (j < 3 || j >= 6 || (float)q[j] >= 0.0f);
+            const double len = std::sqrt(q[6] * q[6] + q[7] * q[7] + q[8] * q[8] + q[9] * q[9]);
+            ok = ok && std::isfinite(len) && len > 0.0;
+            if (!ok) {
+                std::cerr << "--overlap-oriented cx,cy,cz,hx,hy,hz,qw,qx,qy,qz[,k]: finite values, half extents >= 0, a quaternion that is not zero, k = 0..8 or all" << std::endl;
+                return 2;
+            }
+            // the quaternion is normalised in double; the rotation it stands for, local -> world, rounded to float once per entry
+            for (int j = 6; j < 10; j++) q[j] /= len;
+            const double w = q[6], x = q[7], y = q[8], z = q[9];
+            const double r[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w), 2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                                 2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
+            for (int row = 0; row < 3; row++) {
+                for (int col = 0; col < 3; col++) b.v[4 * row + col] = (float)r[3 * row + col];
+                b.v[4 * row + 3] = (float)q[row];
+                b.v[12 + row] = (float)q[3 + row];
+            }
+            b.k = (uint32_t)k;
+            oriented_overlaps.push_back(b);
         }
         else if (a == "--intersect") {
             IntersectTri t = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, 8u};
@@ -1684,6 +1726,7 @@ int main(int argc, char** argv)
         if (!triDistances.empty()) { std::cout.flush(); triangleDistances(state, obj, triDistances); }
         if (!collides.empty()) { std::cout.flush(); collideMeshes(state, collides); }
         if (!overlaps.empty()) { std::cout.flush(); overlapBoxes(state, obj, overlaps); }
+        if (!oriented_overlaps.empty()) { std::cout.flush(); overlapBoxes(state, obj, oriented_overlaps, true); }
         if (!intersects.empty()) { std::cout.flush(); intersectTriangles(state, intersects); }
         if (!sweeps.empty()) { std::cout.flush(); sweepSpheres(state, obj, sweeps); }
         if (!casts.empty()) { std::cout.flush(); castTriangles(state, obj, casts); }

@@ -1448,10 +1448,26 @@ def queryOverlapAny(state, centres, half_extents=None):
     return out.view(np.bool_)
 
 
-def occupancyBoxes(resolution, lo, hi):
+def _occupancy_frame(frame):
+    """(rotation float32 (3, 3), translation float64 (3,), the 3 x 3 part in float64) of a 3 x 4 or 4 x 4 frame, local -> world"""
+    try:
+        f = np.asarray(frame, np.float64)
+    except (TypeError, ValueError):
+        f = np.zeros(0)
+    if f.shape not in ((3, 4), (4, 4), (12,)) or not np.isfinite(f).all():
+        raise PathTracerError("bakeOccupancy: frame is a finite 3 x 4 matrix [rotation | origin], local -> world, got %r" % (frame,))
+    f = f.reshape(-1, 4)[:3]
+    return f[:, :3].astype(np.float32), f[:, 3].copy(), f[:, :3].astype(np.float32).astype(np.float64)
+
+
+def occupancyBoxes(resolution, lo, hi, frame=None):
     """The cells of an (nz, ny, nx) grid over the box [lo, hi] as (nz * ny * nx, 8) float32 box records, x fastest: the centres are
     distanceFieldPoints', the half extent is half a cell, (hi - lo) / (2 n) per axis computed in float64 and rounded UP to float32, so
-    that the cells' union covers the grid."""
+    that the cells' union covers the grid.
+
+    frame: a 3 x 4 matrix [rotation | origin], local -> world.  [lo, hi] and the grid are then in the frame's coordinates and the cells
+    come as (n, 16) oriented-box records (orientedBoxes): the same half extents, the frame's rotation, the centres taken to the world in
+    float64 and rounded to float32."""
     try:
         pts = distanceFieldPoints(resolution, lo, hi)
     except PathTracerError as e:
@@ -1461,20 +1477,29 @@ def occupancyBoxes(resolution, lo, hi):
     half64 = 0.5 * (hi - lo) / np.array([nx, ny, nz], np.float64)
     half = half64.astype(np.float32)
     half = np.where(half.astype(np.float64) < half64, np.nextafter(half, np.float32(np.inf)), half).astype(np.float32)
+    if frame is not None:
+        rot, origin, rot64 = _occupancy_frame(frame)
+        return orientedBoxes((pts.astype(np.float64) @ rot64.T + origin).astype(np.float32), half, rot)
     b = np.zeros((pts.shape[0], 8), np.float32)
     b[:, 0:3] = pts
     b[:, 3:6] = half
     return b
 
 
-def bakeOccupancy(state, resolution, bounds=None, counts=False):
+def bakeOccupancy(state, resolution, bounds=None, counts=False, frame=None):
     """Conservative voxelisation: which cells of an (nz, ny, nx) grid does the scene's surface touch.  The cells are occupancyBoxes' —
     centres from distanceFieldPoints, x fastest, so the 64 boxes of a wave are neighbours; half extent half a cell — and go through
     queryOverlapAny: a bool [nz, ny, nx] grid.  counts=True goes through queryOverlap with max_prims = 0 instead and returns how many
     triangles touch each cell, uint32 [nz, ny, nx].  bounds: (lo xyz, hi xyz) of the grid, the scene box if not given.  A cell is
     occupied iff a triangle overlaps it by include/acgpt.h's closed conditions, so a triangle in a face between two cells occupies
-    both."""
+    both.
+
+    frame: a 3 x 4 matrix [rotation | origin], local -> world — a vehicle's or a sensor's pose.  The grid then lies in that frame
+    (bounds, which must be given, are in its coordinates) and its cells are oriented boxes through queryOverlapOrientedAny /
+    queryOverlapOriented: an egocentric occupancy grid.  A frame that is not orthonormal to 2^-10 raises ValueError."""
     if bounds is None:
+        if frame is not None:
+            raise PathTracerError("bakeOccupancy: bounds must be given with a frame (they are in the frame's coordinates)")
         info = getBvhInfo(state)
         lo, hi = [float(x) for x in info.scene_lo], [float(x) for x in info.scene_hi]
     else:
@@ -1482,8 +1507,12 @@ def bakeOccupancy(state, resolution, bounds=None, counts=False):
             lo, hi = bounds
         except (TypeError, ValueError):
             raise PathTracerError("bakeOccupancy: bounds is (lo xyz, hi xyz), got %r" % (bounds,))
-    boxes = occupancyBoxes(resolution, lo, hi)
+    boxes =occupancyBoxes(resolution, lo, hi) if frame is None else occupancyBoxes(resolution, lo, hi, frame)
     shape = tuple(int(r) for r in resolution)
+    if frame is not None:
+        if counts:
+            return queryOverlapOriented(state, boxes, max_prims=0, counts=True)["count"].reshape(shape)
+        return queryOverlapOrientedAny(state, boxes).reshape(shape)
     if counts:
         return queryOverlap(state, boxes, max_prims=0, counts=True)["count"].reshape(shape)
     return queryOverlapAny(state, boxes).reshape(shape)
@@ -1685,6 +1714,248 @@ def queryTrianglesLists(state, triangles):
     else:
         recs = _triangle_records("queryTrianglesLists", triangles)
     return _query_lists("pt_query_triangles_lists", state, recs, L.pt_query_triangles, L.pt_query_triangles_lists)
+
+
+# ------------------------------------------------------------------ oriented-box overlap ----
+OBOX_ORTHO_TOL = np.float32(2.0 ** -10)      # kOBoxOrthoTol (csrc/oriented.h)
+
+
+def orientedBoxes(centres, half_extents, rotations):
+    """(n, 16) float32 oriented-box records {m[0..11] | hx, hy, hz, 0} (include/acgpt.h pt_query_overlap_oriented): centres (n, 3),
+    half_extents (n, 3), (3,) or a number, rotations (3, 3) or (n, 3, 3), applied local -> world: the box's axes are a rotation's
+    columns.  m is the row-major 3 x 4 matrix [rotation | centre], a pose of queryPosesAny."""
+    what = "orientedBoxes"
+    c, h, r = np.asarray(centres), np.asarray(half_extents), np.asarray(rotations)
+    for a, name in ((c, "centres"), (h, "half extents"), (r, "rotations")):
+        if a.dtype.kind not in "fiu":
+            raise PathTracerError("%s: the %s must be numbers, got %s" % (what, name, a.dtype))
+    if c.ndim != 2 or c.shape[1] != 3:
+        raise PathTracerError("%s: expected (n, 3) centres, got shape %s" % (what, c.shape))
+    n = c.shape[0]
+    try:
+        h = np.broadcast_to(h.astype(np.float32), (n, 3))
+    except ValueError:
+        raise PathTracerError("%s: half_extents of shape %s do not broadcast against %s centres" % (what, h.shape, c.shape))
+    if not (h >= 0.0).all():
+        raise PathTracerError("%s: every half extent must be non-negative" % what)
+    if r.shape not in ((3, 3), (n, 3, 3)):
+        raise PathTracerError("%s: expected (3, 3) or (n, 3, 3) rotations for %d centres, got shape %s" % (what, n, r.shape))
+    b = np.zeros((n, 16), np.float32)
+    m = b[:, :12].reshape(n, 3, 4)
+    m[:, :, :3] = r
+    m[:, :, 3] = c
+    b[:, 12:15] = h
+    return b
+
+
+def _oriented_searchable_axes(b):
+    """The orthonormality rule of include/acgpt.h on (n, 16) float32 records, in fp32 as the device evaluates it"""
+    m = b[:, :12].reshape(-1, 3, 4)
+    u, v, w = m[:, :, 0], m[:, :, 1], m[:, :, 2]
+    dot = lambda a, c: (a[:, 0] * c[:, 0] + a[:, 1] * c[:, 1]) + a[:, 2] * c[:, 2]
+    one, tol = np.float32(1.0), OBOX_ORTHO_TOL
+    with np.errstate(all="ignore"):
+        return (np.abs(dot(u, u) - one) <= tol) & (np.abs(dot(v, v) - one) <= tol) & (np.abs(dot(w, w) - one) <= tol) & \
+               (np.abs(dot(u, v)) <= tol) & (np.abs(dot(v, w)) <= tol) & (np.abs(dot(w, u)) <= tol)
+
+
+def _oriented_records(what, state, boxes):
+    """The records of an oriented query: a contiguous float32 (n, 16) tensor on the context's device as it is, or an (n, 16) float32
+    array of anything np.asarray takes.  NumPy records whose axes are finite and not orthonormal to 2^-10 raise ValueError (on the
+    device such a record is silently a miss, as a bad box is)."""
+    if _is_tensor(boxes):
+        import torch
+        if boxes.device.type != "cuda" or boxes.device.index != state._device:
+            raise PathTracerError("%s: the boxes are on %s, the context is on cuda:%d" % (what, boxes.device, state._device))
+        if boxes.dtype != torch.float32:
+            raise PathTracerError("%s: the boxes must be float32, got %s" % (what, boxes.dtype))
+        if boxes.dim() != 2 or boxes.shape[1] != 16:
+            raise PathTracerError("%s: expected an (n, 16) tensor {m[0..11], hx, hy, hz, 0}, got shape %s" % (what, tuple(boxes.shape)))
+        if not boxes.is_contiguous():
+            raise PathTracerError("%s: the boxes must be contiguous (nothing is copied)" % what)
+        return boxes
+    b = np.asarray(boxes)
+    if b.dtype.kind not in "fiu":
+        raise PathTracerError("%s: the boxes must be numbers, got %s" % (what, b.dtype))
+    if b.ndim != 2 or b.shape[1] != 16:
+        raise PathTracerError("%s: expected (n, 16) records {m[0..11], hx, hy, hz, 0} (orientedBoxes makes them), got shape %s" % (what, b.shape))
+    b = np.ascontiguousarray(b, np.float32)
+    axes = b[:, :12].reshape(-1, 3, 4)[:, :, :3].reshape(-1, 9)
+    bad = np.isfinite(axes).all(axis=1) & ~_oriented_searchable_axes(b)
+    if bad.any():
+        raise ValueError("%s: the axes of box %d are not orthonormal to 2^-10 (an oriented box is a rotation or a mirror, not a scale or a shear)"
+                         % (what, int(np.flatnonzero(bad)[0])))
+    return b
+
+
+def queryOverlapOriented(state, boxes, max_prims=8, counts=True):
+    """Which triangles of the scene on the GPU overlap each oriented box (include/acgpt.h pt_query_overlap_oriented): queryOverlap for
+    (n, 16) records {m[0..11] | hx, hy, hz, 0}, which orientedBoxes and poseBoxes make.  max_prims, counts and the result are
+    queryOverlap's: a dict of prim (n, max_prims), the lowest indices among the overlapping triangles, ascending, 0xFFFFFFFF past the
+    last one, and count (n,) when asked.
+
+    NumPy input goes through device buffers and comes back as uint32 arrays; axes that are not orthonormal to 2^-10 raise ValueError.  A
+    contiguous float32 (n, 16) tensor on the context's device goes in by data_ptr() without a copy and is answered with int32 tensors
+    (-1 past the last triangle); there a record that is not orthonormal is a miss."""
+    k = _overlap_args("queryOverlapOriented", max_prims, counts)
+    L = _native.hip()
+    recs = _oriented_records("queryOverlapOriented", state, boxes)
+    n = int(recs.shape[0])
+    if _is_tensor(recs):
+        import torch
+        with torch.cuda.device(recs.device):
+            out = torch.empty((n, k), dtype=torch.int32, device=recs.device)
+            cnt = torch.empty((n,), dtype=torch.int32, device=recs.device) if counts else None
+            torch.cuda.current_stream().synchronize()      # the boxes' producer and the allocations; the call below returns synchronised
+        _check(state.context, L.pt_query_overlap_oriented(state.context, recs.data_ptr() if n else None, n, k, out.data_ptr() if n and k else None,
+                                                          cnt.data_ptr() if n and counts else None), "pt_query_overlap_oriented")
+        got = {"prim": out}
+        if counts:
+            got["count"] = cnt
+        return got
+    out = np.full((n, k), 0xFFFFFFFF, np.uint32)
+    cnt = np.zeros(n, np.uint32)
+    if n:
+        bufs, d_prims, d_counts = _device_buffers(state, 1, recs.nbytes), None, None
+        try:
+            if k:
+                bufs += _device_buffers(state, 1, out.nbytes)
+                d_prims = bufs[-1]
+            if counts:
+                bufs += _device_buffers(state, 1, cnt.nbytes)
+                d_counts = bufs[-1]
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], recs.ctypes.data, recs.nbytes), "copy to device")
+            _check(state.context, L.pt_query_overlap_oriented(state.context, bufs[0], n, k, d_prims, d_counts), "pt_query_overlap_oriented")
+            if k:
+                _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, d_prims, out.nbytes), "copy to host")
+            if counts:
+                _check(state.context, L.pt_copy_to_host(state.context, cnt.ctypes.data, d_counts, cnt.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    got = {"prim": out}
+    if counts:
+        got["count"] = cnt
+    return got
+
+
+def queryOverlapOrientedAny(state, boxes):
+    """Does any triangle of the scene overlap each oriented box (include/acgpt.h pt_query_overlap_oriented_any): queryOverlapOriented's
+    records, a bool array (n,), or a bool tensor for a tensor.  A box's walk ends at the first triangle it accepts."""
+    L = _native.hip()
+    recs = _oriented_records("queryOverlapOrientedAny", state, boxes)
+    n = int(recs.shape[0])
+    if _is_tensor(recs):
+        import torch
+        with torch.cuda.device(recs.device):
+            out = torch.empty((n,), dtype=torch.uint8, device=recs.device)
+            torch.cuda.current_stream().synchronize()
+        _check(state.context, L.pt_query_overlap_oriented_any(state.context, recs.data_ptr() if n else None, n, out.data_ptr() if n else None),
+               "pt_query_overlap_oriented_any")
+        return out.view(torch.bool)
+    out = np.zeros(n, np.uint8)
+    if n:
+        bufs = _device_buffers(state, 1, recs.nbytes) + _device_buffers(state, 1, n)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], recs.ctypes.data, recs.nbytes), "copy to device")
+            _check(state.context, L.pt_query_overlap_oriented_any(state.context, bufs[0], n, bufs[1]), "pt_query_overlap_oriented_any")
+            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    return out.view(np.bool_)
+
+
+def queryOverlapOrientedLists(state, boxes):
+    """Every triangle of the scene on the GPU that overlaps each oriented box (include/acgpt.h pt_query_overlap_oriented_lists):
+    queryOverlapOriented's records, queryOverlapLists' result — a dict of offsets (n + 1,), prim (offsets[n],) and count (n,), box i's
+    triangles in prim[offsets[i]:offsets[i + 1]], ascending.  Arrays for arrays, tensors for a tensor, which is not copied."""
+    L = _native.hip()
+    recs = _oriented_records("queryOverlapOrientedLists", state, boxes)
+    return _query_lists("pt_query_overlap_oriented_lists", state, recs, L.pt_query_overlap_oriented, L.pt_query_overlap_oriented_lists)
+
+
+def _local_box(what, lo, hi):
+    """(cx, cy, cz, hx, hy, hz) float32 of the box [lo, hi]: the centre rounded to float32, the half extent the larger of hi - c and
+    c - lo per axis, rounded UP, so that the record's box covers [lo, hi]"""
+    try:
+        lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    except (TypeError, ValueError):
+        raise PathTracerError("%s: lo and hi are xyz, got %r and %r" % (what, lo, hi))
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all()):
+        raise PathTracerError("%s: lo and hi must be finite with lo <= hi, got %s and %s" % (what, lo, hi))
+    c = (0.5 * (lo + hi)).astype(np.float32)
+    h64 = np.maximum(hi - c.astype(np.float64), c.astype(np.float64) - lo)
+    h = h64.astype(np.float32)
+    h = np.where(h.astype(np.float64) < h64, np.nextafter(h, np.float32(np.inf)), h).astype(np.float32)
+    return np.concatenate([c, h]).astype(np.float32)
+
+
+def poseBoxes(state, poses, lo, hi):
+    """One oriented-box record per pose, made on the device (include/acgpt.h pt_pose_boxes): the box [lo, hi] of the mesh's own frame
+    under each pose.  Record p is pose p with its translation replaced by the posed centre of [lo, hi], then the half extent: what
+    queryOverlapOriented* take.  Poses: queryPosesAny's forms; an (P, 16) float32 array for arrays, a tensor on the device for a tensor,
+    which is not copied."""
+    L = _native.hip()
+    lb = _local_box("poseBoxes", lo, hi)
+    recs = _pose_records("poseBoxes", state, poses)
+    P = int(recs.shape[0])
+    p_lb = lb.ctypes.data_as(C.POINTER(C.c_float))
+    if _is_tensor(recs):
+        import torch
+        with torch.cuda.device(recs.device):
+            out = torch.empty((P, 16), dtype=torch.float32, device=recs.device)
+            torch.cuda.current_stream().synchronize()
+        _check(state.context, L.pt_pose_boxes(state.context, recs.data_ptr() if P else None, P, p_lb, out.data_ptr() if P else None), "pt_pose_boxes")
+        return out
+    out = np.zeros((P, 16), np.float32)
+    if P:
+        bufs = _device_buffers(state, 1, recs.nbytes) + _device_buffers(state, 1, out.nbytes)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], recs.ctypes.data, recs.nbytes), "copy to device")
+            _check(state.context, L.pt_pose_boxes(state.context, bufs[0], P, p_lb, bufs[1]), "pt_pose_boxes")
+            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    return out
+
+
+def posedMeshBoxPad(vertices, max_translation):
+    """The default pad of posedMeshBoxes, float64.  With lc the centre of the mesh's bounding box, rho the largest distance of a vertex
+    from it, T the largest |translation entry| of the poses and u = 2^-24: a posed vertex ((m0 x + m1 y) + m2 z) + m3 differs from the
+    exact one by at most 4.1 u |x| + u T per component, the posed centre likewise, their difference rounds by u rho, each of the
+    statement's local coordinates by 3.03 u rho more, and the component errors pass through the axes with a factor sqrt 3:
+    14.2 u |lc| + 11.9 u rho + 3.5 u T in all.  A rotation that was built in fp32 is orthonormal to 2^-22 or better; one that is off by
+    e moves a local coordinate by up to 1.74 e rho.  The pad is 2^-20 (|lc| + rho + T) + 2^-19 rho: the rounding with a third to spare,
+    and poses orthonormal to 2^-20."""
+    v = np.asarray(vertices, np.float64).reshape(-1, np.asarray(vertices).shape[-1])[:, :3]
+    lo, hi = v.min(axis=0), v.max(axis=0)
+    lc = 0.5 * (lo + hi)
+    rho = float(np.sqrt(((v - lc) ** 2).sum(axis=1).max()))
+    return 2.0 ** -20 * (float(np.sqrt((lc * lc).sum())) + rho + float(max_translation)) + 2.0 ** -19 * rho
+
+
+def posedMeshBoxes(state, vertices, poses, pad=None):
+    """The bounding box of a mesh under every pose as oriented-box records: poseBoxes of the mesh's own bounding box, grown by pad on
+    every side.  pad=None takes posedMeshBoxPad's, under which every posed vertex of posedTriangles lies inside its pose's box by the
+    fp32 statement of queryOverlapOriented, for poses orthonormal to 2^-20 — so a pose whose box is free of the scene
+    (queryOverlapOrientedAny) cannot collide (queryPosesAny).  vertices: (V, 3) or (V, 4); poses: queryPosesAny's forms."""
+    v = np.asarray(vertices)
+    if v.dtype.kind not in "fiu" or v.ndim != 2 or v.shape[1] not in (3, 4) or v.shape[0] == 0 or not np.isfinite(v[:, :3].astype(np.float64)).all():
+        raise PathTracerError("posedMeshBoxes: expected finite (V, 3) or (V, 4) vertices, V >= 1, got %s %s" % (v.dtype, v.shape))
+    recs = _pose_records("posedMeshBoxes", state, poses)
+    if pad is None:
+        if _is_tensor(recs):
+            t = float(recs[:, 3::4].abs().nan_to_num(nan=0.0, posinf=0.0, neginf=0.0).max()) if recs.shape[0] else 0.0
+        else:
+            t = float(np.nan_to_num(np.abs(recs[:, 3::4]), nan=0.0, posinf=0.0, neginf=0.0).max()) if recs.shape[0] else 0.0
+        pad = posedMeshBoxPad(v, t)
+    try:
+        pad = float(pad)
+    except (TypeError, ValueError):
+        raise PathTracerError("posedMeshBoxes: pad is a number >= 0 or None, got %r" % (pad,))
+    if not (pad >= 0.0 and np.isfinite(pad)):
+        raise PathTracerError("posedMeshBoxes: pad is a number >= 0 or None, got %r" % (pad,))
+    v64 = v[:, :3].astype(np.float32).astype(np.float64)      # the vertices as setQueryMesh stores them
+    return poseBoxes(state, recs, v64.min(axis=0) - pad, v64.max(axis=0) + pad)
 
 
 def _posed_records(what, vertices, indices, poses):

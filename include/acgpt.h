@@ -634,6 +634,44 @@ int pt_query_overlap_lists(pt_ctx* ctx, const float* boxes, size_t n, const uint
 int pt_query_triangles_lists(pt_ctx* ctx, const float* tris, size_t n, const uint32_t* offsets,
                              uint32_t* prims, size_t capacity, uint32_t* found);
 
+/* ---- oriented-box overlap queries on the device (opt-in; nothing above changes) ----------------------------------------------------
+ * pt_query_overlap for a box in a frame of its own: a robot link, a vehicle hull, a tool, a selection gizmo, the cells of a grid that
+ * is turned against the world.  The world AABB of such a box reports many times the triangles and calls free space occupied; its
+ * twelve surface triangles miss everything that lies inside it.  The three calls are pt_query_overlap, pt_query_overlap_any and
+ * pt_query_overlap_lists with another record and another statement; everything else is theirs, word for word: the memory rules (DEVICE
+ * arrays, boxes and prims 16-byte aligned, counts / offsets / found 4-byte, hit any alignment), the refusals, which leave the context
+ * usable, PT_QUERY_OVERLAP_MAX, the max_prims / counts combinations, the CSR contract with pt_list_offsets (ascending, surplus slots
+ * 0xFFFFFFFF, the mismatch flag, no write outside a slice whatever offsets holds), rank 0 of a pt_create_multi context, no atomics —
+ * two calls give the same bits —, device_bytes unchanged.
+ *
+ *   boxes     n records of 16 floats, 64 bytes: {m[0..11] | hx, hy, hz, 0}.  m is a row-major 3 x 4 matrix laid out exactly as a pose
+ *             of pt_query_poses_* (below); the box is the image of [-h, h] under m.  Its axes in world coordinates are the columns of
+ *             the 3 x 3 part, u = (m0, m4, m8), v = (m1, m5, m9), w = (m2, m6, m10), its centre is c = (m3, m7, m11).  The last
+ *             float is reserved and ignored.  A half extent of 0 (or -0) is allowed: rectangles, segments, points.
+ *   overlap   all fp32, every operation on its own, evaluated as written, no fused multiply-add (tests/oriented_ref.py is the NumPy
+ *             statement, equal bit for bit).  A world vector p has the local coordinates
+ *               L(p) = ((m0 p.x + m4 p.y) + m8 p.z,  (m1 p.x + m5 p.y) + m9 p.z,  (m2 p.x + m6 p.y) + m10 p.z)
+ *             and on the triangle's stored vectors v0, e1, e2:  P0 = L(v0 - c),  E1 = L(e1),  E2 = L(e2).  The triangle overlaps the box
+ *             iff the 13 conditions of pt_query_overlap hold for centre (0, 0, 0), half extent h and the vectors (P0, E1, E2) in the
+ *             place of (v0, e1, e2).  The edges are rotated, not formed again from rotated points: with the exact identity as the
+ *             3 x 3 part the statement reproduces pt_query_overlap's answers.
+ *   a miss before any traversal: a non-finite value among the first 15 floats; a negative or NaN half extent; a scene without
+ *             triangles; axes that are not orthonormal: with dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z the record is searchable only
+ *             if |dot(u,u) - 1|, |dot(v,v) - 1|, |dot(w,w) - 1|, |dot(u,v)|, |dot(v,w)| and |dot(w,u)| are all <= 2^-10.  Mirrors
+ *             pass; a rotation built in fp32 from a quaternion is within 2e-7.  The rule lets the walk bound the box in world space
+ *             without inverting a matrix; it is part of the statement.  A miss gives count 0, prims all 0xFFFFFFFF, hit 0.
+ *
+ * pt_pose_boxes turns poses that are on the device already into oriented-box records: record p is pose p with its fourth column
+ * replaced by the pose statement (below, "pose") applied to local_box[0..2], followed by {local_box[3..5], 0}.  local_box is a HOST
+ * pointer: centre and half extent of the box in the mesh's own frame.  poses and boxes_out are DEVICE, 16-byte aligned, P * 48 and
+ * P * 64 bytes, and must not overlap.  The call needs neither a scene nor a query mesh.  P == 0 is a no-op success.  Refused: a null
+ * context or argument, P > 0x7FFFFFFF, a negative or non-finite local_box, a misaligned array, boxes_out overlapping the poses.       */
+int pt_query_overlap_oriented(pt_ctx* ctx, const float* boxes, size_t n, uint32_t max_prims, uint32_t* prims, uint32_t* counts);
+int pt_query_overlap_oriented_any(pt_ctx* ctx, const float* boxes, size_t n, uint8_t* hit);
+int pt_query_overlap_oriented_lists(pt_ctx* ctx, const float* boxes, size_t n, const uint32_t* offsets,
+                                    uint32_t* prims, size_t capacity, uint32_t* found);
+int pt_pose_boxes(pt_ctx* ctx, const float* poses, size_t P, const float local_box[6], float* boxes_out);
+
 /* ---- swept-sphere casts on the device (opt-in; nothing above changes) --------------------------------------------------------------
  * How far a ball of radius r travels along a direction before it touches the mesh, and where it touches: the sphere cast of physics
  * and robotics libraries — continuous collision, character and camera controllers, path clearance of a round robot, thick rays and

@@ -145,6 +145,11 @@ int pt_debug_nearest_visits(pt_ctx* ctx, const float* points, size_t n, pt_neare
  * that also counts its work: visits[2 i] = inner nodes box i visited, visits[2 i + 1] = triangles it tested.  counts: DEVICE, n words;
  * visits: DEVICE, 8-byte aligned, 2 n words; neither may be null.  tools/overlap_timing.py. */
 int pt_debug_overlap_visits(pt_ctx* ctx, const float* boxes, size_t n, uint32_t* counts, uint32_t* visits);
+/* Its twin for pt_query_overlap_oriented's 64-byte records: the same counts, the same refusals.  tools/oriented_timing.py. */
+int pt_debug_overlap_oriented_visits(pt_ctx* ctx, const float* boxes, size_t n, uint32_t* counts, uint32_t* visits);
+/* The same counting walk with the nine axes cross(world axis, box axis) added to its admission: the other arm of the six-against-
+ * fifteen-axis measurement.  The same counts; no call of include/acgpt.h walks this way. */
+int pt_debug_overlap_oriented_visits_cross(pt_ctx* ctx, const float* boxes, size_t n, uint32_t* counts, uint32_t* visits);
 /* pt_query_sweep (same arguments, same records, same refusals) from a kernel instantiation that also counts: visits[2 i] = inner nodes
  * sweep i visited, visits[2 i + 1] = triangles it tested.  visits: DEVICE, 8-byte aligned, 2 n words.  tools/sweep_timing.py. */
 int pt_debug_sweep_visits(pt_ctx* ctx, const float* sweeps, size_t n, pt_sweep_hit* hits, uint32_t* visits);
