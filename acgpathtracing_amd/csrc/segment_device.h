@@ -1,6 +1,7 @@
 // segment_device.h — the device functions the segment query (segment.hip) and the triangle-distance query (tridist.hip) share: the
 // closest point of a triangle to a point (closest_point.h: pt_query_nearest's own, features 0 and 1), the clamp and the
-// segment-against-edge statement of include/acgpt.h's segment section.
+// segment-against-edge statement of include/acgpt.h's segment section; and the whole segment-to-triangle statement, which the
+// capsule cast (capsule.hip) shares with segment.hip: its start-overlap test and its record.
 // Evaluated as written (-ffp-contract=off); tests/segment_ref.py mirrors them operation for operation.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -46,6 +47,66 @@ __device__ __forceinline__ float segment_edge(const f3& p0, const f3& d, float a
     c = mk(A.x + E.x * t, A.y + E.y * t, A.z + E.z * t);
     const f3 w = ps - c;
     return dot(w, w);
+}
+
+struct SegPoint { float d2, s, feature; f3 c; };
+
+// Take candidate k if its d2 is smaller (ties stay with the lower feature); a NaN is no candidate.  The empty statement and the
+// barrier close one sub-test before the next starts: left to itself the compiler runs the five side by side and keeps their state
+// live together (tritri.hip's fold).
+template <bool FULL>
+__device__ __forceinline__ void seg_take(SegPoint& best, float d2, float s, float feature, const f3& c)
+{
+    const bool take = d2 < best.d2 || (best.d2 != best.d2 && d2 == d2);
+    best.d2 = take ? d2 : best.d2;
+    if (FULL) {
+        best.s = take ? s : best.s;
+        best.feature = take ? feature : best.feature;
+        best.c = mk(take ? c.x : best.c.x, take ? c.y : best.c.y, take ? c.z : best.c.z);
+    }
+    asm volatile("" : "+v"(best.d2));
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// The statement of include/acgpt.h: six sub-tests in the order of their feature numbers.  FULL = false is the walk's: d2 alone, the
+// same operations on the same inputs, so the same bits.
+template <bool FULL>
+__device__ __forceinline__ SegPoint segment_triangle(const f3& p0, const f3& p1, const f3& d, float a, const f3& v0, const f3& e1, const f3& e2)
+{
+    SegPoint best;
+    f3 c;
+    float s = 0.0f;
+    const ClosestPoint c0 = closest_on_triangle(p0, v0, e1, e2);
+    best.d2 = c0.d2; best.c = c0.c;
+    best.s = 0.0f; best.feature = 0.0f;
+    asm volatile("" : "+v"(best.d2));
+    __builtin_amdgcn_sched_barrier(0);
+    const ClosestPoint c1 = closest_on_triangle(p1, v0, e1, e2);
+    seg_take<FULL>(best, c1.d2, 1.0f, 1.0f, c1.c);
+    float d2 = segment_edge(p0, d, a, v0, e1, s, c);
+    seg_take<FULL>(best, d2, s, 2.0f, c);
+    d2 = segment_edge(p0, d, a, v0, e2, s, c);
+    seg_take<FULL>(best, d2, s, 3.0f, c);
+    d2 = segment_edge(p0, d, a, v0 + e1, e2 - e1, s, c);
+    seg_take<FULL>(best, d2, s, 4.0f, c);
+    // feature 5: a two-sided Moeller-Trumbore test of {p0, d} against the triangle in plain multiplies and adds (not tri_test, whose
+    // fused operations NumPy cannot mirror)
+    const f3 pv = cross(d, e2);
+    float det = dot(e1, pv);
+    const f3 tv = p0 - v0;
+    float U = dot(tv, pv);
+    const f3 qv = cross(tv, e1);
+    float V = dot(d, qv), T = dot(e2, qv);
+    if (det < 0.0f) { det = -det; U = -U; V = -V; T = -T; }
+    const bool crosses = det > 0.0f && U >= 0.0f && V >= 0.0f && U + V <= det && T >= 0.0f && T <= det;
+    best.d2 = crosses ? 0.0f : best.d2;
+    if (FULL) {
+        const float sx = T / det;
+        best.s = crosses ? sx : best.s;
+        best.feature = crosses ? 5.0f : best.feature;
+        best.c = mk(crosses ? p0.x + d.x * sx : best.c.x, crosses ? p0.y + d.y * sx : best.c.y, crosses ? p0.z + d.z * sx : best.c.z);
+    }
+    return best;
 }
 
 }  // namespace ptd

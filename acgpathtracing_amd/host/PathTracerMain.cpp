@@ -18,7 +18,7 @@
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
 //              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k|,all] ...] [--overlap-oriented cx,cy,cz,hx,hy,hz,qw,qx,qy,qz[,k|,all] ...] [--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k|,all] ...]
 //              [--cast x0,y0,z0,x1,y1,z1,x2,y2,z2,dx,dy,dz[,tmax] ...] [--cast-mesh mesh.obj,dx,dy,dz[,tmax] ...]
-//              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...] [--clearance x0,y0,z0,x1,y1,z1[,radius] ...]
+//              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...] [--capsule-cast x0,y0,z0,x1,y1,z1,dx,dy,dz,r[,tmax] ...] [--clearance x0,y0,z0,x1,y1,z1[,radius] ...]
 //              [--tri-distance x0,y0,z0,x1,y1,z1,x2,y2,z2[,radius] ...]
 //              [--collide mesh.obj[,tx,ty,tz[,radius]] ...]
 //              [--nearest-k x,y,z,k[,radius] ...] [--within x,y,z,radius ...] [--winding x,y,z[,beta] ...]
@@ -78,6 +78,12 @@
 // weights of its second and third vertex there), {"sweep": [...], "tmax": ..., "hit": false} if nothing is touched.  Floats are printed
 // with nine digits.  A value that is not finite (tmax may be inf), a negative radius or a negative tmax is refused with exit status 2.
 // The frames are the same with or without it.
+// --capsule-cast x0,y0,z0,x1,y1,z1,dx,dy,dz,r[,tmax] (repeatable): how far the capsule of radius r around the axis {p0, p1} travels along d
+// before it touches the scene (t in units of |d|, at most tmax, default unbounded), all in one call of pt_query_capsule_cast, one JSON
+// line each: {"capsule_cast": [the ten numbers], "tmax": <tmax or null>, "hit": true, "t": ..., "triangle": <index>, "material":
+// "<newmtl name>", "point": [x, y, z], "s": ..., "feature": <0..5>} (the contact point on the triangle, the parameter of the axis' point
+// that touches and pt_query_segments' feature there), {"capsule_cast": [...], "tmax": ..., "hit": false} if nothing is touched.  The same
+// refusals as --sweep.  The frames are the same with or without it.
 // --cast x0,y0,z0,x1,y1,z1,x2,y2,z2,dx,dy,dz[,tmax] (repeatable): how far the triangle of these three vertices translates along d before it
 // first touches the scene (t in units of |d|, at most tmax, default unbounded), all in one call of pt_query_triangle_cast, one JSON line
 // each: {"cast": [the twelve numbers], "tmax": <tmax or null>, "hit": true, "t": ..., "triangle": <index>, "feature": <0..15>,
@@ -957,6 +963,37 @@ static void sweepSpheres(PathTracerState& state, const TinyObjWrapper& obj, cons
     fflush(stdout);
 }
 
+// --capsule-cast: every capsule in one call of pt_query_capsule_cast; one JSON line per cast
+struct CapsuleCastArg { float v[12]; };
+static void castCapsules(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<CapsuleCastArg>& casts)
+{
+    const size_t n = casts.size();
+    void* d_casts = nullptr; void* d_out = nullptr;
+    std::vector<pt_capsule_cast_hit> out(n);
+    std::string err;
+    if (pt_device_malloc(state.context, &d_casts, n * 48) != 0 || pt_device_malloc(state.context, &d_out, n * sizeof(pt_capsule_cast_hit)) != 0 ||
+        pt_copy_to_device(state.context, d_casts, casts.data(), n * 48) != 0 ||
+        pt_query_capsule_cast(state.context, (const float*)d_casts, n, (pt_capsule_cast_hit*)d_out) != 0 ||
+        pt_copy_to_host(state.context, out.data(), d_out, n * sizeof(pt_capsule_cast_hit)) != 0)
+        err = pt_last_error(state.context);
+    if (d_casts) pt_device_free(state.context, d_casts);
+    if (d_out) pt_device_free(state.context, d_out);
+    if (!err.empty()) throw Exception("capsule-cast: " + err);
+    const std::vector<std::string>& names = obj.getMaterialNames();
+    for (size_t i = 0; i < n; i++) {
+        const pt_capsule_cast_hit& r = out[i];
+        const float* q = casts[i].v;
+        printf("{\"capsule_cast\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g, %.9g], \"tmax\": ", q[0], q[1], q[2], q[4], q[5], q[6], q[8], q[9], q[10], q[3]);
+        if (std::isfinite(q[7])) printf("%.9g", q[7]); else printf("null");
+        if (r.prim == 0xFFFFFFFFu) { printf(", \"hit\": false}\n"); continue; }
+        std::string name = r.material < names.size() ? names[r.material] : std::string();
+        for (size_t k = 0; k < name.size(); k++) if (name[k] == '"' || name[k] == '\\' || (unsigned char)name[k] < 0x20) name[k] = '_';
+        printf(", \"hit\": true, \"t\": %.9g, \"triangle\": %u, \"material\": \"%s\", \"point\": [%.9g, %.9g, %.9g], \"s\": %.9g, \"feature\": %d}\n",
+               r.t, r.prim, name.c_str(), r.cx, r.cy, r.cz, r.s, (int)r.feature);
+    }
+    fflush(stdout);
+}
+
 // --cast: every translating triangle in one call of pt_query_triangle_cast; one JSON line per cast
 struct CastArg { float v[16]; };
 static void printCastHit(const pt_triangle_cast_hit& r, const std::vector<std::string>& names, bool posed)
@@ -1336,6 +1373,7 @@ int main(int argc, char** argv)
     std::vector<OverlapBox> overlaps, oriented_overlaps;
     std::vector<IntersectTri> intersects;
     std::vector<SweepArg> sweeps;
+    std::vector<CapsuleCastArg> capsuleCasts;
     std::vector<CastArg> casts;
     std::vector<CastMesh> castMeshList;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
@@ -1568,6 +1606,15 @@ int main(int argc, char** argv)
             if (!ok) { std::cerr << "--sweep ox,oy,oz,dx,dy,dz,r[,tmax]: finite values, a radius >= 0, a tmax >= 0" << std::endl; return 2; }
             sweeps.push_back(w);
         }
+        else if (a == "--capsule-cast") {
+            CapsuleCastArg w = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, INFINITY, 0.0f, 0.0f, 0.0f, 0.0f}};
+            float* v = w.v;
+            const int got = sscanf(next(), "%f,%f,%f,%f,%f,%f,%f,%f,%f,%f,%f", &v[0], &v[1], &v[2], &v[4], &v[5], &v[6], &v[8], &v[9], &v[10], &v[3], &v[7]);
+            bool ok = got >= 10 && v[3] >= 0.0f && v[7] >= 0.0f;
+            for (int j = 0; j < 11; j++) ok = ok && (j == 7 || std::isfinite(v[j]));
+            if (!ok) { std::cerr << "--capsule-cast x0,y0,z0,x1,y1,z1,dx,dy,dz,r[,tmax]: finite values, a radius >= 0, a tmax >= 0" << std::endl; return 2; }
+            capsuleCasts.push_back(w);
+        }
         else if (a == "--cast") {
             CastArg w = {{0.0f, 0.0f, 0.0f, INFINITY, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};
             float* v = w.v;
@@ -1729,6 +1776,7 @@ int main(int argc, char** argv)
         if (!oriented_overlaps.empty()) { std::cout.flush(); overlapBoxes(state, obj, oriented_overlaps, true); }
         if (!intersects.empty()) { std::cout.flush(); intersectTriangles(state, intersects); }
         if (!sweeps.empty()) { std::cout.flush(); sweepSpheres(state, obj, sweeps); }
+        if (!capsuleCasts.empty()) { std::cout.flush(); castCapsules(state, obj, capsuleCasts); }
         if (!casts.empty()) { std::cout.flush(); castTriangles(state, obj, casts); }
         if (!castMeshList.empty()) { std::cout.flush(); castMeshes(state, obj, castMeshList); }
         if (ao_samples > 0) ambientOcclusion(state, ao_samples, ao_radius, ao_bias, ao_frames, ao_out);

@@ -2430,6 +2430,140 @@ def sweepContacts(result, sweeps):
     return np.where(hit[:, None], centre, nan).astype(np.float32), np.where(hit[:, None], normal, nan).astype(np.float32), t == 0
 
 
+# ------------------------------------------------------------------ swept capsules ----
+CAPSULE_CAST_DTYPE = np.dtype([("t", np.float32), ("prim", np.uint32), ("s", np.float32), ("feature", np.float32), ("point", np.float32, 3),
+                               ("material", np.uint32)])      # pt_capsule_cast_hit
+assert CAPSULE_CAST_DTYPE.itemsize == 32
+
+
+def _capsule_records(casts_or_p0, p1, directions, radius, tmax):
+    """The (n, 12) float32 records {p0, radius | p1, tmax | d, ignored} of a NumPy call, every refusal before any device work."""
+    p = np.asarray(casts_or_p0)
+    if p.dtype.kind not in "fiu":
+        raise PathTracerError("queryCapsuleCast: the casts must be numbers, got %s" % p.dtype)
+    if p1 is None and directions is None:
+        if p.ndim != 2 or p.shape[1] != 12:
+            raise PathTracerError("queryCapsuleCast: expected an (n, 12) array {p0, radius, p1, tmax, d, ignored}, or (n, 3) p0 with p1 and directions, got shape %s" % (p.shape,))
+        if radius is not None:
+            raise PathTracerError("queryCapsuleCast: the radius is in the fourth column of (n, 12) casts; radius= goes with p0, p1 and directions")
+        return np.ascontiguousarray(p, np.float32)
+    if p1 is None or directions is None:
+        raise PathTracerError("queryCapsuleCast: p0 goes with both p1 and directions")
+    q, d = np.asarray(p1), np.asarray(directions)
+    if p.ndim != 2 or p.shape[1] != 3 or q.shape != p.shape or d.shape != p.shape or q.dtype.kind not in "fiu" or d.dtype.kind not in "fiu":
+        raise PathTracerError("queryCapsuleCast: expected (n, 3) p0 and as many p1 and directions, got shapes %s, %s and %s" % (p.shape, q.shape, d.shape))
+    if radius is None:
+        raise PathTracerError("queryCapsuleCast: p0, p1 and directions need a radius")
+    s = np.zeros((p.shape[0], 12), np.float32)
+    s[:, 0:3], s[:, 4:7], s[:, 8:11] = p, q, d
+    for k, val, what in ((3, radius, "radius"), (7, tmax, "tmax")):
+        a = np.asarray(val, np.float64)
+        if a.ndim not in (0, 1) or (a.ndim == 1 and a.shape[0] != p.shape[0]):
+            raise PathTracerError("queryCapsuleCast: %s is one number or one per capsule, got shape %s" % (what, a.shape))
+        if not (a >= 0.0).all() or (k == 3 and np.isinf(a).any()):
+            raise PathTracerError("queryCapsuleCast: %s must be non-negative%s, got %r" % (what, " and finite" if k == 3 else "", val))
+        s[:, k] = a
+    return s
+
+
+def _capsule_tensor(state, casts, p1, directions, radius):
+    import torch
+    if p1 is not None or directions is not None or radius is not None:
+        raise PathTracerError("queryCapsuleCast: a tensor holds whole records (n, 12) {p0, radius, p1, tmax, d, ignored}; p1, directions and radius go with arrays")
+    if casts.device.type != "cuda" or casts.device.index != state._device:
+        raise PathTracerError("queryCapsuleCast: the casts are on %s, the context is on cuda:%d" % (casts.device, state._device))
+    if casts.dtype != torch.float32:
+        raise PathTracerError("queryCapsuleCast: the casts must be float32, got %s" % casts.dtype)
+    if casts.dim() != 2 or casts.shape[1] != 12:
+        raise PathTracerError("queryCapsuleCast: expected an (n, 12) tensor {p0, radius, p1, tmax, d, ignored}, got shape %s" % (tuple(casts.shape),))
+    if not casts.is_contiguous():
+        raise PathTracerError("queryCapsuleCast: the casts must be contiguous (nothing is copied)")
+    return torch
+
+
+def queryCapsuleCast(state, casts_or_p0, p1=None, directions=None, radius=None, tmax=float("inf"), any_hit=False):
+    """How far a capsule travels before it touches the scene on the GPU, and where (include/acgpt.h pt_query_capsule_cast): the axis is
+    {p0 + t d, p1 + t d} for 0 <= t <= tmax, t in units of |d|.
+
+    NumPy (or anything np.asarray takes): (n, 12) records {p0, radius | p1, tmax | d, ignored}, or (n, 3) p0 with (n, 3) p1, (n, 3)
+    directions, a radius (one number or one per capsule) and tmax.  The answer is a dict of arrays t (n,) float32 (-1 on a miss), prim
+    (n,) uint32 (0xFFFFFFFF), s the parameter on the axis and feature the kind of pt_query_segments' closest pair at impact, point (n, 3)
+    the contact point on the triangle, material (n,) uint32.  capsuleContacts turns it into axis ends, axis points and normals.
+    any_hit=True asks pt_query_capsule_cast_any instead and returns a bool array (n,): blocked or not.
+
+    A torch tensor must be (n, 12) float32, contiguous and on the context's device; nothing is copied, its data_ptr() goes straight in,
+    and the answer is torch tensors on that device: views of one (n, 8) float32 tensor, prim and material as int32 (-1 on a miss), or a
+    bool tensor with any_hit.  torch's current stream is synchronised before the call, and the call returns synchronised."""
+    if _is_tensor(casts_or_p0):
+        x = casts_or_p0
+        torch = _capsule_tensor(state, x, p1, directions, radius)
+        L = _native.hip()
+        n = int(x.shape[0])
+        with torch.cuda.device(x.device):
+            out = torch.empty((n,), dtype=torch.uint8, device=x.device) if any_hit else torch.empty((n, 8), dtype=torch.float32, device=x.device)
+            torch.cuda.current_stream().synchronize()      # the casts' producer and the allocation; the call below returns synchronised
+        if any_hit:
+            _check(state.context, L.pt_query_capsule_cast_any(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_capsule_cast_any")
+            return out.view(torch.bool)
+        _check(state.context, L.pt_query_capsule_cast(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_capsule_cast")
+        return {"t": out[:, 0], "prim": out[:, 1].view(torch.int32), "s": out[:, 2], "feature": out[:, 3], "point": out[:, 4:7], "material": out[:, 7].view(torch.int32)}
+    s = _capsule_records(casts_or_p0, p1, directions, radius, tmax)
+    L = _native.hip()
+    n = s.shape[0]
+    out = np.zeros(n, np.uint8) if any_hit else np.zeros(n, CAPSULE_CAST_DTYPE)
+    if n:
+        bufs = _device_buffers(state, 2, s.nbytes)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], s.ctypes.data, s.nbytes), "copy to device")
+            if any_hit:
+                _check(state.context, L.pt_query_capsule_cast_any(state.context, bufs[0], n, bufs[1]), "pt_query_capsule_cast_any")
+            else:
+                _check(state.context, L.pt_query_capsule_cast(state.context, bufs[0], n, bufs[1]), "pt_query_capsule_cast")
+            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    if any_hit:
+        return out.view(np.bool_)
+    return {k: np.ascontiguousarray(out[k]) for k in CAPSULE_CAST_DTYPE.names}
+
+
+def capsuleContacts(result, casts):
+    """What a controller needs of queryCapsuleCast's answer: (p0, p1, axis_point, normal, start_overlap) — the axis' ends at impact
+    p0 + d * t and p1 + d * t (n, 3), the point of the axis that touches, p0' + (p1' - p0') * s (n, 3), the unit contact normal
+    (axis point - point) / |axis point - point| (n, 3), from the surface towards the axis, and where the capsule touched the scene before
+    it moved, t == 0 (n,) bool.  A miss has NaN ends, axis points and normals; an axis point on the surface itself (radius 0, or a start
+    overlap with the axis through a triangle) has a zero normal.  casts: the (n, 12) records the result answers; arrays with arrays,
+    tensors with tensors."""
+    if _is_tensor(casts):
+        import torch
+        if casts.dim() != 2 or casts.shape[1] != 12 or result["t"].shape[0] != casts.shape[0]:
+            raise PathTracerError("capsuleContacts: expected the (n, 12) casts of the result, got shape %s" % (tuple(casts.shape),))
+        t = result["t"]
+        hit = t >= 0
+        move = casts[:, 8:11] * t[:, None]
+        q0, q1 = casts[:, 0:3] + move, casts[:, 4:7] + move
+        on_axis = q0 + (q1 - q0) * result["s"][:, None]
+        diff = on_axis - result["point"]
+        length = torch.sqrt((diff * diff).sum(dim=1, keepdim=True))
+        normal = torch.where(length > 0, diff / torch.where(length > 0, length, torch.ones_like(length)), torch.zeros_like(diff))
+        nan = torch.full_like(q0, float("nan"))
+        return tuple(torch.where(hit[:, None], x, nan) for x in (q0, q1, on_axis, normal)) + (t == 0,)
+    c = np.asarray(casts, np.float32)
+    t = np.asarray(result["t"], np.float32)
+    if c.ndim != 2 or c.shape[1] != 12 or t.shape != (c.shape[0],):
+        raise PathTracerError("capsuleContacts: expected the (n, 12) casts of the result, got shape %s" % (c.shape,))
+    hit = t >= 0
+    with np.errstate(all="ignore"):
+        move = c[:, 8:11] * t[:, None]
+        q0, q1 = c[:, 0:3] + move, c[:, 4:7] + move
+        on_axis = q0 + (q1 - q0) * np.asarray(result["s"], np.float32)[:, None]
+        diff = on_axis - np.asarray(result["point"], np.float32)
+        length = np.sqrt((diff * diff).sum(axis=1, keepdims=True))
+        normal = np.where(length > 0, diff / np.where(length > 0, length, np.float32(1.0)), np.float32(0.0))
+    nan = np.float32(np.nan)
+    return tuple(np.where(hit[:, None], x, nan).astype(np.float32) for x in (q0, q1, on_axis, normal)) + (t == 0,)
+
+
 # ------------------------------------------------------------------ translating-triangle casts ----
 TRIANGLE_CAST_DTYPE = np.dtype([("t", np.float32), ("prim", np.uint32), ("feature", np.float32), ("query_triangle", np.uint32), ("point", np.float32, 3),
                                 ("material", np.uint32)])      # pt_triangle_cast_hit

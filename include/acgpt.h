@@ -724,6 +724,50 @@ typedef struct { float t; uint32_t prim; float u, v; float cx, cy, cz; uint32_t 
 int pt_query_sweep(pt_ctx* ctx, const float* sweeps, size_t n, pt_sweep_hit* hits);
 int pt_query_sweep_any(pt_ctx* ctx, const float* sweeps, size_t n, uint8_t* blocked);
 
+/* ---- swept-capsule casts on the device (opt-in; nothing above changes) -------------------------------------------------------------
+ * How far a capsule — a segment with a radius: a character, a camera boom, a robot link — travels along a direction before it touches
+ * the mesh, and where: the capsule cast that physics libraries offer beside the sphere cast.  Sampling spheres along the axis and
+ * casting each misses every contact between the samples, a vertex or an edge of the mesh that meets the cylinder's side.
+ * pt_query_sweep's memory and call rules: DEVICE arrays, 16-byte aligned (blocked: any alignment); the call enqueues on the context's
+ * stream and returns synchronised, acts on rank 0 of a pt_create_multi context, never writes the accumulation buffer, the frame buffer
+ * or pt_stats, walks the node array the scene holds and uses no atomics: two calls give the same bits.
+ *
+ *   casts     n records of 12 floats {p0.x, p0.y, p0.z, radius | p1.x, p1.y, p1.z, tmax | d.x, d.y, d.z, ignored}; the first eight have
+ *             the layout of a pt_query_segments record.  The twelfth float is never read into a decision.  The capsule's axis is
+ *             {p0 + t d, p1 + t d} for 0 <= t <= tmax, closed at both ends.  d is not normalised and t is in units of its length.
+ *             radius = 0 (a swept segment), tmax = +inf and p1 == p0 (a sphere) are allowed.
+ *   time of impact of one triangle: the entry of the line p0 + t d into the r-offset of the prism K = triangle + (-[0, a]),
+ *             a = p1 - p0 (one subtraction per component).  K has 6 vertices, 9 edges and 5 faces, and outside K the distance to K is
+ *             the distance to its faces, so the time is the smallest candidate of the twenty-two sub-tests below.  All fp32, every
+ *             operation on its own, evaluated as written, no fused multiply-add, IEEE division and square root (tests/capsule_ref.py
+ *             is the NumPy statement, equal bit for bit), on the stored v0, e1, e2; dd = dot(d, d), rr = r * r; "vertex", "edge" and
+ *             "face" are pt_query_sweep's three feature forms above with the m and E given here:
+ *               at p0           pt_query_sweep's seven features other than the start overlap, with o = p0
+ *               at p1           the same seven with o = p1, p1 as the record gives it (not p0 + a)
+ *               axis edge       P in (v0, v0 + e1, v0 + e2): the edge form with m = p1 - P, E = a
+ *               side face       (A, E) in ((v0, e1), (v0, e2), (v0 + e1, e2 - e1)): the face form with m = p1 - A, E in the place of e1
+ *                               and a in the place of e2; candidate iff t >= 0, 0 <= u <= 1 and 0 <= v <= 1
+ *               start overlap   d2 of pt_query_segments' statement for the segment {p0, p1} (its d = a, its a = dot(a, a)) against the
+ *                               triangle; d2 <= rr: t = 0, whatever the candidates say
+ *             Every compare is false on a NaN, so a degenerate feature — a = 0, E parallel to a, d parallel to a, d = 0 — simply is
+ *             no candidate.  What two sub-tests share depends on E and d alone and may be computed once: the bits do not change.
+ *   the answer over all triangles, the smallest finite time of impact t <= tmax; ties go to the lowest index in the caller's
+ *             index-buffer order.  The walk's boxes only prune; the winner is decided by the test above alone.
+ *   hits      per cast {t, prim, s, feature, cx, cy, cz, material}: the time of impact, the winning triangle, then pt_query_segments'
+ *             (s, feature, c) for the segment {p0 + d * t, p1 + d * t} (one multiply and one add per component) against the winner,
+ *             evaluated once after the walk: the parameter on the axis and the point of the triangle where the two come closest, and
+ *             the triangle's material id.  The point on the axis is p0' + (p1' - p0') * s and the contact normal the caller's
+ *             (axis point - c) / r.  A miss is pt_segment_hit's: {-1, 0xFFFFFFFF, 0, 0, 0, 0, 0, 0xFFFFFFFF}.
+ *   blocked   pt_query_capsule_cast_any: one byte per cast, 1 iff some triangle has a time of impact t <= tmax (iff hits[i].t >= 0).  A
+ *             cast's walk ends at its first such triangle.
+ *   a miss before any traversal: a non-finite component of p0, p1, a or d, a radius that is NaN, negative or infinite, a NaN or
+ *             negative tmax, a scene without triangles.
+ * Not watertight at shared edges, as pt_query_sweep is not.  n == 0 is a no-op success.  Refused, with the context left usable:
+ * n > 0x7FFFFFFF, a null pointer, a misaligned casts or hits array, an output that overlaps the casts, a context without a scene.   */
+typedef struct { float t; uint32_t prim; float s, feature; float cx, cy, cz; uint32_t material; } pt_capsule_cast_hit;   /* 32 bytes */
+int pt_query_capsule_cast(pt_ctx* ctx, const float* casts, size_t n, pt_capsule_cast_hit* hits);
+int pt_query_capsule_cast_any(pt_ctx* ctx, const float* casts, size_t n, uint8_t* blocked);
+
 /* ---- segment-to-mesh distance on the device (opt-in; nothing above changes) --------------------------------------------------------
  * How far a line segment is from the surface and where the two come closest: the clearance query of motion planning.  A capsule (robot
  * link, cable, tool shaft, limb) clears the mesh by this distance minus its radius, and the closest pair is the direction to push away
