@@ -6,6 +6,8 @@ importing this module's `hip()` raises — there is no fallback.
 import ctypes as C
 import os
 
+import numpy as np
+
 PKG = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -177,13 +179,17 @@ ABI_SYMBOLS = [
     "pt_create", "pt_create_multi", "pt_device_count", "pt_destroy", "pt_last_error", "pt_set_scene", "pt_set_build_mode", "pt_scene_handle", "pt_get_bvh_info",
     "pt_launch", "pt_launch_frames", "pt_resolve_framebuffer", "pt_set_partition", "pt_set_sample_chunks", "pt_set_light_mode", "pt_set_math_mode", "pt_set_scratch_limit", "pt_set_tuning",
     "pt_variant_name", "pt_variant_kernel", "pt_kernel_source_hash", "pt_set_stream", "pt_get_stats",
-    "pt_trace_closest", "pt_trace_any", "pt_query_closest", "pt_query_any", "pt_query_multi", "pt_query_nearest", "pt_query_overlap", "pt_query_overlap_any", "pt_query_sweep", "pt_query_sweep_any", "pt_query_capsule_cast", "pt_query_capsule_cast_any", "pt_query_triangles", "pt_query_triangles_any", "pt_list_offsets", "pt_query_overlap_lists", "pt_query_triangles_lists", "pt_query_overlap_oriented", "pt_query_overlap_oriented_any", "pt_query_overlap_oriented_lists", "pt_pose_boxes", "pt_query_segments", "pt_query_triangle_distance", "pt_set_query_mesh", "pt_get_query_mesh", "pt_pose_triangles", "pt_query_poses_any", "pt_query_poses_distance", "pt_query_triangle_cast", "pt_query_triangle_cast_any", "pt_query_poses_cast", "pt_query_nearest_k", "pt_query_within_any", "pt_query_winding", "pt_get_winding_info", "pt_ao_points", "pt_ao_image", "pt_render_features", "pt_denoise", "pt_temporal_blend", "pt_temporal_blend_motion", "pt_update_vertices", "pt_update_materials", "pt_set_environment",
+    "pt_trace_closest", "pt_trace_any", "pt_query_closest", "pt_query_any", "pt_query_multi", "pt_query_nearest", "pt_query_overlap", "pt_query_overlap_any", "pt_query_sweep", "pt_query_sweep_any", "pt_query_capsule_cast", "pt_query_capsule_cast_any", "pt_query_box_cast", "pt_query_box_cast_any", "pt_query_triangles", "pt_query_triangles_any", "pt_list_offsets", "pt_query_overlap_lists", "pt_query_triangles_lists", "pt_query_overlap_oriented", "pt_query_overlap_oriented_any", "pt_query_overlap_oriented_lists", "pt_pose_boxes", "pt_query_segments", "pt_query_triangle_distance", "pt_set_query_mesh", "pt_get_query_mesh", "pt_pose_triangles", "pt_query_poses_any", "pt_query_poses_distance", "pt_query_triangle_cast", "pt_query_triangle_cast_any", "pt_query_poses_cast", "pt_query_nearest_k", "pt_query_within_any", "pt_query_winding", "pt_get_winding_info", "pt_ao_points", "pt_ao_image", "pt_render_features", "pt_denoise", "pt_temporal_blend", "pt_temporal_blend_motion", "pt_update_vertices", "pt_update_materials", "pt_set_environment",
     "pt_set_material_model", "pt_display_transform", "pt_convergence_update", "pt_firefly_filter", "pt_bloom",
     "pt_device_malloc", "pt_device_free", "pt_device_memset", "pt_copy_to_host", "pt_copy_to_device",
     "pt_host_malloc_mapped", "pt_host_free_mapped", "pt_abi_version",
 ]
+# pt_box_cast_hit: {t, prim, feature, material | n.xyz, pad | c.xyz, pad}
+BOX_CAST_DTYPE = np.dtype({"names": ["t", "prim", "feature", "material", "normal", "point"],
+                           "formats": [np.float32, np.uint32, np.float32, np.uint32, (np.float32, 3), (np.float32, 3)],
+                           "offsets": [0, 4, 8, 12, 16, 32], "itemsize": 48})
 # ... and include/acgpt_test.h (test hooks and diagnostics; same library)
-TEST_SYMBOLS = ["pt_bench_traversal", "pt_selftest", "pt_debug_wave_times", "pt_debug_queue_progress", "pt_debug_window_moves", "pt_debug_queue_order", "pt_debug_pixel_classes", "pt_debug_row_spans", "pt_read_morton", "pt_debug_environment", "pt_debug_environment_tables", "pt_debug_microfacet", "pt_debug_nearest_visits", "pt_debug_overlap_visits", "pt_debug_overlap_oriented_visits", "pt_debug_overlap_oriented_visits_cross", "pt_debug_sweep_visits", "pt_debug_capsule_cast_visits", "pt_debug_triangles_visits", "pt_debug_segments_visits", "pt_debug_triangle_distance_visits", "pt_debug_nearest_k_visits", "pt_debug_winding_visits", "pt_debug_list_phases", "pt_debug_query_poses", "pt_debug_triangle_cast_visits", "pt_debug_query_poses_cast", "pt_debug_read_winding", "pt_debug_read_tree", "pt_debug_build_stats",
+TEST_SYMBOLS = ["pt_bench_traversal", "pt_selftest", "pt_debug_wave_times", "pt_debug_queue_progress", "pt_debug_window_moves", "pt_debug_queue_order", "pt_debug_pixel_classes", "pt_debug_row_spans", "pt_read_morton", "pt_debug_environment", "pt_debug_environment_tables", "pt_debug_microfacet", "pt_debug_nearest_visits", "pt_debug_overlap_visits", "pt_debug_overlap_oriented_visits", "pt_debug_overlap_oriented_visits_cross", "pt_debug_sweep_visits", "pt_debug_capsule_cast_visits", "pt_debug_box_cast_visits", "pt_debug_triangles_visits", "pt_debug_segments_visits", "pt_debug_triangle_distance_visits", "pt_debug_nearest_k_visits", "pt_debug_winding_visits", "pt_debug_list_phases", "pt_debug_query_poses", "pt_debug_triangle_cast_visits", "pt_debug_query_poses_cast", "pt_debug_read_winding", "pt_debug_read_tree", "pt_debug_build_stats",
                 "pt_debug_small_kernel", "pt_debug_small_kernel_path", "pt_debug_small_ref", "pt_debug_small_budget",
                 "pt_debug_small_shape", "pt_debug_small_float_budget", "pt_debug_small_staged"]
 
@@ -298,6 +304,9 @@ def hip():
     L.pt_query_capsule_cast.argtypes = [vp, vp, sz, vp]; L.pt_query_capsule_cast.restype = C.c_int
     L.pt_query_capsule_cast_any.argtypes = [vp, vp, sz, vp]; L.pt_query_capsule_cast_any.restype = C.c_int
     L.pt_debug_capsule_cast_visits.argtypes = [vp, vp, sz, vp, vp, C.c_uint32]; L.pt_debug_capsule_cast_visits.restype = C.c_int
+    L.pt_query_box_cast.argtypes = [vp, vp, sz, vp]; L.pt_query_box_cast.restype = C.c_int
+    L.pt_query_box_cast_any.argtypes = [vp, vp, sz, vp]; L.pt_query_box_cast_any.restype = C.c_int
+    L.pt_debug_box_cast_visits.argtypes = [vp, vp, sz, vp, vp, C.c_uint32]; L.pt_debug_box_cast_visits.restype = C.c_int
     L.pt_query_triangles.argtypes = [vp, vp, sz, C.c_uint32, vp, vp]; L.pt_query_triangles.restype = C.c_int
     L.pt_query_triangles_any.argtypes = [vp, vp, sz, vp]; L.pt_query_triangles_any.restype = C.c_int
     L.pt_debug_triangles_visits.argtypes = [vp, vp, sz, vp, vp]; L.pt_debug_triangles_visits.restype = C.c_int

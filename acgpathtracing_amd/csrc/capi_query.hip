@@ -7,13 +7,15 @@
 // the complete lists in CSR form: pt_list_offsets, pt_query_overlap_lists, pt_query_triangles_lists, and the posed-mesh queries
 // pt_set_query_mesh, pt_get_query_mesh, pt_pose_triangles, pt_query_poses_any, pt_query_poses_distance, and the translating-triangle
 // casts pt_query_triangle_cast, pt_query_triangle_cast_any, pt_query_poses_cast, and the oriented-box overlap queries
-// pt_query_overlap_oriented, pt_query_overlap_oriented_any, pt_query_overlap_oriented_lists with pt_pose_boxes.
-// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, capsule.hip, tritri.hip, segment.hip, tridist.hip, winding.hip, lists.hip, poses.hip, tricast.hip and oriented.hip; their one walk, leaf routine and launch are in bvh_walk.h, closest_point.h and query_launch.h.  The context and what the units share: context.h.
+// pt_query_overlap_oriented, pt_query_overlap_oriented_any, pt_query_overlap_oriented_lists with pt_pose_boxes, and the swept
+// oriented-box casts pt_query_box_cast, pt_query_box_cast_any.
+// Host code only; the kernels are in query.hip, multihit.hip, ao.hip, nearest.hip, nearest_k.hip, overlap.hip, sweep.hip, capsule.hip, tritri.hip, segment.hip, tridist.hip, winding.hip, lists.hip, poses.hip, tricast.hip, oriented.hip and boxcast.hip; their one walk, leaf routine and launch are in bvh_walk.h, closest_point.h and query_launch.h.  The context and what the units share: context.h.
 #include <cmath>
 
 #include "../../include/acgpt_test.h"
 #include "context.h"
 #include "ao.h"
+#include "boxcast.h"
 #include "capsule.h"
 #include "lists.h"
 #include "multihit.h"
@@ -33,6 +35,7 @@ static_assert(sizeof(pt_hit) == 32, "pt_hit: a change of this layout bumps pt_ab
 static_assert(sizeof(pt_nearest) == 32, "pt_nearest: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_sweep_hit) == 32, "pt_sweep_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_capsule_cast_hit) == 32, "pt_capsule_cast_hit: a change of this layout bumps pt_abi_version");
+static_assert(sizeof(pt_box_cast_hit) == 48, "pt_box_cast_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_segment_hit) == 32, "pt_segment_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_triangle_distance_hit) == 48, "pt_triangle_distance_hit: a change of this layout bumps pt_abi_version");
 static_assert(sizeof(pt_pose_distance_hit) == 48, "pt_pose_distance_hit: a change of this layout bumps pt_abi_version");
@@ -852,6 +855,58 @@ PT_API int pt_debug_capsule_cast_visits(pt_ctx* c, const float* casts, size_t n,
     if (int rc = capsule_cast_prepare(c, "pt_debug_capsule_cast_visits", casts, n, hits, sizeof(pt_capsule_cast_hit), true, visits, true, &fmt)) return rc < 0 ? 0 : rc;
     CK(c, ptd::launch_capsule_cast_visits(fmt, device_scene(c), c->stack_entries, ptd::sweep_scene_scale(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)casts,
                                           (uint32_t)n, (float4*)hits, (uint2*)visits, mode == 0u && ptd::kCapsulePlane, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- swept oriented boxes ---------------------------------------------------------------------------------------------------------
+// every refusal of the three calls before any device work, in pt_query_capsule_cast's order; a cast is 80 bytes.  out_bytes: bytes of
+// output per cast.  Returns 0 to go on, 1 refused, -1 nothing to do (n == 0).
+static int box_cast_prepare(pt_ctx* c, const char* fn, const float* casts, size_t n, const void* out, size_t out_bytes, bool out_aligned, const void* visits,
+                            bool with_visits, int* fmt)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (!c) return fail(nullptr, f + "null context");
+    if (n == 0) return -1;
+    if (!casts || !out || (with_visits && !visits)) return fail(c, f + "null argument");
+    if (n > 0x7FFFFFFFull) return fail(c, f + "too many casts (2^31 - 1 per call)");
+    if (((uintptr_t)casts & 15u) || (out_aligned && ((uintptr_t)out & 15u)) || ((uintptr_t)visits & 7u))
+        return fail(c, f + "the cast and hit arrays must be 16-byte aligned");
+    if (spans_overlap(casts, n * 80u, out, n * out_bytes)) return fail(c, f + "the output overlaps the casts");
+    if (with_visits && (spans_overlap(casts, n * 80u, visits, n * 8u) || spans_overlap(out, n * out_bytes, visits, n * 8u)))
+        return fail(c, f + "the visit counts overlap another array");
+    return query_node_format(c, f, fmt);
+}
+
+PT_API int pt_query_box_cast(pt_ctx* c, const float* casts, size_t n, pt_box_cast_hit* hits)
+{
+    int fmt = 0;
+    if (int rc = box_cast_prepare(c, "pt_query_box_cast", casts, n, hits, sizeof(pt_box_cast_hit), true, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_box_cast");
+    CK(c, ptd::launch_query_box_toi(fmt, device_scene(c), c->stack_entries, ptd::sweep_scene_scale(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)casts,
+                                    (uint32_t)n, (float4*)hits, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_query_box_cast_any(pt_ctx* c, const float* casts, size_t n, uint8_t* blocked)
+{
+    int fmt = 0;
+    if (int rc = box_cast_prepare(c, "pt_query_box_cast_any", casts, n, blocked, 1, false, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
+    Range range("pt_query_box_cast_any");
+    CK(c, ptd::launch_query_box_toi_any(fmt, device_scene(c), c->stack_entries, ptd::sweep_scene_scale(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)casts,
+                                        (uint32_t)n, blocked, c->stream));
+    CK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+PT_API int pt_debug_box_cast_visits(pt_ctx* c, const float* casts, size_t n, pt_box_cast_hit* hits, uint32_t* visits, uint32_t mode)
+{
+    if (c && mode > 1u) return fail(c, "pt_debug_box_cast_visits: mode is 0 (the walk with the extra axes) or 1 (the slab alone)");
+    int fmt = 0;
+    if (int rc = box_cast_prepare(c, "pt_debug_box_cast_visits", casts, n, hits, sizeof(pt_box_cast_hit), true, visits, true, &fmt)) return rc < 0 ? 0 : rc;
+    CK(c, ptd::launch_box_toi_visits(fmt, device_scene(c), c->stack_entries, ptd::sweep_scene_scale(c->bvh.scene_lo, c->bvh.scene_hi), (const float4*)casts,
+                                     (uint32_t)n, (float4*)hits, (uint2*)visits, mode == 0u, c->stream));
     CK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -18,7 +18,8 @@
 //              [--firefly ratio[,rank[,radius]]] [--bloom [threshold,intensity[,levels[,spread]]]] [--pick x,y ...]
 //              [--nearest x,y,z[,radius] ...] [--pick-all x,y[,k] ...] [--overlap cx,cy,cz,hx,hy,hz[,k|,all] ...] [--overlap-oriented cx,cy,cz,hx,hy,hz,qw,qx,qy,qz[,k|,all] ...] [--intersect x0,y0,z0,x1,y1,z1,x2,y2,z2[,k|,all] ...]
 //              [--cast x0,y0,z0,x1,y1,z1,x2,y2,z2,dx,dy,dz[,tmax] ...] [--cast-mesh mesh.obj,dx,dy,dz[,tmax] ...]
-//              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...] [--capsule-cast x0,y0,z0,x1,y1,z1,dx,dy,dz,r[,tmax] ...] [--clearance x0,y0,z0,x1,y1,z1[,radius] ...]
+//              [--sweep ox,oy,oz,dx,dy,dz,r[,tmax] ...] [--capsule-cast x0,y0,z0,x1,y1,z1,dx,dy,dz,r[,tmax] ...]
+//              [--box-cast cx,cy,cz,hx,hy,hz,qw,qx,qy,qz,dx,dy,dz[,tmax] ...] [--clearance x0,y0,z0,x1,y1,z1[,radius] ...]
 //              [--tri-distance x0,y0,z0,x1,y1,z1,x2,y2,z2[,radius] ...]
 //              [--collide mesh.obj[,tx,ty,tz[,radius]] ...]
 //              [--nearest-k x,y,z,k[,radius] ...] [--within x,y,z,radius ...] [--winding x,y,z[,beta] ...]
@@ -84,6 +85,13 @@
 // "<newmtl name>", "point": [x, y, z], "s": ..., "feature": <0..5>} (the contact point on the triangle, the parameter of the axis' point
 // that touches and pt_query_segments' feature there), {"capsule_cast": [...], "tmax": ..., "hit": false} if nothing is touched.  The same
 // refusals as --sweep.  The frames are the same with or without it.
+// --box-cast cx,cy,cz,hx,hy,hz,qw,qx,qy,qz,dx,dy,dz[,tmax] (repeatable): how far the box of centre c and half extents h, turned by the unit
+// quaternion q, travels along d before it touches the scene (t in units of |d|, at most tmax, default unbounded), all in one call of
+// pt_query_box_cast, one JSON line each: {"box_cast": [the thirteen numbers], "tmax": <tmax or null>, "hit": true, "t": ..., "triangle":
+// <index>, "material": "<newmtl name>", "feature": <0..13>, "normal": [x, y, z], "point": [x, y, z]} (the winning axis of the 13-axis
+// test, 13 for a box that starts in contact; the unit normal from the triangle to the box and the contact point),
+// {"box_cast": [...], "tmax": ..., "hit": false} if nothing is touched.  Refused: a value that is not finite, a negative half extent or
+// tmax, a quaternion whose squared length is off 1 by more than 1e-4.  The frames are the same with or without it.
 // --cast x0,y0,z0,x1,y1,z1,x2,y2,z2,dx,dy,dz[,tmax] (repeatable): how far the triangle of these three vertices translates along d before it
 // first touches the scene (t in units of |d|, at most tmax, default unbounded), all in one call of pt_query_triangle_cast, one JSON line
 // each: {"cast": [the twelve numbers], "tmax": <tmax or null>, "hit": true, "t": ..., "triangle": <index>, "feature": <0..15>,
@@ -994,6 +1002,41 @@ static void castCapsules(PathTracerState& state, const TinyObjWrapper& obj, cons
     fflush(stdout);
 }
 
+// --box-cast: every oriented box in one call of pt_query_box_cast; one JSON line per cast.  in: the thirteen numbers as given
+struct BoxCastArg { float v[20]; float in[13]; };
+static void castBoxes(PathTracerState& state, const TinyObjWrapper& obj, const std::vector<BoxCastArg>& casts)
+{
+    const size_t n = casts.size();
+    std::vector<float> recs(n * 20);
+    for (size_t i = 0; i < n; i++) for (int j = 0; j < 20; j++) recs[i * 20 + j] = casts[i].v[j];
+    void* d_casts = nullptr; void* d_out = nullptr;
+    std::vector<pt_box_cast_hit> out(n);
+    std::string err;
+    if (pt_device_malloc(state.context, &d_casts, n * 80) != 0 || pt_device_malloc(state.context, &d_out, n * sizeof(pt_box_cast_hit)) != 0 ||
+        pt_copy_to_device(state.context, d_casts, recs.data(), n * 80) != 0 ||
+        pt_query_box_cast(state.context, (const float*)d_casts, n, (pt_box_cast_hit*)d_out) != 0 ||
+        pt_copy_to_host(state.context, out.data(), d_out, n * sizeof(pt_box_cast_hit)) != 0)
+        err = pt_last_error(state.context);
+    if (d_casts) pt_device_free(state.context, d_casts);
+    if (d_out) pt_device_free(state.context, d_out);
+    if (!err.empty()) throw Exception("box-cast: " + err);
+    const std::vector<std::string>& names = obj.getMaterialNames();
+    for (size_t i = 0; i < n; i++) {
+        const pt_box_cast_hit& r = out[i];
+        const float* q = casts[i].in;
+        printf("{\"box_cast\": [");
+        for (int j = 0; j < 13; j++) printf(j ? ", %.9g" : "%.9g", q[j]);
+        printf("], \"tmax\": ");
+        if (std::isfinite(casts[i].v[19])) printf("%.9g", casts[i].v[19]); else printf("null");
+        if (r.prim == 0xFFFFFFFFu) { printf(", \"hit\": false}\n"); continue; }
+        std::string name = r.material < names.size() ? names[r.material] : std::string();
+        for (size_t k = 0; k < name.size(); k++) if (name[k] == '"' || name[k] == '\\' || (unsigned char)name[k] < 0x20) name[k] = '_';
+        printf(", \"hit\": true, \"t\": %.9g, \"triangle\": %u, \"material\": \"%s\", \"feature\": %d, \"normal\": [%.9g, %.9g, %.9g], \"point\": [%.9g, %.9g, %.9g]}\n",
+               r.t, r.prim, name.c_str(), (int)r.feature, r.nx, r.ny, r.nz, r.cx, r.cy, r.cz);
+    }
+    fflush(stdout);
+}
+
 // --cast: every translating triangle in one call of pt_query_triangle_cast; one JSON line per cast
 struct CastArg { float v[16]; };
 static void printCastHit(const pt_triangle_cast_hit& r, const std::vector<std::string>& names, bool posed)
@@ -1374,6 +1417,7 @@ int main(int argc, char** argv)
     std::vector<IntersectTri> intersects;
     std::vector<SweepArg> sweeps;
     std::vector<CapsuleCastArg> capsuleCasts;
+    std::vector<BoxCastArg> boxCasts;
     std::vector<CastArg> casts;
     std::vector<CastMesh> castMeshList;
     int32_t width = 512, height = 512, frames = 8, dump_every = 0, denoise_iters = 0;
@@ -1615,6 +1659,26 @@ int main(int argc, char** argv)
             if (!ok) { std::cerr << "--capsule-cast x0,y0,z0,x1,y1,z1,dx,dy,dz,r[,tmax]: finite values, a radius >= 0, a tmax >= 0" << std::endl; return 2; }
             capsuleCasts.push_back(w);
         }
+        else if (a == "--box-cast") {
+            BoxCastArg w = {};
+            float* q = w.in;
+            float tmax = INFINITY;
+            const int got = sscanf(next(), "%f,%f,%f,%f,%f,%f,%f,%f,%f,%f,%f,%f,%f,%f", &q[0], &q[1], &q[2], &q[3], &q[4], &q[5], &q[6], &q[7], &q[8], &q[9], &q[10], &q[11],
+                                   &q[12], &tmax);
+            bool ok = got >= 13 && q[3] >= 0.0f && q[4] >= 0.0f && q[5] >= 0.0f && tmax >= 0.0f;
+            for (int j = 0; j < 13; j++) ok = ok && std::isfinite(q[j]);
+            const float qw = q[6], qx = q[7], qy = q[8], qz = q[9];
+            ok = ok && std::fabs((qw * qw + qx * qx) + (qy * qy + qz * qz) - 1.0f) <= 1e-4f;
+            if (!ok) { std::cerr << "--box-cast cx,cy,cz,hx,hy,hz,qw,qx,qy,qz,dx,dy,dz[,tmax]: finite values, half extents >= 0, a unit quaternion, a tmax >= 0" << std::endl; return 2; }
+            // the rotation of the unit quaternion, row-major beside the centre: a pt_query_overlap_oriented record, then {d, tmax}
+            const float m[12] = {1.0f - 2.0f * (qy * qy + qz * qz), 2.0f * (qx * qy - qz * qw), 2.0f * (qx * qz + qy * qw), q[0],
+                                 2.0f * (qx * qy + qz * qw), 1.0f - 2.0f * (qx * qx + qz * qz), 2.0f * (qy * qz - qx * qw), q[1],
+                                 2.0f * (qx * qz - qy * qw), 2.0f * (qy * qz + qx * qw), 1.0f - 2.0f * (qx * qx + qy * qy), q[2]};
+            for (int j = 0; j < 12; j++) w.v[j] = m[j];
+            w.v[12] = q[3]; w.v[13] = q[4]; w.v[14] = q[5]; w.v[15] = 0.0f;
+            w.v[16] = q[10]; w.v[17] = q[11]; w.v[18] = q[12]; w.v[19] = tmax;
+            boxCasts.push_back(w);
+        }
         else if (a == "--cast") {
             CastArg w = {{0.0f, 0.0f, 0.0f, INFINITY, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};
             float* v = w.v;
@@ -1777,6 +1841,7 @@ int main(int argc, char** argv)
         if (!intersects.empty()) { std::cout.flush(); intersectTriangles(state, intersects); }
         if (!sweeps.empty()) { std::cout.flush(); sweepSpheres(state, obj, sweeps); }
         if (!capsuleCasts.empty()) { std::cout.flush(); castCapsules(state, obj, capsuleCasts); }
+        if (!boxCasts.empty()) { std::cout.flush(); castBoxes(state, obj, boxCasts); }
         if (!casts.empty()) { std::cout.flush(); castTriangles(state, obj, casts); }
         if (!castMeshList.empty()) { std::cout.flush(); castMeshes(state, obj, castMeshList); }
         if (ao_samples > 0) ambientOcclusion(state, ao_samples, ao_radius, ao_bias, ao_frames, ao_out);

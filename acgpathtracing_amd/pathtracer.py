@@ -2564,6 +2564,154 @@ def capsuleContacts(result, casts):
     return tuple(np.where(hit[:, None], x, nan).astype(np.float32) for x in (q0, q1, on_axis, normal)) + (t == 0,)
 
 
+# ------------------------------------------------------------------ swept oriented boxes ----
+BOX_CAST_DTYPE = _native.BOX_CAST_DTYPE      # pt_box_cast_hit
+
+
+def _box_cast_records(casts_or_boxes, directions, tmax):
+    """The (n, 20) float32 records {m0..m11 | hx hy hz - | d, tmax} of a NumPy call, every refusal before any device work."""
+    what = "queryBoxCast"
+    b = np.asarray(casts_or_boxes)
+    if b.dtype.kind not in "fiu":
+        raise PathTracerError("%s: the casts must be numbers, got %s" % (what, b.dtype))
+    if directions is None:
+        if b.ndim != 2 or b.shape[1] != 20:
+            raise PathTracerError("%s: expected an (n, 20) array {m[0..11], hx, hy, hz, 0, d, tmax}, or (n, 16) oriented boxes with directions, got shape %s" % (what, b.shape))
+        return np.ascontiguousarray(b, np.float32)
+    d = np.asarray(directions)
+    if b.ndim != 2 or b.shape[1] != 16:
+        raise PathTracerError("%s: directions go with (n, 16) oriented boxes (orientedBoxes makes them), got shape %s" % (what, b.shape))
+    if d.dtype.kind not in "fiu" or d.shape not in ((b.shape[0], 3), (3,)):
+        raise PathTracerError("%s: expected (n, 3) directions or one (3,) for %d boxes, got shape %s" % (what, b.shape[0], d.shape))
+    t = np.asarray(tmax, np.float64)
+    if t.ndim not in (0, 1) or (t.ndim == 1 and t.shape[0] != b.shape[0]):
+        raise PathTracerError("%s: tmax is one number or one per box, got shape %s" % (what, t.shape))
+    if not (t >= 0.0).all():
+        raise PathTracerError("%s: tmax must be non-negative, got %r" % (what, tmax))
+    s = np.zeros((b.shape[0], 20), np.float32)
+    s[:, :16], s[:, 16:19], s[:, 19] = b, d, t
+    return s
+
+
+def _box_cast_tensor(state, casts, directions):
+    import torch
+    what = "queryBoxCast"
+    if directions is not None:
+        raise PathTracerError("%s: a tensor holds whole records (n, 20) {m[0..11], hx, hy, hz, 0, d, tmax}; directions go with arrays" % what)
+    if casts.device.type != "cuda" or casts.device.index != state._device:
+        raise PathTracerError("%s: the casts are on %s, the context is on cuda:%d" % (what, casts.device, state._device))
+    if casts.dtype != torch.float32:
+        raise PathTracerError("%s: the casts must be float32, got %s" % (what, casts.dtype))
+    if casts.dim() != 2 or casts.shape[1] != 20:
+        raise PathTracerError("%s: expected an (n, 20) tensor {m[0..11], hx, hy, hz, 0, d, tmax}, got shape %s" % (what, tuple(casts.shape)))
+    if not casts.is_contiguous():
+        raise PathTracerError("%s: the casts must be contiguous (nothing is copied)" % what)
+    return torch
+
+
+def queryBoxCast(state, casts_or_boxes, directions=None, tmax=float("inf"), any_hit=False):
+    """How far an oriented box travels before it touches the scene on the GPU, which triangle it touches, with which normal and where
+    (include/acgpt.h pt_query_box_cast): the box is at centre + t d for 0 <= t <= tmax, t in units of |d|.
+
+    NumPy (or anything np.asarray takes): (n, 20) records {m[0..11] | hx, hy, hz, 0 | d, tmax}, or (n, 16) oriented boxes
+    (orientedBoxes' output) with (n, 3) or (3,) directions and tmax (one number or one per box).  The answer is a dict of arrays t (n,)
+    float32 (-1 on a miss), prim (n,) uint32 (0xFFFFFFFF), feature (n,) float32 (the winning axis 0..12 of the 13-axis test, 13 for a
+    box that starts in contact), material (n,) uint32, normal (n, 3) the unit normal from the triangle to the box and point (n, 3) the
+    contact point (both zero on a miss and on a start overlap).  boxCastContacts turns it into what a controller needs.
+    any_hit=True asks pt_query_box_cast_any instead and returns a bool array (n,): blocked or not.
+
+    A torch tensor must be (n, 20) float32, contiguous and on the context's device; nothing is copied, its data_ptr() goes straight in,
+    and the answer is torch tensors on that device: views of one (n, 12) float32 tensor, prim and material as int32 (-1 on a miss), or a
+    bool tensor with any_hit.  torch's current stream is synchronised before the call, and the call returns synchronised."""
+    if _is_tensor(casts_or_boxes):
+        x = casts_or_boxes
+        torch = _box_cast_tensor(state, x, directions)
+        L = _native.hip()
+        n = int(x.shape[0])
+        with torch.cuda.device(x.device):
+            out = torch.empty((n,), dtype=torch.uint8, device=x.device) if any_hit else torch.empty((n, 12), dtype=torch.float32, device=x.device)
+            torch.cuda.current_stream().synchronize()      # the casts' producer and the allocation; the call below returns synchronised
+        if any_hit:
+            _check(state.context, L.pt_query_box_cast_any(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_box_cast_any")
+            return out.view(torch.bool)
+        _check(state.context, L.pt_query_box_cast(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_box_cast")
+        return {"t": out[:, 0], "prim": out[:, 1].view(torch.int32), "feature": out[:, 2], "material": out[:, 3].view(torch.int32), "normal": out[:, 4:7], "point": out[:, 8:11]}
+    s = _box_cast_records(casts_or_boxes, directions, tmax)
+    n = s.shape[0]
+    out = np.zeros(n, np.uint8) if any_hit else np.zeros(n, BOX_CAST_DTYPE)
+    if n:
+        L = _native.hip()
+        bufs = _device_buffers(state, 2, s.nbytes)
+        try:
+            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], s.ctypes.data, s.nbytes), "copy to device")
+            if any_hit:
+                _check(state.context, L.pt_query_box_cast_any(state.context, bufs[0], n, bufs[1]), "pt_query_box_cast_any")
+            else:
+                _check(state.context, L.pt_query_box_cast(state.context, bufs[0], n, bufs[1]), "pt_query_box_cast")
+            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
+        finally:
+            _free_device_buffers(state, bufs)
+    if any_hit:
+        return out.view(np.bool_)
+    return {k: np.ascontiguousarray(out[k]) for k in ("t", "prim", "feature", "material", "normal", "point")}
+
+
+def boxCastContacts(result, casts):
+    """What a controller needs of queryBoxCast's answer: (centre, normal, point, start_overlap, slide) — the box's centre at impact
+    c + d * t (n, 3), the unit contact normal from the surface towards the box and the contact point as the result gives them, where
+    the box touched the scene before it moved, t == 0 (n,) bool, and the direction the box can go on in without entering the surface,
+    d - n (n . d) (n, 3): d itself on a start overlap, whose normal is zero.  A miss has NaN centres, normals, points and slides.
+    casts: the (n, 20) records the result answers; arrays with arrays, tensors with tensors."""
+    if _is_tensor(casts):
+        import torch
+        if casts.dim() != 2 or casts.shape[1] != 20 or result["t"].shape[0] != casts.shape[0]:
+            raise PathTracerError("boxCastContacts: expected the (n, 20) casts of the result, got shape %s" % (tuple(casts.shape),))
+        t = result["t"]
+        hit = t >= 0
+        d = casts[:, 16:19]
+        centre = torch.stack([casts[:, 3], casts[:, 7], casts[:, 11]], dim=1) + d * t[:, None]
+        nrm = result["normal"]
+        slide = d - nrm * (nrm * d).sum(dim=1, keepdim=True)
+        nan = torch.full_like(centre, float("nan"))
+        return tuple(torch.where(hit[:, None], x, nan) for x in (centre, nrm, result["point"])) + (t == 0, torch.where(hit[:, None], slide, nan))
+    c = np.asarray(casts, np.float32)
+    t = np.asarray(result["t"], np.float32)
+    if c.ndim != 2 or c.shape[1] != 20 or t.shape != (c.shape[0],):
+        raise PathTracerError("boxCastContacts: expected the (n, 20) casts of the result, got shape %s" % (c.shape,))
+    hit = t >= 0
+    nrm, point = np.asarray(result["normal"], np.float32), np.asarray(result["point"], np.float32)
+    with np.errstate(all="ignore"):
+        d = c[:, 16:19]
+        centre = c[:, [3, 7, 11]] + d * t[:, None]
+        slide = d - nrm * (nrm * d).sum(axis=1, keepdims=True)
+    nan = np.float32(np.nan)
+    return tuple(np.where(hit[:, None], x, nan).astype(np.float32) for x in (centre, nrm, point)) + (t == 0, np.where(hit[:, None], slide, nan).astype(np.float32))
+
+
+def poseBoxCasts(state, poses, local_box, motions):
+    """The (P, 20) casts of a box of the mesh's own frame under each pose, assembled on the device: poseBoxes' record (pt_pose_boxes)
+    with the motion {d, tmax} behind it, what queryBoxCast takes — a registered hull's bounding box cast per pose ahead of
+    queryPosesCast.  local_box: (lo, hi) of the box in the mesh's frame, as poseBoxes takes them.  motions: queryPosesCast's ((P, 4)
+    {d, tmax}, (P, 3) directions, or one row for all poses); with a poses tensor a (P, 4) float32 tensor on the same device, and the
+    answer is a tensor there."""
+    try:
+        lo, hi = local_box
+    except (TypeError, ValueError):
+        raise PathTracerError("poseBoxCasts: local_box is (lo, hi), two xyz, got %r" % (local_box,))
+    if _is_tensor(poses):
+        if not _is_tensor(motions):
+            raise PathTracerError("poseBoxCasts: tensor poses take a (P, 4) tensor of motions")
+        torch = _cast_tensor("poseBoxCasts", state, motions, 4, "motions")
+        boxes = poseBoxes(state, poses, lo, hi)
+        if int(motions.shape[0]) != int(boxes.shape[0]):
+            raise PathTracerError("poseBoxCasts: %d poses and %d motions" % (int(boxes.shape[0]), int(motions.shape[0])))
+        return torch.cat([boxes, motions], dim=1).contiguous()
+    _local_box("poseBoxCasts", lo, hi)
+    recs = _pose_records("poseBoxCasts", state, poses)
+    m = _motion_records("poseBoxCasts", motions, int(recs.shape[0]))
+    return np.ascontiguousarray(np.concatenate([poseBoxes(state, recs, lo, hi), m], axis=1))
+
+
 # ------------------------------------------------------------------ translating-triangle casts ----
 TRIANGLE_CAST_DTYPE = np.dtype([("t", np.float32), ("prim", np.uint32), ("feature", np.float32), ("query_triangle", np.uint32), ("point", np.float32, 3),
                                 ("material", np.uint32)])      # pt_triangle_cast_hit

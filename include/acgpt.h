@@ -768,6 +768,66 @@ typedef struct { float t; uint32_t prim; float s, feature; float cx, cy, cz; uin
 int pt_query_capsule_cast(pt_ctx* ctx, const float* casts, size_t n, pt_capsule_cast_hit* hits);
 int pt_query_capsule_cast_any(pt_ctx* ctx, const float* casts, size_t n, uint8_t* blocked);
 
+/* ---- swept oriented-box casts on the device (opt-in; nothing above changes) ---------------------------------------------------------
+ * How far an oriented box — a vehicle hull, a crate, a robot link with a square section, a door, a camera volume — travels along a
+ * direction before it touches the mesh, which triangle it touches, with which normal and where: the box cast that physics libraries
+ * offer beside the sphere and the capsule cast.  Casting the 12 triangles of the box's surface with pt_query_triangle_cast misses every
+ * triangle that starts wholly inside the solid box.  pt_query_capsule_cast's memory and call rules: DEVICE arrays, 16-byte aligned
+ * (blocked: any alignment); the call enqueues on the context's stream and returns synchronised, acts on rank 0 of a pt_create_multi
+ * context, never writes the accumulation buffer, the frame buffer or pt_stats, walks the node array the scene holds and uses no
+ * atomics: two calls give the same bits.
+ *
+ *   casts     n records of 20 floats {m0 .. m11 | hx hy hz - | d.x d.y d.z tmax}: the first sixteen are a pt_query_overlap_oriented
+ *             record word for word (the sixteenth is never read).  The box occupies centre c + t d for 0 <= t <= tmax, closed at both
+ *             ends.  d is not normalised and t is in units of its length.  tmax = +inf is allowed and stands for the largest finite
+ *             float.  A half extent may be 0: a swept rectangle, segment or point.
+ *   time of impact of one triangle: in the box's frame the box is the cube |q_j| <= h_j and the triangle translates by -L(d) t; the
+ *             time is the entry of that line into the Minkowski difference of triangle and cube, a convex polytope whose face normals
+ *             are the 13 axes of pt_query_overlap's test.  All fp32, every operation on its own, evaluated as written, no fused
+ *             multiply-add, IEEE division and square root (tests/boxcast_ref.py is the NumPy statement, equal bit for bit), on the
+ *             stored v0, e1, e2.  With L pt_query_overlap_oriented's local:  P0 = L(v0 - c), E1 = L(e1), E2 = L(e2), D = L(d),
+ *             V = (-D.x, -D.y, -D.z), corners p0 = P0, p1 = P0 + E1, p2 = P0 + E2, h the half extent.
+ *               per axis, in this order (axis number 0..12):
+ *                 0, 1, 2         box face k:  lo = fmin3, hi = fmax3 of (p0[k], p1[k], p2[k]);  r = h[k];  s = V[k]
+ *                 3               N = cross(E1, E2):  lo = hi = dot(N, p0);  r = (h.x |N.x| + h.y |N.y|) + h.z |N.z|;  s = dot(N, V)
+ *                 4 + 3 g + i     edge f_g in (E1, E2 - E1, E2), box axis i, (j, k) the two axes after i:  proj(p) = p[k] f[j] - p[j] f[k];
+ *                                 lo = fmin3, hi = fmax3 of proj(p0), proj(p1), proj(p2);  r = h[j] |f[k]| + h[k] |f[j]|;  s = proj(V)
+ *               (fmin3(a, b, c) = fmin(fmin(a, b), c), likewise fmax3: pt_query_overlap's own projections and radii.)
+ *               s != 0:  a = (-r - hi) / s;  b = (r - lo) / s;  entry = b < a ? b : a;  exit = b < a ? a : b
+ *               s == 0:  entry = +inf, exit = -inf if lo > r or hi < -r (the axis rules the pair out), else entry = -inf, exit = +inf
+ *                        (a degenerate axis, lo = hi = r = s = 0, constrains nothing)
+ *               te = -inf, axis = 0, tx = +inf; then per axis in order:  if entry > te: te = entry, axis = this one (ties keep the
+ *               lowest axis);  if exit < tx: tx = exit.  Every compare is false on a NaN.
+ *               candidate iff te <= tx and tx >= 0 and te <= tmax;  t = te > 0 ? te : 0
+ *               start overlap   pt_query_overlap_oriented's statement on the same P0, E1, E2 holds: t = 0, feature 13, whatever the
+ *                               entry times say.  So t == 0 iff pt_query_overlap_oriented_any's byte for the first sixteen floats,
+ *                               for that triangle, bit for bit; with d = 0 the cast is that query.
+ *   the answer over all triangles, the smallest time of impact; ties go to the lowest index in the caller's index-buffer order.  The
+ *             walk's boxes only prune; the winner is decided by the test above alone.
+ *   hits      per cast {t, prim, feature, material | n.xyz, 0 | c.xyz, 0}, evaluated once after the walk on the winner.  feature: the
+ *             winning axis as a float, 0..12, or 13 for a start overlap (then n = c = 0).  With sg the s of the winning axis and a the
+ *             axis in local coordinates (unit k; N; for 4..12 the vector with a[i] = 0, a[j] = -f[k], a[k] = f[j]):
+ *               g = sg > 0 ? a : -a;  W[k] = (g.x m[4 k] + g.y m[4 k + 1]) + g.z m[4 k + 2];  len = sqrt(dot(W, W));
+ *               n = len > 0 ? W / len : 0 — the unit normal from the triangle to the box, dot(n, d) <= 0
+ *               sc[j] = g[j] > 0 ? -h[j] : h[j] — the box's corner towards the triangle, in local coordinates
+ *               0, 1, 2     ext = sg > 0 ? hi : lo of the axis;  c = the first of v0, v0 + e1, v0 + e2 whose projection equals ext
+ *               3           cen = c + d * t;  c[k] = cen[k] + ((sc.x m[4 k] + sc.y m[4 k + 1]) + sc.z m[4 k + 2]): the box corner
+ *               4 + 3 g + i the triangle's edge (A, E) in ((v0, e1), (v0 + e1, e2 - e1), (v0, e2)), pa = its start p0, p1, p0;
+ *                           al = pa + V * t;  dj = sc[j] - al[j];  dk = sc[k] - al[k];  ff = f[j] f[j] + f[k] f[k];
+ *                           u = (dj f[j] + dk f[k]) / ff, clamped to [0, 1] (u < 0 ? 0, then u > 1 ? 1), 0 unless ff > 0;  c = A + E * u
+ *             (x + y * s for vectors is per component, one multiply and one add.)  A contact that is a segment or a polygon reports
+ *             this one representative point.  material: the hit triangle's material id.
+ *             A miss is {-1, 0xFFFFFFFF, 0, 0xFFFFFFFF | 0 0 0 0 | 0 0 0 0}.
+ *   blocked   pt_query_box_cast_any: one byte per cast, 1 iff hits[i].t >= 0.  A cast's walk ends at its first candidate.
+ *   a miss before any traversal: pt_query_overlap_oriented's rules on the first sixteen floats (a non-finite value among the first
+ *             fifteen, a negative half extent, axes not orthonormal to 2^-10), a non-finite component of d, a NaN or negative tmax, a
+ *             scene without triangles.
+ * Not watertight at shared edges, as pt_query_sweep is not.  n == 0 is a no-op success.  Refused, with the context left usable:
+ * n > 0x7FFFFFFF, a null pointer, a misaligned casts or hits array, an output that overlaps the casts, a context without a scene.   */
+typedef struct { float t; uint32_t prim; float feature; uint32_t material; float nx, ny, nz, pad0; float cx, cy, cz, pad1; } pt_box_cast_hit;   /* 48 bytes */
+int pt_query_box_cast(pt_ctx* ctx, const float* casts, size_t n, pt_box_cast_hit* hits);
+int pt_query_box_cast_any(pt_ctx* ctx, const float* casts, size_t n, uint8_t* blocked);
+
 /* ---- segment-to-mesh distance on the device (opt-in; nothing above changes) --------------------------------------------------------
  * How far a line segment is from the surface and where the two come closest: the clearance query of motion planning.  A capsule (robot
  * link, cable, tool shaft, limb) clears the mesh by this distance minus its radius, and the closest pair is the direction to push away

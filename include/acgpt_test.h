@@ -158,6 +158,11 @@ int pt_debug_sweep_visits(pt_ctx* ctx, const float* sweeps, size_t n, pt_sweep_h
  * without the plane axis (the box's separation from the plane of the swept axis), which changes the counts and never the records;
  * anything else is refused.  tools/capsule_timing.py. */
 int pt_debug_capsule_cast_visits(pt_ctx* ctx, const float* casts, size_t n, pt_capsule_cast_hit* hits, uint32_t* visits, uint32_t mode);
+/* pt_query_box_cast (same records, same refusals) from a kernel instantiation that also counts: visits[2 i] = inner nodes cast i
+ * visited, visits[2 i + 1] = triangles it tested.  visits: DEVICE, 8-byte aligned, 2 n words.  mode: 0 the walk with the six extra axes
+ * (the box's own axes against the swept interval, and cross(box axis, d)), 1 the walk on the inflated slab alone, which changes the
+ * counts and never the records; anything else is refused.  tools/boxcast_timing.py. */
+int pt_debug_box_cast_visits(pt_ctx* ctx, const float* casts, size_t n, pt_box_cast_hit* hits, uint32_t* visits, uint32_t mode);
 /* pt_query_triangles' counting walk (max_prims = 0: the same triangles, the same counts, the same refusals) from a kernel
  * instantiation that also counts its work: visits[2 i] = inner nodes query i visited, visits[2 i + 1] = triangles it tested.  counts:
  * DEVICE, n words; visits: DEVICE, 8-byte aligned, 2 n words; neither may be null.  tools/triangles_timing.py. */
