@@ -639,26 +639,128 @@ def _is_tensor(x):
     return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
 
 
-def _query_rays_tensor(state, rays, any_hit):
+def _tensor_records(what, state, x, width, noun, layout=""):
+    """The refusals of a tensor of query records: on the context's device, float32, (n, width), contiguous.  layout: what the shape's
+    message adds behind "tensor".  Returns n."""
     import torch
-    if rays.device.type != "cuda" or rays.device.index != state._device:
-        raise PathTracerError("queryRays: the rays are on %s, the context is on cuda:%d" % (rays.device, state._device))
-    if rays.dtype != torch.float32:
-        raise PathTracerError("queryRays: the rays must be float32, got %s" % rays.dtype)
-    if rays.dim() != 2 or rays.shape[1] != 8:
-        raise PathTracerError("queryRays: expected an (n, 8) tensor, got shape %s" % (tuple(rays.shape),))
-    if not rays.is_contiguous():
-        raise PathTracerError("queryRays: the rays must be contiguous (nothing is copied)")
-    n = int(rays.shape[0])
+    if x.device.type != "cuda" or x.device.index != state._device:
+        raise PathTracerError("%s: the %s are on %s, the context is on cuda:%d" % (what, noun, x.device, state._device))
+    if x.dtype != torch.float32:
+        raise PathTracerError("%s: the %s must be float32, got %s" % (what, noun, x.dtype))
+    if x.dim() != 2 or x.shape[1] != width:
+        raise PathTracerError("%s: expected an (n, %d) tensor%s, got shape %s" % (what, width, layout, tuple(x.shape)))
+    if not x.is_contiguous():
+        raise PathTracerError("%s: the %s must be contiguous (nothing is copied)" % (what, noun))
+    return int(x.shape[0])
+
+
+def _host_call(state, ins, outs, call):
+    """The round trip of host arrays: a device buffer per array of ins and of outs, the ins uploaded, call(*device pointers) in that
+    order, the outs downloaded, everything freed whatever happens.  An output that is None or holds nothing gets no buffer and goes
+    in as a null pointer.  Nothing happens where the first input holds no record."""
+    if ins and not ins[0].shape[0]:
+        return
     L = _native.hip()
-    with torch.cuda.device(rays.device):
-        out = torch.empty((n,), dtype=torch.uint8, device=rays.device) if any_hit else torch.empty((n, 8), dtype=torch.float32, device=rays.device)
-        torch.cuda.current_stream().synchronize()      # the rays' producer and the allocation; the call below returns synchronised
-    if any_hit:
-        _check(state.context, L.pt_query_any(state.context, rays.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_any")
+    bufs, ptrs = [], []
+    try:
+        for a in list(ins) + list(outs):
+            if a is not None and a.nbytes:
+                bufs += _device_buffers(state, 1, a.nbytes)
+            ptrs.append(bufs[-1] if a is not None and a.nbytes else None)
+        for a, d in zip(ins, ptrs):
+            _check(state.context, L.pt_copy_to_device(state.context, d, a.ctypes.data, a.nbytes), "copy to device")
+        call(*ptrs)
+        for a, d in zip(outs, ptrs[len(ins):]):
+            if d is not None:
+                _check(state.context, L.pt_copy_to_host(state.context, a.ctypes.data, d, a.nbytes), "copy to host")
+    finally:
+        _free_device_buffers(state, bufs)
+
+
+def _tensor_call(x, outs, call):
+    """The call on a tensor of records: the outputs allocated on its device ((shape, torch dtype name) each, or None), torch's current
+    stream synchronised once — the records' producer and the allocations; the call returns synchronised —, call(pointers) with null for
+    what holds nothing.  Returns the outputs."""
+    import torch
+    with torch.cuda.device(x.device):
+        got = [None if o is None else torch.empty(o[0], dtype=getattr(torch, o[1]), device=x.device) for o in outs]
+        torch.cuda.current_stream().synchronize()
+    call(*[t.data_ptr() if t is not None and t.numel() else None for t in [x] + got])
+    return got
+
+
+_TENSOR_DTYPE = {np.dtype(np.float32): "float32", np.dtype(np.uint32): "int32", np.dtype(np.uint8): "uint8"}
+
+
+def _query(state, symbol, recs, outs, *scalars):
+    """symbol(context, records, n, *scalars, *outputs) on records that are a checked tensor or an (n, w) float32 array.  outs: (row
+    shape, numpy dtype[, what an array holds before the call: 0]) per output, None for one the caller does not ask for.  Returns the
+    outputs: tensors for a tensor (uint32 as int32), arrays for an array."""
+    n = int(recs.shape[0])
+    fn = getattr(_native.hip(), symbol)
+
+    def call(d_recs, *d_outs):
+        _check(state.context, fn(state.context, d_recs, n, *(scalars + d_outs)), symbol)
+    if _is_tensor(recs):
+        return _tensor_call(recs, [None if o is None else ((n,) + o[0], _TENSOR_DTYPE[np.dtype(o[1])]) for o in outs], call)
+    got = [None if o is None else np.full((n,) + o[0], o[2] if len(o) > 2 else 0, o[1]) for o in outs]
+    _host_call(state, [recs], got, call)
+    return got
+
+
+# The columns of the 32- and 48-byte records the queries write, per layout: (key, first float, floats, whole numbers).  Both the
+# arrays and the tensor views of a result come from these, off one float32 array or tensor whose last axis is the record.
+_HIT_COLUMNS = (("t", 0, 1, False), ("prim", 1, 1, True), ("uv", 2, 2, False), ("normal", 4, 3, False), ("material", 7, 1, True))                                # pt_hit
+_MULTI_COLUMNS = (("t", 0, 1, False), ("prim", 1, 1, True), ("u", 2, 1, False), ("v", 3, 1, False), ("normal", 4, 3, False), ("material", 7, 1, True))           # pt_hit, uv apart
+_NEAREST_COLUMNS = (("distance", 0, 1, False), ("prim", 1, 1, True), ("u", 2, 1, False), ("v", 3, 1, False), ("point", 4, 3, False), ("material", 7, 1, True))    # pt_nearest
+_SEGMENT_COLUMNS = (("distance", 0, 1, False), ("prim", 1, 1, True), ("s", 2, 1, False), ("feature", 3, 1, False), ("point", 4, 3, False), ("material", 7, 1, True))      # pt_segment_hit
+_SWEEP_COLUMNS = (("t", 0, 1, False), ("prim", 1, 1, True), ("u", 2, 1, False), ("v", 3, 1, False), ("point", 4, 3, False), ("material", 7, 1, True))            # pt_sweep_hit
+_CAPSULE_CAST_COLUMNS = (("t", 0, 1, False), ("prim", 1, 1, True), ("s", 2, 1, False), ("feature", 3, 1, False), ("point", 4, 3, False), ("material", 7, 1, True))        # pt_capsule_cast_hit
+_BOX_CAST_COLUMNS = (("t", 0, 1, False), ("prim", 1, 1, True), ("feature", 2, 1, False), ("material", 3, 1, True), ("normal", 4, 3, False), ("point", 8, 3, False))      # pt_box_cast_hit
+_TRIANGLE_DISTANCE_COLUMNS = (("distance", 0, 1, False), ("prim", 1, 1, True), ("feature", 2, 1, False), ("material", 3, 1, True), ("on_query", 4, 3, False),
+                              ("point", 8, 3, False))                                                                                                           # pt_triangle_distance_hit
+_TRIANGLE_CAST_COLUMNS = (("t", 0, 1, False), ("prim", 1, 1, True), ("feature", 2, 1, False), ("query_triangle", 3, 1, True), ("point", 4, 3, False),
+                          ("material", 7, 1, True))                                                                                                             # pt_triangle_cast_hit
+
+
+def _columns(out, columns):
+    """The dict of a result from the float32 records out[..., w]: views of a tensor (whole numbers as int32), contiguous arrays of an
+    array (whole numbers as uint32)."""
+    tensor = _is_tensor(out)
+    if tensor:
+        import torch
+    got = {}
+    for key, first, width, whole in columns:
+        col = out[..., first] if width == 1 else out[..., first:first + width]
+        if tensor:
+            got[key] = col.view(torch.int32) if whole else col
+        else:
+            got[key] = np.ascontiguousarray(col).view(np.uint32) if whole else np.ascontiguousarray(col)
+    return got
+
+
+def _as_bool(out):
+    """the bytes of an any-hit answer as bools, tensor or array"""
+    if _is_tensor(out):
+        import torch
         return out.view(torch.bool)
-    _check(state.context, L.pt_query_closest(state.context, rays.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_closest")
-    return {"t": out[:, 0], "prim": out[:, 1].view(torch.int32), "uv": out[:, 2:4], "normal": out[:, 4:7], "material": out[:, 7].view(torch.int32)}
+    return out.view(np.bool_)
+
+
+def _records_or_hit(state, recs, any_hit, symbol, any_symbol, width, columns):
+    """The calls with an any-hit twin: any_symbol and a bool per record, or symbol, `width` floats per record and their columns."""
+    if any_hit:
+        return _as_bool(_query(state, any_symbol, recs, [((), np.uint8)])[0])
+    return _columns(_query(state, symbol, recs, [((width,), np.float32)])[0], columns)
+
+
+def _list_or_counts(state, symbol, recs, k, counts):
+    """The calls that list up to k triangle indices per record and count them: {"prim", and "count" when asked}."""
+    out, cnt = _query(state, symbol, recs, [((k,), np.uint32, 0xFFFFFFFF), ((), np.uint32) if counts else None], k)
+    got = {"prim": out}
+    if counts:
+        got["count"] = cnt
+    return got
 
 
 def queryRays(state, rays, any_hit=False):
@@ -674,30 +776,16 @@ def queryRays(state, rays, any_hit=False):
     the answer is torch tensors on that device: views of one (n, 8) float32 tensor, prim and material as int32 (-1 on a miss), or a
     bool tensor with any_hit.  torch's current stream is synchronised before the call, and the call returns synchronised."""
     if _is_tensor(rays):
-        return _query_rays_tensor(state, rays, any_hit)
-    r = np.asarray(rays)
-    if r.ndim != 2 or r.shape[1] != 8:
-        raise PathTracerError("queryRays: expected an (n, 8) array, got shape %s" % (r.shape,))
-    if r.dtype.kind not in "fiu":
-        raise PathTracerError("queryRays: the rays must be numbers, got %s" % r.dtype)
-    r = np.ascontiguousarray(r, np.float32)
-    n = r.shape[0]
-    out = np.zeros(n, np.uint8) if any_hit else np.zeros(n, HIT_DTYPE)
-    if n:
-        L = _native.hip()
-        bufs = _device_buffers(state, 2, max(r.nbytes, out.nbytes))
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], r.ctypes.data, r.nbytes), "copy to device")
-            if any_hit:
-                _check(state.context, L.pt_query_any(state.context, bufs[0], n, bufs[1]), "pt_query_any")
-            else:
-                _check(state.context, L.pt_query_closest(state.context, bufs[0], n, bufs[1]), "pt_query_closest")
-            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    if any_hit:
-        return out.view(np.bool_)
-    return {k: np.ascontiguousarray(out[k]) for k in HIT_DTYPE.names}
+        _tensor_records("queryRays", state, rays, 8, "rays")
+        r = rays
+    else:
+        r = np.asarray(rays)
+        if r.ndim != 2 or r.shape[1] != 8:
+            raise PathTracerError("queryRays: expected an (n, 8) array, got shape %s" % (r.shape,))
+        if r.dtype.kind not in "fiu":
+            raise PathTracerError("queryRays: the rays must be numbers, got %s" % r.dtype)
+        r = np.ascontiguousarray(r, np.float32)
+    return _records_or_hit(state, r, any_hit, "pt_query_closest", "pt_query_any", 8, _HIT_COLUMNS)
 
 
 # ------------------------------------------------------------------ the first hits in order ----
@@ -714,30 +802,6 @@ def _multi_args(what, max_hits, counts):
     if k == 0 and not counts:
         raise PathTracerError("%s: max_hits = 0 leaves only the counts to ask for (counts=True)" % what)
     return k
-
-
-def _query_multi_tensor(state, rays, k, counts):
-    import torch
-    if rays.device.type != "cuda" or rays.device.index != state._device:
-        raise PathTracerError("queryRaysMulti: the rays are on %s, the context is on cuda:%d" % (rays.device, state._device))
-    if rays.dtype != torch.float32:
-        raise PathTracerError("queryRaysMulti: the rays must be float32, got %s" % rays.dtype)
-    if rays.dim() != 2 or rays.shape[1] != 8:
-        raise PathTracerError("queryRaysMulti: expected an (n, 8) tensor, got shape %s" % (tuple(rays.shape),))
-    if not rays.is_contiguous():
-        raise PathTracerError("queryRaysMulti: the rays must be contiguous (nothing is copied)")
-    n = int(rays.shape[0])
-    with torch.cuda.device(rays.device):
-        out = torch.empty((n, k, 8), dtype=torch.float32, device=rays.device)
-        cnt = torch.empty((n,), dtype=torch.int32, device=rays.device) if counts else None
-        torch.cuda.current_stream().synchronize()      # the rays' producer and the allocations; the call below returns synchronised
-    _check(state.context, _native.hip().pt_query_multi(state.context, rays.data_ptr() if n else None, n, k, out.data_ptr() if n and k else None,
-                                                       cnt.data_ptr() if n and counts else None), "pt_query_multi")
-    got = {"t": out[:, :, 0], "prim": out[:, :, 1].view(torch.int32), "u": out[:, :, 2], "v": out[:, :, 3], "normal": out[:, :, 4:7],
-           "material": out[:, :, 7].view(torch.int32)}
-    if counts:
-        got["count"] = cnt
-    return got
 
 
 def queryRaysMulti(state, rays, max_hits=4, counts=False):
@@ -757,36 +821,17 @@ def queryRaysMulti(state, rays, max_hits=4, counts=False):
     last hit), count int32.  torch's current stream is synchronised before the call, and the call returns synchronised."""
     k = _multi_args("queryRaysMulti", max_hits, counts)
     if _is_tensor(rays):
-        return _query_multi_tensor(state, rays, k, bool(counts))
-    r = np.asarray(rays)
-    if r.ndim != 2 or r.shape[1] != 8:
-        raise PathTracerError("queryRaysMulti: expected an (n, 8) array, got shape %s" % (r.shape,))
-    if r.dtype.kind not in "fiu":
-        raise PathTracerError("queryRaysMulti: the rays must be numbers, got %s" % r.dtype)
-    r = np.ascontiguousarray(r, np.float32)
-    n = r.shape[0]
-    out = np.zeros((n, k), HIT_DTYPE)
-    cnt = np.zeros(n, np.uint32)
-    if n:
-        L = _native.hip()
-        bufs, d_hits, d_counts = _device_buffers(state, 1, r.nbytes), None, None
-        try:
-            if k:
-                bufs += _device_buffers(state, 1, out.nbytes)
-                d_hits = bufs[-1]
-            if counts:
-                bufs += _device_buffers(state, 1, cnt.nbytes)
-                d_counts = bufs[-1]
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], r.ctypes.data, r.nbytes), "copy to device")
-            _check(state.context, L.pt_query_multi(state.context, bufs[0], n, k, d_hits, d_counts), "pt_query_multi")
-            if k:
-                _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, d_hits, out.nbytes), "copy to host")
-            if counts:
-                _check(state.context, L.pt_copy_to_host(state.context, cnt.ctypes.data, d_counts, cnt.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    got = {"t": out["t"], "prim": out["prim"], "u": out["uv"][..., 0], "v": out["uv"][..., 1], "normal": out["normal"], "material": out["material"]}
-    got = {key: np.ascontiguousarray(val) for key, val in got.items()}
+        _tensor_records("queryRaysMulti", state, rays, 8, "rays")
+        r = rays
+    else:
+        r = np.asarray(rays)
+        if r.ndim != 2 or r.shape[1] != 8:
+            raise PathTracerError("queryRaysMulti: expected an (n, 8) array, got shape %s" % (r.shape,))
+        if r.dtype.kind not in "fiu":
+            raise PathTracerError("queryRaysMulti: the rays must be numbers, got %s" % r.dtype)
+        r = np.ascontiguousarray(r, np.float32)
+    out, cnt = _query(state, "pt_query_multi", r, [((k, 8), np.float32), ((), np.uint32) if counts else None], k)
+    got = _columns(out, _MULTI_COLUMNS)
     if counts:
         got["count"] = cnt
     return got
@@ -860,24 +905,6 @@ NEAREST_DTYPE = np.dtype([("distance", np.float32), ("prim", np.uint32), ("u", n
 assert NEAREST_DTYPE.itemsize == 32
 
 
-def _query_nearest_tensor(state, points):
-    import torch
-    if points.device.type != "cuda" or points.device.index != state._device:
-        raise PathTracerError("queryNearest: the points are on %s, the context is on cuda:%d" % (points.device, state._device))
-    if points.dtype != torch.float32:
-        raise PathTracerError("queryNearest: the points must be float32, got %s" % points.dtype)
-    if points.dim() != 2 or points.shape[1] != 4:
-        raise PathTracerError("queryNearest: expected an (n, 4) tensor {x, y, z, max_radius}, got shape %s" % (tuple(points.shape),))
-    if not points.is_contiguous():
-        raise PathTracerError("queryNearest: the points must be contiguous (nothing is copied)")
-    n = int(points.shape[0])
-    with torch.cuda.device(points.device):
-        out = torch.empty((n, 8), dtype=torch.float32, device=points.device)
-        torch.cuda.current_stream().synchronize()      # the points' producer and the allocation; the call below returns synchronised
-    _check(state.context, _native.hip().pt_query_nearest(state.context, points.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_nearest")
-    return {"distance": out[:, 0], "prim": out[:, 1].view(torch.int32), "u": out[:, 2], "v": out[:, 3], "point": out[:, 4:7], "material": out[:, 7].view(torch.int32)}
-
-
 def queryNearest(state, points, max_radius=float("inf")):
     """The closest surface point of the scene on the GPU to each query point (include/acgpt.h pt_query_nearest).
 
@@ -890,33 +917,24 @@ def queryNearest(state, points, max_radius=float("inf")):
     goes straight in, and the answer is torch tensors on that device: views of one (n, 8) float32 tensor, prim and material as int32
     (-1 on a miss).  torch's current stream is synchronised before the call, and the call returns synchronised."""
     if _is_tensor(points):
-        return _query_nearest_tensor(state, points)
-    p = np.asarray(points)
-    if p.ndim != 2 or p.shape[1] not in (3, 4):
-        raise PathTracerError("queryNearest: expected an (n, 3) or (n, 4) array, got shape %s" % (p.shape,))
-    if p.dtype.kind not in "fiu":
-        raise PathTracerError("queryNearest: the points must be numbers, got %s" % p.dtype)
-    if p.shape[1] == 3:
-        radius = float(max_radius)
-        if not radius >= 0.0:
-            raise PathTracerError("queryNearest: max_radius must be non-negative, got %r" % (max_radius,))
-        q = np.empty((p.shape[0], 4), np.float32)
-        q[:, 0:3] = p
-        q[:, 3] = radius
+        _tensor_records("queryNearest", state, points, 4, "points", " {x, y, z, max_radius}")
+        q = points
     else:
-        q = np.ascontiguousarray(p, np.float32)
-    n = q.shape[0]
-    out = np.zeros(n, NEAREST_DTYPE)
-    if n:
-        L = _native.hip()
-        bufs = _device_buffers(state, 2, out.nbytes)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], q.ctypes.data, q.nbytes), "copy to device")
-            _check(state.context, L.pt_query_nearest(state.context, bufs[0], n, bufs[1]), "pt_query_nearest")
-            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    return {k: np.ascontiguousarray(out[k]) for k in NEAREST_DTYPE.names}
+        p = np.asarray(points)
+        if p.ndim != 2 or p.shape[1] not in (3, 4):
+            raise PathTracerError("queryNearest: expected an (n, 3) or (n, 4) array, got shape %s" % (p.shape,))
+        if p.dtype.kind not in "fiu":
+            raise PathTracerError("queryNearest: the points must be numbers, got %s" % p.dtype)
+        if p.shape[1] == 3:
+            radius = float(max_radius)
+            if not radius >= 0.0:
+                raise PathTracerError("queryNearest: max_radius must be non-negative, got %r" % (max_radius,))
+            q = np.empty((p.shape[0], 4), np.float32)
+            q[:, 0:3] = p
+            q[:, 3] = radius
+        else:
+            q = np.ascontiguousarray(p, np.float32)
+    return _columns(_query(state, "pt_query_nearest", q, [((8,), np.float32)])[0], _NEAREST_COLUMNS)
 
 
 def distanceFieldPoints(resolution, lo, hi):
@@ -990,33 +1008,17 @@ def queryWinding(state, points, beta=_native.WINDING_BETA_DEFAULT):
     is a float32 tensor on that device.  torch's current stream is synchronised before the call, and the call returns synchronised."""
     b = _winding_beta(beta)
     if _is_tensor(points):
-        import torch
-        n = _point_tensor("queryWinding", state, points)
-        with torch.cuda.device(points.device):
-            out = torch.empty((n,), dtype=torch.float32, device=points.device)
-            torch.cuda.current_stream().synchronize()      # the points' producer and the allocation; the call below returns synchronised
-        _check(state.context, _native.hip().pt_query_winding(state.context, points.data_ptr() if n else None, n, b, out.data_ptr() if n else None),
-               "pt_query_winding")
-        return out
-    p = np.asarray(points)
-    if p.ndim != 2 or p.shape[1] not in (3, 4):
-        raise PathTracerError("queryWinding: expected an (n, 3) or (n, 4) array, got shape %s" % (p.shape,))
-    if p.dtype.kind not in "fiu":
-        raise PathTracerError("queryWinding: the points must be numbers, got %s" % p.dtype)
-    n = p.shape[0]
-    q = np.zeros((n, 4), np.float32)
-    q[:, 0:3] = p[:, 0:3]
-    out = np.zeros(n, np.float32)
-    if n:
-        L = _native.hip()
-        bufs = _device_buffers(state, 2, q.nbytes)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], q.ctypes.data, q.nbytes), "copy to device")
-            _check(state.context, L.pt_query_winding(state.context, bufs[0], n, b, bufs[1]), "pt_query_winding")
-            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    return out
+        _point_tensor("queryWinding", state, points)
+        q = points
+    else:
+        p = np.asarray(points)
+        if p.ndim != 2 or p.shape[1] not in (3, 4):
+            raise PathTracerError("queryWinding: expected an (n, 3) or (n, 4) array, got shape %s" % (p.shape,))
+        if p.dtype.kind not in "fiu":
+            raise PathTracerError("queryWinding: the points must be numbers, got %s" % p.dtype)
+        q = np.zeros((p.shape[0], 4), np.float32)
+        q[:, 0:3] = p[:, 0:3]
+    return _query(state, "pt_query_winding", q, [((), np.float32)], b)[0]
 
 
 def getWindingInfo(state):
@@ -1062,16 +1064,7 @@ def _point_records(what, points, max_radius):
 
 
 def _point_tensor(what, state, points):
-    import torch
-    if points.device.type != "cuda" or points.device.index != state._device:
-        raise PathTracerError("%s: the points are on %s, the context is on cuda:%d" % (what, points.device, state._device))
-    if points.dtype != torch.float32:
-        raise PathTracerError("%s: the points must be float32, got %s" % (what, points.dtype))
-    if points.dim() != 2 or points.shape[1] != 4:
-        raise PathTracerError("%s: expected an (n, 4) tensor {x, y, z, max_radius}, got shape %s" % (what, tuple(points.shape)))
-    if not points.is_contiguous():
-        raise PathTracerError("%s: the points must be contiguous (nothing is copied)" % what)
-    return int(points.shape[0])
+    return _tensor_records(what, state, points, 4, "points", " {x, y, z, max_radius}")
 
 
 def queryNearestK(state, points, k=4, max_radius=float("inf"), counts=False):
@@ -1090,43 +1083,12 @@ def queryNearestK(state, points, k=4, max_radius=float("inf"), counts=False):
     last candidate), count int32.  torch's current stream is synchronised before the call, and the call returns synchronised."""
     kk = _nearest_k_args("queryNearestK", k, counts)
     if _is_tensor(points):
-        import torch
-        L = _native.hip()
-        n = _point_tensor("queryNearestK", state, points)
-        with torch.cuda.device(points.device):
-            out = torch.empty((n, kk, 8), dtype=torch.float32, device=points.device)
-            cnt = torch.empty((n,), dtype=torch.int32, device=points.device) if counts else None
-            torch.cuda.current_stream().synchronize()      # the points' producer and the allocations; the call below returns synchronised
-        _check(state.context, L.pt_query_nearest_k(state.context, points.data_ptr() if n else None, n, kk, out.data_ptr() if n and kk else None,
-                                                   cnt.data_ptr() if n and counts else None), "pt_query_nearest_k")
-        got = {"distance": out[:, :, 0], "prim": out[:, :, 1].view(torch.int32), "u": out[:, :, 2], "v": out[:, :, 3], "point": out[:, :, 4:7],
-               "material": out[:, :, 7].view(torch.int32)}
-        if counts:
-            got["count"] = cnt
-        return got
-    q = _point_records("queryNearestK", points, max_radius)
-    n = q.shape[0]
-    out = np.zeros((n, kk), NEAREST_DTYPE)
-    cnt = np.zeros(n, np.uint32)
-    if n:
-        L = _native.hip()
-        bufs, d_out, d_counts = _device_buffers(state, 1, q.nbytes), None, None
-        try:
-            if kk:
-                bufs += _device_buffers(state, 1, out.nbytes)
-                d_out = bufs[-1]
-            if counts:
-                bufs += _device_buffers(state, 1, cnt.nbytes)
-                d_counts = bufs[-1]
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], q.ctypes.data, q.nbytes), "copy to device")
-            _check(state.context, L.pt_query_nearest_k(state.context, bufs[0], n, kk, d_out, d_counts), "pt_query_nearest_k")
-            if kk:
-                _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, d_out, out.nbytes), "copy to host")
-            if counts:
-                _check(state.context, L.pt_copy_to_host(state.context, cnt.ctypes.data, d_counts, cnt.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    got = {key: np.ascontiguousarray(out[key]) for key in NEAREST_DTYPE.names}
+        _point_tensor("queryNearestK", state, points)
+        q = points
+    else:
+        q = _point_records("queryNearestK", points, max_radius)
+    out, cnt = _query(state, "pt_query_nearest_k", q, [((kk, 8), np.float32), ((), np.uint32) if counts else None], kk)
+    got = _columns(out, _NEAREST_COLUMNS)
     if counts:
         got["count"] = cnt
     return got
@@ -1139,34 +1101,18 @@ def queryWithinAny(state, points, radius=None):
     bool.  A torch tensor must be (n, 4) float32, contiguous and on the context's device; nothing is copied and the answer is a torch
     bool tensor on that device."""
     if _is_tensor(points):
-        import torch
-        L = _native.hip()
         if radius is not None:
             raise PathTracerError("queryWithinAny: a tensor carries its radii in the fourth column; radius must stay None")
-        n = _point_tensor("queryWithinAny", state, points)
-        with torch.cuda.device(points.device):
-            hit = torch.empty((n,), dtype=torch.uint8, device=points.device)
-            torch.cuda.current_stream().synchronize()
-        _check(state.context, L.pt_query_within_any(state.context, points.data_ptr() if n else None, n, hit.data_ptr() if n else None), "pt_query_within_any")
-        return hit != 0
-    p = np.asarray(points)
-    if p.ndim == 2 and p.shape[1] == 3 and radius is None:
-        raise PathTracerError("queryWithinAny: (n, 3) points need a radius")
-    if p.ndim == 2 and p.shape[1] == 4 and radius is not None:
-        raise PathTracerError("queryWithinAny: (n, 4) points carry their radii in the fourth column; radius must stay None")
-    q = _point_records("queryWithinAny", p, radius)
-    n = q.shape[0]
-    hit = np.zeros(n, np.uint8)
-    if n:
-        L = _native.hip()
-        bufs = _device_buffers(state, 2, q.nbytes)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], q.ctypes.data, q.nbytes), "copy to device")
-            _check(state.context, L.pt_query_within_any(state.context, bufs[0], n, bufs[1]), "pt_query_within_any")
-            _check(state.context, L.pt_copy_to_host(state.context, hit.ctypes.data, bufs[1], hit.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    return hit != 0
+        _point_tensor("queryWithinAny", state, points)
+        q = points
+    else:
+        p = np.asarray(points)
+        if p.ndim == 2 and p.shape[1] == 3 and radius is None:
+            raise PathTracerError("queryWithinAny: (n, 3) points need a radius")
+        if p.ndim == 2 and p.shape[1] == 4 and radius is not None:
+            raise PathTracerError("queryWithinAny: (n, 4) points carry their radii in the fourth column; radius must stay None")
+        q = _point_records("queryWithinAny", p, radius)
+    return _query(state, "pt_query_within_any", q, [((), np.uint8)])[0] != 0
 
 
 def _sphere_contact_args(centres, radius, max_contacts):
@@ -1218,24 +1164,6 @@ SEGMENT_HIT_DTYPE = np.dtype([("distance", np.float32), ("prim", np.uint32), ("s
 assert SEGMENT_HIT_DTYPE.itemsize == 32
 
 
-def _query_segments_tensor(state, segments):
-    import torch
-    if segments.device.type != "cuda" or segments.device.index != state._device:
-        raise PathTracerError("querySegments: the segments are on %s, the context is on cuda:%d" % (segments.device, state._device))
-    if segments.dtype != torch.float32:
-        raise PathTracerError("querySegments: the segments must be float32, got %s" % segments.dtype)
-    if segments.dim() != 2 or segments.shape[1] != 8:
-        raise PathTracerError("querySegments: expected an (n, 8) tensor {p0, max_radius, p1, ignored}, got shape %s" % (tuple(segments.shape),))
-    if not segments.is_contiguous():
-        raise PathTracerError("querySegments: the segments must be contiguous (nothing is copied)")
-    n = int(segments.shape[0])
-    with torch.cuda.device(segments.device):
-        out = torch.empty((n, 8), dtype=torch.float32, device=segments.device)
-        torch.cuda.current_stream().synchronize()      # the segments' producer and the allocation; the call below returns synchronised
-    _check(state.context, _native.hip().pt_query_segments(state.context, segments.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_segments")
-    return {"distance": out[:, 0], "prim": out[:, 1].view(torch.int32), "s": out[:, 2], "feature": out[:, 3], "point": out[:, 4:7], "material": out[:, 7].view(torch.int32)}
-
-
 def _segment_records(what, segments, max_radius):
     """(n, 8) float32 {p0, max_radius | p1, 0} from an (n, 6) array {p0, p1} and one radius, or the (n, 8) array itself"""
     g = np.asarray(segments)
@@ -1269,20 +1197,11 @@ def querySegments(state, segments, max_radius=float("inf")):
     and the answer is torch tensors on that device: views of one (n, 8) float32 tensor, prim and material as int32 (-1 on a miss).
     torch's current stream is synchronised before the call, and the call returns synchronised."""
     if _is_tensor(segments):
-        return _query_segments_tensor(state, segments)
-    q = _segment_records("querySegments", segments, max_radius)
-    n = q.shape[0]
-    out = np.zeros(n, SEGMENT_HIT_DTYPE)
-    if n:
-        L = _native.hip()
-        bufs = _device_buffers(state, 2, out.nbytes)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], q.ctypes.data, q.nbytes), "copy to device")
-            _check(state.context, L.pt_query_segments(state.context, bufs[0], n, bufs[1]), "pt_query_segments")
-            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    return {k: np.ascontiguousarray(out[k]) for k in SEGMENT_HIT_DTYPE.names}
+        _tensor_records("querySegments", state, segments, 8, "segments", " {p0, max_radius, p1, ignored}")
+        q = segments
+    else:
+        q = _segment_records("querySegments", segments, max_radius)
+    return _columns(_query(state, "pt_query_segments", q, [((8,), np.float32)])[0], _SEGMENT_COLUMNS)
 
 
 def capsuleClearance(state, p0, p1, radius):
@@ -1353,18 +1272,9 @@ def _overlap_boxes(what, centres, half_extents):
 
 
 def _overlap_tensor(what, state, boxes, half_extents):
-    import torch
     if half_extents is not None:
         raise PathTracerError("%s: a tensor is (n, 8) records that carry their half extents; half_extents must be None" % what)
-    if boxes.device.type != "cuda" or boxes.device.index != state._device:
-        raise PathTracerError("%s: the boxes are on %s, the context is on cuda:%d" % (what, boxes.device, state._device))
-    if boxes.dtype != torch.float32:
-        raise PathTracerError("%s: the boxes must be float32, got %s" % (what, boxes.dtype))
-    if boxes.dim() != 2 or boxes.shape[1] != 8:
-        raise PathTracerError("%s: expected an (n, 8) tensor {cx, cy, cz, hx, hy, hz, 0, 0}, got shape %s" % (what, tuple(boxes.shape)))
-    if not boxes.is_contiguous():
-        raise PathTracerError("%s: the boxes must be contiguous (nothing is copied)" % what)
-    return torch
+    return _tensor_records(what, state, boxes, 8, "boxes", " {cx, cy, cz, hx, hy, hz, 0, 0}")
 
 
 def queryOverlap(state, centres, half_extents=None, max_prims=8, counts=True):
@@ -1381,71 +1291,23 @@ def queryOverlap(state, centres, half_extents=None, max_prims=8, counts=True):
     straight in, and the answer is torch tensors on that device, prim and count as int32 (-1 past the last triangle).  torch's current
     stream is synchronised before the call, and the call returns synchronised."""
     k = _overlap_args("queryOverlap", max_prims, counts)
-    L = _native.hip()
     if _is_tensor(centres):
-        torch = _overlap_tensor("queryOverlap", state, centres, half_extents)
-        n = int(centres.shape[0])
-        with torch.cuda.device(centres.device):
-            out = torch.empty((n, k), dtype=torch.int32, device=centres.device)
-            cnt = torch.empty((n,), dtype=torch.int32, device=centres.device) if counts else None
-            torch.cuda.current_stream().synchronize()      # the boxes' producer and the allocations; the call below returns synchronised
-        _check(state.context, L.pt_query_overlap(state.context, centres.data_ptr() if n else None, n, k, out.data_ptr() if n and k else None,
-                                                 cnt.data_ptr() if n and counts else None), "pt_query_overlap")
-        got = {"prim": out}
-        if counts:
-            got["count"] = cnt
-        return got
-    b = _overlap_boxes("queryOverlap", centres, half_extents)
-    n = b.shape[0]
-    out = np.full((n, k), 0xFFFFFFFF, np.uint32)
-    cnt = np.zeros(n, np.uint32)
-    if n:
-        bufs, d_prims, d_counts = _device_buffers(state, 1, b.nbytes), None, None
-        try:
-            if k:
-                bufs += _device_buffers(state, 1, out.nbytes)
-                d_prims = bufs[-1]
-            if counts:
-                bufs += _device_buffers(state, 1, cnt.nbytes)
-                d_counts = bufs[-1]
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], b.ctypes.data, b.nbytes), "copy to device")
-            _check(state.context, L.pt_query_overlap(state.context, bufs[0], n, k, d_prims, d_counts), "pt_query_overlap")
-            if k:
-                _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, d_prims, out.nbytes), "copy to host")
-            if counts:
-                _check(state.context, L.pt_copy_to_host(state.context, cnt.ctypes.data, d_counts, cnt.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    got = {"prim": out}
-    if counts:
-        got["count"] = cnt
-    return got
+        _overlap_tensor("queryOverlap", state, centres, half_extents)
+        b = centres
+    else:
+        b = _overlap_boxes("queryOverlap", centres, half_extents)
+    return _list_or_counts(state, "pt_query_overlap", b, k, counts)
 
 
 def queryOverlapAny(state, centres, half_extents=None):
     """Does any triangle of the scene overlap each box (include/acgpt.h pt_query_overlap_any): queryOverlap's arguments, a bool array
     (n,), or a bool tensor for a tensor.  A box's walk ends at the first triangle it accepts."""
-    L = _native.hip()
     if _is_tensor(centres):
-        torch = _overlap_tensor("queryOverlapAny", state, centres, half_extents)
-        n = int(centres.shape[0])
-        with torch.cuda.device(centres.device):
-            out = torch.empty((n,), dtype=torch.uint8, device=centres.device)
-            torch.cuda.current_stream().synchronize()
-        _check(state.context, L.pt_query_overlap_any(state.context, centres.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_overlap_any")
-        return out.view(torch.bool)
-    b = _overlap_boxes("queryOverlapAny", centres, half_extents)
-    n = b.shape[0]
-    out = np.zeros(n, np.uint8)
-    if n:
-        bufs = _device_buffers(state, 2, b.nbytes)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], b.ctypes.data, b.nbytes), "copy to device")
-            _check(state.context, L.pt_query_overlap_any(state.context, bufs[0], n, bufs[1]), "pt_query_overlap_any")
-            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    return out.view(np.bool_)
+        _overlap_tensor("queryOverlapAny", state, centres, half_extents)
+        b = centres
+    else:
+        b = _overlap_boxes("queryOverlapAny", centres, half_extents)
+    return _as_bool(_query(state, "pt_query_overlap_any", b, [((), np.uint8)])[0])
 
 
 def _occupancy_frame(frame):
@@ -1535,16 +1397,7 @@ def _triangle_records(what, triangles):
 
 
 def _triangle_tensor(what, state, tris):
-    import torch
-    if tris.device.type != "cuda" or tris.device.index != state._device:
-        raise PathTracerError("%s: the triangles are on %s, the context is on cuda:%d" % (what, tris.device, state._device))
-    if tris.dtype != torch.float32:
-        raise PathTracerError("%s: the triangles must be float32, got %s" % (what, tris.dtype))
-    if tris.dim() != 2 or tris.shape[1] != 12:
-        raise PathTracerError("%s: expected an (n, 12) tensor {a0.xyz, 0, a1.xyz, 0, a2.xyz, 0}, got shape %s" % (what, tuple(tris.shape)))
-    if not tris.is_contiguous():
-        raise PathTracerError("%s: the triangles must be contiguous (nothing is copied)" % what)
-    return torch
+    return _tensor_records(what, state, tris, 12, "triangles", " {a0.xyz, 0, a1.xyz, 0, a2.xyz, 0}")
 
 
 def queryTriangles(state, triangles, max_prims=8, counts=True):
@@ -1561,71 +1414,23 @@ def queryTriangles(state, triangles, max_prims=8, counts=True):
     straight in, and the answer is torch tensors on that device, prim and count as int32 (-1 past the last triangle).  torch's current
     stream is synchronised before the call, and the call returns synchronised."""
     k = _overlap_args("queryTriangles", max_prims, counts)
-    L = _native.hip()
     if _is_tensor(triangles):
-        torch = _triangle_tensor("queryTriangles", state, triangles)
-        n = int(triangles.shape[0])
-        with torch.cuda.device(triangles.device):
-            out = torch.empty((n, k), dtype=torch.int32, device=triangles.device)
-            cnt = torch.empty((n,), dtype=torch.int32, device=triangles.device) if counts else None
-            torch.cuda.current_stream().synchronize()      # the triangles' producer and the allocations; the call below returns synchronised
-        _check(state.context, L.pt_query_triangles(state.context, triangles.data_ptr() if n else None, n, k, out.data_ptr() if n and k else None,
-                                                   cnt.data_ptr() if n and counts else None), "pt_query_triangles")
-        got = {"prim": out}
-        if counts:
-            got["count"] = cnt
-        return got
-    r = _triangle_records("queryTriangles", triangles)
-    n = r.shape[0]
-    out = np.full((n, k), 0xFFFFFFFF, np.uint32)
-    cnt = np.zeros(n, np.uint32)
-    if n:
-        bufs, d_prims, d_counts = _device_buffers(state, 1, r.nbytes), None, None
-        try:
-            if k:
-                bufs += _device_buffers(state, 1, out.nbytes)
-                d_prims = bufs[-1]
-            if counts:
-                bufs += _device_buffers(state, 1, cnt.nbytes)
-                d_counts = bufs[-1]
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], r.ctypes.data, r.nbytes), "copy to device")
-            _check(state.context, L.pt_query_triangles(state.context, bufs[0], n, k, d_prims, d_counts), "pt_query_triangles")
-            if k:
-                _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, d_prims, out.nbytes), "copy to host")
-            if counts:
-                _check(state.context, L.pt_copy_to_host(state.context, cnt.ctypes.data, d_counts, cnt.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    got = {"prim": out}
-    if counts:
-        got["count"] = cnt
-    return got
+        _triangle_tensor("queryTriangles", state, triangles)
+        r = triangles
+    else:
+        r = _triangle_records("queryTriangles", triangles)
+    return _list_or_counts(state, "pt_query_triangles", r, k, counts)
 
 
 def queryTrianglesAny(state, triangles):
     """Does any triangle of the scene intersect each triangle (include/acgpt.h pt_query_triangles_any): queryTriangles' argument, a bool
     array (n,), or a bool tensor for a tensor.  A query's walk ends at the first scene triangle it accepts."""
-    L = _native.hip()
     if _is_tensor(triangles):
-        torch = _triangle_tensor("queryTrianglesAny", state, triangles)
-        n = int(triangles.shape[0])
-        with torch.cuda.device(triangles.device):
-            out = torch.empty((n,), dtype=torch.uint8, device=triangles.device)
-            torch.cuda.current_stream().synchronize()
-        _check(state.context, L.pt_query_triangles_any(state.context, triangles.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_triangles_any")
-        return out.view(torch.bool)
-    r = _triangle_records("queryTrianglesAny", triangles)
-    n = r.shape[0]
-    out = np.zeros(n, np.uint8)
-    if n:
-        bufs = _device_buffers(state, 2, r.nbytes)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], r.ctypes.data, r.nbytes), "copy to device")
-            _check(state.context, L.pt_query_triangles_any(state.context, bufs[0], n, bufs[1]), "pt_query_triangles_any")
-            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    return out.view(np.bool_)
+        _triangle_tensor("queryTrianglesAny", state, triangles)
+        r = triangles
+    else:
+        r = _triangle_records("queryTrianglesAny", triangles)
+    return _as_bool(_query(state, "pt_query_triangles_any", r, [((), np.uint8)])[0])
 
 
 # ------------------------------------------------------------------ complete lists in CSR form ----
@@ -1643,7 +1448,6 @@ def _list_total(state, what, d_counts, n, d_offsets):
 
 def _query_lists(what, state, recs, count_call, lists_call):
     """The four steps on records that are an (n, w) float32 array or a device tensor: count, offsets, allocate, fill"""
-    L = _native.hip()
     if _is_tensor(recs):
         import torch
         n = int(recs.shape[0])
@@ -1662,24 +1466,15 @@ def _query_lists(what, state, recs, count_call, lists_call):
             return {"offsets": off.to(torch.int64) & 0xFFFFFFFF, "prim": prim, "count": cnt}
     n = recs.shape[0]
     cnt, off = np.zeros(n, np.uint32), np.zeros(n + 1, np.uint32)
-    prim = np.zeros(0, np.uint32)
-    if n:
-        bufs = _device_buffers(state, 1, recs.nbytes) + _device_buffers(state, 1, cnt.nbytes) + _device_buffers(state, 1, off.nbytes)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], recs.ctypes.data, recs.nbytes), "copy to device")
-            _check(state.context, count_call(state.context, bufs[0], n, 0, None, bufs[1]), what + " (counts)")
-            total = _list_total(state, what, bufs[1], n, bufs[2])
-            prim = np.zeros(total, np.uint32)
-            if total:
-                bufs += _device_buffers(state, 1, prim.nbytes)
-            _check(state.context, lists_call(state.context, bufs[0], n, bufs[2], bufs[3] if total else None, total, None), what)
-            _check(state.context, L.pt_copy_to_host(state.context, cnt.ctypes.data, bufs[1], cnt.nbytes), "copy to host")
-            _check(state.context, L.pt_copy_to_host(state.context, off.ctypes.data, bufs[2], off.nbytes), "copy to host")
-            if total:
-                _check(state.context, L.pt_copy_to_host(state.context, prim.ctypes.data, bufs[3], prim.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    return {"offsets": off, "prim": prim, "count": cnt}
+    got = {"offsets": off, "prim": np.zeros(0, np.uint32), "count": cnt}
+
+    def call(d_recs, d_cnt, d_off):
+        _check(state.context, count_call(state.context, d_recs, n, 0, None, d_cnt), what + " (counts)")
+        total = _list_total(state, what, d_cnt, n, d_off)
+        got["prim"] = np.zeros(total, np.uint32)      # allocated once the total is known, filled while the records and offsets are still up
+        _host_call(state, [], [got["prim"]], lambda d_prim: _check(state.context, lists_call(state.context, d_recs, n, d_off, d_prim, total, None), what))
+    _host_call(state, [recs], [cnt, off], call)
+    return got
 
 
 def queryOverlapLists(state, centres, half_extents=None):
@@ -1764,15 +1559,7 @@ def _oriented_records(what, state, boxes):
     array of anything np.asarray takes.  NumPy records whose axes are finite and not orthonormal to 2^-10 raise ValueError (on the
     device such a record is silently a miss, as a bad box is)."""
     if _is_tensor(boxes):
-        import torch
-        if boxes.device.type != "cuda" or boxes.device.index != state._device:
-            raise PathTracerError("%s: the boxes are on %s, the context is on cuda:%d" % (what, boxes.device, state._device))
-        if boxes.dtype != torch.float32:
-            raise PathTracerError("%s: the boxes must be float32, got %s" % (what, boxes.dtype))
-        if boxes.dim() != 2 or boxes.shape[1] != 16:
-            raise PathTracerError("%s: expected an (n, 16) tensor {m[0..11], hx, hy, hz, 0}, got shape %s" % (what, tuple(boxes.shape)))
-        if not boxes.is_contiguous():
-            raise PathTracerError("%s: the boxes must be contiguous (nothing is copied)" % what)
+        _tensor_records(what, state, boxes, 16, "boxes", " {m[0..11], hx, hy, hz, 0}")
         return boxes
     b = np.asarray(boxes)
     if b.dtype.kind not in "fiu":
@@ -1798,70 +1585,13 @@ def queryOverlapOriented(state, boxes, max_prims=8, counts=True):
     contiguous float32 (n, 16) tensor on the context's device goes in by data_ptr() without a copy and is answered with int32 tensors
     (-1 past the last triangle); there a record that is not orthonormal is a miss."""
     k = _overlap_args("queryOverlapOriented", max_prims, counts)
-    L = _native.hip()
-    recs = _oriented_records("queryOverlapOriented", state, boxes)
-    n = int(recs.shape[0])
-    if _is_tensor(recs):
-        import torch
-        with torch.cuda.device(recs.device):
-            out = torch.empty((n, k), dtype=torch.int32, device=recs.device)
-            cnt = torch.empty((n,), dtype=torch.int32, device=recs.device) if counts else None
-            torch.cuda.current_stream().synchronize()      # the boxes' producer and the allocations; the call below returns synchronised
-        _check(state.context, L.pt_query_overlap_oriented(state.context, recs.data_ptr() if n else None, n, k, out.data_ptr() if n and k else None,
-                                                          cnt.data_ptr() if n and counts else None), "pt_query_overlap_oriented")
-        got = {"prim": out}
-        if counts:
-            got["count"] = cnt
-        return got
-    out = np.full((n, k), 0xFFFFFFFF, np.uint32)
-    cnt = np.zeros(n, np.uint32)
-    if n:
-        bufs, d_prims, d_counts = _device_buffers(state, 1, recs.nbytes), None, None
-        try:
-            if k:
-                bufs += _device_buffers(state, 1, out.nbytes)
-                d_prims = bufs[-1]
-            if counts:
-                bufs += _device_buffers(state, 1, cnt.nbytes)
-                d_counts = bufs[-1]
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], recs.ctypes.data, recs.nbytes), "copy to device")
-            _check(state.context, L.pt_query_overlap_oriented(state.context, bufs[0], n, k, d_prims, d_counts), "pt_query_overlap_oriented")
-            if k:
-                _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, d_prims, out.nbytes), "copy to host")
-            if counts:
-                _check(state.context, L.pt_copy_to_host(state.context, cnt.ctypes.data, d_counts, cnt.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    got = {"prim": out}
-    if counts:
-        got["count"] = cnt
-    return got
+    return _list_or_counts(state, "pt_query_overlap_oriented", _oriented_records("queryOverlapOriented", state, boxes), k, counts)
 
 
 def queryOverlapOrientedAny(state, boxes):
     """Does any triangle of the scene overlap each oriented box (include/acgpt.h pt_query_overlap_oriented_any): queryOverlapOriented's
     records, a bool array (n,), or a bool tensor for a tensor.  A box's walk ends at the first triangle it accepts."""
-    L = _native.hip()
-    recs = _oriented_records("queryOverlapOrientedAny", state, boxes)
-    n = int(recs.shape[0])
-    if _is_tensor(recs):
-        import torch
-        with torch.cuda.device(recs.device):
-            out = torch.empty((n,), dtype=torch.uint8, device=recs.device)
-            torch.cuda.current_stream().synchronize()
-        _check(state.context, L.pt_query_overlap_oriented_any(state.context, recs.data_ptr() if n else None, n, out.data_ptr() if n else None),
-               "pt_query_overlap_oriented_any")
-        return out.view(torch.bool)
-    out = np.zeros(n, np.uint8)
-    if n:
-        bufs = _device_buffers(state, 1, recs.nbytes) + _device_buffers(state, 1, n)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], recs.ctypes.data, recs.nbytes), "copy to device")
-            _check(state.context, L.pt_query_overlap_oriented_any(state.context, bufs[0], n, bufs[1]), "pt_query_overlap_oriented_any")
-            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    return out.view(np.bool_)
+    return _as_bool(_query(state, "pt_query_overlap_oriented_any", _oriented_records("queryOverlapOrientedAny", state, boxes), [((), np.uint8)])[0])
 
 
 def queryOverlapOrientedLists(state, boxes):
@@ -1894,28 +1624,9 @@ def poseBoxes(state, poses, lo, hi):
     under each pose.  Record p is pose p with its translation replaced by the posed centre of [lo, hi], then the half extent: what
     queryOverlapOriented* take.  Poses: queryPosesAny's forms; an (P, 16) float32 array for arrays, a tensor on the device for a tensor,
     which is not copied."""
-    L = _native.hip()
     lb = _local_box("poseBoxes", lo, hi)
     recs = _pose_records("poseBoxes", state, poses)
-    P = int(recs.shape[0])
-    p_lb = lb.ctypes.data_as(C.POINTER(C.c_float))
-    if _is_tensor(recs):
-        import torch
-        with torch.cuda.device(recs.device):
-            out = torch.empty((P, 16), dtype=torch.float32, device=recs.device)
-            torch.cuda.current_stream().synchronize()
-        _check(state.context, L.pt_pose_boxes(state.context, recs.data_ptr() if P else None, P, p_lb, out.data_ptr() if P else None), "pt_pose_boxes")
-        return out
-    out = np.zeros((P, 16), np.float32)
-    if P:
-        bufs = _device_buffers(state, 1, recs.nbytes) + _device_buffers(state, 1, out.nbytes)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], recs.ctypes.data, recs.nbytes), "copy to device")
-            _check(state.context, L.pt_pose_boxes(state.context, bufs[0], P, p_lb, bufs[1]), "pt_pose_boxes")
-            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    return out
+    return _query(state, "pt_pose_boxes", recs, [((16,), np.float32)], lb.ctypes.data_as(C.POINTER(C.c_float)))[0]
 
 
 def posedMeshBoxPad(vertices, max_translation):
@@ -2081,30 +1792,14 @@ def queryTriangleDistance(state, triangles, max_radius=float("inf")):
     A torch tensor must be (n, 12) float32 records, contiguous and on the context's device; nothing is copied, its data_ptr() goes
     straight in, and the answer is torch tensors on that device: views of one (n, 12) float32 tensor, prim and material as int32 (-1
     on a miss).  torch's current stream is synchronised before the call, and the call returns synchronised."""
-    L = _native.hip()
     if _is_tensor(triangles):
-        torch = _triangle_tensor("queryTriangleDistance", state, triangles)
-        n = int(triangles.shape[0])
-        with torch.cuda.device(triangles.device):
-            out = torch.empty((n, 12), dtype=torch.float32, device=triangles.device)
-            torch.cuda.current_stream().synchronize()      # the triangles' producer and the allocation; the call below returns synchronised
-        _check(state.context, L.pt_query_triangle_distance(state.context, triangles.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_triangle_distance")
-        return {"distance": out[:, 0], "prim": out[:, 1].view(torch.int32), "feature": out[:, 2], "material": out[:, 3].view(torch.int32), "on_query": out[:, 4:7],
-                "point": out[:, 8:11]}
-    r = _triangle_records("queryTriangleDistance", triangles)
-    if np.asarray(triangles).shape[-1] != 12:
-        r[:, 3] = _checked_radius("queryTriangleDistance", max_radius)
-    n = r.shape[0]
-    out = np.zeros(n, TRIANGLE_DISTANCE_DTYPE)
-    if n:
-        bufs = _device_buffers(state, 2, out.nbytes)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], r.ctypes.data, r.nbytes), "copy to device")
-            _check(state.context, L.pt_query_triangle_distance(state.context, bufs[0], n, bufs[1]), "pt_query_triangle_distance")
-            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    return {k: np.ascontiguousarray(out[k]) for k in ("distance", "prim", "feature", "material", "on_query", "point")}
+        _triangle_tensor("queryTriangleDistance", state, triangles)
+        r = triangles
+    else:
+        r = _triangle_records("queryTriangleDistance", triangles)
+        if np.asarray(triangles).shape[-1] != 12:
+            r[:, 3] = _checked_radius("queryTriangleDistance", max_radius)
+    return _columns(_query(state, "pt_query_triangle_distance", r, [((12,), np.float32)])[0], _TRIANGLE_DISTANCE_COLUMNS)
 
 
 def meshClearance(state, vertices, indices, poses=None, max_radius=float("inf")):
@@ -2215,7 +1910,6 @@ def _pose_call(what, state, poses, outs, call, limit):
     P = int(recs.shape[0])
     T = getQueryMesh(state)["triangles"] if P or state.context else 0
     step = max(1, int(limit) // max(T, 1))
-    L = _native.hip()
     if _is_tensor(recs):
         import torch
         with torch.cuda.device(recs.device):
@@ -2226,23 +1920,11 @@ def _pose_call(what, state, poses, outs, call, limit):
             call(recs.data_ptr() + 48 * s, n, [None if g is None else g.data_ptr() + s * g[0].numel() * g.element_size() for g in got])
         return got
     got = [None if o is None else np.zeros((P,) + tuple(o[0](T)), o[1]) for o in outs]
-    if P:
-        bufs = _device_buffers(state, 1, recs.nbytes)
-        try:
-            ptrs = []
-            for g in got:
-                if g is not None and g.nbytes:
-                    bufs += _device_buffers(state, 1, g.nbytes)
-                ptrs.append(bufs[-1] if g is not None and g.nbytes else None)
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], recs.ctypes.data, recs.nbytes), "copy to device")
-            for s in range(0, P, step):
-                n = min(P, s + step) - s
-                call(bufs[0] + 48 * s, n, [None if d is None else d + s * (g.nbytes // P) for d, g in zip(ptrs, got)])
-            for d, g in zip(ptrs, got):
-                if d is not None:
-                    _check(state.context, L.pt_copy_to_host(state.context, g.ctypes.data, d, g.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
+
+    def slices(d_poses, *d_outs):
+        for s in range(0, P, step):
+            call(d_poses + 48 * s, min(P, s + step) - s, [None if d is None else d + s * (g.nbytes // P) for d, g in zip(d_outs, got)])
+    _host_call(state, [recs], got, slices)
     return got
 
 
@@ -2340,18 +2022,9 @@ def _sweep_records(origins_or_sweeps, directions, radius, tmax):
 
 
 def _sweep_tensor(state, sweeps, directions, radius):
-    import torch
     if directions is not None or radius is not None:
         raise PathTracerError("querySweep: a tensor holds whole records (n, 8) {o, d, radius, tmax}; directions and radius go with arrays")
-    if sweeps.device.type != "cuda" or sweeps.device.index != state._device:
-        raise PathTracerError("querySweep: the sweeps are on %s, the context is on cuda:%d" % (sweeps.device, state._device))
-    if sweeps.dtype != torch.float32:
-        raise PathTracerError("querySweep: the sweeps must be float32, got %s" % sweeps.dtype)
-    if sweeps.dim() != 2 or sweeps.shape[1] != 8:
-        raise PathTracerError("querySweep: expected an (n, 8) tensor {o, d, radius, tmax}, got shape %s" % (tuple(sweeps.shape),))
-    if not sweeps.is_contiguous():
-        raise PathTracerError("querySweep: the sweeps must be contiguous (nothing is copied)")
-    return torch
+    return _tensor_records("querySweep", state, sweeps, 8, "sweeps", " {o, d, radius, tmax}")
 
 
 def querySweep(state, origins_or_sweeps, directions=None, radius=None, tmax=float("inf"), any_hit=False):
@@ -2366,36 +2039,12 @@ def querySweep(state, origins_or_sweeps, directions=None, radius=None, tmax=floa
     A torch tensor must be (n, 8) float32, contiguous and on the context's device; nothing is copied, its data_ptr() goes straight in, and
     the answer is torch tensors on that device: views of one (n, 8) float32 tensor, prim and material as int32 (-1 on a miss), or a bool
     tensor with any_hit.  torch's current stream is synchronised before the call, and the call returns synchronised."""
-    L = _native.hip()
     if _is_tensor(origins_or_sweeps):
-        x = origins_or_sweeps
-        torch = _sweep_tensor(state, x, directions, radius)
-        n = int(x.shape[0])
-        with torch.cuda.device(x.device):
-            out = torch.empty((n,), dtype=torch.uint8, device=x.device) if any_hit else torch.empty((n, 8), dtype=torch.float32, device=x.device)
-            torch.cuda.current_stream().synchronize()      # the sweeps' producer and the allocation; the call below returns synchronised
-        if any_hit:
-            _check(state.context, L.pt_query_sweep_any(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_sweep_any")
-            return out.view(torch.bool)
-        _check(state.context, L.pt_query_sweep(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_sweep")
-        return {"t": out[:, 0], "prim": out[:, 1].view(torch.int32), "u": out[:, 2], "v": out[:, 3], "point": out[:, 4:7], "material": out[:, 7].view(torch.int32)}
-    s = _sweep_records(origins_or_sweeps, directions, radius, tmax)
-    n = s.shape[0]
-    out = np.zeros(n, np.uint8) if any_hit else np.zeros(n, SWEEP_DTYPE)
-    if n:
-        bufs = _device_buffers(state, 2, s.nbytes)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], s.ctypes.data, s.nbytes), "copy to device")
-            if any_hit:
-                _check(state.context, L.pt_query_sweep_any(state.context, bufs[0], n, bufs[1]), "pt_query_sweep_any")
-            else:
-                _check(state.context, L.pt_query_sweep(state.context, bufs[0], n, bufs[1]), "pt_query_sweep")
-            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    if any_hit:
-        return out.view(np.bool_)
-    return {k: np.ascontiguousarray(out[k]) for k in SWEEP_DTYPE.names}
+        _sweep_tensor(state, origins_or_sweeps, directions, radius)
+        s = origins_or_sweeps
+    else:
+        s = _sweep_records(origins_or_sweeps, directions, radius, tmax)
+    return _records_or_hit(state, s, any_hit, "pt_query_sweep", "pt_query_sweep_any", 8, _SWEEP_COLUMNS)
 
 
 def sweepContacts(result, sweeps):
@@ -2467,18 +2116,9 @@ def _capsule_records(casts_or_p0, p1, directions, radius, tmax):
 
 
 def _capsule_tensor(state, casts, p1, directions, radius):
-    import torch
     if p1 is not None or directions is not None or radius is not None:
         raise PathTracerError("queryCapsuleCast: a tensor holds whole records (n, 12) {p0, radius, p1, tmax, d, ignored}; p1, directions and radius go with arrays")
-    if casts.device.type != "cuda" or casts.device.index != state._device:
-        raise PathTracerError("queryCapsuleCast: the casts are on %s, the context is on cuda:%d" % (casts.device, state._device))
-    if casts.dtype != torch.float32:
-        raise PathTracerError("queryCapsuleCast: the casts must be float32, got %s" % casts.dtype)
-    if casts.dim() != 2 or casts.shape[1] != 12:
-        raise PathTracerError("queryCapsuleCast: expected an (n, 12) tensor {p0, radius, p1, tmax, d, ignored}, got shape %s" % (tuple(casts.shape),))
-    if not casts.is_contiguous():
-        raise PathTracerError("queryCapsuleCast: the casts must be contiguous (nothing is copied)")
-    return torch
+    return _tensor_records("queryCapsuleCast", state, casts, 12, "casts", " {p0, radius, p1, tmax, d, ignored}")
 
 
 def queryCapsuleCast(state, casts_or_p0, p1=None, directions=None, radius=None, tmax=float("inf"), any_hit=False):
@@ -2495,36 +2135,11 @@ def queryCapsuleCast(state, casts_or_p0, p1=None, directions=None, radius=None, 
     and the answer is torch tensors on that device: views of one (n, 8) float32 tensor, prim and material as int32 (-1 on a miss), or a
     bool tensor with any_hit.  torch's current stream is synchronised before the call, and the call returns synchronised."""
     if _is_tensor(casts_or_p0):
-        x = casts_or_p0
-        torch = _capsule_tensor(state, x, p1, directions, radius)
-        L = _native.hip()
-        n = int(x.shape[0])
-        with torch.cuda.device(x.device):
-            out = torch.empty((n,), dtype=torch.uint8, device=x.device) if any_hit else torch.empty((n, 8), dtype=torch.float32, device=x.device)
-            torch.cuda.current_stream().synchronize()      # the casts' producer and the allocation; the call below returns synchronised
-        if any_hit:
-            _check(state.context, L.pt_query_capsule_cast_any(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_capsule_cast_any")
-            return out.view(torch.bool)
-        _check(state.context, L.pt_query_capsule_cast(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_capsule_cast")
-        return {"t": out[:, 0], "prim": out[:, 1].view(torch.int32), "s": out[:, 2], "feature": out[:, 3], "point": out[:, 4:7], "material": out[:, 7].view(torch.int32)}
-    s = _capsule_records(casts_or_p0, p1, directions, radius, tmax)
-    L = _native.hip()
-    n = s.shape[0]
-    out = np.zeros(n, np.uint8) if any_hit else np.zeros(n, CAPSULE_CAST_DTYPE)
-    if n:
-        bufs = _device_buffers(state, 2, s.nbytes)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], s.ctypes.data, s.nbytes), "copy to device")
-            if any_hit:
-                _check(state.context, L.pt_query_capsule_cast_any(state.context, bufs[0], n, bufs[1]), "pt_query_capsule_cast_any")
-            else:
-                _check(state.context, L.pt_query_capsule_cast(state.context, bufs[0], n, bufs[1]), "pt_query_capsule_cast")
-            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    if any_hit:
-        return out.view(np.bool_)
-    return {k: np.ascontiguousarray(out[k]) for k in CAPSULE_CAST_DTYPE.names}
+        _capsule_tensor(state, casts_or_p0, p1, directions, radius)
+        s = casts_or_p0
+    else:
+        s = _capsule_records(casts_or_p0, p1, directions, radius, tmax)
+    return _records_or_hit(state, s, any_hit, "pt_query_capsule_cast", "pt_query_capsule_cast_any", 8, _CAPSULE_CAST_COLUMNS)
 
 
 def capsuleContacts(result, casts):
@@ -2594,19 +2209,10 @@ def _box_cast_records(casts_or_boxes, directions, tmax):
 
 
 def _box_cast_tensor(state, casts, directions):
-    import torch
     what = "queryBoxCast"
     if directions is not None:
         raise PathTracerError("%s: a tensor holds whole records (n, 20) {m[0..11], hx, hy, hz, 0, d, tmax}; directions go with arrays" % what)
-    if casts.device.type != "cuda" or casts.device.index != state._device:
-        raise PathTracerError("%s: the casts are on %s, the context is on cuda:%d" % (what, casts.device, state._device))
-    if casts.dtype != torch.float32:
-        raise PathTracerError("%s: the casts must be float32, got %s" % (what, casts.dtype))
-    if casts.dim() != 2 or casts.shape[1] != 20:
-        raise PathTracerError("%s: expected an (n, 20) tensor {m[0..11], hx, hy, hz, 0, d, tmax}, got shape %s" % (what, tuple(casts.shape)))
-    if not casts.is_contiguous():
-        raise PathTracerError("%s: the casts must be contiguous (nothing is copied)" % what)
-    return torch
+    return _tensor_records(what, state, casts, 20, "casts", " {m[0..11], hx, hy, hz, 0, d, tmax}")
 
 
 def queryBoxCast(state, casts_or_boxes, directions=None, tmax=float("inf"), any_hit=False):
@@ -2624,36 +2230,11 @@ def queryBoxCast(state, casts_or_boxes, directions=None, tmax=float("inf"), any_
     and the answer is torch tensors on that device: views of one (n, 12) float32 tensor, prim and material as int32 (-1 on a miss), or a
     bool tensor with any_hit.  torch's current stream is synchronised before the call, and the call returns synchronised."""
     if _is_tensor(casts_or_boxes):
-        x = casts_or_boxes
-        torch = _box_cast_tensor(state, x, directions)
-        L = _native.hip()
-        n = int(x.shape[0])
-        with torch.cuda.device(x.device):
-            out = torch.empty((n,), dtype=torch.uint8, device=x.device) if any_hit else torch.empty((n, 12), dtype=torch.float32, device=x.device)
-            torch.cuda.current_stream().synchronize()      # the casts' producer and the allocation; the call below returns synchronised
-        if any_hit:
-            _check(state.context, L.pt_query_box_cast_any(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_box_cast_any")
-            return out.view(torch.bool)
-        _check(state.context, L.pt_query_box_cast(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_box_cast")
-        return {"t": out[:, 0], "prim": out[:, 1].view(torch.int32), "feature": out[:, 2], "material": out[:, 3].view(torch.int32), "normal": out[:, 4:7], "point": out[:, 8:11]}
-    s = _box_cast_records(casts_or_boxes, directions, tmax)
-    n = s.shape[0]
-    out = np.zeros(n, np.uint8) if any_hit else np.zeros(n, BOX_CAST_DTYPE)
-    if n:
-        L = _native.hip()
-        bufs = _device_buffers(state, 2, s.nbytes)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], s.ctypes.data, s.nbytes), "copy to device")
-            if any_hit:
-                _check(state.context, L.pt_query_box_cast_any(state.context, bufs[0], n, bufs[1]), "pt_query_box_cast_any")
-            else:
-                _check(state.context, L.pt_query_box_cast(state.context, bufs[0], n, bufs[1]), "pt_query_box_cast")
-            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    if any_hit:
-        return out.view(np.bool_)
-    return {k: np.ascontiguousarray(out[k]) for k in ("t", "prim", "feature", "material", "normal", "point")}
+        _box_cast_tensor(state, casts_or_boxes, directions)
+        s = casts_or_boxes
+    else:
+        s = _box_cast_records(casts_or_boxes, directions, tmax)
+    return _records_or_hit(state, s, any_hit, "pt_query_box_cast", "pt_query_box_cast_any", 12, _BOX_CAST_COLUMNS)
 
 
 def boxCastContacts(result, casts):
@@ -2701,7 +2282,8 @@ def poseBoxCasts(state, poses, local_box, motions):
     if _is_tensor(poses):
         if not _is_tensor(motions):
             raise PathTracerError("poseBoxCasts: tensor poses take a (P, 4) tensor of motions")
-        torch = _cast_tensor("poseBoxCasts", state, motions, 4, "motions")
+        import torch
+        _cast_tensor("poseBoxCasts", state, motions, 4, "motions")
         boxes = poseBoxes(state, poses, lo, hi)
         if int(motions.shape[0]) != int(boxes.shape[0]):
             raise PathTracerError("poseBoxCasts: %d poses and %d motions" % (int(boxes.shape[0]), int(motions.shape[0])))
@@ -2752,24 +2334,7 @@ def _cast_records(what, casts, directions, tmax):
 
 
 def _cast_tensor(what, state, x, width, name):
-    import torch
-    if x.device.type != "cuda" or x.device.index != state._device:
-        raise PathTracerError("%s: the %s are on %s, the context is on cuda:%d" % (what, name, x.device, state._device))
-    if x.dtype != torch.float32:
-        raise PathTracerError("%s: the %s must be float32, got %s" % (what, name, x.dtype))
-    if x.dim() != 2 or x.shape[1] != width:
-        raise PathTracerError("%s: expected an (n, %d) tensor of %s, got shape %s" % (what, width, name, tuple(x.shape)))
-    if not x.is_contiguous():
-        raise PathTracerError("%s: the %s must be contiguous (nothing is copied)" % (what, name))
-    return torch
-
-
-def _cast_columns(out):
-    if _is_tensor(out):
-        import torch
-        return {"t": out[:, 0], "prim": out[:, 1].view(torch.int32), "feature": out[:, 2], "query_triangle": out[:, 3].view(torch.int32), "point": out[:, 4:7],
-                "material": out[:, 7].view(torch.int32)}
-    return {k: np.ascontiguousarray(out[k]) for k in TRIANGLE_CAST_DTYPE.names}
+    return _tensor_records(what, state, x, width, name, " of " + name)
 
 
 def queryTriangleCast(state, casts_or_triangles, directions=None, tmax=float("inf"), any_hit=False):
@@ -2787,36 +2352,14 @@ def queryTriangleCast(state, casts_or_triangles, directions=None, tmax=float("in
     and the answer is torch tensors on that device: views of one (n, 8) float32 tensor, prim, query_triangle and material as int32
     (-1 on a miss), or a bool tensor with any_hit.  torch's current stream is synchronised before the call, and the call returns
     synchronised."""
-    L = _native.hip()
     if _is_tensor(casts_or_triangles):
-        x = casts_or_triangles
         if directions is not None:
             raise PathTracerError("queryTriangleCast: a tensor holds whole records (n, 16); directions go with arrays")
-        torch = _cast_tensor("queryTriangleCast", state, x, 16, "casts")
-        n = int(x.shape[0])
-        with torch.cuda.device(x.device):
-            out = torch.empty((n,), dtype=torch.uint8, device=x.device) if any_hit else torch.empty((n, 8), dtype=torch.float32, device=x.device)
-            torch.cuda.current_stream().synchronize()      # the casts' producer and the allocation; the call below returns synchronised
-        if any_hit:
-            _check(state.context, L.pt_query_triangle_cast_any(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_triangle_cast_any")
-            return out.view(torch.bool)
-        _check(state.context, L.pt_query_triangle_cast(state.context, x.data_ptr() if n else None, n, out.data_ptr() if n else None), "pt_query_triangle_cast")
-        return _cast_columns(out)
-    s = _cast_records("queryTriangleCast", casts_or_triangles, directions, tmax)
-    n = s.shape[0]
-    out = np.zeros(n, np.uint8) if any_hit else np.zeros(n, TRIANGLE_CAST_DTYPE)
-    if n:
-        bufs = _device_buffers(state, 2, s.nbytes)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], s.ctypes.data, s.nbytes), "copy to device")
-            if any_hit:
-                _check(state.context, L.pt_query_triangle_cast_any(state.context, bufs[0], n, bufs[1]), "pt_query_triangle_cast_any")
-            else:
-                _check(state.context, L.pt_query_triangle_cast(state.context, bufs[0], n, bufs[1]), "pt_query_triangle_cast")
-            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[1], out.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    return out.view(np.bool_) if any_hit else _cast_columns(out)
+        _cast_tensor("queryTriangleCast", state, casts_or_triangles, 16, "casts")
+        s = casts_or_triangles
+    else:
+        s = _cast_records("queryTriangleCast", casts_or_triangles, directions, tmax)
+    return _records_or_hit(state, s, any_hit, "pt_query_triangle_cast", "pt_query_triangle_cast_any", 8, _TRIANGLE_CAST_COLUMNS)
 
 
 def _motion_records(what, motions, P):
@@ -2835,33 +2378,23 @@ def queryPosesCast(state, poses, motions):
     first (the smallest t, ties to the lowest index; 0xFFFFFFFF, or -1 in a tensor, where nothing is touched).  The P x T posed
     triangles are formed in registers.  Poses as queryPosesAny takes them; with a poses tensor the motions are a (P, 4) float32 tensor on
     the same device, and the answer is tensors."""
-    L = _native.hip()
     recs = _pose_records("queryPosesCast", state, poses)
     P = int(recs.shape[0])
+    fn = _native.hip().pt_query_poses_cast
+
+    def call(d_poses, d_motions, d_out):
+        _check(state.context, fn(state.context, d_poses, d_motions, P, d_out), "pt_query_poses_cast")
     if _is_tensor(recs):
         if not _is_tensor(motions):
             raise PathTracerError("queryPosesCast: tensor poses take a (P, 4) tensor of motions")
-        torch = _cast_tensor("queryPosesCast", state, motions, 4, "motions")
+        _cast_tensor("queryPosesCast", state, motions, 4, "motions")
         if int(motions.shape[0]) != P:
             raise PathTracerError("queryPosesCast: %d poses and %d motions" % (P, int(motions.shape[0])))
-        with torch.cuda.device(recs.device):
-            out = torch.empty((P, 8), dtype=torch.float32, device=recs.device)
-            torch.cuda.current_stream().synchronize()
-        _check(state.context, L.pt_query_poses_cast(state.context, recs.data_ptr() if P else None, motions.data_ptr() if P else None, P, out.data_ptr() if P else None),
-               "pt_query_poses_cast")
-        return _cast_columns(out)
-    m = _motion_records("queryPosesCast", motions, P)
-    out = np.zeros(P, TRIANGLE_CAST_DTYPE)
-    if P:
-        bufs = _device_buffers(state, 3, recs.nbytes)
-        try:
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[0], recs.ctypes.data, recs.nbytes), "copy to device")
-            _check(state.context, L.pt_copy_to_device(state.context, bufs[1], m.ctypes.data, m.nbytes), "copy to device")
-            _check(state.context, L.pt_query_poses_cast(state.context, bufs[0], bufs[1], P, bufs[2]), "pt_query_poses_cast")
-            _check(state.context, L.pt_copy_to_host(state.context, out.ctypes.data, bufs[2], out.nbytes), "copy to host")
-        finally:
-            _free_device_buffers(state, bufs)
-    return _cast_columns(out)
+        out = _tensor_call(recs, [((P, 8), "float32")], lambda d_poses, d_out: call(d_poses, motions.data_ptr() if P else None, d_out))[0]
+    else:
+        out = np.zeros((P, 8), np.float32)
+        _host_call(state, [recs, _motion_records("queryPosesCast", motions, P)], [out], call)
+    return _columns(out, _TRIANGLE_CAST_COLUMNS)
 
 
 def meshCast(state, vertices, indices, poses, motions):
@@ -2892,7 +2425,7 @@ def meshCast(state, vertices, indices, poses, motions):
         for k in ("t", "prim", "feature", "point", "material"):
             out[k][found] = got[k][row][found]
         out["query_triangle"][found] = tri[found]
-    return _cast_columns(out)
+    return _columns(out.view(np.float32).reshape(P, 8), _TRIANGLE_CAST_COLUMNS)
 
 
 def castContacts(result, casts, vertices, indices):
