@@ -34,6 +34,7 @@
 #include "render_common.h"
 #include "render_small.h"
 #include "small_ref.h"
+#include "small_slab.h"
 
 namespace ptd {
 
@@ -60,8 +61,8 @@ __device__ __forceinline__ void small_node(const char* p, uint4& a, uint4& b)
 // ---- kSmallNodesFloatLds: the nodes as fp32 ----
 // Each 16-byte half of an HNode {cx | hx << 16, cy | hy << 16, cz | hz << 16, child} becomes two 16-byte records,
 // {(float)cx, (float)cy, (float)cz, child in the local form of small_ref.h} and {(float)hx, (float)hy, (float)hz, 0}: a node is 64
-// bytes, at node << 2 from the same 16-bit reference.  The conversion is exact, so fma((float)h, mul, add) on the staged float is
-// the fma slab_hc does on the half.  The one staging code of the kernel and of pt_debug_small_staged.
+// bytes, at node << 2 from the same 16-bit reference.  The conversion is exact, so a v_fma_f32 on the staged float gives the bits
+// of the v_fma_mix_f32 on the half (slab_hcf_f32 / slab_hcf, small_slab.h).  The one staging code of the kernel and of pt_debug_small_staged.
 __device__ __forceinline__ void small_stage_f32(uint4* dst, const uint4* src, uint32_t n_halves, uint32_t first, uint32_t stride)
 {
     for (uint32_t i = first; i < n_halves; i += stride) {
@@ -79,14 +80,7 @@ __device__ __forceinline__ void small_node_f32(const char* p, uint4& ca, uint4& 
     ca = make_uint4(v0.x, v0.y, v0.z, v0.w); ha = make_uint4(v1.x, v1.y, v1.z, v1.w);
     cb = make_uint4(v2.x, v2.y, v2.z, v2.w); hb = make_uint4(v3.x, v3.y, v3.z, v3.w);
 }
-// slab_hc (pt_device.h) on the staged floats, operation for operation: the conservativeness proof (pt_selftest op 19) is of this formula
-__device__ __forceinline__ void slab_hc_f32(const uint4& c, const uint4& h, const f3& mul, const f3& add, float rtmin, float& tn, float& tf)
-{
-    const float cx = __builtin_fmaf(__uint_as_float(c.x), mul.x, add.x), cy = __builtin_fmaf(__uint_as_float(c.y), mul.y, add.y), cz = __builtin_fmaf(__uint_as_float(c.z), mul.z, add.z);
-    const float ex = __builtin_fmaf(__uint_as_float(h.x), fabsf(mul.x), 0.0f), ey = __builtin_fmaf(__uint_as_float(h.y), fabsf(mul.y), 0.0f), ez = __builtin_fmaf(__uint_as_float(h.z), fabsf(mul.z), 0.0f);
-    tn = fmaxf(fmaxf(cx - ex, cy - ey), fmaxf(cz - ez, rtmin));
-    tf = fminf(fminf(cx + ex, cy + ey), cz + ez) * kFarWiden;
-}
+// the box test on these records is slab_hcf_f32 (small_slab.h)
 
 #include "render_small.inc"
 

@@ -1,7 +1,13 @@
 // render_small.inc — the body of k_render_small (render_small.hip): render_pw.inc at NODE_FMT 14, INNER 6, LEAVES 2, SHADE_K 40,
 // LEAF_K 16, light mode 0, no environment map, the reference material model — every other format and every experiment branch
-// taken out.  Per lane the operations and their order are those of k_render_pw<40,16,11,256,5,false,0,6,2,false,0,0,MATH>: same
-// image bits, same counters.  What differs is where things live:
+// taken out.  Everything that is under the bit-exact contract is k_render_pw<40,16,11,256,5,false,0,6,2,false,0,0,MATH>'s, operation
+// for operation: ray setup, tri_test_lazy, the (t, prim) tie rule, shading, accumulation.  The box test is not under that contract
+// and is not variant 7's: slab_hcf / slab_hcf_f32 (small_slab.h) form near and far with one fma each where slab_hc rounds the half
+// extent's product first.  A box test only decides which leaves a ray reaches; a hit is decided by tri_test_lazy alone, the closest
+// by (t, prim) whatever the order the leaves come in, a shadow ray by any hit, and the counters count rays and paths, not visits.
+// So any conservative box test leaves image bits and counters where they are: same image bits, same counters as variant 7, while
+// the order in which two children with nearly equal entry distances are walked may differ from variant 7's.  What else differs is
+// where things live:
 //   * the fp16 nodes are read from a copy in LDS that the workgroup stages once (ds_read_b128), child words rewritten to the
 //     16-bit local form of small_ref.h; the texture path sees the triangle records only;
 //   * stack entries are 16 bits, entry-major, lane-minor, two lanes to a dword (ds_write_b16 / ds_read_i16);
@@ -10,13 +16,24 @@
 // fold books (waves x kBookDwords x 4 B) — small_lds_bytes() in render_small.hip.
 // NODES (render_small.h) says where the nodes are.  kSmallNodesHalfLds is the above.  kSmallNodesFloatLds: the copy holds every fp16
 // number as the float it converts to (small_stage_f32: n_lds_nodes x 64 B, a node at node << 2), a visit is four ds_read_b128 and
-// slab_hc_f32, whose twelve v_fma_f32 give the bits of slab_hc's twelve v_fma_mix_f32 at full rate.  kSmallNodesHalfGlobal: no copy;
+// two slab_hcf_f32: eighteen full-rate v_fma_f32, the bits of slab_hcf's eighteen v_fma_mix_f32.  kSmallNodesHalfGlobal: no copy;
 // a visit reads the fp16 node from sc.hcnodes as variant 7 does and halves an inner child's byte offset on the way to the stack.
+// The loop shape can be set from the command line of a scratch build (-DSMALL_INNER=.. -DSMALL_LEAF_K=.. -DSMALL_SHADE_K=..); the
+// defaults are what profiles/small_fma_ab.txt measured best.
+#ifndef SMALL_INNER
+#define SMALL_INNER 6
+#endif
+#ifndef SMALL_LEAF_K
+#define SMALL_LEAF_K 16
+#endif
+#ifndef SMALL_SHADE_K
+#define SMALL_SHADE_K 40
+#endif
 template <int THREADS, int MATH, int NODES>
 __global__ void __launch_bounds__(THREADS, 5)
 k_render_small(const SmallArgsBox B)
 {
-    constexpr int SHADE_K = 40, LEAF_K = 16, INNER = 6, LEAVES = 2;
+    constexpr int SHADE_K = SMALL_SHADE_K, LEAF_K = SMALL_LEAF_K, INNER = SMALL_INNER, LEAVES = 2;
     constexpr int FM = MATH ? 2 : 0;                  // arithmetic level of the shade phase
     constexpr uint32_t WAVES = THREADS / 64;
     const RenderArgs& A = B.a[0];
@@ -187,21 +204,21 @@ k_render_small(const SmallArgsBox B)
                     uint4 ca, ha, cb, hb;
                     small_node_f32(lds_nodes + ((uint32_t)node << 2), ca, ha, cb, hb);
                     c0 = (int)ca.w; c1 = (int)cb.w;
-                    slab_hc_f32(ca, ha, rinv, gro, rtmin, n0, f0);
-                    slab_hc_f32(cb, hb, rinv, gro, rtmin, n1, f1);
+                    slab_hcf_f32(ca, ha, rinv, gro, rtmin, n0, f0);
+                    slab_hcf_f32(cb, hb, rinv, gro, rtmin, n1, f1);
                 } else if constexpr (NODES == kSmallNodesHalfGlobal) {
                     // as variant 7 reads them; min(c >> 1, c) is small_ref_local(c) for every word a node holds: ~slot stays, a byte offset is halved
                     const uint4* np = (const uint4*)((const char*)sc.hcnodes + (size_t)((uint32_t)node << 1));
                     const uint4 qa = np[0], qb = np[1];
                     c0 = min((int)qa.w >> 1, (int)qa.w); c1 = min((int)qb.w >> 1, (int)qb.w);
-                    slab_hc(qa.x, qa.y, qa.z, rinv, gro, rtmin, n0, f0);
-                    slab_hc(qb.x, qb.y, qb.z, rinv, gro, rtmin, n1, f1);
+                    slab_hcf(qa.x, qa.y, qa.z, rinv, gro, rtmin, n0, f0);
+                    slab_hcf(qb.x, qb.y, qb.z, rinv, gro, rtmin, n1, f1);
                 } else {
                     uint4 qa, qb;
                     small_node(lds_nodes + ((uint32_t)node << 1), qa, qb);
                     c0 = (int)qa.w; c1 = (int)qb.w;
-                    slab_hc(qa.x, qa.y, qa.z, rinv, gro, rtmin, n0, f0);
-                    slab_hc(qb.x, qb.y, qb.z, rinv, gro, rtmin, n1, f1);
+                    slab_hcf(qa.x, qa.y, qa.z, rinv, gro, rtmin, n0, f0);
+                    slab_hcf(qb.x, qb.y, qb.z, rinv, gro, rtmin, n1, f1);
                 }
                 f0 = fminf(f0, best_t * kTieWiden);
                 f1 = fminf(f1, best_t * kTieWiden);

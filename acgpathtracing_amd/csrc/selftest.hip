@@ -6,6 +6,7 @@
 #include "pt_device.h"
 #include "pt_shading.h"
 #include "selftest.h"
+#include "small_slab.h"
 
 namespace ptd {
 
@@ -141,6 +142,26 @@ __global__ void k_selftest(int op, const uint32_t* __restrict__ in, uint32_t n, 
         setup_ray_hc(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), hs, mul, add);
         float tn, tf;
         slab_hc(px, py, pz, mul, add, 0.01f, tn, tf);
+        out[3 * i] = tn <= fminf(tf, r[18]) ? 1u : 0u; fout[3 * i + 1] = tn; fout[3 * i + 2] = tf;
+        return;
+    }
+    if (op == 42 || op == 43) {
+        // op 41's records through the small-scene kernel's box test (small_slab.h): 42 on the packed fp16 words (slab_hcf), 43 on the two
+        // float records small_stage_f32 makes of them (slab_hcf_f32)
+        const float* r = fin + 19 * i;
+        HSpace hs; hs.cx = r[12]; hs.cy = r[13]; hs.cz = r[14]; hs.inv_scale = r[15]; hs.isx = r[15]; hs.isy = r[16]; hs.isz = r[17]; hs.pad_ = 0.0f;
+        const uint32_t px = pack_centre_half(r[6], r[9], hs.cx, 1.0f / hs.isx), py = pack_centre_half(r[7], r[10], hs.cy, 1.0f / hs.isy), pz = pack_centre_half(r[8], r[11], hs.cz, 1.0f / hs.isz);
+        f3 mul, add;
+        setup_ray_hc(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), hs, mul, add);
+        float tn, tf;
+        if (op == 42) {
+            slab_hcf(px, py, pz, mul, add, 0.01f, tn, tf);
+        } else {
+            const half2_t hx = __builtin_bit_cast(half2_t, px), hy = __builtin_bit_cast(half2_t, py), hz = __builtin_bit_cast(half2_t, pz);
+            const uint4 cc = make_uint4(__float_as_uint((float)hx.x), __float_as_uint((float)hy.x), __float_as_uint((float)hz.x), 0u);
+            const uint4 hh = make_uint4(__float_as_uint((float)hx.y), __float_as_uint((float)hy.y), __float_as_uint((float)hz.y), 0u);
+            slab_hcf_f32(cc, hh, mul, add, 0.01f, tn, tf);
+        }
         out[3 * i] = tn <= fminf(tf, r[18]) ? 1u : 0u; fout[3 * i + 1] = tn; fout[3 * i + 2] = tf;
         return;
     }
