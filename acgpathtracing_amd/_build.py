@@ -16,7 +16,7 @@ HOST = os.path.join(PKG, "host")
 
 HIP_SOURCES = ["capi.hip", "capi_image.hip", "capi_query.hip", "capi_test.hip", "lbvh_build.hip", "wide_bvh.hip", "render_megakernel.hip", "selftest.hip", "denoise.hip", "temporal.hip", "refit.hip", "materials.hip", "environment.hip", "microfacet.hip", "display.hip", "convergence.hip", "firefly.hip", "bloom.hip", "query.hip", "ao.hip", "nearest.hip", "multihit.hip", "overlap.hip", "sweep.hip", "render_small.hip", "tritri.hip", "segment.hip", "nearest_k.hip", "winding.hip", "tridist.hip", "lists.hip", "poses.hip", "tricast.hip", "oriented.hip", "capsule.hip", "boxcast.hip"]
 EXPERIMENT_SOURCES = ["render_wavefront.hip"]      # kernels that were measured and lost: libacgpt_hip_exp.so only
-HIP_HEADERS = ["pt_device.h", "pt_shading.h", "lbvh_build.h", "render_megakernel.h", "render_common.h", "render_pw.inc", "render_experiments.inc", "lbvh_experiments.inc", "selftest.h", "denoise.h", "temporal.h", "refit.h", "materials.h", "environment.h", "pt_environment.h", "pt_microfacet.h", "display.h", "convergence.h", "firefly.h", "bloom.h", "image_common.h", "context.h", "traverse_hc.h", "query.h", "ao.h", "nearest.h", "multihit.h", "overlap.h", "sweep.h", "render_small.h", "render_small.inc", "small_ref.h", "small_slab.h", "tritri.h", "segment.h", "nearest_k.h", "winding.h", "segment_device.h", "tridist.h", "lists.h", "overlap_device.h", "tritri_device.h", "query_launch.h", "bvh_walk.h", "closest_point.h", "tridist_device.h", "poses.h", "tricast.h", "tricast_device.h", "oriented.h", "oriented_device.h", "capsule.h", "sweep_device.h", "boxcast.h", "boxcast_device.h"]
+HIP_HEADERS = ["pt_device.h", "pt_shading.h", "lbvh_build.h", "render_megakernel.h", "render_common.h", "render_pw.inc", "render_experiments.inc", "lbvh_experiments.inc", "selftest.h", "denoise.h", "temporal.h", "refit.h", "materials.h", "environment.h", "pt_environment.h", "pt_microfacet.h", "display.h", "convergence.h", "firefly.h", "bloom.h", "image_common.h", "context.h", "traverse_hc.h", "query.h", "ao.h", "nearest.h", "multihit.h", "overlap.h", "sweep.h", "render_small.h", "render_small.inc", "small_ref.h", "small_slab.h", "tritri.h", "segment.h", "nearest_k.h", "winding.h", "segment_device.h", "tridist.h", "lists.h", "overlap_device.h", "tritri_device.h", "query_launch.h", "bvh_walk.h", "cast_walk.h", "closest_point.h", "tridist_device.h", "poses.h", "tricast.h", "tricast_device.h", "oriented.h", "oriented_device.h", "capsule.h", "sweep_device.h", "boxcast.h", "boxcast_device.h"]
 HOST_SOURCES = ["host_capi.cpp", "TinyObjWrapper.cpp", "Camera.cpp", "Trackball.cpp", "ImageIO.cpp"]
 
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-fvisibility=hidden", "-std=c++17"]

@@ -59,7 +59,7 @@ constexpr bool kBoxCastAxes = true;
 
 // fmt: 11 = fp16 centre / half-extent nodes (sc.hcnodes), 0 = fp32 nodes (sc.nodes).  casts: n records of five float4 {m0 m1 m2 m3 |
 // m4 m5 m6 m7 | m8 m9 m10 m11 | hx hy hz - | d.xyz tmax}; out: n records of three float4 (pt_box_cast_hit).  Both DEVICE, 16-byte
-// aligned, 1 <= n <= 2^31 - 1.  scene_scale: sweep_scene_scale of the scene.
+// aligned, 1 <= n <= 2^31 - 1.  scene_scale: scene_max_abs (query_launch.h) of the scene box.
 hipError_t launch_query_box_toi(int fmt, const DeviceScene& sc, uint32_t stack_entries, float scene_scale, const float4* casts, uint32_t n, float4* out,
                                 hipStream_t stream);
 // blocked: n bytes, 1 where some triangle has a time of impact within [0, tmax]; a lane leaves the walk at its first such triangle.

@@ -1,6 +1,7 @@
 // bvh_walk.h — the one stack walk of the query kernels over the scene's two-child BVH.  nearest.hip,
-// nearest_k.hip, segment.hip, tridist.hip, sweep.hip, multihit.hip, overlap.hip, tritri.hip and lists.hip walk through it; the render
-// kernels (pt_device.h, traverse_hc.h) and winding.hip, which walks its own node record, keep their loops.
+// nearest_k.hip, segment.hip, tridist.hip, multihit.hip, overlap.hip, oriented.hip, tritri.hip, lists.hip and poses.hip walk through
+// it with policies of their own, and the casts (sweep.hip, capsule.hip, boxcast.hip, tricast.hip) with the one policy of cast_walk.h;
+// the render kernels (pt_device.h, traverse_hc.h) and winding.hip, which walks its own node record, keep their loops.
 //
 // What the walk guarantees, whatever the policy:
 //   * One query per lane.  An inactive lane (a lane past n, a query that is a miss before any traversal) and every lane of an empty

@@ -40,6 +40,7 @@
 #include "overlap.h"
 #include "poses.h"
 #include "query.h"
+#include "query_launch.h"
 #include "segment.h"
 #include "tridist.h"
 #include "sweep.h"
@@ -162,8 +163,7 @@ static int run_query(pt_ctx* c, const char* fn, bool product, Launch launch)
 static float nearest_abs_term(pt_ctx* c) { return ptd::nearest_abs_term(c->bvh.scene_lo, c->bvh.scene_hi); }
 static float overlap_scene_term(pt_ctx* c) { return ptd::overlap_scene_term(c->bvh.scene_lo, c->bvh.scene_hi); }
 static float oriented_term(pt_ctx* c) { return ptd::oriented_scene_term(c->bvh.scene_lo, c->bvh.scene_hi); }
-static float sweep_scene_scale(pt_ctx* c) { return ptd::sweep_scene_scale(c->bvh.scene_lo, c->bvh.scene_hi); }
-static float cast_scene_scale(pt_ctx* c) { return ptd::cast_scene_scale(c->bvh.scene_lo, c->bvh.scene_hi); }
+static float query_scene_scale(pt_ctx* c) { return ptd::scene_max_abs(c->bvh.scene_lo, c->bvh.scene_hi); }      // S of sweep.h, capsule.h, boxcast.h, tricast.h
 
 // ---- rays -------------------------------------------------------------------------------------------------------------------------
 PT_API int pt_query_closest(pt_ctx* c, const float* rays, size_t n, pt_hit* hits)
@@ -698,7 +698,7 @@ PT_API int pt_query_sweep(pt_ctx* c, const float* sweeps, size_t n, pt_sweep_hit
     int fmt = 0;
     if (int rc = records_prepare(c, "pt_query_sweep", kSweeps, sweeps, n, hits, sizeof(pt_sweep_hit), 15u, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
     return run_query(c, "pt_query_sweep", true, [&] {
-        return ptd::launch_query_sweep(fmt, device_scene(c), c->stack_entries, sweep_scene_scale(c), (const float4*)sweeps, (uint32_t)n, (float4*)hits, c->stream);
+        return ptd::launch_query_sweep(fmt, device_scene(c), c->stack_entries, query_scene_scale(c), (const float4*)sweeps, (uint32_t)n, (float4*)hits, c->stream);
     });
 }
 
@@ -707,7 +707,7 @@ PT_API int pt_query_sweep_any(pt_ctx* c, const float* sweeps, size_t n, uint8_t*
     int fmt = 0;
     if (int rc = records_prepare(c, "pt_query_sweep_any", kSweeps, sweeps, n, blocked, 1u, 0u, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
     return run_query(c, "pt_query_sweep_any", true, [&] {
-        return ptd::launch_query_sweep_any(fmt, device_scene(c), c->stack_entries, sweep_scene_scale(c), (const float4*)sweeps, (uint32_t)n, blocked, c->stream);
+        return ptd::launch_query_sweep_any(fmt, device_scene(c), c->stack_entries, query_scene_scale(c), (const float4*)sweeps, (uint32_t)n, blocked, c->stream);
     });
 }
 
@@ -716,7 +716,7 @@ PT_API int pt_debug_sweep_visits(pt_ctx* c, const float* sweeps, size_t n, pt_sw
     int fmt = 0;
     if (int rc = records_prepare(c, "pt_debug_sweep_visits", kSweeps, sweeps, n, hits, sizeof(pt_sweep_hit), 15u, visits, true, &fmt)) return rc < 0 ? 0 : rc;
     return run_query(c, "pt_debug_sweep_visits", false, [&] {
-        return ptd::launch_sweep_visits(fmt, device_scene(c), c->stack_entries, sweep_scene_scale(c), (const float4*)sweeps, (uint32_t)n, (float4*)hits, (uint2*)visits, c->stream);
+        return ptd::launch_sweep_visits(fmt, device_scene(c), c->stack_entries, query_scene_scale(c), (const float4*)sweeps, (uint32_t)n, (float4*)hits, (uint2*)visits, c->stream);
     });
 }
 
@@ -727,7 +727,7 @@ PT_API int pt_query_capsule_cast(pt_ctx* c, const float* casts, size_t n, pt_cap
     int fmt = 0;
     if (int rc = records_prepare(c, "pt_query_capsule_cast", kCapsuleCasts, casts, n, hits, sizeof(pt_capsule_cast_hit), 15u, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
     return run_query(c, "pt_query_capsule_cast", true, [&] {
-        return ptd::launch_query_capsule_cast(fmt, device_scene(c), c->stack_entries, sweep_scene_scale(c), (const float4*)casts, (uint32_t)n, (float4*)hits, c->stream);
+        return ptd::launch_query_capsule_cast(fmt, device_scene(c), c->stack_entries, query_scene_scale(c), (const float4*)casts, (uint32_t)n, (float4*)hits, c->stream);
     });
 }
 
@@ -736,7 +736,7 @@ PT_API int pt_query_capsule_cast_any(pt_ctx* c, const float* casts, size_t n, ui
     int fmt = 0;
     if (int rc = records_prepare(c, "pt_query_capsule_cast_any", kCapsuleCasts, casts, n, blocked, 1u, 0u, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
     return run_query(c, "pt_query_capsule_cast_any", true, [&] {
-        return ptd::launch_query_capsule_cast_any(fmt, device_scene(c), c->stack_entries, sweep_scene_scale(c), (const float4*)casts, (uint32_t)n, blocked, c->stream);
+        return ptd::launch_query_capsule_cast_any(fmt, device_scene(c), c->stack_entries, query_scene_scale(c), (const float4*)casts, (uint32_t)n, blocked, c->stream);
     });
 }
 
@@ -746,7 +746,7 @@ PT_API int pt_debug_capsule_cast_visits(pt_ctx* c, const float* casts, size_t n,
     int fmt = 0;
     if (int rc = records_prepare(c, "pt_debug_capsule_cast_visits", kCapsuleCasts, casts, n, hits, sizeof(pt_capsule_cast_hit), 15u, visits, true, &fmt)) return rc < 0 ? 0 : rc;
     return run_query(c, "pt_debug_capsule_cast_visits", false, [&] {
-        return ptd::launch_capsule_cast_visits(fmt, device_scene(c), c->stack_entries, sweep_scene_scale(c), (const float4*)casts, (uint32_t)n, (float4*)hits, (uint2*)visits,
+        return ptd::launch_capsule_cast_visits(fmt, device_scene(c), c->stack_entries, query_scene_scale(c), (const float4*)casts, (uint32_t)n, (float4*)hits, (uint2*)visits,
                                                mode == 0u && ptd::kCapsulePlane, c->stream);
     });
 }
@@ -758,7 +758,7 @@ PT_API int pt_query_box_cast(pt_ctx* c, const float* casts, size_t n, pt_box_cas
     int fmt = 0;
     if (int rc = records_prepare(c, "pt_query_box_cast", kBoxCasts, casts, n, hits, sizeof(pt_box_cast_hit), 15u, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
     return run_query(c, "pt_query_box_cast", true, [&] {
-        return ptd::launch_query_box_toi(fmt, device_scene(c), c->stack_entries, sweep_scene_scale(c), (const float4*)casts, (uint32_t)n, (float4*)hits, c->stream);
+        return ptd::launch_query_box_toi(fmt, device_scene(c), c->stack_entries, query_scene_scale(c), (const float4*)casts, (uint32_t)n, (float4*)hits, c->stream);
     });
 }
 
@@ -767,7 +767,7 @@ PT_API int pt_query_box_cast_any(pt_ctx* c, const float* casts, size_t n, uint8_
     int fmt = 0;
     if (int rc = records_prepare(c, "pt_query_box_cast_any", kBoxCasts, casts, n, blocked, 1u, 0u, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
     return run_query(c, "pt_query_box_cast_any", true, [&] {
-        return ptd::launch_query_box_toi_any(fmt, device_scene(c), c->stack_entries, sweep_scene_scale(c), (const float4*)casts, (uint32_t)n, blocked, c->stream);
+        return ptd::launch_query_box_toi_any(fmt, device_scene(c), c->stack_entries, query_scene_scale(c), (const float4*)casts, (uint32_t)n, blocked, c->stream);
     });
 }
 
@@ -777,7 +777,7 @@ PT_API int pt_debug_box_cast_visits(pt_ctx* c, const float* casts, size_t n, pt_
     int fmt = 0;
     if (int rc = records_prepare(c, "pt_debug_box_cast_visits", kBoxCasts, casts, n, hits, sizeof(pt_box_cast_hit), 15u, visits, true, &fmt)) return rc < 0 ? 0 : rc;
     return run_query(c, "pt_debug_box_cast_visits", false, [&] {
-        return ptd::launch_box_toi_visits(fmt, device_scene(c), c->stack_entries, sweep_scene_scale(c), (const float4*)casts, (uint32_t)n, (float4*)hits, (uint2*)visits, mode == 0u,
+        return ptd::launch_box_toi_visits(fmt, device_scene(c), c->stack_entries, query_scene_scale(c), (const float4*)casts, (uint32_t)n, (float4*)hits, (uint2*)visits, mode == 0u,
                                           c->stream);
     });
 }
@@ -789,7 +789,7 @@ PT_API int pt_query_triangle_cast(pt_ctx* c, const float* casts, size_t n, pt_tr
     int fmt = 0;
     if (int rc = records_prepare(c, "pt_query_triangle_cast", kTriangleCasts, casts, n, hits, sizeof(pt_triangle_cast_hit), 15u, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
     return run_query(c, "pt_query_triangle_cast", true, [&] {
-        return ptd::launch_query_triangle_cast(fmt, device_scene(c), c->stack_entries, cast_scene_scale(c), (const float4*)casts, (uint32_t)n, (float4*)hits, c->stream);
+        return ptd::launch_query_triangle_cast(fmt, device_scene(c), c->stack_entries, query_scene_scale(c), (const float4*)casts, (uint32_t)n, (float4*)hits, c->stream);
     });
 }
 
@@ -798,7 +798,7 @@ PT_API int pt_query_triangle_cast_any(pt_ctx* c, const float* casts, size_t n, u
     int fmt = 0;
     if (int rc = records_prepare(c, "pt_query_triangle_cast_any", kTriangleCasts, casts, n, blocked, 1u, 0u, nullptr, false, &fmt)) return rc < 0 ? 0 : rc;
     return run_query(c, "pt_query_triangle_cast_any", true, [&] {
-        return ptd::launch_query_triangle_cast_any(fmt, device_scene(c), c->stack_entries, cast_scene_scale(c), (const float4*)casts, (uint32_t)n, blocked, c->stream);
+        return ptd::launch_query_triangle_cast_any(fmt, device_scene(c), c->stack_entries, query_scene_scale(c), (const float4*)casts, (uint32_t)n, blocked, c->stream);
     });
 }
 
@@ -807,7 +807,7 @@ PT_API int pt_debug_triangle_cast_visits(pt_ctx* c, const float* casts, size_t n
     int fmt = 0;
     if (int rc = records_prepare(c, "pt_debug_triangle_cast_visits", kTriangleCasts, casts, n, hits, sizeof(pt_triangle_cast_hit), 15u, visits, true, &fmt)) return rc < 0 ? 0 : rc;
     return run_query(c, "pt_debug_triangle_cast_visits", false, [&] {
-        return ptd::launch_triangle_cast_visits(fmt, device_scene(c), c->stack_entries, cast_scene_scale(c), (const float4*)casts, (uint32_t)n, (float4*)hits, (uint2*)visits, c->stream);
+        return ptd::launch_triangle_cast_visits(fmt, device_scene(c), c->stack_entries, query_scene_scale(c), (const float4*)casts, (uint32_t)n, (float4*)hits, (uint2*)visits, c->stream);
     });
 }
 
@@ -815,7 +815,7 @@ static int poses_cast_run(pt_ctx* c, const char* fn, const float* poses, const f
 {
     const PoseArray others[2] = {{motions, 16u, 15u, true, "the motions"}, {out, sizeof(pt_triangle_cast_hit), 15u, true, "out"}};
     return poses_run(c, fn, poses, P, others, 2, false, true, [&](int fmt) {
-        return ptd::launch_poses_cast(fmt, device_scene(c), c->stack_entries, cast_scene_scale(c), c->d_pose_mesh.p, c->pose_mesh_tris, (const float4*)poses, (const float4*)motions,
+        return ptd::launch_poses_cast(fmt, device_scene(c), c->stack_entries, query_scene_scale(c), c->d_pose_mesh.p, c->pose_mesh_tris, (const float4*)poses, (const float4*)motions,
                                       (uint32_t)P, c->d_pose_words.p, (float4*)out, flags, c->stream);
     });
 }

@@ -1,9 +1,10 @@
 // query_launch.h — what every query unit repeats around its kernel: the LDS lane stack (one declaration, its size, the calling lane's
-// LaneStack), the launch of 256-lane workgroups with that much dynamic LDS, and the scene's scale on the host.  The render kernels
-// keep their own (pt_device.h is not touched); LaneStack and kSentinel stay there.
+// LaneStack), the launch of 256-lane workgroups with that much dynamic LDS, the dispatch on the scene's node format, and the scene's
+// scale on the host.  The render kernels keep their own (pt_device.h is not touched); LaneStack and kSentinel stay there.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
+#include <type_traits>
 #include "pt_device.h"
 
 namespace ptd {
@@ -37,6 +38,20 @@ template <typename K, typename... A>
 static hipError_t launch_lane_stack(K kernel, uint32_t stack_entries, uint32_t n, hipStream_t stream, A... args)
 {
     return launch_lane_stack_blocks(kernel, stack_entries, (n + 255u) / 256u, stream, args...);
+}
+
+// The node format the scene holds (11: the fp16 centre / half-extent nodes, else 0: the fp32 nodes) as a template argument:
+// f(std::integral_constant<int, FMT>{}), so a launcher names its kernel once, as k<decltype(F)::value>.  With a bool, which goes the
+// same way: f(std::integral_constant<int, FMT>{}, std::bool_constant<B>{}).
+template <typename F>
+static hipError_t dispatch_format(int fmt, F f)
+{
+    return fmt == 11 ? f(std::integral_constant<int, 11>{}) : f(std::integral_constant<int, 0>{});
+}
+template <typename F>
+static hipError_t dispatch_format(int fmt, bool b, F f)
+{
+    return dispatch_format(fmt, [&](auto fmt_c) { return b ? f(fmt_c, std::true_type{}) : f(fmt_c, std::false_type{}); });
 }
 
 // The largest finite |coordinate| of the scene box the builder (or the last refit) recorded; 0 when there is none.  The absolute terms

@@ -33,11 +33,9 @@ constexpr float kSweepRelT = 1.0f + 0x1p-16f;
 constexpr float kSweepLinT = 0x1p-17f;
 constexpr float kSweepSqrtT = 0x1p-8f;
 
-// S of the scene box the builder (or the last refit) recorded: the largest finite |coordinate|, 0 for a scene without triangles.
-float sweep_scene_scale(const float scene_lo[3], const float scene_hi[3]);
-
 // fmt: 11 = fp16 centre / half-extent nodes (sc.hcnodes), 0 = fp32 nodes (sc.nodes).  sweeps: n records of two float4 {o.xyz, d.x |
-// d.yz, radius, tmax}; out: n records of two float4 (pt_sweep_hit).  Both DEVICE, 16-byte aligned, 1 <= n <= 2^31 - 1.
+// d.yz, radius, tmax}; out: n records of two float4 (pt_sweep_hit).  Both DEVICE, 16-byte aligned, 1 <= n <= 2^31 - 1.  scene_scale:
+// S, query_launch.h's scene_max_abs of the scene box the builder (or the last refit) recorded.
 hipError_t launch_query_sweep(int fmt, const DeviceScene& sc, uint32_t stack_entries, float scene_scale, const float4* sweeps, uint32_t n, float4* out,
                               hipStream_t stream);
 // blocked: n bytes, 1 where some triangle has a time of impact within [0, tmax]; a lane leaves the walk at its first such triangle.

@@ -38,12 +38,9 @@ constexpr float kCastRelT = 1.0f + 0x1p-16f;
 
 // flags of launch_poses_cast (acgpt_test.h pt_debug_query_poses_cast; the product passes 0): poses.h kPoseNoEarly, kPosePoseMajor
 
-// S of the scene box the builder (or the last refit) recorded: the largest finite |coordinate|, 0 for a scene without triangles.
-float cast_scene_scale(const float scene_lo[3], const float scene_hi[3]);
-
 // fmt: 11 = fp16 centre / half-extent nodes (sc.hcnodes), 0 = fp32 nodes (sc.nodes).  casts: n records of four float4 {a0.xyz, tmax |
 // a1.xyz, . | a2.xyz, . | d.xyz, .}; out: n records of two float4 (pt_triangle_cast_hit).  Both DEVICE, 16-byte aligned,
-// 1 <= n <= 2^31 - 1.
+// 1 <= n <= 2^31 - 1.  scene_scale: scene_max_abs (query_launch.h) of the scene box.
 hipError_t launch_query_triangle_cast(int fmt, const DeviceScene& sc, uint32_t stack_entries, float scene_scale, const float4* casts, uint32_t n, float4* out,
                                       hipStream_t stream);
 // blocked: n bytes, 1 where some triangle has a time of impact within [0, tmax]; a lane leaves the walk at its first such triangle.

@@ -7,17 +7,15 @@
 //   k_query_triangle_cast_any<FMT>      one byte per cast; a lane leaves the walk at its first triangle with a time of impact
 //                                       within [0, tmax].
 //   k_cast_pose<FMT>                    phase 1 of the posed call, one lane per (pose, mesh triangle): the lane transforms its
-//                                       triangle in registers, walks as k_query_triangle_cast does (the same CastWalk) and fetch_mins
+//                                       triangle in registers, walks as k_query_triangle_cast does (the same walk) and fetch_mins
 //                                       (bits of t) << 32 | mesh triangle into the pose's 64-bit key.
 //   k_cast_pose_record<FMT>             phase 2, one lane per pose: the winning triangle transformed again, k_query_triangle_cast's
 //                                       own walk and epilogue for it with the full tmax, the record written with query_triangle.
 //
-// FMT 11 walks the fp16 centre / half-extent nodes, FMT 0 the fp32 nodes: the node array the scene holds.  The walk is a slab test of
-// the centre line of the query's box against each child box inflated by the box's half extent (tricast.h: by a little more), clipped
-// to [0, min(tmax, best t)] widened (tricast.h), nearer child first.  256-lane workgroups over a one-dimensional grid, the lane stack
-// of query_launch.h (stack_entries * 64 words per wave).  A cast is four 16-byte loads and a record two 16-byte stores per lane.
-// Lanes past n and lanes whose cast is a miss before any traversal stay in the wave, inactive.  The per-triangle kernels use no
-// atomics: two calls give the same bits.
+// FMT 11 walks the fp16 centre / half-extent nodes, FMT 0 the fp32 nodes: the node array the scene holds.  The walk, the any-hit
+// kernel and the record kernel's frame are cast_walk.h's; what is this unit's own (the leaf statement cast_pair, the centre line of
+// the query's box, the inflation and the cut of tricast.h) is in tricast_device.h.  A cast is four 16-byte loads and a record two
+// 16-byte stores per lane.  The per-triangle kernels use no atomics: two calls give the same bits.
 //
 // The posed kernels follow poses.hip's k_pose_distance and k_pose_record.  The transform is include/acgpt.h's statement, x' = ((m[0] x
 // + m[1] y) + m[2] z) + m[3] per row, every operation on its own, so the posed vertices are pt_pose_triangles' bits.  The per-pose keys
@@ -30,7 +28,7 @@
 // smaller tmax finds the same t.  The key orders exactly as (t, triangle) does: a candidate's t is never a NaN, never negative and
 // never -0 (the statement's + 0), so its bits order as an unsigned integer and stay below the all-ones of an empty key.
 // Built with -ffp-contract=off: the time of impact is evaluated as written, and tests/tricast_ref.py mirrors it operation for
-// operation.  The box test is outside that contract (it only prunes) and uses explicit fused multiply-adds.
+// operation.
 #include "tricast.h"
 #include "tricast_device.h"
 #include "poses.h"
@@ -42,34 +40,20 @@ __global__ void __launch_bounds__(256)
 k_query_triangle_cast(const DeviceScene sc, uint32_t stack_entries, float scene_scale, const float4* __restrict__ casts, uint32_t n, float4* __restrict__ out,
                       uint2* __restrict__ visits_out)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;      // n <= 2^31 - 1: the grid's last lane is below 2^31 + 255
-    const LaneStack st = lane_stack(stack_entries);
-    CastQuery q;
-    const bool ok = q.load(casts, i, n);
-    CastWalk<false> best(q, cast_slab_setup<FMT>(q, scene_scale, sc.hspace), q.tmax);
-    uint2 visits = make_uint2(0u, 0u);
-    bvh_walk<FMT, COUNT>(sc, st, ok, best, visits);
-    if (i >= n) return;
-    float4 o0, o1;
-    cast_record(sc, q, ok, best, 0u, o0, o1);
-    out[2ull * i] = o0;
-    out[2ull * i + 1ull] = o1;
-    if (COUNT) visits_out[i] = visits;
+    cast_record_body<FMT, COUNT, CastQuery, const CastQuery&>(sc, stack_entries, scene_scale, casts, n, visits_out,
+                                                              [&](uint32_t i, const CastQuery& q, bool found, const TriCastWalk& best) {
+        float4 o0, o1;
+        cast_record(sc, q, found, best, 0u, o0, o1);
+        out[2ull * i] = o0;
+        out[2ull * i + 1ull] = o1;
+    });
 }
 
 template <int FMT>
 __global__ void __launch_bounds__(256)
 k_query_triangle_cast_any(const DeviceScene sc, uint32_t stack_entries, float scene_scale, const float4* __restrict__ casts, uint32_t n, uint8_t* __restrict__ blocked)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const LaneStack st = lane_stack(stack_entries);
-    CastQuery q;
-    const bool ok = q.load(casts, i, n);
-    CastWalk<true> best(q, cast_slab_setup<FMT>(q, scene_scale, sc.hspace), q.tmax);
-    uint2 visits = make_uint2(0u, 0u);
-    bvh_walk<FMT, false>(sc, st, ok, best, visits);
-    if (i >= n) return;
-    blocked[i] = (ok && best.slot >= 0) ? (uint8_t)1 : (uint8_t)0;
+    cast_any_body<FMT, CastQuery, const CastQuery&>(sc, stack_entries, scene_scale, casts, n, blocked);
 }
 
 // ---- the posed call ----------------------------------------------------------------------------------------------------------------
@@ -115,7 +99,8 @@ k_cast_pose(const DeviceScene sc, uint32_t stack_entries, float scene_scale, con
             if (kt == 0.0f && (uint32_t)key < t) ok = false;                // nothing is below (0, a lower index)
         }
     }
-    CastWalk<false> best(q, cast_slab_setup<FMT>(q, scene_scale, sc.hspace), tmax);
+    q.line<FMT>(scene_scale, sc.hspace);
+    TriCastWalk best(q, tmax);
     uint2 visits = make_uint2(0u, 0u);
     bvh_walk<FMT, false>(sc, st, ok, best, visits);
     if (ok && best.slot >= 0)
@@ -136,37 +121,36 @@ k_cast_pose_record(const DeviceScene sc, uint32_t stack_entries, float scene_sca
     const uint32_t t = found ? (uint32_t)key : 0u;
     CastQuery q;
     const bool ok = cast_pose_query(q, mesh, t, poses, motions, p, found);
-    CastWalk<false> best(q, cast_slab_setup<FMT>(q, scene_scale, sc.hspace), q.tmax);
+    q.line<FMT>(scene_scale, sc.hspace);
+    TriCastWalk best(q, q.tmax);
     uint2 visits = make_uint2(0u, 0u);
     bvh_walk<FMT, false>(sc, st, ok, best, visits);
     if (i >= P) return;
     float4 o0, o1;
-    cast_record(sc, q, ok, best, ok && best.slot >= 0 ? t : 0xFFFFFFFFu, o0, o1);
+    const bool found_one = ok && best.slot >= 0;
+    cast_record(sc, q, found_one, best, found_one ? t : 0xFFFFFFFFu, o0, o1);
     out[2ull * i] = o0;
     out[2ull * i + 1ull] = o1;
 }
 
-float cast_scene_scale(const float scene_lo[3], const float scene_hi[3]) { return scene_max_abs(scene_lo, scene_hi); }
-
 hipError_t launch_query_triangle_cast(int fmt, const DeviceScene& sc, uint32_t stack_entries, float scene_scale, const float4* casts, uint32_t n, float4* out,
                                       hipStream_t stream)
 {
-    if (fmt == 11) return launch_lane_stack(k_query_triangle_cast<11, false>, stack_entries, n, stream, sc, stack_entries, scene_scale, casts, n, out, (uint2*)nullptr);
-    return launch_lane_stack(k_query_triangle_cast<0, false>, stack_entries, n, stream, sc, stack_entries, scene_scale, casts, n, out, (uint2*)nullptr);
+    return dispatch_format(fmt, [&](auto F) {
+        return launch_cast(k_query_triangle_cast<decltype(F)::value, false>, sc, stack_entries, scene_scale, casts, n, stream, out, (uint2*)nullptr);
+    });
 }
 
 hipError_t launch_query_triangle_cast_any(int fmt, const DeviceScene& sc, uint32_t stack_entries, float scene_scale, const float4* casts, uint32_t n,
                                           uint8_t* blocked, hipStream_t stream)
 {
-    if (fmt == 11) return launch_lane_stack(k_query_triangle_cast_any<11>, stack_entries, n, stream, sc, stack_entries, scene_scale, casts, n, blocked);
-    return launch_lane_stack(k_query_triangle_cast_any<0>, stack_entries, n, stream, sc, stack_entries, scene_scale, casts, n, blocked);
+    return dispatch_format(fmt, [&](auto F) { return launch_cast(k_query_triangle_cast_any<decltype(F)::value>, sc, stack_entries, scene_scale, casts, n, stream, blocked); });
 }
 
 hipError_t launch_triangle_cast_visits(int fmt, const DeviceScene& sc, uint32_t stack_entries, float scene_scale, const float4* casts, uint32_t n, float4* out,
                                        uint2* visits, hipStream_t stream)
 {
-    if (fmt == 11) return launch_lane_stack(k_query_triangle_cast<11, true>, stack_entries, n, stream, sc, stack_entries, scene_scale, casts, n, out, visits);
-    return launch_lane_stack(k_query_triangle_cast<0, true>, stack_entries, n, stream, sc, stack_entries, scene_scale, casts, n, out, visits);
+    return dispatch_format(fmt, [&](auto F) { return launch_cast(k_query_triangle_cast<decltype(F)::value, true>, sc, stack_entries, scene_scale, casts, n, stream, out, visits); });
 }
 
 hipError_t launch_poses_cast(int fmt, const DeviceScene& sc, uint32_t stack_entries, float scene_scale, const float4* mesh, uint32_t T, const float4* poses,
@@ -175,11 +159,11 @@ hipError_t launch_poses_cast(int fmt, const DeviceScene& sc, uint32_t stack_entr
     const uint32_t n = P * T;      // <= 2^31 - 1 (capi_query.hip)
     hipError_t e = hipMemsetAsync(keys, 0xFF, (size_t)P * sizeof(unsigned long long), stream);
     if (e != hipSuccess) return e;
-    if (fmt == 11) e = launch_lane_stack(k_cast_pose<11>, stack_entries, n, stream, sc, stack_entries, scene_scale, mesh, T, poses, motions, P, n, keys, flags);
-    else e = launch_lane_stack(k_cast_pose<0>, stack_entries, n, stream, sc, stack_entries, scene_scale, mesh, T, poses, motions, P, n, keys, flags);
-    if (e != hipSuccess) return e;
-    if (fmt == 11) return launch_lane_stack(k_cast_pose_record<11>, stack_entries, P, stream, sc, stack_entries, scene_scale, mesh, poses, motions, P, (const unsigned long long*)keys, out);
-    return launch_lane_stack(k_cast_pose_record<0>, stack_entries, P, stream, sc, stack_entries, scene_scale, mesh, poses, motions, P, (const unsigned long long*)keys, out);
+    return dispatch_format(fmt, [&](auto F) {
+        const hipError_t e1 = launch_lane_stack(k_cast_pose<decltype(F)::value>, stack_entries, n, stream, sc, stack_entries, scene_scale, mesh, T, poses, motions, P, n, keys, flags);
+        if (e1 != hipSuccess) return e1;
+        return launch_lane_stack(k_cast_pose_record<decltype(F)::value>, stack_entries, P, stream, sc, stack_entries, scene_scale, mesh, poses, motions, P, (const unsigned long long*)keys, out);
+    });
 }
 
 }  // namespace ptd

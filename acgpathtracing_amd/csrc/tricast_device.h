@@ -1,22 +1,26 @@
-// tricast_device.h — the device functions of the translating-triangle casts (tricast.hip): the query record CastQuery, the time of
-// impact of one pair cast_pair, the slab test of the query box's centre line and the walk's policy CastWalk.  The start-overlap test
-// is tritri_device.h's tri_tri_intersect.  Include only from a unit built with -ffp-contract=off (the statement is evaluated as
-// written, and tests/tricast_ref.py mirrors it operation for operation).  The slab test is outside that contract (it only prunes) and
-// uses explicit fused multiply-adds.
+// tricast_device.h — the device functions of the translating-triangle casts (tricast.hip): the query record CastQuery, which is
+// cast_walk.h's per-query struct, the time of impact of one pair cast_pair and the record of a finished walk.  The walk is
+// cast_walk.h's; this unit's own are the leaf statement cast_pair, the centre line of the query's box with each child box inflated by
+// the box's half extent (tricast.h: by a little more), the cut of tricast.h, and no extra admission test.  The start-overlap test is
+// tritri_device.h's tri_tri_intersect.  Include only from a unit built with -ffp-contract=off (the statement is evaluated as written,
+// and tests/tricast_ref.py mirrors it operation for operation).
 #pragma once
 #include "tricast.h"
-#include "bvh_walk.h"
+#include "cast_walk.h"
 #include "tritri_device.h"
-
-#include <cfloat>
 
 namespace ptd {
 
 // What a lane keeps of its cast.  set() returns whether the cast can touch something: every coordinate of the triangle, of d and of
 // the three edge vectors finite, tmax >= 0 and no NaN (include/acgpt.h: "a miss before any traversal"); a cast that cannot is zeroed.
+// line() then fills the slab test's view of it (tricast.h): the centre line of the query's box and the inflation per axis.
 struct CastQuery {
+    static constexpr bool kAdmits = false, kTracksCut = false;
     f3 a0, a1, a2, d;
     float tmax;         // +inf is the largest finite t: a time of impact of +inf stands for "no candidate"
+    f3 inv;             // finite 1-ulp reciprocals of d
+    f3 qc;              // cq, the centre of the query's box, minus the centre of HSpace for FMT 11
+    f3 infl;            // hq + R
     __device__ __forceinline__ bool set(const f3& a0_, const f3& a1_, const f3& a2_, const f3& d_, float tmax_, bool have)
     {
         const f3 f1 = a1_ - a0_, f2 = a2_ - a0_, g = a2_ - a1_;
@@ -29,14 +33,32 @@ struct CastQuery {
         tmax = ok ? fminf(tmax_, FLT_MAX) : 0.0f;
         return ok;
     }
+    template <int FMT>
+    __device__ __forceinline__ void line(float scene_scale, const HSpace& hs)
+    {
+        const f3 lo = mk(fmin3(a0.x, a1.x, a2.x), fmin3(a0.y, a1.y, a2.y), fmin3(a0.z, a1.z, a2.z));
+        const f3 hi = mk(fmax3(a0.x, a1.x, a2.x), fmax3(a0.y, a1.y, a2.y), fmax3(a0.z, a1.z, a2.z));
+        const f3 cq = mk(0.5f * lo.x + 0.5f * hi.x, 0.5f * lo.y + 0.5f * hi.y, 0.5f * lo.z + 0.5f * hi.z);
+        const float big = scene_scale + fmax3(fmaxf(fabsf(lo.x), fabsf(hi.x)), fmaxf(fabsf(lo.y), fabsf(hi.y)), fmaxf(fabsf(lo.z), fabsf(hi.z)));
+        const float R = big * kCastBoxAbs;
+        inv = mk(finite_rcp(d.x), finite_rcp(d.y), finite_rcp(d.z));
+        infl = mk(fmaxf(hi.x - cq.x, cq.x - lo.x) + R, fmaxf(hi.y - cq.y, cq.y - lo.y) + R, fmaxf(hi.z - cq.z, cq.z - lo.z) + R);
+        qc = FMT == 11 ? mk(cq.x - hs.cx, cq.y - hs.cy, cq.z - hs.cz) : cq;
+    }
     // cast i of the array, or an inert one for a lane past n.  The eighth, twelfth and sixteenth float are loaded with their float4
     // and never used.
-    __device__ __forceinline__ bool load(const float4* __restrict__ casts, uint32_t i, uint32_t n)
+    template <int FMT>
+    __device__ __forceinline__ bool load(const float4* __restrict__ casts, uint32_t i, uint32_t n, float scene_scale, const HSpace& hs)
     {
         float4 g0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g1 = g0, g2 = g0, g3 = g0;
         if (i < n) { g0 = casts[4ull * i]; g1 = casts[4ull * i + 1ull]; g2 = casts[4ull * i + 2ull]; g3 = casts[4ull * i + 3ull]; }
-        return set(mk(g0.x, g0.y, g0.z), mk(g1.x, g1.y, g1.z), mk(g2.x, g2.y, g2.z), mk(g3.x, g3.y, g3.z), g0.w, i < n);
+        const bool ok = set(mk(g0.x, g0.y, g0.z), mk(g1.x, g1.y, g1.z), mk(g2.x, g2.y, g2.z), mk(g3.x, g3.y, g3.z), g0.w, i < n);
+        line<FMT>(scene_scale, hs);
+        return ok;
     }
+    // cut of tricast.h for tb = min(tmax, best t); at most FLT_MAX, so that a box the line never reaches (entry +inf) is not entered
+    __device__ __forceinline__ float cut(float tb) const { return fminf(tb * kCastRelT, FLT_MAX); }
+    __device__ __forceinline__ float toi(const float4& r0, const float4& r1, const float4& r2) const;      // cast_pair<false>'s t
 };
 
 struct CastPair { float t, feature; f3 c; };
@@ -152,106 +174,22 @@ __device__ __forceinline__ CastPair cast_pair(const CastQuery& q, const f3& v0, 
     return best;
 }
 
-// The slab test's view of the cast (tricast.h): the query box's centre line and the inflation per axis.
-struct CastSlab {
-    f3 inv;             // finite 1-ulp reciprocals of d
-    f3 o;               // cq (FMT 0), cq - centre of HSpace (FMT 11)
-    f3 infl;            // hq + R
-};
-
-template <int FMT>
-__device__ __forceinline__ CastSlab cast_slab_setup(const CastQuery& q, float scene_scale, const HSpace& hs)
+__device__ __forceinline__ float CastQuery::toi(const float4& r0, const float4& r1, const float4& r2) const
 {
-    const f3 lo = mk(fmin3(q.a0.x, q.a1.x, q.a2.x), fmin3(q.a0.y, q.a1.y, q.a2.y), fmin3(q.a0.z, q.a1.z, q.a2.z));
-    const f3 hi = mk(fmax3(q.a0.x, q.a1.x, q.a2.x), fmax3(q.a0.y, q.a1.y, q.a2.y), fmax3(q.a0.z, q.a1.z, q.a2.z));
-    const f3 cq = mk(0.5f * lo.x + 0.5f * hi.x, 0.5f * lo.y + 0.5f * hi.y, 0.5f * lo.z + 0.5f * hi.z);
-    const float big = scene_scale + fmax3(fmaxf(fabsf(lo.x), fabsf(hi.x)), fmaxf(fabsf(lo.y), fabsf(hi.y)), fmaxf(fabsf(lo.z), fabsf(hi.z)));
-    const float R = big * kCastBoxAbs;
-    CastSlab s;
-    s.inv = mk(finite_rcp(q.d.x), finite_rcp(q.d.y), finite_rcp(q.d.z));
-    s.infl = mk(fmaxf(hi.x - cq.x, cq.x - lo.x) + R, fmaxf(hi.y - cq.y, cq.y - lo.y) + R, fmaxf(hi.z - cq.z, cq.z - lo.z) + R);
-    s.o = FMT == 11 ? mk(cq.x - hs.cx, cq.y - hs.cy, cq.z - hs.cz) : cq;
-    return s;
+    return cast_pair<false>(*this, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x)).t;
 }
 
-// Entry and exit of the centre line in one child box inflated by s.infl, clipped to [0, cut]; tn = NaN for an empty child, which no
-// compare admits (an inflated empty box would be hit).  c: the box centre minus cq, e: the inflated half extent, per axis, in world
-// units; the products with +-1e30 for a zero direction component give +-inf or 0, never a NaN.
-__device__ __forceinline__ void cast_slab(const f3& c, const f3& e, const f3& inv, float cut, bool empty, float& tn, float& tf)
-{
-    const float x0 = (c.x - e.x) * inv.x, x1 = (c.x + e.x) * inv.x;
-    const float y0 = (c.y - e.y) * inv.y, y1 = (c.y + e.y) * inv.y;
-    const float z0 = (c.z - e.z) * inv.z, z1 = (c.z + e.z) * inv.z;
-    tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), 0.0f));
-    tf = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), cut));
-    if (empty) tn = __builtin_nanf("");
-}
-__device__ __forceinline__ void cast_slab_hc(uint32_t px, uint32_t py, uint32_t pz, const CastSlab& s, const HSpace& hs, float cut, float& tn, float& tf)
-{
-    // world = g * is + centre: c = centre_g * is - o, e = half_g * is + infl, one v_fma_mix_f32 each
-    const half2_t hx = __builtin_bit_cast(half2_t, px), hy = __builtin_bit_cast(half2_t, py), hz = __builtin_bit_cast(half2_t, pz);
-    const f3 c = mk(__builtin_fmaf((float)hx.x, hs.isx, -s.o.x), __builtin_fmaf((float)hy.x, hs.isy, -s.o.y), __builtin_fmaf((float)hz.x, hs.isz, -s.o.z));
-    const f3 e = mk(__builtin_fmaf((float)hx.y, hs.isx, s.infl.x), __builtin_fmaf((float)hy.y, hs.isy, s.infl.y), __builtin_fmaf((float)hz.y, hs.isz, s.infl.z));
-    cast_slab(c, e, s.inv, cut, (float)hx.y < 0.0f, tn, tf);
-}
-__device__ __forceinline__ void cast_slab_f32(float lx, float ly, float lz, float hx, float hy, float hz, const CastSlab& s, float cut, float& tn, float& tf)
-{
-    // the half extent from the rounded centre m, so that [m - e, m + e] holds [lo, hi] to an ulp of the extent
-    const f3 m = mk(0.5f * lx + 0.5f * hx, 0.5f * ly + 0.5f * hy, 0.5f * lz + 0.5f * hz);
-    const f3 c = m - s.o;
-    const f3 e = mk(fmaxf(hx - m.x, m.x - lx) + s.infl.x, fmaxf(hy - m.y, m.y - ly) + s.infl.y, fmaxf(hz - m.z, m.z - lz) + s.infl.z);
-    cast_slab(c, e, s.inv, cut, !(lx <= hx), tn, tf);
-}
-
-// cut of tricast.h for tb = min(tmax, best t); at most FLT_MAX, so that a box the line never reaches (entry +inf) is not entered
-__device__ __forceinline__ float cast_cut(float tb) { return fminf(tb * kCastRelT, FLT_MAX); }
-
-// One cast per lane through the two-child BVH (bvh_walk.h: the stack depth, the one-word entries).  The boxes only prune: the winner
-// is decided by the leaf test, t <= tmax, smallest t, ties to the lowest triangle index, whatever order the walk reaches the triangles
-// in.  tmax: the cast's own, or a smaller one that the posed kernel has seen in its pose's key.  ANY: leave at the first triangle with
-// t <= tmax (slot >= 0 says so).
-template <bool ANY>
-struct CastWalk {
-    const CastQuery& q;
-    CastSlab s;
-    float tmax, cut;
-    float t; int slot; uint32_t prim;      // the best candidate so far
-    __device__ __forceinline__ CastWalk(const CastQuery& q_, const CastSlab& s_, float tmax_) : q(q_), s(s_), tmax(tmax_), cut(cast_cut(tmax_)), t(INFINITY), slot(-1), prim(0xFFFFFFFFu) {}
-    __device__ __forceinline__ void children_hc(const uint4& qa, const uint4& qb, const HSpace& hs, bool& h0, bool& h1, bool& first0) const
-    {
-        float n0, f0, n1, f1;
-        cast_slab_hc(qa.x, qa.y, qa.z, s, hs, cut, n0, f0);
-        cast_slab_hc(qb.x, qb.y, qb.z, s, hs, cut, n1, f1);
-        admit_by_interval(n0, f0, n1, f1, h0, h1, first0);
-    }
-    __device__ __forceinline__ void children_f32(const float4& a, const float4& b, const float4& c, bool& h0, bool& h1, bool& first0) const
-    {
-        float n0, f0, n1, f1;
-        cast_slab_f32(a.x, a.y, a.z, a.w, b.x, b.y, s, cut, n0, f0);
-        cast_slab_f32(b.z, b.w, c.x, c.y, c.z, c.w, s, cut, n1, f1);
-        admit_by_interval(n0, f0, n1, f1, h0, h1, first0);
-    }
-    __device__ __forceinline__ bool leaf(int slot_, const float4& r0, const float4& r1, const float4& r2)
-    {
-        const float t_ = cast_pair<false>(q, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x)).t;
-        const uint32_t prim_ = __float_as_uint(r2.y);
-        if (ANY) {
-            if (t_ <= tmax) { slot = slot_; return true; }
-        } else if (t_ <= tmax && (t_ < t || (t_ == t && prim_ < prim))) {
-            t = t_; slot = slot_; prim = prim_;
-            cut = cast_cut(t_);
-        }
-        return false;
-    }
-};
+// The walk of the per-triangle and the posed kernels.  tmax: the cast's own, or a smaller one that the posed kernel has seen in its
+// pose's key.  The query is held by reference.
+using TriCastWalk = CastWalk<false, const CastQuery&>;
 
 // The record of a finished walk: the pair statement once more on the winner (the same statement on the same inputs gives the same
 // bits, and the walk carries three registers for its best candidate), or the miss record.  query_triangle: the fourth word.
-__device__ __forceinline__ void cast_record(const DeviceScene& sc, const CastQuery& q, bool ok, const CastWalk<false>& best, uint32_t query_triangle, float4& o0, float4& o1)
+__device__ __forceinline__ void cast_record(const DeviceScene& sc, const CastQuery& q, bool found, const TriCastWalk& best, uint32_t query_triangle, float4& o0, float4& o1)
 {
     o0 = make_float4(-1.0f, __uint_as_float(0xFFFFFFFFu), 0.0f, __uint_as_float(query_triangle));
     o1 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
-    if (ok && best.slot >= 0) {
+    if (found) {
         const TriRecord* tp = sc.tris + best.slot;
         const float4 r0 = tp->r0, r1 = tp->r1, r2 = tp->r2;
         const CastPair p = cast_pair<true>(q, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x));

@@ -352,6 +352,14 @@ def test_build_lists_and_abi():
         define = "__device__ __forceinline__ " + ("void " if fn.startswith("sweep") else "") + fn + "("
         assert define in open(os.path.join(_build.CSRC, header)).read(), fn
         assert define not in open(os.path.join(_build.CSRC, unit)).read(), fn
+    # and the walk of the four cast families in cast_walk.h, once: the line slab, the child decode, the tie rule, the any-hit body
+    assert "cast_walk.h" in _build.HIP_HEADERS and "cast_walk.h" not in _build.KERNEL_SOURCES
+    walk = open(os.path.join(_build.CSRC, "cast_walk.h")).read()
+    for text in ("__device__ __forceinline__ void cast_line_slab(", "__device__ __forceinline__ CastChild cast_child_hc(", "__device__ __forceinline__ CastChild cast_child_f32(",
+                 "t_ == t && prim_ < prim", "fminf(x0, x1)", "(float)hx.y < 0.0f", "blocked[i] ="):
+        assert walk.count(text) == 1, text
+        for unit in ("sweep.hip", "capsule.hip", "boxcast.hip", "tricast_device.h", "tricast.hip"):
+            assert text not in open(os.path.join(_build.CSRC, unit)).read(), (unit, text)
 
 
 def test_symbols_are_exported_and_bound(built):
