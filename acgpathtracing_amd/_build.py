@@ -87,7 +87,7 @@ def build_main(force=False, verbose=False):
     if not os.path.exists(src):
         return None
     out = os.path.join(PKG, "acgpt_main")
-    srcs = [src] + [os.path.join(HOST, s) for s in ("TinyObjWrapper.cpp", "Camera.cpp", "Trackball.cpp", "ImageIO.cpp")]
+    srcs = [src] + [os.path.join(HOST, s) for s in ("QueryCommands.cpp", "TinyObjWrapper.cpp", "Camera.cpp", "Trackball.cpp", "ImageIO.cpp")]
     deps = srcs + [os.path.join(HOST, h) for h in os.listdir(HOST) if h.endswith(".h")] + [os.path.join(ROOT, "include", "acgpt.h")]
     if force or _stale(out, deps):
         cmd = ["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-o", out] + srcs + \
